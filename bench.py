@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpix/s denoised (fwd+bwd) at K=30, M=64, P=7 (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" is one complete pass of the hot path over one batch: the reference's training step
@@ -67,7 +67,12 @@ def parse():
                     help="how the fused sweeps store the codes that never leave them: fp32 pixel-blocked (default, "
                          "bit-identical to the reference layout), bf16 pixel-blocked (opt-in: half the fat bytes, "
                          "PSNR parity only), or fp32 in the reference's NCHW layout")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step produced as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(n, argv):
@@ -218,6 +223,25 @@ def pmc_traffic(kernel_label, batch, size, M, P, layout):
     return None, None
 
 
+def dump_outputs(out_dir, net, loss, sigma):
+    """What a caller of the timed step receives from its last call: the returned loss and noise level, and the
+    parameters and (clipped) gradients the step leaves on the net -- float32, a few MB at the headline shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss, "sigma": torch.as_tensor(sigma)}
+    for n, p in net.named_parameters():
+        arrays[f"param.{n}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        total += a.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    note(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
 def cpu_baseline(sd, x, y, sigma, K, P, reps=2):
     """The CPU oracle (PyTorch restatement of the reference, kind='port') timed on this host's cores
     on a bounded sample of the same workload: fwd+bwd of `x.shape[0]` images."""
@@ -301,9 +325,7 @@ def run_rank(args):
     dgen = torch.Generator(device=dev).manual_seed(99 + rank)
 
     def step():
-        loss, _ = cva.train_step(net, opt, x, 25, clip_grad=5e-2, project=True,
-                                 generator=dgen)
-        return loss
+        return cva.train_step(net, opt, x, 25, clip_grad=5e-2, project=True, generator=dgen)
 
     def barrier():
         torch.cuda.synchronize()
@@ -318,7 +340,7 @@ def run_rank(args):
     note("timing")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, sigma = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -327,6 +349,8 @@ def run_rank(args):
         elapsed = float(t)
     ms_per_step = elapsed * 1e3 / args.steps
     note(f"{ms_per_step:.1f} ms/step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, loss, sigma)
     pix_per_step = world * B * S * S
     value = pix_per_step / (ms_per_step * 1e-3) / 1e6
 

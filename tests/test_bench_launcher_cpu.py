@@ -136,3 +136,31 @@ def test_backward_end_hook_runs_once_per_pass_after_the_gradients_exist():
         remove()
     Sweep.apply(w).sum().backward()
     assert len(seen) == 2
+
+
+def test_dump_outputs_writes_the_last_step_as_float32_npy(tmp_path, monkeypatch):
+    """--dump-outputs DIR: loss, sigma, every parameter and its gradient, one float32 .npy each; --steps < 1 is refused."""
+    import numpy as np
+    import cdlnet_video_amd as cva
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "torch", torch)
+    net = cva.CDLNet(K=2, M=4, P=5, init=False)
+    for p in net.parameters():
+        p.grad = torch.full_like(p, 0.25)
+    bench.dump_outputs(str(tmp_path / "out"), net, torch.tensor(0.5), 25)
+    names = {"loss", "sigma"} | {f"{k}.{n}" for n, _ in net.named_parameters() for k in ("param", "grad")}
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + ".npy" for n in names)
+    for n, p in net.named_parameters():
+        a = np.load(tmp_path / "out" / f"param.{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, p.detach().numpy())
+        assert np.all(np.load(tmp_path / "out" / f"grad.{n}.npy") == 0.25)
+    assert float(np.load(tmp_path / "out" / "loss.npy")) == 0.5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        bench.parse()
+        raise AssertionError("--steps 0 must be refused")
+    except SystemExit as e:
+        assert e.code != 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.steps == 3 and args.dump_outputs == "d"
