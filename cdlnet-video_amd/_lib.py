@@ -91,6 +91,19 @@ SIGNATURES = {
     "cdl_fusedg_dtau_reduce": [_G, _P, _P, _P, _P, _P],
     "cdl_fusedg_forward": [_G, _I] + [_P] * 11 + [_I, _P],
     "cdl_fusedg_backward": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P],
+    # gradients with respect to the data (y, sigma): the _x forms take dyp / dtau (nullable) after the old arguments
+    "cdl_preprocess_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _IP, _P],
+    "cdl_tau_grad_x": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_tau_grad_gate_x": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_dyp_split": [_G, _P, _P, _P, _I, _I, _P],
+    "cdl_analysis_rev_ws_x": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_ista_backward_x": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P],
+    "cdl_fused2d_assemble_acc": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
+    "cdl_fused2d_dtau_reduce_x": [_G, _P, _P, _P, _P, _P, _P],
+    "cdl_fused2d_backward_x": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P],
+    "cdl_fusedg_assemble_acc": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
+    "cdl_fusedg_dtau_reduce_x": [_G, _P, _P, _P, _P, _P, _P],
+    "cdl_fusedg_backward_x": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P, _P, _P],
 }
 SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G], "cdl_fusedg_patch_floats": [_G], "cdl_fusedg_tiles": [_G],
                 "cdl_fusedg_map_words": [_G], "cdl_fused2d_frag_bytes": [_I], "cdl_fused2d_patch_floats": [_G], "cdl_fused2d_code_bytes": [_G, _I],

@@ -464,7 +464,7 @@ size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g)
 
 int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                           const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *ws,
-                          size_t ws_floats, void *stream)
+                          size_t ws_floats, void *stream, float *dtau_n)
 {
     Plan p;
     const size_t need = cdl_mfma_analysis_rev_ws_floats(g);
@@ -483,6 +483,8 @@ int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, flo
     if (rc) return rc;
     k_ana_tau_final<<<g->M, 512, 0, S(stream)>>>(dtp, c, dt0, dt1, g->N, g->M, S_);
     CDL_LAUNCH_CHECK();
+    if (dtau_n)                                                    // per-sample: the S_ tile partials of row (n, m)
+        return cdl_dtau_per_sample(dtp, g->N, g->M, S_, (size_t)g->M * S_, (size_t)S_, 1, dtau_n, stream);
     return 0;
 }
 

@@ -47,6 +47,9 @@
 #ifdef CDL_F2D_WY4
 #define CDL_WY 4
 #define cdl_fused2d_assemble cdl_fused2d_assemble_wy4
+#define cdl_fused2d_assemble_acc cdl_fused2d_assemble_acc_wy4
+#define cdl_fused2d_backward_x cdl_fused2d_backward_x_wy4
+#define cdl_fused2d_dtau_reduce_x cdl_fused2d_dtau_reduce_x_wy4
 #define cdl_fused2d_backward cdl_fused2d_backward_wy4
 #define cdl_fused2d_code_bytes cdl_fused2d_code_bytes_wy4
 #define cdl_fused2d_dtau_reduce cdl_fused2d_dtau_reduce_wy4
@@ -1010,7 +1013,7 @@ __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patc
                                                   const float *__restrict__ mask,
                                                   const float *__restrict__ sub, float alpha,
                                                   float *__restrict__ out, int N, int H, int W,
-                                                  int tilesX, int tilesY)
+                                                  int tilesX, int tilesY, float *__restrict__ acc, int acc_add)
 {
     // grid (ceil(W/256), ceil(H/ASM_ROWS), N): no runtime divisions (TW, TH are powers of two), rows coalesced
     const int X = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
@@ -1020,7 +1023,10 @@ __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patc
         const int Y = blockIdx.y * ASM_ROWS + j;
         if (Y >= H) break;
         const size_t i = ((size_t)n * H + Y) * W + X;
-        float sum = alpha * patch_sum(patches, n, Y, X, tilesX, tilesY);
+        const float raw = patch_sum(patches, n, Y, X, tilesX, tilesY);
+        if (acc) acc[i] = acc_add ? acc[i] + raw : raw;
+        if (!out) continue;
+        float sum = alpha * raw;
         if (mask) sum *= mask[i];
         if (sub) sum -= sub[i];
         out[i] = sum;
@@ -1032,7 +1038,7 @@ __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patc
 __global__ __launch_bounds__(256) void k_assemble_v4(const float *__restrict__ patches,
                                                      const float *__restrict__ mask, const float *__restrict__ sub,
                                                      float alpha, float *__restrict__ out, int N, int H, int W,
-                                                     int tilesX, int tilesY)
+                                                     int tilesX, int tilesY, float *__restrict__ accum, int acc_add)
 {
     // 4 consecutive pixels x 2 rows per thread.  The terms of a pixel are added in patch_sum's order (row above, own
     // row, row below; left neighbour, own tile, right neighbour), but the row candidates are wave-uniform branches and
@@ -1072,6 +1078,15 @@ __global__ __launch_bounds__(256) void k_assemble_v4(const float *__restrict__ p
         row(0);
         if (vy > 0) row(dy);
         const size_t i = ((size_t)n * H + Y) * W + X;
+        if (accum) {                                         // the unmasked, unscaled sum (data gradient)
+            float4 a = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            if (acc_add) {
+                const float4 o = *reinterpret_cast<const float4 *>(accum + i);
+                a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+            }
+            *reinterpret_cast<float4 *>(accum + i) = a;
+        }
+        if (!out) continue;
         float4 v = make_float4(alpha * acc[0], alpha * acc[1], alpha * acc[2], alpha * acc[3]);
         if (mask) {
             const float4 m = *reinterpret_cast<const float4 *>(mask + i);
@@ -1671,6 +1686,15 @@ int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const 
     return 0;
 }
 
+int cdl_fused2d_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
+                              float *dtau_n, void *stream)
+{
+    const int rc = cdl_fused2d_dtau_reduce(g, dtau_partial, c, dt0, dt1, stream);
+    if (rc || !dtau_n) return rc;
+    const int per_img = tiles_x(g) * tiles_y(g);             // partial rows: [n][tile][m]
+    return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
+}
+
 size_t cdl_fused2d_wgrad_workspace_floats(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
@@ -1720,23 +1744,30 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
     return 0;
 }
 
-int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
-                         float alpha, float *out, void *stream)
+int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
+                             float alpha, float *out, float *acc, int acc_add, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!patches || !out) return CDL_EINVAL;
+    if (!patches || (!out && !acc)) return CDL_EINVAL;
     if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
-        k_assemble_v4<<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g));
+        k_assemble_v4<<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
     } else if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20)) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)g->N);
-        k_assemble<4><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g));
+        k_assemble<4><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
     } else {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)g->N);
-        k_assemble<1><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g));
+        k_assemble<1><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
     }
     CDL_LAUNCH_CHECK();
     return 0;
+}
+
+int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
+                         float alpha, float *out, void *stream)
+{
+    if (!out) return CDL_EINVAL;
+    return cdl_fused2d_assemble_acc(g, patches, mask, sub, alpha, out, nullptr, 0, stream);
 }
 
 }  // extern "C"
@@ -1868,11 +1899,12 @@ static int snake_enabled() { return cdl_opts().fused_snake; }
 int cdl_fused2d_forward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                             const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                             unsigned *const *maps, float *xp, void *frags, float *patches, int precision, void *stream);
-int cdl_fused2d_backward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                             const float *const *wA, const float *const *wB, const float *const *z,
-                             const float *const *r, const unsigned *const *maps, const float *g_xp, const float *g_z,
-                             float *const *dA, float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
-                             float *patches, float *dtau_partial, float *wgrad_ws, int precision, void *stream);
+int cdl_fused2d_backward_x_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                               const float *const *wA, const float *const *wB, const float *const *z,
+                               const float *const *r, const unsigned *const *maps, const float *g_xp, const float *g_z,
+                               float *const *dA, float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
+                               float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
+                               float *dtau, void *stream);
 #endif
 
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
@@ -1917,12 +1949,13 @@ int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *
     return 0;
 }
 
-int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
                          const float *const *wA, const float *const *wB, const float *const *z,
                          const float *const *r, const unsigned *const *maps, const float *g_xp,
                          const float *g_z, float *const *dA,
                          float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
-                         float *patches, float *dtau_partial, float *wgrad_ws, int precision, void *stream)
+                         float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
+                           float *dtau, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
@@ -1935,8 +1968,8 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
     const int L = f.lin;
 #ifndef CDL_F2D_WY4
     if (L == LAY_BLK16)
-        return cdl_fused2d_backward_wy4(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
-                                        patches, dtau_partial, wgrad_ws, precision, stream);
+        return cdl_fused2d_backward_x_wy4(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
+                                          patches, dtau_partial, wgrad_ws, precision, dyp, dtau, stream);
 #endif
     // the forward's last launch ran in direction (K-1)&1: stages take that one, filter gradients the other
     const int sdir = snake_enabled() ? (((K - 1) & 1) ? CDL_TILES_REVERSED : 0) : 0;
@@ -1958,15 +1991,21 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
         const bool ride = TH == GW_TH && cdl_opts().fused_da;
         {
             TimingScope ts(1, S(stream));
-            rc = stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1,
+            rc = stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
                            sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
                            ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], wgrad_ws, stream);
         }
         if (rc) return rc;
-        rc = cdl_fused2d_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, stream);
+        rc = cdl_fused2d_dtau_reduce_x(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
+                                       dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
         if (rc) return rc;
+        if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
+            rc = cdl_fused2d_assemble_acc(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
+            if (rc) return rc;
+        }
         if (k >= 1) {
-            rc = cdl_fused2d_assemble(g, patches, mask, nullptr, -1.0f, q, stream);
+            // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
+            rc = cdl_fused2d_assemble_acc(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
             if (rc) return rc;
             {
                 TimingScope ts(2, S(stream));
@@ -1984,6 +2023,17 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
         base = duk;
     }
     return 0;
+}
+
+int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                         const float *const *wA, const float *const *wB, const float *const *z,
+                         const float *const *r, const unsigned *const *maps, const float *g_xp,
+                         const float *g_z, float *const *dA,
+                         float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
+                         float *patches, float *dtau_partial, float *wgrad_ws, int precision, void *stream)
+{
+    return cdl_fused2d_backward_x(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
+                                  patches, dtau_partial, wgrad_ws, precision, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

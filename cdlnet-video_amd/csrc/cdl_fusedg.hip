@@ -740,7 +740,8 @@ __global__ __launch_bounds__(NT) void k_stage_g(GParams p)
 template <int P>
 __global__ __launch_bounds__(256) void k_assemble_g(const float *__restrict__ patches, const float *__restrict__ mask,
                                                     const float *__restrict__ sub, float alpha, float *__restrict__ out,
-                                                    int N, int C, int D, int H, int W, int Pd, int tilesX, int tilesY)
+                                                    int N, int C, int D, int H, int W, int Pd, int tilesX, int tilesY, float *__restrict__ accum,
+                                                    int acc_add)
 {
     constexpr int HALO = P / 2, PY = TH + P - 1, PX = TW + P - 1;
     const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
@@ -764,6 +765,8 @@ __global__ __launch_bounds__(256) void k_assemble_g(const float *__restrict__ pa
             }
     }
     const size_t i = ((((size_t)n * C + c) * D + d) * H + Y) * W + X;
+    if (accum) accum[i] = acc_add ? accum[i] + sum : sum;     // the unmasked, unscaled sum (data gradient)
+    if (!out) return;
     float v = alpha * sum;
     if (mask) v *= mask[i];
     if (sub) v -= sub[i];
@@ -776,7 +779,8 @@ __global__ __launch_bounds__(256) void k_assemble_g(const float *__restrict__ pa
 template <int P>
 __global__ __launch_bounds__(256) void k_assemble_g4(const float *__restrict__ patches, const float *__restrict__ mask,
                                                      const float *__restrict__ sub, float alpha, float *__restrict__ out,
-                                                     int N, int C, int D, int H, int W, int Pd, int tilesX, int tilesY)
+                                                     int N, int C, int D, int H, int W, int Pd, int tilesX, int tilesY, float *__restrict__ accum,
+                                                     int acc_add)
 {
     constexpr int HALO = P / 2, PY = TH + P - 1, PX = TW + P - 1;
     const int X0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, Y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -815,6 +819,15 @@ __global__ __launch_bounds__(256) void k_assemble_g4(const float *__restrict__ p
         }
     }
     const size_t i = ((((size_t)n * C + c) * D + d) * H + Y) * W + X0;
+    if (accum) {                                              // the unmasked, unscaled sum (data gradient)
+        float4 a = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        if (acc_add) {
+            const float4 o = *reinterpret_cast<const float4 *>(accum + i);
+            a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+        }
+        *reinterpret_cast<float4 *>(accum + i) = a;
+    }
+    if (!out) return;
     float4 v = make_float4(alpha * acc[0], alpha * acc[1], alpha * acc[2], alpha * acc[3]);
     if (mask) {
         const float4 m = *reinterpret_cast<const float4 *>(mask + i);
@@ -1135,28 +1148,35 @@ int cdl_fusedg_stage_bwd(const cdl_geom *g, const float *thin, const float *base
     return dispatch(g, p, pl, MODE_BWD, precision, S(stream));
 }
 
-int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
-                        float *out, void *stream)
+int cdl_fusedg_assemble_acc(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
+                            float *out, float *acc, int acc_add, void *stream)
 {
     Route rt;
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
     const Plan &pl = rt.pl;
-    if (!patches || !out) return CDL_EINVAL;
-    if (rt.kind == 1) return cdl_strip_assemble(g, rt.sp, patches, mask, sub, alpha, out, S(stream));
-    if (rt.kind == 2) return cdl_stripg_assemble(g, rt.gp, patches, mask, sub, alpha, out, S(stream));
+    if (!patches || (!out && !acc)) return CDL_EINVAL;
+    if (rt.kind == 1) return cdl_strip_assemble(g, rt.sp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
+    if (rt.kind == 2) return cdl_stripg_assemble(g, rt.gp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
     if ((g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)(g->N * g->C * g->D));
-#define CDL_ASM4(P_) k_assemble_g4<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY)
+#define CDL_ASM4(P_) k_assemble_g4<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
         if (pl.P == 3) CDL_ASM4(3); else if (pl.P == 5) CDL_ASM4(5); else CDL_ASM4(7);
 #undef CDL_ASM4
     } else {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)(g->N * g->C * g->D));
-#define CDL_ASM(P_) k_assemble_g<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY)
+#define CDL_ASM(P_) k_assemble_g<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
         if (pl.P == 3) CDL_ASM(3); else if (pl.P == 5) CDL_ASM(5); else CDL_ASM(7);
 #undef CDL_ASM
     }
     CDL_LAUNCH_CHECK();
     return 0;
+}
+
+int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
+                        float *out, void *stream)
+{
+    if (!out) return CDL_EINVAL;
+    return cdl_fusedg_assemble_acc(g, patches, mask, sub, alpha, out, nullptr, 0, stream);
 }
 
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
@@ -1170,6 +1190,19 @@ int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const f
     k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, per_img, g->M);
     CDL_LAUNCH_CHECK();
     return 0;
+}
+
+int cdl_fusedg_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
+                             float *dtau_n, void *stream)
+{
+    const int rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt0, dt1, stream);
+    if (rc || !dtau_n) return rc;
+    Route rt;
+    route_for(g, &rt);
+    const int per_img = rt.kind == 1 ? rt.sp.nsx * rt.sp.nsy
+                        : rt.kind == 2 ? g->D * rt.gp.nsx * rt.gp.nsy : g->D * rt.pl.tilesX * rt.pl.tilesY;
+    // partial rows: [n][tile][m], as k_dtau_reduce_g reads them
+    return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
 }
 
 /* ---- whole sweeps (one C call each), the counterparts of cdl_fused2d_forward / _backward ------------------------ */
@@ -1220,11 +1253,12 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
 /* Reverse sweep: the fused stage produces du_k (one fat write), the threshold partials and the patches of q_k; the
  * filter gradients dA_k = -du_k (x) r_k and dB_k = z_k (x) q_k come from the shape-generic cdl_wgrad (its matrix-core
  * kernel where the shape has one).  wgrad_ws: cdl_wgrad_workspace_floats(g) floats. */
-int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
                         const float *const *wA, const float *const *wB, const float *const *z, const float *const *r,
                         const unsigned *const *maps, const float *g_xp, const float *g_z, float *const *dA,
                         float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
-                        float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, void *stream)
+                        float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, float *dyp,
+                          float *dtau, void *stream)
 {
     Route rt;
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
@@ -1256,14 +1290,20 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
     for (int k = K - 1, flip = 0; k >= 0; --k, flip ^= 1) {
         const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
         float *duk = du[flip];
-        rc = cdl_fusedg_stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1,
+        rc = cdl_fusedg_stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
                                   bprec | (((K - 1 - k) & 1) ? (sdir ^ CDL_TILES_REVERSED) : sdir) |
                                       CDL_LAYOUT_IN(k == K - 1 ? CDL_LAY_NCHW : lay) | CDL_LAYOUT_OUT(lay), stream);
         if (rc) return rc;
-        rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, stream);
+        rc = cdl_fusedg_dtau_reduce_x(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
+                                      dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
         if (rc) return rc;
+        if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
+            rc = cdl_fusedg_assemble_acc(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
+            if (rc) return rc;
+        }
         if (k >= 1) {
-            rc = cdl_fusedg_assemble(g, patches, mask, nullptr, -1.0f, q, stream);
+            // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
+            rc = cdl_fusedg_assemble_acc(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
             if (rc) return rc;
             rc = rsc ? cdl_mfma_wgrad_pair_lay(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], wgrad_ws,
                                                wgrad_ws_floats, 1, stream)
@@ -1277,6 +1317,16 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
         base = duk;
     }
     return 0;
+}
+
+int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                        const float *const *wA, const float *const *wB, const float *const *z, const float *const *r,
+                        const unsigned *const *maps, const float *g_xp, const float *g_z, float *const *dA,
+                        float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
+                        float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, void *stream)
+{
+    return cdl_fusedg_backward_x(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
+                                 patches, dtau_partial, wgrad_ws, wgrad_ws_floats, precision, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

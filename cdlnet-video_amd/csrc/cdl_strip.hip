@@ -543,7 +543,8 @@ __global__ __launch_bounds__(NTS) void k_strip(SParams p)
 template <int P, int S, int V>
 __global__ __launch_bounds__(256) void k_assemble_s(const float *__restrict__ patches, const float *__restrict__ mask,
                                                     const float *__restrict__ sub, float alpha, float *__restrict__ out,
-                                                    int N, int H, int W, int nsx, int nsy, int SEG, int prows)
+                                                    int N, int H, int W, int nsx, int nsy, int SEG, int prows, float *__restrict__ accum,
+                                                    int acc_add)
 {
     constexpr int HALO = P / 2, PXW = Strip<P, S>::PXW;
     const int X0 = (blockIdx.x * 256 + threadIdx.x) * V, Y = blockIdx.y, n = blockIdx.z;
@@ -572,9 +573,21 @@ __global__ __launch_bounds__(256) void k_assemble_s(const float *__restrict__ pa
         }
         if (x_lo) sum += at(sy_hi, sx_hi - 1);
         sum += at(sy_hi, sx_hi);
-        v[k] = alpha * sum;
+        v[k] = sum;
     }
     const size_t i = ((size_t)n * H + Y) * W + X0;
+    if (accum) {                                                         // the unmasked, unscaled sum (data gradient)
+        if (V == 4) {
+            float4 a = make_float4(v[0], v[1], v[2], v[3]);
+            if (acc_add) { const float4 o = *reinterpret_cast<const float4 *>(accum + i); a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w; }
+            *reinterpret_cast<float4 *>(accum + i) = a;
+        } else {
+            accum[i] = acc_add ? accum[i] + v[0] : v[0];
+        }
+    }
+    if (!out) return;
+#pragma unroll
+    for (int k = 0; k < V; ++k) v[k] *= alpha;
     if (V == 4) {
         float4 o = make_float4(v[0], v[1], v[2], v[3]);
         if (mask) { const float4 mm = *reinterpret_cast<const float4 *>(mask + i); o.x *= mm.x; o.y *= mm.y; o.z *= mm.z; o.w *= mm.w; }
@@ -725,14 +738,14 @@ size_t cdl_strip_rsc_floats(const cdl_geom *g, const cdl_strip_plan &pl)
 }
 
 int cdl_strip_assemble(const cdl_geom *g, const cdl_strip_plan &pl, const float *patches, const float *mask,
-                       const float *sub, float alpha, float *out, hipStream_t st)
+                       const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st)
 {
     const bool v4 = (g->W & 3) == 0 && !cdl_opts().scalar_assemble;      // (CDL_SCALAR_ASSEMBLE=1: the scalar form, for tests)
     dim3 grid((unsigned)(((v4 ? g->W / 4 : g->W) + 255) / 256), (unsigned)g->H, (unsigned)g->N);
 #define CDL_ASM_S(P_, S_)                                                                                                   \
     do {                                                                                                                    \
-        if (v4) k_assemble_s<P_, S_, 4><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows); \
-        else k_assemble_s<P_, S_, 1><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows);    \
+        if (v4) k_assemble_s<P_, S_, 4><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add); \
+        else k_assemble_s<P_, S_, 1><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add);    \
     } while (0)
     if (pl.S == 2) { if (pl.P == 3) CDL_ASM_S(3, 2); else if (pl.P == 5) CDL_ASM_S(5, 2); else CDL_ASM_S(7, 2); }
     else { if (pl.P == 3) CDL_ASM_S(3, 1); else if (pl.P == 5) CDL_ASM_S(5, 1); else CDL_ASM_S(7, 1); }

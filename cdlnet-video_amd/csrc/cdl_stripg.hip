@@ -462,7 +462,7 @@ template <int P>
 __global__ __launch_bounds__(256) void k_assemble_sg(const float *__restrict__ patches, const float *__restrict__ mask,
                                                      const float *__restrict__ sub, float alpha, float *__restrict__ out,
                                                      int N, int C, int D, int H, int W, int Pd, int nsx, int nsy, int SEG,
-                                                     int prows)
+                                                     int prows, float *__restrict__ accum, int acc_add)
 {
     constexpr int HALO = P / 2, PXW = Strip<P, 1>::PXW;
     const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
@@ -493,6 +493,8 @@ __global__ __launch_bounds__(256) void k_assemble_sg(const float *__restrict__ p
         sum += at(sy_hi, sx_hi);
     }
     const size_t i = ((((size_t)n * C + c) * D + d) * H + Y) * W + X;
+    if (accum) accum[i] = acc_add ? accum[i] + sum : sum;             // the unmasked, unscaled sum (data gradient)
+    if (!out) return;
     float v = alpha * sum;
     if (mask) v *= mask[i];
     if (sub) v -= sub[i];
@@ -599,10 +601,10 @@ int cdl_stripg_stage(const cdl_geom *g, const cdl_stripg_plan &pl, int mode, con
 }
 
 int cdl_stripg_assemble(const cdl_geom *g, const cdl_stripg_plan &pl, const float *patches, const float *mask,
-                        const float *sub, float alpha, float *out, hipStream_t st)
+                        const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st)
 {
     dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)(g->N * g->C * g->D));
-#define CDL_ASM_G(P_) k_assemble_sg<P_><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.nsx, pl.nsy, pl.SEG, pl.prows)
+#define CDL_ASM_G(P_) k_assemble_sg<P_><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add)
     if (pl.P == 3) CDL_ASM_G(3); else if (pl.P == 5) CDL_ASM_G(5); else CDL_ASM_G(7);
 #undef CDL_ASM_G
     CDL_LAUNCH_CHECK();

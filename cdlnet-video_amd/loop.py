@@ -12,7 +12,11 @@ reference, train.py:98); with du_k = [z_{k+1} != 0] * g_{k+1}:
     dA_k    = -du_k (x) r_k,   r_k = mask * B_k z_k - yp  (kept from the forward sweep; it is thin)
     dB_k    =  z_k  (x) q_k
     g_k     = du_k + B_k^T q_k
-Only parameter gradients are produced (the reference never differentiates w.r.t. the image).
+and, when y / sigma require grad (the forward is a torch graph in both in the reference), with u_0 = A_0 yp:
+    dL/dyp  = sum_k A_k^T du_k            (the unmasked sum behind q_k; k = 0 adds the synthesis half of stage 0)
+    dL/dc_n = sum_k sum_m t[k,1,m] dtau[k,n,m]     (per-sample threshold gradients, contracted here)
+    dL/dy   = cdl_preprocess_bwd(dL/dyp, dL/dxhat)  (reflect pad adjoint and the mean)
+The gradient with respect to the mask is not produced (it needs mask * B_k z_k at masked-out pixels).
 """
 import torch
 
@@ -169,23 +173,24 @@ def _forward_fusedg(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nc
     return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid else [])
 
 
-def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw"):
+def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw", dyp=None, dtau=None):
     """cdl_fusedg_backward: per iteration one fused reverse stage (du_k, threshold partials, patches of q_k), a thin
     assemble and the two filter gradients.  `layout`: that of codes[:-1]."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
     return ops.fusedg_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
-                               maps=list(maps) if maps else None, layout=layout)
+                               maps=list(maps) if maps else None, layout=layout, dyp=dyp, dtau=dtau)
 
 
-def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None):
-    """Reverse sweep from one C call (cdl_ista_backward)."""
+def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None):
+    """Reverse sweep from one C call (cdl_ista_backward_x; dyp / dtau: see ops.fused_backward)."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
-    return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt)
+    return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, dyp=dyp,
+                             dtau=dtau)
 
 
-def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None):
+def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
     dA, dB = [None] * K, [None] * K
     zK = codes[K - 1]
@@ -197,27 +202,36 @@ def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_
         gk = g_z.contiguous() if g_z is not None else torch.zeros_like(zK)
     for k in range(K - 1, 0, -1):
         z_next, z_k, r_k = codes[k], codes[k - 1], resid[k - 1]
-        ops.tau_grad(g, gk, z_next, c, dt[k])
-        q = ops.synthesis(g, gk, A[k], -1.0, z_next, mask_p, None)
+        ops.tau_grad(g, gk, z_next, c, dt[k], dtau[k] if dtau is not None else None)
+        if dyp is not None:                                         # S = A_k^T du_k; dyp (+)= S; q = -mask S
+            q = ops.synthesis(g, gk, A[k], 1.0, z_next, None, None)
+            ops.dyp_split(g, q, mask_p, dyp, k < K - 1)
+        else:
+            q = ops.synthesis(g, gk, A[k], -1.0, z_next, mask_p, None)
         dA[k] = ops.wgrad(g, gk, r_k, -1.0, gate=z_next)
         dB[k] = ops.wgrad(g, z_k, q, 1.0)
         gk = ops.analysis(g, q, B[k], 1.0, gk, z_next, None)
-    ops.tau_grad(g, gk, codes[0], c, dt[0])
+    ops.tau_grad(g, gk, codes[0], c, dt[0], dtau[0] if dtau is not None else None)
     dA[0] = ops.wgrad(g, gk, yp, 1.0, gate=codes[0])
+    if dyp is not None:                                             # u_0 = A_0 yp
+        ops.dyp_split(g, ops.synthesis(g, gk, A[0], 1.0, codes[0]), None, dyp, K > 1, make_q=False)
     return dA, dB
 
 
-def _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout=None, precision=None):
+def _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout=None, precision=None,
+                    dyp=None, dtau=None):
     """Reverse sweep from one C call (cdl_fused2d_backward): per iteration one stage launch (1 fat read +
     the 2-bit map of z_{k+1}, 1 fat write), a thin assemble, and one MFMA filter-gradient launch (2 fat
     reads).  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1]."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
     return ops.fused_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
-                              precision or PRECISION, maps=list(maps) if maps else None, layout=layout or CODE_LAYOUT)
+                              precision or PRECISION, maps=list(maps) if maps else None, layout=layout or CODE_LAYOUT,
+                              dyp=dyp, dtau=dtau)
 
 
-def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw"):
+def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
+                             dyp=None, dtau=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
     assert maps or layout == "nchw"
     prec = PRECISION
@@ -230,11 +244,14 @@ def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z,
     (dB[0],) = ops.fused_wgrad(g, ws, codes[K - 1], g_xp, 1.0, precision=prec)[:1]
     for k in range(K - 1, -1, -1):
         frags = ops.fused_prep(B[(k + 1) % K], A[k])          # analysis-like bank, synthesis-like bank
-        du = ops.fused_stage_bwd(g, thin, du_next, maps[k] if maps else codes[k], frags, patches, dtp, k >= 1, prec,
-                                 lay_in="nchw" if k == K - 1 else layout, lay_out=layout)
-        ops.fused_dtau_reduce(g, dtp, c, dt[k])
+        du = ops.fused_stage_bwd(g, thin, du_next, maps[k] if maps else codes[k], frags, patches, dtp,
+                                 k >= 1 or dyp is not None, prec, lay_in="nchw" if k == K - 1 else layout, lay_out=layout)
+        ops.fused_dtau_reduce(g, dtp, c, dt[k], dtau[k] if dtau is not None else None)
+        if k == 0 and dyp is not None:                              # u_0 = A_0 yp
+            ops.fused_assemble_acc(g, patches, dyp, K > 1, write_out=False)
         if k >= 1:
-            q = ops.fused_assemble(g, patches, mask_p, None, -1.0)
+            q = (ops.fused_assemble_acc(g, patches, dyp, k < K - 1, mask_p, None, -1.0) if dyp is not None
+                 else ops.fused_assemble(g, patches, mask_p, None, -1.0))
             dA[k], dB[k] = ops.fused_wgrad(g, ws, du, resid[k - 1], -1.0, codes[k - 1], q, 1.0, prec, layout=layout)
             thin = q
         else:
@@ -261,11 +278,11 @@ def _arithmetic_aware(cls):
     return cls
 
 
-def _no_data_gradients(ctx):
-    """The reverse sweeps produce parameter (and neighbour-code) gradients only.  The reference's loop is
-    differentiable in the observation, the mask and sigma as well (no caller in the reference uses that); asking for
-    those here must fail loudly rather than return a silent None."""
-    for idx, name in ((0, "y"), (1, "mask"), (2, "sigma")):
+def _no_data_gradients(ctx, names=((0, "y"), (1, "mask"), (2, "sigma"))):
+    """The CSR reverse sweeps produce parameter and neighbour-code gradients only, UnrolledISTA's no mask gradient.  The
+    reference's loop is differentiable in the observation, the mask and sigma (no caller in the reference uses the
+    mask's); asking for what a sweep does not produce must fail loudly rather than return a silent None."""
+    for idx, name in names:
         if ctx.needs_input_grad[idx]:
             raise NotImplementedError(f"cdlnet_video_amd: the gradient with respect to `{name}` is not implemented "
                                       f"(the HIP reverse sweep returns parameter gradients only); detach() it")
@@ -289,8 +306,10 @@ class UnrolledISTA(torch.autograd.Function):
         tau = ops.thresholds(t, c, N)
 
         ctx.set_materialize_grads(False)          # an unused z output must not cost a fat zero tensor
-        _no_data_gradients(ctx)
+        _no_data_gradients(ctx, ((1, "mask"),))   # y and sigma (through c): dL/dyp and dtau from the sweeps
         keep = any(ctx.needs_input_grad)          # all False under torch.no_grad()
+        ctx.want_y = ctx.needs_input_grad[0]
+        ctx.want_c = ctx.needs_input_grad[2] and c is not None
         want_codes = cfg.get("all_codes", False)
         auto = BACKEND == "auto" and not ctx.exact     # "fp32": the fused kernels are matrix-core kernels
         ctx.fused = auto and ops.fused_supported(g)
@@ -311,9 +330,11 @@ class UnrolledISTA(torch.autograd.Function):
         ctx.geom, ctx.pads, ctx.K = g, pads, K
         ctx.has_mask, ctx.has_c = mask_p is not None, c is not None
         if keep:
+            # the adjoint of preprocess needs the unpadded mask (its per-sample sum is taken in cdl_preprocess_bwd)
+            y_mask = mask if (ctx.want_y and mask is not None) else yp.new_empty(0)
             ctx.save_for_backward(yp, mask_p if mask_p is not None else yp.new_empty(0),
                                   c if c is not None else yp.new_empty(0), t, *weights,
-                                  *codes, *resid, *maps)
+                                  *codes, *resid, *maps, y_mask)
             ctx.n_maps = len(maps)
         outs = (xhat, z)
         if want_codes:
@@ -333,22 +354,33 @@ class UnrolledISTA(torch.autograd.Function):
         B = saved[4 + K:4 + 2 * K]
         codes = saved[4 + 2 * K:4 + 3 * K]            # z_1..z_K
         resid = saved[4 + 3 * K:4 + 3 * K + (K - 1)]  # r_1..r_{K-1}
-        maps = saved[4 + 3 * K + (K - 1):]            # fused path: support/sign bit maps of z_1..z_K
+        maps = saved[4 + 3 * K + (K - 1):-1]          # fused path: support/sign bit maps of z_1..z_K
+        y_mask = saved[-1] if (ctx.want_y and ctx.has_mask) else None
         assert len(maps) == ctx.n_maps
         dt = torch.zeros((K, 2, g.M), device=yp.device, dtype=torch.float32)
         g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
         if g_z is not None:
             g_z = g_z.contiguous()
+        live = g_xp is not None or g_z is not None
+        # data gradients only when asked for: otherwise the sweeps get NULLs and run exactly the parameter-only launches
+        dyp = torch.empty(g.image_shape(), device=yp.device, dtype=torch.float32) if ctx.want_y and live else None
+        dtau = torch.empty((K, g.N, g.M), device=yp.device, dtype=torch.float32) if ctx.want_c and live else None
         if ctx.fusedg:
-            dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=ctx.layout)
+            dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=ctx.layout,
+                                      dyp=dyp, dtau=dtau)
         elif ctx.fused:                                # a loss on z only is a zero image gradient to the sweep
             dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
-                                     layout=ctx.layout, precision=ctx.precision)
+                                     layout=ctx.layout, precision=ctx.precision, dyp=dyp, dtau=dtau)
         else:
-            dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt)
+            dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, dtau=dtau)
+        dy = dc = None
+        if dyp is not None:                            # a loss on z only: no mean term
+            dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, y_mask)
+        if dtau is not None:                           # tau[k,n,m] = t[k,0,m] + c[n] t[k,1,m]
+            dc = torch.einsum("knm,km->n", dtau, t.detach().reshape(K, 2, g.M)[:, 1])
 
         _queue_backward_end()
-        return (None, None, None, dt.reshape(t.shape), None, *dA, *dB)
+        return (dy, None, dc, dt.reshape(t.shape), None, *dA, *dB)
 
 
 # ------------------------------------------------------------------------------------------

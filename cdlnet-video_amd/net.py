@@ -232,6 +232,11 @@ class _CSRBase(_ISTANet):
             raise RuntimeError(
                 f"{type(self).__name__}.forward: input is on {y.device}. This package has no CPU "
                 "compute path; the iterations run in HIP kernels on a ROCm device.")
+        if torch.is_grad_enabled() and (y.requires_grad or (torch.is_tensor(sigma) and sigma.requires_grad)):
+            # the CSR sweeps (TemporalISTA) return parameter and neighbour-code gradients only; the no-neighbour
+            # branch runs UnrolledISTA, which could, but the variant's surface stays one contract
+            raise NotImplementedError(f"cdlnet_video_amd: {type(self).__name__}: gradients with respect to y / sigma "
+                                      "are not implemented; detach() them")
         y = y.to(torch.float32)
         return y, _mask_tensor(mask, y), _noise_scale(sigma, self.adaptive, y.shape[0], y.device)
 

@@ -199,6 +199,24 @@ def postprocess_bwd(gxhat, pads):
     return out
 
 
+def preprocess_bwd(dyp, pads, g_xhat=None, mask=None):
+    """dL/dy from dL/dyp (the reflect pad's adjoint, the mean's) and, through the mean postprocess adds back, from
+    dL/dxhat (cdl_preprocess_bwd).  `mask`: the unpadded mask preprocess was given."""
+    dyp = _dev(dyp, "dyp")
+    g_xhat, mask = _opt(g_xhat, "g_xhat"), _opt(mask, "mask")
+    nd = dyp.dim() - 2
+    N, C = dyp.shape[:2]
+    p6 = _pads6(pads, nd)
+    spp = _three(dyp.shape[2:], 1)
+    sp = [spp[i] - p6[2 * i] - p6[2 * i + 1] for i in range(3)]
+    dy = torch.empty((N, C) + tuple(sp[3 - nd:]), device=dyp.device, dtype=torch.float32)
+    for t in (g_xhat, mask):
+        assert t is None or tuple(t.shape) == tuple(dy.shape)
+    rc = _lib.lib().cdl_preprocess_bwd(_ptr(dyp), _ptr(g_xhat), _ptr(mask), _ptr(dy), N, C, *sp, p6, _stream())
+    _lib.check(rc, "cdl_preprocess_bwd")
+    return dy
+
+
 def thresholds(t, c, N):
     """tau (K,N,M) = t[k,0] + c[n]*t[k,1]; t is the (K,2,M,1,1[,1]) parameter."""
     t = _dev(t, "t")
@@ -301,17 +319,30 @@ def wgrad_pair(g: Geometry, z0, x0, alpha0, z1, x1, alpha1):
     return dw0, dw1
 
 
-def tau_grad(g: Geometry, gup, zout, c, dt_k):
-    """Writes the (2,M) slice `dt_k` of the threshold gradient for one iteration."""
+def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None):
+    """Writes the (2,M) slice `dt_k` of the threshold gradient for one iteration [and the per-sample (N,M) `dtau_n`]."""
     gup, zout, c = _dev(gup, "g"), _dev(zout, "zout"), _opt(c, "c")
     scratch = torch.empty(16 * g.N * g.M, device=gup.device, dtype=torch.float32)      # CDL_TAU_SPLITS * N * M
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_tau_grad(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c),
-                                 ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M),
-                                 _ptr(scratch), _stream())
-    _lib.check(rc, "cdl_tau_grad")
+    if dtau_n is None:
+        rc = _lib.lib().cdl_tau_grad(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c),
+                                     ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M),
+                                     _ptr(scratch), _stream())
+        _lib.check(rc, "cdl_tau_grad")
+        return
+    assert dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M
+    rc = _lib.lib().cdl_tau_grad_x(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
+                                   ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _stream())
+    _lib.check(rc, "cdl_tau_grad_x")
+
+
+def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
+    """Generic reverse sweep: q holds S = A_k^T du_k (unmasked); dyp (+)= S, then q = -mask * S in place (cdl_dyp_split)."""
+    rc = _lib.lib().cdl_dyp_split(ctypes.byref(g.c_struct()), _ptr(q), _ptr(_opt(mask, "mask")), _ptr(dyp),
+                                  int(bool(acc_add)), int(bool(make_q)), _stream())
+    _lib.check(rc, "cdl_dyp_split")
 
 
 def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None):
@@ -663,6 +694,20 @@ def fused_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=Non
     return out
 
 
+def fused_assemble_acc(g: Geometry, patches, acc, acc_add, mask=None, sub=None, alpha=1.0, out=None, write_out=True):
+    """fused_assemble, and acc = S or acc += S with S the unmasked, unscaled overlap-sum (cdl_fused2d_assemble_acc);
+    write_out=False: acc only.  Returns out (None without write_out)."""
+    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
+    assert acc.is_contiguous() and tuple(acc.shape) == g.image_shape()
+    if write_out and out is None:
+        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
+    rc = _lib.lib().cdl_fused2d_assemble_acc(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
+                                             float(alpha), _ptr(out if write_out else None), _ptr(acc),
+                                             int(bool(acc_add)), _stream())
+    _lib.check(rc, "cdl_fused2d_assemble_acc")
+    return out if write_out else None
+
+
 def fused_tiles(g: Geometry) -> int:
     gs = g.c_struct()
     return int(_lib.lib().cdl_fused2d_tiles(ctypes.byref(gs)))
@@ -699,14 +744,16 @@ def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial,
     return out
 
 
-def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k):
+def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
+    """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`: cdl_fused2d_dtau_reduce_x]."""
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
+    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fused2d_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                            ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M),
-                                            _stream())
-    _lib.check(rc, "cdl_fused2d_dtau_reduce")
+    rc = _lib.lib().cdl_fused2d_dtau_reduce_x(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
+                                              ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
+                                              _stream())
+    _lib.check(rc, "cdl_fused2d_dtau_reduce_x")
 
 
 def fused_wgrad_workspace(g: Geometry, device):
@@ -734,6 +781,14 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
                                       PRECISION[precision] | _lay_in(layout), _stream())
     _lib.check(rc, "cdl_fused2d_wgrad")
     return outs
+
+
+def _check_data_grads(g: Geometry, K, dyp, dtau):
+    """The optional outputs of the *_backward_x sweeps: dyp (thin, as yp), dtau (K,N,M); contiguous fp32."""
+    for t, shape in ((dyp, g.image_shape()), (dtau, (K, g.N, g.M))):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+                (tuple(t.shape), shape)
 
 
 def _ptr_table(tensors):
@@ -774,11 +829,12 @@ def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", 
 
 
 def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision="split3", maps=None,
-                   layout="blocked"):
+                   layout="blocked", dyp=None, dtau=None):
     """Whole reverse sweep in one C call; returns (dA list, dB list); dt (K,2,M) is written in place.
     maps: the forward's bit maps of z_1..z_K (built here from the codes when not given).  `layout`: that of
     codes[:-1] (as fused_forward returned them) and of the du work buffers; codes[-1] = z_K, g_z: NCHW.
-    g_xp None (a loss on the code only) is a zero image gradient."""
+    g_xp None (a loss on the code only) is a zero image gradient.  dyp (thin, as yp) / dtau (K,N,M): filled with
+    dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward_x; None: the plain sweep)."""
     K = len(A)
     dev = yp.device
     if not maps:
@@ -801,13 +857,14 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
     ws = fused_wgrad_workspace(g, dev)
     assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
     gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_backward(
+    _check_data_grads(g, K, dyp, dtau)
+    rc = _lib.lib().cdl_fused2d_backward_x(
         ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
         _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
         _ptr_table(dB), _ptr(dt),
         _ptr(du0), _ptr(du1), _ptr(q), _ptr(frags), _ptr(patches), _ptr(dtp), _ptr(ws),
-        PRECISION[precision] | _lay_in(layout), _stream())
-    _lib.check(rc, "cdl_fused2d_backward")
+        PRECISION[precision] | _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
+    _lib.check(rc, "cdl_fused2d_backward_x")
     return dA, dB
 
 
@@ -910,6 +967,19 @@ def fusedg_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=No
     return out
 
 
+def fusedg_assemble_acc(g: Geometry, patches, acc, acc_add, mask=None, sub=None, alpha=1.0, out=None, write_out=True):
+    """fusedg_assemble with the unmasked sum into `acc` (cdl_fusedg_assemble_acc; see fused_assemble_acc)."""
+    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
+    assert acc.is_contiguous() and tuple(acc.shape) == g.image_shape()
+    if write_out and out is None:
+        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
+    rc = _lib.lib().cdl_fusedg_assemble_acc(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
+                                            float(alpha), _ptr(out if write_out else None), _ptr(acc),
+                                            int(bool(acc_add)), _stream())
+    _lib.check(rc, "cdl_fusedg_assemble_acc")
+    return out if write_out else None
+
+
 def fusedg_support_map(g: Geometry, z):
     """Bit map of a code tensor in the layout the fused stages use: (N, 4 * pairs, code dims) words; channel
     32R + 8q + 4h + e is bit 16(R&1) + 4q + e of plane 4(R>>1) + 2h (support, [z != 0]) and of plane 4(R>>1) + 2h + 1
@@ -949,13 +1019,15 @@ def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_par
     return out
 
 
-def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k):
+def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
+    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fusedg_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                           ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _stream())
-    _lib.check(rc, "cdl_fusedg_dtau_reduce")
+    rc = _lib.lib().cdl_fusedg_dtau_reduce_x(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
+                                             ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
+                                             _stream())
+    _lib.check(rc, "cdl_fusedg_dtau_reduce_x")
 
 
 def fusedg_code_layout(g: Geometry, training=True) -> str:
@@ -1002,9 +1074,10 @@ def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw"):
     return xp, zK, (z if keep else [zK]), (r if keep else []), maps
 
 
-def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw"):
-    """Whole reverse sweep in one C call (cdl_fusedg_backward); returns (dA list, dB list), fills dt (K,2,M).
-    `layout`: that of codes[:-1] (and of the du buffers allocated here)."""
+def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
+                    dyp=None, dtau=None):
+    """Whole reverse sweep in one C call (cdl_fusedg_backward_x); returns (dA list, dB list), fills dt (K,2,M) [and
+    dyp, dtau: see fused_backward].  `layout`: that of codes[:-1] (and of the du buffers allocated here)."""
     K = len(A)
     dev = yp.device
     if not maps:
@@ -1029,12 +1102,13 @@ def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, d
     nws = int(_lib.lib().cdl_wgrad_workspace_floats(ctypes.byref(gs)))
     ws = torch.empty(max(nws, 1), device=dev, dtype=torch.float32)
     assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
-    rc = _lib.lib().cdl_fusedg_backward(
+    _check_data_grads(g, K, dyp, dtau)
+    rc = _lib.lib().cdl_fusedg_backward_x(
         ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
         _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
         _ptr_table(dB), _ptr(dt), _ptr(du[0]), _ptr(du[1 if K > 1 else 0]), _ptr(q), _ptr(frags), _ptr(patches),
-        _ptr(dtp), _ptr(ws), nws, _lay_in(layout), _stream())
-    _lib.check(rc, "cdl_fusedg_backward")
+        _ptr(dtp), _ptr(ws), nws, _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
+    _lib.check(rc, "cdl_fusedg_backward_x")
     return dA, dB
 
 
@@ -1079,8 +1153,10 @@ def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=
 
 
 def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, us=None, z_prev=None,
-                  z_after=None, lam=None, gam1=None, gam2=None, dg1=None, dg2=None, gz_prev=None, gz_after=None):
-    """Generic reverse sweep in one C call; returns (dA, dB) and fills dt [, dg1, dg2, gz_prev, gz_after]."""
+                  z_after=None, lam=None, gam1=None, gam2=None, dg1=None, dg2=None, gz_prev=None, gz_after=None,
+                  dyp=None, dtau=None):
+    """Generic reverse sweep in one C call (cdl_ista_backward_x); returns (dA, dB) and fills dt [, dg1, dg2, gz_prev,
+    gz_after] [, dyp, dtau: see fused_backward; plain loop only]."""
     K = len(A)
     dev = yp.device
     A = [_dev(w, "A") for w in A]
@@ -1090,15 +1166,16 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
     g0, g1, q = _new(g.code_shape(), dev), _new(g.code_shape(), dev), _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
     gs = g.c_struct()
-    rc = _lib.lib().cdl_ista_backward(
+    _check_data_grads(g, K, dyp, dtau)
+    rc = _lib.lib().cdl_ista_backward_x(
         ctypes.byref(gs), K, _ptr(_dev(yp, "yp")), _ptr(_opt(mask_p, "mask")), _ptr(_opt(c, "c")),
         _ptr(_opt(z_prev, "z_prev")), _ptr(_opt(z_after, "z_after")), _ptr(_opt(lam, "lam")),
         _ptr(_opt(gam1, "gam1")), _ptr(_opt(gam2, "gam2")), _ptr_table(A), _ptr_table(B),
         _ptr_table([_dev(t, "z") for t in codes]), _ptr_table([_dev(t, "r") for t in resid]) if resid else None,
         _ptr_table([_dev(t, "u") for t in us]) if us else None, _ptr(_opt(g_xp, "g_xp")), _ptr(_opt(g_z, "g_z")),
         _ptr_table(dA), _ptr_table(dB), _ptr(dt), _ptr(dg1), _ptr(dg2), _ptr(gz_prev), _ptr(gz_after),
-        _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_ista_backward")
+        _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _stream())
+    _lib.check(rc, "cdl_ista_backward_x")
     return dA, dB
 
 

@@ -80,6 +80,16 @@ int cdl_postprocess(const float *xp, const float *mean, float *xhat,
 int cdl_postprocess_bwd(const float *gxhat, float *gxp, int N, int C, int D, int H, int W,
                         const int pads[6], void *stream);
 
+/* Adjoint of cdl_preprocess (+ the mean that cdl_postprocess adds back), for gradients with respect to y: with
+ * G = the adjoint of the reflect pad applied to dyp (mirrored border values added into their interior sources) and
+ * sums over (C,D,H,W) per sample,
+ *     no mask: dy = G - mean(G) + sum(g_xhat) / (C D H W)
+ *     mask:    dy = mask * G + (sum(g_xhat) - sum(mask * G)) / sum(mask)
+ * g_xhat NULL = a loss on the code only (no mean term).  One workgroup per sample, double sums in a fixed order:
+ * deterministic.  dyp: (N,C,D+..,H+..,W+..); g_xhat, mask, dy: (N,C,D,H,W) unpadded. */
+int cdl_preprocess_bwd(const float *dyp, const float *g_xhat /*nullable*/, const float *mask /*nullable*/, float *dy,
+                       int N, int C, int D, int H, int W, const int pads[6], void *stream);
+
 /* tau[k,n,m] = t[k,0,m] + c[n] * t[k,1,m]   (net.py:82,85,87; c = sigma/255 or absent = 0) */
 int cdl_thresholds(const float *t /*K,2,M*/, const float *c /*N, nullable*/, float *tau /*K,N,M*/,
                    int K, int N, int M, void *stream);
@@ -114,6 +124,11 @@ size_t cdl_analysis_workspace_floats(const cdl_geom *g);
 int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
                         const float *zsup, const float *c /*nullable*/, float *dt0, float *dt1, float *out,
                         float *workspace, size_t workspace_floats, void *stream);
+/* The same with the per-sample threshold gradients of `out` (cdl_tau_grad_x's dtau_n; nullable). */
+int cdl_analysis_rev_ws_x(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
+                          const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
+                          float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
+                          void *stream);
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g);
 
 /* ---- synthesis half: F.conv_transpose2d/3d at net.py:87,90,205,210 and gabor.py:64 ----------
@@ -160,6 +175,19 @@ int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const f
  * consumers of the gated gradient then need no gate (one fat read each less). */
 int cdl_tau_grad_gate(const cdl_geom *g, float *gup /*inout*/, const float *zout, const float *c /*N, nullable*/,
                       float *dt0 /*M*/, float *dt1 /*M*/, float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+/* The same two, and (dtau_n non-NULL) the per-sample threshold gradient dtau_n[n,m] = -sum_pix sign(zout)*du of
+ * sample n (dt0 = sum_n dtau_n, dt1 = sum_n c[n] dtau_n): what dL/dc needs.  dt0 / dt1 are bit-identical to the
+ * forms above. */
+int cdl_tau_grad_x(const cdl_geom *g, const float *gup, const float *zout, const float *c /*N, nullable*/,
+                   float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
+                   float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+int cdl_tau_grad_gate_x(const cdl_geom *g, float *gup /*inout*/, const float *zout, const float *c /*N, nullable*/,
+                        float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
+                        float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+/* Generic reverse sweep, iteration k: q holds S = A_k^T du_k (unmasked, alpha = +1); dyp = S (acc_add 0) or dyp += S,
+ * then with make_q: q = -(mask ? mask : 1) * S in place -- the q_k the sweep continues with. */
+int cdl_dyp_split(const cdl_geom *g, float *q /*inout, thin*/, const float *mask /*nullable*/, float *dyp,
+                  int acc_add, int make_q, void *stream);
 
 /* ---- CSR temporal variants --------------------------------------
  * prox_CSR / prox_CSR_f2 of model/net.py:229-262, the shrinkage that CDLNet_CSR.forward
@@ -250,6 +278,20 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
                       float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
                       size_t scratch_floats, void *stream);
+/* The same with the gradients of the data (plain loop only: z_prev must be NULL when either is given):
+ *     dyp  (thin, as yp; nullable):  dL/dyp = sum_k A_k^T du_k  (u_0 = A_0 yp, u_k = z_k - A_k(mask B_k z_k - yp))
+ *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau)
+ * With both NULL it is cdl_ista_backward: same launches, same arguments. */
+int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
+                        const float *c /*N, nullable*/, const float *z_prev /*nullable*/,
+                        const float *z_after /*nullable*/, const float *lam, const float *gam1, const float *gam2,
+                        const float *const *wA, const float *const *wB, const float *const *z,
+                        const float *const *r, const float *const *u /*CSR*/, const float *g_xp /*nullable*/,
+                        const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt,
+                        float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
+                        float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
+                        size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M, nullable*/,
+                        void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
  * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere.  w inout. */
@@ -337,6 +379,11 @@ int cdl_fused2d_support_map(const cdl_geom *g, const float *z, unsigned *map, vo
 /* out = (mask ? mask : 1) * alpha * (sum of the overlapping patches) - (sub ? sub : 0) */
 int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
                          const float *sub /*nullable*/, float alpha, float *out, void *stream);
+/* The same, and (acc non-NULL) the plain sum S of the patches, unmasked and unscaled: acc = S (acc_add 0) or acc += S.
+ * S comes from the same summation as `out`, which is bit-identical to cdl_fused2d_assemble's.  out NULL: acc only. */
+int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
+                             const float *sub /*nullable*/, float alpha, float *out /*nullable*/,
+                             float *acc /*nullable*/, int acc_add, void *stream);
 
 /* ---- fused reverse sweep (what loss.backward() does through ATen in the reference, train.py:98) ----
  * One stage per iteration k = K-1 .. 0, same kernel skeleton as the forward launch:
@@ -362,6 +409,9 @@ int cdl_fused2d_stage_bwd_da(const cdl_geom *g, const float *thin, const float *
 /* dt0[m] = sum over workgroups; dt1[m] = sum_n c[n] * (sum over the workgroups of image n); c nullable */
 int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/,
                             float *dt0 /*M*/, float *dt1 /*M*/, void *stream);
+/* The same, and (dtau_n non-NULL) the per-image sums dtau_n[n,m] of the partial rows, tiles in order */
+int cdl_fused2d_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/, float *dt0 /*M*/,
+                              float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/, void *stream);
 
 /* Filter gradients on the matrix cores: up to two independent reductions per launch
  *     dw_a[m,i,j] = alpha_a * sum_{n,y,x} Xa[n,m,y,x] * Ta[n,y-p+i,x-p+j]     (a = 0, 1; either may be absent)
@@ -391,6 +441,16 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
                          float *dt,
                          float *du0, float *du1, float *q, void *frags, float *patches,
                          float *dtau_partial, float *wgrad_ws, int precision, void *stream);
+/* The same with the gradients of the data, as cdl_ista_backward_x: dyp (thin, nullable) receives sum_k A_k^T du_k -- the
+ * unmasked sum each assemble already forms, plus the k = 0 synthesis half (its stage then runs with do_synth = 1) and
+ * one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients.  Both NULL: cdl_fused2d_backward. */
+int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
+                           const float *c /*N, nullable*/, const float *const *wA, const float *const *wB,
+                           const float *const *z, const float *const *r, const unsigned *const *maps,
+                           const float *g_xp, const float *g_z /*nullable*/, float *const *dA, float *const *dB,
+                           float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
+                           float *dtau_partial, float *wgrad_ws, int precision, float *dyp /*nullable*/,
+                           float *dtau /*K*N*M, nullable*/, void *stream);
 
 /* ==== fused MFMA path for the other shapes (cdl_fusedg.hip): any C, 2-D / 3-D, unit stride, square planes ====
  * P in {3,5,7}, odd Pd with C*Pd in {1,3,5,7}, M <= 64 -- CDLNetVideo.forward's loop body (net.py:204-207) and
@@ -426,6 +486,12 @@ int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *ma
                         const float *sub /*nullable*/, float alpha, float *out, void *stream);
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N, nullable*/, float *dt0,
                            float *dt1, void *stream);
+/* As cdl_fused2d_assemble_acc / cdl_fused2d_dtau_reduce_x (every route: tile, strip and grouped strip kernels) */
+int cdl_fusedg_assemble_acc(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
+                            const float *sub /*nullable*/, float alpha, float *out /*nullable*/,
+                            float *acc /*nullable*/, int acc_add, void *stream);
+int cdl_fusedg_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c /*N, nullable*/, float *dt0,
+                             float *dt1, float *dtau_n /*N,M, nullable*/, void *stream);
 /* Whole sweeps (arguments as cdl_fused2d_forward / _backward).  The reverse sweep takes the filter gradients
  * dA_k = -du_k (x) r_k, dB_k = z_k (x) q_k from cdl_wgrad: wgrad_ws = cdl_wgrad_workspace_floats(g) floats. */
 int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/, const float *tau,
@@ -438,6 +504,14 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
                         const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt, float *du0,
                         float *du1, float *q, void *frags, float *patches, float *dtau_partial, float *wgrad_ws,
                         size_t wgrad_ws_floats, int precision, void *stream);
+/* With the gradients of the data, as cdl_fused2d_backward_x.  Both NULL: cdl_fusedg_backward. */
+int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
+                          const float *c /*nullable*/, const float *const *wA, const float *const *wB,
+                          const float *const *z, const float *const *r, const unsigned *const *maps, const float *g_xp,
+                          const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt, float *du0,
+                          float *du1, float *q, void *frags, float *patches, float *dtau_partial, float *wgrad_ws,
+                          size_t wgrad_ws_floats, int precision, float *dyp /*nullable*/,
+                          float *dtau /*K*N*M, nullable*/, void *stream);
 
 /* Per-kernel timing inside the fused sweeps: cdl_fused2d_timing(1) starts collecting HIP-event pairs around
  * every forward stage (class 0; the k = 0 launch, which reads no code, is class 3), reverse stage (1) and
