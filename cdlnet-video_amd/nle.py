@@ -1,11 +1,14 @@
-"""Blind noise-level estimation (reference model/nle.py): `noise_level(y, method="MAD")` / `nle_mad(y)`.
+"""Blind noise-level estimation (reference model/nle.py): `noise_level(y, method="MAD")` / `nle_mad(y)`, `nle_pca(y)`.
 
-The estimate runs in libcdlnet_hip.so (cdl_nle_mad): depthwise stride-2 correlation with the 'bior4.4'
-diagonal (HH) analysis filter and an exact per-sample median.  `nle_pca` (the reference's other method, a
-CPU eigen-decomposition translated from MATLAB) is not part of the hot path and is not provided.
+`nle_mad` runs in libcdlnet_hip.so (cdl_nle_mad): depthwise stride-2 correlation with the 'bior4.4'
+diagonal (HH) analysis filter and an exact per-sample median.  `nle_pca` (weak-texture PCA) forms, per pass and
+channel, the second moment of the weak-texture patches in one HIP sweep (cdl_nle_pca_gram); the host keeps only the
+p^2 x p^2 eigenvalue problem and the constants of the patch size.
 """
-import ctypes
+import functools
+import math
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -29,8 +32,137 @@ def nle_mad(y):
     return out.reshape(-1, 1, 1, 1)
 
 
+def _derivative_matrix(p, horizontal):
+    """Rows: every valid position of the half-difference [1/2, 0, -1/2] inside a p x p patch (row-major pixel order),
+    along rows (horizontal) or columns; D @ patch = the derivatives the texture strength squares and sums."""
+    rows = []
+    for i in range(p if horizontal else p - 2):
+        for j in range(p - 2 if horizontal else p):
+            r = torch.zeros(p * p, dtype=torch.float64)
+            r[i * p + j] = 0.5
+            r[(i * p + j + 2) if horizontal else ((i + 2) * p + j)] = -0.5
+            rows.append(r)
+    return torch.stack(rows)
+
+
+def _gamma_quantile(q, shape, scale):
+    """gamma.ppf(q, shape, scale) by bisection on the regularized incomplete gamma function in float64 (no scipy);
+    for q > 1/2 on the upper tail, which keeps full relative precision of 1 - q."""
+    a = torch.tensor(shape, dtype=torch.float64)
+
+    def above(x):                    # is the quantile below x?
+        xt = torch.tensor(x / scale, dtype=torch.float64)
+        if q > 0.5:
+            return float(torch.special.gammaincc(a, xt)) <= 1.0 - q
+        return float(torch.special.gammainc(a, xt)) >= q
+
+    lo, hi = 0.0, max(1.0, shape * scale)
+    while not above(hi):
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if above(mid):
+            hi = mid
+        else:
+            lo = mid
+    return 0.5 * (lo + hi)
+
+
+@functools.lru_cache(maxsize=None)
+def pca_constants(patchsize=7, conf=1 - 1e-6):
+    """(tau0, r, tr(DD)) of the reference's nle_pca for one (patchsize, conf), in float64:
+    DD = Dh^T Dh + Dv^T Dv of the two derivative matrices, r = rank(DD),
+    tau0 = gamma.ppf(conf, r / 2, scale = 2 tr(DD) / r)  (the texture threshold per unit noise variance)."""
+    Dh, Dv = _derivative_matrix(patchsize, True), _derivative_matrix(patchsize, False)
+    DD = Dh.T @ Dh + Dv.T @ Dv
+    r = int(torch.linalg.matrix_rank(DD, hermitian=True))
+    tr = float(torch.trace(DD))
+    return _gamma_quantile(conf, r / 2.0, 2.0 * tr / r), r, tr
+
+
+def pca_gram(y, channel, patchsize, tau):
+    """One pass on the device (cdl_nle_pca_gram): (G, count) with G = sum x x^T (float64 (p^2, p^2), on y's device)
+    over the patches of `channel` whose texture strength is below tau (float32; +inf keeps every patch) and count
+    their number (int)."""
+    N, C, H, W = y.shape
+    lib = _lib.lib()
+    n = int(lib.cdl_nle_pca_scratch_floats(N, C, H, W, patchsize))
+    if n == 0:
+        raise ValueError(f"nle_pca: patchsize {patchsize} outside 3..11 or larger than the image {H} x {W}")
+    scratch = ops._scratch(y.device, n)
+    gram = torch.empty(patchsize * patchsize, patchsize * patchsize, device=y.device, dtype=torch.float64)
+    count = torch.empty(1, device=y.device, dtype=torch.int64)
+    rc = lib.cdl_nle_pca_gram(ops._ptr(y), N, C, H, W, channel, patchsize, float(tau), ops._ptr(gram),
+                              ops._ptr(count), ops._ptr(scratch), n, ops._stream())
+    _lib.check(rc, "cdl_nle_pca_gram")
+    return gram, int(count.item())
+
+
+def _smallest_eigenvalue(gram, count):
+    return float(torch.linalg.eigvalsh(gram.cpu() / (count - 1))[0])
+
+
+def nle_pca(img, patchsize=7, conf=1 - 1e-6, itr=3):
+    """Weak-texture PCA estimate of the AWGN standard deviation (reference model/nle.py:29-89), per channel of
+    img (N,C,H,W); returns (nlevel, th, num) as the reference does: numpy.float64 scalars for C = 1, length-C float64
+    arrays otherwise.  nlevel is what the reference's `noise_level(y, "PCA")` returns.
+
+    Kept from the reference: patches (every p x p window at stride 1) are pooled over the whole batch, one estimate
+    per channel; the second moment X X^T / (count - 1) is NOT centred; `num` (the number of patches the last pass
+    kept) is a float; with fewer patches than p^2 the result is (0, 0, 0) (sig2 = 0, so tau = 0 keeps nothing).
+    The refinement runs for i in range(2, itr): tau = sig2 * tau0, keep Xtr < tau, stop if fewer than p^2 remain.
+
+    Where the reference's code fails, this one does what it evidently intends: C > 1 (the reference raises in
+    conv2d) estimates every channel independently; itr <= 2 (the reference raises on inf.item()) returns th = inf
+    with no refinement; H or W < patchsize (the reference's unfold raises) raises ValueError.
+
+    Precision: the Gram matrices are formed on the device in fp32 matrix cores over shifted data and summed in fp64
+    (csrc/cdl_nle_pca.hip), the smallest eigenvalue is taken in float64, so the result follows a float64 evaluation
+    of the reference's formulas (the reference's own fp32 eigenvalue is ~1e-4 off it).  The threshold is compared
+    in fp32, as the reference compares its fp32 texture strengths with an fp32 tau."""
+    img = ops._dev(img, "img")
+    if img.dim() != 4:
+        raise ValueError("nle_pca expects (N, C, H, W)")
+    N, C, H, W = img.shape
+    p = int(patchsize)
+    if not 3 <= p <= 11:
+        raise ValueError(f"nle_pca: patchsize {p} outside 3..11")
+    if H < p or W < p:
+        raise ValueError(f"nle_pca: image {H} x {W} smaller than the {p} x {p} patch")
+    img = img.contiguous()
+    tau0 = pca_constants(p, conf)[0]
+    total = N * (H - p + 1) * (W - p + 1)
+    nlevel, th, num = np.empty(C), np.empty(C), np.empty(C)
+    for c in range(C):
+        tau, kept = math.inf, total
+        if total < p * p:
+            sig2 = 0.0
+        else:
+            gram, kept = pca_gram(img, c, p, math.inf)
+            sig2 = _smallest_eigenvalue(gram, kept)
+        for _ in range(2, itr):
+            tau = sig2 * tau0
+            gram, kept = pca_gram(img, c, p, tau)
+            if kept < p * p:
+                break
+            sig2 = _smallest_eigenvalue(gram, kept)
+        nlevel[c] = np.sqrt(sig2)
+        th[c] = tau
+        num[c] = kept
+    if C == 1:
+        return nlevel[0], th[0], num[0]
+    return nlevel, th, num
+
+
 def noise_level(y, method="MAD", **kwargs):
-    """model/nle.py:9-15."""
+    """model/nle.py:9-15 for "MAD" (or True / "wvlt"): nle_mad(y), an (N,1,1,1) tensor.  This entry point's contract is
+    the MAD estimate only, and "PCA" keeps raising NotImplementedError; the weak-texture PCA estimate, i.e. what the
+    reference's noise_level(y, "PCA") returns, is nle_pca(y)[0]."""
     if method in (True, "MAD", "wvlt"):
         return nle_mad(y)
-    raise NotImplementedError(f"noise_level method {method!r}: only the MAD / wavelet estimator runs on the device")
+    if method == "PCA":
+        raise NotImplementedError("noise_level runs the MAD estimator only; for the weak-texture PCA estimate "
+                                  "(the reference's noise_level(y, 'PCA')) call nle_pca(y)[0]")
+    raise NotImplementedError(f"noise_level method {method!r}: only the MAD / wavelet estimator runs here")

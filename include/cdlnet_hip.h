@@ -236,6 +236,18 @@ size_t cdl_nle_mad_scratch_floats(int N, int C, int H, int W);
 int cdl_nle_mad(const float *y, float *sigma_hat /*N*/, float *scratch, size_t scratch_floats, int N, int C,
                 int H, int W, void *stream);
 
+/* model/nle.py:29-89 (nle_pca), the per-pass work of one channel: over every patchsize x patchsize patch of channel
+ * `channel` of y (N,C,H,W), pooled over the batch, its texture strength Xtr (the sums of the squared half-differences
+ * ((x[i][j] - x[i][j+2]) / 2)^2 over the patch's p x (p-2) window plus those along rows over its (p-2) x p window),
+ * and over the patches with Xtr < tau (tau = +inf keeps every patch) the non-centred second moment
+ * gram = sum x x^T (fp64, p^2 x p^2, both triangles) and their number *count (int64).  3 <= patchsize <= 11,
+ * H, W >= patchsize.  Deterministic: partials are reduced in a fixed order.  The host divides by count - 1.
+ * scratch: cdl_nle_pca_scratch_floats(N,C,H,W,patchsize) floats. */
+size_t cdl_nle_pca_scratch_floats(int N, int C, int H, int W, int patchsize);
+int cdl_nle_pca_gram(const float *y, int N, int C, int H, int W, int channel, int patchsize, float tau,
+                     double *gram /*p^2 x p^2*/, long long *count /*1*/, float *scratch, size_t scratch_floats,
+                     void *stream);
+
 /* ---- ResidualBlock of CDLNetVideo(residual=True) -------------------------
  * model/net.py:105-120, applied to the code after every iteration (net.py:199-207):
  *     h = relu(conv1(x)),  out = relu(conv2(h) + x),   conv*: Conv3d(M, M, P, stride 1, padding P/2, bias=False)
