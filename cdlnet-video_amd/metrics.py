@@ -1,0 +1,213 @@
+"""SSIM on the device: the evaluation metric and the differentiable loss term of the reference's pipeline.
+
+* `ssim(X, Y, ...)`: pytorch_msssim's `ssim` for (N, C, H, W), differentiable in X, Y and data_range (the SSIM
+  term of loss.py's CombinedLossWithSSIM is built on it);
+* `ssim_frames(output, target)`: that term for (N, C, D, H, W) clips, every frame in one launch;
+* `structural_similarity(x, y, ...)`: skimage's `structural_similarity` (analyzemri.py's metric), per plane;
+* `video_ssim(video, denoised)`: analyzemri.py's `ssim_total / frame_count` for one batch, one host sync.
+
+The per-plane means of the SSIM map and their reverse sweep run in libcdlnet_hip.so (`cdl_ssim_fwd` /
+`cdl_ssim_bwd`, csrc/cdl_ssim.hip).  The host builds the 1-D window and passes it by value; data_range is a device
+tensor of one value per plane, so nothing on these paths copies from the device or synchronises.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _lib, ops
+
+_TAPS_MAX = 15
+
+
+def _gaussian_window(win_size, win_sigma):
+    """pytorch_msssim's _fspecial_gauss_1d: exp(-(i - win_size // 2)^2 / (2 sigma^2)), normalised (in float32, as
+    pytorch_msssim builds it)."""
+    coords = torch.arange(win_size, dtype=torch.float32) - win_size // 2
+    g = torch.exp(-(coords ** 2) / (2 * win_sigma ** 2))
+    return (g / g.sum()).tolist()
+
+
+def _check_window(win_size, H, W):
+    if win_size % 2 != 1 or win_size < 3:
+        raise ValueError(f"win_size must be odd and at least 3, got {win_size}")
+    if win_size > _TAPS_MAX:
+        raise ValueError(f"win_size {win_size}: the device kernel takes windows of up to {_TAPS_MAX} taps")
+    if H < win_size or W < win_size:
+        raise ValueError(f"win_size {win_size} exceeds the image extent {H} x {W}")
+
+
+def _window_arg(win):
+    return (ctypes.c_float * len(win))(*win)
+
+
+def _planes_range(data_range, P, like):
+    """data_range (number or tensor broadcastable to the P planes) -> contiguous float32 device tensor (P,)."""
+    if torch.is_tensor(data_range):
+        r = data_range.to(device=like.device, dtype=torch.float32)
+        return r.reshape(()).expand(P).contiguous() if r.numel() == 1 else r.reshape(P).contiguous()
+    return torch.full((P,), float(data_range), device=like.device, dtype=torch.float32)
+
+
+class _SSIMPlanes(torch.autograd.Function):
+    """(x, y, R) of P planes (P, H, W), R (P,) -> per-plane mean of the SSIM map (P,)."""
+
+    @staticmethod
+    def forward(ctx, x, y, R, win, K1, K2, kappa):
+        P, H, W = x.shape
+        if R.shape != (P,):
+            raise ValueError(f"data_range: expected one value per plane, shape ({P},), got {tuple(R.shape)}")
+        R = R.contiguous()          # the kernels read R[plane]: an expanded (stride-0) view must not reach them
+        lib = _lib.lib()
+        n = int(lib.cdl_ssim_scratch_floats(P, H, W, len(win)))
+        scratch = ops._scratch(x.device, n)
+        out = torch.empty(P, device=x.device, dtype=torch.float32)
+        rc = lib.cdl_ssim_fwd(ops._ptr(x), ops._ptr(y), P, H, W, _window_arg(win), len(win), K1, K2, kappa,
+                              ops._ptr(R), ops._ptr(out), None, ops._ptr(scratch), n, ops._stream())
+        _lib.check(rc, "cdl_ssim_fwd")
+        ctx.save_for_backward(x, y, R)
+        ctx.args = (win, K1, K2, kappa)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, R = ctx.saved_tensors
+        win, K1, K2, kappa = ctx.args
+        nx, ny, nr = ctx.needs_input_grad[:3]
+        if not (nx or ny or nr):
+            return (None,) * 7
+        P, H, W = x.shape
+        g = g.to(torch.float32).contiguous()
+        dx = torch.empty_like(x) if nx else None
+        dy = torch.empty_like(y) if ny else None
+        dr = torch.empty(P, device=x.device, dtype=torch.float32) if nr else None
+        lib = _lib.lib()
+        n = int(lib.cdl_ssim_scratch_floats(P, H, W, len(win)))
+        scratch = ops._scratch(x.device, n)
+        rc = lib.cdl_ssim_bwd(ops._ptr(x), ops._ptr(y), P, H, W, _window_arg(win), len(win), K1, K2, kappa,
+                              ops._ptr(R), ops._ptr(g), ops._ptr(dx), ops._ptr(dy), ops._ptr(dr),
+                              ops._ptr(scratch), n, ops._stream())
+        _lib.check(rc, "cdl_ssim_bwd")
+        return dx, dy, dr, None, None, None, None
+
+
+def _plane_ssim(x, y, R, win, K1, K2, kappa):
+    """x, y (..., H, W) device float32, R (P,) -> per-plane SSIM means shaped like the leading dims."""
+    lead, (H, W) = x.shape[:-2], x.shape[-2:]
+    P = math.prod(lead)
+    with torch.cuda.device(x.device):
+        out = _SSIMPlanes.apply(x.reshape(P, H, W), y.reshape(P, H, W), R, win, float(K1), float(K2), float(kappa))
+    return out.reshape(lead)
+
+
+def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, K=(0.01, 0.03),
+         nonnegative_ssim=False):
+    """pytorch_msssim.ssim for 4-D (N, C, H, W) input: Gaussian window (win_size, win_sigma), valid filtering.
+
+    Returns ssim_per_channel.mean(), or .mean(1) per image when size_average=False.  Differentiable in X, Y and
+    data_range (a python number or a tensor, e.g. `out.max() - out.min()`).
+
+    Deviations from pytorch_msssim, both raised before any device work:
+    * a spatial side smaller than the window raises ValueError (pytorch_msssim warns and skips that axis);
+    * 5-D input raises NotImplementedError (pytorch_msssim would switch to a 3-D window): per-frame SSIM of a clip is
+      `ssim_frames`.
+    """
+    if not (torch.is_tensor(X) and torch.is_tensor(Y)):
+        raise TypeError("ssim: expected tensors")
+    if X.shape != Y.shape:
+        raise ValueError(f"input images should have the same dimensions, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if X.dim() == 5:
+        raise NotImplementedError("ssim takes (N, C, H, W); pytorch_msssim's 3-D window for 5-D input is not "
+                                  "implemented -- for the per-frame SSIM of (N, C, D, H, W) clips use ssim_frames")
+    if X.dim() != 4:
+        raise ValueError(f"expected 4-D (N, C, H, W) input, got {tuple(X.shape)}")
+    _check_window(win_size, X.shape[-2], X.shape[-1])
+    X, Y = ops._dev(X, "X"), ops._dev(Y, "Y")
+    N, C = X.shape[:2]
+    win = _gaussian_window(win_size, win_sigma)
+    R = _planes_range(data_range, N * C, X)
+    per_channel = _plane_ssim(X, Y, R, win, K[0], K[1], 1.0)
+    if nonnegative_ssim:
+        per_channel = torch.relu(per_channel)
+    return per_channel.mean() if size_average else per_channel.mean(1)
+
+
+def ssim_frames(output, target, data_range=None):
+    """The SSIM term of loss.py's CombinedLossWithSSIM for (N, C, D, H, W) clips:
+    mean_t (1 - ssim(output[:, :, t], target[:, :, t], data_range=R_t)), pytorch_msssim's defaults otherwise.
+
+    data_range=None is the reference's R_t = output[:, :, t].max() - output[:, :, t].min() (over N and C, output only;
+    the gradient reaches the max / min elements as torch's max() / min() send it, split evenly among ties).  A number
+    or a tensor broadcastable to (D,) is used as given.
+
+    The reference repeats every frame to three channels first (`repeat(1, 3, 1, 1)`).  That changes nothing: the
+    three copies have the same SSIM, so their mean is the one-channel value and the same max / min; in the reverse
+    pass each copy receives a third of the gradient and repeat's backward adds the three thirds.  All frames run in
+    one forward and one backward launch, with no host synchronisation.
+    """
+    if not (torch.is_tensor(output) and torch.is_tensor(target)):
+        raise TypeError("ssim_frames: expected tensors")
+    if output.shape != target.shape:
+        raise ValueError(f"input clips should have the same dimensions, got {tuple(output.shape)} and "
+                         f"{tuple(target.shape)}")
+    if output.dim() != 5:
+        raise ValueError(f"ssim_frames expects (N, C, D, H, W), got {tuple(output.shape)}")
+    _check_window(11, output.shape[-2], output.shape[-1])
+    output, target = ops._dev(output, "output"), ops._dev(target, "target")
+    N, C, D = output.shape[:3]
+    if data_range is None:
+        R_t = output.amax(dim=(0, 1, 3, 4)) - output.amin(dim=(0, 1, 3, 4))
+    elif torch.is_tensor(data_range):
+        r = data_range.to(device=output.device, dtype=torch.float32)
+        R_t = r.reshape(()).expand(D) if r.numel() == 1 else r.reshape(D)
+    else:
+        R_t = torch.full((D,), float(data_range), device=output.device, dtype=torch.float32)
+    R = R_t.reshape(1, 1, D).expand(N, C, D).contiguous().reshape(-1)
+    per_plane = _plane_ssim(output, target, R, _gaussian_window(11, 1.5), 0.01, 0.03, 1.0)   # (N, C, D)
+    ssim_t = per_plane.mean(dim=(0, 1))
+    return (1 - ssim_t).mean()
+
+
+def structural_similarity(x, y, data_range=1.0, win_size=7, K1=0.01, K2=0.03, channel_axis=None):
+    """skimage.metrics.structural_similarity with its defaults (uniform window, use_sample_covariance=True, so
+    kappa = n / (n - 1) with n = win_size^2), for every trailing (H, W) plane of x and y at once.
+
+    skimage filters with reflect padding and then crops (win_size - 1) // 2 from every side before the mean: what
+    remains are exactly the positions a valid filter produces, so the border mode never matters and the kernel filters
+    "valid".  Returns a tensor shaped like the leading dims (0-d for one (H, W) image).  `channel_axis` (an axis of the
+    leading dims) averages over it, as skimage does for a colour image.  Forward only, no gradient.
+    """
+    if not (torch.is_tensor(x) and torch.is_tensor(y)):
+        raise TypeError("structural_similarity: expected tensors")
+    if x.shape != y.shape:
+        raise ValueError(f"input images must have the same dimensions, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.dim() < 2:
+        raise ValueError("structural_similarity expects (..., H, W)")
+    if win_size % 2 != 1:
+        raise ValueError("Window size must be odd.")
+    if win_size > min(x.shape[-2:]):
+        raise ValueError(f"win_size {win_size} exceeds the image extent {tuple(x.shape[-2:])}")
+    _check_window(win_size, x.shape[-2], x.shape[-1])
+    if channel_axis is not None and not (-(x.dim() - 2) <= channel_axis < x.dim() - 2):
+        raise ValueError(f"channel_axis {channel_axis} is not a leading axis of {tuple(x.shape)}")
+    x, y = ops._dev(x, "x"), ops._dev(y, "y")
+    npx = win_size * win_size
+    lead = x.shape[:-2]
+    R = _planes_range(data_range, math.prod(lead), x)
+    with torch.no_grad():
+        out = _plane_ssim(x, y, R, [1.0 / win_size] * win_size, K1, K2, npx / (npx - 1.0))
+    if channel_axis is not None:
+        out = out.mean(dim=channel_axis)
+    return out
+
+
+def video_ssim(video, denoised, data_range=1.0):
+    """analyzemri.py's SSIM for one batch (B, C, D, H, W): skimage's structural_similarity of every (b, d) frame,
+    averaged over its channels for C > 1, summed and divided by the frame count B * D.  One launch and one host
+    sync for the whole batch (the reference copies every frame to the host)."""
+    if not (torch.is_tensor(video) and torch.is_tensor(denoised)):
+        raise TypeError("video_ssim: expected tensors")
+    if video.dim() != 5:
+        raise ValueError(f"video_ssim expects (B, C, D, H, W), got {tuple(video.shape)}")
+    per_plane = structural_similarity(denoised, video, data_range=data_range)       # (B, C, D)
+    return float(per_plane.mean(dim=1).mean())

@@ -248,6 +248,27 @@ int cdl_nle_pca_gram(const float *y, int N, int C, int H, int W, int channel, in
                      double *gram /*p^2 x p^2*/, long long *count /*1*/, float *scratch, size_t scratch_floats,
                      void *stream);
 
+/* ---- SSIM (the evaluation metric of analyzemri.py and the loss term of loss.py's CombinedLossWithSSIM) ----------
+ * P independent contiguous H x W planes of x and y; the window is `taps` host-side 1-D weights `win` (odd, 3..15,
+ * H, W >= taps) that sum to 1 (within 1e-5; otherwise CDL_EINVAL: the kernels centre each tile on one pixel, which is
+ * exact only for a normalised window), applied along both axes with valid filtering: Ho x Wo = (H - taps + 1) x
+ * (W - taps + 1) positions.
+ * Per position, with the window moments of x and y, sx = kappa (E[x^2] - E[x]^2) (and sy, sxy alike),
+ * C1 = (K1 R)^2, C2 = (K2 R)^2, R = data_range[plane] (device, P floats):
+ *     cs = (2 sxy + C2) / (sx + sy + C2),  S = (2 mx my + C1) / (mx^2 + my^2 + C1) * cs.
+ * cdl_ssim_fwd writes the per-plane means of S and cs over the positions (cs nullable).  cdl_ssim_bwd takes the
+ * per-plane upstream gradients g_ssim of those SSIM means and writes dx, dy (each nullable) and the per-plane
+ * dL/dR (nullable); at least one of the three.  Both deterministic: fixed-order fp64 reductions, no atomics.
+ * scratch: cdl_ssim_scratch_floats(P,H,W,taps) floats, shared by both (0: shape or taps not supported). */
+size_t cdl_ssim_scratch_floats(int P, int H, int W, int taps);
+int cdl_ssim_fwd(const float *x, const float *y, int P, int H, int W, const float *win /*host, taps*/, int taps,
+                 float K1, float K2, float kappa, const float *data_range /*P*/, float *ssim /*P*/,
+                 float *cs /*P, nullable*/, float *scratch, size_t scratch_floats, void *stream);
+int cdl_ssim_bwd(const float *x, const float *y, int P, int H, int W, const float *win /*host, taps*/, int taps,
+                 float K1, float K2, float kappa, const float *data_range /*P*/, const float *g_ssim /*P*/,
+                 float *dx /*nullable*/, float *dy /*nullable*/, float *d_range /*P, nullable*/, float *scratch,
+                 size_t scratch_floats, void *stream);
+
 /* ---- ResidualBlock of CDLNetVideo(residual=True) -------------------------
  * model/net.py:105-120, applied to the code after every iteration (net.py:199-207):
  *     h = relu(conv1(x)),  out = relu(conv2(h) + x),   conv*: Conv3d(M, M, P, stride 1, padding P/2, bias=False)
