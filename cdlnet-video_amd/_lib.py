@@ -47,14 +47,14 @@ SIGNATURES = {
     "cdl_synthesis_ws": [_G, _P, _P, _P, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_wgrad": [_G, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
     "cdl_wgrad_pair": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
-    "cdl_tau_grad": [_G, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_tau_grad_gate": [_G, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_tau_grad": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_tau_grad_gate": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_analysis_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
-    "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_analysis_prox_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P],
-    "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P],
+    "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P],
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -77,36 +77,25 @@ SIGNATURES = {
     "cdl_fused2d_support_map": [_G, _P, _P, _P],
     "cdl_fused2d_timing": [_I],
     "cdl_fused2d_timing_read": [ctypes.POINTER(ctypes.c_double), _IP],
-    "cdl_fused2d_assemble": [_G, _P, _P, _P, _F, _P, _P],
-    "cdl_fused2d_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "cdl_fused2d_stage_bwd_da": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _I, _P],
-    "cdl_fused2d_dtau_reduce": [_G, _P, _P, _P, _P, _P],
+    "cdl_fused2d_assemble": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
+    "cdl_fused2d_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _I, _P],
+    "cdl_fused2d_dtau_reduce": [_G, _P, _P, _P, _P, _P, _P],
     "cdl_fused2d_wgrad": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, _I, _P],
     "cdl_fused2d_forward": [_G, _I] + [_P] * 11 + [_I, _P],
-    "cdl_fused2d_backward": [_G, _I] + [_P] * 20 + [_I, _P],
+    "cdl_fused2d_backward": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P],
     "cdl_fusedg_supported": [_G],
     "cdl_fusedg_code_layout": [_G, _I],
     "cdl_fusedg_set_timeline": [_P],
     "cdl_fusedg_prep": [_G, _P, _P, _P, _P],
     "cdl_fusedg_iter_fwd": [_G, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P],
     "cdl_fusedg_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "cdl_fusedg_assemble": [_G, _P, _P, _P, _F, _P, _P],
-    "cdl_fusedg_dtau_reduce": [_G, _P, _P, _P, _P, _P],
+    "cdl_fusedg_assemble": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
+    "cdl_fusedg_dtau_reduce": [_G, _P, _P, _P, _P, _P, _P],
     "cdl_fusedg_forward": [_G, _I] + [_P] * 11 + [_I, _P],
-    "cdl_fusedg_backward": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P],
-    # gradients with respect to the data (y, sigma): the _x forms take dyp / dtau (nullable) after the old arguments
+    "cdl_fusedg_backward": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P, _P, _P],
+    # gradients with respect to the data (y, sigma)
     "cdl_preprocess_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _IP, _P],
-    "cdl_tau_grad_x": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_tau_grad_gate_x": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_dyp_split": [_G, _P, _P, _P, _I, _I, _P],
-    "cdl_analysis_rev_ws_x": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
-    "cdl_ista_backward_x": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P],
-    "cdl_fused2d_assemble_acc": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
-    "cdl_fused2d_dtau_reduce_x": [_G, _P, _P, _P, _P, _P, _P],
-    "cdl_fused2d_backward_x": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P],
-    "cdl_fusedg_assemble_acc": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
-    "cdl_fusedg_dtau_reduce_x": [_G, _P, _P, _P, _P, _P, _P],
-    "cdl_fusedg_backward_x": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P, _P, _P],
 }
 SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G], "cdl_fusedg_patch_floats": [_G], "cdl_fusedg_tiles": [_G],
                 "cdl_fusedg_map_words": [_G], "cdl_fused2d_frag_bytes": [_I], "cdl_fused2d_patch_floats": [_G], "cdl_fused2d_code_bytes": [_G, _I],

@@ -47,9 +47,6 @@
 #ifdef CDL_F2D_WY4
 #define CDL_WY 4
 #define cdl_fused2d_assemble cdl_fused2d_assemble_wy4
-#define cdl_fused2d_assemble_acc cdl_fused2d_assemble_acc_wy4
-#define cdl_fused2d_backward_x cdl_fused2d_backward_x_wy4
-#define cdl_fused2d_dtau_reduce_x cdl_fused2d_dtau_reduce_x_wy4
 #define cdl_fused2d_backward cdl_fused2d_backward_wy4
 #define cdl_fused2d_code_bytes cdl_fused2d_code_bytes_wy4
 #define cdl_fused2d_dtau_reduce cdl_fused2d_dtau_reduce_wy4
@@ -60,7 +57,6 @@
 #define cdl_fused2d_patch_floats cdl_fused2d_patch_floats_wy4
 #define cdl_fused2d_prep cdl_fused2d_prep_wy4
 #define cdl_fused2d_stage_bwd cdl_fused2d_stage_bwd_wy4
-#define cdl_fused2d_stage_bwd_da cdl_fused2d_stage_bwd_da_wy4
 #define cdl_fused2d_support_map cdl_fused2d_support_map_wy4
 #define cdl_fused2d_supported cdl_fused2d_supported_wy4
 #define cdl_fused2d_tiles cdl_fused2d_tiles_wy4
@@ -1660,38 +1656,23 @@ static int stage_bwd(const cdl_geom *g, const float *thin, const float *base, co
 }
 
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
-                          const void *frags, float *du_out, float *patches, float *dtau_partial,
-                          int do_synth, int precision, void *stream)
+                          const void *frags, float *du_out, float *patches, float *dtau_partial, int do_synth,
+                          const float *r2, float alpha, float *dA, float *workspace, int precision, void *stream)
 {
-    return stage_bwd(g, thin, base, map, frags, du_out, patches, dtau_partial, do_synth, precision, nullptr, 0.0f, nullptr,
-                     nullptr, stream);
-}
-
-int cdl_fused2d_stage_bwd_da(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
-                             const void *frags, float *du_out, float *patches, float *dtau_partial, int do_synth,
-                             const float *r2, float alpha, float *dA, float *workspace, int precision, void *stream)
-{
-    if (!r2 || !dA || !workspace) return CDL_EINVAL;
+    if (!r2 != !dA || !r2 != !workspace) return CDL_EINVAL;     // the filter gradient: all three set, or none
     return stage_bwd(g, thin, base, map, frags, du_out, patches, dtau_partial, do_synth, precision, r2, alpha, dA, workspace,
                      stream);
 }
 
-int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0,
-                            float *dt1, void *stream)
+int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
+                            float *dtau_n, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
-    k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, tiles_x(g) * tiles_y(g), g->M);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-int cdl_fused2d_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
-                              float *dtau_n, void *stream)
-{
-    const int rc = cdl_fused2d_dtau_reduce(g, dtau_partial, c, dt0, dt1, stream);
-    if (rc || !dtau_n) return rc;
     const int per_img = tiles_x(g) * tiles_y(g);             // partial rows: [n][tile][m]
+    k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, per_img, g->M);
+    CDL_LAUNCH_CHECK();
+    if (!dtau_n) return 0;
     return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
 }
 
@@ -1744,8 +1725,8 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
     return 0;
 }
 
-int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
-                             float alpha, float *out, float *acc, int acc_add, void *stream)
+int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
+                         float alpha, float *out, float *acc, int acc_add, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!patches || (!out && !acc)) return CDL_EINVAL;
@@ -1761,13 +1742,6 @@ int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const floa
     }
     CDL_LAUNCH_CHECK();
     return 0;
-}
-
-int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
-                         float alpha, float *out, void *stream)
-{
-    if (!out) return CDL_EINVAL;
-    return cdl_fused2d_assemble_acc(g, patches, mask, sub, alpha, out, nullptr, 0, stream);
 }
 
 }  // extern "C"
@@ -1899,12 +1873,12 @@ static int snake_enabled() { return cdl_opts().fused_snake; }
 int cdl_fused2d_forward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                             const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                             unsigned *const *maps, float *xp, void *frags, float *patches, int precision, void *stream);
-int cdl_fused2d_backward_x_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                               const float *const *wA, const float *const *wB, const float *const *z,
-                               const float *const *r, const unsigned *const *maps, const float *g_xp, const float *g_z,
-                               float *const *dA, float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
-                               float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
-                               float *dtau, void *stream);
+int cdl_fused2d_backward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                             const float *const *wA, const float *const *wB, const float *const *z,
+                             const float *const *r, const unsigned *const *maps, const float *g_xp, const float *g_z,
+                             float *const *dA, float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
+                             float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
+                             float *dtau, void *stream);
 #endif
 
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
@@ -1939,23 +1913,23 @@ int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *
         }
         if (rc) return rc;
         if (k < K - 1) {
-            rc = cdl_fused2d_assemble(g, patches, mask, yp, 1.0f, r[k], stream);
+            rc = cdl_fused2d_assemble(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
             thin = r[k];
         } else {
-            rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, xp, stream);
+            rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
         }
         if (rc) return rc;
     }
     return 0;
 }
 
-int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
                          const float *const *wA, const float *const *wB, const float *const *z,
                          const float *const *r, const unsigned *const *maps, const float *g_xp,
                          const float *g_z, float *const *dA,
                          float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
                          float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
-                           float *dtau, void *stream)
+                         float *dtau, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
@@ -1968,8 +1942,8 @@ int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const floa
     const int L = f.lin;
 #ifndef CDL_F2D_WY4
     if (L == LAY_BLK16)
-        return cdl_fused2d_backward_x_wy4(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
-                                          patches, dtau_partial, wgrad_ws, precision, dyp, dtau, stream);
+        return cdl_fused2d_backward_wy4(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
+                                        patches, dtau_partial, wgrad_ws, precision, dyp, dtau, stream);
 #endif
     // the forward's last launch ran in direction (K-1)&1: stages take that one, filter gradients the other
     const int sdir = snake_enabled() ? (((K - 1) & 1) ? CDL_TILES_REVERSED : 0) : 0;
@@ -1996,16 +1970,16 @@ int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const floa
                            ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], wgrad_ws, stream);
         }
         if (rc) return rc;
-        rc = cdl_fused2d_dtau_reduce_x(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
-                                       dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
+        rc = cdl_fused2d_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
+                                     dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
         if (rc) return rc;
         if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
-            rc = cdl_fused2d_assemble_acc(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
+            rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
             if (rc) return rc;
         }
         if (k >= 1) {
             // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
-            rc = cdl_fused2d_assemble_acc(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
+            rc = cdl_fused2d_assemble(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
             if (rc) return rc;
             {
                 TimingScope ts(2, S(stream));
@@ -2023,17 +1997,6 @@ int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const floa
         base = duk;
     }
     return 0;
-}
-
-int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                         const float *const *wA, const float *const *wB, const float *const *z,
-                         const float *const *r, const unsigned *const *maps, const float *g_xp,
-                         const float *g_z, float *const *dA,
-                         float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
-                         float *patches, float *dtau_partial, float *wgrad_ws, int precision, void *stream)
-{
-    return cdl_fused2d_backward_x(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
-                                  patches, dtau_partial, wgrad_ws, precision, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1148,8 +1148,8 @@ int cdl_fusedg_stage_bwd(const cdl_geom *g, const float *thin, const float *base
     return dispatch(g, p, pl, MODE_BWD, precision, S(stream));
 }
 
-int cdl_fusedg_assemble_acc(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
-                            float *out, float *acc, int acc_add, void *stream)
+int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
+                        float *out, float *acc, int acc_add, void *stream)
 {
     Route rt;
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
@@ -1172,15 +1172,8 @@ int cdl_fusedg_assemble_acc(const cdl_geom *g, const float *patches, const float
     return 0;
 }
 
-int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
-                        float *out, void *stream)
-{
-    if (!out) return CDL_EINVAL;
-    return cdl_fusedg_assemble_acc(g, patches, mask, sub, alpha, out, nullptr, 0, stream);
-}
-
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
-                           void *stream)
+                           float *dtau_n, void *stream)
 {
     Route rt;
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
@@ -1189,18 +1182,7 @@ int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const f
                         : rt.kind == 2 ? g->D * rt.gp.nsx * rt.gp.nsy : g->D * rt.pl.tilesX * rt.pl.tilesY;
     k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, per_img, g->M);
     CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-int cdl_fusedg_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
-                             float *dtau_n, void *stream)
-{
-    const int rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt0, dt1, stream);
-    if (rc || !dtau_n) return rc;
-    Route rt;
-    route_for(g, &rt);
-    const int per_img = rt.kind == 1 ? rt.sp.nsx * rt.sp.nsy
-                        : rt.kind == 2 ? g->D * rt.gp.nsx * rt.gp.nsy : g->D * rt.pl.tilesX * rt.pl.tilesY;
+    if (!dtau_n) return 0;
     // partial rows: [n][tile][m], as k_dtau_reduce_g reads them
     return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
 }
@@ -1240,10 +1222,10 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
                                  maps ? maps[k] : nullptr, flags, stream);
         if (rc) return rc;
         if (k < K - 1) {
-            rc = cdl_fusedg_assemble(g, patches, mask, yp, 1.0f, r[k], stream);
+            rc = cdl_fusedg_assemble(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
             thin = r[k];
         } else {
-            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, xp, stream);
+            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
         }
         if (rc) return rc;
     }
@@ -1253,12 +1235,12 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
 /* Reverse sweep: the fused stage produces du_k (one fat write), the threshold partials and the patches of q_k; the
  * filter gradients dA_k = -du_k (x) r_k and dB_k = z_k (x) q_k come from the shape-generic cdl_wgrad (its matrix-core
  * kernel where the shape has one).  wgrad_ws: cdl_wgrad_workspace_floats(g) floats. */
-int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
                         const float *const *wA, const float *const *wB, const float *const *z, const float *const *r,
                         const unsigned *const *maps, const float *g_xp, const float *g_z, float *const *dA,
                         float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
                         float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, float *dyp,
-                          float *dtau, void *stream)
+                        float *dtau, void *stream)
 {
     Route rt;
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
@@ -1294,16 +1276,16 @@ int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float
                                   bprec | (((K - 1 - k) & 1) ? (sdir ^ CDL_TILES_REVERSED) : sdir) |
                                       CDL_LAYOUT_IN(k == K - 1 ? CDL_LAY_NCHW : lay) | CDL_LAYOUT_OUT(lay), stream);
         if (rc) return rc;
-        rc = cdl_fusedg_dtau_reduce_x(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
-                                      dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
+        rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
+                                    dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
         if (rc) return rc;
         if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
-            rc = cdl_fusedg_assemble_acc(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
+            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
             if (rc) return rc;
         }
         if (k >= 1) {
             // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
-            rc = cdl_fusedg_assemble_acc(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
+            rc = cdl_fusedg_assemble(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
             if (rc) return rc;
             rc = rsc ? cdl_mfma_wgrad_pair_lay(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], wgrad_ws,
                                                wgrad_ws_floats, 1, stream)
@@ -1317,16 +1299,6 @@ int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float
         base = duk;
     }
     return 0;
-}
-
-int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                        const float *const *wA, const float *const *wB, const float *const *z, const float *const *r,
-                        const unsigned *const *maps, const float *g_xp, const float *g_z, float *const *dA,
-                        float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
-                        float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, void *stream)
-{
-    return cdl_fusedg_backward_x(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
-                                 patches, dtau_partial, wgrad_ws, wgrad_ws_floats, precision, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

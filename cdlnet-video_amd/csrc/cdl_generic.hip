@@ -740,9 +740,9 @@ size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
     return r > n ? r : n;
 }
 
-int cdl_analysis_rev_ws_x(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                         const float *zsup, const float *c, float *dt0, float *dt1, float *dtau_n, float *out,
-                          float *workspace, size_t workspace_floats, void *stream)
+                        float *workspace, size_t workspace_floats, void *stream)
 {
     if (!cdl_geom_ok(g) || !x || !w || !out || !zsup || !dt0 || !dt1 || !workspace) return CDL_EINVAL;
     if (out == zin || out == zsup) return CDL_EINVAL;
@@ -754,14 +754,7 @@ int cdl_analysis_rev_ws_x(const cdl_geom *g, const float *x, const float *w, flo
     }
     const int rc = cdl_analysis_ws(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, stream);
     if (rc) return rc;
-    return cdl_tau_grad_gate_x(g, out, zsup, c, dt0, dt1, dtau_n, workspace, stream);
-}
-
-int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                        const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *workspace,
-                        size_t workspace_floats, void *stream)
-{
-    return cdl_analysis_rev_ws_x(g, x, w, alpha, zin, zsup, c, dt0, dt1, nullptr, out, workspace, workspace_floats, stream);
+    return cdl_tau_grad_gate(g, out, zsup, c, dt0, dt1, dtau_n, workspace, stream);
 }
 
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
@@ -939,7 +932,7 @@ int cdl_wgrad_pair(const cdl_geom *g, const float *z0, const float *x0, float al
 }
 
 static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                         float *scratch, bool gate_inplace, void *stream, float *dtau_n = nullptr)
+                         float *scratch, bool gate_inplace, void *stream, float *dtau_n)
 {
     if (!cdl_geom_ok(g) || !gup || !zout || !dt0 || !dt1 || !scratch) return CDL_EINVAL;
     size_t per_m = (size_t)(g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
@@ -962,26 +955,14 @@ static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const
     return 0;
 }
 
-int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const float *c, float *dt0,
-                 float *dt1, float *scratch, void *stream)
-{
-    return tau_grad_impl(g, const_cast<float *>(gup), zout, c, dt0, dt1, scratch, false, stream);
-}
-
-int cdl_tau_grad_gate(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                      float *scratch, void *stream)
-{
-    return tau_grad_impl(g, gup, zout, c, dt0, dt1, scratch, true, stream);
-}
-
-int cdl_tau_grad_x(const cdl_geom *g, const float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                   float *dtau_n, float *scratch, void *stream)
+int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const float *c, float *dt0, float *dt1,
+                 float *dtau_n, float *scratch, void *stream)
 {
     return tau_grad_impl(g, const_cast<float *>(gup), zout, c, dt0, dt1, scratch, false, stream, dtau_n);
 }
 
-int cdl_tau_grad_gate_x(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                        float *dtau_n, float *scratch, void *stream)
+int cdl_tau_grad_gate(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
+                      float *dtau_n, float *scratch, void *stream)
 {
     return tau_grad_impl(g, gup, zout, c, dt0, dt1, scratch, true, stream, dtau_n);
 }

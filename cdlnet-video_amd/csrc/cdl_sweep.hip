@@ -56,13 +56,13 @@ int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mas
     return cdl_synthesis_ws(g, z[K - 1], nullptr, wB[0], 1.0f, nullptr, nullptr, xp, scratch, scratch_floats, stream);
 }
 
-int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                        const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                        const float *gam2, const float *const *wA, const float *const *wB,
-                        const float *const *z, const float *const *r, const float *const *u, const float *g_xp,
-                        const float *g_z, float *const *dA, float *const *dB, float *dt, float *dg1, float *dg2,
-                        float *gz_prev, float *gz_after, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                        size_t scratch_floats, float *dyp, float *dtau, void *stream)
+int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                      const float *z_prev, const float *z_after, const float *lam, const float *gam1,
+                      const float *gam2, const float *const *wA, const float *const *wB,
+                      const float *const *z, const float *const *r, const float *const *u, const float *g_xp,
+                      const float *g_z, float *const *dA, float *const *dB, float *dt, float *dg1, float *dg2,
+                      float *gz_prev, float *gz_after, float *gbuf0, float *gbuf1, float *q, float *scratch,
+                      size_t scratch_floats, float *dyp, float *dtau, void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !yp || !wA || !wB || !z || !dA || !dB || !dt || !gbuf0 || !gbuf1 || !q ||
         !scratch || (K > 1 && !r))
@@ -82,9 +82,9 @@ int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *
     if (g_xp) {
         CDL_TRY(cdl_wgrad(g, z[K - 1], nullptr, g_xp, 1.0f, dB[0], scratch, scratch_floats, stream));
         if (!z_prev) {
-            CDL_TRY(cdl_analysis_rev_ws_x(g, g_xp, wB[0], 1.0f, g_z, z[K - 1], c, dt + (size_t)(K - 1) * 2 * M,
-                                          dt + (size_t)(K - 1) * 2 * M + M, dtau ? dtau + (K - 1) * NM : nullptr, gk,
-                                          scratch, scratch_floats, stream));
+            CDL_TRY(cdl_analysis_rev_ws(g, g_xp, wB[0], 1.0f, g_z, z[K - 1], c, dt + (size_t)(K - 1) * 2 * M,
+                                        dt + (size_t)(K - 1) * 2 * M + M, dtau ? dtau + (K - 1) * NM : nullptr, gk,
+                                        scratch, scratch_floats, stream));
             gated = true;
         } else
         CDL_TRY(cdl_analysis_ws(g, g_xp, wB[0], 1.0f, g_z, nullptr, nullptr, gk, scratch, scratch_floats, stream));   // B_0^T g_xp (+ g_z)
@@ -104,8 +104,8 @@ int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *
         } else if (!gated) {
             // threshold gradients, and gk gated in place by the support of z_{k+1} in the same pass: the synthesis,
             // the filter gradient and the analysis below then read no gate (3 fat reads less per iteration)
-            CDL_TRY(cdl_tau_grad_gate_x(g, gk, z[k], c, dt + k * 2 * M, dt + k * 2 * M + M, dtau ? dtau + k * NM : nullptr,
-                                        scratch, stream));
+            CDL_TRY(cdl_tau_grad_gate(g, gk, z[k], c, dt + k * 2 * M, dt + k * 2 * M + M, dtau ? dtau + k * NM : nullptr,
+                                      scratch, stream));
         }
         if (k == 0) {
             CDL_TRY(cdl_wgrad(g, gk, gate, yp, 1.0f, dA[0], scratch, scratch_floats, stream));
@@ -123,9 +123,9 @@ int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *
         CDL_TRY(cdl_synthesis_ws(g, gk, gate, wA[k], -1.0f, mask, nullptr, q, scratch, scratch_floats, stream));
         CDL_TRY(cdl_wgrad_pair(g, gk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], scratch, scratch_floats, stream));   // gk is gated in place above
         if (!z_prev) {                                       // dL/dz_{k-1}, gated, with the thresholds' gradient of iteration k-1
-            CDL_TRY(cdl_analysis_rev_ws_x(g, q, wB[k], 1.0f, gk, z[k - 1], c, dt + (size_t)(k - 1) * 2 * M,
-                                          dt + (size_t)(k - 1) * 2 * M + M, dtau ? dtau + (k - 1) * NM : nullptr, other,
-                                          scratch, scratch_floats, stream));
+            CDL_TRY(cdl_analysis_rev_ws(g, q, wB[k], 1.0f, gk, z[k - 1], c, dt + (size_t)(k - 1) * 2 * M,
+                                        dt + (size_t)(k - 1) * 2 * M + M, dtau ? dtau + (k - 1) * NM : nullptr, other,
+                                        scratch, scratch_floats, stream));
             gated = true;
         } else
         CDL_TRY(cdl_analysis_ws(g, q, wB[k], 1.0f, gk, gate, nullptr, other, scratch, scratch_floats, stream));
@@ -134,19 +134,6 @@ int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *
         other = t;
     }
     return 0;
-}
-
-int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                      const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                      const float *gam2, const float *const *wA, const float *const *wB,
-                      const float *const *z, const float *const *r, const float *const *u, const float *g_xp,
-                      const float *g_z, float *const *dA, float *const *dB, float *dt, float *dg1, float *dg2,
-                      float *gz_prev, float *gz_after, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                      size_t scratch_floats, void *stream)
-{
-    return cdl_ista_backward_x(g, K, yp, mask, c, z_prev, z_after, lam, gam1, gam2, wA, wB, z, r, u, g_xp, g_z, dA, dB,
-                               dt, dg1, dg2, gz_prev, gz_after, gbuf0, gbuf1, q, scratch, scratch_floats, nullptr,
-                               nullptr, stream);
 }
 
 }  // extern "C"

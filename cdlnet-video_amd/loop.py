@@ -183,7 +183,7 @@ def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, map
 
 
 def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None):
-    """Reverse sweep from one C call (cdl_ista_backward_x; dyp / dtau: see ops.fused_backward)."""
+    """Reverse sweep from one C call (cdl_ista_backward; dyp / dtau: see ops.fused_backward)."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
     return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, dyp=dyp,
@@ -248,10 +248,9 @@ def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z,
                                  k >= 1 or dyp is not None, prec, lay_in="nchw" if k == K - 1 else layout, lay_out=layout)
         ops.fused_dtau_reduce(g, dtp, c, dt[k], dtau[k] if dtau is not None else None)
         if k == 0 and dyp is not None:                              # u_0 = A_0 yp
-            ops.fused_assemble_acc(g, patches, dyp, K > 1, write_out=False)
+            ops.fused_assemble(g, patches, acc=dyp, acc_add=K > 1, write_out=False)
         if k >= 1:
-            q = (ops.fused_assemble_acc(g, patches, dyp, k < K - 1, mask_p, None, -1.0) if dyp is not None
-                 else ops.fused_assemble(g, patches, mask_p, None, -1.0))
+            q = ops.fused_assemble(g, patches, mask_p, None, -1.0, acc=dyp, acc_add=k < K - 1)
             dA[k], dB[k] = ops.fused_wgrad(g, ws, du, resid[k - 1], -1.0, codes[k - 1], q, 1.0, prec, layout=layout)
             thin = q
         else:

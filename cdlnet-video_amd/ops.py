@@ -324,18 +324,12 @@ def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None):
     gup, zout, c = _dev(gup, "g"), _dev(zout, "zout"), _opt(c, "c")
     scratch = torch.empty(16 * g.N * g.M, device=gup.device, dtype=torch.float32)      # CDL_TAU_SPLITS * N * M
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
+    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    if dtau_n is None:
-        rc = _lib.lib().cdl_tau_grad(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c),
-                                     ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M),
-                                     _ptr(scratch), _stream())
-        _lib.check(rc, "cdl_tau_grad")
-        return
-    assert dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M
-    rc = _lib.lib().cdl_tau_grad_x(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
-                                   ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _stream())
-    _lib.check(rc, "cdl_tau_grad_x")
+    rc = _lib.lib().cdl_tau_grad(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
+                                 ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _stream())
+    _lib.check(rc, "cdl_tau_grad")
 
 
 def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
@@ -358,8 +352,8 @@ def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None):
     ws = _scratch(x.device, n)
     base = dt_k.data_ptr()
     rc = _lib.lib().cdl_analysis_rev_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(zsup), _ptr(c),
-                                        ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(out), _ptr(ws), n,
-                                        _stream())
+                                        ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), None, _ptr(out), _ptr(ws),
+                                        n, _stream())
     _lib.check(rc, "cdl_analysis_rev_ws")
     return out
 
@@ -682,29 +676,18 @@ def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3"
     return out
 
 
-def fused_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None):
-    """out = mask * alpha * (overlap-sum of the patches) - sub."""
+def fused_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None, acc=None, acc_add=False,
+                   write_out=True):
+    """out = mask * alpha * (overlap-sum of the patches) - sub [and acc = S or acc += S with S the unmasked, unscaled
+    overlap-sum]; write_out=False: acc only.  Returns out (None without write_out)."""
     mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    if out is None:
-        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_assemble(ctypes.byref(gs), _ptr(patches), _ptr(mask), _ptr(sub),
-                                         float(alpha), _ptr(out), _stream())
-    _lib.check(rc, "cdl_fused2d_assemble")
-    return out
-
-
-def fused_assemble_acc(g: Geometry, patches, acc, acc_add, mask=None, sub=None, alpha=1.0, out=None, write_out=True):
-    """fused_assemble, and acc = S or acc += S with S the unmasked, unscaled overlap-sum (cdl_fused2d_assemble_acc);
-    write_out=False: acc only.  Returns out (None without write_out)."""
-    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    assert acc.is_contiguous() and tuple(acc.shape) == g.image_shape()
+    assert acc is None or (acc.is_contiguous() and tuple(acc.shape) == g.image_shape())
     if write_out and out is None:
         out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_fused2d_assemble_acc(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
-                                             float(alpha), _ptr(out if write_out else None), _ptr(acc),
-                                             int(bool(acc_add)), _stream())
-    _lib.check(rc, "cdl_fused2d_assemble_acc")
+    rc = _lib.lib().cdl_fused2d_assemble(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
+                                         float(alpha), _ptr(out if write_out else None), _ptr(acc),
+                                         int(bool(acc_add)), _stream())
+    _lib.check(rc, "cdl_fused2d_assemble")
     return out if write_out else None
 
 
@@ -718,7 +701,7 @@ def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial,
     """One reverse-sweep stage: du = [z' != 0] * (base + corr(thin; W1)); patches = W2^T du.  `gate` is the
     bit map of z' (int32, from the forward or fused_support_map) or z' itself (the map is built first).
     With `r2` (thin) and `workspace` (fused_wgrad_workspace) the launch also accumulates dA = alpha * du (x) im2col(r2)
-    (cdl_fused2d_stage_bwd_da) and (du, dA) is returned."""
+    and (du, dA) is returned."""
     thin = _dev(thin, "thin")
     if base is not None and lay_in == "nchw":
         base = _dev(base, "base")
@@ -729,31 +712,25 @@ def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial,
         out = fused_code_buffer(g, lay_out, thin.device)[0]
     gs = g.c_struct()
     flags = PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out)
-    if r2 is not None:
-        r2 = _dev(r2, "r2")
-        dA = torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
-        rc = _lib.lib().cdl_fused2d_stage_bwd_da(ctypes.byref(gs), _ptr(thin), _ptr(base), _ptr(gate), _ptr(frags),
-                                                 _ptr(out), _ptr(patches), _ptr(dtau_partial), int(bool(do_synth)),
-                                                 _ptr(r2), float(alpha), _ptr(dA), _ptr(workspace), flags, _stream())
-        _lib.check(rc, "cdl_fused2d_stage_bwd_da")
-        return out, dA
-    rc = _lib.lib().cdl_fused2d_stage_bwd(ctypes.byref(gs), _ptr(thin), _ptr(base), _ptr(gate),
-                                          _ptr(frags), _ptr(out), _ptr(patches), _ptr(dtau_partial),
-                                          int(bool(do_synth)), flags, _stream())
+    r2 = _opt(r2, "r2")
+    dA = None if r2 is None else torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
+    rc = _lib.lib().cdl_fused2d_stage_bwd(ctypes.byref(gs), _ptr(thin), _ptr(base), _ptr(gate), _ptr(frags), _ptr(out),
+                                          _ptr(patches), _ptr(dtau_partial), int(bool(do_synth)), _ptr(r2),
+                                          float(alpha), _ptr(dA), _ptr(workspace), flags, _stream())
     _lib.check(rc, "cdl_fused2d_stage_bwd")
-    return out
+    return out if dA is None else (out, dA)
 
 
 def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
-    """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`: cdl_fused2d_dtau_reduce_x]."""
+    """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`]."""
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
     assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fused2d_dtau_reduce_x(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                              ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
-                                              _stream())
-    _lib.check(rc, "cdl_fused2d_dtau_reduce_x")
+    rc = _lib.lib().cdl_fused2d_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
+                                            ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
+                                            _stream())
+    _lib.check(rc, "cdl_fused2d_dtau_reduce")
 
 
 def fused_wgrad_workspace(g: Geometry, device):
@@ -784,7 +761,7 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
 
 
 def _check_data_grads(g: Geometry, K, dyp, dtau):
-    """The optional outputs of the *_backward_x sweeps: dyp (thin, as yp), dtau (K,N,M); contiguous fp32."""
+    """The optional outputs of the *_backward sweeps: dyp (thin, as yp), dtau (K,N,M); contiguous fp32."""
     for t, shape in ((dyp, g.image_shape()), (dtau, (K, g.N, g.M))):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
@@ -834,7 +811,7 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
     maps: the forward's bit maps of z_1..z_K (built here from the codes when not given).  `layout`: that of
     codes[:-1] (as fused_forward returned them) and of the du work buffers; codes[-1] = z_K, g_z: NCHW.
     g_xp None (a loss on the code only) is a zero image gradient.  dyp (thin, as yp) / dtau (K,N,M): filled with
-    dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward_x; None: the plain sweep)."""
+    dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward; None: the plain sweep)."""
     K = len(A)
     dev = yp.device
     if not maps:
@@ -858,13 +835,13 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
     assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
     gs = g.c_struct()
     _check_data_grads(g, K, dyp, dtau)
-    rc = _lib.lib().cdl_fused2d_backward_x(
+    rc = _lib.lib().cdl_fused2d_backward(
         ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
         _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
         _ptr_table(dB), _ptr(dt),
         _ptr(du0), _ptr(du1), _ptr(q), _ptr(frags), _ptr(patches), _ptr(dtp), _ptr(ws),
         PRECISION[precision] | _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
-    _lib.check(rc, "cdl_fused2d_backward_x")
+    _lib.check(rc, "cdl_fused2d_backward")
     return dA, dB
 
 
@@ -956,27 +933,16 @@ def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out
     return out
 
 
-def fusedg_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None):
+def fusedg_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None, acc=None, acc_add=False,
+                    write_out=True):
+    """As fused_assemble (the optional unmasked sum into `acc` included)."""
     mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    if out is None:
-        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fusedg_assemble(ctypes.byref(gs), _ptr(patches), _ptr(mask), _ptr(sub), float(alpha),
-                                        _ptr(out), _stream())
-    _lib.check(rc, "cdl_fusedg_assemble")
-    return out
-
-
-def fusedg_assemble_acc(g: Geometry, patches, acc, acc_add, mask=None, sub=None, alpha=1.0, out=None, write_out=True):
-    """fusedg_assemble with the unmasked sum into `acc` (cdl_fusedg_assemble_acc; see fused_assemble_acc)."""
-    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    assert acc.is_contiguous() and tuple(acc.shape) == g.image_shape()
+    assert acc is None or (acc.is_contiguous() and tuple(acc.shape) == g.image_shape())
     if write_out and out is None:
         out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_fusedg_assemble_acc(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
-                                            float(alpha), _ptr(out if write_out else None), _ptr(acc),
-                                            int(bool(acc_add)), _stream())
-    _lib.check(rc, "cdl_fusedg_assemble_acc")
+    rc = _lib.lib().cdl_fusedg_assemble(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub), float(alpha),
+                                        _ptr(out if write_out else None), _ptr(acc), int(bool(acc_add)), _stream())
+    _lib.check(rc, "cdl_fusedg_assemble")
     return out if write_out else None
 
 
@@ -1024,10 +990,10 @@ def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
     assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fusedg_dtau_reduce_x(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                             ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
-                                             _stream())
-    _lib.check(rc, "cdl_fusedg_dtau_reduce_x")
+    rc = _lib.lib().cdl_fusedg_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
+                                           ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
+                                           _stream())
+    _lib.check(rc, "cdl_fusedg_dtau_reduce")
 
 
 def fusedg_code_layout(g: Geometry, training=True) -> str:
@@ -1076,7 +1042,7 @@ def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw"):
 
 def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
                     dyp=None, dtau=None):
-    """Whole reverse sweep in one C call (cdl_fusedg_backward_x); returns (dA list, dB list), fills dt (K,2,M) [and
+    """Whole reverse sweep in one C call (cdl_fusedg_backward); returns (dA list, dB list), fills dt (K,2,M) [and
     dyp, dtau: see fused_backward].  `layout`: that of codes[:-1] (and of the du buffers allocated here)."""
     K = len(A)
     dev = yp.device
@@ -1103,12 +1069,12 @@ def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, d
     ws = torch.empty(max(nws, 1), device=dev, dtype=torch.float32)
     assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
     _check_data_grads(g, K, dyp, dtau)
-    rc = _lib.lib().cdl_fusedg_backward_x(
+    rc = _lib.lib().cdl_fusedg_backward(
         ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
         _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
         _ptr_table(dB), _ptr(dt), _ptr(du[0]), _ptr(du[1 if K > 1 else 0]), _ptr(q), _ptr(frags), _ptr(patches),
         _ptr(dtp), _ptr(ws), nws, _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
-    _lib.check(rc, "cdl_fusedg_backward_x")
+    _lib.check(rc, "cdl_fusedg_backward")
     return dA, dB
 
 
@@ -1155,7 +1121,7 @@ def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=
 def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, us=None, z_prev=None,
                   z_after=None, lam=None, gam1=None, gam2=None, dg1=None, dg2=None, gz_prev=None, gz_after=None,
                   dyp=None, dtau=None):
-    """Generic reverse sweep in one C call (cdl_ista_backward_x); returns (dA, dB) and fills dt [, dg1, dg2, gz_prev,
+    """Generic reverse sweep in one C call (cdl_ista_backward); returns (dA, dB) and fills dt [, dg1, dg2, gz_prev,
     gz_after] [, dyp, dtau: see fused_backward; plain loop only]."""
     K = len(A)
     dev = yp.device
@@ -1167,7 +1133,7 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
     ws, n = ista_scratch(g, dev)
     gs = g.c_struct()
     _check_data_grads(g, K, dyp, dtau)
-    rc = _lib.lib().cdl_ista_backward_x(
+    rc = _lib.lib().cdl_ista_backward(
         ctypes.byref(gs), K, _ptr(_dev(yp, "yp")), _ptr(_opt(mask_p, "mask")), _ptr(_opt(c, "c")),
         _ptr(_opt(z_prev, "z_prev")), _ptr(_opt(z_after, "z_after")), _ptr(_opt(lam, "lam")),
         _ptr(_opt(gam1, "gam1")), _ptr(_opt(gam2, "gam2")), _ptr_table(A), _ptr_table(B),
@@ -1175,7 +1141,7 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
         _ptr_table([_dev(t, "u") for t in us]) if us else None, _ptr(_opt(g_xp, "g_xp")), _ptr(_opt(g_z, "g_z")),
         _ptr_table(dA), _ptr_table(dB), _ptr(dt), _ptr(dg1), _ptr(dg2), _ptr(gz_prev), _ptr(gz_after),
         _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _stream())
-    _lib.check(rc, "cdl_ista_backward_x")
+    _lib.check(rc, "cdl_ista_backward")
     return dA, dB
 
 

@@ -118,17 +118,14 @@ int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alp
                     void *stream);
 size_t cdl_analysis_workspace_floats(const cdl_geom *g);
 /* One step of the reverse sweep (autograd of net.py:87 / 205 through the shrinkage of the previous iteration):
- *   out = [zsup != 0] * (zin + alpha * A x),   (dt0, dt1) = cdl_tau_grad(out, zsup, c)
+ *   out = [zsup != 0] * (zin + alpha * A x),   (dt0, dt1[, dtau_n]) = cdl_tau_grad(out, zsup, c)
  * i.e. cdl_analysis_ws followed by cdl_tau_grad_gate, as ONE fat launch where the matrix-core analysis covers the
- * geometry (gate and threshold partials in its epilogue).  out must differ from zin and zsup. */
+ * geometry (gate and threshold partials in its epilogue).  dtau_n NULL: no per-sample threshold gradients.
+ * out must differ from zin and zsup. */
 int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
-                        const float *zsup, const float *c /*nullable*/, float *dt0, float *dt1, float *out,
-                        float *workspace, size_t workspace_floats, void *stream);
-/* The same with the per-sample threshold gradients of `out` (cdl_tau_grad_x's dtau_n; nullable). */
-int cdl_analysis_rev_ws_x(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
-                          const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
-                          float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
-                          void *stream);
+                        const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
+                        float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
+                        void *stream);
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g);
 
 /* ---- synthesis half: F.conv_transpose2d/3d at net.py:87,90,205,210 and gabor.py:64 ----------
@@ -166,24 +163,19 @@ size_t cdl_wgrad_workspace_floats(const cdl_geom *g);
 
 /* Threshold gradients of one iteration: with du = [zout!=0]*g,
  *   dt0[m] = -sum_{n,pix} sign(zout)*du,   dt1[m] = -sum_n c[n] * sum_pix sign(zout)*du
- * (c NULL -> dt1 = 0).  scratch: CDL_TAU_SPLITS*N*M floats (rows are split over workgroups and folded in a fixed
+ * (c NULL -> dt1 = 0).  dtau_n (nullable) receives the per-sample threshold gradient dtau_n[n,m] = -sum_pix
+ * sign(zout)*du of sample n (dt0 = sum_n dtau_n, dt1 = sum_n c[n] dtau_n): what dL/dc needs; dt0 / dt1 do not depend
+ * on whether it is given.  scratch: CDL_TAU_SPLITS*N*M floats (rows are split over workgroups and folded in a fixed
  * order). dt0/dt1 are overwritten. */
 #define CDL_TAU_SPLITS 16
 int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const float *c /*N, nullable*/,
-                 float *dt0 /*M*/, float *dt1 /*M*/, float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+                 float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
+                 float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
 /* Same, and gup is gated IN PLACE (gup[i] = 0 where zout[i] == 0) in the same pass: the reverse sweep's three
  * consumers of the gated gradient then need no gate (one fat read each less). */
 int cdl_tau_grad_gate(const cdl_geom *g, float *gup /*inout*/, const float *zout, const float *c /*N, nullable*/,
-                      float *dt0 /*M*/, float *dt1 /*M*/, float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
-/* The same two, and (dtau_n non-NULL) the per-sample threshold gradient dtau_n[n,m] = -sum_pix sign(zout)*du of
- * sample n (dt0 = sum_n dtau_n, dt1 = sum_n c[n] dtau_n): what dL/dc needs.  dt0 / dt1 are bit-identical to the
- * forms above. */
-int cdl_tau_grad_x(const cdl_geom *g, const float *gup, const float *zout, const float *c /*N, nullable*/,
-                   float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
-                   float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
-int cdl_tau_grad_gate_x(const cdl_geom *g, float *gup /*inout*/, const float *zout, const float *c /*N, nullable*/,
-                        float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
-                        float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+                      float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
+                      float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
 /* Generic reverse sweep, iteration k: q holds S = A_k^T du_k (unmasked, alpha = +1); dyp = S (acc_add 0) or dyp += S,
  * then with make_q: q = -(mask ? mask : 1) * S in place -- the q_k the sweep continues with. */
 int cdl_dyp_split(const cdl_geom *g, float *q /*inout, thin*/, const float *mask /*nullable*/, float *dyp,
@@ -294,7 +286,10 @@ int cdl_residual_backward(const cdl_geom *g, const float *x, const float *h, con
  * cdl_ista_scratch_floats(g) floats.
  * Backward: z, r, u as saved by the forward; g_xp = dL/d(D z_K) and / or g_z = dL/dz_K; writes dA[k],
  * dB[k], dt (K,2,M) [, dg1, dg2 (K,2,M)], accumulates gz_prev / gz_after (nullable); gbuf0, gbuf1 fat
- * scratch, q thin scratch, scratch as above (required). */
+ * scratch, q thin scratch, scratch as above (required).  The gradients of the data (plain loop only: z_prev must be
+ * NULL when either is given; both NULL: neither is computed):
+ *     dyp  (thin, as yp; nullable):  dL/dyp = sum_k A_k^T du_k  (u_0 = A_0 yp, u_k = z_k - A_k(mask B_k z_k - yp))
+ *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau) */
 size_t cdl_ista_scratch_floats(const cdl_geom *g);
 int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                      const float *tau, const float *z_prev /*nullable*/, const float *z_after /*nullable*/,
@@ -310,21 +305,8 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt,
                       float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
                       float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                      size_t scratch_floats, void *stream);
-/* The same with the gradients of the data (plain loop only: z_prev must be NULL when either is given):
- *     dyp  (thin, as yp; nullable):  dL/dyp = sum_k A_k^T du_k  (u_0 = A_0 yp, u_k = z_k - A_k(mask B_k z_k - yp))
- *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau)
- * With both NULL it is cdl_ista_backward: same launches, same arguments. */
-int cdl_ista_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
-                        const float *c /*N, nullable*/, const float *z_prev /*nullable*/,
-                        const float *z_after /*nullable*/, const float *lam, const float *gam1, const float *gam2,
-                        const float *const *wA, const float *const *wB, const float *const *z,
-                        const float *const *r, const float *const *u /*CSR*/, const float *g_xp /*nullable*/,
-                        const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt,
-                        float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
-                        float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                        size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M, nullable*/,
-                        void *stream);
+                      size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M, nullable*/,
+                      void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
  * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere.  w inout. */
@@ -409,14 +391,12 @@ int cdl_fused2d_iter_fwd(const cdl_geom *g, const float *r, const float *zin /*n
  * builds it from a tensor for callers that did not get it from cdl_fused2d_iter_fwd. */
 size_t cdl_fused2d_map_words(const cdl_geom *g);
 int cdl_fused2d_support_map(const cdl_geom *g, const float *z, unsigned *map, void *stream);
-/* out = (mask ? mask : 1) * alpha * (sum of the overlapping patches) - (sub ? sub : 0) */
+/* out = (mask ? mask : 1) * alpha * (sum of the overlapping patches) - (sub ? sub : 0), and (acc non-NULL) the plain
+ * sum S of the patches, unmasked and unscaled: acc = S (acc_add 0) or acc += S.  S comes from the same summation as
+ * `out`, which does not depend on whether acc is given.  out may be NULL only when acc is set (acc only). */
 int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
-                         const float *sub /*nullable*/, float alpha, float *out, void *stream);
-/* The same, and (acc non-NULL) the plain sum S of the patches, unmasked and unscaled: acc = S (acc_add 0) or acc += S.
- * S comes from the same summation as `out`, which is bit-identical to cdl_fused2d_assemble's.  out NULL: acc only. */
-int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
-                             const float *sub /*nullable*/, float alpha, float *out /*nullable*/,
-                             float *acc /*nullable*/, int acc_add, void *stream);
+                         const float *sub /*nullable*/, float alpha, float *out /*nullable iff acc*/,
+                         float *acc /*nullable*/, int acc_add, void *stream);
 
 /* ---- fused reverse sweep (what loss.backward() does through ATen in the reference, train.py:98) ----
  * One stage per iteration k = K-1 .. 0, same kernel skeleton as the forward launch:
@@ -427,24 +407,21 @@ int cdl_fused2d_assemble_acc(const cdl_geom *g, const float *patches, const floa
  *     patches : partial W2^T du_k (W2 = A_k)    -> cdl_fused2d_assemble(alpha = -1, mask) gives q_k
  * frags = cdl_fused2d_prep(W1, W2).  do_synth = 0 for k = 0 (no q_0 is needed). */
 size_t cdl_fused2d_tiles(const cdl_geom *g);               /* workgroups (= dtau_partial rows) per launch */
+/* r2, dA, workspace (all three set, or all three NULL; a mix is CDL_EINVAL): the analysis-filter gradient of the
+ * iteration rides in the stage (what autograd of net.py:87 computes from du_k and r_k): dA = alpha * sum_px du_out (x)
+ * im2col(r2) -- cdl_fused2d_wgrad's product, taken from the stage's registers instead of a second fat read of du_out.
+ * du_out / patches / dtau_partial do not depend on whether it rides; workspace: cdl_fused2d_wgrad_workspace_floats(g).
+ * The whole-sweep entry point cdl_fused2d_backward uses it (5.1 instead of 6.1 fat passes per iteration;
+ * CDL_FUSED_DA=0 restores the two-launch form for A/B runs). */
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base /*nullable*/,
-                          const unsigned *map /*of z_{k+1}*/, const void *frags, float *du_out,
-                          float *patches, float *dtau_partial, int do_synth, int precision, void *stream);
-/* The same stage with the analysis-filter gradient of the iteration riding in it (what autograd of net.py:87 computes from
- * du_k and r_k): dA = alpha * sum_px du_out (x) im2col(r2) -- cdl_fused2d_wgrad's product, taken from the stage's registers
- * instead of a second fat read of du_out.  du_out / patches / dtau_partial are bit-identical to cdl_fused2d_stage_bwd's;
- * workspace: cdl_fused2d_wgrad_workspace_floats(g).  The whole-sweep entry point cdl_fused2d_backward uses this form
- * (5.1 instead of 6.1 fat passes per iteration; CDL_FUSED_DA=0 restores the two-launch form for A/B runs). */
-int cdl_fused2d_stage_bwd_da(const cdl_geom *g, const float *thin, const float *base /*nullable*/,
-                             const unsigned *map, const void *frags, float *du_out, float *patches,
-                             float *dtau_partial, int do_synth, const float *r2 /*(N,1,H,W)*/, float alpha,
-                             float *dA /*(M,1,P,P)*/, float *workspace, int precision, void *stream);
-/* dt0[m] = sum over workgroups; dt1[m] = sum_n c[n] * (sum over the workgroups of image n); c nullable */
-int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/,
-                            float *dt0 /*M*/, float *dt1 /*M*/, void *stream);
-/* The same, and (dtau_n non-NULL) the per-image sums dtau_n[n,m] of the partial rows, tiles in order */
-int cdl_fused2d_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/, float *dt0 /*M*/,
-                              float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/, void *stream);
+                          const unsigned *map /*of z_{k+1}*/, const void *frags, float *du_out, float *patches,
+                          float *dtau_partial, int do_synth, const float *r2 /*(N,1,H,W), nullable*/, float alpha,
+                          float *dA /*(M,1,P,P), nullable*/, float *workspace /*nullable*/, int precision,
+                          void *stream);
+/* dt0[m] = sum over workgroups; dt1[m] = sum_n c[n] * (sum over the workgroups of image n); c nullable.
+ * dtau_n (nullable) receives the per-image sums dtau_n[n,m] of the partial rows, tiles in order. */
+int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/, float *dt0 /*M*/,
+                            float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/, void *stream);
 
 /* Filter gradients on the matrix cores: up to two independent reductions per launch
  *     dw_a[m,i,j] = alpha_a * sum_{n,y,x} Xa[n,m,y,x] * Ta[n,y-p+i,x-p+j]     (a = 0, 1; either may be absent)
@@ -462,7 +439,10 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
  * xp receives D z_K.  frags: K * cdl_fused2d_frag_bytes(M) bytes (every pair is prepared up front, one launch).
  * Backward (net.py forward lines in reverse): z[k] = z_{k+1}, r[k] = r_{k+1}, maps[k] as saved by the forward,
  * g_xp = dL/d(D z_K), g_z = dL/dz_K or NULL; writes dA[k], dB[k] (filter shapes) and dt (K,2,M);
- * du0/du1 fat scratch, q thin scratch, dtau_partial (tiles x M), wgrad_ws (workspace_floats). */
+ * du0/du1 fat scratch, q thin scratch, dtau_partial (tiles x M), wgrad_ws (workspace_floats).
+ * The gradients of the data, as cdl_ista_backward's (both NULL: neither is computed): dyp (thin, nullable) receives
+ * sum_k A_k^T du_k -- the unmasked sum each assemble already forms, plus the k = 0 synthesis half (its stage then runs
+ * with do_synth = 1) and one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients. */
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                         const float *tau /*K,N,M*/, const float *const *wA, const float *const *wB,
                         float *const *z, float *const *r, unsigned *const *maps /*nullable*/, float *xp,
@@ -471,19 +451,9 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
                          const float *c /*N, nullable*/, const float *const *wA, const float *const *wB,
                          const float *const *z, const float *const *r, const unsigned *const *maps,
                          const float *g_xp, const float *g_z /*nullable*/, float *const *dA, float *const *dB,
-                         float *dt,
-                         float *du0, float *du1, float *q, void *frags, float *patches,
-                         float *dtau_partial, float *wgrad_ws, int precision, void *stream);
-/* The same with the gradients of the data, as cdl_ista_backward_x: dyp (thin, nullable) receives sum_k A_k^T du_k -- the
- * unmasked sum each assemble already forms, plus the k = 0 synthesis half (its stage then runs with do_synth = 1) and
- * one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients.  Both NULL: cdl_fused2d_backward. */
-int cdl_fused2d_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
-                           const float *c /*N, nullable*/, const float *const *wA, const float *const *wB,
-                           const float *const *z, const float *const *r, const unsigned *const *maps,
-                           const float *g_xp, const float *g_z /*nullable*/, float *const *dA, float *const *dB,
-                           float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
-                           float *dtau_partial, float *wgrad_ws, int precision, float *dyp /*nullable*/,
-                           float *dtau /*K*N*M, nullable*/, void *stream);
+                         float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
+                         float *dtau_partial, float *wgrad_ws, int precision, float *dyp /*nullable*/,
+                         float *dtau /*K*N*M, nullable*/, void *stream);
 
 /* ==== fused MFMA path for the other shapes (cdl_fusedg.hip): any C, 2-D / 3-D, unit stride, square planes ====
  * P in {3,5,7}, odd Pd with C*Pd in {1,3,5,7}, M <= 64 -- CDLNetVideo.forward's loop body (net.py:204-207) and
@@ -515,17 +485,14 @@ int cdl_fusedg_iter_fwd(const cdl_geom *g, const float *r, const float *zin /*nu
 int cdl_fusedg_stage_bwd(const cdl_geom *g, const float *thin, const float *base /*nullable*/, const unsigned *map,
                          const void *frags, float *du_out, float *patches /*nullable iff !do_synth*/,
                          float *dtau_partial /*tiles,M*/, int do_synth, int precision, void *stream);
+/* As cdl_fused2d_assemble / cdl_fused2d_dtau_reduce, optional outputs included (every route: tile, strip and grouped
+ * strip kernels) */
 int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
-                        const float *sub /*nullable*/, float alpha, float *out, void *stream);
+                        const float *sub /*nullable*/, float alpha, float *out /*nullable iff acc*/,
+                        float *acc /*nullable*/, int acc_add, void *stream);
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N, nullable*/, float *dt0,
-                           float *dt1, void *stream);
-/* As cdl_fused2d_assemble_acc / cdl_fused2d_dtau_reduce_x (every route: tile, strip and grouped strip kernels) */
-int cdl_fusedg_assemble_acc(const cdl_geom *g, const float *patches, const float *mask /*nullable*/,
-                            const float *sub /*nullable*/, float alpha, float *out /*nullable*/,
-                            float *acc /*nullable*/, int acc_add, void *stream);
-int cdl_fusedg_dtau_reduce_x(const cdl_geom *g, const float *dtau_partial, const float *c /*N, nullable*/, float *dt0,
-                             float *dt1, float *dtau_n /*N,M, nullable*/, void *stream);
-/* Whole sweeps (arguments as cdl_fused2d_forward / _backward).  The reverse sweep takes the filter gradients
+                           float *dt1, float *dtau_n /*N,M, nullable*/, void *stream);
+/* Whole sweeps (arguments as cdl_fused2d_forward / _backward, the data gradients dyp / dtau included).  The reverse sweep takes the filter gradients
  * dA_k = -du_k (x) r_k, dB_k = z_k (x) q_k from cdl_wgrad: wgrad_ws = cdl_wgrad_workspace_floats(g) floats. */
 int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/, const float *tau,
                        const float *const *wA, const float *const *wB, float *const *z, float *const *r,
@@ -536,15 +503,8 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
                         const float *const *z, const float *const *r, const unsigned *const *maps, const float *g_xp,
                         const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt, float *du0,
                         float *du1, float *q, void *frags, float *patches, float *dtau_partial, float *wgrad_ws,
-                        size_t wgrad_ws_floats, int precision, void *stream);
-/* With the gradients of the data, as cdl_fused2d_backward_x.  Both NULL: cdl_fusedg_backward. */
-int cdl_fusedg_backward_x(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
-                          const float *c /*nullable*/, const float *const *wA, const float *const *wB,
-                          const float *const *z, const float *const *r, const unsigned *const *maps, const float *g_xp,
-                          const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt, float *du0,
-                          float *du1, float *q, void *frags, float *patches, float *dtau_partial, float *wgrad_ws,
-                          size_t wgrad_ws_floats, int precision, float *dyp /*nullable*/,
-                          float *dtau /*K*N*M, nullable*/, void *stream);
+                        size_t wgrad_ws_floats, int precision, float *dyp /*nullable*/,
+                        float *dtau /*K*N*M, nullable*/, void *stream);
 
 /* Per-kernel timing inside the fused sweeps: cdl_fused2d_timing(1) starts collecting HIP-event pairs around
  * every forward stage (class 0; the k = 0 launch, which reads no code, is class 3), reverse stage (1) and

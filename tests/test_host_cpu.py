@@ -24,6 +24,51 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(cva._lib.Geom) == 15 * 4
 
 
+def _declared_entry_points():
+    """name -> (return type, [argument kind]) for every int / size_t cdl_* declaration of include/cdlnet_hip.h."""
+    header = open(os.path.join(ROOT, "include", "cdlnet_hip.h")).read()
+    header = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    decls = {}
+    for ret, name, params in re.findall(r"\b(int|size_t)\s+(cdl_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
+        kinds = []
+        for p in params.split(","):
+            p = p.strip()
+            if p in ("", "void"):
+                continue
+            if "*" in p or "[" in p:                         # an array parameter decays to a pointer
+                kinds.append("pointer")
+            else:
+                kind = next((t for t in ("size_t", "float", "int") if re.search(rf"\b{t}\b", p)), None)
+                assert kind, f"{name}: unrecognised parameter {p!r}"
+                kinds.append(kind)
+        assert name not in decls, f"{name} declared twice"
+        decls[name] = (ret, kinds)
+    return decls
+
+
+def _ctypes_kind(t):
+    if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}[t]
+
+
+def test_bindings_match_header_declarations():
+    """ctypes trusts SIGNATURES / SIZE_T_FUNCS: an argument list one short or out of order would hand the C side whatever
+    sits in that position, as a device pointer.  Check every binding against its declaration, position by position."""
+    decls = _declared_entry_points()
+    assert len(decls) >= 13
+    for table, ret in ((cva._lib.SIGNATURES, "int"), (cva._lib.SIZE_T_FUNCS, "size_t")):
+        for name, argtypes in table.items():
+            assert name in decls, f"{name} bound but not declared in include/cdlnet_hip.h"
+            dret, dkinds = decls[name]
+            assert dret == ret, f"{name}: declared to return {dret}, bound as returning {ret}"
+            kinds = [_ctypes_kind(t) for t in argtypes]
+            assert len(kinds) == len(dkinds), f"{name}: {len(dkinds)} parameters declared, {len(kinds)} bound"
+            for i, (k, d) in enumerate(zip(kinds, dkinds)):
+                assert k == d, f"{name}: argument {i} is declared {d}, bound as {k}"
+    assert set(decls) == set(cva._lib.SIGNATURES) | set(cva._lib.SIZE_T_FUNCS)
+
+
 def test_exact_fp32_switch_is_per_thread_and_scoped():
     """cdl_set_exact_fp32 (host-only state, no GPU needed): returns the previous setting, is private to the calling thread, and
     the Python scopes restore what they found -- also when the body raises."""
