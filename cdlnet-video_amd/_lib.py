@@ -59,6 +59,8 @@ SIGNATURES = {
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_bwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_vgg_forward": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_vgg_backward": [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_residual_forward": [_G, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_residual_backward": [_G] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_prox_csr": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -104,7 +106,7 @@ SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G
                 "cdl_synthesis_workspace_floats": [_G], "cdl_ista_scratch_floats": [_G], "cdl_analysis_workspace_floats": [_G], "cdl_analysis_rev_workspace_floats": [_G],
                 "cdl_nle_mad_scratch_floats": [_I, _I, _I, _I],
                 "cdl_nle_pca_scratch_floats": [_I, _I, _I, _I, _I], "cdl_residual_scratch_floats": [_G],
-                "cdl_ssim_scratch_floats": [_I, _I, _I, _I]}
+                "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_vgg_scratch_floats": [_I, _I, _I, _I]}
 
 _lib = None
 

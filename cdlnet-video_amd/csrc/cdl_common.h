@@ -157,6 +157,13 @@ int cdl_dense_conv(const cdl_geom *g, int transpose, const float *x, const float
                    float alpha, const float *add, const float *add_gate, const float *mask, const float *sub,
                    const float *tau, int relu, const float *out_gate, float *out, float *ws, size_t ws_floats,
                    void *stream);
+// the VGG16 layers of the perceptual loss (cdl_vgg.hip) on the dense tier: forms of cdl_dense_vgg
+enum { CDL_VGG_PLAIN = 0, CDL_VGG_BIAS = 1, CDL_VGG_POOL = 2, CDL_VGG_DIFF = 3, CDL_VGG_UNPOOL = 4 };
+size_t cdl_dense_vgg_workgroups(const cdl_geom *g, int transpose);
+int cdl_dense_vgg(const cdl_geom *g, int transpose, int form, const float *x, const float *w, const float *bias,
+                  const float *out_gate, float *out, unsigned char *pool_arg, const unsigned char *unpool_arg,
+                  const float *fy, float *seed_x, float *seed_y, double *partial, float *ws, size_t ws_floats,
+                  void *stream);
 int cdl_mfma_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
                       size_t ws_floats, void *stream);

@@ -19,6 +19,13 @@
 //     v = 0 where out_gate == 0
 // which covers the analysis role (add = zin, tau), the synthesis role (transposed + flipped weights, input gate,
 // mask, sub) and the ResidualBlock's fused relu.
+// The VGG16 perceptual loss (cdl_vgg.hip) adds compile-time modes (DenseMode bits; mode 0 is the kernel above, unchanged):
+//     DM_BIAS    v = relu(alpha * acc + bias[o])
+//     DM_POOL    2x2 stride-2 max-pool of that in registers: rows 2w, 2w+1 are the wave's two accumulator rows, the
+//                column pair is one lane swap; writes (H/2, W/2) (floor) and a 1-byte argmax (first maximum)
+//     DM_DIFF    d = v - fy (the target's features): seeds d*[v > 0] (and d*[fy > 0]) and per-workgroup fp64 sums
+//                of d^2; v itself is not written
+//     DM_UNPOOL  staging reads a pooled gradient (H/2, W/2) and places it at its argmax (the backward's unpool)
 #include "cdl_common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -40,6 +47,17 @@ struct DenseArgs {
     float *out;
     int N, I, O, D, H, W, Pd, Ph, Pw, tilesX, tilesY, NCC, MTT;
     CDL_DBG_FIELD(int dbg;)                                // probe build only (CDL_DENSE_DEBUG): 1 no global loads, 2 no MFMAs, 4 no epilogue
+};
+
+enum DenseMode { DM_BIAS = 1, DM_POOL = 2, DM_DIFF = 4, DM_UNPOOL = 8 };
+
+struct DenseExt {                                          // fields of the DenseMode bits (cdl_dense_vgg)
+    const float *bias;                                     // DM_BIAS: per output channel
+    unsigned char *pool_arg;                               // DM_POOL: argmax 0..3 (row-major in the window), nullable
+    const unsigned char *unpool_arg;                       // DM_UNPOOL: the argmax codes of x (pooled extents)
+    const float *fy;                                       // DM_DIFF: the target's features, laid out as out
+    float *seed_x, *seed_y;                                // DM_DIFF: d*[v > 0], d*[fy > 0] (nullable)
+    double *partial;                                       // DM_DIFF: one sum of d^2 per workgroup
 };
 
 // frags[(((cc*Pd + kd)*taps + tap)*MTT + R)*2 + {hi,lo}][64]: lane (l32, h) holds output channel o = 32R + l32,
@@ -73,8 +91,8 @@ __global__ void k_dense_prep(const float *__restrict__ w, uint4 *__restrict__ fr
     frags[base + 64 + lane] = __builtin_bit_cast(uint4, lo);
 }
 
-template <int MT>
-__global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd argument = waves per SIMD -> <= 128 VGPRs, two workgroups per CU
+template <int MT, int MODE>
+__device__ __forceinline__ void dense_body(DenseArgs a, DenseExt ex)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int XH = DTY + a.Ph - 1, XW = DTX + a.Pw - 1, taps = a.Ph * a.Pw;
@@ -124,7 +142,19 @@ __global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd arg
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-            if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
+            if constexpr ((MODE & DM_UNPOOL) != 0) {
+                // x is the pooled gradient (H/2, W/2): pixel (yy, xx) gets it where it was its window's argmax; the
+                // row / column that floor mode dropped gets nothing
+                const int Hp = a.H >> 1, Wp = a.W >> 1, py = yy >> 1, px = xx >> 1;
+                if (yy >= 0 && xx >= 0 && py < Hp && px < Wp) {
+                    const size_t pplane = (size_t)Hp * Wp, pslab = (size_t)a.D * pplane;
+                    const size_t pb = ((size_t)n * a.I + c0) * pslab + (size_t)d * pplane + (size_t)py * Wp + px;
+                    const unsigned char code = (unsigned char)(((yy & 1) << 1) | (xx & 1));
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (c0 + e < a.I && ex.unpool_arg[pb + e * pslab] == code) v[e] = a.x[pb + e * pslab];
+                }
+            } else if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
                 const size_t base = ((size_t)n * a.I + c0) * slab + (size_t)d * plane + (size_t)yy * a.W + xx;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
@@ -193,6 +223,75 @@ __global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd arg
 
     // epilogue: register v of tile R is output channel 32(r0+R) + 8(v>>2) + 4h + (v&3) of pixel column l32
     const int x = tx * DTX + l32;
+    if constexpr ((MODE & DM_POOL) != 0) {
+        // pooled output (H/2, W/2): the even lane of a column pair takes its partner's two rows by a lane swap and
+        // writes the window's maximum; ties go to the first maximum in row-major order (torch's max-pool backward)
+        const int Hp = a.H >> 1, Wp = a.W >> 1;
+        const size_t pplane = (size_t)Hp * Wp, pslab = (size_t)a.D * pplane;
+        const size_t pbase = (size_t)n * a.O * pslab + (size_t)zd * pplane;
+        const int Y = (ty * DTY + 2 * wv) >> 1, X = x >> 1;
+        const bool own = (l32 & 1) == 0 && Y < Hp && X < Wp;
+#pragma unroll
+        for (int R = 0; R < MT; ++R) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int m = 32 * (r0 + R) + 8 * (v >> 2) + 4 * h + (v & 3);
+                const float bm = ex.bias[m < a.O ? m : 0];
+                const float v0 = fmaxf(a.alpha * acc[0][R][v] + bm, 0.0f);
+                const float v1 = fmaxf(a.alpha * acc[1][R][v] + bm, 0.0f);
+                const float w0 = __shfl_xor(v0, 1), w1 = __shfl_xor(v1, 1);      // every lane, before any branch
+                if (!own || m >= a.O) continue;
+                float mx = v0;
+                unsigned char am = 0;
+                if (w0 > mx) { mx = w0; am = 1; }
+                if (v1 > mx) { mx = v1; am = 2; }
+                if (w1 > mx) { mx = w1; am = 3; }
+                const size_t idx = pbase + (size_t)m * pslab + (size_t)Y * Wp + X;
+                a.out[idx] = mx;
+                if (ex.pool_arg) ex.pool_arg[idx] = am;
+            }
+        }
+        return;
+    }
+    if constexpr ((MODE & DM_DIFF) != 0) {
+        // the backward's seeds and the workgroup's sum of d^2 (fixed order: per lane, a butterfly over the wave, the
+        // eight waves in order)
+        const size_t nb = (size_t)n * a.O * slab + (size_t)zd * plane;
+        double s = 0.0;
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int y = ty * DTY + 2 * wv + rr;
+            if (y >= a.H || x >= a.W) continue;
+            const int pix = y * a.W + x;
+#pragma unroll
+            for (int R = 0; R < MT; ++R) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int m = 32 * (r0 + R) + 8 * (v >> 2) + 4 * h + (v & 3);
+                    if (m >= a.O) continue;
+                    const size_t idx = nb + (size_t)m * slab + pix;
+                    const float fx = fmaxf(a.alpha * acc[rr][R][v] + ex.bias[m], 0.0f);
+                    const float fy = ex.fy[idx];
+                    const float dd = fx - fy;
+                    ex.seed_x[idx] = fx > 0.0f ? dd : 0.0f;
+                    if (ex.seed_y) ex.seed_y[idx] = fy > 0.0f ? dd : 0.0f;
+                    s += (double)dd * (double)dd;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        __syncthreads();                                   // the last stage's LDS readers are done
+        double *red = reinterpret_cast<double *>(smem);
+        if (lane == 0) red[wv] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int w = 0; w < DNT / 64; ++w) t += red[w];
+            ex.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+        }
+        return;
+    }
     const size_t nbase = (size_t)n * a.O * slab + (size_t)zd * plane;   // offsets inside the sample are 32-bit
     const float *add_n = a.add ? a.add + nbase : nullptr;
     const float *ag_n = (a.add && a.add_gate) ? a.add_gate + nbase : nullptr;
@@ -219,6 +318,7 @@ __global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd arg
                     if (!ag_n || ag_n[idx] != 0.0f) val += av;
                 }
                 if (sub_n) val -= sub_n[idx];
+                if constexpr ((MODE & DM_BIAS) != 0) val += ex.bias[m];
                 if (a.tau) val = cdl_shrink(val, a.tau[n * a.O + m]);
                 if (a.relu) val = fmaxf(val, 0.0f);
                 if (og_n && og_n[idx] == 0.0f) val = 0.0f;
@@ -226,6 +326,18 @@ __global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd arg
             }
         }
     }
+}
+
+template <int MT>
+__global__ __launch_bounds__(DNT, 4) void k_dense(DenseArgs a)   // HIP: 2nd argument = waves per SIMD -> <= 128 VGPRs, two workgroups per CU
+{
+    dense_body<MT, 0>(a, DenseExt{});
+}
+
+template <int MODE>
+__global__ __launch_bounds__(DNT, 4) void k_dense_vgg(DenseArgs a, DenseExt ex)   // the DenseMode variants, MT = 2
+{
+    dense_body<2, MODE>(a, ex);
 }
 
 struct DensePlan {
@@ -300,6 +412,66 @@ int cdl_dense_conv(const cdl_geom *g, int transpose, const float *x, const float
                       g->N, in, outc, g->D, g->H, g->W, g->Pd, g->Ph, g->Pw, p.tilesX, p.tilesY, p.NCC, p.MTT
                       CDL_DBG_COMMA(cdl_opts().dense_debug)};
     return p.MT == 2 ? launch_dense<2>(p, a, S(stream)) : launch_dense<1>(p, a, S(stream));
+}
+
+namespace {
+
+template <int MODE>
+int launch_dense_vgg(const DensePlan &p, const DenseArgs &a, const DenseExt &ex, hipStream_t st)
+{
+    if (p.lds > 64 * 1024) {
+        const int rc = cdl_ensure_dynamic_lds((const void *)k_dense_vgg<MODE>, 160 * 1024);
+        if (rc) return rc;
+    }
+    k_dense_vgg<MODE><<<dim3((unsigned)p.tiles, (unsigned)p.ngy), DNT, p.lds, st>>>(a, ex);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+// Workgroups of one cdl_dense_vgg launch (the partial sums of CDL_VGG_DIFF); 0: not a dense-tier geometry
+size_t cdl_dense_vgg_workgroups(const cdl_geom *g, int transpose)
+{
+    DensePlan p;
+    const int in = transpose ? g->M : g->C, out = transpose ? g->C : g->M;
+    return dense_plan(g, in, out, &p) ? p.tiles * p.ngy : 0;
+}
+
+// The VGG16 layers on the dense tier (cdl_vgg.hip): one 3x3 convolution with ReLU, in one of the forms
+//     CDL_VGG_PLAIN    cdl_dense_conv's synthesis role with out_gate (the backward's transposed layers)
+//     CDL_VGG_BIAS     out = relu(conv(x) + bias)
+//     CDL_VGG_POOL     out = maxpool2x2(relu(conv(x) + bias)) at (H/2, W/2), argmax codes into pool_arg (nullable)
+//     CDL_VGG_DIFF     seeds and partial sums against fy (out unused)
+//     CDL_VGG_UNPOOL   the synthesis role on x = a pooled gradient placed at the argmax codes unpool_arg, out_gate
+// The geometry's (H, W) is the convolution's own extent.  Returns CDL_EUNSUPPORTED off the dense tier.
+int cdl_dense_vgg(const cdl_geom *g, int transpose, int form, const float *x, const float *w, const float *bias,
+                  const float *out_gate, float *out, unsigned char *pool_arg, const unsigned char *unpool_arg,
+                  const float *fy, float *seed_x, float *seed_y, double *partial, float *ws, size_t ws_floats,
+                  void *stream)
+{
+    DensePlan p;
+    const int in = transpose ? g->M : g->C, outc = transpose ? g->C : g->M;
+    if (!dense_plan(g, in, outc, &p) || p.MT != 2) return CDL_EUNSUPPORTED;
+    if (!ws || ws_floats < p.frag_uint4 * 4 || (reinterpret_cast<size_t>(ws) & 15)) return CDL_EUNSUPPORTED;
+    uint4 *frags = reinterpret_cast<uint4 *>(ws);
+    const int nprep = p.NCC * g->Pd * g->Ph * g->Pw * p.MTT * 64;
+    k_dense_prep<<<(nprep + 255) / 256, 256, 0, S(stream)>>>(w, frags, outc, in, g->Pd, g->Ph, g->Pw, p.MTT, p.NCC,
+                                                              transpose);
+    CDL_LAUNCH_CHECK();
+    const int relu = form == CDL_VGG_BIAS;
+    const DenseArgs a{x, nullptr, frags, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, out_gate, relu, out,
+                      g->N, in, outc, g->D, g->H, g->W, g->Pd, g->Ph, g->Pw, p.tilesX, p.tilesY, p.NCC, p.MTT
+                      CDL_DBG_COMMA(0)};
+    const DenseExt ex{bias, pool_arg, unpool_arg, fy, seed_x, seed_y, partial};
+    switch (form) {
+    case CDL_VGG_PLAIN: return launch_dense<2>(p, a, S(stream));
+    case CDL_VGG_BIAS: return launch_dense_vgg<DM_BIAS>(p, a, ex, S(stream));
+    case CDL_VGG_POOL: return launch_dense_vgg<DM_BIAS | DM_POOL>(p, a, ex, S(stream));
+    case CDL_VGG_DIFF: return launch_dense_vgg<DM_BIAS | DM_DIFF>(p, a, ex, S(stream));
+    case CDL_VGG_UNPOOL: return launch_dense_vgg<DM_UNPOOL>(p, a, ex, S(stream));
+    default: return CDL_EINVAL;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------

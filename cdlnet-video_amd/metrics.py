@@ -4,7 +4,10 @@
   term of loss.py's CombinedLossWithSSIM is built on it);
 * `ssim_frames(output, target)`: that term for (N, C, D, H, W) clips, every frame in one launch;
 * `structural_similarity(x, y, ...)`: skimage's `structural_similarity` (analyzemri.py's metric), per plane;
-* `video_ssim(video, denoised)`: analyzemri.py's `ssim_total / frame_count` for one batch, one host sync.
+* `video_ssim(video, denoised)`: analyzemri.py's `ssim_total / frame_count` for one batch, one host sync;
+* `perceptual_frames(output, target, weights)`: the VGG16 relu3_3 perceptual term of CombinedLossWithSSIM for
+  (N, 1, D, H, W) clips, differentiable in both (`cdl_vgg_forward` / `cdl_vgg_backward`, csrc/cdl_vgg.hip);
+  `vgg16_features(frames, weights)`: the relu3_3 features themselves.
 
 The per-plane means of the SSIM map and their reverse sweep run in libcdlnet_hip.so (`cdl_ssim_fwd` /
 `cdl_ssim_bwd`, csrc/cdl_ssim.hip).  The host builds the 1-D window and passes it by value; data_range is a device
@@ -166,6 +169,137 @@ def ssim_frames(output, target, data_range=None):
     per_plane = _plane_ssim(output, target, R, _gaussian_window(11, 1.5), 0.01, 0.03, 1.0)   # (N, C, D)
     ssim_t = per_plane.mean(dim=(0, 1))
     return (1 - ssim_t).mean()
+
+
+# ------------------------------------------------------------------------------ perceptual term (VGG16 relu3_3)
+VGG_CONVS = (0, 2, 5, 7, 10, 12, 14)            # torchvision's vgg16().features indices of the seven convolutions
+VGG_SHAPES = {0: (64, 3), 2: (64, 64), 5: (128, 64), 7: (128, 128), 10: (256, 128), 12: (256, 256), 14: (256, 256)}
+_VGG_DX, _VGG_DY = 1, 2
+
+
+def vgg16_state(sd):
+    """The seven convolutions of VGG16 features[:16] from a state dict in any of three key layouts -- torchvision's
+    `features.N.*` (`classifier.*` and the deeper layers ignored), the reference loss module's `vgg.N.*`, bare `N.*` --
+    as {"N.weight", "N.bias"} float32 tensors, shapes checked."""
+    out = {}
+    for key, v in sd.items():
+        parts = key.split(".")
+        if parts[0] in ("features", "vgg"):
+            parts = parts[1:]
+        if len(parts) != 2 or not parts[0].isdigit() or parts[1] not in ("weight", "bias"):
+            continue
+        if int(parts[0]) in VGG_CONVS:
+            out[f"{int(parts[0])}.{parts[1]}"] = v
+    for i in VGG_CONVS:
+        o, c = VGG_SHAPES[i]
+        for name, shape in (("weight", (o, c, 3, 3)), ("bias", (o,))):
+            k = f"{i}.{name}"
+            if k not in out:
+                raise KeyError(f"VGG16 weights: {k} (or features.{k} / vgg.{k}) missing")
+            if tuple(out[k].shape) != shape:
+                raise ValueError(f"VGG16 weights: {k} has shape {tuple(out[k].shape)}, expected {shape}")
+            out[k] = out[k].detach().to(torch.float32)
+    return {f"{i}.{n}": out[f"{i}.{n}"] for i in VGG_CONVS for n in ("weight", "bias")}
+
+
+def _vgg_tables(weights, device):
+    sd = vgg16_state(weights)
+    ws = [sd[f"{i}.weight"].to(device).contiguous() for i in VGG_CONVS]
+    bs = [sd[f"{i}.bias"].to(device).contiguous() for i in VGG_CONVS]
+    return ws, bs
+
+
+def _check_planes(H, W):
+    if H < 4 or W < 4:
+        raise ValueError(f"the VGG16 features need frames of at least 4 x 4, got {H} x {W}")
+
+
+class _PerceptualPlanes(torch.autograd.Function):
+    """(x, y) of P planes (P, H, W) -> mean over all relu3_3 elements of (F(x) - F(y))^2, one forward and one backward
+    call into libcdlnet_hip.so (cdl_vgg_forward / cdl_vgg_backward).  The scratch holds the activations the backward
+    gates on, so it is owned by this call (not the shared per-stream scratch)."""
+
+    @staticmethod
+    def forward(ctx, x, y, ws, bs):
+        P, H, W = x.shape
+        grads = (_VGG_DX if ctx.needs_input_grad[0] else 0) | (_VGG_DY if ctx.needs_input_grad[1] else 0)
+        lib = _lib.lib()
+        n = int(lib.cdl_vgg_scratch_floats(P, H, W, grads))
+        if n == 0:
+            raise ValueError(f"perceptual loss: {P} planes of {H} x {W} not supported")
+        scratch = torch.empty(n, device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        wt, bt = ops._ptr_table(ws), ops._ptr_table(bs)
+        rc = lib.cdl_vgg_forward(ops._ptr(x), ops._ptr(y), P, H, W, wt, bt, grads, None, ops._ptr(loss),
+                                 ops._ptr(scratch), n, ops._stream())
+        _lib.check(rc, "cdl_vgg_forward")
+        ctx.state = (scratch, ws, bs, grads, (P, H, W))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        scratch, ws, bs, grads, (P, H, W) = ctx.state
+        if not grads:
+            return None, None, None, None
+        g = g.to(torch.float32).contiguous()
+        dx = torch.empty((P, H, W), device=g.device, dtype=torch.float32) if grads & _VGG_DX else None
+        dy = torch.empty((P, H, W), device=g.device, dtype=torch.float32) if grads & _VGG_DY else None
+        wt, bt = ops._ptr_table(ws), ops._ptr_table(bs)
+        rc = _lib.lib().cdl_vgg_backward(P, H, W, wt, bt, grads, ops._ptr(g), ops._ptr(dx), ops._ptr(dy),
+                                         ops._ptr(scratch), scratch.numel(), ops._stream())
+        _lib.check(rc, "cdl_vgg_backward")
+        ctx.state = None
+        return dx, dy, None, None
+
+
+def perceptual_frames(output, target, weights):
+    """The perceptual term of loss.py's CombinedLossWithSSIM for (N, 1, D, H, W) clips:
+    (1/D) sum_t mean((F(o_t) - F(g_t))^2), F = VGG16 features[:16] (relu3_3) of the frame repeated to three channels.
+    Every frame has the same number of features, so this is one mean over all N*D planes.  `weights`: a state dict
+    in any layout `vgg16_state` reads.  Differentiable in output and target (not in the weights); one forward and one
+    backward launch sequence, no host synchronisation."""
+    if not (torch.is_tensor(output) and torch.is_tensor(target)):
+        raise TypeError("perceptual_frames: expected tensors")
+    if output.shape != target.shape:
+        raise ValueError(f"input clips should have the same dimensions, got {tuple(output.shape)} and "
+                         f"{tuple(target.shape)}")
+    if output.dim() != 5:
+        raise ValueError(f"perceptual_frames expects (N, 1, D, H, W), got {tuple(output.shape)}")
+    if output.shape[1] != 1:
+        raise ValueError(f"perceptual_frames takes one-channel clips (the reference repeats each frame to three "
+                         f"channels; C = {output.shape[1]} would give {3 * output.shape[1]}), got {tuple(output.shape)}")
+    H, W = output.shape[-2:]
+    _check_planes(H, W)
+    output, target = ops._dev(output, "output"), ops._dev(target, "target")
+    P = math.prod(output.shape[:3])
+    with torch.cuda.device(output.device):
+        ws, bs = _vgg_tables(weights, output.device)
+        return _PerceptualPlanes.apply(output.reshape(P, H, W), target.reshape(P, H, W), ws, bs)
+
+
+def vgg16_features(frames, weights):
+    """relu3_3 of VGG16 features[:16] for every one-channel (H, W) plane of `frames` (..., H, W), each repeated to
+    three channels: (..., 256, H4, W4), H4 = floor(floor(H/2)/2).  Forward only."""
+    if not torch.is_tensor(frames) or frames.dim() < 2:
+        raise TypeError("vgg16_features: expected a tensor (..., H, W)")
+    H, W = frames.shape[-2:]
+    _check_planes(H, W)
+    frames = ops._dev(frames, "frames")
+    lead = frames.shape[:-2]
+    P = math.prod(lead)
+    H4, W4 = H // 2 // 2, W // 2 // 2
+    with torch.cuda.device(frames.device):
+        ws, bs = _vgg_tables(weights, frames.device)
+        lib = _lib.lib()
+        n = int(lib.cdl_vgg_scratch_floats(P, H, W, 0))
+        if n == 0:
+            raise ValueError(f"vgg16_features: {P} planes of {H} x {W} not supported")
+        scratch = torch.empty(n, device=frames.device, dtype=torch.float32)
+        feat = torch.empty((P, 256, H4, W4), device=frames.device, dtype=torch.float32)
+        rc = lib.cdl_vgg_forward(None, ops._ptr(frames), P, H, W, ops._ptr_table(ws), ops._ptr_table(bs), 0,
+                                 ops._ptr(feat), None, ops._ptr(scratch), n, ops._stream())
+        _lib.check(rc, "cdl_vgg_forward")
+    return feat.reshape(*lead, 256, H4, W4)
 
 
 def structural_similarity(x, y, data_range=1.0, win_size=7, K1=0.01, K2=0.03, channel_axis=None):

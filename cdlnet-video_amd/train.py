@@ -101,11 +101,12 @@ def mcsure_loss(net, obsrv, xhat, sigma, mask=1, h=1e-3, generator=None, b=None)
 
 
 def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, project=True,
-               grad_sync=None, generator=None, mcsure=False):
+               grad_sync=None, generator=None, mcsure=False, loss_fn=None):
     """One optimiser step: awgn -> forward -> MSE (or MC-SURE) -> backward -> [all-reduce] -> clip -> Adam
     -> project (train.py:76-102).
 
-    `grad_sync` is a callable run between backward and clipping (parallel.GradientBucket.sync).
+    `grad_sync` is a callable run between backward and clipping (parallel.GradientBucket.sync).  `loss_fn(xhat, batch)`
+    replaces the MSE (trainmri.py's `combmse`: a loss.CombinedLossWithSSIM); `mcsure` takes precedence over it.
     Returns (loss tensor, sigma).
     """
     mask = gen_bayer_mask(batch) if demosaic else 1
@@ -115,6 +116,8 @@ def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, proje
     xhat, _ = net(obsrv, sigma, mask=mask)
     if mcsure:
         loss = mcsure_loss(net, obsrv, xhat, sigma, mask=mask, generator=generator)
+    elif loss_fn is not None:
+        loss = loss_fn(xhat, batch)
     else:
         loss = torch.mean((batch - xhat) ** 2)
     loss.backward()
@@ -160,7 +163,8 @@ def save_args(args, ckpt=True):
 
 def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), save_dir=None, start_epoch=1,
         clip_grad=1, noise_std=25, demosaic=False, verbose=True, val_freq=1, save_freq=1, epoch_fun=None,
-        mcsure=False, backtrack_thresh=1, grad_sync=None, log=print, group=None, generator=None):
+        mcsure=False, backtrack_thresh=1, grad_sync=None, log=print, group=None, generator=None, combmse=False,
+        loss_fn=None):
     """The reference's training driver (train.py:35-158), same arguments and files:
 
     * phases train / val (every `val_freq` epochs) / test (only at `epoch == epochs`, as written there);
@@ -187,6 +191,10 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     Rank 0 alone writes logs and checkpoints into `save_dir` (one node: the directory is shared); a
     barrier orders its writes before the other ranks' reads, and a backtrack reloads the SAME file on
     every rank, so replicas, optimiser states and learning rates stay identical.
+    `combmse` (trainmri.py / train3d.py): the train phase's loss is `loss_fn`, by default
+    loss.CombinedLossWithSSIM(1.0, 0.01, 0.1) (VGG16 weights from the default local file); a `loss_fn` given without
+    `combmse` is used the same way.  `mcsure` takes precedence; val and test keep the MSE; the logged train PSNR is
+    -10 log10 of that training loss, as in the reference.
     Returns the history [(epoch, phase, psnr)].
     """
     ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -207,6 +215,9 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     os.makedirs(save_dir, exist_ok=True)
     if not isinstance(noise_std, (list, tuple)):
         noise_std = (noise_std, noise_std)
+    if combmse and loss_fn is None:
+        from .loss import CombinedLossWithSSIM
+        loss_fn = CombinedLossWithSSIM(alpha=1.0, beta=0.01, gamma=0.1).to(device)
     log(f"fit: using device {device}")
     log("Saving initialization to 0.ckpt")
     if rank0:
@@ -231,7 +242,7 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
                 batch = batch.to(device)
                 if phase == "train":
                     loss_t, _ = train_step(net, opt, batch, phase_nstd, clip_grad=clip_grad, demosaic=demosaic,
-                                           grad_sync=grad_sync, mcsure=mcsure, generator=generator)
+                                           grad_sync=grad_sync, mcsure=mcsure, generator=generator, loss_fn=loss_fn)
                 else:
                     with torch.no_grad():
                         mask = gen_bayer_mask(batch) if demosaic else 1

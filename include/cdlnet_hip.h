@@ -261,6 +261,28 @@ int cdl_ssim_bwd(const float *x, const float *y, int P, int H, int W, const floa
                  float *dx /*nullable*/, float *dy /*nullable*/, float *d_range /*P, nullable*/, float *scratch,
                  size_t scratch_floats, void *stream);
 
+/* ---- perceptual term of loss.py's CombinedLossWithSSIM: VGG16 features[:16] (relu3_3) -------------------------
+ * P independent contiguous one-channel H x W planes (H, W >= 4) of the output x and the target y; every frame is the
+ * reference's three-channel repeat, so conv1_1 runs on the filters summed over their input channels.  The seven
+ * convolutions (torchvision's features.{0,2,5,7,10,12,14}) come as device pointer arrays w[7] ((O, I, 3, 3)) and
+ * b[7] (O).  With F = relu3_3, (256, H4, W4) per plane, H4 = floor(floor(H/2)/2) (W4 alike):
+ *     loss = mean over all P * 256 * H4 * W4 elements of (F(x) - F(y))^2.
+ * cdl_vgg_forward runs F(y) first, into feat (P * 256 * H4 * W4, nullable: scratch), then, with x, writes loss (one
+ * device float) and the seeds of the backward; x NULL: F(y) into feat only (grads 0).  grads (CDL_VGG_DX |
+ * CDL_VGG_DY) asks it to keep what cdl_vgg_backward needs for dx / dy.  cdl_vgg_backward (the same grads, scratch and
+ * weights) writes dx = dloss/dx * g_loss[0] and dy (each nullable, at least one; g_loss a device float).  No weight
+ * gradients.  Both deterministic (fixed-order fp64 sums, no atomics), no host synchronisation.
+ * scratch: cdl_vgg_scratch_floats(P, H, W, grads) floats, 16-byte aligned (0: shape not supported). */
+#define CDL_VGG_DX 1
+#define CDL_VGG_DY 2
+size_t cdl_vgg_scratch_floats(int P, int H, int W, int grads);
+int cdl_vgg_forward(const float *x /*nullable*/, const float *y, int P, int H, int W, const float *const *w,
+                    const float *const *b, int grads, float *feat /*nullable unless x is NULL*/,
+                    float *loss /*1, nullable iff x is NULL*/, float *scratch, size_t scratch_floats, void *stream);
+int cdl_vgg_backward(int P, int H, int W, const float *const *w, const float *const *b, int grads,
+                     const float *g_loss /*1*/, float *dx /*nullable*/, float *dy /*nullable*/, float *scratch,
+                     size_t scratch_floats, void *stream);
+
 /* ---- ResidualBlock of CDLNetVideo(residual=True) -------------------------
  * model/net.py:105-120, applied to the code after every iteration (net.py:199-207):
  *     h = relu(conv1(x)),  out = relu(conv2(h) + x),   conv*: Conv3d(M, M, P, stride 1, padding P/2, bias=False)
