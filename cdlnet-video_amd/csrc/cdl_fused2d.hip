@@ -1153,7 +1153,10 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
     __bf16 *thin = reinterpret_cast<__bf16 *>(dsm);                            // [op][hl][s][TCOPY]
     __bf16 *imgs = reinterpret_cast<__bf16 *>(dsm + WG_THIN_BYTES);            // [wave][R][hl][IMG_ELEMS]
     constexpr int M = 32 * MT;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    // the wave index as a SCALAR: what hangs on it (operator pair, the pointers p.X[op] / p.T[op], tile and row indices)
+    // then lives in SGPRs and comes from scalar loads.  As a per-lane value the compiler re-read p.X[op] through a
+    // vector load inside the row loop and drained every outstanding fat load with vmcnt(0) in front of it
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int op = wid >> 2, wq = wid & 3;                                     // operator pair, wave in group
     const int wxi = wq & 1, wyi = wq >> 1;
     const int c = lane & 31, h = lane >> 5;
@@ -1172,150 +1175,185 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
 
     const bool present = p.X[op] != nullptr;
     const int nsteps = p.single ? (p.numTiles + 1) / 2 : p.numTiles;
-    for (int t0 = blockIdx.x; t0 < nsteps; t0 += gridDim.x) {
+    const size_t img_b = lay_image_bytes<LAY>(M, p.H, p.W);
+    const int hw4 = (int)HW * 4;
+
+    // Software pipeline of the fat operand.  A wave used to load a row block, wait, convert, multiply, with nothing in
+    // flight while it computed.  Now the loads run one row block ahead, into the other of two register sets (the row
+    // loop alternates between them: no copies, and the wait in front of the conversions is for the older set only), the
+    // first row block of the NEXT tile included -- tiles are a fixed stride -- so that they stay in flight across the
+    // thin staging and its barriers.  Tiles, pixels and the order of the sums are what they were.  (The thin tile a tile
+    // ahead as well, or no thin staging and no barriers at all, changed nothing measurable: DESIGN.md 5.2f.)
+    struct Tile { bool active; int n, tx0, ty0; };
+    auto tile_at = [&](int t0) {
         const int t = p.single ? 2 * t0 + op : t0;         // single operator: the wave groups take alternate tiles
-        const bool active = present && t < p.numTiles;    // (per wave group)
+        Tile q;
+        q.active = present && t0 < nsteps && t < p.numTiles;                  // (per wave group)
         int bid = p.rev ? p.numTiles - 1 - t : t;
         const int txi = bid % p.tilesX; bid /= p.tilesX;
         const int tyi = bid % p.tilesY;
-        const int n = active ? bid / p.tilesY : 0;
-        const int tx0 = txi * TW, ty0 = tyi * GW_TH;
-        __syncthreads();                                  // previous tile's readers are done
-        if (active) {                                     // each group of 256 threads stages its own thin tile
-            const float *timg = p.T[op] + (size_t)n * HW;
-            // all of a thread's elements are loaded (clamped addresses, no branches) before any is converted: one at a time
-            // was seven dependent global-load latencies per 64 x 16 tile, a quarter of the single-operator launch
-            constexpr int NSW = (GW_RTH * RTW + 255) / 256;
-            float tv[NSW];
+        q.n = q.active ? bid / p.tilesY : 0;
+        q.tx0 = txi * TW; q.ty0 = tyi * GW_TH;
+        return q;
+    };
+    // each group of 256 threads stages its own thin tile: all of a thread's elements are loaded (clamped addresses, no
+    // branches) before any is converted: one at a time was seven dependent global-load latencies per 64 x 16 tile
+    constexpr int NSW = (GW_RTH * RTW + 255) / 256;
+    auto thin_load = [&](float (&tv)[NSW], const Tile &q) {
+        const float *timg = p.T[op] + (size_t)q.n * HW;
 #pragma unroll
-            for (int k = 0; k < NSW; ++k) {
-                const int i = (tid & 255) + k * 256;
-                const int yy = i / RTW, xx = i % RTW;
-                const int gy = ty0 - HALO + yy, gx = tx0 - HALO + xx;
-                const bool ok = i < GW_RTH * RTW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-                const float v = timg[ok ? (size_t)gy * p.W + gx : 0];
-                tv[k] = ok ? v : 0.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < NSW; ++k) {
-                const int i = (tid & 255) + k * 256;
-                if (i >= GW_RTH * RTW) continue;
-                const int yy = i / RTW, xx = i % RTW;
-                const __bf16 hh = (__bf16)tv[k];
-                const __bf16 ll = (__bf16)(tv[k] - (float)hh);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    if (xx - s >= 0) {
-                        thin[((op * 2 + 0) * 4 + s) * TCOPY + yy * TPITCH + xx - s] = hh;
-                        if (PREC != 1) thin[((op * 2 + 1) * 4 + s) * TCOPY + yy * TPITCH + xx - s] = ll;
-                    }
-            }
+        for (int k = 0; k < NSW; ++k) {
+            const int i = (tid & 255) + k * 256;
+            const int yy = i / RTW, xx = i % RTW;
+            const int gy = q.ty0 - HALO + yy, gx = q.tx0 - HALO + xx;
+            const bool ok = i < GW_RTH * RTW && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
+            const float v = timg[ok ? (size_t)gy * p.W + gx : 0];
+            tv[k] = ok ? v : 0.0f;
         }
-        __syncthreads();
-        if (!active) continue;
-
-        const int x = tx0 + wxi * 32 + c;
-        const bool xok = x < p.W;
-#pragma unroll 1
-        for (int b = 0; b < RB; ++b) {
-            const int yl = wyi * RB + b, y = ty0 + yl;
-            const bool valid = xok && y < p.H;
-            // ---- fat operand: registers (lanes = pixels) -> bf16 hi/lo -> transposition images
-            const size_t img_b = lay_image_bytes<LAY>(M, p.H, p.W);
-            const __amdgpu_buffer_rsrc_t rs = uniform_rsrc((const char *)p.X[op] + (size_t)n * img_b, img_b);   // op: per wave group
+    };
+    auto thin_write = [&](const float (&tv)[NSW]) {
+#pragma unroll
+        for (int k = 0; k < NSW; ++k) {
+            const int i = (tid & 255) + k * 256;
+            if (i >= GW_RTH * RTW) continue;
+            const int yy = i / RTW, xx = i % RTW;
+            const __bf16 hh = (__bf16)tv[k];
+            const __bf16 ll = (__bf16)(tv[k] - (float)hh);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (xx - s >= 0) {
+                    thin[((op * 2 + 0) * 4 + s) * TCOPY + yy * TPITCH + xx - s] = hh;
+                    if (PREC != 1) thin[((op * 2 + 1) * 4 + s) * TCOPY + yy * TPITCH + xx - s] = ll;
+                }
+        }
+    };
+    // ---- fat operand of one row block: registers (lanes = pixels); an inactive tile or an outside pixel loads zeros
+    //      (offset beyond the descriptor: no memory access)
+    struct Fat {
+        float xv[MT][16];
+        u32x2 xr[MT][4];                 // LAY_BLK16: the stored bf16 pairs ARE the hi fragments; there is no lo part
+    };
+    auto fat_load = [&](Fat &f, const Tile &q, int b) {
+        const int x = q.tx0 + wxi * 32 + c, y = q.ty0 + wyi * RB + b;
+        const bool valid = q.active && x < p.W && y < p.H;
+        const __amdgpu_buffer_rsrc_t rs = uniform_rsrc((const char *)p.X[op] + (size_t)q.n * img_b, img_b);   // op: per wave group
+        if (LAY == LAY_BLK16) {
+            const int XB = (p.W + 31) / 32, xb = (q.tx0 >> 5) + wxi;
+            blk16_load_raw<MT>(f.xr, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 8 : OOB);
+        } else if (LAY == LAY_BLK) {
+            const int XB = (p.W + 31) / 32, xb = (q.tx0 >> 5) + wxi;
+            blk_load<LAY_BLK, MT>(f.xv, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 16 : OOB);
+        } else {
             const int voff = valid ? (int)((4 * h) * HW + (size_t)y * p.W + x) * 4 : OOB;
-            const int hw4 = (int)HW * 4;
-            float xv[MT][16];
-            u32x2 xr[MT][4];                 // LAY_BLK16: the stored bf16 pairs ARE the hi fragments; there is no lo part
-            if (LAY == LAY_BLK16) {
-                const int XB = (p.W + 31) / 32, xb = (tx0 >> 5) + wxi;
-                blk16_load_raw<MT>(xr, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 8 : OOB);
-            } else if (LAY == LAY_BLK) {
-                const int XB = (p.W + 31) / 32, xb = (tx0 >> 5) + wxi;
-                blk_load<LAY_BLK, MT>(xv, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 16 : OOB);
-            } else {
-#pragma unroll
-                for (int R = 0; R < MT; ++R)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v)
-                        xv[R][v] = buf_ld(rs, voff, (32 * R + 8 * (v >> 2) + (v & 3)) * hw4);
-            }
 #pragma unroll
             for (int R = 0; R < MT; ++R)
 #pragma unroll
-                for (int qv = 0; qv < 4; ++qv) {
-                    bf16x4 hi4, lo4;
-                    if (LAY == LAY_BLK16) {
-                        hi4 = __builtin_bit_cast(bf16x4, xr[R][qv]);
-                    } else {
+                for (int v = 0; v < 16; ++v)
+                    f.xv[R][v] = buf_ld(rs, voff, (32 * R + 8 * (v >> 2) + (v & 3)) * hw4);
+        }
+    };
+    // ---- one row block: bf16 hi/lo -> transposition images -> MFMAs against the thin tile's windows
+    auto row_block = [&](const Fat &f, int b) {
+        const int yl = wyi * RB + b;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float val = xv[R][4 * qv + e];
-                            const __bf16 hh = (__bf16)val;
-                            hi4[e] = hh;
-                            lo4[e] = (__bf16)(val - (float)hh);
-                        }
-                    }
-                    const int slot = (2 * qv + h) ^ ((c >> 1) & 7);      // 8-byte slot of channels 8qv+4h..+3
-                    __bf16 *dst = wimg + (size_t)(R * 2) * IMG_ELEMS + c * 32 + slot * 4;
-                    *reinterpret_cast<bf16x4 *>(dst) = hi4;
-                    if (PREC != 1 && LAY != LAY_BLK16) *reinterpret_cast<bf16x4 *>(dst + IMG_ELEMS) = lo4;
-                }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+        for (int R = 0; R < MT; ++R)
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                // B fragments: tap column of this lane, 8 consecutive pixels 16kk + 8h + (0..7)
-                bf16x8 Bh[2], Bl[2];
+            for (int qv = 0; qv < 4; ++qv) {
+                bf16x4 hi4, lo4;
+                if (LAY == LAY_BLK16) {
+                    hi4 = __builtin_bit_cast(bf16x4, f.xr[R][qv]);
+                } else {
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    const int tap = 32 * tt + c, ti = tap >> 3, tj = tap & 7;
-                    const int e0 = wxi * 32 + 16 * kk + 8 * h + (tj & 4);
-                    const __bf16 *ph = thin + ((op * 2 + 0) * 4 + (tj & 3)) * TCOPY + (yl + ti) * TPITCH + e0;
-                    const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(ph);
-                    const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(ph + 4);
-                    Bh[tt] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    if (PREC != 1) {
-                        const __bf16 *pl = ph + 4 * TCOPY;
-                        const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(pl);
-                        const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(pl + 4);
-                        Bl[tt] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+                    for (int e = 0; e < 4; ++e) {
+                        const float val = f.xv[R][4 * qv + e];
+                        const __bf16 hh = (__bf16)val;
+                        hi4[e] = hh;
+                        lo4[e] = (__bf16)(val - (float)hh);
                     }
                 }
+                const int slot = (2 * qv + h) ^ ((c >> 1) & 7);      // 8-byte slot of channels 8qv+4h..+3
+                __bf16 *dst = wimg + (size_t)(R * 2) * IMG_ELEMS + c * 32 + slot * 4;
+                *reinterpret_cast<bf16x4 *>(dst) = hi4;
+                if (PREC != 1 && LAY != LAY_BLK16) *reinterpret_cast<bf16x4 *>(dst + IMG_ELEMS) = lo4;
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int R = 0; R < MT; ++R) {
-                    // A fragments by transposed reads: lane (i = lane&15 of group g) gets channel
-                    // 16(g&1) + i, pixels 16kk + 8h + 4*half + (0..3)
-                    const int gg = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
-                    bf16x4 part[2][2];
+        for (int kk = 0; kk < 2; ++kk) {
+            // B fragments: tap column of this lane, 8 consecutive pixels 16kk + 8h + (0..7)
+            bf16x8 Bh[2], Bl[2];
 #pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const int row = 16 * kk + 8 * h + 4 * half + qq;
-                        const int slot = (4 * gg + pp) ^ ((row >> 1) & 7);
-                        const __bf16 *src = wimg + (size_t)(R * 2) * IMG_ELEMS + row * 32 + slot * 4;
-                        part[0][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4 *)(src));
-                        if (PREC != 1 && LAY != LAY_BLK16)
-                            part[1][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                                (__attribute__((address_space(3))) bf16x4 *)(src + IMG_ELEMS));
-                    }
-                    const bf16x8 Ah = __builtin_shufflevector(part[0][0], part[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    bf16x8 Al;
-                    if (PREC != 1 && LAY != LAY_BLK16) Al = __builtin_shufflevector(part[1][0], part[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) {
-                        if (PREC != 1) {
-                            if (LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[tt], acc[R][tt], 0, 0, 0);
-                            acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[tt], acc[R][tt], 0, 0, 0);
-                            if (PREC == 2 && LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bl[tt], acc[R][tt], 0, 0, 0);
-                        }
-                        acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[tt], acc[R][tt], 0, 0, 0);
-                    }
+            for (int tt = 0; tt < 2; ++tt) {
+                const int tap = 32 * tt + c, ti = tap >> 3, tj = tap & 7;
+                const int e0 = wxi * 32 + 16 * kk + 8 * h + (tj & 4);
+                const __bf16 *ph = thin + ((op * 2 + 0) * 4 + (tj & 3)) * TCOPY + (yl + ti) * TPITCH + e0;
+                const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(ph);
+                const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(ph + 4);
+                Bh[tt] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+                if (PREC != 1) {
+                    const __bf16 *pl = ph + 4 * TCOPY;
+                    const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(pl);
+                    const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(pl + 4);
+                    Bl[tt] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int R = 0; R < MT; ++R) {
+                // A fragments by transposed reads: lane (i = lane&15 of group g) gets channel
+                // 16(g&1) + i, pixels 16kk + 8h + 4*half + (0..3)
+                const int gg = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
+                bf16x4 part[2][2];
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    const int row = 16 * kk + 8 * h + 4 * half + qq;
+                    const int slot = (4 * gg + pp) ^ ((row >> 1) & 7);
+                    const __bf16 *src = wimg + (size_t)(R * 2) * IMG_ELEMS + row * 32 + slot * 4;
+                    part[0][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                        (__attribute__((address_space(3))) bf16x4 *)(src));
+                    if (PREC != 1 && LAY != LAY_BLK16)
+                        part[1][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                            (__attribute__((address_space(3))) bf16x4 *)(src + IMG_ELEMS));
+                }
+                const bf16x8 Ah = __builtin_shufflevector(part[0][0], part[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                bf16x8 Al;
+                if (PREC != 1 && LAY != LAY_BLK16) Al = __builtin_shufflevector(part[1][0], part[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) {
+                    if (PREC != 1) {
+                        if (LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[tt], acc[R][tt], 0, 0, 0);
+                        acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[tt], acc[R][tt], 0, 0, 0);
+                        if (PREC == 2 && LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bl[tt], acc[R][tt], 0, 0, 0);
+                    }
+                    acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[tt], acc[R][tt], 0, 0, 0);
+                }
+            }
         }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    static_assert(RB % 2 == 0, "the row loop alternates between two landing sets");
+    Tile cur = tile_at(blockIdx.x);
+    Fat fa, fb;
+    fat_load(fa, cur, 0);
+    for (int t0 = blockIdx.x; t0 < nsteps; t0 += gridDim.x) {
+        const Tile nxt = tile_at(t0 + gridDim.x);
+        __syncthreads();                                  // previous tile's readers are done
+        if (cur.active) {
+            float tv[NSW];
+            thin_load(tv, cur);
+            thin_write(tv);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int b = 0; b < RB; b += 2) {
+            fat_load(fb, cur, b + 1);
+            if (cur.active) row_block(fa, b);
+            if (b + 2 < RB) fat_load(fa, cur, b + 2);
+            else fat_load(fa, nxt, 0);
+            if (cur.active) row_block(fb, b + 1);
+        }
+        cur = nxt;
     }
 
     // ---- sum the four waves of each group through LDS (wave 0 stores, 1..3 add in turn: fixed
@@ -1345,55 +1383,72 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
 // 32 strided partial sums each (1024 threads: the kernel is latency-bound, 16 loads per thread), combined
 // in a fixed order (deterministic).
 //   merge: both operator slots hold partials of ONE gradient (single-operator launches of k_wgrad2d): dw0 gets their sum
-__global__ __launch_bounds__(1024) void k_wgrad_reduce(const float *__restrict__ partial, int G,
-                                                       float *__restrict__ dw0, float alpha0,
-                                                       float *__restrict__ dw1, float alpha1, int M, int P, int merge = 0)
+struct WgradReduce {
+    const float *partial;    // (G, 2, M, 64)
+    int G;
+    float *dw0, *dw1;        // nullptr: operator absent
+    float alpha0, alpha1;
+    int merge;
+};
+__device__ __forceinline__ void wgrad_reduce_block(float (*red)[33], int block, const WgradReduce &q, int M, int P)
 {
-    __shared__ float red[32][33];
+    const float *__restrict__ partial = q.partial;
     const int o = threadIdx.x & 31, part = threadIdx.x >> 5;
-    const int t = blockIdx.x * 32 + o;
+    const int t = block * 32 + o;
     const int per = M * P * P;
-    const bool live = t < (merge ? per : 2 * per);
+    const bool live = t < (q.merge ? per : 2 * per);
     float sum = 0.0f;
     int op = 0, r = 0;
     if (live) {
         op = t / per; r = t % per;
         const int ch = r / (P * P), ij = r % (P * P), off = (7 - P) / 2;
         const int tap = 8 * (ij / P + off) + (ij % P + off);
-        for (int g = part; g < G; g += 32) {
+        for (int g = part; g < q.G; g += 32) {
             sum += partial[((size_t)(g * 2 + op) * M + ch) * 64 + tap];
-            if (merge) sum += partial[((size_t)(g * 2 + 1) * M + ch) * 64 + tap];
+            if (q.merge) sum += partial[((size_t)(g * 2 + 1) * M + ch) * 64 + tap];
         }
     }
     red[part][o] = sum;
     __syncthreads();
     if (part == 0 && live) {
-        float *dw = op ? dw1 : dw0;
+        float *dw = op ? q.dw1 : q.dw0;
         if (dw) {
             float tot = 0.0f;
 #pragma unroll
             for (int k = 0; k < 32; ++k) tot += red[k][o];
-            dw[r] = (op ? alpha1 : alpha0) * tot;
+            dw[r] = (op ? q.alpha1 : q.alpha0) * tot;
         }
     }
+}
+inline int wgrad_reduce_blocks(const WgradReduce &q, int M, int P) { return ((q.merge ? 1 : 2) * M * P * P + 31) / 32; }
+
+__global__ __launch_bounds__(1024) void k_wgrad_reduce(WgradReduce q, int M, int P)
+{
+    __shared__ float red[32][33];
+    wgrad_reduce_block(red, blockIdx.x, q, M, P);
 }
 
 // dt0[m] = sum over workgroups; dt1[m] = sum_n c[n] * (sum over the workgroups of image n).  4 channels x 256
 // row-strided partial sums per workgroup, tree-combined in a fixed order.
-__global__ __launch_bounds__(1024) void k_dtau_reduce(const float *__restrict__ partial,
-                                                      const float *__restrict__ c, float *__restrict__ dt0,
-                                                      float *__restrict__ dt1, int N, int per_img, int M)
+struct DtauReduce {
+    const float *partial;    // (N * per_img, M)
+    const float *c;
+    float *dt0, *dt1;
+    int N, per_img;
+};
+__device__ __forceinline__ void dtau_reduce_block(float (*r0)[4], float (*r1)[4], int block, const DtauReduce &q, int M)
 {
-    __shared__ float r0[256][4], r1[256][4];
+    const float *__restrict__ partial = q.partial;
+    const float *__restrict__ c = q.c;
     const int mi = threadIdx.x & 3, part = threadIdx.x >> 2;
-    const int m = blockIdx.x * 4 + mi;
+    const int m = block * 4 + mi;
     float a0 = 0.0f, a1 = 0.0f;
-    const int rows = N * per_img;
+    const int rows = q.N * q.per_img;
     if (m < M)
         for (int row = part; row < rows; row += 256) {
             const float v = partial[(size_t)row * M + m];
             a0 += v;
-            if (c) a1 = fmaf(c[row / per_img], v, a1);
+            if (c) a1 = fmaf(c[row / q.per_img], v, a1);
         }
     r0[part][mi] = a0;
     r1[part][mi] = a1;
@@ -1402,7 +1457,37 @@ __global__ __launch_bounds__(1024) void k_dtau_reduce(const float *__restrict__ 
         if (part < stride) { r0[part][mi] += r0[part + stride][mi]; r1[part][mi] += r1[part + stride][mi]; }
         __syncthreads();
     }
-    if (part == 0 && m < M) { dt0[m] = r0[0][mi]; dt1[m] = r1[0][mi]; }
+    if (part == 0 && m < M) { q.dt0[m] = r0[0][mi]; q.dt1[m] = r1[0][mi]; }
+}
+
+__global__ __launch_bounds__(1024) void k_dtau_reduce(DtauReduce q, int M)
+{
+    __shared__ float r0[256][4], r1[256][4];
+    dtau_reduce_block(r0, r1, blockIdx.x, q, M);
+}
+
+// Every reduction of one reverse-sweep iteration in ONE launch: the three are tiny, latency-bound grids under which the
+// device idles, so they run side by side on disjoint workgroup ranges -- [filter gradients a | filter gradients b |
+// threshold gradients].  Each range runs the code of its stand-alone kernel: same sums in the same order.
+struct SweepReduce {
+    WgradReduce w[2];
+    int wblocks[2];          // workgroups of each filter-gradient range (0: absent)
+    DtauReduce t;
+};
+__global__ __launch_bounds__(1024) void k_sweep_reduce(SweepReduce q, int M, int P)
+{
+    __shared__ float sm[2 * 256 * 4];
+    static_assert(sizeof(sm) >= 32 * 33 * sizeof(float), "k_wgrad_reduce's staging fits too");
+    int block = blockIdx.x;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (block < q.wblocks[j]) {                          // (workgroup-uniform)
+            wgrad_reduce_block(reinterpret_cast<float (*)[33]>(sm), block, q.w[j], M, P);
+            return;
+        }
+        block -= q.wblocks[j];
+    }
+    dtau_reduce_block(reinterpret_cast<float (*)[4]>(sm), reinterpret_cast<float (*)[4]>(sm + 256 * 4), block, q.t, M);
 }
 
 inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
@@ -1510,11 +1595,16 @@ int dispatch_stage(const cdl_geom *g, const FusedParams &p, int mode, const Flag
                          : launch_stage<1, 2>(p, mode, f.lin, f.lout, grid, st);
 }
 
+// persistent workgroups, one per CU (117 KB of LDS each: a CU holds one).  More than that -- it was 512 -- runs in
+// rounds, and every round pays the LDS zero pass, a cold first tile, the cross-wave sum and 32 KB of partials again
 int wgrad_grid(const cdl_geom *g)
 {
     const size_t tiles = (size_t)g->N * tiles_x(g) * ((g->H + GW_TH - 1) / GW_TH);
-    return (int)(tiles < 512 ? tiles : 512);
+    const size_t cus = (size_t)cdl_cu_count();
+    return (int)(tiles < cus ? tiles : cus);
 }
+
+size_t wgrad_region_floats(const cdl_geom *g) { return (size_t)wgrad_grid(g) * 2 * g->M * 64; }
 
 template <int MT, int PREC, int LAY>
 int launch_wgrad_one(const WgradParams &p, int G, hipStream_t st)
@@ -1626,11 +1716,19 @@ int cdl_fused2d_iter_fwd(const cdl_geom *g, const float *r, const float *zin, co
     return dispatch_stage(g, p, zin ? MODE_FWD : MODE_FIRST, f, S(stream));
 }
 
+static int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t st)
+{
+    k_wgrad_reduce<<<wgrad_reduce_blocks(job, g->M, g->Ph), 1024, 0, st>>>(job, g->M, g->Ph);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
 // r2 != nullptr: the launch also produces dA = alpha * du_out (x) im2col(r2) (cdl_fused2d_wgrad's first operator pair, same
 // arithmetic), through `workspace` (cdl_fused2d_wgrad_workspace_floats) -- one fat read of du_out less than the two-launch form
+// defer: the reduction of the dA partials is not launched but described there
 static int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map, const void *frags,
                      float *du_out, float *patches, float *dtau_partial, int do_synth, int precision, const float *r2,
-                     float alpha, float *dA, float *workspace, void *stream)
+                     float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
@@ -1648,11 +1746,9 @@ static int stage_bwd(const cdl_geom *g, const float *thin, const float *base, co
     p.r2 = r2; p.da_partial = workspace;
     int rc = dispatch_stage(g, p, MODE_BWD, f, S(stream));
     if (rc || !r2) return rc;
-    const int G = stage_grid(g, p);
-    const int total = 2 * g->M * g->Ph * g->Pw;
-    k_wgrad_reduce<<<(total + 31) / 32, 1024, 0, S(stream)>>>(workspace, G, dA, alpha, nullptr, 0.0f, g->M, g->Ph);
-    CDL_LAUNCH_CHECK();
-    return 0;
+    const WgradReduce job = {workspace, stage_grid(g, p), dA, nullptr, alpha, 0.0f, 0};
+    if (defer) { *defer = job; return 0; }                  // the sweep reduces it with the iteration's other sums
+    return launch_wgrad_reduce(g, job, S(stream));
 }
 
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
@@ -1670,7 +1766,8 @@ int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const 
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
     const int per_img = tiles_x(g) * tiles_y(g);             // partial rows: [n][tile][m]
-    k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, per_img, g->M);
+    const DtauReduce job = {dtau_partial, c, dt0, dt1, g->N, per_img};
+    k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(job, g->M);
     CDL_LAUNCH_CHECK();
     if (!dtau_n) return 0;
     return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
@@ -1679,7 +1776,9 @@ int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const 
 size_t cdl_fused2d_wgrad_workspace_floats(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
-    const size_t own = (size_t)wgrad_grid(g) * 2 * g->M * 64;
+    // two regions of per-workgroup partials: a reverse sweep holds the stage's dA_k partials in the first and k_wgrad2d's
+    // in the second until its one reduction launch per iteration; a stand-alone call uses the first
+    const size_t own = 2 * wgrad_region_floats(g);
 #ifndef CDL_F2D_WY4
     return larger(own, cdl_fused2d_wgrad_workspace_floats_wy4(g));
 #else
@@ -1687,9 +1786,10 @@ size_t cdl_fused2d_wgrad_workspace_floats(const cdl_geom *g)
 #endif
 }
 
-int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
-                      const float *X1, const float *T1, float alpha1, float *dw1, float *workspace,
-                      int precision, void *stream)
+// k_wgrad2d into `workspace`; the reduction that finishes the gradient(s) is described in *job, not launched
+static int wgrad_partials(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
+                          const float *X1, const float *T1, float alpha1, float *dw1, float *workspace,
+                          int precision, void *stream, WgradReduce *job)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!workspace || (!X0 && !X1)) return CDL_EINVAL;
@@ -1718,11 +1818,17 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
         rc = f.prec == 0 ? launch_wgrad<1, 0>(p, f.lin, G, S(stream))
              : f.prec == 1 ? launch_wgrad<1, 1>(p, f.lin, G, S(stream)) : launch_wgrad<1, 2>(p, f.lin, G, S(stream));
     if (rc) return rc;
-    const int total = 2 * g->M * g->Ph * g->Pw;
-    k_wgrad_reduce<<<(total + 31) / 32, 1024, 0, S(stream)>>>(workspace, G, X0 ? dw0 : nullptr, alpha0,
-                                                             X1 ? dw1 : nullptr, alpha1, g->M, g->Ph, p.single);
-    CDL_LAUNCH_CHECK();
+    *job = WgradReduce{workspace, G, X0 ? dw0 : nullptr, X1 ? dw1 : nullptr, alpha0, alpha1, p.single};
     return 0;
+}
+
+int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
+                      const float *X1, const float *T1, float alpha1, float *dw1, float *workspace,
+                      int precision, void *stream)
+{
+    WgradReduce job;
+    if (int rc = wgrad_partials(g, X0, T0, alpha0, dw0, X1, T1, alpha1, dw1, workspace, precision, stream, &job)) return rc;
+    return launch_wgrad_reduce(g, job, S(stream));
 }
 
 int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
@@ -1956,6 +2062,11 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
     const size_t fb = cdl_fused2d_frag_bytes(M);
     rc = prep_pairs(wB, wA, K, 0, frags, M, g->Ph, S(stream));               // (B_{k+1}, A_k) for every k, one launch
     if (rc) return rc;
+    // One reduction launch per iteration (k_sweep_reduce), after the iteration's last fat kernel: dA_k (the stage's
+    // partials, first region of the workspace), dB_k (k_wgrad2d's, second region) and the threshold gradients of k.
+    // dtau_partial is next written by stage k-1, behind that launch in stream order.
+    float *ws_a = wgrad_ws, *ws_b = wgrad_ws + wgrad_region_floats(g);
+    const int per_img = tiles_x(g) * tiles_y(g);             // dtau_partial rows: [n][tile][m]
     for (int k = K - 1, flip = 0; k >= 0; --k, flip ^= 1) {
         const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
         float *duk = du[flip];
@@ -1963,16 +2074,20 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
         // read once (by stage k-1), not twice -- 5.1 fat passes per iteration instead of 6.1 (CDL_FUSED_DA=0: the two-launch
         // form, for A/B runs)
         const bool ride = TH == GW_TH && cdl_opts().fused_da;
+        SweepReduce red = {};
         {
             TimingScope ts(1, S(stream));
             rc = stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
                            sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
-                           ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], wgrad_ws, stream);
+                           ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0]);
         }
         if (rc) return rc;
-        rc = cdl_fused2d_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
-                                     dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
-        if (rc) return rc;
+        if (ride) red.wblocks[0] = wgrad_reduce_blocks(red.w[0], M, g->Ph);
+        red.t = DtauReduce{dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, g->N, per_img};
+        if (dtau) {
+            rc = cdl_dtau_per_sample(dtau_partial, g->N, M, per_img, (size_t)per_img * M, 1, M, dtau + (size_t)k * g->N * M, stream);
+            if (rc) return rc;
+        }
         if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
             rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
             if (rc) return rc;
@@ -1983,17 +2098,20 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
             if (rc) return rc;
             {
                 TimingScope ts(2, S(stream));
-                rc = ride ? cdl_fused2d_wgrad(g, z[k - 1], q, 1.0f, dB[k], nullptr, nullptr, 0.0f, nullptr, wgrad_ws,
-                                              wprec | CDL_LAYOUT_IN(L), stream)
-                          : cdl_fused2d_wgrad(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], wgrad_ws,
-                                              wprec | CDL_LAYOUT_IN(L), stream);
+                rc = ride ? wgrad_partials(g, z[k - 1], q, 1.0f, dB[k], nullptr, nullptr, 0.0f, nullptr, ws_b,
+                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1])
+                          : wgrad_partials(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], ws_b,
+                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1]);
             }
             thin = q;
         } else if (!ride) {
-            rc = cdl_fused2d_wgrad(g, duk, yp, 1.0f, dA[0], nullptr, nullptr, 0.0f, nullptr, wgrad_ws,
-                                   wprec | CDL_LAYOUT_IN(L), stream);
+            rc = wgrad_partials(g, duk, yp, 1.0f, dA[0], nullptr, nullptr, 0.0f, nullptr, ws_b, wprec | CDL_LAYOUT_IN(L), stream,
+                                &red.w[1]);
         }
         if (rc) return rc;
+        if (k >= 1 || !ride) red.wblocks[1] = wgrad_reduce_blocks(red.w[1], M, g->Ph);
+        k_sweep_reduce<<<red.wblocks[0] + red.wblocks[1] + (M + 3) / 4, 1024, 0, S(stream)>>>(red, M, g->Ph);
+        CDL_LAUNCH_CHECK();
         base = duk;
     }
     return 0;

@@ -221,8 +221,8 @@ def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_
 def _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout=None, precision=None,
                     dyp=None, dtau=None):
     """Reverse sweep from one C call (cdl_fused2d_backward): per iteration one stage launch (1 fat read +
-    the 2-bit map of z_{k+1}, 1 fat write), a thin assemble, and one MFMA filter-gradient launch (2 fat
-    reads).  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1]."""
+    the 2-bit map of z_{k+1}, 1 fat write; dA_k rides in it), a thin assemble, one MFMA filter-gradient launch (dB_k: 1 fat
+    read) and one launch that reduces dA_k, dB_k and dt[k].  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1]."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
     return ops.fused_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,

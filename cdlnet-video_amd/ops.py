@@ -740,8 +740,9 @@ def fused_wgrad_workspace(g: Geometry, device):
 
 
 def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T1=None, alpha1=1.0,
-                precision="split3", layout="nchw"):
-    """Up to two filter gradients in one launch: dw_a = alpha_a * sum X_a (x) im2col(T_a); `layout` of X0, X1."""
+                precision="split3", layout="nchw", tiles_reversed=False):
+    """Up to two filter gradients in one launch: dw_a = alpha_a * sum X_a (x) im2col(T_a); `layout` of X0, X1.
+    tiles_reversed: walk the tiles from the last to the first (what every other launch of a sweep does)."""
     outs = []
     args = []
     for X, T, al in ((X0, T0, alpha0), (X1, T1, alpha1)):
@@ -755,7 +756,8 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
             args += [_ptr(X), _ptr(T), float(al), _ptr(dw)]
     gs = g.c_struct()
     rc = _lib.lib().cdl_fused2d_wgrad(ctypes.byref(gs), *args, _ptr(workspace),
-                                      PRECISION[precision] | _lay_in(layout), _stream())
+                                      PRECISION[precision] | _lay_in(layout) | (TILES_REVERSED if tiles_reversed else 0),
+                                      _stream())
     _lib.check(rc, "cdl_fused2d_wgrad")
     return outs
 

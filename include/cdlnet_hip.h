@@ -448,7 +448,9 @@ int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const 
 /* Filter gradients on the matrix cores: up to two independent reductions per launch
  *     dw_a[m,i,j] = alpha_a * sum_{n,y,x} Xa[n,m,y,x] * Ta[n,y-p+i,x-p+j]     (a = 0, 1; either may be absent)
  * e.g. (Xa,Ta,alpha) = (du_k, r_k, -1) -> dA_k and (z_k, q_k, +1) -> dB_k.  Two-stage and deterministic:
- * per-workgroup partial sums in `workspace`, then a fixed-order reduction.  workspace_floats() floats. */
+ * per-workgroup partial sums in `workspace`, then a fixed-order reduction.  workspace_floats() floats: two regions of
+ * partials, so that cdl_fused2d_backward can hold dA_k's and dB_k's until its one reduction launch per iteration (a
+ * stand-alone call uses the first). */
 size_t cdl_fused2d_wgrad_workspace_floats(const cdl_geom *g);
 int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
                       const float *X1, const float *T1, float alpha1, float *dw1,
@@ -462,6 +464,8 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
  * Backward (net.py forward lines in reverse): z[k] = z_{k+1}, r[k] = r_{k+1}, maps[k] as saved by the forward,
  * g_xp = dL/d(D z_K), g_z = dL/dz_K or NULL; writes dA[k], dB[k] (filter shapes) and dt (K,2,M);
  * du0/du1 fat scratch, q thin scratch, dtau_partial (tiles x M), wgrad_ws (workspace_floats).
+ * Per iteration four launches: stage (with dA_k's partials), assemble, dB_k's partials, and ONE reduction of dA_k, dB_k
+ * and dt[k] -- each summed in the order of its stand-alone entry point (bit-identical to them).
  * The gradients of the data, as cdl_ista_backward's (both NULL: neither is computed): dyp (thin, nullable) receives
  * sum_k A_k^T du_k -- the unmasked sum each assemble already forms, plus the k = 0 synthesis half (its stage then runs
  * with do_synth = 1) and one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients. */
