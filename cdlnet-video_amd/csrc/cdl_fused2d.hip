@@ -24,7 +24,7 @@
 //
 // Work decomposition: workgroup = 256 threads = 4 waves, ONE per SIMD, = 64 x 16 pixel tile of one image (2 x 2 waves of
 // 32 x 8); persistent grid, one workgroup per CU.  (Rounds 1-2: 8 waves on 64 x 32 tiles, two per SIMD so that a wave's memory
-// waits were covered by its partner -- -DCDL_WY=4 still builds that form.  One wave per SIMD costs the forward nothing and the
+// waits were covered by its partner -- Shape<4> below is that form.  One wave per SIMD costs the forward nothing and the
 // reverse stage 11 %, and frees the registers -- up to 512 per wave -- and the LDS that let the reverse stage accumulate
 // dA_k itself: one fat pass per iteration less)  Weight fragments: staged through LDS (32 KB) once per
 // workgroup, then resident in every wave's registers.  Each
@@ -40,31 +40,11 @@
 
 #include "cdl_common.h"
 
-// This file is compiled TWICE (csrc/Makefile).  The default object carries the C ABI; the second one (-DCDL_F2D_WY4) is the
-// same code on 64 x 32 tiles with two waves per SIMD -- rounds 1-2's form -- with every entry point suffixed _wy4.  The
-// whole-sweep entry points of the default object hand sweeps with bf16 code STORAGE (CDL_LAY_BLK16) to it: those kernels
-// are compute-bound, and lose at one wave per SIMD what the fp32-storage sweep gains from it (28.5 against 26.5 ms/step).
-#ifdef CDL_F2D_WY4
-#define CDL_WY 4
-#define cdl_fused2d_assemble cdl_fused2d_assemble_wy4
-#define cdl_fused2d_backward cdl_fused2d_backward_wy4
-#define cdl_fused2d_code_bytes cdl_fused2d_code_bytes_wy4
-#define cdl_fused2d_dtau_reduce cdl_fused2d_dtau_reduce_wy4
-#define cdl_fused2d_forward cdl_fused2d_forward_wy4
-#define cdl_fused2d_frag_bytes cdl_fused2d_frag_bytes_wy4
-#define cdl_fused2d_iter_fwd cdl_fused2d_iter_fwd_wy4
-#define cdl_fused2d_map_words cdl_fused2d_map_words_wy4
-#define cdl_fused2d_patch_floats cdl_fused2d_patch_floats_wy4
-#define cdl_fused2d_prep cdl_fused2d_prep_wy4
-#define cdl_fused2d_stage_bwd cdl_fused2d_stage_bwd_wy4
-#define cdl_fused2d_support_map cdl_fused2d_support_map_wy4
-#define cdl_fused2d_supported cdl_fused2d_supported_wy4
-#define cdl_fused2d_tiles cdl_fused2d_tiles_wy4
-#define cdl_fused2d_timing cdl_fused2d_timing_wy4
-#define cdl_fused2d_timing_read cdl_fused2d_timing_read_wy4
-#define cdl_fused2d_wgrad cdl_fused2d_wgrad_wy4
-#define cdl_fused2d_wgrad_workspace_floats cdl_fused2d_wgrad_workspace_floats_wy4
-#endif
+// Two tile shapes, one template argument.  Everything that works on the stage's tiles takes WY, the wave rows per workgroup
+// (Shape<WY> below): WY = 2 is the shape described above and the one every step-wise entry point uses; WY = 4 is rounds
+// 1-2's 64 x 32 tile with two waves per SIMD.  cdl_fused2d_forward / _backward run sweeps with bf16 code STORAGE
+// (CDL_LAY_BLK16) on WY = 4: those kernels are compute-bound, and lose at one wave per SIMD what the fp32-storage sweep gains
+// from it (28.5 against 26.5 ms/step).  Only the kernels such a sweep can launch exist at WY = 4 (launch_stage_lay).
 
 namespace {
 
@@ -72,28 +52,14 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-#ifndef CDL_WY
-#define CDL_WY 2                            // wave rows per workgroup: 2 (64 x 16 tiles, one wave per SIMD) or 4 (64 x 32, two)
-#endif
-constexpr int WX = 2, WY = CDL_WY;          // waves per workgroup along x / y
-constexpr int NW = WX * WY;                 // 4 waves
-constexpr int NT = 64 * NW;                 // 256 threads
+constexpr int WX = 2;                       // waves per workgroup along x
 constexpr int RB = 8;                       // row blocks (image rows) per wave
-constexpr int TW = 32 * WX, TH = RB * WY;   // 64 x 16 tile
+constexpr int TW = 32 * WX;                 // tiles are 64 pixels wide
 constexpr int HALO = 3;                     // filters are embedded in a 7 x 7 (padded 8 x 8) tap grid
-constexpr int RTW = TW + 2 * HALO, RTH = TH + 2 * HALO;   // 70 x 22 residual tile / patch
+constexpr int RTW = TW + 2 * HALO;          // 70 columns of residual tile / patch
 constexpr int RTC = RTW + 2;                // columns kept in LDS (col 70 is the zero-weight pad tap)
-constexpr int PITCH = WY == 2 ? 28 : 44;    // bf16 elements per LDS column (>= RTH + 2; 56 / 88 B: 14 / 22 dwords between the columns of
-                                            // neighbouring lanes -- conflict-free b64 reads)
-constexpr int COPY = RTC * PITCH;           // elements per shifted copy
-constexpr int LDS_RT = 2 * 4 * COPY * 2;    // bytes: {hi,lo} x 4 row-shifted copies             (50688)
-constexpr int SLAB = RTH * RTW;             // floats per col2im slab
-constexpr int LDS_RSUM = 4 * SLAB * 4;      // 4 slabs by wave parity (wxi&1, wyi&1): waves sharing a slab
-                                            // never touch the same word, slabs are summed in a fixed order
 constexpr int LDS_W = 32 * 64 * 16;         // 32 weight fragments of 1 KB (split3, M = 64)
 constexpr int LDS_TAU = 64 * 4;
-constexpr int LDS_TACC = NW * 64 * 4;
-constexpr int LDS_STAGE = LDS_RT + LDS_RSUM + LDS_W + LDS_TAU + LDS_TACC;
 
 constexpr int GW_TH = 16;                    // tile rows of the filter-gradient kernel
 constexpr int GW_RTH = GW_TH + 2 * HALO;     // 22
@@ -103,8 +69,31 @@ constexpr int TCOPY = TROWS * TPITCH;
 constexpr int WG_THIN_BYTES = 2 * 2 * 4 * TCOPY * 2;      // [op][hl][shift] copies               (52992)
 constexpr int IMG_ELEMS = 32 * 32;           // one [32 px][32 ch] bf16 image (2 KB)
 
-constexpr int LDS_DA_THIN = 2 * 4 * TCOPY * 2;           // reverse stage with dA_k: r_k as [hl][shift] copies   (26496)
-constexpr int LDS_DA = LDS_DA_THIN + NW * 2 * 2 * IMG_ELEMS * 2;   // + [wave][channel tile][hl] transposition images
+// What depends on the tile height.  WY_ = wave rows per workgroup: 2 (64 x 16 tiles, one wave per SIMD) or 4 (64 x 32, two).
+// The values in the comments are those of WY_ = 2.
+template <int WY_>
+struct Shape {
+    static_assert(WY_ == 2 || WY_ == 4, "64 x 16 or 64 x 32 tiles");
+    static constexpr int WY = WY_;
+    static constexpr int NW = WX * WY;                 // 4 waves
+    static constexpr int NT = 64 * NW;                 // 256 threads
+    static constexpr int TH = RB * WY;                 // 64 x 16 tile
+    static constexpr int RTH = TH + 2 * HALO;          // 70 x 22 residual tile / patch
+    static constexpr int PITCH = WY == 2 ? 28 : 44;    // bf16 elements per LDS column (>= RTH + 2; 56 / 88 B: 14 / 22 dwords between the
+                                                       // columns of neighbouring lanes -- conflict-free b64 reads)
+    static constexpr int COPY = RTC * PITCH;           // elements per shifted copy
+    static constexpr int LDS_RT = 2 * 4 * COPY * 2;    // bytes: {hi,lo} x 4 row-shifted copies             (32256)
+    static constexpr int SLAB = RTH * RTW;             // floats per col2im slab
+    static constexpr int LDS_RSUM = 4 * SLAB * 4;      // 4 slabs by wave parity (wxi&1, wyi&1): waves sharing a slab
+                                                       // never touch the same word, slabs are summed in a fixed order
+    static constexpr int LDS_TACC = NW * 64 * 4;
+    static constexpr int LDS_STAGE = LDS_RT + LDS_RSUM + LDS_W + LDS_TAU + LDS_TACC;
+    static constexpr int LDS_DA_THIN = 2 * 4 * TCOPY * 2;      // reverse stage with dA_k: r_k as [hl][shift] copies   (26496)
+    static constexpr int LDS_DA = LDS_DA_THIN + NW * 2 * 2 * IMG_ELEMS * 2;   // + [wave][channel tile][hl] transposition images
+    static constexpr int NSTG = (RTH * RTW + NT - 1) / NT;     // thin-tile elements staged per thread
+    // One wave per SIMD: every weight fragment of the launch lives in the wave's registers; two: read from LDS where used
+    static constexpr bool WREG = WY == 2;
+};
 
 struct FusedParams {
     const float *r;          // (N,H,W) thin input of the analysis-like half (r_k, yp, q_{k+1} or g_xp)
@@ -400,9 +389,13 @@ __device__ __forceinline__ float col2im_row(const float (&rv)[4], int h)
 //   LIN / LOUT: layouts of zin and zout (LAY_*)
 //   DA (reverse stage only): the filter gradient dA_k = du_k (x) im2col(r2) rides in the launch -- du_k is transposed per row
 //   block through wave-private LDS images exactly as k_wgrad2d does it, and accumulated in 2 x MT more accumulator tiles
-template <int MT, int PREC, int MODE, int LIN, int LOUT, bool DA = false>
-__global__ __launch_bounds__(NT) void k_stage(FusedParams p)
+//   WY: the tile shape (Shape<WY>)
+template <int MT, int PREC, int MODE, int LIN, int LOUT, bool DA = false, int WY = 2>
+__global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
 {
+    using G = Shape<WY>;
+    constexpr int NW = G::NW, NT = G::NT, TH = G::TH, RTH = G::RTH, PITCH = G::PITCH, COPY = G::COPY, SLAB = G::SLAB;
+    constexpr int LDS_RT = G::LDS_RT, LDS_RSUM = G::LDS_RSUM, LDS_STAGE = G::LDS_STAGE, LDS_DA_THIN = G::LDS_DA_THIN;
     static_assert(!DA || (MODE == MODE_BWD && TH == GW_TH), "dA_k rides in the reverse stage, on k_wgrad2d's 64 x 16 tiles");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __bf16 *rt = reinterpret_cast<__bf16 *>(smem);                               // [hl][q][col][PITCH]
@@ -416,7 +409,7 @@ __global__ __launch_bounds__(NT) void k_stage(FusedParams p)
     constexpr int M = 32 * MT;
     constexpr int FA = MT * 4, FB = 4 * MT;
     constexpr int NFRAG = (PREC != 1 ? 2 : 1) * (FA + FB);   // bf16 mode stages only the hi fragments
-    constexpr int NSTG = (RTH * RTW + NT - 1) / NT;          // thin-tile elements staged per thread
+    constexpr int NSTG = G::NSTG;                            // thin-tile elements staged per thread
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wxi = wid % WX, wyi = wid / WX;
     const int c = lane & 31, h = lane >> 5;
@@ -533,7 +526,7 @@ __global__ __launch_bounds__(NT) void k_stage(FusedParams p)
     // One wave per SIMD: every weight fragment of the launch lives in this wave's registers (32 x 4 at M = 64, split3; the
     // 512-register budget has the room) -- with no partner wave on the SIMD, the LDS latency of a fragment read in front of
     // (almost) every MFMA was most of the row block's time.  Two waves per SIMD: read from LDS where used.
-    constexpr bool WREG = WY == 2;
+    constexpr bool WREG = G::WREG;
     bf16x8 wreg[WREG ? NFRAG : 1];
     if constexpr (WREG) {
 #pragma unroll
@@ -975,9 +968,11 @@ __global__ __launch_bounds__(NT) void k_stage(FusedParams p)
 // out[n,Y,X] = (mask ? mask : 1) * alpha * sum_{patches covering (Y,X)} patch - (sub ? sub : 0)
 // A pixel is covered by its own tile's patch and, within HALO of a tile border, by the neighbour's across
 // that border (and the diagonal one in a corner): at most 4 patches, visited in (tile row, tile column) order.
+template <int WY>
 __device__ __forceinline__ float patch_sum(const float *__restrict__ patches, int n, int Y, int X,
                                            int tilesX, int tilesY)
 {
+    constexpr int TH = Shape<WY>::TH, SLAB = Shape<WY>::SLAB;
     const int tyc = Y / TH, txc = X / TW;
     const int ly = Y - tyc * TH, lx = X - txc * TW;
     const int hx = (lx < HALO && txc > 0) ? -1 : ((lx >= TW - HALO && txc + 1 < tilesX) ? 1 : 0);
@@ -1004,7 +999,7 @@ __device__ __forceinline__ float patch_sum(const float *__restrict__ patches, in
 
 // ASM_ROWS image rows per thread: 4 for batches (fewer, fatter workgroups, 4 independent load chains), 1 for
 // single small images where the launch is latency-bound and wants every workgroup it can get
-template <int ASM_ROWS>
+template <int ASM_ROWS, int WY>
 __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patches,
                                                   const float *__restrict__ mask,
                                                   const float *__restrict__ sub, float alpha,
@@ -1019,7 +1014,7 @@ __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patc
         const int Y = blockIdx.y * ASM_ROWS + j;
         if (Y >= H) break;
         const size_t i = ((size_t)n * H + Y) * W + X;
-        const float raw = patch_sum(patches, n, Y, X, tilesX, tilesY);
+        const float raw = patch_sum<WY>(patches, n, Y, X, tilesX, tilesY);
         if (acc) acc[i] = acc_add ? acc[i] + raw : raw;
         if (!out) continue;
         float sum = alpha * raw;
@@ -1031,11 +1026,13 @@ __global__ __launch_bounds__(256) void k_assemble(const float *__restrict__ patc
 
 // Batch form (W % 4 == 0): a thread owns 4 consecutive pixels of 2 rows -- the thin operands move as 16-byte vectors,
 // a quarter of the threads issue half the memory instructions per pixel (same sums in the same order: bit-identical)
+template <int WY>
 __global__ __launch_bounds__(256) void k_assemble_v4(const float *__restrict__ patches,
                                                      const float *__restrict__ mask, const float *__restrict__ sub,
                                                      float alpha, float *__restrict__ out, int N, int H, int W,
                                                      int tilesX, int tilesY, float *__restrict__ accum, int acc_add)
 {
+    constexpr int TH = Shape<WY>::TH, SLAB = Shape<WY>::SLAB;
     // 4 consecutive pixels x 2 rows per thread.  The terms of a pixel are added in patch_sum's order (row above, own
     // row, row below; left neighbour, own tile, right neighbour), but the row candidates are wave-uniform branches and
     // the 8 loads of a patch row (4 own + up to 4 from the horizontal neighbour) are issued side by side instead of as
@@ -1505,7 +1502,7 @@ inline bool fused_shape_ok(const cdl_geom *g)
 inline int debug_flags() { return cdl_opts().fused_debug; }
 
 inline int tiles_x(const cdl_geom *g) { return (g->W + TW - 1) / TW; }
-inline int tiles_y(const cdl_geom *g) { return (g->H + TH - 1) / TH; }
+template <int WY> inline int tiles_y(const cdl_geom *g) { return (g->H + Shape<WY>::TH - 1) / Shape<WY>::TH; }
 
 // `precision` argument of the entry points: bits 0-3 arithmetic (0 split-bf16 x3, 1 plain bf16, 2 split-bf16 x4: the
 // lo * lo products as well -- exact fp32 products, for objectives that difference two forward passes), bit 4
@@ -1525,52 +1522,56 @@ inline Flags parse_flags(int precision)
     return f;
 }
 
-template <int MT, int PREC, int MODE, int LIN, int LOUT>
+template <int WY, int MT, int PREC, int MODE, int LIN, int LOUT>
 int launch_stage_one(const FusedParams &p, dim3 grid, hipStream_t st)
 {
-    if constexpr (MODE == MODE_BWD && TH == GW_TH) {
+    using G = Shape<WY>;
+    if constexpr (MODE == MODE_BWD && G::TH == GW_TH) {
         if (p.r2) {                                          // the reverse stage that also accumulates dA_k
-            if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true>, LDS_STAGE + LDS_DA)) return rc;
-            k_stage<MT, PREC, MODE, LIN, LOUT, true><<<grid, NT, LDS_STAGE + LDS_DA, st>>>(p);
+            if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true, WY>, G::LDS_STAGE + G::LDS_DA)) return rc;
+            k_stage<MT, PREC, MODE, LIN, LOUT, true, WY><<<grid, G::NT, G::LDS_STAGE + G::LDS_DA, st>>>(p);
             hipError_t e = hipGetLastError();
             return e == hipSuccess ? 0 : -(int)e;
         }
     }
     if (p.r2) return CDL_EUNSUPPORTED;
-    if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT>, LDS_STAGE)) return rc;
-    k_stage<MT, PREC, MODE, LIN, LOUT><<<grid, NT, LDS_STAGE, st>>>(p);
+    if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, false, WY>, G::LDS_STAGE)) return rc;
+    k_stage<MT, PREC, MODE, LIN, LOUT, false, WY><<<grid, G::NT, G::LDS_STAGE, st>>>(p);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
 }
 
 // The layout pairs the sweeps and the step-wise entry points use: same layout on both sides, or NCHW on one
 // side (z_K leaves a sweep as NCHW, a user gradient enters one as NCHW).  MODE_FIRST has no fat input.
-template <int MT, int PREC, int MODE>
+// WY = 4 exists for sweeps with bf16 code storage only, and only the pairs such a sweep launches are instantiated:
+//   FIRST (BLK16, BLK16) k = 0 of K > 1     FWD (BLK16, BLK16) 0 < k < K-1     BWD (NCHW, BLK16)  k = K-1
+//   FIRST (NCHW, NCHW)   k = 0 of K = 1     FWD (BLK16, NCHW)  k = K-1 > 0     BWD (BLK16, BLK16) k < K-1
+template <int WY, int MT, int PREC, int MODE>
 int launch_stage_lay(const FusedParams &p, int lin, int lout, dim3 grid, hipStream_t st)
 {
     if (MODE == MODE_FIRST) lin = lout;
-#define CDL_LAY_CASE(a, b) if (lin == a && lout == b) return launch_stage_one<MT, PREC, MODE, a, b>(p, grid, st)
-    CDL_LAY_CASE(LAY_NCHW, LAY_NCHW);
-    CDL_LAY_CASE(LAY_BLK, LAY_BLK);
+#define CDL_LAY_CASE(a, b) if (lin == a && lout == b) return launch_stage_one<WY, MT, PREC, MODE, a, b>(p, grid, st)
+    if constexpr (WY == 2 || MODE == MODE_FIRST) CDL_LAY_CASE(LAY_NCHW, LAY_NCHW);
+    if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_BLK);
     CDL_LAY_CASE(LAY_BLK16, LAY_BLK16);
     if constexpr (MODE == MODE_FWD) {
-        CDL_LAY_CASE(LAY_BLK, LAY_NCHW);
+        if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);
         CDL_LAY_CASE(LAY_BLK16, LAY_NCHW);
     }
     if constexpr (MODE == MODE_BWD) {
-        CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
+        if constexpr (WY == 2) CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
         CDL_LAY_CASE(LAY_NCHW, LAY_BLK16);
     }
 #undef CDL_LAY_CASE
     return CDL_EUNSUPPORTED;
 }
 
-template <int MT, int PREC>
+template <int WY, int MT, int PREC>
 int launch_stage(const FusedParams &p, int mode, int lin, int lout, dim3 grid, hipStream_t st)
 {
-    if (mode == MODE_FWD) return launch_stage_lay<MT, PREC, MODE_FWD>(p, lin, lout, grid, st);
-    if (mode == MODE_FIRST) return launch_stage_lay<MT, PREC, MODE_FIRST>(p, lin, lout, grid, st);
-    return launch_stage_lay<MT, PREC, MODE_BWD>(p, lin, lout, grid, st);
+    if (mode == MODE_FWD) return launch_stage_lay<WY, MT, PREC, MODE_FWD>(p, lin, lout, grid, st);
+    if (mode == MODE_FIRST) return launch_stage_lay<WY, MT, PREC, MODE_FIRST>(p, lin, lout, grid, st);
+    return launch_stage_lay<WY, MT, PREC, MODE_BWD>(p, lin, lout, grid, st);
 }
 
 // persistent workgroups: one per CU (most of its LDS each), striding over the tiles
@@ -1583,16 +1584,17 @@ int stage_grid(const cdl_geom *, const FusedParams &p)
     return (int)(tiles < cus ? tiles : cus);
 }
 
+template <int WY>
 int dispatch_stage(const cdl_geom *g, const FusedParams &p, int mode, const Flags &f, hipStream_t st)
 {
     dim3 grid((unsigned)stage_grid(g, p));
     if (g->M == 64)
-        return f.prec == 0   ? launch_stage<2, 0>(p, mode, f.lin, f.lout, grid, st)
-               : f.prec == 1 ? launch_stage<2, 1>(p, mode, f.lin, f.lout, grid, st)
-                             : launch_stage<2, 2>(p, mode, f.lin, f.lout, grid, st);
-    return f.prec == 0   ? launch_stage<1, 0>(p, mode, f.lin, f.lout, grid, st)
-           : f.prec == 1 ? launch_stage<1, 1>(p, mode, f.lin, f.lout, grid, st)
-                         : launch_stage<1, 2>(p, mode, f.lin, f.lout, grid, st);
+        return f.prec == 0   ? launch_stage<WY, 2, 0>(p, mode, f.lin, f.lout, grid, st)
+               : f.prec == 1 ? launch_stage<WY, 2, 1>(p, mode, f.lin, f.lout, grid, st)
+                             : launch_stage<WY, 2, 2>(p, mode, f.lin, f.lout, grid, st);
+    return f.prec == 0   ? launch_stage<WY, 1, 0>(p, mode, f.lin, f.lout, grid, st)
+           : f.prec == 1 ? launch_stage<WY, 1, 1>(p, mode, f.lin, f.lout, grid, st)
+                         : launch_stage<WY, 1, 2>(p, mode, f.lin, f.lout, grid, st);
 }
 
 // persistent workgroups, one per CU (117 KB of LDS each: a CU holds one).  More than that -- it was 512 -- runs in
@@ -1624,44 +1626,334 @@ int launch_wgrad(const WgradParams &p, int lay, int G, hipStream_t st)
     return launch_wgrad_one<MT, PREC, LAY_NCHW>(p, G, st);
 }
 
+inline size_t larger(size_t a, size_t b) { return a > b ? a : b; }
+template <int WY> inline size_t shape_tiles(const cdl_geom *g) { return (size_t)g->N * tiles_x(g) * tiles_y<WY>(g); }
+
+// ---- the bodies behind the entry points that depend on the tile shape ------------------------------------
+// what every stage launch sets, forward or reverse
+template <int WY>
+FusedParams stage_params(const cdl_geom *g, const Flags &f, const void *frags, float *patches)
+{
+    FusedParams p = {};
+    p.rev = f.rev;
+    p.frags = reinterpret_cast<const uint4 *>(frags);
+    p.patches = patches; CDL_DBG_FIELD(p.dbg = debug_flags();)
+    p.N = g->N; p.H = g->H; p.W = g->W;
+    p.tilesX = tiles_x(g); p.tilesY = tiles_y<WY>(g);
+    return p;
+}
+
+template <int WY>
+int iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *tau, const void *frags, float sgn,
+             float *zout, float *patches, unsigned *map_out, int precision, void *stream)
+{
+    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
+    if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
+    const Flags f = parse_flags(precision);
+    if (!f.ok) return CDL_EINVAL;
+    FusedParams p = stage_params<WY>(g, f, frags, patches);
+    p.r = r; p.zin = zin; p.zout = zout; p.tau = tau; p.map = map_out;
+    p.sgn = sgn; p.do_synth = 1;
+    return dispatch_stage<WY>(g, p, zin ? MODE_FWD : MODE_FIRST, f, S(stream));
+}
+
+int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t st)
+{
+    k_wgrad_reduce<<<wgrad_reduce_blocks(job, g->M, g->Ph), 1024, 0, st>>>(job, g->M, g->Ph);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+// r2 != nullptr: the launch also produces dA = alpha * du_out (x) im2col(r2) (cdl_fused2d_wgrad's first operator pair, same
+// arithmetic), through `workspace` (cdl_fused2d_wgrad_workspace_floats) -- one fat read of du_out less than the two-launch form
+// defer: the reduction of the dA partials is not launched but described there
+template <int WY>
+int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map, const void *frags,
+              float *du_out, float *patches, float *dtau_partial, int do_synth, int precision, const float *r2,
+              float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr)
+{
+    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
+    if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
+    if (do_synth && !patches) return CDL_EINVAL;
+    if (r2 && (!dA || !workspace)) return CDL_EINVAL;
+    const Flags f = parse_flags(precision);
+    if (!f.ok) return CDL_EINVAL;
+    FusedParams p = stage_params<WY>(g, f, frags, patches);
+    p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
+    p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0;
+    p.r2 = r2; p.da_partial = workspace;
+    int rc = dispatch_stage<WY>(g, p, MODE_BWD, f, S(stream));
+    if (rc || !r2) return rc;
+    const WgradReduce job = {workspace, stage_grid(g, p), dA, nullptr, alpha, 0.0f, 0};
+    if (defer) { *defer = job; return 0; }                  // the sweep reduces it with the iteration's other sums
+    return launch_wgrad_reduce(g, job, S(stream));
+}
+
+// k_wgrad2d into `workspace`; the reduction that finishes the gradient(s) is described in *job, not launched
+int wgrad_partials(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
+                   const float *X1, const float *T1, float alpha1, float *dw1, float *workspace,
+                   int precision, void *stream, WgradReduce *job)
+{
+    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
+    if (!workspace || (!X0 && !X1)) return CDL_EINVAL;
+    if ((X0 && (!T0 || !dw0)) || (X1 && (!T1 || !dw1))) return CDL_EINVAL;
+    const Flags f = parse_flags(precision);
+    if (!f.ok) return CDL_EINVAL;
+    WgradParams p = {};
+    p.rev = f.rev;
+    p.X[0] = X0; p.T[0] = T0; p.X[1] = X1; p.T[1] = T1;
+    p.single = (X0 != nullptr) != (X1 != nullptr);
+    if (p.single) {                                         // one gradient: both wave groups on it
+        if (!X0) { X0 = X1; T0 = T1; alpha0 = alpha1; dw0 = dw1; X1 = nullptr; }
+        p.X[0] = p.X[1] = X0; p.T[0] = p.T[1] = T0;
+    }
+    p.partial = workspace;
+    p.N = g->N; p.H = g->H; p.W = g->W;
+    p.tilesX = tiles_x(g); p.tilesY = (g->H + GW_TH - 1) / GW_TH;
+    p.numTiles = p.N * p.tilesX * p.tilesY;
+    int G = wgrad_grid(g);
+    if (p.single && G > (p.numTiles + 1) / 2) G = (p.numTiles + 1) / 2;
+    int rc;
+    if (g->M == 64)
+        rc = f.prec == 0 ? launch_wgrad<2, 0>(p, f.lin, G, S(stream))
+             : f.prec == 1 ? launch_wgrad<2, 1>(p, f.lin, G, S(stream)) : launch_wgrad<2, 2>(p, f.lin, G, S(stream));
+    else
+        rc = f.prec == 0 ? launch_wgrad<1, 0>(p, f.lin, G, S(stream))
+             : f.prec == 1 ? launch_wgrad<1, 1>(p, f.lin, G, S(stream)) : launch_wgrad<1, 2>(p, f.lin, G, S(stream));
+    if (rc) return rc;
+    *job = WgradReduce{workspace, G, X0 ? dw0 : nullptr, X1 ? dw1 : nullptr, alpha0, alpha1, p.single};
+    return 0;
+}
+
+template <int WY>
+int assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha, float *out,
+             float *acc, int acc_add, void *stream)
+{
+    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
+    if (!patches || (!out && !acc)) return CDL_EINVAL;
+    const int tx = tiles_x(g), ty = tiles_y<WY>(g);
+    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
+        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
+        k_assemble_v4<WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+    } else if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20)) {
+        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)g->N);
+        k_assemble<4, WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+    } else {
+        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)g->N);
+        k_assemble<1, WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+    }
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+/* ---- optional per-kernel timing inside the sweeps (HIP events on the launch stream) -------------------
+ * bench.py turns it on for a few steps to report the in-step average duration of the three fat kernels
+ * (isolated re-launches of one kernel miss the cache state the step leaves behind).  Off: no events. */
+// Process-wide and mutex-guarded: the one piece of state of this file, used by bench.py only.  Events are
+// recorded on whichever stream the timed sweep runs on; pairs of different devices are kept apart by the
+// device they were created on (an event can only be recorded on its own device's streams).
+struct TimingState {
+    std::mutex mu;
+    std::atomic<bool> on{false};
+    struct Pair { hipEvent_t start, stop; int cls, dev; };
+    std::vector<Pair> pairs;               // in launch order; class 0 forward stage (k >= 1), 1 reverse stage,
+                                           // 2 filter gradients, 3 first forward stage (k = 0: no fat read)
+    std::vector<std::pair<hipEvent_t, int>> spare;     // recycled events with their device
+};
+TimingState g_timing;
+
+struct TimingScope {
+    hipStream_t st;
+    hipEvent_t stop = nullptr;
+    TimingScope(int c, hipStream_t s) : st(s)
+    {
+        if (!g_timing.on.load(std::memory_order_relaxed)) return;
+        std::lock_guard<std::mutex> lk(g_timing.mu);
+        const int dev = cdl_current_device();
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; ++i) {
+            for (size_t k = 0; k < g_timing.spare.size() && !ev[i]; ++k)
+                if (g_timing.spare[k].second == dev) {
+                    ev[i] = g_timing.spare[k].first;
+                    g_timing.spare.erase(g_timing.spare.begin() + k);
+                }
+            if (!ev[i] && hipEventCreate(&ev[i]) != hipSuccess) return;
+        }
+        (void)hipEventRecord(ev[0], st);
+        stop = ev[1];
+        g_timing.pairs.push_back({ev[0], ev[1], c, dev});
+    }
+    ~TimingScope()
+    {
+        if (stop) (void)hipEventRecord(stop, st);
+    }
+};
+
+/* ---- whole sweeps: every launch of a forward / reverse pass enqueued from one C call ----------------
+ * Snake order: consecutive fat launches walk the tiles in opposite directions, so each one starts on
+ * the bytes the previous one touched last, which are still in the 256 MiB Infinity Cache (it holds
+ * the last ~256 MiB loaded or stored).  Tile results do not depend on the order; only the filter
+ * gradients' per-workgroup partial sums are grouped differently.  CDL_FUSED_SNAKE=0 turns it off. */
+// fragments of K (analysis-like, synthesis-like) pairs, pair k at frags + k * cdl_fused2d_frag_bytes(M)
+int prep_pairs(const float *const *w1, const float *const *w2, int K, int shift2, void *frags, int M, int P,
+               hipStream_t st)
+{
+    const int MT = M / 32, threads = 8 * MT * 64;
+    const int frag_uint4 = (int)(cdl_fused2d_frag_bytes(M) / 16);
+    for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
+        const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
+        PrepBatch b = {};
+        for (int i = 0; i < nb; ++i) {
+            const int k = k0 + i;
+            // forward: (A_k, B_{k+1 mod K});  backward: (B_{k+1 mod K}, A_k) -- the shifted bank is index shift2
+            b.wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
+            b.wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
+        }
+        dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
+        k_prep_batch<<<grid, 256, 0, st>>>(b, reinterpret_cast<uint4 *>(frags) + (size_t)k0 * frag_uint4, frag_uint4, MT, P);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return -(int)e;
+    }
+    return 0;
+}
+
+int snake_enabled() { return cdl_opts().fused_snake; }
+
+// Sweeps: CDL_LAYOUT_IN(L) in `precision` selects the layout L of the tensors that stay inside the sweeps --
+// z_1 .. z_{K-1} (z[0..K-2]) and the du ping-pong buffers; z_K (z[K-1]) and g_z are always NCHW fp32.
+// The C entry points have checked the arguments and picked WY from L.
+template <int WY>
+int forward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
+                  const float *const *wA, const float *const *wB, float *const *z, float *const *r,
+                  unsigned *const *maps, float *xp, void *frags, float *patches, const Flags &f, void *stream)
+{
+    const size_t nm = (size_t)g->N * g->M;
+    const int snake = snake_enabled();
+    const int L = f.lin;
+    const float *thin = yp;
+    const size_t fb = cdl_fused2d_frag_bytes(g->M);
+    int rc = prep_pairs(wA, wB, K, 1, frags, g->M, g->Ph, S(stream));       // (A_k, B_{k+1}) for every k, one launch
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) {
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
+        {
+            TimingScope ts(k ? 0 : 3, S(stream));
+            rc = iter_fwd<WY>(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k],
+                              patches, maps ? maps[k] : nullptr,
+                              f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(k == K - 1 ? LAY_NCHW : L) |
+                                  ((k & 1) && snake ? CDL_TILES_REVERSED : 0),
+                              stream);
+        }
+        if (rc) return rc;
+        if (k < K - 1) {
+            rc = assemble<WY>(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
+            thin = r[k];
+        } else {
+            rc = assemble<WY>(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+template <int WY>
+int backward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
+                   const float *const *wA, const float *const *wB, const float *const *z,
+                   const float *const *r, const unsigned *const *maps, const float *g_xp,
+                   const float *g_z, float *const *dA,
+                   float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
+                   float *patches, float *dtau_partial, float *wgrad_ws, const Flags &f, float *dyp,
+                   float *dtau, void *stream)
+{
+    const int M = g->M;
+    float *du[2] = {du0, du1};
+    const int L = f.lin;
+    // the forward's last launch ran in direction (K-1)&1: stages take that one, filter gradients the other
+    const int sdir = snake_enabled() ? (((K - 1) & 1) ? CDL_TILES_REVERSED : 0) : 0;
+    const int wdir = snake_enabled() ? (sdir ^ CDL_TILES_REVERSED) : 0;
+    const int sprec = f.prec | sdir, wprec = f.prec | wdir;
+    int rc = cdl_fused2d_wgrad(g, z[K - 1], g_xp, 1.0f, dB[0], nullptr, nullptr, 0.0f, nullptr, wgrad_ws,
+                               wprec, stream);                           // dB_0 = z_K (x) dL/d(D z_K); z_K is NCHW
+    if (rc) return rc;
+    const float *thin = g_xp, *base = g_z;
+    const size_t fb = cdl_fused2d_frag_bytes(M);
+    rc = prep_pairs(wB, wA, K, 0, frags, M, g->Ph, S(stream));               // (B_{k+1}, A_k) for every k, one launch
+    if (rc) return rc;
+    // One reduction launch per iteration (k_sweep_reduce), after the iteration's last fat kernel: dA_k (the stage's
+    // partials, first region of the workspace), dB_k (k_wgrad2d's, second region) and the threshold gradients of k.
+    // dtau_partial is next written by stage k-1, behind that launch in stream order.
+    float *ws_a = wgrad_ws, *ws_b = wgrad_ws + wgrad_region_floats(g);
+    const int per_img = tiles_x(g) * tiles_y<WY>(g);         // dtau_partial rows: [n][tile][m]
+    for (int k = K - 1, flip = 0; k >= 0; --k, flip ^= 1) {
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
+        float *duk = du[flip];
+        // dA_k = -du_k (x) r_k (k = 0: du_0 (x) yp) rides in the reverse stage, which has du_k in its registers: du_k is
+        // read once (by stage k-1), not twice -- 5.1 fat passes per iteration instead of 6.1 (CDL_FUSED_DA=0: the two-launch
+        // form, for A/B runs).  On 64 x 32 tiles it does not: k_wgrad2d takes both operand pairs
+        const bool ride = Shape<WY>::TH == GW_TH && cdl_opts().fused_da;
+        SweepReduce red = {};
+        {
+            TimingScope ts(1, S(stream));
+            rc = stage_bwd<WY>(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
+                               sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
+                               ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0]);
+        }
+        if (rc) return rc;
+        if (ride) red.wblocks[0] = wgrad_reduce_blocks(red.w[0], M, g->Ph);
+        red.t = DtauReduce{dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, g->N, per_img};
+        if (dtau) {
+            rc = cdl_dtau_per_sample(dtau_partial, g->N, M, per_img, (size_t)per_img * M, 1, M, dtau + (size_t)k * g->N * M, stream);
+            if (rc) return rc;
+        }
+        if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
+            rc = assemble<WY>(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
+            if (rc) return rc;
+        }
+        if (k >= 1) {
+            // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
+            rc = assemble<WY>(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
+            if (rc) return rc;
+            {
+                TimingScope ts(2, S(stream));
+                rc = ride ? wgrad_partials(g, z[k - 1], q, 1.0f, dB[k], nullptr, nullptr, 0.0f, nullptr, ws_b,
+                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1])
+                          : wgrad_partials(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], ws_b,
+                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1]);
+            }
+            thin = q;
+        } else if (!ride) {
+            rc = wgrad_partials(g, duk, yp, 1.0f, dA[0], nullptr, nullptr, 0.0f, nullptr, ws_b, wprec | CDL_LAYOUT_IN(L), stream,
+                                &red.w[1]);
+        }
+        if (rc) return rc;
+        if (k >= 1 || !ride) red.wblocks[1] = wgrad_reduce_blocks(red.w[1], M, g->Ph);
+        k_sweep_reduce<<<red.wblocks[0] + red.wblocks[1] + (M + 3) / 4, 1024, 0, S(stream)>>>(red, M, g->Ph);
+        CDL_LAUNCH_CHECK();
+        base = duk;
+    }
+    return 0;
+}
+
 }  // namespace
 
+// The C ABI.  Step-wise entry points always work on 64 x 16 tiles; the two sweeps pick the shape from the code layout.
 extern "C" {
 
 int cdl_fused2d_supported(const cdl_geom *g) { return fused_shape_ok(g) ? 1 : 0; }
 
 size_t cdl_fused2d_frag_bytes(int M) { return (size_t)2 * (M / 32) * 8 * 64 * 16; }
 
-// (buffers a caller sizes with these serve sweeps of either object: the larger of the two tile geometries)
-#ifndef CDL_F2D_WY4
-size_t cdl_fused2d_patch_floats_wy4(const cdl_geom *g);
-size_t cdl_fused2d_tiles_wy4(const cdl_geom *g);
-size_t cdl_fused2d_wgrad_workspace_floats_wy4(const cdl_geom *g);
-static size_t larger(size_t a, size_t b) { return a > b ? a : b; }
-#else
-static size_t larger(size_t a, size_t) { return a; }
-#endif
-
+// (buffers a caller sizes with these serve sweeps on either tile shape: the larger of the two needs)
 size_t cdl_fused2d_patch_floats(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
-    const size_t own = (size_t)g->N * tiles_x(g) * tiles_y(g) * SLAB;
-#ifndef CDL_F2D_WY4
-    return larger(own, cdl_fused2d_patch_floats_wy4(g));
-#else
-    return own;
-#endif
+    return larger(shape_tiles<2>(g) * Shape<2>::SLAB, shape_tiles<4>(g) * Shape<4>::SLAB);
 }
 
 size_t cdl_fused2d_tiles(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
-    const size_t own = (size_t)g->N * tiles_x(g) * tiles_y(g);
-#ifndef CDL_F2D_WY4
-    return larger(own, cdl_fused2d_tiles_wy4(g));
-#else
-    return own;
-#endif
+    return larger(shape_tiles<2>(g), shape_tiles<4>(g));
 }
 
 int cdl_fused2d_prep(const float *wA, const float *wB, void *frags, int M, int P, void *stream)
@@ -1702,53 +1994,7 @@ int cdl_fused2d_iter_fwd(const cdl_geom *g, const float *r, const float *zin, co
                          const void *frags, float sgn, float *zout, float *patches, unsigned *map_out,
                          int precision, void *stream)
 {
-    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
-    const Flags f = parse_flags(precision);
-    if (!f.ok) return CDL_EINVAL;
-    FusedParams p = {};
-    p.rev = f.rev;
-    p.r = r; p.zin = zin; p.zout = zout; p.tau = tau; p.map = map_out;
-    p.frags = reinterpret_cast<const uint4 *>(frags);
-    p.patches = patches; p.sgn = sgn; p.do_synth = 1; CDL_DBG_FIELD(p.dbg = debug_flags();)
-    p.N = g->N; p.H = g->H; p.W = g->W;
-    p.tilesX = tiles_x(g); p.tilesY = tiles_y(g);
-    return dispatch_stage(g, p, zin ? MODE_FWD : MODE_FIRST, f, S(stream));
-}
-
-static int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t st)
-{
-    k_wgrad_reduce<<<wgrad_reduce_blocks(job, g->M, g->Ph), 1024, 0, st>>>(job, g->M, g->Ph);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
-// r2 != nullptr: the launch also produces dA = alpha * du_out (x) im2col(r2) (cdl_fused2d_wgrad's first operator pair, same
-// arithmetic), through `workspace` (cdl_fused2d_wgrad_workspace_floats) -- one fat read of du_out less than the two-launch form
-// defer: the reduction of the dA partials is not launched but described there
-static int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map, const void *frags,
-                     float *du_out, float *patches, float *dtau_partial, int do_synth, int precision, const float *r2,
-                     float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr)
-{
-    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
-    if (do_synth && !patches) return CDL_EINVAL;
-    if (r2 && (!dA || !workspace)) return CDL_EINVAL;
-    const Flags f = parse_flags(precision);
-    if (!f.ok) return CDL_EINVAL;
-    FusedParams p = {};
-    p.rev = f.rev;
-    p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
-    p.frags = reinterpret_cast<const uint4 *>(frags);
-    p.patches = patches; p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0; CDL_DBG_FIELD(p.dbg = debug_flags();)
-    p.N = g->N; p.H = g->H; p.W = g->W;
-    p.tilesX = tiles_x(g); p.tilesY = tiles_y(g);
-    p.r2 = r2; p.da_partial = workspace;
-    int rc = dispatch_stage(g, p, MODE_BWD, f, S(stream));
-    if (rc || !r2) return rc;
-    const WgradReduce job = {workspace, stage_grid(g, p), dA, nullptr, alpha, 0.0f, 0};
-    if (defer) { *defer = job; return 0; }                  // the sweep reduces it with the iteration's other sums
-    return launch_wgrad_reduce(g, job, S(stream));
+    return iter_fwd<2>(g, r, zin, tau, frags, sgn, zout, patches, map_out, precision, stream);
 }
 
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
@@ -1756,8 +2002,8 @@ int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *bas
                           const float *r2, float alpha, float *dA, float *workspace, int precision, void *stream)
 {
     if (!r2 != !dA || !r2 != !workspace) return CDL_EINVAL;     // the filter gradient: all three set, or none
-    return stage_bwd(g, thin, base, map, frags, du_out, patches, dtau_partial, do_synth, precision, r2, alpha, dA, workspace,
-                     stream);
+    return stage_bwd<2>(g, thin, base, map, frags, du_out, patches, dtau_partial, do_synth, precision, r2, alpha, dA, workspace,
+                        stream);
 }
 
 int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
@@ -1765,7 +2011,7 @@ int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const 
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
-    const int per_img = tiles_x(g) * tiles_y(g);             // partial rows: [n][tile][m]
+    const int per_img = tiles_x(g) * tiles_y<2>(g);          // partial rows: [n][tile][m]
     const DtauReduce job = {dtau_partial, c, dt0, dt1, g->N, per_img};
     k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(job, g->M);
     CDL_LAUNCH_CHECK();
@@ -1777,49 +2023,9 @@ size_t cdl_fused2d_wgrad_workspace_floats(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
     // two regions of per-workgroup partials: a reverse sweep holds the stage's dA_k partials in the first and k_wgrad2d's
-    // in the second until its one reduction launch per iteration; a stand-alone call uses the first
-    const size_t own = 2 * wgrad_region_floats(g);
-#ifndef CDL_F2D_WY4
-    return larger(own, cdl_fused2d_wgrad_workspace_floats_wy4(g));
-#else
-    return own;
-#endif
-}
-
-// k_wgrad2d into `workspace`; the reduction that finishes the gradient(s) is described in *job, not launched
-static int wgrad_partials(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
-                          const float *X1, const float *T1, float alpha1, float *dw1, float *workspace,
-                          int precision, void *stream, WgradReduce *job)
-{
-    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!workspace || (!X0 && !X1)) return CDL_EINVAL;
-    if ((X0 && (!T0 || !dw0)) || (X1 && (!T1 || !dw1))) return CDL_EINVAL;
-    const Flags f = parse_flags(precision);
-    if (!f.ok) return CDL_EINVAL;
-    WgradParams p = {};
-    p.rev = f.rev;
-    p.X[0] = X0; p.T[0] = T0; p.X[1] = X1; p.T[1] = T1;
-    p.single = (X0 != nullptr) != (X1 != nullptr);
-    if (p.single) {                                         // one gradient: both wave groups on it
-        if (!X0) { X0 = X1; T0 = T1; alpha0 = alpha1; dw0 = dw1; X1 = nullptr; }
-        p.X[0] = p.X[1] = X0; p.T[0] = p.T[1] = T0;
-    }
-    p.partial = workspace;
-    p.N = g->N; p.H = g->H; p.W = g->W;
-    p.tilesX = tiles_x(g); p.tilesY = (g->H + GW_TH - 1) / GW_TH;
-    p.numTiles = p.N * p.tilesX * p.tilesY;
-    int G = wgrad_grid(g);
-    if (p.single && G > (p.numTiles + 1) / 2) G = (p.numTiles + 1) / 2;
-    int rc;
-    if (g->M == 64)
-        rc = f.prec == 0 ? launch_wgrad<2, 0>(p, f.lin, G, S(stream))
-             : f.prec == 1 ? launch_wgrad<2, 1>(p, f.lin, G, S(stream)) : launch_wgrad<2, 2>(p, f.lin, G, S(stream));
-    else
-        rc = f.prec == 0 ? launch_wgrad<1, 0>(p, f.lin, G, S(stream))
-             : f.prec == 1 ? launch_wgrad<1, 1>(p, f.lin, G, S(stream)) : launch_wgrad<1, 2>(p, f.lin, G, S(stream));
-    if (rc) return rc;
-    *job = WgradReduce{workspace, G, X0 ? dw0 : nullptr, X1 ? dw1 : nullptr, alpha0, alpha1, p.single};
-    return 0;
+    // in the second until its one reduction launch per iteration; a stand-alone call uses the first.  k_wgrad2d's tiles
+    // are 64 x 16 whatever the stage's shape, and only the 64 x 16 stage writes dA_k partials: one need for both shapes
+    return 2 * wgrad_region_floats(g);
 }
 
 int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float alpha0, float *dw0,
@@ -1834,79 +2040,11 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
 int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub,
                          float alpha, float *out, float *acc, int acc_add, void *stream)
 {
-    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!patches || (!out && !acc)) return CDL_EINVAL;
-    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
-        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
-        k_assemble_v4<<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
-    } else if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20)) {
-        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)g->N);
-        k_assemble<4><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
-    } else {
-        dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)g->N);
-        k_assemble<1><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tiles_x(g), tiles_y(g), acc, acc_add);
-    }
-    CDL_LAUNCH_CHECK();
-    return 0;
+    return assemble<2>(g, patches, mask, sub, alpha, out, acc, acc_add, stream);
 }
 
-}  // extern "C"
-
-/* ---- optional per-kernel timing inside the sweeps (HIP events on the launch stream) -------------------
- * bench.py turns it on for a few steps to report the in-step average duration of the three fat kernels
- * (isolated re-launches of one kernel miss the cache state the step leaves behind).  Off: no events. */
-namespace {
-// Process-wide and mutex-guarded: the one piece of state of this file, used by bench.py only.  Events are
-// recorded on whichever stream the timed sweep runs on; pairs of different devices are kept apart by the
-// device they were created on (an event can only be recorded on its own device's streams).
-struct TimingState {
-    std::mutex mu;
-    std::atomic<bool> on{false};
-    struct Pair { hipEvent_t start, stop; int cls, dev; };
-    std::vector<Pair> pairs;               // in launch order; class 0 forward stage (k >= 1), 1 reverse stage,
-                                           // 2 filter gradients, 3 first forward stage (k = 0: no fat read)
-    std::vector<std::pair<hipEvent_t, int>> spare;     // recycled events with their device
-};
-TimingState g_timing;
-
-struct TimingScope {
-    hipStream_t st;
-    hipEvent_t stop = nullptr;
-    TimingScope(int c, hipStream_t s) : st(s)
-    {
-        if (!g_timing.on.load(std::memory_order_relaxed)) return;
-        std::lock_guard<std::mutex> lk(g_timing.mu);
-        const int dev = cdl_current_device();
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        for (int i = 0; i < 2; ++i) {
-            for (size_t k = 0; k < g_timing.spare.size() && !ev[i]; ++k)
-                if (g_timing.spare[k].second == dev) {
-                    ev[i] = g_timing.spare[k].first;
-                    g_timing.spare.erase(g_timing.spare.begin() + k);
-                }
-            if (!ev[i] && hipEventCreate(&ev[i]) != hipSuccess) return;
-        }
-        (void)hipEventRecord(ev[0], st);
-        stop = ev[1];
-        g_timing.pairs.push_back({ev[0], ev[1], c, dev});
-    }
-    ~TimingScope()
-    {
-        if (stop) (void)hipEventRecord(stop, st);
-    }
-};
-}  // namespace
-
-#ifndef CDL_F2D_WY4
-extern "C" int cdl_fused2d_timing_wy4(int enable);
-extern "C" int cdl_fused2d_timing_read_wy4(double *ms_sum, int *count);
-#endif
-
-extern "C" int cdl_fused2d_timing(int enable)
+int cdl_fused2d_timing(int enable)
 {
-#ifndef CDL_F2D_WY4
-    if (int rc = cdl_fused2d_timing_wy4(enable)) return rc;     // the sweeps of the other object (bf16 code storage) too
-#endif
     std::lock_guard<std::mutex> lk(g_timing.mu);
     g_timing.on.store(enable != 0, std::memory_order_relaxed);
     if (enable) {
@@ -1919,7 +2057,7 @@ extern "C" int cdl_fused2d_timing(int enable)
     return 0;
 }
 
-extern "C" int cdl_fused2d_timing_read(double *ms_sum, int *count)
+int cdl_fused2d_timing_read(double *ms_sum, int *count)
 {
     if (!ms_sum || !count) return CDL_EINVAL;
     std::lock_guard<std::mutex> lk(g_timing.mu);
@@ -1932,60 +2070,8 @@ extern "C" int cdl_fused2d_timing_read(double *ms_sum, int *count)
         ms_sum[pr.cls] += ms;
         ++count[pr.cls];
     }
-#ifndef CDL_F2D_WY4
-    double ms2[4];
-    int n2[4];
-    if (int rc = cdl_fused2d_timing_read_wy4(ms2, n2)) return rc;
-    for (int c = 0; c < 4; ++c) { ms_sum[c] += ms2[c]; count[c] += n2[c]; }
-#endif
     return 0;
 }
-
-extern "C" {
-/* ---- whole sweeps: every launch of a forward / reverse pass enqueued from one C call ----------------
- * Snake order: consecutive fat launches walk the tiles in opposite directions, so each one starts on
- * the bytes the previous one touched last, which are still in the 256 MiB Infinity Cache (it holds
- * the last ~256 MiB loaded or stored).  Tile results do not depend on the order; only the filter
- * gradients' per-workgroup partial sums are grouped differently.  CDL_FUSED_SNAKE=0 turns it off. */
-// fragments of K (analysis-like, synthesis-like) pairs, pair k at frags + k * cdl_fused2d_frag_bytes(M)
-static int prep_pairs(const float *const *w1, const float *const *w2, int K, int shift2, void *frags, int M, int P,
-                      hipStream_t st)
-{
-    const int MT = M / 32, threads = 8 * MT * 64;
-    const int frag_uint4 = (int)(cdl_fused2d_frag_bytes(M) / 16);
-    for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
-        const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
-        PrepBatch b = {};
-        for (int i = 0; i < nb; ++i) {
-            const int k = k0 + i;
-            // forward: (A_k, B_{k+1 mod K});  backward: (B_{k+1 mod K}, A_k) -- the shifted bank is index shift2
-            b.wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
-            b.wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
-        }
-        dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
-        k_prep_batch<<<grid, 256, 0, st>>>(b, reinterpret_cast<uint4 *>(frags) + (size_t)k0 * frag_uint4, frag_uint4, MT, P);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
-    return 0;
-}
-
-static int snake_enabled() { return cdl_opts().fused_snake; }
-
-// Sweeps: CDL_LAYOUT_IN(L) in `precision` selects the layout L of the tensors that stay inside the sweeps --
-// z_1 .. z_{K-1} (z[0..K-2]) and the du ping-pong buffers; z_K (z[K-1]) and g_z are always NCHW fp32.
-
-#ifndef CDL_F2D_WY4
-int cdl_fused2d_forward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
-                            const float *const *wA, const float *const *wB, float *const *z, float *const *r,
-                            unsigned *const *maps, float *xp, void *frags, float *patches, int precision, void *stream);
-int cdl_fused2d_backward_wy4(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
-                             const float *const *wA, const float *const *wB, const float *const *z,
-                             const float *const *r, const unsigned *const *maps, const float *g_xp, const float *g_z,
-                             float *const *dA, float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
-                             float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
-                             float *dtau, void *stream);
-#endif
 
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                         const float *const *wA, const float *const *wB, float *const *z, float *const *r,
@@ -1994,39 +2080,11 @@ int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !tau || !wA || !wB || !z || !xp || !frags || !patches || (K > 1 && !r)) return CDL_EINVAL;
-    const size_t nm = (size_t)g->N * g->M;
-    const int snake = snake_enabled();
     const Flags f = parse_flags(precision);
     if (!f.ok || f.lout != 0) return CDL_EINVAL;
-    const int L = f.lin;
-#ifndef CDL_F2D_WY4
-    if (L == LAY_BLK16)                      // bf16 code storage: the two-waves-per-SIMD object (see the top of the file)
-        return cdl_fused2d_forward_wy4(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, precision, stream);
-#endif
-    const float *thin = yp;
-    const size_t fb = cdl_fused2d_frag_bytes(g->M);
-    int rc = prep_pairs(wA, wB, K, 1, frags, g->M, g->Ph, S(stream));       // (A_k, B_{k+1}) for every k, one launch
-    if (rc) return rc;
-    for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        {
-            TimingScope ts(k ? 0 : 3, S(stream));
-            rc = cdl_fused2d_iter_fwd(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k],
-                                      patches, maps ? maps[k] : nullptr,
-                                      f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(k == K - 1 ? LAY_NCHW : L) |
-                                          ((k & 1) && snake ? CDL_TILES_REVERSED : 0),
-                                      stream);
-        }
-        if (rc) return rc;
-        if (k < K - 1) {
-            rc = cdl_fused2d_assemble(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
-            thin = r[k];
-        } else {
-            rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    if (f.lin == LAY_BLK16)                  // bf16 code storage: 64 x 32 tiles, two waves per SIMD (see the top of the file)
+        return forward_sweep<4>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
+    return forward_sweep<2>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
 }
 
 int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,
@@ -2041,80 +2099,13 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
         !patches || !dtau_partial || !wgrad_ws || (K > 1 && !r))
         return CDL_EINVAL;
-    const int M = g->M;
-    float *du[2] = {du0, du1};
     const Flags f = parse_flags(precision);
     if (!f.ok || f.lout != 0) return CDL_EINVAL;
-    const int L = f.lin;
-#ifndef CDL_F2D_WY4
-    if (L == LAY_BLK16)
-        return cdl_fused2d_backward_wy4(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags,
-                                        patches, dtau_partial, wgrad_ws, precision, dyp, dtau, stream);
-#endif
-    // the forward's last launch ran in direction (K-1)&1: stages take that one, filter gradients the other
-    const int sdir = snake_enabled() ? (((K - 1) & 1) ? CDL_TILES_REVERSED : 0) : 0;
-    const int wdir = snake_enabled() ? (sdir ^ CDL_TILES_REVERSED) : 0;
-    const int sprec = f.prec | sdir, wprec = f.prec | wdir;
-    int rc = cdl_fused2d_wgrad(g, z[K - 1], g_xp, 1.0f, dB[0], nullptr, nullptr, 0.0f, nullptr, wgrad_ws,
-                               wprec, stream);                           // dB_0 = z_K (x) dL/d(D z_K); z_K is NCHW
-    if (rc) return rc;
-    const float *thin = g_xp, *base = g_z;
-    const size_t fb = cdl_fused2d_frag_bytes(M);
-    rc = prep_pairs(wB, wA, K, 0, frags, M, g->Ph, S(stream));               // (B_{k+1}, A_k) for every k, one launch
-    if (rc) return rc;
-    // One reduction launch per iteration (k_sweep_reduce), after the iteration's last fat kernel: dA_k (the stage's
-    // partials, first region of the workspace), dB_k (k_wgrad2d's, second region) and the threshold gradients of k.
-    // dtau_partial is next written by stage k-1, behind that launch in stream order.
-    float *ws_a = wgrad_ws, *ws_b = wgrad_ws + wgrad_region_floats(g);
-    const int per_img = tiles_x(g) * tiles_y(g);             // dtau_partial rows: [n][tile][m]
-    for (int k = K - 1, flip = 0; k >= 0; --k, flip ^= 1) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        float *duk = du[flip];
-        // dA_k = -du_k (x) r_k (k = 0: du_0 (x) yp) rides in the reverse stage, which has du_k in its registers: du_k is
-        // read once (by stage k-1), not twice -- 5.1 fat passes per iteration instead of 6.1 (CDL_FUSED_DA=0: the two-launch
-        // form, for A/B runs)
-        const bool ride = TH == GW_TH && cdl_opts().fused_da;
-        SweepReduce red = {};
-        {
-            TimingScope ts(1, S(stream));
-            rc = stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
-                           sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
-                           ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0]);
-        }
-        if (rc) return rc;
-        if (ride) red.wblocks[0] = wgrad_reduce_blocks(red.w[0], M, g->Ph);
-        red.t = DtauReduce{dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, g->N, per_img};
-        if (dtau) {
-            rc = cdl_dtau_per_sample(dtau_partial, g->N, M, per_img, (size_t)per_img * M, 1, M, dtau + (size_t)k * g->N * M, stream);
-            if (rc) return rc;
-        }
-        if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
-            rc = cdl_fused2d_assemble(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);
-            if (rc) return rc;
-        }
-        if (k >= 1) {
-            // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
-            rc = cdl_fused2d_assemble(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
-            if (rc) return rc;
-            {
-                TimingScope ts(2, S(stream));
-                rc = ride ? wgrad_partials(g, z[k - 1], q, 1.0f, dB[k], nullptr, nullptr, 0.0f, nullptr, ws_b,
-                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1])
-                          : wgrad_partials(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], ws_b,
-                                           wprec | CDL_LAYOUT_IN(L), stream, &red.w[1]);
-            }
-            thin = q;
-        } else if (!ride) {
-            rc = wgrad_partials(g, duk, yp, 1.0f, dA[0], nullptr, nullptr, 0.0f, nullptr, ws_b, wprec | CDL_LAYOUT_IN(L), stream,
-                                &red.w[1]);
-        }
-        if (rc) return rc;
-        if (k >= 1 || !ride) red.wblocks[1] = wgrad_reduce_blocks(red.w[1], M, g->Ph);
-        k_sweep_reduce<<<red.wblocks[0] + red.wblocks[1] + (M + 3) / 4, 1024, 0, S(stream)>>>(red, M, g->Ph);
-        CDL_LAUNCH_CHECK();
-        base = duk;
-    }
-    return 0;
+    if (f.lin == LAY_BLK16)
+        return backward_sweep<4>(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags, patches,
+                                 dtau_partial, wgrad_ws, f, dyp, dtau, stream);
+    return backward_sweep<2>(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags, patches,
+                             dtau_partial, wgrad_ws, f, dyp, dtau, stream);
 }
 
 }  // extern "C"

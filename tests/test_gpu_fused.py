@@ -338,11 +338,22 @@ def test_c_sweeps_are_bit_identical_to_stepwise_launches(layout):
     kernel is order-fixed, results must match bit for bit (also checks the ping-pong aliasing).  The
     sweeps alternate the tile direction per launch (snake order, CDL_TILES_REVERSED): stage outputs and
     threshold gradients do not depend on it; the filter gradients group their partial sums differently."""
+    _sweeps_against_stepwise_launches(layout, 4)
+
+
+@pytest.mark.parametrize("layout", ["nchw", "blocked", "blocked_bf16"])
+def test_c_sweeps_match_stepwise_launches_at_one_iteration(layout):
+    """The same at K = 1, where the only forward stage has no fat input and writes z_K as NCHW, and the only reverse stage
+    reads an NCHW gradient: with bf16 code storage, the one sweep that launches the 64 x 32 first stage with NCHW output."""
+    _sweeps_against_stepwise_launches(layout, 1)
+
+
+def _sweeps_against_stepwise_launches(layout, K):
     import cdlnet_video_amd as cva
     from cdlnet_video_amd import loop
     o = cva.ops
     torch.manual_seed(31)
-    K, M, P, N, H, W = 4, 64, 7, 2, 40, 72
+    M, P, N, H, W = 64, 7, 2, 40, 72
     net = cva.CDLNet(K=K, M=M, P=P, s=1, C=1, t0=5e-3, adaptive=True, init=True).cuda()
     y = torch.rand(N, 1, H, W, generator=torch.Generator().manual_seed(1)).cuda()
     yp, mean, pads, _ = o.preprocess(y, 1, None)
@@ -351,8 +362,8 @@ def test_c_sweeps_are_bit_identical_to_stepwise_launches(layout):
     tau = o.thresholds(net.t.detach(), c, N)
     A = [m.weight.detach() for m in net.A]
     B = [m.weight.detach() for m in net.B]
-    # bf16 code storage: the whole-sweep entry points run the library's 64 x 32-tile object (two waves per SIMD: those sweeps
-    # are compute-bound), the step-wise ones its 64 x 16-tile object -- another partition of the col2im sums, so the thin
+    # bf16 code storage: the whole-sweep entry points run the library's 64 x 32-tile kernels (two waves per SIMD: those sweeps
+    # are compute-bound), the step-wise ones its 64 x 16-tile kernels -- another partition of the col2im sums, so the thin
     # tensors differ in their last bits and the bf16 rounding of the codes turns that into bf16-sized differences: agreement
     # to storage accuracy there, bit for bit for the fp32 layouts
     exact = layout != "blocked_bf16"

@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -19,6 +21,12 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/cdlnet_hip.h but not exported"
     bound = set(cva._lib.SIGNATURES) | set(cva._lib.SIZE_T_FUNCS) | {"cdl_version"}
     assert declared <= bound, declared - bound          # every entry point has a Python binding
+    # and the other way round: the library exports no cdl_* symbol the header does not declare (no shadow ABI)
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", cva._lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split()}
+    ours = {s for s in exported if s.startswith("cdl_")}
+    assert any(s.startswith("cdl_fused2d_") for s in ours) and ours <= declared, ours - declared
     lib.cdl_version.restype = ctypes.c_char_p
     assert b"gfx950" in lib.cdl_version()
     assert ctypes.sizeof(cva._lib.Geom) == 15 * 4
