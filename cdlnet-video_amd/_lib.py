@@ -42,19 +42,20 @@ SIGNATURES = {
     "cdl_postprocess_bwd": [_P, _P, _I, _I, _I, _I, _I, _IP, _P],
     "cdl_thresholds": [_P, _P, _P, _I, _I, _I, _P],
     "cdl_shrink": [_P, _P, _P, _I, ctypes.c_size_t, _P],
-    "cdl_analysis": [_G, _P, _P, _F, _P, _P, _P, _P, _P],
+    "cdl_analysis": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P],               # .., out, cmap, tslope, stream
     "cdl_synthesis": [_G, _P, _P, _P, _F, _P, _P, _P, _P],
     "cdl_synthesis_ws": [_G, _P, _P, _P, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_wgrad": [_G, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
     "cdl_wgrad_pair": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
-    "cdl_tau_grad": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_tau_grad_gate": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_analysis_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
-    "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_tau_grad": [_G, _P, _P, _P, _P, _P, _P, _P, _P, _P],                   # .., scratch, cmap, stream
+    "cdl_tau_grad_gate": [_G, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_sigma_grad": [_G, _P, _P, _P, _P, _I, _P],
+    "cdl_analysis_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],      # .., cmap, tslope, stream
+    "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P],   # .., cmap, stream
     "cdl_analysis_prox_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P],
-    "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P],
+    "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P, _P, _P],                  # .., cmap, tslope, stream
+    "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],

@@ -57,13 +57,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const float *base
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((size_t)hi << 32) | lo), 0, (int)bytes, 0x00020000);
 }
 
-template <int PH, int PW, int SW, int MT, bool PROX, bool REV>
+// MAP: the thresholds follow a noise-level map (cdl_map_args: thr = tau[n,m] + cmap[n,pix] * tslope[m], every thread
+// keeps its pixel's map value in a register); in reverse mode a second, map-weighted partial per (channel, tile) goes to
+// dtpw.  A compile-time variant: the other instantiations are the kernels they were.
+template <int PH, int PW, int SW, int MT, bool PROX, bool REV, bool MAP>
 __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restrict__ x,
                                                const uint4 *__restrict__ frags, float alpha,
                                                const float *__restrict__ zin, const float *__restrict__ gate,
                                                const float *__restrict__ tau, float *__restrict__ out,
                                                cdl_prox_args px, int tilesX, int tilesY, int KS,
-                                               const float *__restrict__ zsup, float *__restrict__ dtp, int tpw)
+                                               const float *__restrict__ zsup, float *__restrict__ dtp, int tpw,
+                                               cdl_map_args mp, float *__restrict__ dtpw)
 {
     constexpr int XH = (ALY - 1) * SW + PH, XW = (ALX - 1) * SW + PW;
     constexpr int PS = ((XH * XW + 7) / 8) * 8;            // elements per plane
@@ -76,6 +80,8 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
     float *stage = reinterpret_cast<float *>(xh);          // [32][ALX*ALY] epilogue staging, reuses the planes (32 KB)
     const size_t plane_bytes = (size_t)NP * PS * 4 > (size_t)32 * ALX * ALY * 4 ? (size_t)NP * PS * 4 : (size_t)32 * ALX * ALY * 4;
     float *tau_s = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(xh) + plane_bytes);   // [32 MT] thresholds
+    float *ts_s = tau_s + 32 * MT;                         // MAP: [32 MT] threshold slopes, then the tile's map values
+    float *cm_s = ts_s + 32 * MT;                          // MAP, reverse mode: [ALX*ALY]
     const int Dz = g.D / g.sd, Hz = g.H / g.sh, Wz = g.W / g.sw;
     const int K = NP * PH * PW;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -108,6 +114,7 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
     if (tau && threadIdx.x < 32 * MT) {
         const int m = 32 * r0 + threadIdx.x;
         tau_s[threadIdx.x] = m < g.M ? tau[(size_t)n * g.M + m] : 0.0f;
+        if (MAP) ts_s[threadIdx.x] = m < g.M ? mp.tslope[m] : 0.0f;
     }
     __syncthreads();
     const bool tau_neg = tau && __syncthreads_or(threadIdx.x < 32 * MT && !(tau_s[threadIdx.x] >= 0.0f));   // negative OR NaN
@@ -212,6 +219,13 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
         // the 32 x 256 values with a rolled loop -- 32-bit index arithmetic, pixel-contiguous fat accesses, and none of
         // the 16*MT-fold unrolled 64-bit addressing that sent the M = 169 variant to scratch
         const size_t nbase = (size_t)n * g.M * slab + (size_t)zd * Hz * Wz;
+        float cm = 0.0f;                                   // MAP: the map at this thread's pixel of the tile
+        if (MAP) {
+            const int pxl_ = threadIdx.x & (ALX * ALY - 1);
+            const int oy_ = ty * ALY + pxl_ / ALX, ox_ = tx * ALX + pxl_ % ALX;
+            if (oy_ < Hz && ox_ < Wz) cm = mp.cmap[((size_t)n * Dz + zd) * Hz * Wz + (size_t)oy_ * Wz + ox_];
+            if (REV && threadIdx.x < ALX * ALY) cm_s[pxl_] = cm;      // (the round's first barrier orders it)
+        }
 #pragma unroll
         for (int R = 0; R < MT; ++R) {
             __syncthreads();                               // image planes (first round) / previous tile consumed
@@ -279,17 +293,36 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                     for (int jj = 0; jj < NE; ++jj) stage[(2 * jj + chh) * (ALX * ALY) + pxl] = tg[jj];
                     __syncthreads();
                     const int ch = threadIdx.x >> 4, part = threadIdx.x & 15;
-                    float a = 0.0f;
+                    float a = 0.0f, aw = 0.0f;
+                    float cv[16];
+                    if (MAP) {                               // (cm_s is 16-byte aligned: every LDS region in front of it is)
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) a += stage[ch * (ALX * ALY) + part * 16 + i];
+                        for (int q = 0; q < 4; ++q) {
+                            const float4 c4 = reinterpret_cast<const float4 *>(cm_s + part * 16)[q];
+                            cv[4 * q] = c4.x; cv[4 * q + 1] = c4.y; cv[4 * q + 2] = c4.z; cv[4 * q + 3] = c4.w;
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float t = stage[ch * (ALX * ALY) + part * 16 + i];
+                        a += t;
+                        if (MAP) aw = fmaf(cv[i], t, aw);
+                    }
                     a += __shfl_xor(a, 8, 16);
                     a += __shfl_xor(a, 4, 16);
                     a += __shfl_xor(a, 2, 16);
                     a += __shfl_xor(a, 1, 16);
+                    if (MAP) {
+                        aw += __shfl_xor(aw, 8, 16);
+                        aw += __shfl_xor(aw, 4, 16);
+                        aw += __shfl_xor(aw, 2, 16);
+                        aw += __shfl_xor(aw, 1, 16);
+                    }
                     const int mm = 32 * (r0 + R) + ch;
                     if (part == 0 && mm < g.M) {
                         const int S = Dz * tilesY * tilesX, kt = (zd * tilesY + ty) * tilesX + tx;
                         dtp[((size_t)n * g.M + mm) * S + kt] = a;
+                        if (MAP) dtpw[((size_t)n * g.M + mm) * S + kt] = aw;
                     }
                     continue;
                 }
@@ -298,7 +331,10 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                     const float base = gv[jj] == 0.0f ? 0.0f : bv[jj];
                     const float u = fmaf(alpha, stage[threadIdx.x + jj * ANT], base);
                     const float ts = tau_s[32 * R + chh + 2 * jj];          // (unused when tau == nullptr)
-                    const float val = tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u;
+                    // (MAP: the general shrinkage.  Deciding the clamp form per tile from the signs of t0, the slopes and
+                    // the tile's map values was measured: 473 us against 460 us per launch at cfg2, for its barrier and registers)
+                    const float val = MAP ? cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[32 * R + chh + 2 * jj]))
+                                          : (tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u);
                     const int vo = (tailR && m0 + 2 * jj >= g.M) ? OOB : voff;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rs_out, vo, soff0 + 2 * jj * slab4, 0);
                 }
@@ -325,6 +361,7 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                     const float ts = tau_s[32 * R + chh + 2 * (j0 + j)];     // (unused when tau == nullptr)
                     if (ix[j] >= 0)
                         out_n[ix[j]] = PROX ? cdl_prox_apply(px, u, nbase + ix[j], row)
+                                     : MAP ? cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[32 * R + chh + 2 * (j0 + j)]))
                                             : (tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u);
                 }
             }
@@ -381,15 +418,22 @@ bool plan_for(const cdl_geom *g, Plan *p)
     return true;
 }
 
-template <int PH, int PW, int SW, int MT, bool PROX, bool REV>
+// the map variants keep the slopes and (reverse mode) the tile's map values behind the thresholds in LDS
+bool map_lds(Plan *p)
+{
+    p->lds += (size_t)32 * p->MTW * 4 + (size_t)ALX * ALY * 4;
+    return p->lds <= LDS_MAX;
+}
+
+template <int PH, int PW, int SW, int MT, bool PROX, bool REV, bool MAP>
 int launch_mtp(const cdl_geom *g, const Plan &p, const float *x, const uint4 *frags, float alpha, const float *zin,
                const float *gate, const float *tau, float *out, const cdl_prox_args &px, hipStream_t st,
-               const float *zsup, float *dtp)
+               const float *zsup, float *dtp, const cdl_map_args &mp, float *dtpw)
 {
-    if (int rc = cdl_ensure_dynamic_lds((const void *)k_ana_m<PH, PW, SW, MT, PROX, REV>, p.lds > 96 * 1024 ? LDS_MAX : 96 * 1024))
+    if (int rc = cdl_ensure_dynamic_lds((const void *)k_ana_m<PH, PW, SW, MT, PROX, REV, MAP>, p.lds > 96 * 1024 ? LDS_MAX : 96 * 1024))
         return rc;
-    k_ana_m<PH, PW, SW, MT, PROX, REV><<<dim3((unsigned)p.groups, (unsigned)p.ngy), ANT, p.lds, st>>>(
-        *g, x, frags, alpha, zin, gate, tau, out, px, p.tilesX, p.tilesY, p.KS, zsup, dtp, p.tpw);
+    k_ana_m<PH, PW, SW, MT, PROX, REV, MAP><<<dim3((unsigned)p.groups, (unsigned)p.ngy), ANT, p.lds, st>>>(
+        *g, x, frags, alpha, zin, gate, tau, out, px, p.tilesX, p.tilesY, p.KS, zsup, dtp, p.tpw, mp, dtpw);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -397,45 +441,53 @@ int launch_mtp(const cdl_geom *g, const Plan &p, const float *x, const uint4 *fr
 template <int PH, int PW, int SW, int MT>
 int launch_mt(const cdl_geom *g, const Plan &p, const float *x, const uint4 *frags, float alpha, const float *zin,
               const float *gate, const float *tau, float *out, const cdl_prox_args &px, hipStream_t st,
-              const float *zsup, float *dtp)
+              const float *zsup, float *dtp, const cdl_map_args &mp, float *dtpw)
 {
-    if (px.zp) return launch_mtp<PH, PW, SW, MT, true, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr);
-    if (zsup) return launch_mtp<PH, PW, SW, MT, false, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp);
-    return launch_mtp<PH, PW, SW, MT, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr);
+    const cdl_map_args none{nullptr, nullptr};
+    if (px.zp) return launch_mtp<PH, PW, SW, MT, true, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, none, nullptr);
+    if (zsup && mp.cmap) return launch_mtp<PH, PW, SW, MT, false, true, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
+    if (zsup) return launch_mtp<PH, PW, SW, MT, false, true, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, none, nullptr);
+    if (mp.cmap) return launch_mtp<PH, PW, SW, MT, false, false, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, mp, nullptr);
+    return launch_mtp<PH, PW, SW, MT, false, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, none, nullptr);
 }
 
 template <int PH, int PW, int SW>
 int launch(const cdl_geom *g, const Plan &p, const float *x, const float *w, float alpha, const float *zin,
            const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws, hipStream_t st,
-           const float *zsup = nullptr, float *dtp = nullptr)
+           const cdl_map_args &mp, const float *zsup = nullptr, float *dtp = nullptr, float *dtpw = nullptr)
 {
     uint4 *frags = reinterpret_cast<uint4 *>(ws);
     const int ntile = p.ngy * p.MTW;
     const int nprep = ntile * p.KS * 64;
     k_ana_prep<<<(nprep + 255) / 256, 256, 0, st>>>(w, frags, g->M, g->C * g->Pd * g->Ph * g->Pw, ntile, p.KS);
     CDL_LAUNCH_CHECK();
-    if (p.MTW == 1) return launch_mt<PH, PW, SW, 1>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp);
-    return launch_mt<PH, PW, SW, 2>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp);
+    if (p.MTW == 1) return launch_mt<PH, PW, SW, 1>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
+    return launch_mt<PH, PW, SW, 2>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
 }
 
 // dt0[m] = sum_n sum_k s[(n M + m) S + k], dt1[m] = sum_n c[n] (...): one wave per channel; the lanes split the S tile
 // partials of a sample, a fixed exchange tree adds them, the 8 waves walk every 8th sample and are added in order --
 // deterministic.  (One thread
 // per channel walking N x S strided values took 0.40 ms at the s2030 shape: as long as the analysis itself.)
+// MAP: dt1[m] is the sum of the map-weighted partials sw instead, in the same order, by workgroups of their own
+// (blockIdx.y = 1).
+template <bool MAP>
 __global__ __launch_bounds__(512) void k_ana_tau_final(const float *__restrict__ s, const float *__restrict__ c,
-                                                       float *__restrict__ dt0, float *__restrict__ dt1, int N, int M, int S)
+                                                       float *__restrict__ dt0, float *__restrict__ dt1, int N, int M, int S,
+                                                       const float *__restrict__ sw)
 {
     __shared__ float r0[8], r1[8];
     const int m = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool weighted = MAP && blockIdx.y == 1;
     float a0 = 0.0f, a1 = 0.0f;
     for (int n = wv; n < N; n += 8) {                      // wave wv takes samples wv, wv + 8, ...
-        const float *row = s + (size_t)(n * M + m) * S;
+        const float *row = (weighted ? sw : s) + (size_t)(n * M + m) * S;
         float v = 0.0f;
         for (int k = lane; k < S; k += 64) v += row[k];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
         a0 += v;
-        if (c) a1 = fmaf(c[n], v, a1);
+        if (!MAP && c) a1 = fmaf(c[n], v, a1);
     }
     if (lane == 0) { r0[wv] = a0; r1[wv] = a1; }
     __syncthreads();
@@ -443,6 +495,10 @@ __global__ __launch_bounds__(512) void k_ana_tau_final(const float *__restrict__
         float t0 = 0.0f, t1 = 0.0f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) { t0 += r0[w]; t1 += r1[w]; }
+        if (MAP) {
+            (weighted ? dt1 : dt0)[m] = t0;
+            return;
+        }
         dt0[m] = t0;
         dt1[m] = t1;
     }
@@ -459,29 +515,35 @@ size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g)
     if (!plan_for(g, &p)) return 0;
     const size_t Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
     if ((size_t)g->M * Dz * Hz * Wz * 4 >= ((size_t)1 << 31)) return 0;     // the descriptor epilogue only
-    return p.frag_uint4 * 4 + (size_t)g->N * g->M * Dz * p.tilesY * p.tilesX;
+    return p.frag_uint4 * 4 + (size_t)2 * g->N * g->M * Dz * p.tilesY * p.tilesX;   // (twice: the map-weighted partials)
 }
 
 int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                           const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *ws,
-                          size_t ws_floats, void *stream, float *dtau_n)
+                          size_t ws_floats, void *stream, float *dtau_n, const float *cmap)
 {
     Plan p;
     const size_t need = cdl_mfma_analysis_rev_ws_floats(g);
     if (!need || !plan_for(g, &p) || !ws || ws_floats < need || !zsup || !dt0 || !dt1) return CDL_EUNSUPPORTED;
     if ((reinterpret_cast<size_t>(ws) & 15) != 0) return CDL_EUNSUPPORTED;
+    if (cmap && !map_lds(&p)) return CDL_EUNSUPPORTED;
     float *dtp = ws + p.frag_uint4 * 4;
     const int S_ = (g->D / g->sd) * p.tilesY * p.tilesX;
+    float *dtpw = dtp + (size_t)g->N * g->M * S_;
+    const cdl_map_args mp{cmap, nullptr};
     int rc = CDL_EUNSUPPORTED;
 #define CDL_M(PH_, P_, S2_) \
     if (g->Ph == PH_ && g->Pw == P_ && g->sw == S2_) \
-        rc = launch<PH_, P_, S2_>(g, p, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, ws, S(stream), zsup, dtp)
+        rc = launch<PH_, P_, S2_>(g, p, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, ws, S(stream), mp, zsup, dtp, dtpw)
     CDL_M(3, 3, 1); else CDL_M(5, 5, 1); else CDL_M(7, 7, 1); else CDL_M(9, 9, 1);
     else CDL_M(3, 3, 2); else CDL_M(5, 5, 2); else CDL_M(7, 7, 2); else CDL_M(9, 9, 2);
     else CDL_M(9, 5, 1); else CDL_M(9, 5, 2);
 #undef CDL_M
     if (rc) return rc;
-    k_ana_tau_final<<<g->M, 512, 0, S(stream)>>>(dtp, c, dt0, dt1, g->N, g->M, S_);
+    if (cmap)
+        k_ana_tau_final<true><<<dim3(g->M, 2), 512, 0, S(stream)>>>(dtp, nullptr, dt0, dt1, g->N, g->M, S_, dtpw);
+    else
+        k_ana_tau_final<false><<<g->M, 512, 0, S(stream)>>>(dtp, c, dt0, dt1, g->N, g->M, S_, nullptr);
     CDL_LAUNCH_CHECK();
     if (dtau_n)                                                    // per-sample: the S_ tile partials of row (n, m)
         return cdl_dtau_per_sample(dtp, g->N, g->M, S_, (size_t)g->M * S_, (size_t)S_, 1, dtau_n, stream);
@@ -497,14 +559,15 @@ size_t cdl_mfma_analysis_ws_floats(const cdl_geom *g)
 // CDL_EUNSUPPORTED: the caller falls back to the VALU kernels
 int cdl_mfma_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                      size_t ws_floats, void *stream)
+                      size_t ws_floats, void *stream, const cdl_map_args &mp)
 {
     Plan p;
     if (!plan_for(g, &p) || !ws || ws_floats < p.frag_uint4 * 4) return CDL_EUNSUPPORTED;
     if ((reinterpret_cast<size_t>(ws) & 15) != 0) return CDL_EUNSUPPORTED;
+    if (mp.cmap && !map_lds(&p)) return CDL_EUNSUPPORTED;
 #define CDL_M(PH_, P_, S_) \
     if (g->Ph == PH_ && g->Pw == P_ && g->sw == S_) \
-        return launch<PH_, P_, S_>(g, p, x, w, alpha, zin, gate, tau, out, px, ws, S(stream))
+        return launch<PH_, P_, S_>(g, p, x, w, alpha, zin, gate, tau, out, px, ws, S(stream), mp)
     CDL_M(3, 3, 1); CDL_M(5, 5, 1); CDL_M(7, 7, 1); CDL_M(9, 9, 1);
     CDL_M(3, 3, 2); CDL_M(5, 5, 2); CDL_M(7, 7, 2); CDL_M(9, 9, 2);
     CDL_M(9, 5, 1); CDL_M(9, 5, 2);

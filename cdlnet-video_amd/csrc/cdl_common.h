@@ -84,6 +84,21 @@ __device__ __forceinline__ float cdl_prox_apply(const cdl_prox_args &px, float u
                  : cdl_prox_csr1(u, px.zp[idx], px.lam[row], px.g1[row]).z;
 }
 
+// Optional noise-level map of the shrinkage epilogues: thr = tau[n,m] + cmap[n,pix] * tslope[m],
+// tau then holding t[k,0,m].  The product is rounded before the sum (contraction off), as torch's broadcast
+// `t0 + c * t1` does (model/net.py:83), so the thresholds are the reference's bit for bit.
+struct cdl_map_args {
+    const float *cmap;      // (N, code pixels); nullptr: no map
+    const float *tslope;    // (M)
+};
+
+__device__ __forceinline__ float cdl_map_threshold(float t0, float c, float slope)
+{
+#pragma clang fp contract(off)
+    const float prod = c * slope;
+    return t0 + prod;
+}
+
 __host__ __device__ __forceinline__ int cdl_floordiv(int a, int b)
 {
     int q = a / b;
@@ -138,7 +153,8 @@ static inline bool cdl_geom_ok(const cdl_geom *g)
 
 // register-tiled variants (cdl_generic_tiled.hip): CDL_EUNSUPPORTED means "use the untiled kernel"
 int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream);
+                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
+                       const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
 int cdl_tiled_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
                         const float *mask, const float *sub, float *out, float *ws, size_t ws_floats,
                         void *stream);
@@ -166,7 +182,7 @@ int cdl_dense_vgg(const cdl_geom *g, int transpose, int form, const float *x, co
                   void *stream);
 int cdl_mfma_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                      size_t ws_floats, void *stream);
+                      size_t ws_floats, void *stream, const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
 size_t cdl_mfma_analysis_ws_floats(const cdl_geom *g);
 // per-sample threshold gradients from a sweep's partial sums (cdl_datagrad.hip):
 // dtau_n[n,m] = sum_{j<R} partial[n sN + m sM + j sR], j in order
@@ -175,7 +191,7 @@ int cdl_dtau_per_sample(const float *partial, int N, int M, int R, size_t sN, si
 size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g);
 int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                           const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *ws,
-                          size_t ws_floats, void *stream, float *dtau_n = nullptr);
+                          size_t ws_floats, void *stream, float *dtau_n = nullptr, const float *cmap = nullptr);
 // matrix-core filter gradients (cdl_wgrad_mfma.hip), same convention
 int cdl_mfma_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
                    float *ws, size_t ws_floats, void *stream);

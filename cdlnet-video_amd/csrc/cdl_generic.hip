@@ -14,13 +14,15 @@ constexpr int MCHUNK = 8;         // code channels accumulated per thread per pa
 // analysis: acc[m] = sum_{c,kd,ki,kj} x[c, zd*sd-pd+kd, zy*sh-ph+ki, zx*sw-pw+kj] * w[m,c,kd,ki,kj]
 // One workgroup = one (n, zd, 16x16 tile of (zy,zx)); the image patch (all C, Pd slices, halo)
 // is staged once in LDS and reused for every code channel; filter taps are wave-uniform
-// scalar loads.
+// scalar loads.  MAP: the thresholds follow a noise-level map (cdl_map_args), read once per pixel.
+template <bool MAP>
 __global__ __launch_bounds__(256) void k_analysis(cdl_geom g, const float *__restrict__ x,
                                                   const float *__restrict__ w, float alpha,
                                                   const float *__restrict__ zin,
                                                   const float *__restrict__ gate,
                                                   const float *__restrict__ tau,
-                                                  float *__restrict__ out, int tilesX, int tilesY, cdl_prox_args px)
+                                                  float *__restrict__ out, int tilesX, int tilesY, cdl_prox_args px,
+                                                  cdl_map_args mp)
 {
     extern __shared__ float patch[];
     const int Dz = g.D / g.sd, Hz = g.H / g.sh, Wz = g.W / g.sw;
@@ -50,6 +52,8 @@ __global__ __launch_bounds__(256) void k_analysis(cdl_geom g, const float *__res
     const int taps = g.Pd * g.Ph * g.Pw, wrow = g.C * taps;
     const bool live = zy < Hz && zx < Wz;
     const float *pbase = patch + (ly * g.sh) * PW + lx * g.sw;
+    float cm = 0.0f;
+    if (MAP && live) cm = mp.cmap[(((size_t)n * Dz + zd) * Hz + zy) * Wz + zx];
     for (int m0 = 0; m0 < g.M; m0 += MCHUNK) {
         float acc[MCHUNK];
 #pragma unroll
@@ -80,6 +84,9 @@ __global__ __launch_bounds__(256) void k_analysis(cdl_geom g, const float *__res
                         if (gate && gate[idx] == 0.0f) base = 0.0f;
                     }
                     float u = fmaf(alpha, acc[j], base);
+                    if (MAP)
+                        out[idx] = cdl_shrink(u, cdl_map_threshold(tau[n * g.M + m], cm, mp.tslope[m]));
+                    else
                     out[idx] = px.zp ? cdl_prox_apply(px, u, idx, n * g.M + m)
                                      : (tau ? cdl_shrink(u, tau[n * g.M + m]) : u);
                 }
@@ -235,44 +242,62 @@ __global__ __launch_bounds__(256) void k_wgrad(cdl_geom g, const float *__restri
 }
 
 // ------------------------------------------------------------------------------------------
-// threshold gradient, stage 1: s[n,m] = -sum_pix sign(zout) * g over the support of zout.
-template <bool GATE_INPLACE>
+// threshold gradient, stage 1: s[n,m] = -sum_pix sign(zout) * g over the support of zout.  MAP: a second partial,
+// weighted by the noise-level map cmap[n,pix], goes to s[rows * S + .] (dt1 of a map call).
+template <bool GATE_INPLACE, bool MAP>
 __global__ __launch_bounds__(256) void k_tau_partial(float *__restrict__ gup,
                                                      const float *__restrict__ zout,
-                                                     float *__restrict__ s, size_t per_m, int S)
+                                                     float *__restrict__ s, size_t per_m, int S,
+                                                     const float *__restrict__ cmap, int M)
 {
     // one workgroup per (row, split): the N*M rows alone are too few workgroups for a batch of a few clips, and
     // 4 independent accumulators keep 8 loads in flight per thread
-    __shared__ float red[4];
+    __shared__ float red[4], redw[4];
     const int row = blockIdx.x / S, sp = blockIdx.x % S;
     const size_t chunk = (per_m + S - 1) / S;
     const size_t lo = (size_t)sp * chunk, hi = lo + chunk < per_m ? lo + chunk : per_m;
     const size_t base = (size_t)row * per_m;
-    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, aw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float *cm = MAP ? cmap + (size_t)(row / M) * per_m : nullptr;
     size_t i = lo + threadIdx.x;
     for (; i + 3 * 256 < hi; i += 4 * 256) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float zv = zout[base + i + u * 256], gv = gup[base + i + u * 256];
-            a[u] += zv > 0.0f ? -gv : (zv < 0.0f ? gv : 0.0f);
+            const float t = zv > 0.0f ? -gv : (zv < 0.0f ? gv : 0.0f);
+            a[u] += t;
+            if (MAP) aw[u] = fmaf(cm[i + u * 256], t, aw[u]);
             if (GATE_INPLACE && zv == 0.0f && gv != 0.0f) gup[base + i + u * 256] = 0.0f;
         }
     }
     for (; i < hi; i += 256) {
         const float zv = zout[base + i], gv = gup[base + i];
-        a[0] += zv > 0.0f ? -gv : (zv < 0.0f ? gv : 0.0f);
+        const float t = zv > 0.0f ? -gv : (zv < 0.0f ? gv : 0.0f);
+        a[0] += t;
+        if (MAP) aw[0] = fmaf(cm[i], t, aw[0]);
         if (GATE_INPLACE && zv == 0.0f && gv != 0.0f) gup[base + i] = 0.0f;
     }
     float acc = (a[0] + a[1]) + (a[2] + a[3]);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if (threadIdx.x % 64 == 0) red[threadIdx.x / 64] = acc;
+    if (MAP) {
+        float accw = (aw[0] + aw[1]) + (aw[2] + aw[3]);
+        for (int off = 32; off > 0; off >>= 1) accw += __shfl_down(accw, off, 64);
+        if (threadIdx.x % 64 == 0) redw[threadIdx.x / 64] = accw;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) s[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        s[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        if (MAP) s[(size_t)gridDim.x + blockIdx.x] = (redw[0] + redw[1]) + (redw[2] + redw[3]);
+    }
 }
 
-// stage 2: dt0[m] = sum_n sum_splits s[n,m,.]; dt1[m] = sum_n c[n] * (sum_splits s[n,m,.])
+// stage 2: dt0[m] = sum_n sum_splits s[n,m,.]; dt1[m] = sum_n c[n] * (sum_splits s[n,m,.]), or (MAP) the sum of the
+// map-weighted partials sw[n,m,.]
+template <bool MAP>
 __global__ void k_tau_final(const float *__restrict__ s, const float *__restrict__ c,
-                            float *__restrict__ dt0, float *__restrict__ dt1, int N, int M, int S)
+                            float *__restrict__ dt0, float *__restrict__ dt1, int N, int M, int S,
+                            const float *__restrict__ sw)
 {
     int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
@@ -281,10 +306,47 @@ __global__ void k_tau_final(const float *__restrict__ s, const float *__restrict
         float v = 0.0f;
         for (int k = 0; k < S; ++k) v += s[(size_t)(n * M + m) * S + k];
         a0 += v;
+        if (MAP) {
+            float vw = 0.0f;
+            for (int k = 0; k < S; ++k) vw += sw[(size_t)(n * M + m) * S + k];
+            a1 += vw;
+        } else
         if (c) a1 = fmaf(c[n], v, a1);
     }
     dt0[m] = a0;
     dt1[m] = a1;
+}
+
+// gradient of the noise-level map, one iteration: dcmap[n,pix] (+)= sum_m tslope[m] * (-sign(z) * du)[n,m,pix].  A
+// channel reduction: one thread per code pixel walks the M channels in order (coalesced across the wave, four loads of
+// each tensor in flight) -- deterministic.
+template <bool ACC>
+__global__ __launch_bounds__(256) void k_sigma_grad(const float *__restrict__ du, const float *__restrict__ z,
+                                                    const float *__restrict__ tslope, float *__restrict__ dcmap,
+                                                    int M, size_t per_m)
+{
+    const size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= per_m) return;
+    const int n = blockIdx.y;
+    const size_t base = (size_t)n * M * per_m + pix;
+    float a = 0.0f;
+    int m = 0;
+    for (; m + 4 <= M; m += 4) {
+        float zv[4], gv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            zv[u] = z[base + (size_t)(m + u) * per_m];
+            gv[u] = du[base + (size_t)(m + u) * per_m];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a = fmaf(tslope[m + u], zv[u] > 0.0f ? -gv[u] : (zv[u] < 0.0f ? gv[u] : 0.0f), a);
+    }
+    for (; m < M; ++m) {
+        const float zv = z[base + (size_t)m * per_m], gv = du[base + (size_t)m * per_m];
+        a = fmaf(tslope[m], zv > 0.0f ? -gv : (zv < 0.0f ? gv : 0.0f), a);
+    }
+    const size_t o = (size_t)n * per_m + pix;
+    dcmap[o] = ACC ? dcmap[o] + a : a;
 }
 
 __global__ void k_shrink(const float *__restrict__ x, const float *__restrict__ tau,
@@ -690,7 +752,7 @@ int cdl_shrink(const float *x, const float *tau, float *out, int rows, size_t pe
 
 static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                          const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                         size_t ws_floats, void *stream);
+                         size_t ws_floats, void *stream, const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
 
 // the matrix-core analysis (cdl_analysis_mfma.hip) is the default wherever it has a kernel and the launch is large
 // enough; CDL_MFMA_ANALYSIS=0 selects the VALU kernels (read per call)
@@ -714,16 +776,18 @@ size_t cdl_analysis_workspace_floats(const cdl_geom *g)
 }
 
 int cdl_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                 const float *gate, const float *tau, float *out, void *stream)
+                 const float *gate, const float *tau, float *out, const float *cmap, const float *tslope, void *stream)
 {
-    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, nullptr, 0, stream);
+    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, nullptr, 0, stream,
+                         cdl_map_args{cmap, tslope});
 }
 
 int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                     const float *gate, const float *tau, float *out, float *workspace, size_t workspace_floats,
-                    void *stream)
+                    const float *cmap, const float *tslope, void *stream)
 {
-    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, workspace, workspace_floats, stream);
+    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, workspace, workspace_floats, stream,
+                         cdl_map_args{cmap, tslope});
 }
 
 /* Reverse-sweep step: out = [zsup != 0] (zin + alpha A x)  and  (dt0, dt1) = cdl_tau_grad(out, zsup, c) -- the gradient
@@ -733,7 +797,7 @@ int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alp
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return 0;
-    size_t n = (size_t)CDL_TAU_SPLITS * g->N * g->M;
+    size_t n = (size_t)2 * CDL_TAU_SPLITS * g->N * g->M;       // (twice: the map-weighted partials of a map call)
     const size_t a = cdl_analysis_workspace_floats(g);
     if (a > n) n = a;
     const size_t r = (!cdl_opts().no_tiled && mfma_analysis_enabled(g)) ? cdl_mfma_analysis_rev_ws_floats(g) : 0;
@@ -742,19 +806,21 @@ size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
 
 int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                         const float *zsup, const float *c, float *dt0, float *dt1, float *dtau_n, float *out,
-                        float *workspace, size_t workspace_floats, void *stream)
+                        float *workspace, size_t workspace_floats, const float *cmap, void *stream)
 {
     if (!cdl_geom_ok(g) || !x || !w || !out || !zsup || !dt0 || !dt1 || !workspace) return CDL_EINVAL;
+    if (cmap && (c || dtau_n)) return CDL_EINVAL;               // a map replaces the per-sample scale
     if (out == zin || out == zsup) return CDL_EINVAL;
     if (workspace_floats < cdl_analysis_rev_workspace_floats(g)) return CDL_EINVAL;
     if (!cdl_opts().no_tiled && mfma_analysis_enabled(g) && !(mfma_dense_enabled() && cdl_dense_ws_floats(g, 0) > 0)) {
         const int rc = cdl_mfma_analysis_rev(g, x, w, alpha, zin, zsup, c, dt0, dt1, out, workspace, workspace_floats, stream,
-                                               dtau_n);
+                                               dtau_n, cmap);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
-    const int rc = cdl_analysis_ws(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, stream);
+    const int rc = cdl_analysis_ws(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, nullptr, nullptr,
+                                   stream);
     if (rc) return rc;
-    return cdl_tau_grad_gate(g, out, zsup, c, dt0, dt1, dtau_n, workspace, stream);
+    return cdl_tau_grad_gate(g, out, zsup, c, dt0, dt1, dtau_n, workspace, cmap, stream);
 }
 
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
@@ -777,22 +843,23 @@ int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, floa
 
 static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                          const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                         size_t ws_floats, void *stream)
+                         size_t ws_floats, void *stream, const cdl_map_args &mp)
 {
     if (!cdl_geom_ok(g) || !x || !w || !out) return CDL_EINVAL;
     if (out == zin) return CDL_EINVAL;
     if (gate && !zin) return CDL_EINVAL;
+    if (mp.cmap && (!mp.tslope || !tau || px.zp)) return CDL_EINVAL;   // the map is a form of the ST epilogue only
     if (!cdl_opts().no_tiled) {
-        if (!px.zp && mfma_dense_enabled()) {
+        if (!px.zp && !mp.cmap && mfma_dense_enabled()) {   // (the dense tier's analyses carry no shrinkage map)
             const int rcd = cdl_dense_conv(g, 0, x, nullptr, w, alpha, zin, gate, nullptr, nullptr, tau, 0, nullptr, out, ws,
                                            ws_floats, stream);
             if (rcd != CDL_EUNSUPPORTED) return rcd;
         }
         if (mfma_analysis_enabled(g)) {
-            const int rcm = cdl_mfma_analysis(g, x, w, alpha, zin, gate, tau, out, px, ws, ws_floats, stream);
+            const int rcm = cdl_mfma_analysis(g, x, w, alpha, zin, gate, tau, out, px, ws, ws_floats, stream, mp);
             if (rcm != CDL_EUNSUPPORTED) return rcm;
         }
-        const int rc = cdl_tiled_analysis(g, x, w, alpha, zin, gate, tau, out, px, stream);
+        const int rc = cdl_tiled_analysis(g, x, w, alpha, zin, gate, tau, out, px, stream, mp);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
     const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
@@ -801,11 +868,14 @@ static int analysis_impl(const cdl_geom *g, const float *x, const float *w, floa
     size_t lds = (size_t)g->C * g->Pd * PH * PW * sizeof(float);
     if (lds > 160 * 1024) return CDL_EUNSUPPORTED;
     if (lds > 64 * 1024) {
-        const int rc_ = cdl_ensure_dynamic_lds((const void *)k_analysis, (int)lds);
+        const int rc_ = cdl_ensure_dynamic_lds(mp.cmap ? (const void *)k_analysis<true> : (const void *)k_analysis<false>, (int)lds);
         if (rc_) return rc_;
     }
     dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N);
-    k_analysis<<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px);
+    if (mp.cmap)
+        k_analysis<true><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
+    else
+        k_analysis<false><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -932,9 +1002,10 @@ int cdl_wgrad_pair(const cdl_geom *g, const float *z0, const float *x0, float al
 }
 
 static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                         float *scratch, bool gate_inplace, void *stream, float *dtau_n)
+                         float *scratch, bool gate_inplace, void *stream, float *dtau_n, const float *cmap)
 {
     if (!cdl_geom_ok(g) || !gup || !zout || !dt0 || !dt1 || !scratch) return CDL_EINVAL;
+    if (cmap && (c || dtau_n)) return CDL_EINVAL;               // a map replaces the per-sample scale
     size_t per_m = (size_t)(g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
     // splits per (n, m) row: about 2048 workgroups of at least 4096 elements, at most CDL_TAU_SPLITS (the scratch)
     const int rows = g->N * g->M;
@@ -943,12 +1014,23 @@ static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const
     if ((size_t)Sp > most) Sp = (int)most;
     if (Sp > CDL_TAU_SPLITS) Sp = CDL_TAU_SPLITS;
     if (Sp < 1) Sp = 1;
+    if (cmap) {                                                   // weighted partials behind the plain ones
+        if (gate_inplace)
+            k_tau_partial<true, true><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, cmap, g->M);
+        else
+            k_tau_partial<false, true><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, cmap, g->M);
+        CDL_LAUNCH_CHECK();
+        k_tau_final<true><<<(g->M + 63) / 64, 64, 0, S(stream)>>>(scratch, nullptr, dt0, dt1, g->N, g->M, Sp,
+                                                                   scratch + (size_t)rows * Sp);
+        CDL_LAUNCH_CHECK();
+        return 0;
+    }
     if (gate_inplace)
-        k_tau_partial<true><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp);
+        k_tau_partial<true, false><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, nullptr, g->M);
     else
-        k_tau_partial<false><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp);
+        k_tau_partial<false, false><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, nullptr, g->M);
     CDL_LAUNCH_CHECK();
-    k_tau_final<<<(g->M + 63) / 64, 64, 0, S(stream)>>>(scratch, c, dt0, dt1, g->N, g->M, Sp);
+    k_tau_final<false><<<(g->M + 63) / 64, 64, 0, S(stream)>>>(scratch, c, dt0, dt1, g->N, g->M, Sp, nullptr);
     CDL_LAUNCH_CHECK();
     if (dtau_n)                                                   // per-sample: the Sp splits of row (n, m), in order
         return cdl_dtau_per_sample(scratch, g->N, g->M, Sp, (size_t)g->M * Sp, (size_t)Sp, 1, dtau_n, stream);
@@ -956,15 +1038,31 @@ static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const
 }
 
 int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                 float *dtau_n, float *scratch, void *stream)
+                 float *dtau_n, float *scratch, const float *cmap, void *stream)
 {
-    return tau_grad_impl(g, const_cast<float *>(gup), zout, c, dt0, dt1, scratch, false, stream, dtau_n);
+    return tau_grad_impl(g, const_cast<float *>(gup), zout, c, dt0, dt1, scratch, false, stream, dtau_n, cmap);
 }
 
 int cdl_tau_grad_gate(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,
-                      float *dtau_n, float *scratch, void *stream)
+                      float *dtau_n, float *scratch, const float *cmap, void *stream)
 {
-    return tau_grad_impl(g, gup, zout, c, dt0, dt1, scratch, true, stream, dtau_n);
+    return tau_grad_impl(g, gup, zout, c, dt0, dt1, scratch, true, stream, dtau_n, cmap);
+}
+
+int cdl_sigma_grad(const cdl_geom *g, const float *du, const float *z, const float *tslope, float *dcmap, int acc_add,
+                   void *stream)
+{
+    if (!cdl_geom_ok(g) || !du || !z || !tslope || !dcmap) return CDL_EINVAL;
+    const size_t per_m = (size_t)(g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
+    const size_t blocks = (per_m + 255) / 256;
+    if (blocks >= ((size_t)1 << 31) || g->N > 65535) return CDL_EUNSUPPORTED;
+    dim3 grid((unsigned)blocks, (unsigned)g->N);
+    if (acc_add)
+        k_sigma_grad<true><<<grid, 256, 0, S(stream)>>>(du, z, tslope, dcmap, g->M, per_m);
+    else
+        k_sigma_grad<false><<<grid, 256, 0, S(stream)>>>(du, z, tslope, dcmap, g->M, per_m);
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 int cdl_project_filters(float *w, int nfilters, int flen, void *stream)

@@ -13,14 +13,14 @@ constexpr int PXT = 4;            // columns per thread
 constexpr int MCH = 8;            // code channels per register pass
 
 // ------------------------------------------------------------------------------------------
-template <int PW, int SW>
+template <int PW, int SW, bool MAP>
 __global__ __launch_bounds__(256) void k_analysis_t(cdl_geom g, const float *__restrict__ x,
                                                     const float *__restrict__ w, float alpha,
                                                     const float *__restrict__ zin,
                                                     const float *__restrict__ gate,
                                                     const float *__restrict__ tau,
                                                     float *__restrict__ out, int tilesX, int tilesY,
-                                                    int PH, int PWp, int mper, cdl_prox_args px)
+                                                    int PH, int PWp, int mper, cdl_prox_args px, cdl_map_args mp)
 {
     extern __shared__ float patch[];                       // [C][Pd][PH][PWp]
     constexpr int WL = (PXT - 1) * SW + PW;                // row window per thread
@@ -51,6 +51,12 @@ __global__ __launch_bounds__(256) void k_analysis_t(cdl_geom g, const float *__r
     const int taps = g.Pd * g.Ph * PW, wrow = g.C * taps;
     const float *pbase = patch + (ly * g.sh) * PWp + lx * PXT * SW;
     const int m_lo = blockIdx.z * mper, m_hi = min(g.M, m_lo + mper);   // channel slice of this workgroup
+    float cm[PXT];                                         // MAP: the noise-level map at this thread's pixels
+    if (MAP) {
+#pragma unroll
+        for (int p = 0; p < PXT; ++p)
+            cm[p] = (zy < Hz && zx0 + p < Wz) ? mp.cmap[(((size_t)n * Dz + zd) * Hz + zy) * Wz + zx0 + p] : 0.0f;
+    }
     for (int m0 = m_lo; m0 < m_hi; m0 += MCH) {
         float acc[MCH][PXT];
 #pragma unroll
@@ -82,6 +88,7 @@ __global__ __launch_bounds__(256) void k_analysis_t(cdl_geom g, const float *__r
                 const int m = m0 + j;
                 if (m >= g.M) continue;
                 const float t = tau ? tau[n * g.M + m] : 0.0f;
+                const float ts = MAP ? mp.tslope[m] : 0.0f;
                 const size_t rowi = ((((size_t)n * g.M + m) * Dz + zd) * Hz + zy) * Wz;
 #pragma unroll
                 for (int p = 0; p < PXT; ++p) {
@@ -93,6 +100,9 @@ __global__ __launch_bounds__(256) void k_analysis_t(cdl_geom g, const float *__r
                         if (gate && gate[rowi + zx] == 0.0f) base = 0.0f;
                     }
                     const float u = fmaf(alpha, acc[j][p], base);
+                    if (MAP)
+                        out[rowi + zx] = cdl_shrink(u, cdl_map_threshold(t, cm[p], ts));
+                    else
                     out[rowi + zx] = px.zp ? cdl_prox_apply(px, u, rowi + zx, n * g.M + m) : (tau ? cdl_shrink(u, t) : u);
                 }
             }
@@ -727,9 +737,10 @@ inline int channel_split(int M, long blocks, int *chunks)
     return mper;
 }
 
-template <int PW, int SW>
+template <int PW, int SW, bool MAP>
 int launch_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                    const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream)
+                    const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
+                    const cdl_map_args &mp)
 {
     const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
     const int tilesX = (Wz + TX - 1) / TX, tilesY = (Hz + TY - 1) / TY;
@@ -738,14 +749,14 @@ int launch_analysis(const cdl_geom *g, const float *x, const float *w, float alp
     const size_t lds = (size_t)g->C * g->Pd * PH * PWp * sizeof(float);
     if (lds > 96 * 1024) return CDL_EUNSUPPORTED;
     if (lds > 64 * 1024) {
-        const int rc_ = cdl_ensure_dynamic_lds((const void *)k_analysis_t<PW, SW>, (int)lds);
+        const int rc_ = cdl_ensure_dynamic_lds((const void *)k_analysis_t<PW, SW, MAP>, (int)lds);
         if (rc_) return rc_;
     }
     int chunks;
     const int mper = channel_split(g->M, (long)tilesX * tilesY * Dz * g->N, &chunks);
     dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N, (unsigned)chunks);
-    k_analysis_t<PW, SW><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, PH, PWp,
-                                                        mper, px);
+    k_analysis_t<PW, SW, MAP><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, PH, PWp,
+                                                             mper, px, mp);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -819,10 +830,13 @@ int launch_synthesis(const cdl_geom *g, const float *z, const float *gate, const
 
 // Returns CDL_EUNSUPPORTED when the shape has no tiled instantiation (the caller falls back).
 int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream)
+                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
+                       const cdl_map_args &mp)
 {
     if (g->sw != g->sh) return CDL_EUNSUPPORTED;
-#define CDL_A(PW_, SW_) if (g->Pw == PW_ && g->sw == SW_) return launch_analysis<PW_, SW_>(g, x, w, alpha, zin, gate, tau, out, px, stream)
+#define CDL_A(PW_, SW_) if (g->Pw == PW_ && g->sw == SW_) \
+        return mp.cmap ? launch_analysis<PW_, SW_, true>(g, x, w, alpha, zin, gate, tau, out, px, stream, mp) \
+                       : launch_analysis<PW_, SW_, false>(g, x, w, alpha, zin, gate, tau, out, px, stream, mp)
     CDL_A(3, 1); CDL_A(5, 1); CDL_A(7, 1); CDL_A(9, 1);
     CDL_A(3, 2); CDL_A(5, 2); CDL_A(7, 2); CDL_A(9, 2);
 #undef CDL_A

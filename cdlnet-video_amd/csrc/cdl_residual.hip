@@ -94,9 +94,9 @@ int cdl_residual_forward(const cdl_geom *g, const float *x, const float *w1, con
                                   scratch_floats, stream);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
-    CDL_TRY(cdl_analysis_ws(g, x, w1, 1.0f, nullptr, nullptr, nullptr, h, scratch, scratch_floats, stream));
+    CDL_TRY(cdl_analysis_ws(g, x, w1, 1.0f, nullptr, nullptr, nullptr, h, scratch, scratch_floats, nullptr, nullptr, stream));
     CDL_TRY(relu_inplace(h, n, S(stream)));
-    CDL_TRY(cdl_analysis_ws(g, h, w2, 1.0f, x, nullptr, nullptr, out, scratch, scratch_floats, stream));
+    CDL_TRY(cdl_analysis_ws(g, h, w2, 1.0f, x, nullptr, nullptr, out, scratch, scratch_floats, nullptr, nullptr, stream));
     return relu_inplace(out, n, S(stream));
 }
 

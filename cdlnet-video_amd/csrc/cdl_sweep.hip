@@ -19,7 +19,7 @@ extern "C" {
 size_t cdl_ista_scratch_floats(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return 0;
-    size_t n = (size_t)CDL_TAU_SPLITS * g->N * g->M;             // cdl_tau_grad
+    size_t n = (size_t)2 * CDL_TAU_SPLITS * g->N * g->M;         // cdl_tau_grad (with a map: two partials per split)
     n = max_sz(n, cdl_wgrad_workspace_floats(g));
     n = max_sz(n, cdl_synthesis_workspace_floats(g));
     n = max_sz(n, cdl_prox_csr_scratch_floats(g));
@@ -31,9 +31,11 @@ size_t cdl_ista_scratch_floats(const cdl_geom *g)
 int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                      const float *z_prev, const float *z_after, const float *gam1, const float *gam2,
                      const float *const *wA, const float *const *wB, float *const *z, float *const *r,
-                     float *const *u, float *xp, float *scratch, size_t scratch_floats, void *stream)
+                     float *const *u, float *xp, float *scratch, size_t scratch_floats, const float *cmap,
+                     const float *tslope, void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !yp || !tau || !wA || !wB || !z || !xp || (K > 1 && !r)) return CDL_EINVAL;
+    if (cmap && (!tslope || z_prev)) return CDL_EINVAL;              // noise-level maps: the plain loop only
     if (z_prev ? (!gam1 || (z_after && !gam2)) : (z_after || u)) return CDL_EINVAL;
     const size_t NM = (size_t)g->N * g->M;
     for (int k = 0; k < K; ++k) {
@@ -51,7 +53,7 @@ int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mas
                                          scratch_floats, stream));
         else
             CDL_TRY(cdl_analysis_ws(g, x, wA[k], alpha, zin, nullptr, tau + k * NM, z[k], scratch, scratch_floats,
-                                    stream));
+                                    cmap, cmap ? tslope + (size_t)k * g->M : nullptr, stream));
     }
     return cdl_synthesis_ws(g, z[K - 1], nullptr, wB[0], 1.0f, nullptr, nullptr, xp, scratch, scratch_floats, stream);
 }
@@ -62,7 +64,8 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       const float *const *z, const float *const *r, const float *const *u, const float *g_xp,
                       const float *g_z, float *const *dA, float *const *dB, float *dt, float *dg1, float *dg2,
                       float *gz_prev, float *gz_after, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                      size_t scratch_floats, float *dyp, float *dtau, void *stream)
+                      size_t scratch_floats, float *dyp, float *dtau, const float *cmap, const float *tslope,
+                      float *dcmap, void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !yp || !wA || !wB || !z || !dA || !dB || !dt || !gbuf0 || !gbuf1 || !q ||
         !scratch || (K > 1 && !r))
@@ -70,7 +73,8 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
     if (!g_xp && !g_z) return CDL_EINVAL;
     if (z_prev ? (!u || !lam || !gam1 || !dg1 || (z_after && (!gam2 || !dg2))) : (z_after != nullptr)) return CDL_EINVAL;
     if (scratch_floats < cdl_ista_scratch_floats(g)) return CDL_EINVAL;
-    if (z_prev && (dyp || dtau)) return CDL_EINVAL;                 // data gradients: the plain loop only
+    if (z_prev && (dyp || dtau || cmap || dcmap)) return CDL_EINVAL;   // data gradients, noise-level maps: the plain loop only
+    if (cmap ? (c || dtau || (dcmap && !tslope)) : (dcmap != nullptr)) return CDL_EINVAL;   // a map replaces c; dcmap where dtau was
     const size_t NM = (size_t)g->N * g->M, M = g->M;
     const size_t code = NM * (size_t)(g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
     const size_t flen = (size_t)g->M * g->C * g->Pd * g->Ph * g->Pw;
@@ -84,10 +88,10 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
         if (!z_prev) {
             CDL_TRY(cdl_analysis_rev_ws(g, g_xp, wB[0], 1.0f, g_z, z[K - 1], c, dt + (size_t)(K - 1) * 2 * M,
                                         dt + (size_t)(K - 1) * 2 * M + M, dtau ? dtau + (K - 1) * NM : nullptr, gk,
-                                        scratch, scratch_floats, stream));
+                                        scratch, scratch_floats, cmap, stream));
             gated = true;
         } else
-        CDL_TRY(cdl_analysis_ws(g, g_xp, wB[0], 1.0f, g_z, nullptr, nullptr, gk, scratch, scratch_floats, stream));   // B_0^T g_xp (+ g_z)
+        CDL_TRY(cdl_analysis_ws(g, g_xp, wB[0], 1.0f, g_z, nullptr, nullptr, gk, scratch, scratch_floats, nullptr, nullptr, stream));   // B_0^T g_xp (+ g_z)
     } else {
         hipError_t e = hipMemsetAsync(dB[0], 0, flen * sizeof(float), S(stream));
         if (e != hipSuccess) return -(int)e;
@@ -105,8 +109,10 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
             // threshold gradients, and gk gated in place by the support of z_{k+1} in the same pass: the synthesis,
             // the filter gradient and the analysis below then read no gate (3 fat reads less per iteration)
             CDL_TRY(cdl_tau_grad_gate(g, gk, z[k], c, dt + k * 2 * M, dt + k * 2 * M + M, dtau ? dtau + k * NM : nullptr,
-                                      scratch, stream));
+                                      scratch, cmap, stream));
         }
+        if (dcmap)               // gk is du_k here: dcmap (= at k = K-1, +=) sum_m t[k,1,m] (-sign(z_{k+1}) du_k)
+            CDL_TRY(cdl_sigma_grad(g, gk, z[k], tslope + (size_t)k * M, dcmap, k < K - 1, stream));
         if (k == 0) {
             CDL_TRY(cdl_wgrad(g, gk, gate, yp, 1.0f, dA[0], scratch, scratch_floats, stream));
             if (dyp) {                                       // u_0 = A_0 yp: dyp += A_0^T du_0
@@ -125,10 +131,10 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
         if (!z_prev) {                                       // dL/dz_{k-1}, gated, with the thresholds' gradient of iteration k-1
             CDL_TRY(cdl_analysis_rev_ws(g, q, wB[k], 1.0f, gk, z[k - 1], c, dt + (size_t)(k - 1) * 2 * M,
                                         dt + (size_t)(k - 1) * 2 * M + M, dtau ? dtau + (k - 1) * NM : nullptr, other,
-                                        scratch, scratch_floats, stream));
+                                        scratch, scratch_floats, cmap, stream));
             gated = true;
         } else
-        CDL_TRY(cdl_analysis_ws(g, q, wB[k], 1.0f, gk, gate, nullptr, other, scratch, scratch_floats, stream));
+        CDL_TRY(cdl_analysis_ws(g, q, wB[k], 1.0f, gk, gate, nullptr, other, scratch, scratch_floats, nullptr, nullptr, stream));
         float *t = gk;
         gk = other;
         other = t;

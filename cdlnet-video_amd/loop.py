@@ -15,6 +15,10 @@ reference, train.py:98); with du_k = [z_{k+1} != 0] * g_{k+1}:
 and, when y / sigma require grad (the forward is a torch graph in both in the reference), with u_0 = A_0 yp:
     dL/dyp  = sum_k A_k^T du_k            (the unmasked sum behind q_k; k = 0 adds the synthesis half of stage 0)
     dL/dc_n = sum_k sum_m t[k,1,m] dtau[k,n,m]     (per-sample threshold gradients, contracted here)
+With a noise-level map c[n,pix] (a dense (N,1,*code grid) tensor) the threshold of code element
+(n, m, pix) is t[k,0,m] + c[n,pix] t[k,1,m]: the generic sweeps carry the map into their shrinkage epilogues, and
+    dt[k,1,m]   = -sum_{n,pix} c[n,pix] sign(z_{k+1}) du_k      (a second, map-weighted partial per row)
+    dL/dc[n,pix] = -sum_k sum_m t[k,1,m] sign(z_{k+1}) du_k     (cdl_sigma_grad: a channel reduction per iteration)
     dL/dy   = cdl_preprocess_bwd(dL/dyp, dL/dxhat)  (reflect pad adjoint and the mean)
 The gradient with respect to the mask is not produced (it needs mask * B_k z_k at masked-out pixels).
 """
@@ -107,22 +111,24 @@ def _queue_backward_end():
     torch.autograd.Variable._execution_engine.queue_callback(run)
 
 
-def _forward_generic(g, yp, mask_p, tau, A, B, keep_codes, keep_resid):
-    """Whole sweep from one C call (cdl_ista_forward): same launches as the stepwise form below."""
+def _forward_generic(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, cmap=None, tslope=None):
+    """Whole sweep from one C call (cdl_ista_forward): same launches as the stepwise form below.  cmap (N,1,*code grid)
+    with tslope (K,M): the noise-level map; tau then holds t[k,0,m]."""
     keep = keep_codes or keep_resid
-    xp, z, codes, resid, _ = ops.ista_forward(g, yp, mask_p, tau, A, B, keep)
+    xp, z, codes, resid, _ = ops.ista_forward(g, yp, mask_p, tau, A, B, keep, cmap=cmap, tslope=tslope)
     return xp, z, codes, (resid if keep_resid else []), []
 
 
-def _forward_generic_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid):
+def _forward_generic_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, cmap=None, tslope=None):
     """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
     K = len(A)
     codes, resid = [], []
-    z = ops.analysis(g, yp, A[0], 1.0, None, None, tau[0])
+    slope = (lambda k: tslope[k]) if cmap is not None else (lambda k: None)
+    z = ops.analysis(g, yp, A[0], 1.0, None, None, tau[0], cmap=cmap, tslope=slope(0))
     codes.append(z)
     for k in range(1, K):
         r = ops.synthesis(g, z, B[k], 1.0, None, mask_p, yp)
-        z = ops.analysis(g, r, A[k], -1.0, z, None, tau[k])
+        z = ops.analysis(g, r, A[k], -1.0, z, None, tau[k], cmap=cmap, tslope=slope(k))
         if keep_codes:
             codes.append(z)
         if keep_resid:
@@ -182,16 +188,21 @@ def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, map
                                maps=list(maps) if maps else None, layout=layout, dyp=dyp, dtau=dtau)
 
 
-def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None):
-    """Reverse sweep from one C call (cdl_ista_backward; dyp / dtau: see ops.fused_backward)."""
+def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None,
+                      cmap=None, tslope=None, dcmap=None):
+    """Reverse sweep from one C call (cdl_ista_backward; dyp / dtau: see ops.fused_backward).  cmap / tslope: the noise-level
+    map of the forward in place of c (then None, as dtau); dcmap (nullable) receives dL/dcmap."""
     if g_xp is None and g_z is None:
         return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
     return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, dyp=dyp,
-                             dtau=dtau)
+                             dtau=dtau, cmap=cmap, tslope=tslope, dcmap=dcmap)
 
 
-def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None):
+def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None,
+                               cmap=None, tslope=None, dcmap=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
+    if cmap is not None:
+        return _backward_generic_stepwise_map(g, K, yp, mask_p, A, B, codes, resid, g_xp, g_z, dt, dyp, cmap, tslope, dcmap)
     dA, dB = [None] * K, [None] * K
     zK = codes[K - 1]
     if g_xp is not None:
@@ -215,6 +226,35 @@ def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_
     dA[0] = ops.wgrad(g, gk, yp, 1.0, gate=codes[0])
     if dyp is not None:                                             # u_0 = A_0 yp
         ops.dyp_split(g, ops.synthesis(g, gk, A[0], 1.0, codes[0]), None, dyp, K > 1, make_q=False)
+    return dA, dB
+
+
+def _backward_generic_stepwise_map(g, K, yp, mask_p, A, B, codes, resid, g_xp, g_z, dt, dyp, cmap, tslope, dcmap):
+    """The stepwise reverse sweep with a noise-level map: the launches of cdl_ista_backward, one op each."""
+    dA, dB = [None] * K, [None] * K
+    zK = codes[K - 1]
+    if g_xp is not None:
+        dB[0] = ops.wgrad(g, zK, g_xp, 1.0)
+        gk = ops.analysis_rev(g, g_xp, B[0], 1.0, g_z, zK, None, dt[K - 1], cmap=cmap)
+    else:
+        dB[0] = torch.zeros_like(B[0])
+        gk = g_z.clone()
+        ops.tau_grad(g, gk, zK, None, dt[K - 1], cmap=cmap, gate=True)
+    for k in range(K - 1, -1, -1):                                  # gk = du_k (gated), dt[k] written
+        if dcmap is not None:
+            ops.sigma_grad(g, gk, codes[k], tslope[k], dcmap, k < K - 1)
+        if k == 0:
+            break
+        if dyp is not None:
+            q = ops.synthesis(g, gk, A[k], 1.0, None, None, None)
+            ops.dyp_split(g, q, mask_p, dyp, k < K - 1)
+        else:
+            q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
+        dA[k], dB[k] = ops.wgrad_pair(g, gk, resid[k - 1], -1.0, codes[k - 1], q, 1.0)
+        gk = ops.analysis_rev(g, q, B[k], 1.0, gk, codes[k - 1], None, dt[k - 1], cmap=cmap)
+    dA[0] = ops.wgrad(g, gk, yp, 1.0)
+    if dyp is not None:                                             # u_0 = A_0 yp
+        ops.dyp_split(g, ops.synthesis(g, gk, A[0], 1.0), None, dyp, K > 1, make_q=False)
     return dA, dB
 
 
@@ -302,7 +342,12 @@ class UnrolledISTA(torch.autograd.Function):
         nd = yp.dim() - 2
         P = tuple(A[0].shape[2:])
         g = ops.Geometry.make(N, C, M, yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
-        tau = ops.thresholds(t, c, N)
+        # a noise-level map (dense (N,1,*code grid), net._noise_scale): tau holds t[k,0,m] for every sample and the generic
+        # sweeps form tau + c[n,pix] * t[k,1,m] in their shrinkage epilogues
+        ctx.is_map = c is not None and c.dim() > 1
+        cmap = c if ctx.is_map else None
+        tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
+        tau = ops.thresholds(t, None if ctx.is_map else c, N)
 
         ctx.set_materialize_grads(False)          # an unused z output must not cost a fat zero tensor
         _no_data_gradients(ctx, ((1, "mask"),))   # y and sigma (through c): dL/dyp and dtau from the sweeps
@@ -311,6 +356,7 @@ class UnrolledISTA(torch.autograd.Function):
         ctx.want_c = ctx.needs_input_grad[2] and c is not None
         want_codes = cfg.get("all_codes", False)
         auto = BACKEND == "auto" and not ctx.exact     # "fp32": the fused kernels are matrix-core kernels
+        auto = auto and not ctx.is_map                 # the fused kernels read tau[n,m]: a map runs the generic sweep
         ctx.fused = auto and ops.fused_supported(g)
         ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
         if ctx.fusedg:
@@ -323,7 +369,8 @@ class UnrolledISTA(torch.autograd.Function):
             ctx.precision = PRECISION                  # the reverse sweep runs in the forward's arithmetic
             xp, z, codes, resid, maps = _forward_fused(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
         else:
-            xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, keep or want_codes, keep)
+            xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, keep or want_codes, keep,
+                                                         **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
         xhat = ops.postprocess(xp, mean, pads)
 
         ctx.geom, ctx.pads, ctx.K = g, pads, K
@@ -363,16 +410,23 @@ class UnrolledISTA(torch.autograd.Function):
         live = g_xp is not None or g_z is not None
         # data gradients only when asked for: otherwise the sweeps get NULLs and run exactly the parameter-only launches
         dyp = torch.empty(g.image_shape(), device=yp.device, dtype=torch.float32) if ctx.want_y and live else None
-        dtau = torch.empty((K, g.N, g.M), device=yp.device, dtype=torch.float32) if ctx.want_c and live else None
+        dtau = torch.empty((K, g.N, g.M), device=yp.device, dtype=torch.float32) \
+            if ctx.want_c and live and not ctx.is_map else None
         if ctx.fusedg:
             dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=ctx.layout,
                                       dyp=dyp, dtau=dtau)
         elif ctx.fused:                                # a loss on z only is a zero image gradient to the sweep
             dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
                                      layout=ctx.layout, precision=ctx.precision, dyp=dyp, dtau=dtau)
+        elif ctx.is_map:                               # dL/dc comes back as a map, through the slot of c
+            dcmap = torch.empty_like(c) if ctx.want_c and live else None
+            dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, cmap=c,
+                                       tslope=t.detach().reshape(K, 2, g.M)[:, 1].contiguous(), dcmap=dcmap)
         else:
             dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, dtau=dtau)
         dy = dc = None
+        if ctx.is_map:
+            dc = dcmap
         if dyp is not None:                            # a loss on z only: no mean term
             dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, y_mask)
         if dtau is not None:                           # tau[k,n,m] = t[k,0,m] + c[n] t[k,1,m]
@@ -496,13 +550,15 @@ class _ISTAIteration(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, zin, t_k, wA, wB, g, yp, mask_p, c):
-        tau = ops.thresholds(t_k.reshape((1,) + tuple(t_k.shape)), c, g.N)[0]
+        is_map = c is not None and c.dim() > 1         # noise-level map: see UnrolledISTA
+        tau = ops.thresholds(t_k.reshape((1,) + tuple(t_k.shape)), None if is_map else c, g.N)[0]
+        kw = dict(cmap=c, tslope=t_k.detach().reshape(2, g.M)[1].contiguous()) if is_map else {}
         if zin is None:
             r = yp
-            z = ops.analysis(g, yp, wA, 1.0, None, None, tau)
+            z = ops.analysis(g, yp, wA, 1.0, None, None, tau, **kw)
         else:
             r = ops.synthesis(g, zin, wB, 1.0, None, mask_p, yp)
-            z = ops.analysis(g, r, wA, -1.0, zin, None, tau)
+            z = ops.analysis(g, r, wA, -1.0, zin, None, tau, **kw)
         ctx.g, ctx.first, ctx.t_shape = g, zin is None, tuple(t_k.shape)
         ctx.mask_p, ctx.c = mask_p, c
         ctx.save_for_backward(zin if zin is not None else yp.new_empty(0), r, z, wA, wB)
@@ -514,7 +570,10 @@ class _ISTAIteration(torch.autograd.Function):
         zin, r, z, wA, wB = ctx.saved_tensors
         gk = gz.contiguous()
         dt_k = torch.zeros((2, g.M), device=gk.device, dtype=torch.float32)
-        ops.tau_grad(g, gk, z, ctx.c, dt_k)
+        if ctx.c is not None and ctx.c.dim() > 1:
+            ops.tau_grad(g, gk, z, None, dt_k, cmap=ctx.c)
+        else:
+            ops.tau_grad(g, gk, z, ctx.c, dt_k)
         dt_k = dt_k.reshape(ctx.t_shape)
         if ctx.first:
             dA = ops.wgrad(g, gk, r, 1.0, gate=z)

@@ -67,18 +67,46 @@ class _Synthesis3d(nn.ConvTranspose3d):
         return ops.synthesis(g, z, self.weight.detach())
 
 
-def _noise_scale(sigma, adaptive, N, device):
-    """c = sigma/255 per sample as an (N,) tensor, or None for c = 0 (net.py:82)."""
+def _code_grid(spatial, s):
+    """Spatial extent of the codes of an image of extent `spatial`: the stride-padded extent over the stride."""
+    return tuple(-(-int(d) // int(s)) for d in spatial)
+
+
+def _noise_scale(sigma, adaptive, N, device, code_spatial):
+    """c = sigma/255 (net.py:82): None for c = 0, an (N,) tensor (one level per sample), or -- a noise-level MAP -- a
+    dense (N, 1, *code_spatial) tensor.
+
+    A float, and a tensor with 1 or N elements whatever its shape, is one level per sample.  Every other tensor is a map
+    and must broadcast to (N, 1, *code_spatial) as it does against a code tensor in the reference: one level per frame
+    (N,1,D,1,1), a full map (N,1,Hc,Wc) / (N,1,Dc,Hc,Wc), or anything between; it is expanded on the host (it is 1/M of
+    a code tensor).  The one ambiguity of the first rule: a (1,1,H,W) map with H*W == N is read as N per-sample levels --
+    expand it to (N,1,H,W) to have it read as a map."""
     if sigma is None or not adaptive:
         return None
     if torch.is_tensor(sigma):
-        c = sigma.to(device=device, dtype=torch.float32).reshape(-1) / 255.0
-        if c.numel() == 1:
-            c = c.expand(N)
-        if c.numel() != N:
-            raise ValueError("sigma must be a scalar or hold one value per sample")
-        return c.contiguous()
+        if sigma.numel() in (1, N):
+            c = sigma.to(device=device, dtype=torch.float32).reshape(-1) / 255.0
+            if c.numel() == 1:
+                c = c.expand(N)
+            return c.contiguous()
+        want = (N, 1) + tuple(code_spatial)
+        if sigma.dim() > len(want):
+            raise ValueError(f"sigma of shape {tuple(sigma.shape)} does not broadcast to the code grid {want}")
+        shape = (1,) * (len(want) - sigma.dim()) + tuple(sigma.shape)
+        if shape[1] != 1:
+            raise ValueError(f"sigma of shape {tuple(sigma.shape)} varies over the channel axis: a noise-level map holds "
+                             f"one level per code pixel, (N, 1, *code grid) = {want}")
+        if any(a not in (1, b) for a, b in zip(shape, want)):
+            raise ValueError(f"sigma of shape {tuple(sigma.shape)} does not broadcast to the code grid {want} "
+                             "(the stride-padded image extent over the stride; utils.sigma_to_code_grid maps an "
+                             "image-resolution map onto it)")
+        c = sigma.to(device=device, dtype=torch.float32).reshape(shape) / 255.0
+        return c.expand(want).contiguous()
     return torch.full((N,), float(sigma) / 255.0, device=device, dtype=torch.float32)
+
+
+def _is_map(c):
+    return c is not None and c.dim() > 1
 
 
 def _mask_tensor(mask, y):
@@ -104,7 +132,7 @@ class _ISTANet(nn.Module):
                 "compute path; the iterations run in HIP kernels on a ROCm device.")
         y = y.to(torch.float32)
         A, B = self._filters()
-        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device)
+        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], self.s))
         return loop.run(y, _mask_tensor(mask, y), c, self.t, A, B, self.s, all_codes)
 
     def forward(self, y, sigma=None, mask=1):
@@ -238,7 +266,13 @@ class _CSRBase(_ISTANet):
             raise NotImplementedError(f"cdlnet_video_amd: {type(self).__name__}: gradients with respect to y / sigma "
                                       "are not implemented; detach() them")
         y = y.to(torch.float32)
-        return y, _mask_tensor(mask, y), _noise_scale(sigma, self.adaptive, y.shape[0], y.device)
+        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], self.s))
+        if _is_map(c):
+            # the three threshold families (t, g1, g2) would each follow the map; on every branch, the no-neighbour one
+            # included, so that the variant keeps one contract
+            raise NotImplementedError(f"cdlnet_video_amd: {type(self).__name__}: a noise-level map (sigma of shape "
+                                      f"{tuple(sigma.shape)}) is not implemented for the CSR nets; pass one level per sample")
+        return y, _mask_tensor(mask, y), c
 
 
 class CDLNet_CSR(_CSRBase):
@@ -375,7 +409,7 @@ class CDLNetVideo(_ISTANet):
             raise RuntimeError(f"CDLNetVideo.forward: input is on {y.device}; this package has no CPU compute path")
         y = y.to(torch.float32)
         A, B = self._filters()
-        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device)
+        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], self.s))
         blocks = [(b.conv1.weight, b.conv2.weight) for b in self.residual_blocks]
         return loop.run_residual(y, _mask_tensor(mask, y), c, self.t, A, B, self.s, blocks, all_codes)
 

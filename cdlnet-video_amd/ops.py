@@ -239,9 +239,23 @@ def shrink(x, tau):
     return out
 
 
-def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=None):
+def _check_map(g: Geometry, cmap, tslope=None, rows=1):
+    """A noise-level map is a dense (N, 1, *code_spatial) tensor; its slope row(s) hold `rows` * M values."""
+    if cmap is not None and tuple(cmap.shape) != (g.N, 1) + g.code_spatial:
+        raise ValueError(f"cmap: shape {tuple(cmap.shape)} is not the code grid {(g.N, 1) + g.code_spatial}")
+    if tslope is not None and tslope.numel() != rows * g.M:
+        raise ValueError(f"tslope: expected {rows * g.M} values, got {tslope.numel()}")
+
+
+def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=None, *, cmap=None, tslope=None):
+    """cdl_analysis_ws.  cmap (N,1,*code_spatial) with tslope (M): the threshold of element (n, m, pix) is
+    tau[n,m] + cmap[n,pix] * tslope[m] (tau then holds t[k,0,m])."""
     x, w = _dev(x, "x"), _dev(w, "w")
     zin, gate, tau = _opt(zin, "zin"), _opt(gate, "gate"), _opt(tau, "tau")
+    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
+    if (cmap is None) != (tslope is None):
+        raise ValueError("cmap and tslope go together")
+    _check_map(g, cmap, tslope)
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
     if out is None:
@@ -250,7 +264,7 @@ def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=No
     n = int(_lib.lib().cdl_analysis_workspace_floats(ctypes.byref(gs)))
     ws = _scratch(x.device, n) if n else None
     rc = _lib.lib().cdl_analysis_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin),
-                                    _ptr(gate), _ptr(tau), _ptr(out), _ptr(ws), n, _stream())
+                                    _ptr(gate), _ptr(tau), _ptr(out), _ptr(ws), n, _ptr(cmap), _ptr(tslope), _stream())
     _lib.check(rc, "cdl_analysis_ws")
     return out
 
@@ -319,17 +333,33 @@ def wgrad_pair(g: Geometry, z0, x0, alpha0, z1, x1, alpha1):
     return dw0, dw1
 
 
-def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None):
-    """Writes the (2,M) slice `dt_k` of the threshold gradient for one iteration [and the per-sample (N,M) `dtau_n`]."""
-    gup, zout, c = _dev(gup, "g"), _dev(zout, "zout"), _opt(c, "c")
-    scratch = torch.empty(16 * g.N * g.M, device=gup.device, dtype=torch.float32)      # CDL_TAU_SPLITS * N * M
+def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None, *, cmap=None, gate=False):
+    """Writes the (2,M) slice `dt_k` of the threshold gradient for one iteration [and the per-sample (N,M) `dtau_n`].
+    cmap (in place of c): dt_k[1] is weighted by the noise-level map.  gate: `gup` is also gated in place by the support
+    of `zout` (cdl_tau_grad_gate)."""
+    gup, zout, c, cmap = _dev(gup, "g"), _dev(zout, "zout"), _opt(c, "c"), _opt(cmap, "cmap")
+    _check_map(g, cmap)
+    # CDL_TAU_SPLITS * N * M (twice with a map)
+    scratch = torch.empty((32 if cmap is not None else 16) * g.N * g.M, device=gup.device, dtype=torch.float32)
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
     assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
     gs = g.c_struct()
     base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_tau_grad(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
-                                 ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _stream())
-    _lib.check(rc, "cdl_tau_grad")
+    fn = _lib.lib().cdl_tau_grad_gate if gate else _lib.lib().cdl_tau_grad
+    rc = fn(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
+            ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _ptr(cmap), _stream())
+    _lib.check(rc, "cdl_tau_grad_gate" if gate else "cdl_tau_grad")
+
+
+def sigma_grad(g: Geometry, du, z, tslope, dcmap, acc_add):
+    """dcmap (N,1,*code_spatial) (+)= -sum_m tslope[m] sign(z) du: the noise-level map's gradient of one iteration
+    (cdl_sigma_grad); du is the gated dL/du_k, z = z_{k+1}."""
+    du, z, tslope = _dev(du, "du"), _dev(z, "z"), _dev(tslope, "tslope")
+    assert tuple(du.shape) == g.code_shape() == tuple(z.shape) and dcmap.is_contiguous()
+    _check_map(g, dcmap, tslope)
+    rc = _lib.lib().cdl_sigma_grad(ctypes.byref(g.c_struct()), _ptr(du), _ptr(z), _ptr(tslope), _ptr(dcmap),
+                                   int(bool(acc_add)), _stream())
+    _lib.check(rc, "cdl_sigma_grad")
 
 
 def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
@@ -339,11 +369,13 @@ def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
     _lib.check(rc, "cdl_dyp_split")
 
 
-def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None):
+def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None, *, cmap=None):
     """One reverse-sweep step (cdl_analysis_rev_ws): out = [zsup != 0] (zin + alpha A x), and the (2, M) threshold
     gradient slice `dt_k` of `out` with respect to the code `zsup` -- cdl_analysis followed by cdl_tau_grad_gate, as one
     fat launch where the matrix-core analysis covers the geometry."""
     x, w, zin, zsup, c = _dev(x, "x"), _dev(w, "w"), _opt(zin, "zin"), _dev(zsup, "zsup"), _opt(c, "c")
+    cmap = _opt(cmap, "cmap")                                  # the noise-level map in place of c (dt_k[1] weighted by it)
+    _check_map(g, cmap)
     if out is None:
         out = _new(g.code_shape(), x.device)
     assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
@@ -353,7 +385,7 @@ def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None):
     base = dt_k.data_ptr()
     rc = _lib.lib().cdl_analysis_rev_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(zsup), _ptr(c),
                                         ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), None, _ptr(out), _ptr(ws),
-                                        n, _stream())
+                                        n, _ptr(cmap), _stream())
     _lib.check(rc, "cdl_analysis_rev_ws")
     return out
 
@@ -1092,10 +1124,16 @@ def ista_scratch(g: Geometry, device):
     return _scratch(device, max(n, 1)), n
 
 
-def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=None, gam1=None, gam2=None):
+def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=None, gam1=None, gam2=None, *,
+                 cmap=None, tslope=None):
     """Generic forward sweep in one C call.  Plain ST loop (z_prev None) or the CSR maps.  keep=True:
-    every z_k, r_k (and u_k for CSR) gets its own buffer.  Returns (xp, z_K, codes, resid, us)."""
+    every z_k, r_k (and u_k for CSR) gets its own buffer.  Returns (xp, z_K, codes, resid, us).
+    cmap (N,1,*code_spatial) with tslope (K,M) = t[:,1]: noise-level map, see analysis (plain loop only)."""
     K = len(A)
+    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
+    if (cmap is None) != (tslope is None):
+        raise ValueError("cmap and tslope go together")
+    _check_map(g, cmap, tslope, K)
     yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
@@ -1115,17 +1153,23 @@ def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=
     rc = _lib.lib().cdl_ista_forward(ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(tau), _ptr(z_prev),
                                      _ptr(z_after), _ptr(gam1), _ptr(gam2), _ptr_table(A), _ptr_table(B),
                                      _ptr_table(z), _ptr_table(r) if r else None, _ptr_table(u) if u else None,
-                                     _ptr(xp), _ptr(ws), n, _stream())
+                                     _ptr(xp), _ptr(ws), n, _ptr(cmap), _ptr(tslope), _stream())
     _lib.check(rc, "cdl_ista_forward")
     return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), u
 
 
 def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, us=None, z_prev=None,
                   z_after=None, lam=None, gam1=None, gam2=None, dg1=None, dg2=None, gz_prev=None, gz_after=None,
-                  dyp=None, dtau=None):
+                  dyp=None, dtau=None, *, cmap=None, tslope=None, dcmap=None):
     """Generic reverse sweep in one C call (cdl_ista_backward); returns (dA, dB) and fills dt [, dg1, dg2, gz_prev,
-    gz_after] [, dyp, dtau: see fused_backward; plain loop only]."""
+    gz_after] [, dyp, dtau: see fused_backward; plain loop only].  cmap / tslope as ista_forward's (c is then None);
+    dcmap (N,1,*code_spatial; nullable) receives dL/dcmap where dtau would be returned."""
     K = len(A)
+    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
+    _check_map(g, cmap, tslope, K)
+    if dcmap is not None:
+        assert cmap is not None and tslope is not None and dcmap.is_contiguous()
+        _check_map(g, dcmap)
     dev = yp.device
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
@@ -1142,7 +1186,7 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
         _ptr_table([_dev(t, "z") for t in codes]), _ptr_table([_dev(t, "r") for t in resid]) if resid else None,
         _ptr_table([_dev(t, "u") for t in us]) if us else None, _ptr(_opt(g_xp, "g_xp")), _ptr(_opt(g_z, "g_z")),
         _ptr_table(dA), _ptr_table(dB), _ptr(dt), _ptr(dg1), _ptr(dg2), _ptr(gz_prev), _ptr(gz_after),
-        _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _stream())
+        _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _ptr(cmap), _ptr(tslope), _ptr(dcmap), _stream())
     _lib.check(rc, "cdl_ista_backward")
     return dA, dB
 

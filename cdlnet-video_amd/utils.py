@@ -47,6 +47,24 @@ def awgn3d(input, noise_std, generator=None):
     return _awgn(input, noise_std, generator)
 
 
+def sigma_to_code_grid(sigma_img, s):
+    """An image-resolution noise-level map (N,1,*spatial) on the code grid of a stride-`s` net, the form the nets take
+    as `sigma`: the reflect padding pre_process gives the image (ops.split_pad per axis), then the mean over each s^nd
+    block -- (N,1,*ceil(spatial/s)).  Identity at s = 1.  A convention of this package (one code pixel answers for an
+    s^nd block of the image), not reference behaviour; a thin tensor, host torch ops, differentiable."""
+    from .ops import stride_pads
+    s = int(s)
+    if sigma_img.dim() not in (4, 5) or sigma_img.shape[1] != 1:
+        raise ValueError(f"expected an (N,1,H,W) or (N,1,D,H,W) map, got {tuple(sigma_img.shape)}")
+    if s == 1:
+        return sigma_img
+    padded = torch.nn.functional.pad(sigma_img, stride_pads(sigma_img.shape[2:], s), mode="reflect")
+    N = padded.shape[0]
+    grid = tuple(d // s for d in padded.shape[2:])
+    blocks = padded.reshape((N, 1) + tuple(v for d in grid for v in (d, s)))
+    return blocks.mean(dim=tuple(range(3, 2 + 2 * len(grid), 2)))
+
+
 def psnr(x, xhat):
     """-10 log10 MSE with peak 1.0 (analyze.py:104, analyze3d.py:131-133)."""
     return -10.0 * math.log10(torch.mean((x - xhat) ** 2).item())

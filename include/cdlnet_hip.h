@@ -106,26 +106,30 @@ int cdl_shrink(const float *x, const float *tau /*rows*/, float *out, int rows, 
  *   out  = tau ? ST(base + acc, tau[n,m]) : base + acc,  ST(u,t) = sign(u)*max(|u|-t,0) (net.py:11-14)
  * Forward k=0: (alpha=+1, zin=NULL, tau).  Forward k>=1: (alpha=-1, zin=z_k, tau) with
  * x = mask*B_k z_k - yp.  Backward: g_k = [z_{k+1}!=0]*g_{k+1} + corr(q ; B_k) is
- * (alpha=+1, zin=g_{k+1}, gate=z_{k+1}, tau=NULL).  out must not alias zin. */
+ * (alpha=+1, zin=g_{k+1}, gate=z_{k+1}, tau=NULL).  out must not alias zin.
+ * Noise-level map (net.py:82-87 with a sigma that varies over the code grid; both NULL: none): cmap (N, code pixels)
+ * and tslope (M) turn the threshold of element (n, m, pix) into tau[n,m] + cmap[n,pix] * tslope[m] -- tau then holds
+ * t[k,0,m], tslope t[k,1,m], cmap sigma/255; the product is rounded before the sum, as torch's broadcast does. */
 int cdl_analysis(const cdl_geom *g, const float *x, const float *w, float alpha,
                  const float *zin /*nullable*/, const float *gate /*nullable*/,
-                 const float *tau /*N*M, nullable*/, float *out, void *stream);
+                 const float *tau /*N*M, nullable*/, float *out, const float *cmap /*nullable*/,
+                 const float *tslope /*M, nullable*/, void *stream);
 /* cdl_analysis with scratch (cdl_analysis_workspace_floats(g) floats, 0 when no kernel wants it): lets the
  * matrix-core kernel of the shape-generic path stage its prepared filter fragments.  workspace == NULL: VALU. */
 int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
                     const float *zin /*nullable*/, const float *gate /*nullable*/,
                     const float *tau /*N*M, nullable*/, float *out, float *workspace, size_t workspace_floats,
-                    void *stream);
+                    const float *cmap /*nullable*/, const float *tslope /*M, nullable*/, void *stream);
 size_t cdl_analysis_workspace_floats(const cdl_geom *g);
 /* One step of the reverse sweep (autograd of net.py:87 / 205 through the shrinkage of the previous iteration):
  *   out = [zsup != 0] * (zin + alpha * A x),   (dt0, dt1[, dtau_n]) = cdl_tau_grad(out, zsup, c)
  * i.e. cdl_analysis_ws followed by cdl_tau_grad_gate, as ONE fat launch where the matrix-core analysis covers the
  * geometry (gate and threshold partials in its epilogue).  dtau_n NULL: no per-sample threshold gradients.
- * out must differ from zin and zsup. */
+ * out must differ from zin and zsup.  cmap (nullable; then c and dtau_n must be NULL): as cdl_tau_grad's. */
 int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
                         const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
                         float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
-                        void *stream);
+                        const float *cmap /*N, code pixels; nullable*/, void *stream);
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g);
 
 /* ---- synthesis half: F.conv_transpose2d/3d at net.py:87,90,205,210 and gabor.py:64 ----------
@@ -166,16 +170,23 @@ size_t cdl_wgrad_workspace_floats(const cdl_geom *g);
  * (c NULL -> dt1 = 0).  dtau_n (nullable) receives the per-sample threshold gradient dtau_n[n,m] = -sum_pix
  * sign(zout)*du of sample n (dt0 = sum_n dtau_n, dt1 = sum_n c[n] dtau_n): what dL/dc needs; dt0 / dt1 do not depend
  * on whether it is given.  scratch: CDL_TAU_SPLITS*N*M floats (rows are split over workgroups and folded in a fixed
- * order). dt0/dt1 are overwritten. */
+ * order). dt0/dt1 are overwritten.
+ * cmap (N, code pixels; nullable): the noise-level map of cdl_analysis in place of c (c and dtau_n must then be NULL):
+ *   dt1[m] = -sum_{n,pix} cmap[n,pix] * sign(zout)*du, a second partial per row; scratch: 2*CDL_TAU_SPLITS*N*M floats. */
 #define CDL_TAU_SPLITS 16
 int cdl_tau_grad(const cdl_geom *g, const float *gup, const float *zout, const float *c /*N, nullable*/,
                  float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
-                 float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+                 float *scratch /*CDL_TAU_SPLITS*N*M*/, const float *cmap /*nullable*/, void *stream);
 /* Same, and gup is gated IN PLACE (gup[i] = 0 where zout[i] == 0) in the same pass: the reverse sweep's three
  * consumers of the gated gradient then need no gate (one fat read each less). */
 int cdl_tau_grad_gate(const cdl_geom *g, float *gup /*inout*/, const float *zout, const float *c /*N, nullable*/,
                       float *dt0 /*M*/, float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/,
-                      float *scratch /*CDL_TAU_SPLITS*N*M*/, void *stream);
+                      float *scratch /*CDL_TAU_SPLITS*N*M*/, const float *cmap /*nullable*/, void *stream);
+/* Gradient of the noise-level map, one iteration (a reduction over the code channels, fixed order):
+ *   dcmap[n,pix] (+)= -sum_m tslope[m] * sign(z[n,m,pix]) * du[n,m,pix]      du = dL/du_k (gated), z = z_{k+1}
+ * acc_add 0: dcmap is overwritten. */
+int cdl_sigma_grad(const cdl_geom *g, const float *du, const float *z, const float *tslope /*M*/,
+                   float *dcmap /*N, code pixels*/, int acc_add, void *stream);
 /* Generic reverse sweep, iteration k: q holds S = A_k^T du_k (unmasked, alpha = +1); dyp = S (acc_add 0) or dyp += S,
  * then with make_q: q = -(mask ? mask : 1) * S in place -- the q_k the sweep continues with. */
 int cdl_dyp_split(const cdl_geom *g, float *q /*inout, thin*/, const float *mask /*nullable*/, float *dyp,
@@ -311,14 +322,17 @@ int cdl_residual_backward(const cdl_geom *g, const float *x, const float *h, con
  * scratch, q thin scratch, scratch as above (required).  The gradients of the data (plain loop only: z_prev must be
  * NULL when either is given; both NULL: neither is computed):
  *     dyp  (thin, as yp; nullable):  dL/dyp = sum_k A_k^T du_k  (u_0 = A_0 yp, u_k = z_k - A_k(mask B_k z_k - yp))
- *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau) */
+ *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau)
+ * Noise-level map (plain loop only; all NULL: none): cmap (N, code pixels) and tslope (K,M) = t[:,1,:] as in cdl_analysis,
+ * tau then holding t[k,0,m] for every sample; in the reverse sweep cmap takes the place of c (c and dtau must be NULL) and
+ *     dcmap (N, code pixels; nullable): dL/dcmap = sum_k cdl_sigma_grad(du_k, z_{k+1}, tslope[k]) */
 size_t cdl_ista_scratch_floats(const cdl_geom *g);
 int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                      const float *tau, const float *z_prev /*nullable*/, const float *z_after /*nullable*/,
                      const float *gam1 /*nullable*/, const float *gam2 /*nullable*/,
                      const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                      float *const *u /*nullable*/, float *xp, float *scratch, size_t scratch_floats,
-                     void *stream);
+                     const float *cmap /*nullable*/, const float *tslope /*K*M, nullable*/, void *stream);
 int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                       const float *c /*N, nullable*/, const float *z_prev /*nullable*/,
                       const float *z_after /*nullable*/, const float *lam, const float *gam1, const float *gam2,
@@ -328,6 +342,7 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
                       float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
                       size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M, nullable*/,
+                      const float *cmap /*nullable*/, const float *tslope /*K*M, nullable*/, float *dcmap /*nullable*/,
                       void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
