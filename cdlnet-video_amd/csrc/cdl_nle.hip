@@ -90,6 +90,81 @@ __global__ __launch_bounds__(1024) void k_select(const float *__restrict__ v, fl
     if (threadIdx.x == 0) out[blockIdx.x] = __builtin_bit_cast(float, prefix) / divisor;
 }
 
+// ---- local estimates: the same selection over a window of the band, one workgroup per (image, cell) ----
+// Cells along an axis of band length L, window w, step q: one cell [0, L) if L <= w, otherwise ceil((L - w) / q) + 1
+// cells of w samples, cell i starting at min(i * q, L - w) (the last one flush with the border).
+__host__ __device__ inline int cell_count(int L, int w, int q) { return L <= w ? 1 : (L - w + q - 1) / q + 1; }
+__host__ __device__ inline int cell_start(int i, int L, int w, int q) { return L <= w ? 0 : min(i * q, L - w); }
+
+constexpr int CELL_THREADS = 256, CELL_WAVES = CELL_THREADS / 64;
+// samples staged in LDS next to the 8 KB histogram: 56 KB a workgroup at the most, so two share a CU's 160 KB
+constexpr int CELL_STAGE_MAX = 12288;
+
+// k-th smallest of the C * ch * cw samples of one cell of the band (N, C, Hb, Wb), as k_select finds it (3 radix
+// passes over the bit patterns, integer counting only), with the samples read once into LDS when STAGED (dynamic
+// shared memory: 2048 histogram words, then the samples) and from the band in memory on every pass otherwise.  The
+// bin holding the target rank is found by all threads: each sums nb / 256 consecutive bins, a wave-shuffle prefix
+// scan orders the sums, and the one thread whose range holds the rank walks its own bins.
+template <bool STAGED>
+__global__ __launch_bounds__(CELL_THREADS) void k_select_cells(const float *__restrict__ band,
+                                                                float *__restrict__ out, int C, int Hb, int Wb, int w,
+                                                                int q, int ny, int nx, float divisor)
+{
+    extern __shared__ unsigned cell_lds[];
+    unsigned *hist = cell_lds, *stage = cell_lds + 2048;
+    __shared__ unsigned wave_sum[CELL_WAVES], sel_prefix, sel_rank;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cx = blockIdx.x % nx, cy = (blockIdx.x / nx) % ny;
+    const size_t n = blockIdx.x / ((unsigned)nx * ny);
+    const int ch = min(w, Hb), cw = min(w, Wb), y0 = cell_start(cy, Hb, w, q), x0 = cell_start(cx, Wb, w, q);
+    const unsigned per_c = (unsigned)ch * cw, count = (unsigned)C * per_c;
+    const unsigned *bits = reinterpret_cast<const unsigned *>(band) + (n * C * Hb + y0) * (size_t)Wb + x0;
+    auto load = [&](unsigned e) -> unsigned {              // sample e of the cell, (c, row, column) order
+        const unsigned c = e / per_c, r = e % per_c;
+        return bits[((size_t)c * Hb + r / cw) * Wb + r % cw];
+    };
+    if (STAGED) {
+        for (unsigned e = tid; e < count; e += CELL_THREADS) stage[e] = load(e);
+    }
+    unsigned prefix = 0, mask = 0, rank = (count - 1) / 2;  // torch.median: the lower of the two middle values
+    const int shifts[3] = {21, 10, 0}, widths[3] = {11, 11, 10};
+    for (int pass = 0; pass < 3; ++pass) {
+        const int sh = shifts[pass], nb = 1 << widths[pass], per_t = nb / CELL_THREADS;
+        for (int b = tid; b < nb; b += CELL_THREADS) hist[b] = 0;
+        __syncthreads();
+        for (unsigned e = tid; e < count; e += CELL_THREADS) {
+            const unsigned u = STAGED ? stage[e] : load(e);
+            if ((u & mask) == prefix) atomicAdd(&hist[(u >> sh) & (nb - 1)], 1u);
+        }
+        __syncthreads();
+        unsigned mine = 0;
+        for (int b = 0; b < per_t; ++b) mine += hist[tid * per_t + b];
+        unsigned incl = mine;                                // inclusive scan over the wave, then over the 4 waves
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        unsigned before = incl - mine;
+        for (int v = 0; v < wave; ++v) before += wave_sum[v];
+        if (before <= rank && rank < before + mine) {        // exactly one thread: the matching samples number > rank
+            int b = tid * per_t;
+            for (const int last = b + per_t - 1; b < last; ++b) {   // the rank is in this thread's bins: its last one if no earlier
+                if (before + hist[b] > rank) break;
+                before += hist[b];
+            }
+            sel_prefix = prefix | ((unsigned)b << sh);
+            sel_rank = rank - before;
+        }
+        __syncthreads();
+        prefix = sel_prefix;
+        rank = sel_rank;
+        mask |= (unsigned)(nb - 1) << sh;
+    }
+    if (tid == 0) out[blockIdx.x] = __builtin_bit_cast(float, prefix) / divisor;
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,6 +187,34 @@ int cdl_nle_mad(const float *y, float *sigma_hat, float *scratch, size_t scratch
     CDL_LAUNCH_CHECK();
     // torch.median returns the lower of the two middle values: 0-based rank (n - 1) / 2
     k_select<<<(unsigned)N, 1024, 0, S(stream)>>>(scratch, sigma_hat, per_n, (per_n - 1) / 2, 0.6745f);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t cdl_nle_mad_cells_scratch_floats(int N, int C, int H, int W)
+{
+    return cdl_nle_mad_scratch_floats(N, C, H, W);
+}
+
+int cdl_nle_mad_cells(const float *y, float *cells, float *scratch, size_t scratch_floats, int N, int C, int H, int W,
+                      int window, int step, void *stream)
+{
+    if (!y || !cells || !scratch || N <= 0 || C <= 0) return CDL_EINVAL;
+    if (H < TAPS || W < TAPS || window < 2 || step < 1) return CDL_EINVAL;
+    const int Ho = (H - TAPS) / 2 + 1, Wo = (W - TAPS) / 2 + 1;
+    const size_t total = (size_t)N * C * Ho * Wo;
+    if (scratch_floats < total) return CDL_EINVAL;
+    const int ny = cell_count(Ho, window, step), nx = cell_count(Wo, window, step);
+    const size_t blocks = (size_t)N * ny * nx, count = (size_t)C * min(window, Ho) * min(window, Wo);
+    if (blocks > 0x7fffffffu || count > 0x7fffffffu) return CDL_EINVAL;
+    k_hh_abs<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(y, scratch, N * C, H, W, Ho, Wo);
+    CDL_LAUNCH_CHECK();
+    if (count <= (size_t)CELL_STAGE_MAX)
+        k_select_cells<true><<<(unsigned)blocks, CELL_THREADS, (2048 + count) * sizeof(unsigned), S(stream)>>>(
+            scratch, cells, C, Ho, Wo, window, step, ny, nx, 0.6745f);
+    else
+        k_select_cells<false><<<(unsigned)blocks, CELL_THREADS, 2048 * sizeof(unsigned), S(stream)>>>(
+            scratch, cells, C, Ho, Wo, window, step, ny, nx, 0.6745f);
     CDL_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,6 @@
-"""Blind noise-level estimation (reference model/nle.py): `noise_level(y, method="MAD")` / `nle_mad(y)`, `nle_pca(y)`.
+"""Blind noise-level estimation (reference model/nle.py): `noise_level(y, method="MAD")` / `nle_mad(y)`, `nle_pca(y)`,
+and the local forms of the MAD estimate that produce a noise-level map: `nle_mad_cells`, `nle_mad_map`,
+`nle_mad_frames`.
 
 `nle_mad` runs in libcdlnet_hip.so (cdl_nle_mad): depthwise stride-2 correlation with the 'bior4.4'
 diagonal (HH) analysis filter and an exact per-sample median.  `nle_pca` (weak-texture PCA) forms, per pass and
@@ -11,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, utils
 
 
 def nle_mad(y):
@@ -30,6 +32,125 @@ def nle_mad(y):
     rc = lib.cdl_nle_mad(ops._ptr(y), ops._ptr(out), ops._ptr(scratch), n, N, C, H, W, ops._stream())
     _lib.check(rc, "cdl_nle_mad")
     return out.reshape(-1, 1, 1, 1)
+
+
+TAPS = 10                              # the 'bior4.4' diagonal filter is 10 x 10; band sample i sees pixels 2i .. 2i+9
+
+
+def band_length(L):
+    return (L - TAPS) // 2 + 1
+
+
+def cell_starts(L, window, step):
+    """First band sample of every cell along an axis of band length L: one cell [0, L) if L <= window, otherwise
+    ceil((L - window) / step) + 1 cells of `window` samples, the last flush with the border."""
+    if L <= window:
+        return [0]
+    return [min(i * step, L - window) for i in range(-(-(L - window) // step) + 1)]
+
+
+def _window_step(window, step):
+    if window is None or int(window) != window or window < 2:
+        raise ValueError(f"window {window!r}: expected an integer >= 2 (band samples)")
+    step = int(window) // 2 if step is None else step
+    if int(step) != step or step < 1:
+        raise ValueError(f"step {step!r}: expected an integer >= 1 (band samples)")
+    return int(window), int(step)
+
+
+def _frames(y, name):
+    """(images (B,C,H,W), leading shape of the result): a clip (N,C,D,H,W) is its N*D frames, never mixed."""
+    y = ops._dev(y, "y")
+    if y.dim() == 4:
+        lead = (y.shape[0], 1)
+    elif y.dim() == 5:
+        lead = (y.shape[0], 1, y.shape[2])
+        y = y.transpose(1, 2).reshape((-1, y.shape[1]) + tuple(y.shape[3:]))      # a view for C = 1
+    else:
+        raise ValueError(f"{name} expects (N, C, H, W) or (N, C, D, H, W)")
+    if y.shape[-2] < TAPS or y.shape[-1] < TAPS:
+        raise ValueError("image smaller than the 10 x 10 wavelet filter")
+    return y.contiguous(), lead
+
+
+def _cells(y, window, step):
+    """cdl_nle_mad_cells on images y (B,C,H,W): (B, ny, nx)."""
+    B, C, H, W = y.shape
+    ny = len(cell_starts(band_length(H), window, step))
+    nx = len(cell_starts(band_length(W), window, step))
+    lib = _lib.lib()
+    n = int(lib.cdl_nle_mad_cells_scratch_floats(B, C, H, W))
+    scratch = ops._scratch(y.device, n)
+    out = torch.empty((B, ny, nx), device=y.device, dtype=torch.float32)
+    rc = lib.cdl_nle_mad_cells(ops._ptr(y), ops._ptr(out), ops._ptr(scratch), n, B, C, H, W, window, step,
+                               ops._stream())
+    _lib.check(rc, "cdl_nle_mad_cells")
+    return out
+
+
+def nle_mad_cells(y, window=32, step=None):
+    """The MAD estimate of nle_mad over windows of the band instead of the whole image: the lower median of |HHy|
+    over `window` x `window` band samples (all channels) / 0.6745, one value per cell, cells `step` samples apart
+    (default window // 2), the last cell of an axis flush with the border; an axis whose band is no longer than the
+    window is one cell.  y (N,C,H,W) gives (N,1,ny,nx); a clip (N,C,D,H,W) gives (N,1,D,ny,nx), every frame on its
+    own.  In y's scale.  A window covering the band returns the bits of nle_mad."""
+    window, step = _window_step(window, step)
+    imgs, lead = _frames(y, "nle_mad_cells")
+    cells = _cells(imgs, window, step)
+    return cells.reshape(lead + tuple(cells.shape[1:]))
+
+
+@functools.lru_cache(maxsize=64)
+def _interp_plan(L, window, step, device):
+    """(lo, hi, t) on `device` for one axis of L pixels: pixel p takes (1 - t) * cell[lo] + t * cell[hi], the
+    piecewise-linear interpolation between the cell centres, constant beyond the first and the last.  A cell
+    [i0, i1) of the band sees pixels 2 i0 .. 2 (i1 - 1) + 9: centre i0 + i1 - 1 + 4.5.  Device ops only."""
+    Lb = band_length(L)
+    n = len(cell_starts(Lb, window, step))
+    i0 = (torch.arange(n, device=device) * step).clamp(max=max(Lb - window, 0))
+    centre = (2 * i0 + (min(window, Lb) - 1)).double() + 4.5
+    p = torch.arange(L, device=device, dtype=torch.float64)
+    hi = torch.bucketize(p, centre).clamp(max=n - 1)            # first centre >= p
+    lo = (hi - 1).clamp(min=0)
+    gap = centre[hi] - centre[lo]
+    t = torch.where(gap > 0, (p - centre[lo]) / gap.clamp(min=1.0), torch.zeros_like(p)).clamp(0.0, 1.0)
+    return lo, hi, t.float()
+
+
+def _interpolate(cells, H, W, window, step):
+    """cells (B, ny, nx) -> (B, H, W), separable."""
+    lo, hi, t = _interp_plan(H, window, step, cells.device)
+    rows = torch.lerp(cells.index_select(1, lo), cells.index_select(1, hi), t[:, None])
+    lo, hi, t = _interp_plan(W, window, step, cells.device)
+    return torch.lerp(rows.index_select(2, lo), rows.index_select(2, hi), t)
+
+
+def nle_mad_frames(clip):
+    """One MAD estimate per frame of a clip (N,C,D,H,W): (N,1,D,1,1), each value the bits of nle_mad of that frame;
+    the per-frame form of `sigma` the nets take (times 255)."""
+    clip = ops._dev(clip, "clip")
+    if clip.dim() != 5:
+        raise ValueError("nle_mad_frames expects (N, C, D, H, W)")
+    imgs, lead = _frames(clip, "nle_mad_frames")
+    whole = max(band_length(imgs.shape[-2]), band_length(imgs.shape[-1]), 2)
+    return _cells(imgs, whole, whole).reshape(lead + (1, 1))
+
+
+def nle_mad_map(y, window=32, step=None, s=1):
+    """A blind noise-level map for `net(y, 255 * nle_mad_map(y, s=net.s))`: the cells of nle_mad_cells interpolated
+    to the image grid (separable, piecewise linear between the cell centres, constant beyond the outermost), then
+    taken to the code grid of a stride-`s` net by utils.sigma_to_code_grid.  y (N,C,H,W) gives (N,1,ceil(H/s),ceil(W/s)),
+    a clip (N,C,D,H,W) a map per frame on the clip's code grid.  window=None is one level per image, nle_mad(y)
+    (N,1,1,1), or per frame, nle_mad_frames(y) (N,1,D,1,1).  In y's scale; no copy to the host, no synchronisation."""
+    if window is None:
+        if torch.is_tensor(y) and y.dim() == 5:
+            return nle_mad_frames(y)
+        return nle_mad(y)
+    window, step = _window_step(window, step)
+    imgs, lead = _frames(y, "nle_mad_map")
+    H, W = imgs.shape[-2:]
+    img_map = _interpolate(_cells(imgs, window, step), H, W, window, step).reshape(lead + (H, W))
+    return utils.sigma_to_code_grid(img_map, s)
 
 
 def _derivative_matrix(p, horizontal):

@@ -239,6 +239,16 @@ size_t cdl_nle_mad_scratch_floats(int N, int C, int H, int W);
 int cdl_nle_mad(const float *y, float *sigma_hat /*N*/, float *scratch, size_t scratch_floats, int N, int C,
                 int H, int W, void *stream);
 
+/* The same estimate over windows of the band: along an axis of band length L = (H-10)/2 + 1
+ * there is one cell [0, L) if L <= window, otherwise ceil((L - window) / step) + 1 cells of `window` samples, cell i
+ * starting at min(i * step, L - window).  cells[n][iy][ix] = lower median of |HHy| over the cell and all C channels
+ * / 0.6745, exact; a window that covers the band gives the bits of cdl_nle_mad.  No atomics on floats: repeated
+ * calls are bit-identical.  CDL_EINVAL: null pointers, window < 2, step < 1, H or W < 10.
+ * scratch: cdl_nle_mad_cells_scratch_floats(N,C,H,W) floats (the band). */
+size_t cdl_nle_mad_cells_scratch_floats(int N, int C, int H, int W);
+int cdl_nle_mad_cells(const float *y, float *cells /*N x ny x nx*/, float *scratch, size_t scratch_floats, int N,
+                      int C, int H, int W, int window, int step, void *stream);
+
 /* model/nle.py:29-89 (nle_pca), the per-pass work of one channel: over every patchsize x patchsize patch of channel
  * `channel` of y (N,C,H,W), pooled over the batch, its texture strength Xtr (the sums of the squared half-differences
  * ((x[i][j] - x[i][j+2]) / 2)^2 over the patch's p x (p-2) window plus those along rows over its (p-2) x p window),
