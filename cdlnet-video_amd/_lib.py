@@ -73,6 +73,7 @@ SIGNATURES = {
     "cdl_gabor_filters_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cdl_options_reload": [],
     "cdl_set_exact_fp32": [_I],
+    "cdl_trace": [_I],
     "cdl_gabor_filter_banks": [_I, _P, _P, _P, _P, _IP, _P, _I, _I, _I, _I, _P],
     "cdl_gabor_filter_banks_bwd": [_I, _P, _P, _P, _P, _IP, _P, _P, _I, _I, _I, _I, _P],
     "cdl_fused2d_supported": [_G],
@@ -108,7 +109,8 @@ SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G
                 "cdl_synthesis_workspace_floats": [_G], "cdl_ista_scratch_floats": [_G], "cdl_analysis_workspace_floats": [_G], "cdl_analysis_rev_workspace_floats": [_G],
                 "cdl_nle_mad_scratch_floats": [_I, _I, _I, _I], "cdl_nle_mad_cells_scratch_floats": [_I, _I, _I, _I],
                 "cdl_nle_pca_scratch_floats": [_I, _I, _I, _I, _I], "cdl_residual_scratch_floats": [_G],
-                "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_vgg_scratch_floats": [_I, _I, _I, _I]}
+                "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_vgg_scratch_floats": [_I, _I, _I, _I],
+                "cdl_trace_read": [_P, ctypes.c_size_t]}
 
 _lib = None
 

@@ -432,6 +432,8 @@ int launch_mtp(const cdl_geom *g, const Plan &p, const float *x, const uint4 *fr
 {
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_ana_m<PH, PW, SW, MT, PROX, REV, MAP>, p.lds > 96 * 1024 ? LDS_MAX : 96 * 1024))
         return rc;
+    CDL_TRACE_NOTE("MTW=%d tpw=%d ngy=%d lds_over_96k=%d wgs=%zu", p.MTW, p.tpw, p.ngy, p.lds > 96 * 1024 ? 1 : 0,
+                   p.groups * p.ngy);
     k_ana_m<PH, PW, SW, MT, PROX, REV, MAP><<<dim3((unsigned)p.groups, (unsigned)p.ngy), ANT, p.lds, st>>>(
         *g, x, frags, alpha, zin, gate, tau, out, px, p.tilesX, p.tilesY, p.KS, zsup, dtp, p.tpw, mp, dtpw);
     CDL_LAUNCH_CHECK();
@@ -540,11 +542,13 @@ int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, flo
     else CDL_M(9, 5, 1); else CDL_M(9, 5, 2);
 #undef CDL_M
     if (rc) return rc;
-    if (cmap)
+    if (cmap) {
         k_ana_tau_final<true><<<dim3(g->M, 2), 512, 0, S(stream)>>>(dtp, nullptr, dt0, dt1, g->N, g->M, S_, dtpw);
-    else
+        CDL_LAUNCH_CHECK();
+    } else {
         k_ana_tau_final<false><<<g->M, 512, 0, S(stream)>>>(dtp, c, dt0, dt1, g->N, g->M, S_, nullptr);
-    CDL_LAUNCH_CHECK();
+        CDL_LAUNCH_CHECK();
+    }
     if (dtau_n)                                                    // per-sample: the S_ tile partials of row (n, m)
         return cdl_dtau_per_sample(dtp, g->N, g->M, S_, (size_t)g->M * S_, (size_t)S_, 1, dtau_n, stream);
     return 0;

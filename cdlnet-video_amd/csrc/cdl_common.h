@@ -1,10 +1,26 @@
 // Shared helpers for the gfx950 kernels of libcdlnet_hip.so.
 #pragma once
+#include <atomic>
 #include <hip/hip_runtime.h>
 #include "../../include/cdlnet_hip.h"
 
+// ---- launch trace (cdl_options.hip): host code only, off by default --------------------
+// Every launch site ends in CDL_LAUNCH_CHECK(), which -- while the trace is on -- appends one record: source file and
+// line, the enclosing launcher with the values of its template arguments (__PRETTY_FUNCTION__), and the note that
+// CDL_TRACE_NOTE left on this host thread since the previous launch (the plan's run-time variant values; the kernel's
+// name where one launcher holds several launches).  Off, a launch pays one relaxed atomic load.
+extern __attribute__((visibility("hidden"))) std::atomic<int> cdl_trace_state;   // (not part of the C ABI) 0: off; 1: log (cdl_trace); 2: CDL_TRACE_FILE; < 0: environment not read yet
+void cdl_trace_launch(const char *file, int line, const char *func);
+void cdl_trace_note(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+#define CDL_TRACE_NOTE(...)                                                               \
+    do {                                                                                  \
+        if (cdl_trace_state.load(std::memory_order_relaxed) != 0) cdl_trace_note(__VA_ARGS__); \
+    } while (0)
+
 #define CDL_LAUNCH_CHECK()                                   \
     do {                                                     \
+        if (cdl_trace_state.load(std::memory_order_relaxed) != 0)          \
+            cdl_trace_launch(__FILE__, __LINE__, __PRETTY_FUNCTION__);     \
         hipError_t e_ = hipGetLastError();                   \
         if (e_ != hipSuccess) return -(int)e_;               \
     } while (0)
@@ -131,6 +147,7 @@ struct cdl_options {
     int fusedg_strip;                                            // CDL_FUSEDG_STRIP=1: cdl_stripg.hip instead of the tile kernel k_stage_g
     int scalar_assemble;                                         // CDL_SCALAR_ASSEMBLE=1: the one-pixel-per-thread patch assemble (tests)
     int fused_debug, dense_debug;                                // -DCDL_ABLATE builds only (always 0 in the product)
+    const char *trace_file;                                      // CDL_TRACE_FILE=path: each distinct launch record appended once (nullptr: off)
 };
 const cdl_options &cdl_opts();                                   // snapshot of the environment, read once
 bool cdl_exact_fp32();                                           // this host thread asked for the fp32 VALU tier (cdl_set_exact_fp32)

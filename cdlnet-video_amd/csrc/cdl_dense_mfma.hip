@@ -825,6 +825,7 @@ int cdl_dense_wgrad(const cdl_geom *g, const float *F, const float *gate, const 
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_dense_wgrad<false>, (int)lds)) return rc;
     CDL_DBG_FIELD(const int dbg = cdl_opts().dense_debug;)
     const dim3 grid((unsigned)p.nwg, (unsigned)g->Pd, (unsigned)p.ogroups);
+    CDL_TRACE_NOTE("k_dense_wgrad<%s>", vec ? "true" : "false");
     if (vec)
         k_dense_wgrad<true><<<grid, WNT, lds, S(stream)>>>(F, gate, x, ws, g->N, g->M, g->C, g->D, g->H, g->W, g->Pd,
                                                            p.tilesX, p.tilesY, p.ntiles CDL_DBG_COMMA(dbg));

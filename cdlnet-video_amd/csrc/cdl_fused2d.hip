@@ -1530,15 +1530,15 @@ int launch_stage_one(const FusedParams &p, dim3 grid, hipStream_t st)
         if (p.r2) {                                          // the reverse stage that also accumulates dA_k
             if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true, WY>, G::LDS_STAGE + G::LDS_DA)) return rc;
             k_stage<MT, PREC, MODE, LIN, LOUT, true, WY><<<grid, G::NT, G::LDS_STAGE + G::LDS_DA, st>>>(p);
-            hipError_t e = hipGetLastError();
-            return e == hipSuccess ? 0 : -(int)e;
+            CDL_LAUNCH_CHECK();
+            return 0;
         }
     }
     if (p.r2) return CDL_EUNSUPPORTED;
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, false, WY>, G::LDS_STAGE)) return rc;
     k_stage<MT, PREC, MODE, LIN, LOUT, false, WY><<<grid, G::NT, G::LDS_STAGE, st>>>(p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 // The layout pairs the sweeps and the step-wise entry points use: same layout on both sides, or NCHW on one
@@ -1614,8 +1614,8 @@ int launch_wgrad_one(const WgradParams &p, int G, hipStream_t st)
     const size_t lds = (size_t)WG_THIN_BYTES + (size_t)8 * MT * 2 * IMG_ELEMS * 2;
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_wgrad2d<MT, PREC, LAY>, (int)lds)) return rc;
     k_wgrad2d<MT, PREC, LAY><<<G, 512, lds, st>>>(p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 template <int MT, int PREC>
@@ -1660,8 +1660,8 @@ int iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *t
 int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t st)
 {
     k_wgrad_reduce<<<wgrad_reduce_blocks(job, g->M, g->Ph), 1024, 0, st>>>(job, g->M, g->Ph);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 // r2 != nullptr: the launch also produces dA = alpha * du_out (x) im2col(r2) (cdl_fused2d_wgrad's first operator pair, same
@@ -1735,14 +1735,16 @@ int assemble(const cdl_geom *g, const float *patches, const float *mask, const f
     if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
         k_assemble_v4<WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+        CDL_LAUNCH_CHECK();
     } else if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20)) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)g->N);
         k_assemble<4, WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+        CDL_LAUNCH_CHECK();
     } else {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)g->N);
         k_assemble<1, WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
+        CDL_LAUNCH_CHECK();
     }
-    CDL_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1811,8 +1813,7 @@ int prep_pairs(const float *const *w1, const float *const *w2, int K, int shift2
         }
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         k_prep_batch<<<grid, 256, 0, st>>>(b, reinterpret_cast<uint4 *>(frags) + (size_t)k0 * frag_uint4, frag_uint4, MT, P);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
+        CDL_LAUNCH_CHECK();
     }
     return 0;
 }

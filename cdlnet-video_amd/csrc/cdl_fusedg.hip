@@ -913,8 +913,8 @@ int launch_one(const GParams &p, const Plan &pl, hipStream_t st)
     if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
     const unsigned grid = (unsigned)(pl.tiles < cus ? pl.tiles : cus);
     k_stage_g<P, G, MT, MODE, FOUR><<<grid, NT, lds, st>>>(p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 template <int P, int G, int MT>
@@ -976,11 +976,11 @@ int prep_pairs(const cdl_geom *g, const Plan &pl, const float *const *w1, const 
         }
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         uint4 *out = reinterpret_cast<uint4 *>(frags) + (size_t)k0 * pl.frag_uint4;
+        CDL_TRACE_NOTE("k_prep_g<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
         if (pl.P == 3) k_prep_g<3><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, g->C, g->Pd, pl.MT, pl.KS, pl.KQ);
         else if (pl.P == 5) k_prep_g<5><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, g->C, g->Pd, pl.MT, pl.KS, pl.KQ);
         else k_prep_g<7><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, g->C, g->Pd, pl.MT, pl.KS, pl.KQ);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
+        CDL_LAUNCH_CHECK();
     }
     return 0;
 }
@@ -1160,11 +1160,13 @@ int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *ma
     if ((g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)(g->N * g->C * g->D));
 #define CDL_ASM4(P_) k_assemble_g4<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
+        CDL_TRACE_NOTE("k_assemble_g4<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
         if (pl.P == 3) CDL_ASM4(3); else if (pl.P == 5) CDL_ASM4(5); else CDL_ASM4(7);
 #undef CDL_ASM4
     } else {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)(g->N * g->C * g->D));
 #define CDL_ASM(P_) k_assemble_g<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
+        CDL_TRACE_NOTE("k_assemble_g<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
         if (pl.P == 3) CDL_ASM(3); else if (pl.P == 5) CDL_ASM(5); else CDL_ASM(7);
 #undef CDL_ASM
     }

@@ -698,10 +698,11 @@ int cdl_preprocess(const float *y, const float *mask, float *yp, float *mask_p, 
         k_sample_sums_split<<<N * SUM_SPLIT, 1024, 0, S(stream)>>>(y, mask, part, per_n);
         CDL_LAUNCH_CHECK();
         k_sample_sums_final<<<(N + 63) / 64, 64, 0, S(stream)>>>(part, mean, N, per_n, mask ? 1 : 0);
+        CDL_LAUNCH_CHECK();
     } else {
         k_sample_sums<<<N, 1024, 0, S(stream)>>>(y, mask, mean, per_n);
+        CDL_LAUNCH_CHECK();
     }
-    CDL_LAUNCH_CHECK();
     k_pad_center<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(
         y, mask, mean, yp, mask_p, N, C, D, H, W, pads[0], pads[2], pads[4], Dp, Hp, Wp);
     CDL_LAUNCH_CHECK();
@@ -872,6 +873,7 @@ static int analysis_impl(const cdl_geom *g, const float *x, const float *w, floa
         if (rc_) return rc_;
     }
     dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N);
+    CDL_TRACE_NOTE("k_analysis<%s>", mp.cmap ? "true" : "false");
     if (mp.cmap)
         k_analysis<true><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
     else
@@ -1015,6 +1017,7 @@ static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const
     if (Sp > CDL_TAU_SPLITS) Sp = CDL_TAU_SPLITS;
     if (Sp < 1) Sp = 1;
     if (cmap) {                                                   // weighted partials behind the plain ones
+        CDL_TRACE_NOTE("k_tau_partial<%s,true>", gate_inplace ? "true" : "false");
         if (gate_inplace)
             k_tau_partial<true, true><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, cmap, g->M);
         else
@@ -1025,6 +1028,7 @@ static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const
         CDL_LAUNCH_CHECK();
         return 0;
     }
+    CDL_TRACE_NOTE("k_tau_partial<%s,false>", gate_inplace ? "true" : "false");
     if (gate_inplace)
         k_tau_partial<true, false><<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gup, zout, scratch, per_m, Sp, nullptr, g->M);
     else
@@ -1057,6 +1061,7 @@ int cdl_sigma_grad(const cdl_geom *g, const float *du, const float *z, const flo
     const size_t blocks = (per_m + 255) / 256;
     if (blocks >= ((size_t)1 << 31) || g->N > 65535) return CDL_EUNSUPPORTED;
     dim3 grid((unsigned)blocks, (unsigned)g->N);
+    CDL_TRACE_NOTE("k_sigma_grad<%s>", acc_add ? "true" : "false");
     if (acc_add)
         k_sigma_grad<true><<<grid, 256, 0, S(stream)>>>(du, z, tslope, dcmap, g->M, per_m);
     else

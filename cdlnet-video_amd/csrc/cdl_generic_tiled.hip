@@ -755,6 +755,7 @@ int launch_analysis(const cdl_geom *g, const float *x, const float *w, float alp
     int chunks;
     const int mper = channel_split(g->M, (long)tilesX * tilesY * Dz * g->N, &chunks);
     dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N, (unsigned)chunks);
+    CDL_TRACE_NOTE("chunks=%d", chunks);
     k_analysis_t<PW, SW, MAP><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, PH, PWp,
                                                              mper, px, mp);
     CDL_LAUNCH_CHECK();
@@ -778,6 +779,7 @@ int launch_synthesis_m(const cdl_geom *g, const float *z, const float *gate, con
         mper = g->M;
     }
     dim3 grid((unsigned)(tilesX * tilesY * g->D), (unsigned)g->N, (unsigned)chunks);
+    CDL_TRACE_NOTE("chunks=%d", chunks);
     k_synthesis_t<PW, SW, CC, MCHS><<<grid, 256, lds, S(stream)>>>(*g, z, gate, w, alpha, mask, sub, out, tilesX,
                                                           tilesY, PZH, PZW, mper, chunks > 1 ? ws : nullptr);
     CDL_LAUNCH_CHECK();
@@ -810,10 +812,12 @@ int launch_synthesis(const cdl_geom *g, const float *z, const float *gate, const
                 mper = g->M;
             }
             dim3 grid((unsigned)(tilesX * tilesY * g->D), (unsigned)g->N, (unsigned)chunks);
+            CDL_TRACE_NOTE("k_synthesis_q chunks=%d", chunks);
             k_synthesis_q<PW, SW, CC><<<grid, 256, lds, S(stream)>>>(*g, z, gate, w, alpha, mask, sub, out, tilesX,
                                                                   tilesY, PZH, PZW, mper, chunks > 1 ? ws : nullptr);
             CDL_LAUNCH_CHECK();
             if (chunks > 1) {
+                CDL_TRACE_NOTE("k_synth_fold after k_synthesis_q");
                 k_synth_fold<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(ws, mask, sub, alpha, out, chunks, total);
                 CDL_LAUNCH_CHECK();
             }
@@ -885,8 +889,10 @@ int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const 
             const int totall = g->M * CPd * tapsl;
 #define CDL_L(PH_, PW_, SW_)                                                                              \
             if (g->Ph == PH_ && g->Pw == PW_ && g->sw == SW_) {                                            \
+                CDL_TRACE_NOTE("k_wgrad_l<%d,%d,%d> tiles=%ld", PH_, PW_, SW_, tiles);                     \
                 k_wgrad_l<PH_, PW_, SW_><<<gridl, 256, ldsl, S(stream)>>>(*g, z, gate, x, workspace, tX, tY, XW); \
                 CDL_LAUNCH_CHECK();                                                                        \
+                CDL_TRACE_NOTE("k_wgrad_tfold");                                                           \
                 k_wgrad_tfold<<<(totall + 15) / 16, 256, 0, S(stream)>>>(workspace, dw, alpha, (int)tiles, CPd, g->M, tapsl); \
                 CDL_LAUNCH_CHECK();                                                                        \
                 return 0;                                                                                  \
@@ -911,8 +917,10 @@ int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const 
             dim3 grid2((unsigned)g->M, (unsigned)(g->C * g->Pd), (unsigned)chunks);
 #define CDL_P(PH_, PW_, SW_)                                                                              \
             if (g->Ph == PH_ && g->Pw == PW_ && g->sw == SW_) {                                            \
+                CDL_TRACE_NOTE("k_wgrad_p<%d,%d,%d> chunks=%d", PH_, PW_, SW_, chunks);                    \
                 k_wgrad_p<PH_, PW_, SW_><<<grid2, 256, 0, S(stream)>>>(*g, z, gate, x, workspace, rpc, lpr_shift); \
                 CDL_LAUNCH_CHECK();                                                                        \
+                CDL_TRACE_NOTE("k_wgrad_fold");                                                            \
                 k_wgrad_fold<<<(total + 255) / 256, 256, 0, S(stream)>>>(workspace, dw, alpha, chunks, total); \
                 CDL_LAUNCH_CHECK();                                                                        \
                 return 0;                                                                                  \
@@ -925,6 +933,7 @@ int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const 
     dim3 grid((unsigned)g->M, (unsigned)(g->C * g->Pd * g->Ph));
 #define CDL_W(PW_, SW_)                                                                     \
     if (g->Pw == PW_ && g->sw == SW_) {                                                     \
+        CDL_TRACE_NOTE("k_wgrad_t<%d,%d>", PW_, SW_);                                       \
         k_wgrad_t<PW_, SW_><<<grid, 256, 0, S(stream)>>>(*g, z, gate, x, alpha, dw);        \
         CDL_LAUNCH_CHECK();                                                                 \
         return 0;                                                                           \

@@ -209,6 +209,7 @@ int cdl_nle_mad_cells(const float *y, float *cells, float *scratch, size_t scrat
     if (blocks > 0x7fffffffu || count > 0x7fffffffu) return CDL_EINVAL;
     k_hh_abs<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(y, scratch, N * C, H, W, Ho, Wo);
     CDL_LAUNCH_CHECK();
+    CDL_TRACE_NOTE("k_select_cells<%s>", count <= (size_t)CELL_STAGE_MAX ? "true" : "false");
     if (count <= (size_t)CELL_STAGE_MAX)
         k_select_cells<true><<<(unsigned)blocks, CELL_THREADS, (2048 + count) * sizeof(unsigned), S(stream)>>>(
             scratch, cells, C, Ho, Wo, window, step, ny, nx, 0.6745f);

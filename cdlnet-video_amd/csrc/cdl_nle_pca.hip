@@ -339,6 +339,7 @@ int cdl_nle_pca_gram(const float *y, int N, int C, int H, int W, int channel, in
     double *shift = part + q.part_d;
     double *stage = shift + q.shift_d;
     long long *cnt = reinterpret_cast<long long *>(stage + q.stage_d);
+    CDL_TRACE_NOTE("k_pca_gram<%d>", q.NB == 2 ? 2 : 4);
     if (q.NB == 2)
         k_pca_gram<2><<<q.G, NTHREADS, 0, S(stream)>>>(y, s, tau, part, shift, cnt);
     else

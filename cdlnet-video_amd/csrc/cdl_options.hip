@@ -4,11 +4,19 @@
 //   * experiment / test switches, read from the environment ONCE (first use) into an immutable snapshot;
 //     cdl_options_reload() re-reads them (tests and tools flip a variable, then call it);
 //   * per-device facts: compute-unit count, and which kernels already had their dynamic-LDS limit raised
-//     and to how many bytes on which device (hipFuncSetAttribute is per device: a second GPU in the same process needs its own call).
+//     and to how many bytes on which device (hipFuncSetAttribute is per device: a second GPU in the same process needs its own call);
+//   * the launch trace (cdl_trace, cdl_trace_read, CDL_TRACE_FILE): which kernel of which tier every entry point ran.
 #include <atomic>
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <fcntl.h>
 #include <map>
 #include <mutex>
+#include <set>
+#include <string>
+#include <unistd.h>
 #include <utility>
 
 #include "cdl_common.h"
@@ -17,6 +25,21 @@ namespace {
 
 std::atomic<const cdl_options *> g_opts{nullptr};
 std::mutex g_opts_mutex;
+
+// launch trace: the log and the set of records already written to CDL_TRACE_FILE are process-wide (autograd runs the
+// backward on another thread); the pending note belongs to the host thread that is about to launch
+std::mutex g_trace_mutex;
+bool g_trace_log_on = false;
+std::string g_trace_log;
+std::set<std::string> g_trace_filed;       // records already in the file named g_trace_path
+std::string g_trace_path;
+constexpr size_t TRACE_LOG_MAX = (size_t)16 << 20;
+thread_local char t_trace_note[192];
+
+void trace_set_state(const cdl_options *o)      // with g_trace_mutex held
+{
+    cdl_trace_state.store((g_trace_log_on ? 1 : 0) | ((o && o->trace_file) ? 2 : 0), std::memory_order_relaxed);
+}
 
 int env_int(const char *name, int dflt)
 {
@@ -44,12 +67,23 @@ const cdl_options *load_options()
     o->scalar_assemble = env_int("CDL_SCALAR_ASSEMBLE", 0) ? 1 : 0;
     o->fusedg_strip = env_int("CDL_FUSEDG_STRIP", 0) ? 1 : 0;
     o->fusedg_bwd_prec = env_int("CDL_FUSEDG_PREC", -1);
+    const char *tf = getenv("CDL_TRACE_FILE");
+    o->trace_file = (tf && *tf) ? strdup(tf) : nullptr;
 #ifdef CDL_ABLATE
     o->fused_debug = env_int("CDL_FUSED_DEBUG", 0);
     o->dense_debug = env_int("CDL_DENSE_DEBUG", 0);
 #else
     o->fused_debug = o->dense_debug = 0;
 #endif
+    {
+        std::lock_guard<std::mutex> lk(g_trace_mutex);
+        const std::string path = o->trace_file ? o->trace_file : "";
+        if (path != g_trace_path) {                        // another file starts with every record missing
+            g_trace_filed.clear();
+            g_trace_path = path;
+        }
+        trace_set_state(o);
+    }
     return o;
 }
 
@@ -61,6 +95,8 @@ std::mutex g_attr_mutex;
 std::map<std::pair<int, const void *>, int> g_attr_bytes;     // largest limit set so far per (device, kernel)
 
 }  // namespace
+
+std::atomic<int> cdl_trace_state{-1};
 
 const cdl_options &cdl_opts()
 {
@@ -123,4 +159,61 @@ int cdl_ensure_dynamic_lds(const void *kernel, int bytes)
     if (e != hipSuccess) return -(int)e;
     g_attr_bytes[{dev, kernel}] = bytes;
     return 0;
+}
+
+// ---- launch trace ----------------------------------------------------------------------------------------------
+void cdl_trace_note(const char *fmt, ...)
+{
+    const size_t have = strlen(t_trace_note);
+    if (have + 2 >= sizeof(t_trace_note)) return;
+    size_t at = have;
+    if (have) t_trace_note[at++] = ' ';
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t_trace_note + at, sizeof(t_trace_note) - at, fmt, ap);
+    va_end(ap);
+}
+
+void cdl_trace_launch(const char *file, int line, const char *func)
+{
+    int state = cdl_trace_state.load(std::memory_order_relaxed);
+    const cdl_options &o = cdl_opts();                     // (first use: reads CDL_TRACE_FILE and settles the state)
+    if (state < 0) state = cdl_trace_state.load(std::memory_order_relaxed);
+    if (state > 0) {
+        const char *base = strrchr(file, '/');
+        std::string rec = std::string(base ? base + 1 : file) + ":" + std::to_string(line) + "\t" + func + "\t" + t_trace_note;
+        rec += "\n";
+        std::lock_guard<std::mutex> lk(g_trace_mutex);
+        if (g_trace_log_on && g_trace_log.size() + rec.size() <= TRACE_LOG_MAX) g_trace_log += rec;
+        if (o.trace_file && g_trace_filed.insert(rec).second) {
+            const int fd = open(o.trace_file, O_WRONLY | O_APPEND | O_CREAT | O_CLOEXEC, 0644);
+            if (fd >= 0) {
+                (void)!write(fd, rec.data(), rec.size());  // one O_APPEND write per record: whole lines from every process
+                close(fd);
+            }
+        }
+    }
+    t_trace_note[0] = 0;
+}
+
+extern "C" int cdl_trace(int on)
+{
+    const cdl_options &o = cdl_opts();
+    std::lock_guard<std::mutex> lk(g_trace_mutex);
+    const int prev = g_trace_log_on ? 1 : 0;
+    g_trace_log_on = on != 0;
+    if (on) g_trace_log.clear();
+    trace_set_state(&o);
+    return prev;
+}
+
+extern "C" size_t cdl_trace_read(char *buf, size_t cap)
+{
+    std::lock_guard<std::mutex> lk(g_trace_mutex);
+    if (buf && cap) {
+        const size_t n = g_trace_log.size() < cap - 1 ? g_trace_log.size() : cap - 1;
+        memcpy(buf, g_trace_log.data(), n);
+        buf[n] = 0;
+    }
+    return g_trace_log.size();
 }

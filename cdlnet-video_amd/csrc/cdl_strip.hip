@@ -612,8 +612,8 @@ int launch_one(const SParams &p, const cdl_strip_plan &pl, hipStream_t st)
     const size_t wgs = (pl.items + NWV - 1) / NWV;
     const unsigned grid = (unsigned)(wgs < cus ? wgs : cus);
     k_strip<P, S, MTP, MODE, MAPPED><<<grid, NTS, lds, st>>>(p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 template <int P, int S, int MTP>
@@ -704,11 +704,11 @@ int cdl_strip_prep_pairs(const cdl_geom *g, const cdl_strip_plan &pl, const floa
         }
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         uint4 *out = reinterpret_cast<uint4 *>(frags) + (size_t)k0 * pl.frag_uint4;
+        CDL_TRACE_NOTE("k_prep_s<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
         if (pl.P == 3) k_prep_s<3><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, pl.MT, pl.KQ);
         else if (pl.P == 5) k_prep_s<5><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, pl.MT, pl.KQ);
         else k_prep_s<7><<<grid, 256, 0, st>>>(b, out, (int)pl.frag_uint4, g->M, pl.MT, pl.KQ);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
+        CDL_LAUNCH_CHECK();
     }
     return 0;
 }
@@ -747,6 +747,7 @@ int cdl_strip_assemble(const cdl_geom *g, const cdl_strip_plan &pl, const float 
         if (v4) k_assemble_s<P_, S_, 4><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add); \
         else k_assemble_s<P_, S_, 1><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add);    \
     } while (0)
+    CDL_TRACE_NOTE("k_assemble_s<%d,%d,%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7, pl.S == 2 ? 2 : 1, v4 ? 4 : 1);
     if (pl.S == 2) { if (pl.P == 3) CDL_ASM_S(3, 2); else if (pl.P == 5) CDL_ASM_S(5, 2); else CDL_ASM_S(7, 2); }
     else { if (pl.P == 3) CDL_ASM_S(3, 1); else if (pl.P == 5) CDL_ASM_S(5, 1); else CDL_ASM_S(7, 1); }
 #undef CDL_ASM_S

@@ -512,8 +512,8 @@ int launch_one(const GSParams &p, const cdl_stripg_plan &pl, hipStream_t st)
     const size_t wgs = (pl.items + NWV - 1) / NWV;
     const unsigned grid = (unsigned)(wgs < cus ? wgs : cus);
     k_stripg<P, G, MT, MODE, MAPPED><<<grid, NTS, lds, st>>>(p);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 template <int P, int G, int MT>
@@ -605,6 +605,7 @@ int cdl_stripg_assemble(const cdl_geom *g, const cdl_stripg_plan &pl, const floa
 {
     dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)(g->N * g->C * g->D));
 #define CDL_ASM_G(P_) k_assemble_sg<P_><<<grid, 256, 0, st>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.nsx, pl.nsy, pl.SEG, pl.prows, acc, acc_add)
+    CDL_TRACE_NOTE("k_assemble_sg<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
     if (pl.P == 3) CDL_ASM_G(3); else if (pl.P == 5) CDL_ASM_G(5); else CDL_ASM_G(7);
 #undef CDL_ASM_G
     CDL_LAUNCH_CHECK();

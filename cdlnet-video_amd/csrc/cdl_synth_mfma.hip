@@ -426,11 +426,14 @@ int launch(const cdl_geom *g, const Plan &p, const float *z, const float *gate, 
     while (gy < G && (size_t)grid_m * (gy + 1) <= cus) ++gy;
     const int gspan = (G + gy - 1) / gy;
     const dim3 grid_s(grid_m, (unsigned)((G + gspan - 1) / gspan));
-    if (p.KS <= 4 && G > 1)                  // several groups share the code values: keep their fragments in registers
+    CDL_TRACE_NOTE("streamed=%d gy=%u", p.KCH != p.KS ? 1 : 0, grid_s.y);
+    if (p.KS <= 4 && G > 1) {                // several groups share the code values: keep their fragments in registers
         k_synth_m<PH, PW, SW, 4><<<grid_s, SNT, p.lds, st>>>(*g, z, gate, frags, patches, p.tilesX, p.tilesY, p.KS, p.KCH, (int)p.tiles, gspan);
-    else
+        CDL_LAUNCH_CHECK();
+    } else {
         k_synth_m<PH, PW, SW, 0><<<grid_s, SNT, p.lds, st>>>(*g, z, gate, frags, patches, p.tilesX, p.tilesY, p.KS, p.KCH, (int)p.tiles, gspan);
-    CDL_LAUNCH_CHECK();
+        CDL_LAUNCH_CHECK();
+    }
     const size_t al = reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(mask) | reinterpret_cast<size_t>(sub);
     if ((g->W & 3) == 0 && (al & 15) == 0 && !cdl_opts().scalar_assemble) {     // (CDL_SCALAR_ASSEMBLE=1: the scalar form, for tests)
         dim3 grid4((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)(g->N * g->C * g->D));

@@ -599,6 +599,85 @@ class exact_fp32:
         if self.on:
             _lib.lib().cdl_set_exact_fp32(self.prev)
         return False
+
+
+# ------------------------------------------------------------------------------------------ launch trace
+@dataclass(frozen=True)
+class LaunchRecord:
+    """One kernel launch as the library's trace recorded it (cdl_trace, include/cdlnet_hip.h)."""
+    file: str          # source file of the launch site, e.g. "cdl_analysis_mfma.hip"
+    line: int          # line of the site's CDL_LAUNCH_CHECK
+    func: str          # the launcher with the values of its template arguments
+    note: str          # run-time variant values of the plan ("MTW=2 tpw=4 ..."), the kernel's name where it is needed
+
+    def template(self):
+        """The launcher's template arguments as the compiler printed them: {"PH": 7, "REV": True, ...}."""
+        out = {}
+        if self.func.endswith("]") and "[" in self.func:
+            for tok in self.func[self.func.rindex("[") + 1:-1].split(","):
+                if "=" in tok:
+                    k, v = (t.strip() for t in tok.split("=", 1))
+                    out[k] = {"true": True, "false": False}.get(v, int(v) if v.lstrip("-").isdigit() else v)
+        return out
+
+    def values(self):
+        """The note's `name=value` pairs, integers where they parse."""
+        out = {}
+        for tok in self.note.split():
+            if "=" in tok:
+                k, v = tok.split("=", 1)
+                out[k] = int(v) if v.lstrip("-").isdigit() else v
+        return out
+
+
+def parse_trace(text):
+    """Records of a trace log (cdl_trace_read or a CDL_TRACE_FILE), in order."""
+    out = []
+    for ln in text.splitlines():
+        parts = ln.split("\t")
+        if len(parts) != 3 or ":" not in parts[0]:
+            continue
+        f, _, n = parts[0].rpartition(":")
+        out.append(LaunchRecord(f, int(n), parts[1], parts[2]))
+    return out
+
+
+class Trace(list):
+    """The records of a `with trace() as t:` block (filled when the block ends, or by `t.read()` inside it)."""
+
+    def read(self):
+        lib = _lib.lib()
+        n = lib.cdl_trace_read(None, 0)
+        buf = ctypes.create_string_buffer(n + 1)
+        lib.cdl_trace_read(buf, n + 1)
+        self[:] = parse_trace(buf.value.decode())
+        return self
+
+    def files(self):
+        return {r.file for r in self}
+
+    def find(self, file=None, func=None, note=None):
+        """Records from `file` whose launcher contains `func` and whose note contains `note`."""
+        return [r for r in self if (file is None or r.file == file) and (func is None or func in r.func)
+                and (note is None or note in r.note)]
+
+
+class trace:
+    """`with trace() as t: ...` -- the kernel launches the library made inside the block, from every thread (the log is
+    process-wide: autograd runs the backward on another thread).  Synchronise before leaving the block if launches
+    of other threads are expected."""
+
+    def __enter__(self):
+        self.prev = _lib.lib().cdl_trace(1)
+        self.t = Trace()
+        return self.t
+
+    def __exit__(self, *exc):
+        self.t.read()
+        _lib.lib().cdl_trace(self.prev)
+        return False
+
+
 # layouts of the fat tensors that stay inside a fused sweep (include/cdlnet_hip.h, CDL_LAY_*): "nchw" is the
 # reference's layout, "blocked" the pixel-blocked fp32 layout (same values, 16-byte accesses, the default),
 # "blocked_bf16" opt-in bf16 STORAGE of the codes (half the bytes; outside the 1e-5 parity gate)

@@ -63,6 +63,17 @@ int cdl_options_reload(void);
  * end to end composes the generic ones (the Python host side does: loop.precision_scope("fp32")). */
 int cdl_set_exact_fp32(int on);
 
+/* Launch trace (host code, off by default): which kernel of which tier an entry point ran.
+ * While on, every kernel launch of the library appends one record to a process-wide log:
+ *     <source file>:<line> \t <launcher with the values of its template arguments> \t <note> \n
+ * the note holding the run-time variant values of the launcher's plan (and the kernel's name where one launcher
+ * has several launches).  cdl_trace(on) returns the previous state and clears the log when switched on.
+ * cdl_trace_read copies the log, NUL-terminated and cut to cap, into buf (nullable) and returns its full length in
+ * bytes.  CDL_TRACE_FILE=path (read with the other switches) appends each distinct record once to that file as well,
+ * from every process that has it set.  Off, a launch pays one relaxed atomic load. */
+int cdl_trace(int on);
+size_t cdl_trace_read(char *buf, size_t cap);
+
 /* ---- boundary of the loop: model/utils.py:5-22 (pre_process), :70-87 (pre_process_3d) -------
  * mean[n] = sum(y[n]) / (mask ? sum(mask[n]) : numel);  yp = reflect_pad(mask * (y - mean));
  * mask_p = reflect_pad(mask).  pads = {d_lo, d_hi, h_lo, h_hi, w_lo, w_hi} (floor/ceil split,

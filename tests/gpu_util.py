@@ -14,6 +14,29 @@ def log(line):
         f.write(line + "\n")
 
 
+_SITES = None
+
+
+def launch_sites(trace):
+    """{launch-site id: [records]} of a cva.ops.trace(): the records mapped onto the `kernel<<<...>>>` sites of the
+    sources by tools/launch_coverage.py (ids like "cdl_synth_mfma.hip:k_synth_m<PH,PW,SW,4>").  A record that fits no
+    site, or several, is an error of the trace notes."""
+    global _SITES
+    if _SITES is None:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("launch_coverage", os.path.join(ROOT, "tools", "launch_coverage.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _SITES = (mod, mod.index(mod.scan_sources()))
+    mod, by_check = _SITES
+    out = {}
+    for r in trace:
+        sid = mod.site_of(by_check, (r.file, r.line, r.func, r.note))
+        assert sid is not None, f"trace record that names no single launch site: {r}"
+        out.setdefault(sid, []).append(r)
+    return out
+
+
 def check(name, got, ref, tol):
     """Assert max|got-ref|/max|ref| < tol and record the measured value."""
     err = rel_err(got.detach().float().cpu(), ref.detach().float().cpu())

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import check, log
+from gpu_util import check, launch_sites, log
 from oracle import cdl_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -91,9 +91,15 @@ def test_fused_iteration_vs_generic(N, M, P, H, W, masked, precision, tol):
         bits = torch.full((N, 4, H, W), -1, dtype=torch.int32, device="cuda")     # every word must be written
         z_got = o.fused_iter(geom, r, zin, tau, frags, sgn, patches, precision, map_out=bits)
         assert torch.equal(bits, o.fused_support_map(geom, z_got)), f"{tag} {name}: support/sign map"
-        z_nomap = o.fused_iter(geom, r, zin, tau, frags, sgn, patches, precision)
+        with o.trace() as t:
+            z_nomap = o.fused_iter(geom, r, zin, tau, frags, sgn, patches, precision)
+            r_got = o.fused_assemble(geom, patches, mask, yp)
         assert torch.equal(z_nomap, z_got)
-        r_got = o.fused_assemble(geom, patches, mask, yp)
+        # the 2-D fused stage and its assemble ran, in the arithmetic asked for
+        sites = launch_sites(t)
+        assert {k.split(":")[0] for k in sites} == {"cdl_fused2d.hip"} and len(sites) == 2, t
+        stage = sites["cdl_fused2d.hip:k_stage<MT,PREC,MODE,LIN,LOUT,false,WY>"][0].template()
+        assert stage["MT"] == M // 32 and stage["PREC"] == o.PRECISION[precision], stage
         check(f"{tag} {name} z'", z_got, z_ref, tol)
         # the synthesis check feeds the fused kernel's own z' to the generic kernel: isolates the second GEMM
         check(f"{tag} {name} r_next", r_got, o.synthesis(geom, z_got, wB, 1.0, None, mask, yp), tol)

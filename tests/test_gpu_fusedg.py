@@ -2,7 +2,7 @@
 import pytest
 import torch
 
-from gpu_util import check, log
+from gpu_util import check, launch_sites, log
 
 pytestmark = pytest.mark.gpu
 
@@ -62,8 +62,15 @@ def test_fusedg_iteration_vs_generic(N, C, M, sp, P, masked, kernel):
         check(f"{tag} {name} r_next", r_got, o.synthesis(g, z_got, wB, 1.0, None, mask, yp), 2e-5)
         check(f"{tag} {name} r_next(end-to-end)", r_got, r_ref, 8e-5)
         assert float(((z_got != 0) == (z_ref != 0)).float().mean()) > 0.9999
-        z2 = o.fusedg_iter(g, r, zin, tau, frags, sgn, patches)          # deterministic, with or without the map
+        with o.trace() as t:
+            z2 = o.fusedg_iter(g, r, zin, tau, frags, sgn, patches)      # deterministic, with or without the map
+            o.fusedg_assemble(g, patches, mask, yp)
         assert torch.equal(z2, z_got)
+        # the kernel the fixture asked for, from the launch trace
+        v4 = sp[-1] % 4 == 0
+        want = ({"cdl_fusedg.hip:k_stage_g<P,G,MT,MODE,FOUR>", "cdl_fusedg.hip:k_assemble_g4<P_>" if v4 else "cdl_fusedg.hip:k_assemble_g<P_>"}
+                if kernel == "tile" else {"cdl_stripg.hip:k_stripg<P,G,MT,MODE,MAPPED>", "cdl_stripg.hip:k_assemble_sg<P_>"})
+        assert set(launch_sites(t)) == want, t
 
 
 @pytest.mark.parametrize("N,C,M,sp,P,masked", SHAPES[:4])

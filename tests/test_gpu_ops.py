@@ -2,7 +2,7 @@
 import pytest
 import torch
 
-from gpu_util import check
+from gpu_util import check, launch_sites
 from oracle import cdl_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +49,61 @@ SHAPES = [
 ]
 
 
+# What the comments above promise, asserted from the launch trace at 256 compute units:
+# (operator, index into SHAPES, path) -> [(launch site, template arguments and plan values of one of its records)]
+_TIL, _DEN = "cdl_generic_tiled.hip:", "cdl_dense_mfma.hip:"
+_ANA = "cdl_analysis_mfma.hip:k_ana_m<PH,PW,SW,MT,PROX,REV,MAP>"
+_WGM = "cdl_wgrad_mfma.hip:k_wgm<PH,PW,SW,NG,CT>"
+_SYN0, _SYN4 = "cdl_synth_mfma.hip:k_synth_m<PH,PW,SW,0>", "cdl_synth_mfma.hip:k_synth_m<PH,PW,SW,4>"
+_WL = _TIL + "k_wgrad_l<PH_,PW_,SW_>"
+PINNED = {}
+for _i in (9, 10, 11, 12):                                   # k_wgrad_l on the fp32 path; the matrix cores otherwise
+    PINNED[("wgrad", _i, "valu")] = [(_WL, {})]
+    PINNED[("wgrad", _i, "mfma")] = [(_WGM, {})]
+PINNED[("synthesis", 13, "mfma")] = [(_SYN0, dict(PH=9, SW=2, streamed=1))]
+PINNED[("synthesis", 13, "valu")] = [(_TIL + "k_synthesis_t<PW,SW,CC,MCHS>", dict(PW=9, SW=2))]
+PINNED[("analysis", 13, "mfma")] = [(_ANA, dict(PH=9, SW=2, ngy=3))]
+PINNED[("analysis", 13, "valu")] = [(_TIL + "k_analysis_t<PW,SW,MAP>", dict(PW=9, SW=2))]
+PINNED[("wgrad", 14, "mfma")] = [(_WGM, dict(CT=2, tiles=80))]
+PINNED[("wgrad", 14, "valu")] = [(_TIL + "k_wgrad_p<PH_,PW_,SW_>", {})]
+for _i in (15, 16, 17):                                      # the dense tier, and the sparse ladder with CDL_MFMA_DENSE=0
+    PINNED[("analysis", _i, "mfma")] = PINNED[("synthesis", _i, "mfma")] = [(_DEN + "k_dense<MT>", {})]
+    PINNED[("analysis", _i, "valu")] = PINNED[("synthesis", _i, "valu")] = PINNED[("wgrad", _i, "valu")] = [("!" + _DEN, {})]
+PINNED[("wgrad", 15, "mfma")] = PINNED[("wgrad", 16, "mfma")] = [(_DEN + "k_dense_wfold", {})]
+for _i, _tiles in ((18, 24), (19, 16)):                      # the deep 9 x 9 x 5 filter (> 96 KB of LDS at stride 2)
+    PINNED[("analysis", _i, "mfma")] = [(_ANA, dict(PH=9, PW=5, MTW=1, **({"lds_over_96k": 1} if _i == 18 else {})))]
+    PINNED[("synthesis", _i, "mfma")] = [(_SYN4, dict(PH=9, PW=5))]
+    PINNED[("wgrad", _i, "mfma")] = [(_WGM, dict(PH=9, PW=5, tiles=_tiles)), (_WGM, dict(pair=1, tiles=_tiles))]
+    PINNED[("analysis", _i, "valu")] = [("!cdl_analysis_mfma.hip:", {})]
+    PINNED[("synthesis", _i, "valu")] = [("!cdl_synth_mfma.hip:", {})]
+    PINNED[("wgrad", _i, "valu")] = [("!cdl_wgrad_mfma.hip:", {})]
+
+
+@pytest.fixture
+def launches():
+    with ops().trace() as t:
+        yield t
+
+
+def assert_pinned(trace, op, shape, path):
+    """The kernels SHAPES' comments name for this shape ran (a "!" entry: no launch site with that prefix did)."""
+    want = PINNED.get((op, SHAPES.index(shape), path))
+    if not want:
+        return
+    sites = launch_sites(trace.read())
+    bad = []
+    for site, vals in want:
+        if site.startswith("!"):
+            if any(k.startswith(site[1:]) for k in sites):
+                bad.append(f"{site[1:]}* ran: {sorted(sites)}")
+        elif not any(all({**r.values(), **r.template()}.get(k) == v for k, v in vals.items()) for r in sites.get(site, [])):
+            bad.append(f"{site} {vals}: got {[(r.template(), r.note) for r in sites.get(site, [])] or sorted(sites)}")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if bad and cus != 256:
+        pytest.skip(f"the launch plans were pinned at 256 compute units, this device has {cus}: {bad}")
+    assert not bad, bad
+
+
 def make(N, C, M, sp, P, s, seed=0):
     g = torch.Generator().manual_seed(seed)
     x = torch.randn((N, C) + sp, generator=g)
@@ -61,7 +116,7 @@ def make(N, C, M, sp, P, s, seed=0):
 
 @pytest.mark.parametrize("path,tol", [("mfma", 2e-5), ("valu", 2e-6)])
 @pytest.mark.parametrize("N,C,M,sp,P,s", SHAPES)
-def test_analysis_variants(N, C, M, sp, P, s, path, tol, hip_env):
+def test_analysis_variants(N, C, M, sp, P, s, path, tol, hip_env, launches):
     """Both analysis paths: the matrix-core kernel (default where it exists: >= 96 workgroups of 4 tiles; smaller
     launches fall through) and the fp32 VALU kernels (CDL_MFMA_ANALYSIS=0)."""
     hip_env("CDL_MFMA_ANALYSIS", "1" if path == "mfma" else "0")
@@ -85,11 +140,12 @@ def test_analysis_variants(N, C, M, sp, P, s, path, tol, hip_env):
     gup = torch.randn(z.shape)
     check(tag + " bwd", o.analysis(geom, xd, wd, 1.0, gup.cuda(), zd, None),
           gup * (z != 0) + ref_conv, tol)
+    assert_pinned(launches, "analysis", (N, C, M, sp, P, s), path)
 
 
 @pytest.mark.parametrize("path,tol", [("mfma", 2e-5), ("valu", 2e-6)])
 @pytest.mark.parametrize("N,C,M,sp,P,s", SHAPES)
-def test_synthesis_variants(N, C, M, sp, P, s, path, tol, hip_env):
+def test_synthesis_variants(N, C, M, sp, P, s, path, tol, hip_env, launches):
     """Both synthesis paths: the matrix-core kernels (split-bf16 x3; default wherever they exist, the other
     shapes fall through to the VALU kernels) and the fp32 VALU kernels (CDL_MFMA_SYNTHESIS=0; the library snapshots its switches, hip_env reloads them)."""
     hip_env("CDL_MFMA_SYNTHESIS", "1" if path == "mfma" else "0")
@@ -110,11 +166,12 @@ def test_synthesis_variants(N, C, M, sp, P, s, path, tol, hip_env):
     check(tag + " bwd", o.synthesis(geom, gup.cuda(), wd, -1.0, zd, mask.cuda(), None), ref_b, tol)
     # deterministic: patches are gathered and added in a fixed order
     assert torch.equal(o.synthesis(geom, zd, wd), o.synthesis(geom, zd, wd))
+    assert_pinned(launches, "synthesis", (N, C, M, sp, P, s), path)
 
 
 @pytest.mark.parametrize("path", ["mfma", "valu"])
 @pytest.mark.parametrize("N,C,M,sp,P,s", SHAPES)
-def test_filter_and_threshold_grads(N, C, M, sp, P, s, path, hip_env):
+def test_filter_and_threshold_grads(N, C, M, sp, P, s, path, hip_env, launches):
     """Filter gradients through the matrix-core kernel (default where it exists: >= 64 tiles of 64 x 32 code
     pixels; smaller launches fall through) and through the fp32 VALU kernels (CDL_MFMA_WGRAD=0)."""
     hip_env("CDL_MFMA_WGRAD", "1" if path == "mfma" else "0")
@@ -145,6 +202,7 @@ def test_filter_and_threshold_grads(N, C, M, sp, P, s, path, hip_env):
     s_nm = -(torch.sign(z) * u).sum(dim=tuple(range(2, z.dim())))
     check(tag + " dt0", dt[0], s_nm.sum(0), 1e-5)
     check(tag + " dt1", dt[1], (c[:, None] * s_nm).sum(0), 1e-5)
+    assert_pinned(launches, "wgrad", (N, C, M, sp, P, s), path)
 
 
 @pytest.mark.parametrize("shape,s,masked", [((2, 1, 33, 31), 2, False), ((3, 3, 21, 19), 2, True),

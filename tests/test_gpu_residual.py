@@ -5,7 +5,7 @@ import pytest
 import torch
 
 import cdlnet_video_amd as cva
-from gpu_util import check, load_golden
+from gpu_util import check, launch_sites, load_golden
 from oracle import cdl_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -80,7 +80,12 @@ def test_block_vs_oracle_dense_shapes(N, M, shape):
     wgt = torch.randn((N, M) + shape, generator=gen)
     geom = o.residual_geometry(x, w1)
     xd, w1d, w2d = x.cuda(), w1.cuda(), w2.cuda()
-    h, out = o.residual_forward(geom, xd, w1d, w2d)
+    with o.trace() as t_fwd:
+        h, out = o.residual_forward(geom, xd, w1d, w2d)
+    # all four shapes are inside the dense matrix-core tier's eligibility (>= 16 channels on both sides, 3 x 3 x 3, unit
+    # stride): two fragment preps and two convolutions with the ReLU in the epilogue, no element-wise pass
+    assert sorted(launch_sites(t_fwd)) == ["cdl_dense_mfma.hip:k_dense<MT>", "cdl_dense_mfma.hip:k_dense_prep"], t_fwd
+    assert [r.template().get("MT") for r in launch_sites(t_fwd)["cdl_dense_mfma.hip:k_dense<MT>"]] == [1 if M <= 32 else 2] * 2
     ref_h = torch.relu(F.conv3d(x, w1, padding=1))
     ref = orc.residual_block(x, w1, w2)
     tag = f"block M={M} {shape}"
@@ -92,7 +97,15 @@ def test_block_vs_oracle_dense_shapes(N, M, shape):
     xo, w1o, w2o = (t.clone().requires_grad_(True) for t in (x, w1, w2))
     lin = (F.conv3d(F.conv3d(xo, w1o, padding=1) * G1, w2o, padding=1) + xo) * G2
     (lin * wgt).sum().backward()
-    dx, dw1, dw2 = o.residual_backward(geom, xd, h, out, w1d, w2d, wgt.cuda())
+    with o.trace() as t_bwd:
+        dx, dw1, dw2 = o.residual_backward(geom, xd, h, out, w1d, w2d, wgt.cuda())
+    # ... and so is the backward (>= 8 tiles of 4 x 32 pixels for the dense filter gradient): one gate pass, the two
+    # data gradients and the two filter gradients on the dense tier, nothing from the sparse-dictionary ladder
+    sites_b = launch_sites(t_bwd)
+    vec = "true" if shape[-1] % 4 == 0 else "false"
+    assert sorted(sites_b) == sorted(["cdl_residual.hip:k_gate", "cdl_dense_mfma.hip:k_dense_prep", "cdl_dense_mfma.hip:k_dense<MT>",
+                                      f"cdl_dense_mfma.hip:k_dense_wgrad<{vec}>", "cdl_dense_mfma.hip:k_dense_wfold"]), sorted(sites_b)
+    assert len(sites_b["cdl_dense_mfma.hip:k_dense_wfold"]) == 2 and len(sites_b["cdl_dense_mfma.hip:k_dense<MT>"]) == 2
     check(tag + " grad_x", dx, xo.grad, 2e-5)
     check(tag + " grad_w1", dw1, w1o.grad, 2e-5)
     check(tag + " grad_w2", dw2, w2o.grad, 2e-5)

@@ -5,7 +5,7 @@ whole sweeps.  (Net-level parity against the CPU oracle: tests/test_gpu_nets.py 
 import pytest
 import torch
 
-from gpu_util import check, log
+from gpu_util import check, launch_sites, log
 
 pytestmark = pytest.mark.gpu
 
@@ -56,9 +56,15 @@ def test_strip_iteration_vs_generic(N, M, P, s, sp, masked):
         check(f"{tag} {name} r_next", r_got, o.synthesis(g, z_got, wB, 1.0, None, mask, yp), 2e-5)
         check(f"{tag} {name} r_next(end-to-end)", r_got, r_ref, 8e-5)
         assert float(((z_got != 0) == (z_ref != 0)).float().mean()) > 0.9999
-        z2 = o.fusedg_iter(g, r, zin, tau, frags, sgn, patches)          # deterministic, with or without the map
+        with o.trace() as t:
+            z2 = o.fusedg_iter(g, r, zin, tau, frags, sgn, patches)      # deterministic, with or without the map
+            r2 = o.fusedg_assemble(g, patches, mask, yp)
         assert torch.equal(z2, z_got)
-        assert torch.equal(o.fusedg_assemble(g, patches, mask, yp), r_got)
+        assert torch.equal(r2, r_got)
+        # the strip kernel and its assemble ran, not the tile kernel the same entry points also front
+        assert sorted(launch_sites(t)) == [f"cdl_strip.hip:k_assemble_s<P_,S_,{4 if sp[1] % 4 == 0 else 1}>",
+                                           "cdl_strip.hip:k_strip<P,S,MTP,MODE,MAPPED>"], t
+        assert launch_sites(t)["cdl_strip.hip:k_strip<P,S,MTP,MODE,MAPPED>"][0].template()["P"] == P
 
 
 def test_strip_negative_and_nan_thresholds():

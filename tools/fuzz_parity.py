@@ -4,6 +4,10 @@ launch, the fused generic stage where it applies) against the fp32 VALU tier of 
 `-m gpu` suite pins to the oracle.  Catches indexing slips at ragged / odd sizes the fixed test shapes do not reach.
 
     python tools/fuzz_parity.py [cases] [seed]
+
+run_counted() also returns, per operator, how many cases launched the matrix-core kernel (from the launch trace): a moved
+plan threshold that sends the cases down the fp32 tier would leave a comparison of that tier with itself.  run() keeps
+its two results.
 """
 import json
 import os
@@ -27,10 +31,20 @@ def rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-20))
 
 
+MATRIX_CORE = {"analysis": "cdl_analysis_mfma.hip", "synthesis": "cdl_synth_mfma.hip", "wgrad": "cdl_wgrad_mfma.hip"}
+
+
 def run(cases=40, seed=0, verbose=True):
+    """-> (worst relative error per result, failures)"""
+    return run_counted(cases, seed, verbose)[:2]
+
+
+def run_counted(cases=40, seed=0, verbose=True):
+    """-> (worst relative error per result, failures, {operator: cases that launched its matrix-core kernel})"""
     rng = random.Random(seed)
     worst = {}
     fails = []
+    reached = {k: 0 for k in MATRIX_CORE}
     for case in range(cases):
         three = rng.random() < 0.35
         s = rng.choice([1, 1, 2])
@@ -63,14 +77,21 @@ def run(cases=40, seed=0, verbose=True):
         for mode in ("0", "1"):
             setenv(mode)
             r = {}
-            r["ana"] = o.analysis(g, x, w, -1.0, z, None, None)            # no threshold: ST would amplify sign flips at 0
-            r["ana_first"] = o.analysis(g, x, w, 1.0)
-            r["ana_gate"] = o.analysis(g, x, w, 1.0, u, z, None)
-            r["syn"] = o.synthesis(g, z, w, -1.0, None, mask, x)
-            r["syn_gate"] = o.synthesis(g, u, w, 1.0, z)
-            r["wg"] = o.wgrad(g, z, x, 1.0)
-            r["wg_gate"] = o.wgrad(g, u, x, -1.0, gate=z)
-            r["pair0"], r["pair1"] = o.wgrad_pair(g, u * (z != 0), x, -1.0, z, x, 1.0)
+            with o.trace() as t_ana:
+                r["ana"] = o.analysis(g, x, w, -1.0, z, None, None)            # no threshold: ST would amplify sign flips at 0
+                r["ana_first"] = o.analysis(g, x, w, 1.0)
+                r["ana_gate"] = o.analysis(g, x, w, 1.0, u, z, None)
+            with o.trace() as t_syn:
+                r["syn"] = o.synthesis(g, z, w, -1.0, None, mask, x)
+                r["syn_gate"] = o.synthesis(g, u, w, 1.0, z)
+            with o.trace() as t_wg:
+                r["wg"] = o.wgrad(g, z, x, 1.0)
+                r["wg_gate"] = o.wgrad(g, u, x, -1.0, gate=z)
+                r["pair0"], r["pair1"] = o.wgrad_pair(g, u * (z != 0), x, -1.0, z, x, 1.0)
+            for op, t in (("analysis", t_ana), ("synthesis", t_syn), ("wgrad", t_wg)):
+                ran = MATRIX_CORE[op] in t.files()
+                assert mode == "1" or not ran, (op, "CDL_MFMA_*=0 still launched", MATRIX_CORE[op])
+                reached[op] += int(ran)
             dt = torch.zeros(2, M, device="cuda")
             r["rev"] = o.analysis_rev(g, x, w, 0.7, u, z, tau[:, 0].contiguous(), dt)
             r["rev_dt"] = dt
@@ -104,12 +125,13 @@ def run(cases=40, seed=0, verbose=True):
                     fails.append((tag, "fusedg_r", e2))
         if verbose:
             print(json.dumps({"case": case, "geometry": tag, "fusedg": bool(o.fusedg_supported(g))}), flush=True)
-    return worst, fails
+    return worst, fails, reached
 
 
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     sd = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    worst, fails = run(n, sd)
-    print(json.dumps({"cases": n, "worst_rel_err": {k: float(f"{v:.3e}") for k, v in worst.items()}, "failures": fails}))
+    worst, fails, reached = run_counted(n, sd)
+    print(json.dumps({"cases": n, "worst_rel_err": {k: float(f"{v:.3e}") for k, v in worst.items()}, "failures": fails,
+                      "matrix_core_cases": reached}))
     sys.exit(1 if fails else 0)
