@@ -56,6 +56,8 @@ SIGNATURES = {
     "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P, _P, _P],                  # .., cmap, tslope, stream
     "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
+    "cdl_tangent_forward": [_G, _I] + [_P] * 10 + [ctypes.c_size_t, _P],
+    "cdl_tangent_backward": [_G, _I] + [_P] * 15 + [ctypes.c_size_t, _P],
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_mad_cells": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _I, _P],
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
@@ -88,6 +90,8 @@ SIGNATURES = {
     "cdl_fused2d_wgrad": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, _I, _P],
     "cdl_fused2d_forward": [_G, _I] + [_P] * 11 + [_I, _P],
     "cdl_fused2d_backward": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P],
+    "cdl_fused2d_tangent": [_G, _I] + [_P] * 12 + [_I, _P],
+    "cdl_fusedg_tangent": [_G, _I] + [_P] * 12 + [_I, _P],
     "cdl_fusedg_supported": [_G],
     "cdl_fusedg_code_layout": [_G, _I],
     "cdl_fusedg_set_timeline": [_P],

@@ -1526,7 +1526,8 @@ template <int WY, int MT, int PREC, int MODE, int LIN, int LOUT>
 int launch_stage_one(const FusedParams &p, dim3 grid, hipStream_t st)
 {
     using G = Shape<WY>;
-    if constexpr (MODE == MODE_BWD && G::TH == GW_TH) {
+    // (blocked in, NCHW out) is the tangent sweep's last stage, which carries no dA ride: no such instance of it
+    if constexpr (MODE == MODE_BWD && G::TH == GW_TH && !(LIN == LAY_BLK && LOUT == LAY_NCHW)) {
         if (p.r2) {                                          // the reverse stage that also accumulates dA_k
             if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true, WY>, G::LDS_STAGE + G::LDS_DA)) return rc;
             k_stage<MT, PREC, MODE, LIN, LOUT, true, WY><<<grid, G::NT, G::LDS_STAGE + G::LDS_DA, st>>>(p);
@@ -1560,6 +1561,7 @@ int launch_stage_lay(const FusedParams &p, int lin, int lout, dim3 grid, hipStre
     }
     if constexpr (MODE == MODE_BWD) {
         if constexpr (WY == 2) CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
+        if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);      // the tangent sweep's last stage: zd_K leaves it as NCHW
         CDL_LAY_CASE(LAY_NCHW, LAY_BLK16);
     }
 #undef CDL_LAY_CASE
@@ -1935,6 +1937,41 @@ int backward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask,
     return 0;
 }
 
+// Forward-mode tangent sweep at the primal's supports.  The reverse stage computes
+// [z' != 0] * (base + corr(thin; W1)) and the patches of W2^T of it from ANY prepared pair: with the forward's pairs
+// (A_k, B_{k+1}), base = zd_k, thin = -rd_k and the primal's bit map of z_{k+1} it is one tangent iteration, and the assemble
+// with alpha = -1 and sub = -vp hands the next stage its thin operand -rd_{k+1} = vp - mask B_{k+1} zd_{k+1}.  The stage's
+// threshold partials (dtau_partial) are never reduced.
+template <int WY>
+int tangent_sweep(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask,
+                  const float *const *wA, const float *const *wB, const unsigned *const *maps, float *const *zd,
+                  float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, const Flags &f,
+                  void *stream)
+{
+    const int snake = snake_enabled();
+    const int L = f.lin;
+    const float *thin = vp;
+    const size_t fb = cdl_fused2d_frag_bytes(g->M);
+    int rc = prep_pairs(wA, wB, K, 1, frags, g->M, g->Ph, S(stream));       // (A_k, B_{k+1}), the forward's pairs
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) {
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
+        rc = stage_bwd<WY>(g, thin, k ? zd[k - 1] : nullptr, maps[k], fk, zd[k], patches, dtau_partial, 1,
+                           f.prec | CDL_LAYOUT_IN(k ? L : LAY_NCHW) | CDL_LAYOUT_OUT(k == K - 1 ? LAY_NCHW : L) |
+                               ((k & 1) && snake ? CDL_TILES_REVERSED : 0),
+                           nullptr, 0.0f, nullptr, nullptr, stream);
+        if (rc) return rc;
+        if (k < K - 1) {
+            rc = assemble<WY>(g, patches, mask, nvp, -1.0f, nrd[k], nullptr, 0, stream);
+            thin = nrd[k];
+        } else {
+            rc = assemble<WY>(g, patches, nullptr, nullptr, 1.0f, xdp, nullptr, 0, stream);
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // The C ABI.  Step-wise entry points always work on 64 x 16 tiles; the two sweeps pick the shape from the code layout.
@@ -2086,6 +2123,20 @@ int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *
     if (f.lin == LAY_BLK16)                  // bf16 code storage: 64 x 32 tiles, two waves per SIMD (see the top of the file)
         return forward_sweep<4>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
     return forward_sweep<2>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
+}
+
+int cdl_fused2d_tangent(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask,
+                        const float *const *wA, const float *const *wB, const unsigned *const *maps, float *const *zd,
+                        float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, int precision,
+                        void *stream)
+{
+    if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
+    if (K < 1 || !vp || !nvp || !wA || !wB || !maps || !zd || !xdp || !frags || !patches || !dtau_partial || (K > 1 && !nrd))
+        return CDL_EINVAL;
+    const Flags f = parse_flags(precision);
+    if (!f.ok || f.lout != 0) return CDL_EINVAL;
+    if (f.lin == LAY_BLK16) return CDL_EUNSUPPORTED;          // tangent codes are fp32: no bf16 storage
+    return tangent_sweep<2>(g, K, vp, nvp, mask, wA, wB, maps, zd, nrd, xdp, frags, patches, dtau_partial, f, stream);
 }
 
 int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *c,

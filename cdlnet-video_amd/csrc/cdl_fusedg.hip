@@ -1234,6 +1234,45 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
     return 0;
 }
 
+/* Forward-mode tangent sweep at the primal's supports: the reverse stage with the FORWARD's prepared
+ * pairs (A_k, B_{k+1}), base = zd_k, thin = -rd_k and the primal's bit map of z_{k+1}; the assemble with alpha = -1 and
+ * sub = -vp forms the next thin operand -rd_{k+1}.  Codes stay in the reference's (N,M,..) layout.  The threshold partials
+ * of the stages (dtau_partial) are never reduced. */
+int cdl_fusedg_tangent(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask,
+                       const float *const *wA, const float *const *wB, const unsigned *const *maps, float *const *zd,
+                       float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, int precision,
+                       void *stream)
+{
+    Route rt;
+    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
+    const bool strip = rt.kind == 1;
+    if (K < 1 || !vp || !nvp || !wA || !wB || !maps || !zd || !xdp || !frags || !patches || !dtau_partial || (K > 1 && !nrd))
+        return CDL_EINVAL;
+    if ((precision >> 5) != 0) return CDL_EINVAL;             // CDL_LAY_NCHW codes only
+    const int snake = cdl_opts().fused_snake;
+    const int forced = cdl_opts().fusedg_bwd_prec;            // (see cdl_fusedg_forward)
+    const int pbase = (rt.kind == 0 && (forced == 0 || forced == 2)) ? forced : (precision & 15);
+    const size_t fb = (strip ? rt.sp.frag_uint4 : rt.pl.frag_uint4) * 16;
+    int rc = strip ? cdl_strip_prep_pairs(g, rt.sp, wA, wB, K, 1, frags, S(stream))
+                   : prep_pairs(g, rt.pl, wA, wB, K, 1, frags, S(stream));  // (A_k, B_{k+1}), the forward's pairs
+    if (rc) return rc;
+    const float *thin = vp;
+    for (int k = 0; k < K; ++k) {
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
+        rc = cdl_fusedg_stage_bwd(g, thin, k ? zd[k - 1] : nullptr, maps[k], fk, zd[k], patches, dtau_partial, 1,
+                                  pbase | ((k & 1) && snake ? CDL_TILES_REVERSED : 0), stream);
+        if (rc) return rc;
+        if (k < K - 1) {
+            rc = cdl_fusedg_assemble(g, patches, mask, nvp, -1.0f, nrd[k], nullptr, 0, stream);
+            thin = nrd[k];
+        } else {
+            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, xdp, nullptr, 0, stream);
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 /* Reverse sweep: the fused stage produces du_k (one fat write), the threshold partials and the patches of q_k; the
  * filter gradients dA_k = -du_k (x) r_k and dB_k = z_k (x) q_k come from the shape-generic cdl_wgrad (its matrix-core
  * kernel where the shape has one).  wgrad_ws: cdl_wgrad_workspace_floats(g) floats. */

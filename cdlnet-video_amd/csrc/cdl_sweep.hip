@@ -142,4 +142,60 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
     return 0;
 }
 
+/* Forward-mode tangent of the plain loop at fixed supports: with G_k = [z_{k+1} != 0] of the primal,
+ *   zd_1 = G_0 (A_0 vp),   rd_k = mask B_k zd_k - vp,   zd_{k+1} = G_k (zd_k - A_k rd_k),   xdp = B_0 zd_K.
+ * The launches of cdl_ista_forward with the shrinkage replaced by the gate: cdl_analysis_ws gates its base only, so the
+ * gated step is cdl_analysis_rev_ws (out = [zsup != 0] (zin + alpha A x)), whose threshold sums nobody reads (dt_scratch,
+ * 2*M floats).  zgate[k] = z_{k+1} of the primal; zd / rd: K / K-1 buffers (ping-pong tables are fine when not kept). */
+int cdl_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask, const float *const *wA,
+                        const float *const *wB, const float *const *zgate, float *const *zd, float *const *rd, float *xdp,
+                        float *dt_scratch, float *scratch, size_t scratch_floats, void *stream)
+{
+    if (!cdl_geom_ok(g) || K < 1 || !vp || !wA || !wB || !zgate || !zd || !xdp || !dt_scratch || !scratch || (K > 1 && !rd))
+        return CDL_EINVAL;
+    if (scratch_floats < cdl_ista_scratch_floats(g)) return CDL_EINVAL;
+    const size_t M = g->M;
+    for (int k = 0; k < K; ++k) {
+        const float *zin = nullptr, *x = vp;
+        if (k > 0) {
+            CDL_TRY(cdl_synthesis_ws(g, zd[k - 1], nullptr, wB[k], 1.0f, mask, vp, rd[k - 1], scratch, scratch_floats,
+                                     stream));
+            zin = zd[k - 1];
+            x = rd[k - 1];
+        }
+        CDL_TRY(cdl_analysis_rev_ws(g, x, wA[k], k == 0 ? 1.0f : -1.0f, zin, zgate[k], nullptr, dt_scratch, dt_scratch + M,
+                                    nullptr, zd[k], scratch, scratch_floats, nullptr, stream));
+    }
+    return cdl_synthesis_ws(g, zd[K - 1], nullptr, wB[0], 1.0f, nullptr, nullptr, xdp, scratch, scratch_floats, stream);
+}
+
+/* Reverse sweep of the tangent net (linear in vp with the gates fixed): the launches of cdl_ista_backward's plain branch
+ * with the supports taken from the primal codes zgate and the operands from the tangent sweep (zd, rd, vp); no threshold
+ * gradient leaves it (dt_scratch, 2*M floats) and no data gradient is formed.  g_xp = dL/dxdp. */
+int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float *mask, const float *const *wA,
+                         const float *const *wB, const float *const *zgate, const float *const *zd,
+                         const float *const *rd, const float *g_xp, float *const *dA, float *const *dB, float *gbuf0,
+                         float *gbuf1, float *q, float *dt_scratch, float *scratch, size_t scratch_floats, void *stream)
+{
+    if (!cdl_geom_ok(g) || K < 1 || !vp || !wA || !wB || !zgate || !zd || !g_xp || !dA || !dB || !gbuf0 || !gbuf1 || !q ||
+        !dt_scratch || !scratch || (K > 1 && !rd))
+        return CDL_EINVAL;
+    if (scratch_floats < cdl_ista_scratch_floats(g)) return CDL_EINVAL;
+    const size_t M = g->M;
+    float *gk = gbuf0, *other = gbuf1;
+    CDL_TRY(cdl_wgrad(g, zd[K - 1], nullptr, g_xp, 1.0f, dB[0], scratch, scratch_floats, stream));
+    CDL_TRY(cdl_analysis_rev_ws(g, g_xp, wB[0], 1.0f, nullptr, zgate[K - 1], nullptr, dt_scratch, dt_scratch + M, nullptr, gk,
+                                scratch, scratch_floats, nullptr, stream));
+    for (int k = K - 1; k >= 1; --k) {                          // gk = du_k, gated
+        CDL_TRY(cdl_synthesis_ws(g, gk, nullptr, wA[k], -1.0f, mask, nullptr, q, scratch, scratch_floats, stream));
+        CDL_TRY(cdl_wgrad_pair(g, gk, rd[k - 1], -1.0f, dA[k], zd[k - 1], q, 1.0f, dB[k], scratch, scratch_floats, stream));
+        CDL_TRY(cdl_analysis_rev_ws(g, q, wB[k], 1.0f, gk, zgate[k - 1], nullptr, dt_scratch, dt_scratch + M, nullptr, other,
+                                    scratch, scratch_floats, nullptr, stream));
+        float *t = gk;
+        gk = other;
+        other = t;
+    }
+    return cdl_wgrad(g, gk, nullptr, vp, 1.0f, dA[0], scratch, scratch_floats, stream);
+}
+
 }  // extern "C"

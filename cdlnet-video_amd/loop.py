@@ -437,6 +437,199 @@ class UnrolledISTA(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------
+# Forward-mode tangent of the plain loop: with the supports G_k = [z_{k+1} != 0] of the primal fixed
+# the loop is affine in y, and a direction v in y propagates through the same recursion with the shrinkage replaced by G_k:
+#     zd_1 = G_0 A_0 vp      rd_k = mask B_k zd_k - vp      zd_{k+1} = G_k (zd_k - A_k rd_k)      xdot = post(B_0 zd_K)
+# (vp, the mean added back: preprocess(v)).  No threshold appears.  The tangent net is linear, so its reverse sweep is the
+# primal's with codes -> zd, residuals -> rd, yp -> vp, the PRIMAL's gates, and no threshold / data gradient.
+def _tangent_generic(g, vp, mask_p, A, B, gates, keep):
+    """Whole generic tangent sweep from one C call (cdl_tangent_forward): (xdp, zd, rd)."""
+    return ops.tangent_forward(g, vp, mask_p, A, B, gates, keep)
+
+
+def _tangent_generic_stepwise(g, vp, mask_p, A, B, gates, keep):
+    """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
+    K = len(A)
+    dts = torch.empty(2 * g.M, device=vp.device, dtype=torch.float32)      # threshold sums of the gated step: never read
+    zd, rd = [], []
+    z = ops.analysis_rev(g, vp, A[0], 1.0, None, gates[0], None, dts)
+    zd.append(z)
+    for k in range(1, K):
+        r = ops.synthesis(g, z, B[k], 1.0, None, mask_p, vp)
+        z = ops.analysis_rev(g, r, A[k], -1.0, z, gates[k], None, dts)
+        zd.append(z)
+        rd.append(r)
+    xdp = ops.synthesis(g, z, B[0], 1.0)
+    return xdp, (zd if keep else []), (rd if keep else [])
+
+
+def _tangent_backward_generic(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp):
+    """Reverse sweep of the generic tangent sweep from one C call (cdl_tangent_backward): (dA, dB)."""
+    return ops.tangent_backward(g, vp, mask_p, list(A), list(B), list(gates), list(zd), list(rd), g_xp)
+
+
+def _tangent_backward_generic_stepwise(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp):
+    """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
+    dA, dB = [None] * K, [None] * K
+    dts = torch.empty(2 * g.M, device=vp.device, dtype=torch.float32)
+    dB[0] = ops.wgrad(g, zd[K - 1], g_xp, 1.0)
+    gk = ops.analysis_rev(g, g_xp, B[0], 1.0, None, gates[K - 1], None, dts)
+    for k in range(K - 1, 0, -1):
+        q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
+        dA[k], dB[k] = ops.wgrad_pair(g, gk, rd[k - 1], -1.0, zd[k - 1], q, 1.0)
+        gk = ops.analysis_rev(g, q, B[k], 1.0, gk, gates[k - 1], None, dts)
+    dA[0] = ops.wgrad(g, gk, vp, 1.0)
+    return dA, dB
+
+
+def _tangent_fused(g, vp, mask_p, A, B, maps, keep, layout=None, precision=None):
+    """Whole tangent sweep on the fused 2-D kernels from one C call (cdl_fused2d_tangent): per iteration one reverse-stage
+    launch with the forward's prepared pair and the primal's bit map, and one assemble.  Returns (xdp, zd, nrd): nrd are
+    the NEGATED residuals -rd_k (the stages' thin operand)."""
+    return ops.fused_tangent(g, vp, mask_p, A, B, maps, keep, precision or PRECISION, layout or CODE_LAYOUT)
+
+
+def _tangent_fused_stepwise(g, vp, mask_p, A, B, maps, keep, layout="nchw", precision=None):
+    """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
+    K = len(A)
+    prec = precision or PRECISION
+    frags = [ops.fused_prep(A[k], B[(k + 1) % K]) for k in range(K)]   # the forward's pairs
+    patches = ops.fused_patches(g, vp.device)
+    dtp = torch.empty((ops.fused_tiles(g), g.M), device=vp.device, dtype=torch.float32)
+    nvp = torch.neg(vp)
+    zd, nrd = [], []
+    thin, z = vp, None
+    for k in range(K):
+        z = ops.fused_stage_bwd(g, thin, z, maps[k], frags[k], patches, dtp, True, prec,
+                                lay_in=layout if k else "nchw", lay_out="nchw" if k == K - 1 else layout)
+        zd.append(z)
+        if k < K - 1:
+            thin = ops.fused_assemble(g, patches, mask_p, nvp, -1.0)
+            nrd.append(thin)
+    xdp = ops.fused_assemble(g, patches, None, None, 1.0)
+    return xdp, (zd if keep else []), (nrd if keep else [])
+
+
+def _tangent_fusedg(g, vp, mask_p, A, B, maps, keep):
+    """cdl_fusedg_tangent: the same construction on the tile / strip kernels (codes in the reference's layout)."""
+    return ops.fusedg_tangent(g, vp, mask_p, A, B, maps, keep)
+
+
+def _negate_dA_tail(dA):
+    """The fused tangent sweeps keep -rd_k: the reverse sweep's dA_k = -du_k (x) r_k (k >= 1) comes out negated."""
+    return [dA[0]] + [torch.neg(w) for w in dA[1:]]
+
+
+@_arithmetic_aware
+class TangentISTA(torch.autograd.Function):
+    """(y, v, mask, c, t, A_0..A_{K-1}, B_0..B_{K-1}) -> (xhat, xdot): the primal of UnrolledISTA and its directional
+    derivative in y along v at the primal's supports.  The tangent follows the primal's tier (fused 2-D / fused generic /
+    generic).  Gradients for t (from xhat alone) and both filter banks (the sum of the two reverse sweeps)."""
+
+    @staticmethod
+    def forward(ctx, y, v, mask, c, t, cfg, *weights):
+        K, s = cfg["K"], cfg["s"]
+        A, B = weights[:K], weights[K:]
+        yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
+        vp, vmean, _, _ = ops.preprocess(v, s, mask)          # linear: the same mean rule, mask and reflect pad
+        N, C = yp.shape[:2]
+        M = A[0].shape[0]
+        nd = yp.dim() - 2
+        P = tuple(A[0].shape[2:])
+        g = ops.Geometry.make(N, C, M, yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        ctx.is_map = c is not None and c.dim() > 1
+        cmap = c if ctx.is_map else None
+        tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
+        tau = ops.thresholds(t, None if ctx.is_map else c, N)
+
+        ctx.set_materialize_grads(False)
+        _no_data_gradients(ctx, ((0, "y"), (1, "v"), (2, "mask"), (3, "sigma")))
+        keep = any(ctx.needs_input_grad)
+        auto = BACKEND == "auto" and not ctx.exact and not ctx.is_map
+        ctx.fused = auto and ops.fused_supported(g)
+        ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
+        if ctx.fused:
+            ctx.layout, ctx.precision = CODE_LAYOUT, PRECISION        # net.jvp refuses blocked_bf16; so does the C sweep
+            xp, z, codes, resid, maps = ops.fused_forward(g, yp, mask_p, tau, A, B, keep, PRECISION, ctx.layout,
+                                                          keep_maps=True)
+            xdp, zd, rd = _tangent_fused(g, vp, mask_p, A, B, maps, keep, ctx.layout, ctx.precision)
+        elif ctx.fusedg:
+            ctx.layout = "nchw"
+            xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, ctx.layout, keep_maps=True)
+            xdp, zd, rd = _tangent_fusedg(g, vp, mask_p, A, B, maps, keep)
+        else:                                          # the gates are the primal's codes: all K are kept
+            xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, True, keep,
+                                                         **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
+            xdp, zd, rd = _tangent_generic(g, vp, mask_p, A, B, codes, keep)
+        xhat = ops.postprocess(xp, mean, pads)
+        xdot = ops.postprocess(xdp, vmean, pads)
+
+        ctx.geom, ctx.pads, ctx.K = g, pads, K
+        ctx.has_mask, ctx.has_c = mask_p is not None, c is not None
+        if keep:
+            empty = yp.new_empty(0)
+            ctx.n_maps = len(maps)
+            ctx.save_for_backward(yp, vp, mask_p if mask_p is not None else empty, c if c is not None else empty, t,
+                                  *weights, *codes, *resid, *zd, *rd, *maps)
+        return xhat, xdot
+
+    @staticmethod
+    def backward(ctx, g_xhat, g_xdot):
+        K, g = ctx.K, ctx.geom
+        sv = ctx.saved_tensors
+        yp, vp, mask_p, c, t = sv[:5]
+        mask_p = mask_p if ctx.has_mask else None
+        c = c if ctx.has_c else None
+        o = 5
+        A, B = sv[o:o + K], sv[o + K:o + 2 * K]
+        o += 2 * K
+        codes, resid = sv[o:o + K], sv[o + K:o + 2 * K - 1]
+        o += 2 * K - 1
+        zd, rd = sv[o:o + K], sv[o + K:o + 2 * K - 1]
+        o += 2 * K - 1
+        maps = sv[o:]
+        assert len(maps) == ctx.n_maps
+        dev = yp.device
+        dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
+        dA = dB = None
+        if g_xhat is not None:                         # the primal's reverse sweep, as UnrolledISTA runs it
+            g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads)
+            if ctx.fusedg:
+                dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt, maps=maps,
+                                          layout=ctx.layout)
+            elif ctx.fused:
+                dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt, maps=maps,
+                                         layout=ctx.layout, precision=ctx.precision)
+            elif ctx.is_map:
+                dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, None, dt, cmap=c,
+                                           tslope=t.detach().reshape(K, 2, g.M)[:, 1].contiguous())
+            else:
+                dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt)
+        if g_xdot is not None:                         # the tangent's: same sweep, other operands, the primal's gates
+            g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads)
+            scratch = torch.empty_like(dt)             # its threshold output: never returned
+            if ctx.fusedg:
+                tA, tB = _backward_fusedg(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, None, scratch, maps=maps,
+                                          layout=ctx.layout)
+                tA = _negate_dA_tail(tA)
+            elif ctx.fused:
+                tA, tB = _backward_fused(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, None, scratch, maps=maps,
+                                         layout=ctx.layout, precision=ctx.precision)
+                tA = _negate_dA_tail(tA)
+            else:
+                tA, tB = _tangent_backward_generic(g, K, vp, mask_p, A, B, codes, zd, rd, g_xdp)
+            if dA is None:
+                dA, dB = tA, tB
+            else:
+                dA = [a + b for a, b in zip(dA, tA)]
+                dB = [a + b for a, b in zip(dB, tB)]
+        if dA is None:
+            dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+        _queue_backward_end()
+        return (None, None, None, None, dt.reshape(t.shape), None, *dA, *dB)
+
+
+# ------------------------------------------------------------------------------------------
 # CSR temporal variants (SURVEY.md section 8(f) item 1; reference model/net.py:426-463, 525-568):
 # the same loop with the shrinkage replaced by prox_CSR / prox_CSR_f2 around a neighbour frame's code.
 #     u_0 = A_0 yp                       z_1     = prox(u_0; zp[, za], lam_0, gam_0)
@@ -651,6 +844,12 @@ def run_csr(y, mask, c, z_prev, z_after, t, g1, g2, A, B, s):
     """Front end of the neighbour branches; the no-neighbour branch is `run`."""
     cfg = {"K": len(A), "s": int(s)}
     return TemporalISTA.apply(y, mask, c, z_prev, z_after, t, g1, g2, cfg, *A, *B)
+
+
+def run_tangent(y, v, mask, c, t, A, B, s):
+    """Front end of net.jvp: (xhat, xdot)."""
+    cfg = {"K": len(A), "s": int(s)}
+    return TangentISTA.apply(y, v, mask, c, t, cfg, *A, *B)
 
 
 def run(y, mask, c, t, A, B, s, all_codes=False):

@@ -140,6 +140,40 @@ class _ISTANet(nn.Module):
         xhat, z = self._run(y, sigma, mask, False)
         return xhat, z
 
+    def _jvp_refusal(self):
+        """Why this net has no tangent sweep (None: it has one)."""
+        return None
+
+    def jvp(self, y, v, sigma=None, mask=1):
+        """(xhat, xdot): the forward pass and its directional derivative J(y) v in the observation, at the supports of
+        the primal codes (where the net is affine in y: the derivative autograd of the reference gives, without a step
+        size).  xhat is what forward returns; both are differentiable in the parameters -- `t` through xhat alone (the
+        thresholds do not appear in the tangent recursion).  v is a constant direction shaped like
+        y; gradients with respect to y, v, sigma or mask are not produced."""
+        why = self._jvp_refusal()
+        if why is not None:
+            raise NotImplementedError(f"cdlnet_video_amd: {type(self).__name__}.jvp: {why}")
+        if not torch.is_tensor(v):
+            raise TypeError("jvp: v must be a tensor shaped like y")
+        for name, t in (("y", y), ("v", v)):
+            if not t.is_cuda:
+                raise RuntimeError(
+                    f"{type(self).__name__}.jvp: {name} is on {t.device}. This package has no CPU "
+                    "compute path; the iterations run in HIP kernels on a ROCm device.")
+        if tuple(v.shape) != tuple(y.shape):
+            raise ValueError(f"jvp: v has shape {tuple(v.shape)}, y has {tuple(y.shape)}")
+        for name, t in (("v", v), ("y", y), ("sigma", sigma), ("mask", mask)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"cdlnet_video_amd: jvp: `{name}` requires grad; the tangent sweep returns "
+                                          "parameter gradients only (detach() it)")
+        if loop.CODE_LAYOUT == "blocked_bf16":
+            raise NotImplementedError("cdlnet_video_amd: jvp with set_code_layout('blocked_bf16') is not implemented "
+                                      "(tangent codes are stored in fp32)")
+        y, v = y.to(torch.float32), v.to(torch.float32)
+        A, B = self._filters()
+        c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], self.s))
+        return loop.run_tangent(y, v, _mask_tensor(mask, y), c, self.t, A, B, self.s)
+
     def forward_generator(self, y, sigma=None, mask=1):
         """Yields z_1..z_K, then xhat (net.py:94-104, 214-227)."""
         outs = self._run(y, sigma, mask, True)
@@ -254,6 +288,9 @@ class _CSRBase(_ISTANet):
         """net.py:419-424 / 518-523: only `t`, `A`, `B` are projected (not t2, g*, A2, B2)."""
         self.t.clamp_(0.0)
         ops.project_filter_banks_([m.weight.data for m in self.A] + [m.weight.data for m in self.B])
+
+    def _jvp_refusal(self):
+        return "the CSR nets' proximal maps have no tangent sweep"
 
     def _prep(self, y, sigma, mask):
         if not y.is_cuda:
@@ -412,6 +449,9 @@ class CDLNetVideo(_ISTANet):
         c = _noise_scale(sigma, self.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], self.s))
         blocks = [(b.conv1.weight, b.conv2.weight) for b in self.residual_blocks]
         return loop.run_residual(y, _mask_tensor(mask, y), c, self.t, A, B, self.s, blocks, all_codes)
+
+    def _jvp_refusal(self):
+        return "residual=True (a ResidualBlock after every iteration) has no tangent sweep" if self.residual else None
 
     def forward_generator(self, y, sigma=None, mask=1):
         """net.py:214-227; with residual blocks the yielded codes are the ST outputs (before the block)."""

@@ -886,10 +886,12 @@ def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked"):
+def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False):
     """Whole forward sweep in one C call.  keep=True: every z_k and r_k gets its own buffer (training) and
     each launch also writes the support/sign bit map of its z_{k+1}; keep=False: two ping-pong buffers
     each, no maps.  `layout`: how z_1..z_{K-1} are stored (they never leave the sweeps; z_K is always NCHW).
+    keep_maps (with keep=False): the K bit maps are written although every code and residual ping-pongs (what a tangent
+    sweep under no_grad needs of the primal).
     Returns (xp, z_K, codes, resid, maps); codes[:-1] are flat buffers in `layout` unless it is "nchw"."""
     K = len(A)
     yp, tau = _dev(yp, "yp"), _dev(tau, "tau")
@@ -905,7 +907,8 @@ def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", 
     rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
     z = [zbuf[k % nz] for k in range(K - 1)] + [zK]
     r = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
-    maps = list(torch.empty((K, g.N, 4, g.dims[1], g.dims[2]), device=dev, dtype=torch.int32).unbind(0)) if keep else []
+    maps = list(torch.empty((K, g.N, 4, g.dims[1], g.dims[2]), device=dev, dtype=torch.int32).unbind(0)) \
+        if (keep or keep_maps) else []
     xp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
     frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
     patches = fused_patches(g, dev)
@@ -1124,7 +1127,7 @@ def _fusedg_code_buffers(g: Geometry, layout, device, count):
     return list(fusedg_rsc_buffer(g, device, max(count, 1)).unbind(0))
 
 
-def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw"):
+def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep_maps=False):
     """Whole forward sweep in one C call (cdl_fusedg_forward); same contract as fused_forward: codes[:-1] come back
     in `layout` ("nchw", or "rsc" where fusedg_code_layout allows it), codes[-1] = z_K as (N,M,..)."""
     K = len(A)
@@ -1140,7 +1143,8 @@ def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw"):
     rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
     z = [zint[k % nz] for k in range(K - 1)] + [zK]
     r = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
-    maps = list(torch.empty((K,) + _fusedg_map_shape(g), device=dev, dtype=torch.int32).unbind(0)) if keep else []
+    maps = list(torch.empty((K,) + _fusedg_map_shape(g), device=dev, dtype=torch.int32).unbind(0)) \
+        if (keep or keep_maps) else []                      # keep_maps: see fused_forward
     xp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
     frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
     patches = torch.empty(pf, device=dev, dtype=torch.float32)
@@ -1268,6 +1272,116 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
         _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _ptr(cmap), _ptr(tslope), _ptr(dcmap), _stream())
     _lib.check(rc, "cdl_ista_backward")
     return dA, dB
+
+
+# ------------------------------------------------------------------------------------------
+# forward-mode tangent sweeps at the primal's supports
+def _tangent_tables(K, keep, zbufs, rbufs):
+    nz = K if keep else min(K, 2)
+    nr = (K - 1) if keep else min(K - 1, 2)
+    return [zbufs[k % nz] for k in range(K)], ([rbufs[k % nr] for k in range(K - 1)] if K > 1 else [])
+
+
+def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep):
+    """Generic tangent sweep in one C call (cdl_tangent_forward): gates = the primal's z_1..z_K (N,M,..); vp the
+    pre-processed direction.  Returns (xdp, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else []."""
+    K = len(A)
+    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
+    A = [_dev(w, "A") for w in A]
+    B = [_dev(w, "B") for w in B]
+    gates = [_dev(t, "gate") for t in gates]
+    assert len(gates) == K and all(tuple(t.shape) == g.code_shape() for t in gates)
+    dev = vp.device
+    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
+    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
+    zd, rd = _tangent_tables(K, keep, zbuf, rbuf)
+    xdp = _new(g.image_shape(), dev)
+    dts = _new((2 * g.M,), dev)
+    ws, n = ista_scratch(g, dev)
+    rc = _lib.lib().cdl_tangent_forward(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(mask_p), _ptr_table(A),
+                                        _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
+                                        _ptr_table(rd) if rd else None, _ptr(xdp), _ptr(dts), _ptr(ws), n, _stream())
+    _lib.check(rc, "cdl_tangent_forward")
+    return xdp, (zd if keep else []), (rd if keep else [])
+
+
+def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp):
+    """Reverse sweep of the generic tangent sweep in one C call (cdl_tangent_backward): (dA list, dB list) for
+    dL/dxdp = g_xp; gates = the primal's codes, zd / rd = what tangent_forward kept."""
+    K = len(A)
+    dev = vp.device
+    A = [_dev(w, "A") for w in A]
+    B = [_dev(w, "B") for w in B]
+    gates = [_dev(t, "gate") for t in gates]
+    zd = [_dev(t, "zd") for t in zd]
+    rd = [_dev(t, "rd") for t in rd]
+    assert len(gates) == K == len(zd) and len(rd) == K - 1
+    dAB = _new((2 * K,) + g.filter_shape(), dev)
+    dA, dB = list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
+    g0, g1, q = _new(g.code_shape(), dev), _new(g.code_shape(), dev), _new(g.image_shape(), dev)
+    dts = _new((2 * g.M,), dev)
+    ws, n = ista_scratch(g, dev)
+    rc = _lib.lib().cdl_tangent_backward(ctypes.byref(g.c_struct()), K, _ptr(_dev(vp, "vp")), _ptr(_opt(mask_p, "mask")),
+                                         _ptr_table(A), _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
+                                         _ptr_table(rd) if rd else None, _ptr(_dev(g_xp, "g_xp")), _ptr_table(dA),
+                                         _ptr_table(dB), _ptr(g0), _ptr(g1), _ptr(q), _ptr(dts), _ptr(ws), n, _stream())
+    _lib.check(rc, "cdl_tangent_backward")
+    return dA, dB
+
+
+def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked"):
+    """Tangent sweep on the fused 2-D kernels in one C call (cdl_fused2d_tangent).  maps: the primal's K bit maps.
+    Returns (xdp, zd, nrd): with keep the tangent codes (zd[:-1] in `layout`, zd[-1] NCHW) and the NEGATED tangent
+    residuals -rd_1..-rd_{K-1} (what the stages read), else []."""
+    K = len(A)
+    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
+    A = [_dev(w, "A") for w in A]
+    B = [_dev(w, "B") for w in B]
+    assert len(maps) == K
+    dev = vp.device
+    nvp = torch.neg(vp)                                      # thin: the assemble subtracts it
+    nz = (K - 1) if keep else min(K - 1, 2)
+    nr = nz
+    zK = torch.empty(g.code_shape(), device=dev, dtype=torch.float32)
+    zbuf = fused_code_buffer(g, layout, dev, max(nz, 1))
+    rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
+    zd = [zbuf[k % nz] for k in range(K - 1)] + [zK]
+    nrd = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
+    xdp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
+    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
+    patches = fused_patches(g, dev)
+    dtp = torch.empty((fused_tiles(g), g.M), device=dev, dtype=torch.float32)
+    rc = _lib.lib().cdl_fused2d_tangent(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(nvp), _ptr(mask_p), _ptr_table(A),
+                                        _ptr_table(B), _ptr_table(list(maps)), _ptr_table(zd),
+                                        _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
+                                        PRECISION[precision] | _lay_in(layout), _stream())
+    _lib.check(rc, "cdl_fused2d_tangent")
+    return xdp, (zd if keep else []), (nrd if keep else [])
+
+
+def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep):
+    """cdl_fusedg_tangent: as fused_tangent for the tile / strip kernels' shapes; codes in the reference's layout."""
+    K = len(A)
+    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
+    A = [_dev(w, "A") for w in A]
+    B = [_dev(w, "B") for w in B]
+    assert len(maps) == K
+    dev = vp.device
+    nvp = torch.neg(vp)
+    fb, pf, tiles, mw = _fusedg_sizes(g)
+    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
+    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
+    zd, nrd = _tangent_tables(K, keep, zbuf, rbuf)
+    xdp = _new(g.image_shape(), dev)
+    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
+    patches = _new((pf,), dev)
+    dtp = _new((tiles, g.M), dev)
+    rc = _lib.lib().cdl_fusedg_tangent(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(nvp), _ptr(mask_p), _ptr_table(A),
+                                       _ptr_table(B), _ptr_table(list(maps)), _ptr_table(zd),
+                                       _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
+                                       0, _stream())
+    _lib.check(rc, "cdl_fusedg_tangent")
+    return xdp, (zd if keep else []), (nrd if keep else [])
 
 
 def fused_timing(enable: bool):

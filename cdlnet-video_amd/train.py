@@ -100,6 +100,21 @@ def mcsure_loss(net, obsrv, xhat, sigma, mask=1, h=1e-3, generator=None, b=None)
     return torch.mean((obsrv - xhat) ** 2) + div
 
 
+def sure_loss(net, obsrv, sigma, mask=1, generator=None, b=None):
+    """SURE objective with the divergence term from the exact directional derivative (net.jvp) instead of a finite
+    difference: with (xhat, xdot) = net.jvp(obsrv, b, sigma, mask), b ~ N(0, I) drawn as mcsure_loss draws it,
+        mean((obsrv - xhat)^2) + 2 * mean((sigma/255)^2 * b * xdot)
+    xdot = J(obsrv) b at the supports of the primal codes: what h -> 0 of mcsure_loss converges to, with no step size,
+    no 1/h in the gradient, and the same number of sweeps (two forward, two reverse).
+    Returns (loss, xhat)."""
+    if b is None:
+        dev = generator.device if generator is not None else obsrv.device
+        b = torch.randn(obsrv.shape, device=dev, dtype=obsrv.dtype, generator=generator).to(obsrv.device)
+    xhat, xdot = net.jvp(obsrv, b, sigma, mask=mask)
+    s2 = (sigma / 255.0) ** 2
+    return torch.mean((obsrv - xhat) ** 2) + 2.0 * torch.mean(s2 * b * xdot), xhat
+
+
 def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, project=True,
                grad_sync=None, generator=None, mcsure=False, loss_fn=None):
     """One optimiser step: awgn -> forward -> MSE (or MC-SURE) -> backward -> [all-reduce] -> clip -> Adam
@@ -107,19 +122,26 @@ def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, proje
 
     `grad_sync` is a callable run between backward and clipping (parallel.GradientBucket.sync).  `loss_fn(xhat, batch)`
     replaces the MSE (trainmri.py's `combmse`: a loss.CombinedLossWithSSIM); `mcsure` takes precedence over it.
+    `mcsure`: False, True (the reference's finite-difference MC-SURE, mcsure_loss) or "exact" (sure_loss: the divergence
+    from net.jvp).
     Returns (loss tensor, sigma).
     """
+    if isinstance(mcsure, str) and mcsure != "exact":          # any other value keeps its truthiness
+        raise ValueError(f"mcsure must be False, True or 'exact', got {mcsure!r}")
     mask = gen_bayer_mask(batch) if demosaic else 1
     noisy, sigma = awgn(batch, noise_std, generator)
     obsrv = mask * noisy
     opt.zero_grad(set_to_none=True)
-    xhat, _ = net(obsrv, sigma, mask=mask)
-    if mcsure:
-        loss = mcsure_loss(net, obsrv, xhat, sigma, mask=mask, generator=generator)
-    elif loss_fn is not None:
-        loss = loss_fn(xhat, batch)
+    if isinstance(mcsure, str):
+        loss, xhat = sure_loss(net, obsrv, sigma, mask=mask, generator=generator)
     else:
-        loss = torch.mean((batch - xhat) ** 2)
+        xhat, _ = net(obsrv, sigma, mask=mask)
+        if mcsure:
+            loss = mcsure_loss(net, obsrv, xhat, sigma, mask=mask, generator=generator)
+        elif loss_fn is not None:
+            loss = loss_fn(xhat, batch)
+        else:
+            loss = torch.mean((batch - xhat) ** 2)
     loss.backward()
     if grad_sync is not None:
         grad_sync()
@@ -193,8 +215,8 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     every rank, so replicas, optimiser states and learning rates stay identical.
     `combmse` (trainmri.py / train3d.py): the train phase's loss is `loss_fn`, by default
     loss.CombinedLossWithSSIM(1.0, 0.01, 0.1) (VGG16 weights from the default local file); a `loss_fn` given without
-    `combmse` is used the same way.  `mcsure` takes precedence; val and test keep the MSE; the logged train PSNR is
-    -10 log10 of that training loss, as in the reference.
+    `combmse` is used the same way.  `mcsure` (True: finite differences; "exact": net.jvp, see train_step) takes
+    precedence; val and test keep the MSE; the logged train PSNR is -10 log10 of that training loss, as in the reference.
     Returns the history [(epoch, phase, psnr)].
     """
     ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1

@@ -366,6 +366,25 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       const float *cmap /*nullable*/, const float *tslope /*K*M, nullable*/, float *dcmap /*nullable*/,
                       void *stream);
 
+/* ---- forward-mode tangent of the plain loop at the primal's supports ----
+ * With G_k = [zgate[k] != 0] (zgate[k] = z_{k+1} of the primal) and a direction vp in the padded observation:
+ *   zd_1 = G_0 (A_0 vp),  rd_k = mask B_k zd_k - vp,  zd_{k+1} = G_k (zd_k - A_k rd_k),  xdp = B_0 zd_K
+ * -- no threshold appears.  The launches of cdl_ista_forward with cdl_analysis_rev_ws as the gated step.  zd: K code
+ * buffers, rd: K-1 thin ones (consecutive entries must differ; two each suffice when nothing is kept).  dt_scratch: 2*M
+ * floats nobody reads; scratch: cdl_ista_scratch_floats(g). */
+int cdl_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
+                        const float *const *wA, const float *const *wB, const float *const *zgate, float *const *zd,
+                        float *const *rd, float *xdp, float *dt_scratch, float *scratch, size_t scratch_floats,
+                        void *stream);
+/* Its reverse sweep (the tangent net is linear in vp with the gates fixed): dA[k], dB[k] of a loss with dL/dxdp = g_xp --
+ * cdl_ista_backward's plain branch with the supports taken from zgate and the operands from the tangent sweep; no
+ * threshold and no data gradient.  gbuf0, gbuf1: code-sized; q: thin. */
+int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
+                         const float *const *wA, const float *const *wB, const float *const *zgate,
+                         const float *const *zd, const float *const *rd, const float *g_xp, float *const *dA,
+                         float *const *dB, float *gbuf0, float *gbuf1, float *q, float *dt_scratch, float *scratch,
+                         size_t scratch_floats, void *stream);
+
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
  * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere.  w inout. */
 int cdl_project_filters(float *w, int nfilters, int flen, void *stream);
@@ -517,6 +536,16 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
                          float *dtau_partial, float *wgrad_ws, int precision, float *dyp /*nullable*/,
                          float *dtau /*K*N*M, nullable*/, void *stream);
 
+/* Tangent sweep on the fused 2-D kernels: per iteration one reverse-stage launch with the FORWARD's
+ * prepared pair (A_k, B_{k+1}), base = zd_k, thin = -rd_k and maps[k] = the primal's bit map of z_{k+1}, then one assemble
+ * (alpha = -1, sub = nvp = -vp) that writes nrd[k] = -rd_{k+1}.  zd[0..K-2] in CDL_LAYOUT_IN(precision) (NCHW or blocked
+ * fp32), zd[K-1] NCHW; nrd: K-1 thin buffers holding the NEGATED residuals.  dtau_partial: cdl_fused2d_tiles(g) * M floats
+ * nobody reads.  Buffers as cdl_fused2d_forward's. */
+int cdl_fused2d_tangent(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask /*nullable*/,
+                        const float *const *wA, const float *const *wB, const unsigned *const *maps, float *const *zd,
+                        float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, int precision,
+                        void *stream);
+
 /* ==== fused MFMA path for the other shapes (cdl_fusedg.hip): any C, 2-D / 3-D, unit stride, square planes ====
  * P in {3,5,7}, odd Pd with C*Pd in {1,3,5,7}, M <= 64 -- CDLNetVideo.forward's loop body (net.py:204-207) and
  * CDLNet.forward's (net.py:86-87) with C = 3 + mask (JDD).  Same fusion boundary and call structure as the
@@ -567,6 +596,13 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
                         float *du1, float *q, void *frags, float *patches, float *dtau_partial, float *wgrad_ws,
                         size_t wgrad_ws_floats, int precision, float *dyp /*nullable*/,
                         float *dtau /*K*N*M, nullable*/, void *stream);
+
+/* cdl_fused2d_tangent for the shapes of this family (tile and strip kernels); codes in the reference's layout only
+ * (precision carries no layout bits). */
+int cdl_fusedg_tangent(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask /*nullable*/,
+                       const float *const *wA, const float *const *wB, const unsigned *const *maps, float *const *zd,
+                       float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, int precision,
+                       void *stream);
 
 /* Per-kernel timing inside the fused sweeps: cdl_fused2d_timing(1) starts collecting HIP-event pairs around
  * every forward stage (class 0; the k = 0 launch, which reads no code, is class 3), reverse stage (1) and
