@@ -10,7 +10,8 @@ from .loss import CombinedLossWithSSIM, load_vgg16_weights
 from .metrics import ssim
 from .net import ST, CDLNet, CDLNet_CSR, CDLNet_CSRf2, CDLNetVideo, GDLNet, ResidualBlock, prox_CSR, prox_CSR_f2
 from .temporal import csr_inference_loop, csr_inference_v2
-from .train import build_model, fit, init_model, load_ckpt, mcsure_loss, save_args, save_ckpt, sure_loss, train_step
+from .train import (build_model, fit, init_model, load_ckpt, mcsure_loss, save_args, save_ckpt, sure_loss, sure_loss_clip,
+                    train_step, train_step_clip)
 from .utils import awgn, awgn3d, gen_bayer_mask, psnr
 
 JDD_CDLNet = CDLNet      # BASELINE.json config 4: CDLNet(C=3) + Bayer mask
@@ -18,6 +19,7 @@ JDD_CDLNet = CDLNet      # BASELINE.json config 4: CDLNet(C=3) + Bayer mask
 __all__ = ["CDLNet", "CDLNetVideo", "ResidualBlock", "GDLNet", "JDD_CDLNet", "CDLNet_CSR", "CDLNet_CSRf2", "prox_CSR",
            "prox_CSR_f2", "csr_inference_loop", "csr_inference_v2", "ConvAdjoint2dGabor", "ST",
            "build_model", "init_model", "load_ckpt", "save_ckpt", "train_step", "fit", "mcsure_loss", "sure_loss",
+           "sure_loss_clip", "train_step_clip",
            "save_args",
            "awgn", "awgn3d", "gen_bayer_mask", "psnr", "ssim", "CombinedLossWithSSIM", "load_vgg16_weights", "loss", "metrics", "nle", "ops", "parallel", "train", "utils",
            "HipLibraryMissing", "HipKernelError"]

@@ -57,7 +57,8 @@ SIGNATURES = {
     "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P, _P, _P],                  # .., cmap, tslope, stream
     "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_tangent_forward": [_G, _I] + [_P] * 10 + [ctypes.c_size_t, _P],
-    "cdl_tangent_backward": [_G, _I] + [_P] * 15 + [ctypes.c_size_t, _P],
+    "cdl_tangent_backward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P],      # .., g_xp, g_zd, dA, ..
+    "cdl_csr_tangent_forward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P],
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_mad_cells": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _I, _P],
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
@@ -69,6 +70,9 @@ SIGNATURES = {
     "cdl_residual_backward": [_G] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_prox_csr": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_prox_csr_bwd": [_G] + [_P] * 15 + [ctypes.c_size_t, _P],
+    "cdl_prox_csr_tangent": [_G] + [_P] * 11,
+    "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11,
+    "cdl_analysis_prox_tangent_ws": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_project_filters": [_P, _I, _I, _P],
     "cdl_project_filter_banks": [_P, _I, _I, _I, _P],
     "cdl_gabor_filters": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -87,6 +87,27 @@ __device__ __forceinline__ cdl_prox2 cdl_prox_csr2(float u, float zp, float za, 
     return p;
 }
 
+// d ST(x,t) / dx as autograd sees sign(x) * relu(|x| - t) (sign has zero gradient): the gate of the reverse pass
+// (k_prox_bwd) and of the tangent below.
+__device__ __forceinline__ bool cdl_st_dx(float x, float t) { return x != 0.0f && fabsf(x) - t > 0.0f; }
+
+// Tangents of the two maps at the primal's intermediates (the pointwise pass of cdl_prox.hip): the
+// maps are piecewise linear in (u, zp, za), so the derivative along (ud, zpd, zad) is a nest of gates.  Selects, not
+// products with 0 / 1: a NaN in a dead branch stays there, and (x - zad) + zad is never formed.  No threshold enters a
+// value.  The transposes are k_prox_bwd's: gu = Gm Ga g, gzp += Gm (1 - Ga) g; resp. gu = Gm Gb Ga g, gzp -= Gm Gb Ga g, gza += Gm (1 - Gb) g.
+__device__ __forceinline__ float cdl_prox_csr1_tangent(const cdl_prox1 &p, float lam, float ud, float zpd)
+{
+    const bool Ga = cdl_st_dx(p.a, p.tg), Gm = cdl_st_dx(p.m, lam);
+    return Gm ? (Ga ? ud : zpd) : 0.0f;
+}
+
+__device__ __forceinline__ float cdl_prox_csr2_tangent(const cdl_prox2 &p, float lam, float ud, float zpd, float zad)
+{
+#pragma clang fp contract(off)
+    const bool Ga = cdl_st_dx(p.a, p.t1), Gb = cdl_st_dx(p.b, p.t2), Gm = cdl_st_dx(p.m, lam);
+    return Gm ? (Gb ? (Ga ? ud - zpd : 0.0f) : zad) : 0.0f;
+}
+
 // Optional CSR epilogue of the analysis kernels: out = prox(u; zp[, za]) and, for training, u itself.
 struct cdl_prox_args {
     const float *zp, *za, *lam, *g1, *g2;   // zp == nullptr: epilogue off

@@ -842,6 +842,30 @@ int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, floa
     return analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, px, workspace, workspace_floats, stream);
 }
 
+int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+                              const float *u, const float *z_prev, const float *z_after, const float *lam,
+                              const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
+                              float *out, void *stream)
+{
+    return cdl_analysis_prox_tangent_ws(g, x, w, alpha, zin, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out,
+                                        nullptr, 0, stream);
+}
+
+int cdl_analysis_prox_tangent_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+                                 const float *u, const float *z_prev, const float *z_after, const float *lam,
+                                 const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
+                                 float *out, float *workspace, size_t workspace_floats, void *stream)
+{
+    if (!u || !z_prev || !lam || !gam1) return CDL_EINVAL;
+    if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
+    if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
+    // Two launches: the analysis writes ud into `out`, the pointwise tangent rewrites it in place.  (The tangent as a branch
+    // of the kernels' CSR epilogue cost the PRIMAL epilogue scalar-register spills: DESIGN.md section 22.)
+    const int rc = analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, workspace, workspace_floats, stream);
+    if (rc) return rc;
+    return cdl_prox_csr_tangent(g, out, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, stream);
+}
+
 static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                          const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
                          size_t ws_floats, void *stream, const cdl_map_args &mp)

@@ -14,7 +14,8 @@ namespace {
 __device__ __forceinline__ float sgn(float x) { return cdl_sgn(x); }
 
 // d ST(x,t) / dx and d ST(x,t) / dt as autograd sees sign(x) * relu(|x| - t)  (sign has zero gradient)
-__device__ __forceinline__ float st_dx(float x, float t) { return (x != 0.0f && fabsf(x) - t > 0.0f) ? 1.0f : 0.0f; }
+// (the gate itself, cdl_st_dx, lives in cdl_common.h beside the tangents of the two maps)
+__device__ __forceinline__ float st_dx(float x, float t) { return cdl_st_dx(x, t) ? 1.0f : 0.0f; }
 __device__ __forceinline__ float st_dt(float x, float t) { return (fabsf(x) - t > 0.0f) ? -sgn(x) : 0.0f; }
 
 using Prox1 = cdl_prox1;
@@ -25,15 +26,28 @@ __device__ __forceinline__ Prox2 prox2(float u, float zp, float za, float lam, f
     return cdl_prox_csr2(u, zp, za, lam, g1, g2);
 }
 
-__global__ __launch_bounds__(256) void k_prox_fwd(const float *__restrict__ u, const float *__restrict__ zp,
-                                                  const float *__restrict__ za, const float *__restrict__ lam,
-                                                  const float *__restrict__ g1, const float *__restrict__ g2,
-                                                  float *__restrict__ out, size_t total, size_t per_m)
+// The map itself (up == nullptr: in = u, out = prox(u; zp[, za])) or its tangent at the primal (up, zp[, za]) along
+// (in = ud, zpd, zad; a null neighbour tangent is a zero one): one kernel, one launch site (launch_prox).  out may alias in
+// (each thread reads its element before it writes it).
+__global__ __launch_bounds__(256) void k_prox_fwd(const float *in, const float *__restrict__ up,
+                                                  const float *__restrict__ zp, const float *__restrict__ za,
+                                                  const float *__restrict__ lam, const float *__restrict__ g1,
+                                                  const float *__restrict__ g2, const float *__restrict__ zpd,
+                                                  const float *__restrict__ zad, float *out, size_t total, size_t per_m)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / per_m;
-    out[i] = za ? prox2(u[i], zp[i], za[i], lam[row], g1[row], g2[row]).z : prox1(u[i], zp[i], lam[row], g1[row]).z;
+    if (!up) {
+        out[i] = za ? prox2(in[i], zp[i], za[i], lam[row], g1[row], g2[row]).z : prox1(in[i], zp[i], lam[row], g1[row]).z;
+        return;
+    }
+    const float ud = in[i], l = lam[row], dp = zpd ? zpd[i] : 0.0f;
+    if (!za) {
+        out[i] = cdl_prox_csr1_tangent(prox1(up[i], zp[i], l, g1[row]), l, ud, dp);
+        return;
+    }
+    out[i] = cdl_prox_csr2_tangent(prox2(up[i], zp[i], za[i], l, g1[row], g2[row]), l, ud, dp, zad ? zad[i] : 0.0f);
 }
 
 // Reverse of the map for one (row, split): gu, the neighbour-code gradients (accumulated: a neighbour
@@ -134,16 +148,33 @@ size_t code_elems(const cdl_geom *g) { return (size_t)(g->D / g->sd) * (g->H / g
 
 extern "C" {
 
+static int launch_prox(const cdl_geom *g, const float *in, const float *up, const float *z_prev, const float *z_after,
+                       const float *lam, const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
+                       float *out, void *stream)
+{
+    const size_t per_m = code_elems(g), total = (size_t)g->N * g->M * per_m;
+    k_prox_fwd<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(in, up, z_prev, z_after, lam, gam1, gam2, zd_prev,
+                                                                         zd_after, out, total, per_m);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
 int cdl_prox_csr(const cdl_geom *g, const float *u, const float *z_prev, const float *z_after, const float *lam,
                  const float *gam1, const float *gam2, float *out, void *stream)
 {
     if (!cdl_geom_ok(g) || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
     if (z_after && !gam2) return CDL_EINVAL;
-    const size_t per_m = code_elems(g), total = (size_t)g->N * g->M * per_m;
-    k_prox_fwd<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(u, z_prev, z_after, lam, gam1, gam2, out,
-                                                                         total, per_m);
-    CDL_LAUNCH_CHECK();
-    return 0;
+    return launch_prox(g, u, nullptr, z_prev, z_after, lam, gam1, gam2, nullptr, nullptr, out, stream);
+}
+
+int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, const float *z_prev, const float *z_after,
+                         const float *lam, const float *gam1, const float *gam2, const float *zd_prev,
+                         const float *zd_after, float *out, void *stream)
+{
+    if (!cdl_geom_ok(g) || !ud || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
+    if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
+    if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
+    return launch_prox(g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, stream);
 }
 
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g)

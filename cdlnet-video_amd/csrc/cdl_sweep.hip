@@ -171,11 +171,12 @@ int cdl_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *
 
 /* Reverse sweep of the tangent net (linear in vp with the gates fixed): the launches of cdl_ista_backward's plain branch
  * with the supports taken from the primal codes zgate and the operands from the tangent sweep (zd, rd, vp); no threshold
- * gradient leaves it (dt_scratch, 2*M floats) and no data gradient is formed.  g_xp = dL/dxdp. */
+ * gradient leaves it (dt_scratch, 2*M floats) and no data gradient is formed.  g_xp = dL/dxdp, g_zd (nullable) = dL/dzd_K. */
 int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float *mask, const float *const *wA,
                          const float *const *wB, const float *const *zgate, const float *const *zd,
-                         const float *const *rd, const float *g_xp, float *const *dA, float *const *dB, float *gbuf0,
-                         float *gbuf1, float *q, float *dt_scratch, float *scratch, size_t scratch_floats, void *stream)
+                         const float *const *rd, const float *g_xp, const float *g_zd, float *const *dA, float *const *dB,
+                         float *gbuf0, float *gbuf1, float *q, float *dt_scratch, float *scratch, size_t scratch_floats,
+                         void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !vp || !wA || !wB || !zgate || !zd || !g_xp || !dA || !dB || !gbuf0 || !gbuf1 || !q ||
         !dt_scratch || !scratch || (K > 1 && !rd))
@@ -184,8 +185,8 @@ int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float 
     const size_t M = g->M;
     float *gk = gbuf0, *other = gbuf1;
     CDL_TRY(cdl_wgrad(g, zd[K - 1], nullptr, g_xp, 1.0f, dB[0], scratch, scratch_floats, stream));
-    CDL_TRY(cdl_analysis_rev_ws(g, g_xp, wB[0], 1.0f, nullptr, zgate[K - 1], nullptr, dt_scratch, dt_scratch + M, nullptr, gk,
-                                scratch, scratch_floats, nullptr, stream));
+    CDL_TRY(cdl_analysis_rev_ws(g, g_xp, wB[0], 1.0f, g_zd, zgate[K - 1], nullptr, dt_scratch, dt_scratch + M, nullptr, gk,
+                                scratch, scratch_floats, nullptr, stream));          // B_0^T g_xp (+ g_zd), gated
     for (int k = K - 1; k >= 1; --k) {                          // gk = du_k, gated
         CDL_TRY(cdl_synthesis_ws(g, gk, nullptr, wA[k], -1.0f, mask, nullptr, q, scratch, scratch_floats, stream));
         CDL_TRY(cdl_wgrad_pair(g, gk, rd[k - 1], -1.0f, dA[k], zd[k - 1], q, 1.0f, dB[k], scratch, scratch_floats, stream));
@@ -196,6 +197,40 @@ int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float 
         other = t;
     }
     return cdl_wgrad(g, gk, nullptr, vp, 1.0f, dA[0], scratch, scratch_floats, stream);
+}
+
+/* Forward-mode tangent of the CSR loop at the primal's gates: the proximal maps are piecewise linear
+ * in (u, z_prev, z_after), so with u[k] = u_k of the primal (what cdl_ista_forward kept) and Jprox_k the gate nest of
+ * cdl_prox_csr1_tangent / cdl_prox_csr2_tangent read off (u_k, z_prev, z_after, lam_k, gam*_k),
+ *   ud_0 = A_0 vp,   rd_k = mask B_k zd_k - vp,   ud_k = zd_k - A_k rd_k,   zd_{k+1} = Jprox_k(ud_k; zd_prev, zd_after),
+ *   xdp = B_0 zd_K.
+ * Per iteration cdl_synthesis_ws and cdl_analysis_prox_tangent_ws (the analysis, then the pointwise tangent in place).  zd_prev / zd_after
+ * (nullable): the neighbours' tangents, NULL = a constant neighbour.  zd: K code buffers, rd: K-1 thin ones (consecutive
+ * entries differ; two each suffice when nothing is kept).  Its reverse sweep is cdl_ista_backward's CSR branch with
+ * yp -> vp, z -> zd, r -> rd, the primal's u / lam / gam*, c = NULL and the threshold outputs discarded. */
+int cdl_csr_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask, const float *z_prev,
+                            const float *z_after, const float *lam, const float *gam1, const float *gam2,
+                            const float *zd_prev, const float *zd_after, const float *const *wA, const float *const *wB,
+                            const float *const *u, float *const *zd, float *const *rd, float *xdp, float *scratch,
+                            size_t scratch_floats, void *stream)
+{
+    if (!cdl_geom_ok(g) || K < 1 || !vp || !z_prev || !lam || !gam1 || !wA || !wB || !u || !zd || !xdp || (K > 1 && !rd))
+        return CDL_EINVAL;
+    if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
+    const size_t NM = (size_t)g->N * g->M;
+    for (int k = 0; k < K; ++k) {
+        const float *zin = nullptr, *x = vp;
+        if (k > 0) {
+            CDL_TRY(cdl_synthesis_ws(g, zd[k - 1], nullptr, wB[k], 1.0f, mask, vp, rd[k - 1], scratch, scratch_floats,
+                                     stream));
+            zin = zd[k - 1];
+            x = rd[k - 1];
+        }
+        CDL_TRY(cdl_analysis_prox_tangent_ws(g, x, wA[k], k == 0 ? 1.0f : -1.0f, zin, u[k], z_prev, z_after, lam + k * NM,
+                                             gam1 + k * NM, gam2 ? gam2 + k * NM : nullptr, zd_prev, zd_after, zd[k],
+                                             scratch, scratch_floats, stream));
+    }
+    return cdl_synthesis_ws(g, zd[K - 1], nullptr, wB[0], 1.0f, nullptr, nullptr, xdp, scratch, scratch_floats, stream);
 }
 
 }  // extern "C"

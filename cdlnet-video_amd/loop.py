@@ -442,9 +442,9 @@ class UnrolledISTA(torch.autograd.Function):
 #     zd_1 = G_0 A_0 vp      rd_k = mask B_k zd_k - vp      zd_{k+1} = G_k (zd_k - A_k rd_k)      xdot = post(B_0 zd_K)
 # (vp, the mean added back: preprocess(v)).  No threshold appears.  The tangent net is linear, so its reverse sweep is the
 # primal's with codes -> zd, residuals -> rd, yp -> vp, the PRIMAL's gates, and no threshold / data gradient.
-def _tangent_generic(g, vp, mask_p, A, B, gates, keep):
-    """Whole generic tangent sweep from one C call (cdl_tangent_forward): (xdp, zd, rd)."""
-    return ops.tangent_forward(g, vp, mask_p, A, B, gates, keep)
+def _tangent_generic(g, vp, mask_p, A, B, gates, keep, last=False):
+    """Whole generic tangent sweep from one C call (cdl_tangent_forward): (xdp, zd, rd); `last`: see ops.tangent_forward."""
+    return ops.tangent_forward(g, vp, mask_p, A, B, gates, keep, last=last)
 
 
 def _tangent_generic_stepwise(g, vp, mask_p, A, B, gates, keep):
@@ -463,17 +463,17 @@ def _tangent_generic_stepwise(g, vp, mask_p, A, B, gates, keep):
     return xdp, (zd if keep else []), (rd if keep else [])
 
 
-def _tangent_backward_generic(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp):
+def _tangent_backward_generic(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp, g_zd=None):
     """Reverse sweep of the generic tangent sweep from one C call (cdl_tangent_backward): (dA, dB)."""
-    return ops.tangent_backward(g, vp, mask_p, list(A), list(B), list(gates), list(zd), list(rd), g_xp)
+    return ops.tangent_backward(g, vp, mask_p, list(A), list(B), list(gates), list(zd), list(rd), g_xp, g_zd)
 
 
-def _tangent_backward_generic_stepwise(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp):
+def _tangent_backward_generic_stepwise(g, K, vp, mask_p, A, B, gates, zd, rd, g_xp, g_zd=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
     dA, dB = [None] * K, [None] * K
     dts = torch.empty(2 * g.M, device=vp.device, dtype=torch.float32)
     dB[0] = ops.wgrad(g, zd[K - 1], g_xp, 1.0)
-    gk = ops.analysis_rev(g, g_xp, B[0], 1.0, None, gates[K - 1], None, dts)
+    gk = ops.analysis_rev(g, g_xp, B[0], 1.0, g_zd, gates[K - 1], None, dts)
     for k in range(K - 1, 0, -1):
         q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
         dA[k], dB[k] = ops.wgrad_pair(g, gk, rd[k - 1], -1.0, zd[k - 1], q, 1.0)
@@ -482,11 +482,11 @@ def _tangent_backward_generic_stepwise(g, K, vp, mask_p, A, B, gates, zd, rd, g_
     return dA, dB
 
 
-def _tangent_fused(g, vp, mask_p, A, B, maps, keep, layout=None, precision=None):
+def _tangent_fused(g, vp, mask_p, A, B, maps, keep, layout=None, precision=None, last=False):
     """Whole tangent sweep on the fused 2-D kernels from one C call (cdl_fused2d_tangent): per iteration one reverse-stage
     launch with the forward's prepared pair and the primal's bit map, and one assemble.  Returns (xdp, zd, nrd): nrd are
     the NEGATED residuals -rd_k (the stages' thin operand)."""
-    return ops.fused_tangent(g, vp, mask_p, A, B, maps, keep, precision or PRECISION, layout or CODE_LAYOUT)
+    return ops.fused_tangent(g, vp, mask_p, A, B, maps, keep, precision or PRECISION, layout or CODE_LAYOUT, last=last)
 
 
 def _tangent_fused_stepwise(g, vp, mask_p, A, B, maps, keep, layout="nchw", precision=None):
@@ -510,9 +510,9 @@ def _tangent_fused_stepwise(g, vp, mask_p, A, B, maps, keep, layout="nchw", prec
     return xdp, (zd if keep else []), (nrd if keep else [])
 
 
-def _tangent_fusedg(g, vp, mask_p, A, B, maps, keep):
+def _tangent_fusedg(g, vp, mask_p, A, B, maps, keep, last=False):
     """cdl_fusedg_tangent: the same construction on the tile / strip kernels (codes in the reference's layout)."""
-    return ops.fusedg_tangent(g, vp, mask_p, A, B, maps, keep)
+    return ops.fusedg_tangent(g, vp, mask_p, A, B, maps, keep, last=last)
 
 
 def _negate_dA_tail(dA):
@@ -524,7 +524,9 @@ def _negate_dA_tail(dA):
 class TangentISTA(torch.autograd.Function):
     """(y, v, mask, c, t, A_0..A_{K-1}, B_0..B_{K-1}) -> (xhat, xdot): the primal of UnrolledISTA and its directional
     derivative in y along v at the primal's supports.  The tangent follows the primal's tier (fused 2-D / fused generic /
-    generic).  Gradients for t (from xhat alone) and both filter banks (the sum of the two reverse sweeps)."""
+    generic).  Gradients for t (from xhat alone) and both filter banks (the sum of the two reverse sweeps).
+    With cfg["codes"] (the no-neighbour branch of the CSR nets' jvp_recurrent) the outputs are (xhat, xdot, z_K, zd_K) and
+    the reverse sweeps take the codes' upstream gradients as well."""
 
     @staticmethod
     def forward(ctx, y, v, mask, c, t, cfg, *weights):
@@ -545,6 +547,7 @@ class TangentISTA(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         _no_data_gradients(ctx, ((0, "y"), (1, "v"), (2, "mask"), (3, "sigma")))
         keep = any(ctx.needs_input_grad)
+        want_codes = cfg.get("codes", False)
         auto = BACKEND == "auto" and not ctx.exact and not ctx.is_map
         ctx.fused = auto and ops.fused_supported(g)
         ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
@@ -552,15 +555,18 @@ class TangentISTA(torch.autograd.Function):
             ctx.layout, ctx.precision = CODE_LAYOUT, PRECISION        # net.jvp refuses blocked_bf16; so does the C sweep
             xp, z, codes, resid, maps = ops.fused_forward(g, yp, mask_p, tau, A, B, keep, PRECISION, ctx.layout,
                                                           keep_maps=True)
-            xdp, zd, rd = _tangent_fused(g, vp, mask_p, A, B, maps, keep, ctx.layout, ctx.precision)
+            xdp, zd, rd = _tangent_fused(g, vp, mask_p, A, B, maps, keep, ctx.layout, ctx.precision, last=want_codes)
         elif ctx.fusedg:
             ctx.layout = "nchw"
             xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, ctx.layout, keep_maps=True)
-            xdp, zd, rd = _tangent_fusedg(g, vp, mask_p, A, B, maps, keep)
+            xdp, zd, rd = _tangent_fusedg(g, vp, mask_p, A, B, maps, keep, last=want_codes)
         else:                                          # the gates are the primal's codes: all K are kept
             xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, True, keep,
                                                          **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
-            xdp, zd, rd = _tangent_generic(g, vp, mask_p, A, B, codes, keep)
+            xdp, zd, rd = _tangent_generic(g, vp, mask_p, A, B, codes, keep, last=want_codes)
+        zdK = zd[-1] if want_codes else None           # (N,M,..) on every tier; the ping-pong table's last when nothing is kept
+        if not keep:
+            zd = []
         xhat = ops.postprocess(xp, mean, pads)
         xdot = ops.postprocess(xdp, vmean, pads)
 
@@ -571,10 +577,10 @@ class TangentISTA(torch.autograd.Function):
             ctx.n_maps = len(maps)
             ctx.save_for_backward(yp, vp, mask_p if mask_p is not None else empty, c if c is not None else empty, t,
                                   *weights, *codes, *resid, *zd, *rd, *maps)
-        return xhat, xdot
+        return (xhat, xdot, z, zdK) if want_codes else (xhat, xdot)
 
     @staticmethod
-    def backward(ctx, g_xhat, g_xdot):
+    def backward(ctx, g_xhat, g_xdot, g_z=None, g_zd=None):
         K, g = ctx.K, ctx.geom
         sv = ctx.saved_tensors
         yp, vp, mask_p, c, t = sv[:5]
@@ -592,32 +598,35 @@ class TangentISTA(torch.autograd.Function):
         dev = yp.device
         dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
         dA = dB = None
-        if g_xhat is not None:                         # the primal's reverse sweep, as UnrolledISTA runs it
-            g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads)
+        g_z = g_z.contiguous() if g_z is not None else None
+        g_zd = g_zd.contiguous() if g_zd is not None else None
+        if g_xhat is not None or g_z is not None:      # the primal's reverse sweep, as UnrolledISTA runs it
+            g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
             if ctx.fusedg:
-                dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt, maps=maps,
+                dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
                                           layout=ctx.layout)
             elif ctx.fused:
-                dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt, maps=maps,
+                dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
                                          layout=ctx.layout, precision=ctx.precision)
             elif ctx.is_map:
-                dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, None, dt, cmap=c,
+                dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, g_z, dt, cmap=c,
                                            tslope=t.detach().reshape(K, 2, g.M)[:, 1].contiguous())
             else:
-                dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, None, dt)
-        if g_xdot is not None:                         # the tangent's: same sweep, other operands, the primal's gates
-            g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads)
+                dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt)
+        if g_xdot is not None or g_zd is not None:     # the tangent's: same sweep, other operands, the primal's gates
+            g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads) if g_xdot is not None else None
             scratch = torch.empty_like(dt)             # its threshold output: never returned
             if ctx.fusedg:
-                tA, tB = _backward_fusedg(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, None, scratch, maps=maps,
+                tA, tB = _backward_fusedg(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, scratch, maps=maps,
                                           layout=ctx.layout)
                 tA = _negate_dA_tail(tA)
             elif ctx.fused:
-                tA, tB = _backward_fused(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, None, scratch, maps=maps,
+                tA, tB = _backward_fused(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, scratch, maps=maps,
                                          layout=ctx.layout, precision=ctx.precision)
                 tA = _negate_dA_tail(tA)
-            else:
-                tA, tB = _tangent_backward_generic(g, K, vp, mask_p, A, B, codes, zd, rd, g_xdp)
+            else:                                      # (a loss on zd_K alone: a zero image gradient to the sweep)
+                tA, tB = _tangent_backward_generic(g, K, vp, mask_p, A, B, codes, zd, rd,
+                                                   g_xdp if g_xdp is not None else torch.zeros_like(vp), g_zd)
             if dA is None:
                 dA, dB = tA, tB
             else:
@@ -730,6 +739,160 @@ class TemporalISTA(torch.autograd.Function):
                                        dt, list(us), zp, za, lam, gam1, gam2, dg1, dg2, gzp, gza)
         _queue_backward_end()
         return (None, None, None, gzp, gza, dt.reshape(t.shape), dg1.reshape(g1.shape),
+                dg2.reshape(g2.shape) if dg2 is not None else None, None, *dA, *dB)
+
+
+def _backward_csr(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1, dg2, gzp, gza):
+    """Reverse sweep of the CSR loop from one C call (cdl_ista_backward's CSR branch): (dA, dB); fills dt, dg1[, dg2] and
+    accumulates into gzp / gza (nullable)."""
+    return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, list(us), zp, za,
+                             lam, gam1, gam2, dg1, dg2, gzp, gza)
+
+
+def _backward_csr_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1, dg2,
+                           gzp, gza):
+    """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
+    dA, dB = [None] * K, [None] * K
+    if g_xp is not None:
+        dB[0] = ops.wgrad(g, codes[K - 1], g_xp, 1.0)
+        gk = ops.analysis(g, g_xp, B[0], 1.0, g_z, None, None)       # B_0^T g_xp (+ g_z)
+    else:
+        dB[0] = torch.zeros_like(B[0])
+        gk = g_z.clone()
+    for k in range(K - 1, -1, -1):                                   # gk: dL/dz_{k+1} -> dL/du_k in place
+        ops.prox_csr_bwd(g, gk, us[k], zp, lam[k], gam1[k], c, dt[k], dg1[k], za, gam2[k] if za is not None else None,
+                         dg2[k] if za is not None else None, gzp, gza, out=gk)
+        if k == 0:
+            break
+        q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
+        dA[k], dB[k] = ops.wgrad_pair(g, gk, resid[k - 1], -1.0, codes[k - 1], q, 1.0)
+        gk = ops.analysis(g, q, B[k], 1.0, gk, None, None)
+    dA[0] = ops.wgrad(g, gk, yp, 1.0)
+    return dA, dB
+
+
+# ------------------------------------------------------------------------------------------
+# Forward-mode tangent of the CSR loop (DESIGN.md section 22).  prox_CSR / prox_CSR_f2 are piecewise linear in (u, z_prev,
+# z_after): at the primal's gates (read off u_k, the neighbour codes and the thresholds; ops.prox_csr_tangent) a direction
+# (v, zd_prev, zd_after) in (y, z_prev, z_after) propagates through
+#     ud_0 = A_0 vp     rd_k = mask B_k zd_k - vp     ud_k = zd_k - A_k rd_k     zd_{k+1} = Jprox_k(ud_k; zd_prev, zd_after)
+#     xdot = post(B_0 zd_K)
+# with no threshold in any value.  The tangent net is linear in (vp, zd_prev, zd_after), and the transpose of Jprox_k is
+# what cdl_prox_csr_bwd applies, so its reverse sweep is the primal's (_backward_csr) with yp -> vp, codes -> zd,
+# residuals -> rd and the PRIMAL's u_k, neighbour codes and thresholds: it yields the filter gradients and
+# dL/dzd_prev, dL/dzd_after; its threshold sums are discarded (the gates are piecewise constant).
+def _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep):
+    """Whole CSR tangent sweep from one C call (cdl_csr_tangent_forward): (xdp, zd_K, zd, rd)."""
+    return ops.csr_tangent_forward(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep)
+
+
+def _tangent_csr_stepwise(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep):
+    """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
+    K = len(A)
+    g2 = (lambda k: gam2[k]) if za is not None else (lambda k: None)
+    zd, rd = [], []
+    z = ops.analysis_prox_tangent(g, vp, A[0], 1.0, None, us[0], zp, lam[0], gam1[0], za, g2(0), zdp, zda)
+    zd.append(z)
+    for k in range(1, K):
+        r = ops.synthesis(g, z, B[k], 1.0, None, mask_p, vp)
+        z = ops.analysis_prox_tangent(g, r, A[k], -1.0, z, us[k], zp, lam[k], gam1[k], za, g2(k), zdp, zda)
+        zd.append(z)
+        rd.append(r)
+    xdp = ops.synthesis(g, z, B[0], 1.0)
+    return xdp, z, (zd if keep else []), (rd if keep else [])
+
+
+def _tangent_backward_csr(g, K, vp, mask_p, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, gzdp, gzda,
+                          sweep=_backward_csr):
+    """Reverse sweep of the CSR tangent sweep: (dA, dB), accumulating dL/dzd_prev, dL/dzd_after into gzdp / gzda (nullable).
+    `sweep`: _backward_csr (one C call) or _backward_csr_stepwise."""
+    sink = torch.empty((3, K, 2, g.M), device=vp.device, dtype=torch.float32)       # threshold sums nobody reads
+    return sweep(g, K, vp, mask_p, None, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, sink[0], sink[1],
+                 sink[2] if za is not None else None, gzdp, gzda)
+
+
+@_arithmetic_aware
+class TangentTemporalISTA(torch.autograd.Function):
+    """(y, v, mask, c, z_prev, zd_prev|None, z_after|None, zd_after|None, t, g1, g2|None, A.., B..) -> (xhat, xdot, z_K, zd_K):
+    the primal of TemporalISTA and its derivative along (v, zd_prev, zd_after) at the primal's gates.  Gradients for the
+    neighbour codes and the three threshold families (from xhat and z_K alone), for the neighbour tangents (from xdot and zd_K
+    alone) and for both filter banks (the sum of the two reverse sweeps)."""
+
+    @staticmethod
+    def forward(ctx, y, v, mask, c, zp, zdp, za, zda, t, g1, g2, cfg, *weights):
+        K, s = cfg["K"], cfg["s"]
+        A, B = weights[:K], weights[K:]
+        yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
+        vp, vmean, _, _ = ops.preprocess(v, s, mask)          # linear: the same mean rule, mask and reflect pad
+        N, C = yp.shape[:2]
+        P = tuple(A[0].shape[2:])
+        nd = yp.dim() - 2
+        g = ops.Geometry.make(N, C, A[0].shape[0], yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        for name, x in (("z_prev", zp), ("zdot_prev", zdp), ("z_after", za), ("zdot_after", zda)):
+            if x is not None and tuple(x.shape) != g.code_shape():
+                raise ValueError(f"{name}: shape {tuple(x.shape)} does not match this frame's code shape {g.code_shape()}")
+        zp, zdp, za, zda = (x.contiguous() if x is not None else None for x in (zp, zdp, za, zda))
+        lam, gam1 = ops.thresholds(t, c, N), ops.thresholds(g1, c, N)
+        gam2 = ops.thresholds(g2, c, N) if za is not None else None
+        ctx.set_materialize_grads(False)
+        _no_data_gradients(ctx, ((0, "y"), (1, "v"), (2, "mask"), (3, "sigma")))
+        keep = any(ctx.needs_input_grad)
+        # the gates are read off the primal's u_k: all K are kept whatever `keep` says
+        xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, True)
+        xdp, zdK, zd, rd = _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep)
+        xhat = ops.postprocess(xp, mean, pads)
+        xdot = ops.postprocess(xdp, vmean, pads)
+        ctx.geom, ctx.pads, ctx.K = g, pads, K
+        ctx.has_mask, ctx.has_c, ctx.has_after = mask_p is not None, c is not None, za is not None
+        if keep:
+            e = yp.new_empty(0)
+            ctx.save_for_backward(yp, vp, mask_p if mask_p is not None else e, c if c is not None else e, zp,
+                                  za if za is not None else e, t, g1, g2 if za is not None else e, lam, gam1,
+                                  gam2 if za is not None else e, *weights, *us, *codes, *resid, *zd, *rd)
+        return xhat, xdot, z, zdK
+
+    @staticmethod
+    def backward(ctx, g_xhat, g_xdot, g_z, g_zd):
+        K, g = ctx.K, ctx.geom
+        sv = ctx.saved_tensors
+        yp, vp, mask_p, c, zp, za, t, g1, g2, lam, gam1, gam2 = sv[:12]
+        mask_p = mask_p if ctx.has_mask else None
+        c = c if ctx.has_c else None
+        za, gam2 = (za, gam2) if ctx.has_after else (None, None)
+        o = 12
+        A, B = sv[o:o + K], sv[o + K:o + 2 * K]
+        o += 2 * K
+        us, codes, resid = sv[o:o + K], sv[o + K:o + 2 * K], sv[o + 2 * K:o + 3 * K - 1]
+        o += 3 * K - 1
+        zd, rd = sv[o:o + K], sv[o + K:o + 2 * K - 1]
+        dev = yp.device
+        dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
+        dg1 = torch.zeros_like(dt)
+        dg2 = torch.zeros_like(dt) if za is not None else None
+        need = ctx.needs_input_grad
+        new = lambda want: torch.zeros_like(zp) if want else None
+        gzp, gzdp = new(need[4]), new(need[5])
+        gza, gzda = new(za is not None and need[6]), new(za is not None and need[7])
+        g_z = g_z.contiguous() if g_z is not None else None
+        g_zd = g_zd.contiguous() if g_zd is not None else None
+        dA = dB = None
+        if g_xhat is not None or g_z is not None:      # the primal's reverse sweep, as TemporalISTA runs it
+            g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
+            dA, dB = _backward_csr(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1,
+                                   dg2, gzp, gza)
+        if g_xdot is not None or g_zd is not None:     # the tangent's: same sweep, other operands, the primal's gates
+            g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads) if g_xdot is not None else None
+            tA, tB = _tangent_backward_csr(g, K, vp, mask_p, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, gzdp,
+                                           gzda)
+            if dA is None:
+                dA, dB = tA, tB
+            else:
+                dA = [a + b for a, b in zip(dA, tA)]
+                dB = [a + b for a, b in zip(dB, tB)]
+        if dA is None:
+            dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+        _queue_backward_end()
+        return (None, None, None, None, gzp, gzdp, gza, gzda, dt.reshape(t.shape), dg1.reshape(g1.shape),
                 dg2.reshape(g2.shape) if dg2 is not None else None, None, *dA, *dB)
 
 
@@ -846,10 +1009,16 @@ def run_csr(y, mask, c, z_prev, z_after, t, g1, g2, A, B, s):
     return TemporalISTA.apply(y, mask, c, z_prev, z_after, t, g1, g2, cfg, *A, *B)
 
 
-def run_tangent(y, v, mask, c, t, A, B, s):
-    """Front end of net.jvp: (xhat, xdot)."""
-    cfg = {"K": len(A), "s": int(s)}
+def run_tangent(y, v, mask, c, t, A, B, s, codes=False):
+    """Front end of net.jvp: (xhat, xdot); with `codes` (jvp_recurrent without a neighbour) (xhat, xdot, z_K, zd_K)."""
+    cfg = {"K": len(A), "s": int(s), "codes": bool(codes)}
     return TangentISTA.apply(y, v, mask, c, t, cfg, *A, *B)
+
+
+def run_csr_tangent(y, v, mask, c, z_prev, zd_prev, z_after, zd_after, t, g1, g2, A, B, s):
+    """Front end of the neighbour branches of jvp_recurrent: (xhat, xdot, z_K, zd_K)."""
+    cfg = {"K": len(A), "s": int(s)}
+    return TangentTemporalISTA.apply(y, v, mask, c, z_prev, zd_prev, z_after, zd_after, t, g1, g2, cfg, *A, *B)
 
 
 def run(y, mask, c, t, A, B, s, all_codes=False):

@@ -290,7 +290,33 @@ class _CSRBase(_ISTANet):
         ops.project_filter_banks_([m.weight.data for m in self.A] + [m.weight.data for m in self.B])
 
     def _jvp_refusal(self):
-        return "the CSR nets' proximal maps have no tangent sweep"
+        return ("the CSR nets take neighbour codes, which jvp(y, v) cannot carry; their tangent sweep is "
+                "jvp_recurrent(y, v, z_prev, zdot_prev, ...)")
+
+    def _prep_tangent(self, y, v, sigma, mask, pairs):
+        """Argument checks of jvp_recurrent: forward's (_prep) and jvp's, and each neighbour tangent with its code."""
+        name = type(self).__name__
+        if not torch.is_tensor(v):
+            raise TypeError("jvp_recurrent: v must be a tensor shaped like y")
+        for label, code, dot in pairs:
+            if dot is not None and code is None:
+                raise ValueError(f"jvp_recurrent: zdot_{label} given without z_{label} (a tangent belongs to a code)")
+        for label, x in (("y", y), ("v", v)):
+            if not x.is_cuda:
+                raise RuntimeError(
+                    f"{name}.jvp_recurrent: {label} is on {x.device}. This package has no CPU "
+                    "compute path; the iterations run in HIP kernels on a ROCm device.")
+        if tuple(v.shape) != tuple(y.shape):
+            raise ValueError(f"jvp_recurrent: v has shape {tuple(v.shape)}, y has {tuple(y.shape)}")
+        for label, x in (("v", v), ("y", y), ("sigma", sigma), ("mask", mask)):
+            if torch.is_tensor(x) and x.requires_grad:
+                raise NotImplementedError(f"cdlnet_video_amd: {name}.jvp_recurrent: `{label}` requires grad; the tangent sweep "
+                                          "returns parameter and neighbour-code gradients only (detach() it)")
+        if loop.CODE_LAYOUT == "blocked_bf16":
+            raise NotImplementedError("cdlnet_video_amd: jvp_recurrent with set_code_layout('blocked_bf16') is not "
+                                      "implemented (tangent codes are stored in fp32)")
+        y, mask_t, c = self._prep(y, sigma, mask)
+        return y, v.to(torch.float32), mask_t, c
 
     def _prep(self, y, sigma, mask):
         if not y.is_cuda:
@@ -340,6 +366,20 @@ class CDLNet_CSR(_CSRBase):
         A, B = self._filters()
         return loop.run_csr(y, mask_t, c, z_prev, None, self.t, self.g, None, A, B, self.s)
 
+    def jvp_recurrent(self, y, v, z_prev=None, zdot_prev=None, sigma=None, mask=1):
+        """(xhat, xdot, z, zdot): forward(y, z_prev, sigma, mask) and the derivative of (xhat, z) along (v, zdot_prev) in
+        (y, z_prev), at the gates of the primal's proximal maps (where the net is affine in both: the derivative autograd of
+        the reference gives).  zdot_prev None: a constant neighbour.  All four are differentiable in
+        the parameters and in z_prev / zdot_prev, so the calls of a clip chain; the thresholds get their gradient through
+        (xhat, z) alone.  Gradients with respect to y, v, sigma or mask are not produced."""
+        y, v, mask_t, c = self._prep_tangent(y, v, sigma, mask, (("prev", z_prev, zdot_prev),))
+        if z_prev is None:
+            A = [m.weight for m in self.A2]
+            B = [self.B[0].weight] + [m.weight for m in self.B2][1:]
+            return loop.run_tangent(y, v, mask_t, c, self.t2, A, B, self.s, codes=True)
+        A, B = self._filters()
+        return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, None, None, self.t, self.g, None, A, B, self.s)
+
 
 class CDLNet_CSRf2(_CSRBase):
     """CDLNet with previous- and next-frame CSR priors (net.py:464-568): one bank, thresholds t, g1, g2;
@@ -368,6 +408,21 @@ class CDLNet_CSRf2(_CSRBase):
         if z_prev is not None:
             return loop.run_csr(y, mask_t, c, z_prev, None, self.t, self.g1, None, A, B, self.s)
         return loop.run_csr(y, mask_t, c, z_after, None, self.t, self.g2, None, A, B, self.s)
+
+    def jvp_recurrent(self, y, v, z_prev=None, zdot_prev=None, z_after=None, zdot_after=None, sigma=None, mask=1):
+        """(xhat, xdot, z, zdot): forward(y, z_prev, z_after, sigma, mask) and the derivative of (xhat, z) along
+        (v, zdot_prev, zdot_after) in (y, z_prev, z_after) at the primal's gates; the branch is forward's.  See
+        CDLNet_CSR.jvp_recurrent."""
+        y, v, mask_t, c = self._prep_tangent(y, v, sigma, mask, (("prev", z_prev, zdot_prev), ("after", z_after, zdot_after)))
+        A, B = self._filters()
+        if z_prev is None and z_after is None:
+            return loop.run_tangent(y, v, mask_t, c, self.t, A, B, self.s, codes=True)
+        if z_prev is not None and z_after is not None:
+            return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, z_after, zdot_after, self.t, self.g1, self.g2,
+                                        A, B, self.s)
+        if z_prev is not None:
+            return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, None, None, self.t, self.g1, None, A, B, self.s)
+        return loop.run_csr_tangent(y, v, mask_t, c, z_after, zdot_after, None, None, self.t, self.g2, None, A, B, self.s)
 
 
 # ------------------------------------------------------------------------------------------ 3-D

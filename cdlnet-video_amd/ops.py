@@ -431,6 +431,55 @@ def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None
     return out
 
 
+def _check_codes(g: Geometry, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (tuple(t.shape) != g.code_shape() or not t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous tensor of the code shape {g.code_shape()}")
+
+
+def prox_csr_tangent(g: Geometry, ud, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None, zd_after=None,
+                     out=None):
+    """Tangent of prox_csr at the primal (u, z_prev[, z_after]) along (ud, zd_prev, zd_after) (cdl_prox_csr_tangent): a nest
+    of gates read off the primal's intermediates; a None neighbour tangent is a zero one.  out may be ud."""
+    ud, u, z_prev, lam, gam1 = _dev(ud, "ud"), _dev(u, "u"), _dev(z_prev, "z_prev"), _dev(lam, "lam"), _dev(gam1, "gam1")
+    z_after, gam2 = _opt(z_after, "z_after"), _opt(gam2, "gam2")
+    zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
+    _check_codes(g, ud=ud, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, out=out)
+    for name, t in (("lam", lam), ("gam1", gam1), ("gam2", gam2)):
+        if t is not None and t.numel() != g.N * g.M:
+            raise ValueError(f"{name}: expected {g.N * g.M} per-(sample, channel) thresholds")
+    if out is None:
+        out = torch.empty_like(ud)
+    rc = _lib.lib().cdl_prox_csr_tangent(ctypes.byref(g.c_struct()), _ptr(ud), _ptr(u), _ptr(z_prev), _ptr(z_after),
+                                         _ptr(lam), _ptr(gam1), _ptr(gam2), _ptr(zd_prev), _ptr(zd_after), _ptr(out),
+                                         _stream())
+    _lib.check(rc, "cdl_prox_csr_tangent")
+    return out
+
+
+def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None,
+                          zd_after=None, out=None):
+    """cdl_analysis followed by the tangent of the CSR map in place (cdl_analysis_prox_tangent_ws): with ud = zin +
+    alpha*corr(x; w), returns Jprox(u; z_prev[, z_after]) (ud, zd_prev, zd_after) -- the bits of analysis, then prox_csr_tangent."""
+    x, w = _dev(x, "x"), _dev(w, "w")
+    zin, u, z_prev, z_after = _opt(zin, "zin"), _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
+    zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
+    assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
+    assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
+    _check_codes(g, zin=zin, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, out=out)
+    if out is None:
+        out = torch.empty(g.code_shape(), device=x.device, dtype=torch.float32)
+    gs = g.c_struct()
+    n = int(_lib.lib().cdl_analysis_workspace_floats(ctypes.byref(gs)))
+    ws = _scratch(x.device, n) if n else None
+    rc = _lib.lib().cdl_analysis_prox_tangent_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(u),
+                                                 _ptr(z_prev), _ptr(z_after), _ptr(_dev(lam, "lam")),
+                                                 _ptr(_dev(gam1, "gam1")), _ptr(_opt(gam2, "gam2")), _ptr(zd_prev),
+                                                 _ptr(zd_after), _ptr(out), _ptr(ws), n, _stream())
+    _lib.check(rc, "cdl_analysis_prox_tangent_ws")
+    return out
+
+
 def prox_csr_bwd(g: Geometry, gz, u, z_prev, lam, gam1, c, dlam, dgam1, z_after=None, gam2=None, dgam2=None,
                  gz_prev=None, gz_after=None, out=None):
     """Reverse of prox_csr: returns gu; accumulates into gz_prev / gz_after; writes the (2,M) slices
@@ -1282,9 +1331,10 @@ def _tangent_tables(K, keep, zbufs, rbufs):
     return [zbufs[k % nz] for k in range(K)], ([rbufs[k % nr] for k in range(K - 1)] if K > 1 else [])
 
 
-def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep):
+def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep, last=False):
     """Generic tangent sweep in one C call (cdl_tangent_forward): gates = the primal's z_1..z_K (N,M,..); vp the
-    pre-processed direction.  Returns (xdp, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else []."""
+    pre-processed direction.  Returns (xdp, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else [] (with
+    `last`, zd = [zd_K] when nothing is kept: the last code of the ping-pong table)."""
     K = len(A)
     vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
     A = [_dev(w, "A") for w in A]
@@ -1302,12 +1352,12 @@ def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep):
                                         _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
                                         _ptr_table(rd) if rd else None, _ptr(xdp), _ptr(dts), _ptr(ws), n, _stream())
     _lib.check(rc, "cdl_tangent_forward")
-    return xdp, (zd if keep else []), (rd if keep else [])
+    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (rd if keep else [])
 
 
-def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp):
+def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp, g_zd=None):
     """Reverse sweep of the generic tangent sweep in one C call (cdl_tangent_backward): (dA list, dB list) for
-    dL/dxdp = g_xp; gates = the primal's codes, zd / rd = what tangent_forward kept."""
+    dL/dxdp = g_xp [and dL/dzd_K = g_zd]; gates = the primal's codes, zd / rd = what tangent_forward kept."""
     K = len(A)
     dev = vp.device
     A = [_dev(w, "A") for w in A]
@@ -1323,13 +1373,42 @@ def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp):
     ws, n = ista_scratch(g, dev)
     rc = _lib.lib().cdl_tangent_backward(ctypes.byref(g.c_struct()), K, _ptr(_dev(vp, "vp")), _ptr(_opt(mask_p, "mask")),
                                          _ptr_table(A), _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
-                                         _ptr_table(rd) if rd else None, _ptr(_dev(g_xp, "g_xp")), _ptr_table(dA),
-                                         _ptr_table(dB), _ptr(g0), _ptr(g1), _ptr(q), _ptr(dts), _ptr(ws), n, _stream())
+                                         _ptr_table(rd) if rd else None, _ptr(_dev(g_xp, "g_xp")),
+                                         _ptr(_opt(g_zd, "g_zd")), _ptr_table(dA), _ptr_table(dB), _ptr(g0), _ptr(g1),
+                                         _ptr(q), _ptr(dts), _ptr(ws), n, _stream())
     _lib.check(rc, "cdl_tangent_backward")
     return dA, dB
 
 
-def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked"):
+def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_after, zd_prev, zd_after, A, B, us, keep):
+    """Tangent sweep of the CSR loop in one C call (cdl_csr_tangent_forward): us = the primal's u_0..u_{K-1} (its gates, with
+    z_prev / z_after and the primal's lam / gam* (K,N,M)); zd_prev / zd_after (nullable) the neighbours' tangents.  Returns
+    (xdp, zd_K, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else []."""
+    K = len(A)
+    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
+    A = [_dev(w, "A") for w in A]
+    B = [_dev(w, "B") for w in B]
+    us = [_dev(t, "u") for t in us]
+    z_prev, z_after = _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
+    zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
+    assert len(us) == K
+    _check_codes(g, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, **{f"u[{k}]": t for k, t in enumerate(us)})
+    dev = vp.device
+    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
+    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
+    zd, rd = _tangent_tables(K, keep, zbuf, rbuf)
+    xdp = _new(g.image_shape(), dev)
+    ws, n = ista_scratch(g, dev)
+    rc = _lib.lib().cdl_csr_tangent_forward(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(mask_p), _ptr(z_prev), _ptr(z_after),
+                                            _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")), _ptr(_opt(gam2, "gam2")),
+                                            _ptr(zd_prev), _ptr(zd_after), _ptr_table(A), _ptr_table(B), _ptr_table(us),
+                                            _ptr_table(zd), _ptr_table(rd) if rd else None, _ptr(xdp), _ptr(ws), n,
+                                            _stream())
+    _lib.check(rc, "cdl_csr_tangent_forward")
+    return xdp, zd[K - 1], (zd if keep else []), (rd if keep else [])
+
+
+def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked", last=False):
     """Tangent sweep on the fused 2-D kernels in one C call (cdl_fused2d_tangent).  maps: the primal's K bit maps.
     Returns (xdp, zd, nrd): with keep the tangent codes (zd[:-1] in `layout`, zd[-1] NCHW) and the NEGATED tangent
     residuals -rd_1..-rd_{K-1} (what the stages read), else []."""
@@ -1356,10 +1435,10 @@ def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3",
                                         _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
                                         PRECISION[precision] | _lay_in(layout), _stream())
     _lib.check(rc, "cdl_fused2d_tangent")
-    return xdp, (zd if keep else []), (nrd if keep else [])
+    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
-def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep):
+def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, last=False):
     """cdl_fusedg_tangent: as fused_tangent for the tile / strip kernels' shapes; codes in the reference's layout."""
     K = len(A)
     vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
@@ -1381,7 +1460,7 @@ def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep):
                                        _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
                                        0, _stream())
     _lib.check(rc, "cdl_fusedg_tangent")
-    return xdp, (zd if keep else []), (nrd if keep else [])
+    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
 def fused_timing(enable: bool):

@@ -153,6 +153,152 @@ def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, proje
     return loss.detach(), sigma
 
 
+# ------------------------------------------------------------------------------------------ CSR clip steps
+# The frame-recurrent nets are trained on short clips, the code of one frame fed into the call for its neighbour
+# (traincsr.py:192-217 for CDLNet_CSR on 2 frames, 247-273 for CDLNet_CSRf2 on 3).  _clip_chain is that call sequence, written
+# once over an abstract `call(t, prev, after) -> (out, state)`: the supervised step passes codes as states, the exact SURE
+# step (code, tangent) pairs, so both run the reference's calls in the reference's order.
+def _clip_chain(call, D):
+    """The reference's network calls on a clip of D frames; returns {frame index: out of the call that enters the loss}."""
+    if D == 2:                                           # traincsr.py:201-204
+        cur = None
+        for _ in range(2):
+            out0, prev = call(0, cur, None)
+            out1, cur = call(1, prev, None)
+        return {0: out0, 1: out1}
+    if D == 3:                                           # traincsr.py:257-261
+        out0, prev = call(0, None, None)
+        out1, _ = call(1, prev, None)
+        # line 259 reads `after_denoised` as the input of its own defining call (a NameError as written): the noisy
+        # third frame is what the sequence evidently means; its z_prev stays as written (DESIGN.md section 9)
+        out2, after = call(2, prev, None)
+        out1, _ = call(1, prev, after)
+        out0, prev = call(0, None, after)
+        return {0: out0, 1: out1, 2: out2}
+    raise ValueError(f"a CSR clip has 2 frames (CDLNet_CSR) or 3 (CDLNet_CSRf2), got {D}")
+
+
+def _clip_depth(net, clip):
+    if clip.dim() != 5:
+        raise ValueError(f"clip: expected (B, C, D, H, W), got {tuple(clip.shape)}")
+    D = clip.shape[2]
+    want = 2 if isinstance(net, CDLNet_CSR) else 3 if isinstance(net, CDLNet_CSRf2) else D
+    if D != want:
+        raise ValueError(f"{type(net).__name__} trains on clips of {want} frames, got {D}")
+    return D
+
+
+def _net_call(net, D):
+    """forward of a CSR net as `call(y, prev, after, sigma)`: CDLNet_CSR has no `z_after` argument."""
+    if D == 2:
+        return lambda y, prev, after, sigma: net(y, prev, sigma)
+    return lambda y, prev, after, sigma: net(y, prev, after, sigma)
+
+
+def clip_forward(net, frames, sigmas):
+    """The supervised chain on the noisy frames: [xhat_t] of the calls that enter the loss."""
+    fwd = _net_call(net, len(frames))
+    outs = _clip_chain(lambda t, prev, after: fwd(frames[t], prev, after, sigmas[t]), len(frames))
+    return [outs[t] for t in range(len(frames))]
+
+
+def _draw_b(frames, generator):
+    dev = generator.device if generator is not None else frames[0].device
+    return [torch.randn(y.shape, device=dev, dtype=y.dtype, generator=generator).to(y.device) for y in frames]
+
+
+def sure_loss_clip(net, frames, sigmas, b=None, generator=None):
+    """Exact SURE objective of a clip step: the chain of clip_forward run with `jvp_recurrent`, one direction b_t ~ N(0, I)
+    per distinct frame (drawn as sure_loss draws b, in frame order), the same b_t at every call on frame t, and the code
+    tangent zdot carried from call to call next to the code:
+        sum_t mean((y_t - xhat_t)^2) + 2 mean((sigma_t/255)^2 b_t xdot_t)
+    over the calls that enter the supervised loss.  The chain maps ALL frames to all outputs jointly; sum_t b_t . xdot_t with
+    xdot the derivative along (b_0, .., b_{D-1}) at once is the trace estimator of that joint map's Jacobian -- which needs
+    the dependence of xhat_t on y_s (s != t) through the neighbour codes, hence zdot.
+    Returns (loss, [xhat_t])."""
+    D = len(frames)
+    if b is None:
+        b = _draw_b(frames, generator)
+    if D == 2:
+        jvp = lambda t, prev, after: net.jvp_recurrent(frames[t], b[t], prev[0], prev[1], sigmas[t])
+    else:
+        jvp = lambda t, prev, after: net.jvp_recurrent(frames[t], b[t], prev[0], prev[1], after[0], after[1], sigmas[t])
+    none = (None, None)
+
+    def call(t, prev, after):
+        xhat, xdot, z, zdot = jvp(t, prev or none, after or none)
+        return (xhat, xdot), (z, zdot)
+
+    outs = _clip_chain(call, D)
+    loss = 0.0
+    for t in range(D):
+        xhat, xdot = outs[t]
+        s2 = (sigmas[t] / 255.0) ** 2
+        loss = loss + torch.mean((frames[t] - xhat) ** 2) + 2.0 * torch.mean(s2 * b[t] * xdot)
+    return loss, [outs[t][0] for t in range(D)]
+
+
+def mcsure_loss_clip(net, frames, sigmas, xhats, h=1e-3, b=None, generator=None):
+    """The finite-difference form of sure_loss_clip (mcsure_loss over the chain): a second chain at y_t + h b_t."""
+    if b is None:
+        b = _draw_b(frames, generator)
+    xb = clip_forward(net, [y.clone() + h * bt for y, bt in zip(frames, b)], sigmas)
+    loss = 0.0
+    for y, s, bt, xhat, xhat_b in zip(frames, sigmas, b, xhats, xb):
+        loss = loss + torch.mean((y - xhat) ** 2) + 2.0 * torch.mean((s / 255.0) ** 2 * bt * (xhat_b - xhat)) / h
+    return loss
+
+
+def _clip_noise(clip, noise_std, generator):
+    """awgn per frame, in frame order (traincsr.py:196-197, 251-253)."""
+    clean = [clip[:, :, d] for d in range(clip.shape[2])]
+    noisy, sigmas = zip(*(awgn(x, noise_std, generator) for x in clean))
+    return clean, list(noisy), list(sigmas)
+
+
+def _clip_mse(xhats, clean):
+    per = [torch.mean((xh.detach() - x) ** 2) for xh, x in zip(xhats, clean)]
+    return per, sum(per[1:], per[0]) / float(len(per))
+
+
+def eval_step_clip(net, clip, noise_std, generator=None):
+    """The val / test body of traincsr.py's train_model: (loss, sigmas, mse) of the supervised chain, no step."""
+    D = _clip_depth(net, clip)
+    clean, noisy, sigmas = _clip_noise(clip, noise_std, generator)
+    per, mse = _clip_mse(clip_forward(net, noisy, sigmas), clean)
+    return sum(per[1:], per[0]), sigmas, mse
+
+
+def train_step_clip(net, opt, clip, noise_std, clip_grad=None, project=True, grad_sync=None, generator=None, mcsure=False):
+    """One optimiser step of a CSR net on a clip (B, C, D, H, W) (traincsr.py:192-217 / 247-273): awgn per frame -> the
+    reference's chain of calls -> sum of the per-frame MSEs -> backward -> [all-reduce] -> clip -> Adam -> project.
+    `mcsure`: False (supervised), True (finite differences over the chain, mcsure_loss_clip) or "exact" (sure_loss_clip).
+    Returns (loss, sigmas, mse): mse the mean of the per-frame MSEs against the clean frames (traincsr.py:217, 273)."""
+    if isinstance(mcsure, str) and mcsure != "exact":
+        raise ValueError(f"mcsure must be False, True or 'exact', got {mcsure!r}")
+    _clip_depth(net, clip)
+    clean, noisy, sigmas = _clip_noise(clip, noise_std, generator)
+    opt.zero_grad(set_to_none=True)
+    if isinstance(mcsure, str):
+        loss, xhats = sure_loss_clip(net, noisy, sigmas, generator=generator)
+    else:
+        xhats = clip_forward(net, noisy, sigmas)
+        if mcsure:
+            loss = mcsure_loss_clip(net, noisy, sigmas, xhats, generator=generator)
+        else:
+            per = [torch.mean((xh - x) ** 2) for xh, x in zip(xhats, clean)]
+            loss = sum(per[1:], per[0])
+    loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    if clip_grad is not None:
+        nn.utils.clip_grad_norm_(net.parameters(), clip_grad)
+    opt.step()
+    if project and hasattr(net, "project"):
+        net.project()
+    return loss.detach(), sigmas, _clip_mse(xhats, clean)[1]
+
+
 # ------------------------------------------------------------------------------------------ fit loop
 def grad_norm(params):
     """l2 norm of the mini-batch gradient (train.py:161-170)."""
@@ -217,6 +363,8 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     loss.CombinedLossWithSSIM(1.0, 0.01, 0.1) (VGG16 weights from the default local file); a `loss_fn` given without
     `combmse` is used the same way.  `mcsure` (True: finite differences; "exact": net.jvp, see train_step) takes
     precedence; val and test keep the MSE; the logged train PSNR is -10 log10 of that training loss, as in the reference.
+    A CDLNet_CSR / CDLNet_CSRf2 net takes the clip steps instead (train_step_clip; eval_step_clip under no_grad in val / test):
+    its batches are clips (B, C, D, H, W) and every phase logs 10 log10(1 / mse) of the frames' mean MSE (traincsr.py:124).
     Returns the history [(epoch, phase, psnr)].
     """
     ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -237,7 +385,7 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     os.makedirs(save_dir, exist_ok=True)
     if not isinstance(noise_std, (list, tuple)):
         noise_std = (noise_std, noise_std)
-    if combmse and loss_fn is None:
+    if combmse and loss_fn is None and not isinstance(net, (CDLNet_CSR, CDLNet_CSRf2)):
         from .loss import CombinedLossWithSSIM
         loss_fn = CombinedLossWithSSIM(alpha=1.0, beta=0.01, gamma=0.1).to(device)
     log(f"fit: using device {device}")
@@ -245,6 +393,10 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     if rank0:
         save_ckpt(os.path.join(save_dir, "0.ckpt"), net, 0, opt, sched)
     barrier()
+    clips = isinstance(net, (CDLNet_CSR, CDLNet_CSRf2))      # traincsr.py: clip steps, PSNR from the frames' MSE
+    if clips and (demosaic or combmse or loss_fn is not None):
+        raise ValueError(f"fit: {type(net).__name__} trains on clips with the summed per-frame MSE (or SURE); `demosaic`, "
+                         "`combmse` and `loss_fn` are not taken")
     top_psnr = {"train": 0, "val": 0, "test": 0}
     history = []
     epoch = start_epoch
@@ -262,7 +414,14 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
             psnr, nb, bad = 0.0, 0, False
             for batch in loaders[phase]:
                 batch = batch.to(device)
-                if phase == "train":
+                mse_t = None
+                if clips and phase == "train":
+                    loss_t, _, mse_t = train_step_clip(net, opt, batch, phase_nstd, clip_grad=clip_grad, grad_sync=grad_sync,
+                                                       mcsure=mcsure, generator=generator)
+                elif clips:
+                    with torch.no_grad():
+                        loss_t, _, mse_t = eval_step_clip(net, batch, phase_nstd, generator)
+                elif phase == "train":
                     loss_t, _ = train_step(net, opt, batch, phase_nstd, clip_grad=clip_grad, demosaic=demosaic,
                                            grad_sync=grad_sync, mcsure=mcsure, generator=generator, loss_fn=loss_fn)
                 else:
@@ -274,7 +433,8 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
                 loss = float(loss_t)
                 if verbose and phase == "train":
                     log(f"{phase.upper()}-E{epoch} loss={loss:.1e}|gnorm={grad_norm(net.parameters()):.1e}")
-                psnr = psnr - 10 * np.log10(loss) if loss > 0 else float("nan")
+                level = loss if mse_t is None else float(mse_t)      # clips: 10 log10(1 / mse) (traincsr.py:124)
+                psnr = psnr - 10 * np.log10(level) if level > 0 else float("nan")
                 bad = bad or bool(np.isnan(loss) or np.isinf(loss))
                 nb += 1
             # one reduction per phase: mean PSNR over every rank's batches, nan / inf on ANY rank

@@ -228,6 +228,32 @@ int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, floa
                          float *u_out /*nullable*/, float *out, float *workspace, size_t workspace_floats,
                          void *stream);
 
+/* Tangent of the two maps.  They are piecewise linear in (u, z_prev, z_after); with the intermediates
+ * of the PRIMAL (u, z_prev[, z_after], lam, gam*) and st_dx(x,t) = (x != 0 && |x| - t > 0):
+ *   prox_CSR:     Ga = st_dx(a, lam*gam1), Gm = st_dx(m, lam):              out = Gm ? (Ga ? ud : zd_prev) : 0
+ *   prox_CSR_f2:  Ga = st_dx(a, t1), Gb = st_dx(b, t2), Gm = st_dx(m, lam): out = Gm ? (Gb ? (Ga ? ud - zd_prev : 0) : zd_after) : 0
+ * evaluated as selects (a NaN in a dead branch does not leak); no threshold enters a value.  ud: the tangent of u;
+ * zd_prev / zd_after (nullable): the neighbours' tangents, NULL = zero (a constant neighbour).  out may alias ud. */
+int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, const float *z_prev,
+                         const float *z_after /*nullable*/, const float *lam, const float *gam1,
+                         const float *gam2 /*nullable iff z_after is*/, const float *zd_prev /*nullable*/,
+                         const float *zd_after /*nullable*/, float *out, void *stream);
+
+/* The tangent step of one iteration: ud = zin + alpha*corr(x ; w) (cdl_analysis_ws into out), then
+ * out = Jprox(u; z_prev[, z_after])(ud, zd_prev, zd_after) in place (cdl_prox_csr_tangent): two launches, the bits of the
+ * two calls.  (As a branch of the kernels' CSR epilogue it slowed the primal epilogue: DESIGN.md section 22.) */
+int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha,
+                              const float *zin /*nullable*/, const float *u, const float *z_prev,
+                              const float *z_after /*nullable*/, const float *lam, const float *gam1,
+                              const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
+                              const float *zd_after /*nullable*/, float *out, void *stream);
+int cdl_analysis_prox_tangent_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
+                                 const float *zin /*nullable*/, const float *u, const float *z_prev,
+                                 const float *z_after /*nullable*/, const float *lam, const float *gam1,
+                                 const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
+                                 const float *zd_after /*nullable*/, float *out, float *workspace,
+                                 size_t workspace_floats, void *stream);
+
 /* Reverse of cdl_prox_csr as autograd differentiates the reference expression (sign() has zero
  * gradient): gu = dL/du (may alias gz); gz_prev / gz_after (nullable) are ACCUMULATED into, because a
  * neighbour code feeds all K iterations; dlam, dgam1, dgam2 are (2,M) and receive
@@ -378,12 +404,29 @@ int cdl_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *
                         void *stream);
 /* Its reverse sweep (the tangent net is linear in vp with the gates fixed): dA[k], dB[k] of a loss with dL/dxdp = g_xp --
  * cdl_ista_backward's plain branch with the supports taken from zgate and the operands from the tangent sweep; no
- * threshold and no data gradient.  gbuf0, gbuf1: code-sized; q: thin. */
+ * threshold and no data gradient.  g_zd (nullable) = dL/dzd_K, added before the last gate.  gbuf0, gbuf1: code-sized;
+ * q: thin. */
 int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
                          const float *const *wA, const float *const *wB, const float *const *zgate,
-                         const float *const *zd, const float *const *rd, const float *g_xp, float *const *dA,
-                         float *const *dB, float *gbuf0, float *gbuf1, float *q, float *dt_scratch, float *scratch,
-                         size_t scratch_floats, void *stream);
+                         const float *const *zd, const float *const *rd, const float *g_xp,
+                         const float *g_zd /*nullable*/, float *const *dA, float *const *dB, float *gbuf0, float *gbuf1,
+                         float *q, float *dt_scratch, float *scratch, size_t scratch_floats, void *stream);
+
+/* ---- forward-mode tangent of the CSR loop at the primal's gates ----
+ * u[k] = u_k of the primal (cdl_ista_forward's table), lam / gam1 / gam2 (K,N,M) the primal's; zd_prev / zd_after (nullable)
+ * the tangents of the neighbour codes:
+ *   ud_0 = A_0 vp,  rd_k = mask B_k zd_k - vp,  ud_k = zd_k - A_k rd_k,  zd_{k+1} = Jprox_k(ud_k; zd_prev, zd_after),
+ *   xdp = B_0 zd_K.
+ * Per iteration cdl_synthesis_ws + cdl_analysis_prox_tangent_ws.  zd: K code buffers,
+ * rd: K-1 thin ones (two each suffice when nothing is kept).  The reverse sweep is cdl_ista_backward's CSR branch with
+ * yp -> vp, z -> zd, r -> rd, the primal's u / lam / gam*, c = NULL: gz_prev / gz_after then receive dL/dzd_prev, dL/dzd_after
+ * and dt / dg1 / dg2 sums nobody reads (the gates are piecewise constant: no threshold gradient through the tangent). */
+int cdl_csr_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
+                            const float *z_prev, const float *z_after /*nullable*/, const float *lam,
+                            const float *gam1, const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
+                            const float *zd_after /*nullable*/, const float *const *wA, const float *const *wB,
+                            const float *const *u, float *const *zd, float *const *rd, float *xdp, float *scratch,
+                            size_t scratch_floats, void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
  * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere.  w inout. */
