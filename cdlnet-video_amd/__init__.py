@@ -3,7 +3,7 @@
 Import as `cdlnet_video_amd` (see the loader shim at the repository root; the directory name
 carries a hyphen).  Public surface mirrors the reference's `model/net.py`.
 """
-from . import _lib, loss, metrics, nle, ops, parallel, train, utils
+from . import _lib, functional, loss, metrics, nle, ops, parallel, train, utils
 from ._lib import HipKernelError, HipLibraryMissing
 from .gabor import ConvAdjoint2dGabor
 from .loss import CombinedLossWithSSIM, load_vgg16_weights
@@ -21,5 +21,5 @@ __all__ = ["CDLNet", "CDLNetVideo", "ResidualBlock", "GDLNet", "JDD_CDLNet", "CD
            "build_model", "init_model", "load_ckpt", "save_ckpt", "train_step", "fit", "mcsure_loss", "sure_loss",
            "sure_loss_clip", "train_step_clip",
            "save_args",
-           "awgn", "awgn3d", "gen_bayer_mask", "psnr", "ssim", "CombinedLossWithSSIM", "load_vgg16_weights", "loss", "metrics", "nle", "ops", "parallel", "train", "utils",
+           "awgn", "awgn3d", "gen_bayer_mask", "psnr", "ssim", "CombinedLossWithSSIM", "load_vgg16_weights", "functional", "loss", "metrics", "nle", "ops", "parallel", "train", "utils",
            "HipLibraryMissing", "HipKernelError"]

@@ -29,11 +29,17 @@ class Geom(ctypes.Structure):
                 ("N", "C", "M", "D", "H", "W", "Pd", "Ph", "Pw", "pd", "ph", "pw", "sd", "sh", "sw")]
 
 
+class Bcast(ctypes.Structure):
+    """Mirror of `cdl_bcast`: element strides of a broadcast threshold over (sample, channel, code pixel)."""
+    _fields_ = [(n, ctypes.c_longlong) for n in ("n", "m", "p")]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
 _G = ctypes.POINTER(Geom)
 _IP = ctypes.POINTER(ctypes.c_int)
+_B = ctypes.POINTER(Bcast)
 
 # name -> argtypes; every function returns int except cdl_version
 SIGNATURES = {
@@ -71,6 +77,11 @@ SIGNATURES = {
     "cdl_prox_csr": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_prox_csr_bwd": [_G] + [_P] * 15 + [ctypes.c_size_t, _P],
     "cdl_prox_csr_tangent": [_G] + [_P] * 11,
+    # thresholds of any broadcast shape (each threshold pointer is followed by its strides)
+    "cdl_shrink_b": [_P, _P, _B, _P, _I, _I, ctypes.c_size_t, _P],
+    "cdl_shrink_b_bwd": [_P, _P, _P, _B, _P, _P, _I, _I, ctypes.c_size_t, _P],
+    "cdl_prox_csr_b": [_G, _P, _P, _P, _P, _B, _P, _B, _P, _B, _P, _P],
+    "cdl_prox_csr_b_bwd": [_G, _P, _P, _P, _P, _P, _B, _P, _B, _P, _B] + [_P] * 7 + [ctypes.c_size_t, _P],
     "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11,
     "cdl_analysis_prox_tangent_ws": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_project_filters": [_P, _I, _I, _P],

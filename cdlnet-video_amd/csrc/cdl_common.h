@@ -189,6 +189,17 @@ static inline bool cdl_geom_ok(const cdl_geom *g)
     return true;
 }
 
+// Strides of a broadcast threshold (cdl_bcast): 0 on a broadcast axis, else the dense stride of a contiguous tensor whose
+// other axes are full or 1.  The spatial axes are broadcast together (p == 0) or all present (p == 1).
+static inline bool cdl_bcast_ok(const cdl_bcast *s, int M, size_t per_m)
+{
+    if (!s || (s->p != 0 && s->p != 1)) return false;
+    const long long dm = s->p ? (long long)per_m : 1;
+    if (s->m != 0 && s->m != dm) return false;
+    const long long dn = s->m ? dm * M : dm;
+    return s->n == 0 || s->n == dn;
+}
+
 // register-tiled variants (cdl_generic_tiled.hip): CDL_EUNSUPPORTED means "use the untiled kernel"
 int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                        const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,

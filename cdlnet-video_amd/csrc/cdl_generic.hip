@@ -349,11 +349,28 @@ __global__ __launch_bounds__(256) void k_sigma_grad(const float *__restrict__ du
     dcmap[o] = ACC ? dcmap[o] + a : a;
 }
 
+// ST(x, tau) with tau in the row form (M == 0: tau[i / per_m]) or of any broadcast shape (M > 0 channels, strides st:
+// cdl_bcast).  gup != nullptr: the reverse pass instead -- out = gup where autograd's d ST / dx is 1, else 0, and (nullable)
+// dtau_el = -sign(x) * out, the per-element threshold gradient.
 __global__ void k_shrink(const float *__restrict__ x, const float *__restrict__ tau,
-                         float *__restrict__ out, size_t total, size_t per_m)
+                         float *__restrict__ out, size_t total, size_t per_m, int M, cdl_bcast st,
+                         const float *__restrict__ gup, float *__restrict__ dtau_el)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total) out[i] = cdl_shrink(x[i], tau[i / per_m]);
+    if (i >= total) return;
+    const size_t row = i / per_m;
+    size_t it = row;
+    if (M > 0) {
+        const size_t n = row / (size_t)M, m = row - n * (size_t)M;
+        it = n * (size_t)st.n + m * (size_t)st.m + (i - row * per_m) * (size_t)st.p;
+    }
+    if (!gup) {
+        out[i] = cdl_shrink(x[i], tau[it]);
+        return;
+    }
+    const float xv = x[i], gx = cdl_st_dx(xv, tau[it]) ? gup[i] : 0.0f;
+    out[i] = gx;
+    if (dtau_el) dtau_el[i] = xv > 0.0f ? -gx : gx;
 }
 
 __global__ void k_thresholds(const float *__restrict__ t, const float *__restrict__ c,
@@ -742,13 +759,36 @@ int cdl_thresholds(const float *t, const float *c, float *tau, int K, int N, int
     return 0;
 }
 
+static int launch_shrink(const float *x, const float *tau, float *out, size_t rows, size_t per_m, int M,
+                         const cdl_bcast &st, const float *gup, float *dtau_el, void *stream)
+{
+    const size_t total = rows * per_m, blocks = (total + 255) / 256;
+    if (blocks >= ((size_t)1 << 31)) return CDL_EUNSUPPORTED;
+    k_shrink<<<(unsigned)blocks, 256, 0, S(stream)>>>(x, tau, out, total, per_m, M, st, gup, dtau_el);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
 int cdl_shrink(const float *x, const float *tau, float *out, int rows, size_t per_m, void *stream)
 {
     if (!x || !tau || !out || rows <= 0 || per_m == 0) return CDL_EINVAL;
-    size_t total = (size_t)rows * per_m;
-    k_shrink<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(x, tau, out, total, per_m);
-    CDL_LAUNCH_CHECK();
-    return 0;
+    return launch_shrink(x, tau, out, (size_t)rows, per_m, 0, cdl_bcast{0, 0, 0}, nullptr, nullptr, stream);
+}
+
+int cdl_shrink_b(const float *x, const float *tau, const cdl_bcast *s_tau, float *out, int N, int M, size_t per_m,
+                 void *stream)
+{
+    if (!x || !tau || !out || N <= 0 || M <= 0 || per_m == 0 || !cdl_bcast_ok(s_tau, M, per_m)) return CDL_EINVAL;
+    const bool row = s_tau->n == M && s_tau->m == 1 && s_tau->p == 0;
+    return launch_shrink(x, tau, out, (size_t)N * M, per_m, row ? 0 : M, *s_tau, nullptr, nullptr, stream);
+}
+
+int cdl_shrink_b_bwd(const float *gup, const float *x, const float *tau, const cdl_bcast *s_tau, float *gx,
+                     float *dtau_el, int N, int M, size_t per_m, void *stream)
+{
+    if (!gup || !x || !tau || !gx || N <= 0 || M <= 0 || per_m == 0 || !cdl_bcast_ok(s_tau, M, per_m))
+        return CDL_EINVAL;
+    return launch_shrink(x, tau, gx, (size_t)N * M, per_m, M, *s_tau, gup, dtau_el, stream);
 }
 
 static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,

@@ -26,18 +26,39 @@ __device__ __forceinline__ Prox2 prox2(float u, float zp, float za, float lam, f
     return cdl_prox_csr2(u, zp, za, lam, g1, g2);
 }
 
+// Thresholds of any broadcast shape (cdl_bcast, include/cdlnet_hip.h): element (n, m, pix) reads thr[n*s.n + m*s.m + pix*s.p],
+// a stride being 0 on a broadcast axis.  ROW is the form of the nets' own thresholds, one value per (sample, channel) row.
+struct Bcast3 {
+    cdl_bcast lam, g1, g2;
+};
+constexpr cdl_bcast ROW(int M) { return cdl_bcast{M, 1, 0}; }
+__host__ __device__ __forceinline__ bool is_row(const cdl_bcast &s, int M) { return s.n == M && s.m == 1 && s.p == 0; }
+__device__ __forceinline__ size_t at(const cdl_bcast &s, int n, int m, size_t pix)
+{
+    return (size_t)n * (size_t)s.n + (size_t)m * (size_t)s.m + pix * (size_t)s.p;
+}
+
 // The map itself (up == nullptr: in = u, out = prox(u; zp[, za])) or its tangent at the primal (up, zp[, za]) along
 // (in = ud, zpd, zad; a null neighbour tangent is a zero one): one kernel, one launch site (launch_prox).  out may alias in
-// (each thread reads its element before it writes it).
+// (each thread reads its element before it writes it).  M == 0: every threshold is in the row form (index = row); M > 0:
+// the general broadcast form `bs` of the map itself (up == nullptr), M the channel count.
 __global__ __launch_bounds__(256) void k_prox_fwd(const float *in, const float *__restrict__ up,
                                                   const float *__restrict__ zp, const float *__restrict__ za,
                                                   const float *__restrict__ lam, const float *__restrict__ g1,
                                                   const float *__restrict__ g2, const float *__restrict__ zpd,
-                                                  const float *__restrict__ zad, float *out, size_t total, size_t per_m)
+                                                  const float *__restrict__ zad, float *out, size_t total, size_t per_m,
+                                                  int M, Bcast3 bs)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / per_m;
+    if (M > 0) {                                                     // uniform: the whole launch takes one form
+        const size_t pix = i - row * per_m;                          // (the map only: the tangent's callers pass rows)
+        const int n = (int)(row / (size_t)M), m = (int)(row - (size_t)n * M);
+        const float l = lam[at(bs.lam, n, m, pix)], a1 = g1[at(bs.g1, n, m, pix)];
+        out[i] = za ? prox2(in[i], zp[i], za[i], l, a1, g2[at(bs.g2, n, m, pix)]).z : prox1(in[i], zp[i], l, a1).z;
+        return;
+    }
     if (!up) {
         out[i] = za ? prox2(in[i], zp[i], za[i], lam[row], g1[row], g2[row]).z : prox1(in[i], zp[i], lam[row], g1[row]).z;
         return;
@@ -50,24 +71,30 @@ __global__ __launch_bounds__(256) void k_prox_fwd(const float *in, const float *
     out[i] = cdl_prox_csr2_tangent(prox2(up[i], zp[i], za[i], l, g1[row], g2[row]), l, ud, dp, zad ? zad[i] : 0.0f);
 }
 
-// Reverse of the map for one (row, split): gu, the neighbour-code gradients (accumulated: a neighbour
-// feeds every iteration) and this split's three threshold sums into part[(row*S + split)*3 + {0,1,2}].
-__global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, const float *__restrict__ u,
-                                                  const float *__restrict__ zp, const float *__restrict__ za,
-                                                  const float *__restrict__ lam, const float *__restrict__ g1,
-                                                  const float *__restrict__ g2, float *__restrict__ gu,
-                                                  float *__restrict__ gzp, float *__restrict__ gza,
-                                                  float *__restrict__ part, size_t per_m, int S)
+// One (row, split) of the reverse pass.  EL: some threshold has spatial extent -- it is read per element, and its
+// per-element gradient goes to el_l / el_1 / el_2 (each nullable) for the host to reduce over its broadcast axes; the row
+// sums are formed all the same.  !EL is the loop of the row form, thresholds in scalar registers.
+struct Sums3 {
+    float l, g1, g2;
+};
+
+template <bool EL>
+__device__ __forceinline__ Sums3 prox_bwd_span(const float *__restrict__ gz, const float *__restrict__ u,
+                                              const float *__restrict__ zp, const float *__restrict__ za,
+                                              const float *__restrict__ lam, const float *__restrict__ g1,
+                                              const float *__restrict__ g2, float *__restrict__ gu,
+                                              float *__restrict__ gzp, float *__restrict__ gza, size_t base, size_t lo,
+                                              size_t hi, size_t ol, size_t o1, size_t o2, bool el_lam, bool el_g1, bool el_g2,
+                                              float *__restrict__ el_l, float *__restrict__ el_1,
+                                              float *__restrict__ el_2)
 {
-    __shared__ float red[3][4];
-    const int row = blockIdx.x / S, sp = blockIdx.x % S;
-    const size_t chunk = (per_m + S - 1) / S;
-    const size_t lo = (size_t)sp * chunk, hi = lo + chunk < per_m ? lo + chunk : per_m;
-    const size_t base = (size_t)row * per_m;
-    const float l = lam[row], a1 = g1[row], a2 = g2 ? g2[row] : 0.0f;
     float sl = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    const float l0 = lam[ol], a10 = g1[o1], a20 = g2 ? g2[o2] : 0.0f;
     for (size_t j = lo + threadIdx.x; j < hi; j += 256) {
         const size_t i = base + j;
+        const float l = (EL && el_lam) ? lam[ol + j] : l0;
+        const float a1 = (EL && el_g1) ? g1[o1 + j] : a10;
+        const float a2 = (EL && el_g2) ? g2[o2 + j] : a20;
         const float g = gz[i], uu = u[i], p = zp[i];
         if (!za) {
             const Prox1 q = prox1(uu, p, l, a1);
@@ -78,6 +105,10 @@ __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, 
             if (gzp) gzp[i] += gm - ga;
             sl += g * st_dt(q.m, l) + gtg * a1 + (gm - ga) * q.s;
             s1 += gtg * l;
+            if (EL) {
+                if (el_l) el_l[i] = g * st_dt(q.m, l) + gtg * a1 + (gm - ga) * q.s;
+                if (el_1) el_1[i] = gtg * l;
+            }
         } else {
             const float a = za[i];
             const Prox2 q = prox2(uu, p, a, l, a1, a2);
@@ -95,8 +126,46 @@ __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, 
             sl += g * st_dt(q.m, l) - ga * q.sp + gcb * q.sa_ + p1 * a1 + p2 * a2;
             s1 += p1 * l;
             s2 += p2 * l;
+            if (EL) {
+                if (el_l) el_l[i] = g * st_dt(q.m, l) - ga * q.sp + gcb * q.sa_ + p1 * a1 + p2 * a2;
+                if (el_1) el_1[i] = p1 * l;
+                if (el_2) el_2[i] = p2 * l;
+            }
         }
     }
+    return Sums3{sl, s1, s2};
+}
+
+// Reverse of the map for one (row, split): gu, the neighbour-code gradients (accumulated: a neighbour
+// feeds every iteration) and this split's three threshold sums into part[(row*S + split)*3 + {0,1,2}].
+// M == 0: thresholds in the row form (index = row); M > 0: in the broadcast form `bs`, M channels.  el_*: see prox_bwd_span.
+__global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, const float *__restrict__ u,
+                                                  const float *__restrict__ zp, const float *__restrict__ za,
+                                                  const float *__restrict__ lam, const float *__restrict__ g1,
+                                                  const float *__restrict__ g2, float *__restrict__ gu,
+                                                  float *__restrict__ gzp, float *__restrict__ gza,
+                                                  float *__restrict__ part, size_t per_m, int S, int M, Bcast3 bs,
+                                                  float *__restrict__ el_l, float *__restrict__ el_1,
+                                                  float *__restrict__ el_2)
+{
+    __shared__ float red[3][4];
+    const int row = blockIdx.x / S, sp = blockIdx.x % S;
+    const size_t chunk = (per_m + S - 1) / S;
+    const size_t lo = (size_t)sp * chunk, hi = lo + chunk < per_m ? lo + chunk : per_m;
+    const size_t base = (size_t)row * per_m;
+    size_t ol = (size_t)row, o1 = ol, o2 = ol;                       // M == 0: every threshold in the row form
+    if (M > 0) {
+        const int n = row / M, m = row - n * M;
+        ol = at(bs.lam, n, m, 0), o1 = at(bs.g1, n, m, 0), o2 = at(bs.g2, n, m, 0);
+    }
+    const bool el_lam = bs.lam.p != 0, el_g1 = bs.g1.p != 0, el_g2 = g2 && bs.g2.p != 0;
+    const Sums3 sums =
+        (el_lam | el_g1 | el_g2)
+            ? prox_bwd_span<true>(gz, u, zp, za, lam, g1, g2, gu, gzp, gza, base, lo, hi, ol, o1, o2, el_lam, el_g1, el_g2,
+                                  el_l, el_1, el_2)
+            : prox_bwd_span<false>(gz, u, zp, za, lam, g1, g2, gu, gzp, gza, base, lo, hi, ol, o1, o2, false, false, false,
+                                   nullptr, nullptr, nullptr);
+    float sl = sums.l, s1 = sums.g1, s2 = sums.g2;
     for (int off = 32; off > 0; off >>= 1) {
         sl += __shfl_down(sl, off, 64);
         s1 += __shfl_down(s1, off, 64);
@@ -114,9 +183,10 @@ __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, 
 }
 
 // d(t[k,0,m]) = sum_n s[n,m], d(t[k,1,m]) = sum_n c[n] s[n,m] for each of the three threshold families
-// (lam = t[k,0] + c t[k,1] etc., net.py:444-452).  One thread per (family, m); fixed order.
+// (lam = t[k,0] + c t[k,1] etc., net.py:444-452).  One thread per (family, m); fixed order.  slope == 0: only the first row
+// is written (the per-row sums of the broadcast form: N = 1, M = rows).
 __global__ void k_prox_fold(const float *__restrict__ part, const float *__restrict__ c, float *__restrict__ dlam,
-                            float *__restrict__ dg1, float *__restrict__ dg2, int N, int M, int S)
+                            float *__restrict__ dg1, float *__restrict__ dg2, int N, int M, int S, int slope)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 3 * M) return;
@@ -131,7 +201,7 @@ __global__ void k_prox_fold(const float *__restrict__ part, const float *__restr
         if (c) a1 = fmaf(c[n], v, a1);
     }
     dst[m] = a0;
-    dst[M + m] = a1;
+    if (slope) dst[M + m] = a1;
 }
 
 int splits_for(int rows, size_t per_m)
@@ -150,21 +220,37 @@ extern "C" {
 
 static int launch_prox(const cdl_geom *g, const float *in, const float *up, const float *z_prev, const float *z_after,
                        const float *lam, const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                       float *out, void *stream)
+                       float *out, const Bcast3 &bs, void *stream)
 {
     const size_t per_m = code_elems(g), total = (size_t)g->N * g->M * per_m;
-    k_prox_fwd<<<(unsigned)((total + 255) / 256), 256, 0, S(stream)>>>(in, up, z_prev, z_after, lam, gam1, gam2, zd_prev,
-                                                                         zd_after, out, total, per_m);
+    const bool rows = is_row(bs.lam, g->M) && is_row(bs.g1, g->M) && (!z_after || is_row(bs.g2, g->M));
+    const size_t blocks = (total + 255) / 256;
+    if (blocks >= ((size_t)1 << 31) || (up && !rows)) return CDL_EUNSUPPORTED;
+    k_prox_fwd<<<(unsigned)blocks, 256, 0, S(stream)>>>(in, up, z_prev, z_after, lam, gam1, gam2, zd_prev,
+                                                                         zd_after, out, total, per_m, rows ? 0 : g->M, bs);
     CDL_LAUNCH_CHECK();
     return 0;
+}
+
+int cdl_prox_csr_b(const cdl_geom *g, const float *u, const float *z_prev, const float *z_after, const float *lam,
+                   const cdl_bcast *s_lam, const float *gam1, const cdl_bcast *s_gam1, const float *gam2,
+                   const cdl_bcast *s_gam2, float *out, void *stream)
+{
+    if (!cdl_geom_ok(g) || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
+    if (z_after && !gam2) return CDL_EINVAL;
+    const size_t per_m = code_elems(g);
+    if (!cdl_bcast_ok(s_lam, g->M, per_m) || !cdl_bcast_ok(s_gam1, g->M, per_m)) return CDL_EINVAL;
+    if (z_after && !cdl_bcast_ok(s_gam2, g->M, per_m)) return CDL_EINVAL;
+    const Bcast3 bs{*s_lam, *s_gam1, z_after ? *s_gam2 : cdl_bcast{0, 0, 0}};
+    return launch_prox(g, u, nullptr, z_prev, z_after, lam, gam1, gam2, nullptr, nullptr, out, bs, stream);
 }
 
 int cdl_prox_csr(const cdl_geom *g, const float *u, const float *z_prev, const float *z_after, const float *lam,
                  const float *gam1, const float *gam2, float *out, void *stream)
 {
-    if (!cdl_geom_ok(g) || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
-    if (z_after && !gam2) return CDL_EINVAL;
-    return launch_prox(g, u, nullptr, z_prev, z_after, lam, gam1, gam2, nullptr, nullptr, out, stream);
+    if (!g) return CDL_EINVAL;
+    const cdl_bcast r = ROW(g->M);
+    return cdl_prox_csr_b(g, u, z_prev, z_after, lam, &r, gam1, &r, gam2, &r, out, stream);
 }
 
 int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, const float *z_prev, const float *z_after,
@@ -174,13 +260,34 @@ int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, con
     if (!cdl_geom_ok(g) || !ud || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
     if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
     if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
-    return launch_prox(g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, stream);
+    const Bcast3 bs{ROW(g->M), ROW(g->M), ROW(g->M)};
+    return launch_prox(g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, bs, stream);
 }
 
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return 0;
     return (size_t)g->N * g->M * splits_for(g->N * g->M, code_elems(g)) * 3;
+}
+
+// The one launch pair of the reverse pass.  fold_N x fold_M = rows: (N, M) with c folds the row sums into the (2, M)
+// parameter slices; (1, rows) without slope leaves them per row.  A NULL d* is not written.
+static int launch_prox_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev, const float *z_after,
+                           const float *lam, const float *gam1, const float *gam2, const Bcast3 &bs, const float *c,
+                           float *gu, float *gz_prev, float *gz_after, float *dlam, float *dgam1, float *dgam2,
+                           float *el_l, float *el_1, float *el_2, float *scratch, int fold_N, int fold_M, int slope,
+                           void *stream)
+{
+    const size_t per_m = code_elems(g);
+    const int rows = g->N * g->M, Sp = splits_for(rows, per_m);
+    const bool rowform = is_row(bs.lam, g->M) && is_row(bs.g1, g->M) && (!z_after || is_row(bs.g2, g->M));
+    k_prox_bwd<<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gz, u, z_prev, z_after, lam, gam1, gam2, gu, gz_prev, gz_after,
+                                                             scratch, per_m, Sp, rowform ? 0 : g->M, bs, el_l, el_1, el_2);
+    CDL_LAUNCH_CHECK();
+    if (!dlam && !dgam1 && !dgam2) return 0;
+    k_prox_fold<<<(3 * fold_M + 63) / 64, 64, 0, S(stream)>>>(scratch, c, dlam, dgam1, dgam2, fold_N, fold_M, Sp, slope);
+    CDL_LAUNCH_CHECK();
+    return 0;
 }
 
 int cdl_prox_csr_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev,
@@ -193,15 +300,29 @@ int cdl_prox_csr_bwd(const cdl_geom *g, const float *gz, const float *u, const f
     if (z_after && (!gam2 || !dgam2)) return CDL_EINVAL;
     if (!z_after && gz_after) return CDL_EINVAL;
     if (scratch_floats < cdl_prox_csr_scratch_floats(g)) return CDL_EINVAL;
+    const Bcast3 bs{ROW(g->M), ROW(g->M), ROW(g->M)};
+    return launch_prox_bwd(g, gz, u, z_prev, z_after, lam, gam1, gam2, bs, c, gu, gz_prev, gz_after, dlam, dgam1,
+                           z_after ? dgam2 : nullptr, nullptr, nullptr, nullptr, scratch, g->N, g->M, 1, stream);
+}
+
+int cdl_prox_csr_b_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev, const float *z_after,
+                       const float *lam, const cdl_bcast *s_lam, const float *gam1, const cdl_bcast *s_gam1,
+                       const float *gam2, const cdl_bcast *s_gam2, float *gu, float *gz_prev, float *gz_after,
+                       float *dlam, float *dgam1, float *dgam2, float *scratch, size_t scratch_floats, void *stream)
+{
+    if (!cdl_geom_ok(g) || !gz || !u || !z_prev || !lam || !gam1 || !gu || !scratch) return CDL_EINVAL;
+    if (z_after && !gam2) return CDL_EINVAL;
+    if (!z_after && (gz_after || dgam2)) return CDL_EINVAL;
     const size_t per_m = code_elems(g);
-    const int rows = g->N * g->M, Sp = splits_for(rows, per_m);
-    k_prox_bwd<<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gz, u, z_prev, z_after, lam, gam1, gam2, gu, gz_prev,
-                                                             gz_after, scratch, per_m, Sp);
-    CDL_LAUNCH_CHECK();
-    k_prox_fold<<<(3 * g->M + 63) / 64, 64, 0, S(stream)>>>(scratch, c, dlam, dgam1, z_after ? dgam2 : nullptr,
-                                                             g->N, g->M, Sp);
-    CDL_LAUNCH_CHECK();
-    return 0;
+    if (!cdl_bcast_ok(s_lam, g->M, per_m) || !cdl_bcast_ok(s_gam1, g->M, per_m)) return CDL_EINVAL;
+    if (z_after && !cdl_bcast_ok(s_gam2, g->M, per_m)) return CDL_EINVAL;
+    if (scratch_floats < cdl_prox_csr_scratch_floats(g)) return CDL_EINVAL;
+    const Bcast3 bs{*s_lam, *s_gam1, z_after ? *s_gam2 : cdl_bcast{0, 0, 0}};
+    // a threshold with spatial extent takes its gradient per element, the others as row sums
+    const bool el = bs.lam.p != 0, e1 = bs.g1.p != 0, e2 = bs.g2.p != 0;
+    return launch_prox_bwd(g, gz, u, z_prev, z_after, lam, gam1, gam2, bs, nullptr, gu, gz_prev, gz_after,
+                           el ? nullptr : dlam, e1 ? nullptr : dgam1, e2 ? nullptr : dgam2, el ? dlam : nullptr,
+                           e1 ? dgam1 : nullptr, e2 ? dgam2 : nullptr, scratch, 1, g->N * g->M, 0, stream);
 }
 
 }  // extern "C"

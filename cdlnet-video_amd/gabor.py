@@ -102,10 +102,10 @@ class ConvAdjoint2dGabor(nn.Module):
 
     def T(self, x):
         """Analysis: zero-pad + strided correlation with the (-w0,-psi) filter (gabor.py:53-55)."""
-        g = self._geom(x.shape[0], x.shape[2], x.shape[3])
-        return ops.analysis(g, x, self.get_filter(transpose=True).detach())
+        from . import functional
+        return functional.analysis(x, self.get_filter(transpose=True), self.stride)
 
     def forward(self, x):
         """Synthesis: transposed correlation back to s*H x s*W (gabor.py:57-67)."""
-        g = self._geom(x.shape[0], x.shape[2] * self.stride, x.shape[3] * self.stride)
-        return ops.synthesis(g, x, self.get_filter().detach())
+        from . import functional
+        return functional.synthesis(x, self.get_filter(), self.stride)

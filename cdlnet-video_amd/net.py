@@ -17,7 +17,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import loop, ops
+from . import functional, loop, ops
 from .gabor import ConvAdjoint2dGabor, filter_banks, gabor_kernel_cpu
 from .solvers import gram_operator, power_method
 
@@ -25,46 +25,32 @@ from .solvers import gram_operator, power_method
 def ST(x, t):
     """Shrinkage-thresholding sign(x)*relu(|x|-t) (net.py:11-14) on the device.
 
-    Stand-alone form for callers of the reference's helper (t broadcastable to
-    (N, M, 1, ..)); inside the nets it is fused into the analysis kernel's epilogue.
+    Stand-alone form for callers of the reference's helper (t a number or broadcastable to x),
+    differentiable in x and t (functional.shrink); inside the nets it is fused into the analysis
+    kernel's epilogue.
     """
-    N, M = x.shape[:2]
-    tau = torch.as_tensor(t, dtype=torch.float32, device=x.device)
-    while tau.dim() < x.dim():
-        tau = tau.unsqueeze(0)
-    tau = torch.broadcast_to(tau, (N, M) + (1,) * (x.dim() - 2)).reshape(N, M).contiguous()
-    return ops.shrink(x, tau)
+    return functional.shrink(x, t)
 
 
 # ------------------------------------------------------------------------------------------ banks
 class _Analysis2d(nn.Conv2d):
     def forward(self, x):
-        g = ops.Geometry.make(x.shape[0], self.in_channels, self.out_channels, x.shape[2:],
-                              self.kernel_size, self.padding, self.stride[0])
-        return ops.analysis(g, x, self.weight.detach())
+        return functional.analysis(x, self.weight, self.stride[0])
 
 
 class _Synthesis2d(nn.ConvTranspose2d):
     def forward(self, z):
-        sp = tuple(d * self.stride[0] for d in z.shape[2:])
-        g = ops.Geometry.make(z.shape[0], self.out_channels, self.in_channels, sp,
-                              self.kernel_size, self.padding, self.stride[0])
-        return ops.synthesis(g, z, self.weight.detach())
+        return functional.synthesis(z, self.weight, self.stride[0])
 
 
 class _Analysis3d(nn.Conv3d):
     def forward(self, x):
-        g = ops.Geometry.make(x.shape[0], self.in_channels, self.out_channels, x.shape[2:],
-                              self.kernel_size, self.padding, self.stride[0])
-        return ops.analysis(g, x, self.weight.detach())
+        return functional.analysis(x, self.weight, self.stride[0])
 
 
 class _Synthesis3d(nn.ConvTranspose3d):
     def forward(self, z):
-        sp = tuple(d * self.stride[0] for d in z.shape[2:])
-        g = ops.Geometry.make(z.shape[0], self.out_channels, self.in_channels, sp,
-                              self.kernel_size, self.padding, self.stride[0])
-        return ops.synthesis(g, z, self.weight.detach())
+        return functional.synthesis(z, self.weight, self.stride[0])
 
 
 def _code_grid(spatial, s):
@@ -233,27 +219,14 @@ class CDLNet(_ISTANet):
 
 # ------------------------------------------------------------------------------------------ CSR
 def prox_CSR(u, z_prev, lambd, gamma):
-    """The reference's helper (net.py:229-242) on the device; lambd, gamma broadcastable to (N, M, 1, 1)."""
-    return _prox(u, z_prev, None, lambd, gamma, None)
+    """The reference's helper (net.py:229-242) on the device; lambd, gamma numbers or broadcastable to u; differentiable
+    in every tensor argument (functional.prox_csr)."""
+    return functional.prox_csr(u, z_prev, lambd, gamma)
 
 
 def prox_CSR_f2(u, z_prev, z_after, lambd, gamma1, gamma2):
-    """The reference's helper (net.py:244-262) on the device."""
-    return _prox(u, z_prev, z_after, lambd, gamma1, gamma2)
-
-
-def _prox(u, zp, za, lam, g1, g2):
-    N, M = u.shape[:2]
-    sp = tuple(u.shape[2:])
-    g = ops.Geometry.make(N, 1, M, sp, (1,) * len(sp), (0,) * len(sp), 1)
-
-    def rows(t):
-        t = torch.as_tensor(t, dtype=torch.float32, device=u.device)
-        while t.dim() < u.dim():
-            t = t.unsqueeze(0)
-        return torch.broadcast_to(t, (N, M) + (1,) * len(sp)).reshape(N, M).contiguous()
-
-    return ops.prox_csr(g, u, zp, rows(lam), rows(g1), za, rows(g2) if za is not None else None)
+    """The reference's helper (net.py:244-262) on the device (functional.prox_csr_f2)."""
+    return functional.prox_csr_f2(u, z_prev, z_after, lambd, gamma1, gamma2)
 
 
 class _CSRBase(_ISTANet):

@@ -239,6 +239,97 @@ def shrink(x, tau):
     return out
 
 
+def bcast_strides(shape, code_shape):
+    """cdl_bcast of a contiguous threshold of `shape` against `code_shape` = (N, M, *spatial): each of its first two axes
+    is 1 or full, and its spatial axes are all 1 (the row form) or all full.  Raises ValueError otherwise."""
+    shape, code_shape = tuple(int(v) for v in shape), tuple(int(v) for v in code_shape)
+    sp = code_shape[2:]
+    per_m = 1
+    for d in sp:
+        per_m *= d
+    ok = len(shape) == len(code_shape) and shape[0] in (1, code_shape[0]) and shape[1] in (1, code_shape[1])
+    spatial = ok and shape[2:] == sp and per_m > 1
+    if not ok or not (spatial or all(d == 1 for d in shape[2:])):
+        raise ValueError(f"threshold of shape {shape} is not a broadcast form of the code shape {code_shape}")
+    p = 1 if spatial else 0
+    dm = per_m if spatial else 1
+    m = dm if shape[1] > 1 else 0
+    n = (dm * shape[1] if shape[0] > 1 else 0)
+    return _lib.Bcast(n, m, p)
+
+
+def _thr(t, name, g_shape):
+    t = _dev(t, name)
+    return t, bcast_strides(t.shape, g_shape)
+
+
+def shrink_b(x, tau):
+    """ST(x, tau), tau a broadcast form of x's shape (bcast_strides) (cdl_shrink_b)."""
+    x = _dev(x, "x")
+    tau, st = _thr(tau, "tau", x.shape)
+    N, M = x.shape[:2]
+    out = torch.empty_like(x)
+    rc = _lib.lib().cdl_shrink_b(_ptr(x), _ptr(tau), ctypes.byref(st), _ptr(out), N, M, x.numel() // (N * M), _stream())
+    _lib.check(rc, "cdl_shrink_b")
+    return out
+
+
+def shrink_b_bwd(gup, x, tau, dtau_el=None):
+    """Reverse of shrink_b: returns gx = gup at the support; dtau_el (shaped like x, optional) receives the threshold
+    gradient per code element (cdl_shrink_b_bwd)."""
+    gup, x = _dev(gup, "gup"), _dev(x, "x")
+    tau, st = _thr(tau, "tau", x.shape)
+    assert gup.shape == x.shape and (dtau_el is None or (dtau_el.is_contiguous() and dtau_el.shape == x.shape))
+    N, M = x.shape[:2]
+    gx = torch.empty_like(x)
+    rc = _lib.lib().cdl_shrink_b_bwd(_ptr(gup), _ptr(x), _ptr(tau), ctypes.byref(st), _ptr(gx), _ptr(dtau_el), N, M,
+                                     x.numel() // (N * M), _stream())
+    _lib.check(rc, "cdl_shrink_b_bwd")
+    return gx
+
+
+def prox_csr_b(g: Geometry, u, z_prev, lam, gam1, z_after=None, gam2=None):
+    """prox_csr with thresholds of any broadcast form of the code shape (cdl_prox_csr_b)."""
+    u, z_prev, z_after = _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
+    _check_codes(g, u=u, z_prev=z_prev, z_after=z_after)
+    (lam, sl), (gam1, s1) = _thr(lam, "lam", g.code_shape()), _thr(gam1, "gam1", g.code_shape())
+    gam2, s2 = _thr(gam2, "gam2", g.code_shape()) if z_after is not None else (None, _lib.Bcast(0, 0, 0))
+    out = torch.empty_like(u)
+    rc = _lib.lib().cdl_prox_csr_b(ctypes.byref(g.c_struct()), _ptr(u), _ptr(z_prev), _ptr(z_after), _ptr(lam),
+                                   ctypes.byref(sl), _ptr(gam1), ctypes.byref(s1), _ptr(gam2), ctypes.byref(s2), _ptr(out),
+                                   _stream())
+    _lib.check(rc, "cdl_prox_csr_b")
+    return out
+
+
+def prox_csr_b_bwd(g: Geometry, gz, u, z_prev, lam, gam1, z_after=None, gam2=None, want=(True, True, True),
+                   gz_prev=None, gz_after=None):
+    """Reverse of prox_csr_b: returns (gu, dlam, dgam1, dgam2); gz_prev / gz_after (code-shaped, optional) are accumulated
+    into.  Each threshold gradient asked for in `want` comes before the reduction over the threshold's broadcast axes:
+    (N, M, 1..) row sums for a threshold without spatial extent, the code shape for one with."""
+    gz, u, z_prev, z_after = _dev(gz, "gz"), _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
+    _check_codes(g, gz=gz, u=u, z_prev=z_prev, z_after=z_after, gz_prev=gz_prev, gz_after=gz_after)
+    (lam, sl), (gam1, s1) = _thr(lam, "lam", g.code_shape()), _thr(gam1, "gam1", g.code_shape())
+    gam2, s2 = _thr(gam2, "gam2", g.code_shape()) if z_after is not None else (None, _lib.Bcast(0, 0, 0))
+    rows = (g.N, g.M) + (1,) * g.ndim
+
+    def buf(wanted, st):
+        return torch.empty(g.code_shape() if st.p else rows, device=gz.device, dtype=torch.float32) if wanted else None
+
+    dl, d1 = buf(want[0], sl), buf(want[1], s1)
+    d2 = buf(want[2], s2) if z_after is not None else None
+    gu = torch.empty_like(gz)
+    gs = g.c_struct()
+    n = int(_lib.lib().cdl_prox_csr_scratch_floats(ctypes.byref(gs)))
+    scratch = torch.empty(n, device=gz.device, dtype=torch.float32)
+    rc = _lib.lib().cdl_prox_csr_b_bwd(ctypes.byref(gs), _ptr(gz), _ptr(u), _ptr(z_prev), _ptr(z_after), _ptr(lam),
+                                       ctypes.byref(sl), _ptr(gam1), ctypes.byref(s1), _ptr(gam2), ctypes.byref(s2), _ptr(gu),
+                                       _ptr(gz_prev), _ptr(gz_after), _ptr(dl), _ptr(d1), _ptr(d2), _ptr(scratch), n,
+                                       _stream())
+    _lib.check(rc, "cdl_prox_csr_b_bwd")
+    return gu, dl, d1, d2
+
+
 def _check_map(g: Geometry, cmap, tslope=None, rows=1):
     """A noise-level map is a dense (N, 1, *code_spatial) tensor; its slope row(s) hold `rows` * M values."""
     if cmap is not None and tuple(cmap.shape) != (g.N, 1) + g.code_spatial:

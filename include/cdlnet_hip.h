@@ -107,9 +107,30 @@ int cdl_thresholds(const float *t /*K,2,M*/, const float *c /*N, nullable*/, flo
 
 /* Stand-alone ST(x, t) = sign(x)*relu(|x|-t) (net.py:11-14) over a code-like tensor:
  * out[i] = ST(x[i], tau[i / per_m]) for `rows` = N*M rows of `per_m` elements.  In the nets the
- * shrinkage is fused into cdl_analysis; this exists for callers of the reference's helper. */
+ * shrinkage is fused into cdl_analysis; this exists for callers of the reference's helper.
+ * This and the other pointwise passes (cdl_shrink_b*, cdl_prox_csr*) launch one thread per element and return
+ * CDL_EUNSUPPORTED for a tensor of 2^39 elements or more (2^31 workgroups). */
 int cdl_shrink(const float *x, const float *tau /*rows*/, float *out, int rows, size_t per_m,
                void *stream);
+
+/* ---- thresholds of any broadcast shape --------------------------------------
+ * The reference's ST / prox_CSR / prox_CSR_f2 take any threshold that broadcasts to the code shape (N, M, spatial..): a
+ * noise-level map enters as t[k,:1] + c * t[k,1:2] with c (N,1,H,W).  cdl_bcast holds the element strides of such a tensor
+ * over (sample, channel, code pixel): element (n, m, pix) reads thr[n*s.n + m*s.m + pix*s.p].  A stride is 0 on a
+ * broadcast axis and otherwise the dense stride of the contiguous tensor; the spatial axes are broadcast together (p = 0)
+ * or all present (p = 1: the caller expands a partly spatial threshold to the full code grid).  {M, 1, 0} is the row form
+ * of the entry points without _b, which are its callers.  Anything else is CDL_EINVAL. */
+typedef struct cdl_bcast {
+    long long n, m, p;
+} cdl_bcast;
+
+int cdl_shrink_b(const float *x, const float *tau, const cdl_bcast *s_tau, float *out, int N, int M, size_t per_m,
+                 void *stream);
+/* Reverse of cdl_shrink_b as autograd differentiates sign(x)*relu(|x|-t): gx = gup where x != 0 and |x| - t > 0, else 0
+ * (gx may alias gup), and, when not NULL, dtau_el[i] = -sign(x[i]) * gx[i]: the threshold gradient per code element,
+ * which the caller reduces over the threshold's broadcast axes. */
+int cdl_shrink_b_bwd(const float *gup, const float *x, const float *tau, const cdl_bcast *s_tau, float *gx,
+                     float *dtau_el /*nullable*/, int N, int M, size_t per_m, void *stream);
 
 /* ---- analysis half: F.conv2d / F.conv3d at net.py:85,87,200,205 and gabor.py:55 ------------
  *   acc  = alpha * corr(x ; w)                         x thin, w (M,C,P..), acc fat
@@ -266,6 +287,21 @@ int cdl_prox_csr_bwd(const cdl_geom *g, const float *gz, const float *u, const f
                      float *dgam1 /*2*M*/, float *dgam2 /*2*M, nullable*/, float *scratch,
                      size_t scratch_floats, void *stream);
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g);
+
+/* The two maps and their reverse with thresholds of any broadcast shape (cdl_bcast above; s_gam2 is read only with
+ * z_after).  The forward bits are those of the reference expression for every threshold shape.  In the reverse pass each
+ * of dlam, dgam1, dgam2 (nullable: not wanted) receives the gradient of its threshold before the reduction over its
+ * broadcast axes, which is the caller's: N*M row sums (fixed order) for a threshold without spatial extent (p = 0), one
+ * value per code element (N*M*code pixels) for one with (p = 1).  gu, gz_prev, gz_after, scratch: as cdl_prox_csr_bwd. */
+int cdl_prox_csr_b(const cdl_geom *g, const float *u, const float *z_prev, const float *z_after /*nullable*/,
+                   const float *lam, const cdl_bcast *s_lam, const float *gam1, const cdl_bcast *s_gam1,
+                   const float *gam2 /*nullable iff z_after is*/, const cdl_bcast *s_gam2, float *out, void *stream);
+int cdl_prox_csr_b_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev,
+                       const float *z_after /*nullable*/, const float *lam, const cdl_bcast *s_lam, const float *gam1,
+                       const cdl_bcast *s_gam1, const float *gam2 /*nullable*/, const cdl_bcast *s_gam2, float *gu,
+                       float *gz_prev /*nullable*/, float *gz_after /*nullable*/, float *dlam /*nullable*/,
+                       float *dgam1 /*nullable*/, float *dgam2 /*nullable*/, float *scratch, size_t scratch_floats,
+                       void *stream);
 
 /* ---- blind noise-level estimate --------------------------------------
  * model/nle.py:17-27 (nle_mad) with the filter of model/wvlt.py:13-41: sigma_hat[n] = median over (C,H',W') of

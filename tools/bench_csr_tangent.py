@@ -9,10 +9,14 @@ process after warming all of them (the protocol of tools/bench_sure.py):
     exact        the same step with mcsure="exact"
 
     python tools/bench_csr_tangent.py --steps 7 --warmup 2 [--out profiles/csr_tangent.json]
-    python tools/bench_csr_tangent.py --primal-only                   # what a tree without jvp_recurrent can run
+    python tools/bench_csr_tangent.py --primal-only                   # what a tree without jvp_recurrent can run: the
+                                                                      # primal forms and the supervised step
     python tools/bench_csr_tangent.py --parent PATH --pairs 5 --out profiles/csr_tangent.json
         # additionally: `--primal-only` children of this tree and of the tree at PATH, alternated, `pairs` of them; the
         # gate is: the medians of the two trees differ by no more than the parent's own run-to-run spread
+    python tools/bench_csr_tangent.py --blocks ...
+        # additionally (no gate): the both-neighbour CSR-f2 forward + backward at 1x1x128x128 written from the blocks of
+        # cva.functional against the net's own sweep
 
 Prints one JSON line."""
 import argparse
@@ -69,24 +73,62 @@ def measure(a):
                 v, zd = torch.randn_like(y), torch.randn_like(z0)
                 forms[f"tangent_{n}x{size}"] = lambda y=y, z0=z0, v=v, zd=zd: net.jvp_recurrent(y, v, z0, zd, z0, zd, 25.0)
         times = timed(forms, a.steps, a.warmup)
+    if a.blocks:
+        times.update(timed(block_forms(cva, net), a.steps, a.warmup))
+    # the supervised step also under --primal-only: k_prox_bwd is then on the clock of the comparison with a parent tree
+    torch.manual_seed(2)
+    csr = cva.CDLNet_CSR(K=30, M=169, P=9, s=2, C=1, t0=5e-3, adaptive=True, init=False).cuda()
+    with torch.no_grad():
+        for bank in (csr.A, csr.B, csr.A2, csr.B2):
+            for m in bank:
+                m.weight.mul_(0.02)
+        csr.t.fill_(2e-3)
+        csr.t2.fill_(2e-3)
+        csr.g.fill_(0.5)
+    opt = torch.optim.Adam(csr.parameters(), lr=1e-4)
+    clip = torch.stack([cva.utils.synthetic_clip((4, 1, 128, 128), seed=t) for t in range(2)], dim=2).cuda()
+    gen = torch.Generator().manual_seed(3)
+    step = lambda mode: cva.train_step_clip(csr, opt, clip, (20, 30), clip_grad=5e-2, generator=gen, mcsure=mode)
+    steps = {"supervised": lambda: step(False)}
     if not a.primal_only:
-        torch.manual_seed(2)
-        csr = cva.CDLNet_CSR(K=30, M=169, P=9, s=2, C=1, t0=5e-3, adaptive=True, init=False).cuda()
-        with torch.no_grad():
-            for bank in (csr.A, csr.B, csr.A2, csr.B2):
-                for m in bank:
-                    m.weight.mul_(0.02)
-            csr.t.fill_(2e-3)
-            csr.t2.fill_(2e-3)
-            csr.g.fill_(0.5)
-        opt = torch.optim.Adam(csr.parameters(), lr=1e-4)
-        clip = torch.stack([cva.utils.synthetic_clip((4, 1, 128, 128), seed=t) for t in range(2)], dim=2).cuda()
-        gen = torch.Generator().manual_seed(3)
-        step = lambda mode: cva.train_step_clip(csr, opt, clip, (20, 30), clip_grad=5e-2, generator=gen, mcsure=mode)
-        times.update(timed({"supervised": lambda: step(False), "exact": lambda: step("exact")}, a.steps, a.warmup))
+        steps["exact"] = lambda: step("exact")
+    times.update(timed(steps, a.steps, a.warmup))
     return {"ms": {f: round(statistics.median(t), 3) for f, t in times.items()},
             "spread_pct": {f: round(100.0 * (max(t) - min(t)) / statistics.median(t), 2) for f, t in times.items()},
             "all_ms": {f: [round(v, 3) for v in t] for f, t in times.items()}}
+
+
+def block_forms(cva, net):
+    """Forward + backward of the both-neighbour CDLNet_CSRf2 call at 1x1x128x128: the net's sweep, and the same loop written
+    from cva.functional (per-sample sigma, so that both compute the same thing)."""
+    import torch
+    F = cva.functional
+    y = torch.rand(1, 1, 128, 128, device="cuda")
+    with torch.no_grad():
+        _, z0 = net(y, None, None, 25.0)
+    K, s, c = net.K, net.s, 25.0 / 255.0
+    A, B = [m.weight for m in net.A], [m.weight for m in net.B]
+    thr = lambda p, k: p[k, :1] + c * p[k, 1:2]
+
+    def from_blocks():
+        yp, params, _ = F.pre_process(y, s)
+        z = None
+        for k in range(K):
+            if k == 0:
+                u = F.analysis(yp, A[0], s)
+            else:
+                u = F.analysis(F.synthesis(z, B[k], s, sub=yp), A[k], s, alpha=-1.0, add=z)
+            z = F.prox_csr_f2(u, z0, z0, thr(net.t, k), thr(net.g1, k), thr(net.g2, k))
+        return F.post_process(F.synthesis(z, B[0], s), params), z
+
+    def step(fwd):
+        for p in net.parameters():
+            p.grad = None
+        xhat, z = fwd()
+        (xhat.square().mean() + 0.05 * z.abs().mean()).backward()
+
+    return {"csrf2_fwd_bwd_net_1x128": lambda: step(lambda: net(y, z0, z0, 25.0)),
+            "csrf2_fwd_bwd_blocks_1x128": lambda: step(from_blocks)}
 
 
 def child(root, a):
@@ -104,6 +146,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--primal-only", action="store_true")
+    ap.add_argument("--blocks", action="store_true")
     ap.add_argument("--parent", default=None)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -122,11 +165,15 @@ def main():
                        "parent_spread_ms": round(max(p) - min(p), 3), "diff_ms": round(mt - mp, 3),
                        "within_parent_spread": abs(mt - mp) <= max(p) - min(p)}
         res["primal_vs_parent"] = gate
+        res["gate_passed"] = all(v["within_parent_spread"] for v in gate.values())
     res.update(measure(a))
     if not a.primal_only:
         ms = res["ms"]
         res["tangent_over_primal"] = {f"{n}x{s}": round(ms[f"tangent_{n}x{s}"] / ms[f"primal_{n}x{s}"], 3) for n, s in SIZES}
         res["exact_over_supervised"] = round(ms["exact"] / ms["supervised"], 3)
+    if a.blocks:
+        ms = res["ms"]
+        res["blocks_over_net"] = round(ms["csrf2_fwd_bwd_blocks_1x128"] / ms["csrf2_fwd_bwd_net_1x128"], 3)
     line = json.dumps(res)
     print(line)
     if a.out:
