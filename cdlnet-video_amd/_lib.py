@@ -58,8 +58,8 @@ SIGNATURES = {
     "cdl_sigma_grad": [_G, _P, _P, _P, _P, _I, _P],
     "cdl_analysis_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],      # .., cmap, tslope, stream
     "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P],   # .., cmap, stream
-    "cdl_analysis_prox_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
-    "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cdl_analysis_prox_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],   # .., cmap, tslope, stream
+    "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],                            # .., cmap, tslope, stream
     "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P, _P, _P],                  # .., cmap, tslope, stream
     "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_tangent_forward": [_G, _I] + [_P] * 10 + [ctypes.c_size_t, _P],
@@ -75,7 +75,7 @@ SIGNATURES = {
     "cdl_residual_forward": [_G, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_residual_backward": [_G] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_prox_csr": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cdl_prox_csr_bwd": [_G] + [_P] * 15 + [ctypes.c_size_t, _P],
+    "cdl_prox_csr_bwd": [_G] + [_P] * 15 + [ctypes.c_size_t, _P, _P, _P, _P, _P],              # .., cmap, tslope, dcmap, dsum_n, stream
     "cdl_prox_csr_tangent": [_G] + [_P] * 11,
     # thresholds of any broadcast shape (each threshold pointer is followed by its strides)
     "cdl_shrink_b": [_P, _P, _B, _P, _I, _I, ctypes.c_size_t, _P],

@@ -59,7 +59,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const float *base
 
 // MAP: the thresholds follow a noise-level map (cdl_map_args: thr = tau[n,m] + cmap[n,pix] * tslope[m], every thread
 // keeps its pixel's map value in a register); in reverse mode a second, map-weighted partial per (channel, tile) goes to
-// dtpw.  A compile-time variant: the other instantiations are the kernels they were.
+// dtpw.  A compile-time variant: the other instantiations are the kernels they were.  PROX and MAP: the three thresholds
+// of the CSR epilogue follow the map (cdl_prox_apply_map; tau is null, so the slopes are read from mp.tslope, not from LDS).
 template <int PH, int PW, int SW, int MT, bool PROX, bool REV, bool MAP>
 __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restrict__ x,
                                                const uint4 *__restrict__ frags, float alpha,
@@ -360,7 +361,8 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                     const int row = n * g.M + m;
                     const float ts = tau_s[32 * R + chh + 2 * (j0 + j)];     // (unused when tau == nullptr)
                     if (ix[j] >= 0)
-                        out_n[ix[j]] = PROX ? cdl_prox_apply(px, u, nbase + ix[j], row)
+                        out_n[ix[j]] = PROX ? (MAP ? cdl_prox_apply_map(px, mp, u, nbase + ix[j], row, m, g.M, cm)
+                                                   : cdl_prox_apply(px, u, nbase + ix[j], row))
                                      : MAP ? cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[32 * R + chh + 2 * (j0 + j)]))
                                             : (tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u);
                 }
@@ -446,6 +448,7 @@ int launch_mt(const cdl_geom *g, const Plan &p, const float *x, const uint4 *fra
               const float *zsup, float *dtp, const cdl_map_args &mp, float *dtpw)
 {
     const cdl_map_args none{nullptr, nullptr};
+    if (px.zp && mp.cmap) return launch_mtp<PH, PW, SW, MT, true, false, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, mp, nullptr);
     if (px.zp) return launch_mtp<PH, PW, SW, MT, true, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, none, nullptr);
     if (zsup && mp.cmap) return launch_mtp<PH, PW, SW, MT, false, true, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
     if (zsup) return launch_mtp<PH, PW, SW, MT, false, true, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, none, nullptr);

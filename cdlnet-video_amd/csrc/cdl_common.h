@@ -126,7 +126,7 @@ __device__ __forceinline__ float cdl_prox_apply(const cdl_prox_args &px, float u
 // `t0 + c * t1` does (model/net.py:83), so the thresholds are the reference's bit for bit.
 struct cdl_map_args {
     const float *cmap;      // (N, code pixels); nullptr: no map
-    const float *tslope;    // (M)
+    const float *tslope;    // (M); with the CSR epilogue (3, M): the slopes of lam, gam1, gam2
 };
 
 __device__ __forceinline__ float cdl_map_threshold(float t0, float c, float slope)
@@ -134,6 +134,19 @@ __device__ __forceinline__ float cdl_map_threshold(float t0, float c, float slop
 #pragma clang fp contract(off)
     const float prod = c * slope;
     return t0 + prod;
+}
+
+// The CSR epilogue under a noise-level map: all three threshold families follow the map, px.lam /
+// g1 / g2 holding the constant parts per (sample, channel) row and mp.tslope the 3*M slopes of lam, gam1, gam2 (the third
+// plane unread without z_after).  cm: the map at this element's pixel.
+__device__ __forceinline__ float cdl_prox_apply_map(const cdl_prox_args &px, const cdl_map_args &mp, float u, size_t idx,
+                                                    int row, int m, int M, float cm)
+{
+    if (px.u_out) px.u_out[idx] = u;
+    const float lam = cdl_map_threshold(px.lam[row], cm, mp.tslope[m]);
+    const float g1 = cdl_map_threshold(px.g1[row], cm, mp.tslope[M + m]);
+    return px.za ? cdl_prox_csr2(u, px.zp[idx], px.za[idx], lam, g1, cdl_map_threshold(px.g2[row], cm, mp.tslope[2 * M + m])).z
+                 : cdl_prox_csr1(u, px.zp[idx], lam, g1).z;
 }
 
 __host__ __device__ __forceinline__ int cdl_floordiv(int a, int b)

@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void k_analysis(cdl_geom g, const float *__res
                     }
                     float u = fmaf(alpha, acc[j], base);
                     if (MAP)
-                        out[idx] = cdl_shrink(u, cdl_map_threshold(tau[n * g.M + m], cm, mp.tslope[m]));
+                        out[idx] = px.zp ? cdl_prox_apply_map(px, mp, u, idx, n * g.M + m, m, g.M, cm)
+                                         : cdl_shrink(u, cdl_map_threshold(tau[n * g.M + m], cm, mp.tslope[m]));
                     else
                     out[idx] = px.zp ? cdl_prox_apply(px, u, idx, n * g.M + m)
                                      : (tau ? cdl_shrink(u, tau[n * g.M + m]) : u);
@@ -866,20 +867,23 @@ int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float
 
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                      const float *gam2, float *u_out, float *out, void *stream)
+                      const float *gam2, float *u_out, float *out, const float *cmap, const float *tslope, void *stream)
 {
-    return cdl_analysis_prox_ws(g, x, w, alpha, zin, z_prev, z_after, lam, gam1, gam2, u_out, out, nullptr, 0, stream);
+    return cdl_analysis_prox_ws(g, x, w, alpha, zin, z_prev, z_after, lam, gam1, gam2, u_out, out, nullptr, 0, cmap, tslope,
+                                stream);
 }
 
 int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                          const float *z_prev, const float *z_after, const float *lam, const float *gam1,
                          const float *gam2, float *u_out, float *out, float *workspace, size_t workspace_floats,
-                         void *stream)
+                         const float *cmap, const float *tslope, void *stream)
 {
     if (!z_prev || !lam || !gam1 || (z_after && !gam2)) return CDL_EINVAL;
     if (u_out && (u_out == out || u_out == zin)) return CDL_EINVAL;
+    if ((cmap == nullptr) != (tslope == nullptr)) return CDL_EINVAL;
     const cdl_prox_args px{z_prev, z_after, lam, gam1, gam2, u_out};
-    return analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, px, workspace, workspace_floats, stream);
+    return analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, px, workspace, workspace_floats, stream,
+                         cdl_map_args{cmap, tslope});
 }
 
 int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
@@ -913,7 +917,7 @@ static int analysis_impl(const cdl_geom *g, const float *x, const float *w, floa
     if (!cdl_geom_ok(g) || !x || !w || !out) return CDL_EINVAL;
     if (out == zin) return CDL_EINVAL;
     if (gate && !zin) return CDL_EINVAL;
-    if (mp.cmap && (!mp.tslope || !tau || px.zp)) return CDL_EINVAL;   // the map is a form of the ST epilogue only
+    if (mp.cmap && (!mp.tslope || (!tau && !px.zp))) return CDL_EINVAL;   // the map needs its slopes and constant parts
     if (!cdl_opts().no_tiled) {
         if (!px.zp && !mp.cmap && mfma_dense_enabled()) {   // (the dense tier's analyses carry no shrinkage map)
             const int rcd = cdl_dense_conv(g, 0, x, nullptr, w, alpha, zin, gate, nullptr, nullptr, tau, 0, nullptr, out, ws,

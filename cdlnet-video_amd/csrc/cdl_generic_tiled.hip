@@ -101,7 +101,8 @@ __global__ __launch_bounds__(256) void k_analysis_t(cdl_geom g, const float *__r
                     }
                     const float u = fmaf(alpha, acc[j][p], base);
                     if (MAP)
-                        out[rowi + zx] = cdl_shrink(u, cdl_map_threshold(t, cm[p], ts));
+                        out[rowi + zx] = px.zp ? cdl_prox_apply_map(px, mp, u, rowi + zx, n * g.M + m, m, g.M, cm[p])
+                                               : cdl_shrink(u, cdl_map_threshold(t, cm[p], ts));
                     else
                     out[rowi + zx] = px.zp ? cdl_prox_apply(px, u, rowi + zx, n * g.M + m) : (tau ? cdl_shrink(u, t) : u);
                 }

@@ -136,9 +136,152 @@ __device__ __forceinline__ Sums3 prox_bwd_span(const float *__restrict__ gz, con
     return Sums3{sl, s1, s2};
 }
 
+// ---- the reverse pass under a noise-level map: lam = lam0[n,m] + cmap[n,pix] * tsl[m], and the
+// same for gam1, gam2.  The threshold sums run over pixels, the map gradient over channels, so one workgroup takes MAP_PIX
+// pixels of one sample (MAP_PXT per thread, the map values in registers) and walks a range of channels: the map gradient
+// accumulates in registers, channel after channel, and each wave leaves its [sum s, sum cmap s] of every family per channel
+// (no barrier, no LDS).  prox_fold_map and dcmap_fold add the partials in a fixed order; nothing fat is written beside
+// gu and the neighbour gradients.  These are the map forms of k_prox_bwd and k_prox_fold: each is entered from its kernel
+// on a launch-uniform branch (ProxMap::cmap), with a grid of its own shape, so the reverse pass stays one launch pair.
+struct ProxMap {
+    const float *cmap, *tsl;   // (N, pixels), (3, M); cmap == nullptr: the row / broadcast forms
+    float *dcp, *dcmap;        // map-gradient partials of the channel ranges (scratch), dL/dcmap (both nullable)
+    int N, chunks, MS;         // samples, pixel chunks, channel ranges: k_prox_bwd's grid is their product
+    size_t NP;                 // N * pixels: the elements of dcmap
+};
+constexpr int MAP_PXT = 4;
+constexpr int MAP_PIX = 256 * MAP_PXT;
+
+template <bool F2>
+__device__ __forceinline__ void prox_bwd_map(const float *gz, const float *__restrict__ u, const float *__restrict__ zp,
+                                             const float *__restrict__ za, const float *__restrict__ lam,
+                                             const float *__restrict__ g1, const float *__restrict__ g2, float *gu,
+                                             float *__restrict__ gzp, float *__restrict__ gza, float *__restrict__ part,
+                                             size_t per_m, int M, const ProxMap &mp)
+{
+    constexpr int NQ = F2 ? 6 : 4;
+    const float *__restrict__ cmap = mp.cmap, *__restrict__ tsl = mp.tsl;
+    float *__restrict__ dcp = mp.dcp;
+    const int N = mp.N, chunks = mp.chunks, MS = mp.MS;
+    int b = blockIdx.x;
+    const int chunk = b % chunks;
+    b /= chunks;
+    const int ms = b % MS, n = b / MS;
+    const int mper = (M + MS - 1) / MS, m_lo = ms * mper, m_hi = m_lo + mper < M ? m_lo + mper : M;
+    const size_t j0 = (size_t)chunk * MAP_PIX + threadIdx.x;
+    float cm[MAP_PXT], dc[MAP_PXT];
+#pragma unroll
+    for (int p = 0; p < MAP_PXT; ++p) {
+        const size_t j = j0 + (size_t)p * 256;
+        cm[p] = j < per_m ? cmap[(size_t)n * per_m + j] : 0.0f;
+        dc[p] = 0.0f;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int m = m_lo; m < m_hi; ++m) {
+        const size_t row = (size_t)n * M + m, base = row * per_m;
+        const float l0 = lam[row], a10 = g1[row], a20 = F2 ? g2[row] : 0.0f;
+        const float tl = tsl[m], t1 = tsl[M + m], t2 = F2 ? tsl[2 * M + m] : 0.0f;
+        float sq[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int p = 0; p < MAP_PXT; ++p) {
+            const size_t j = j0 + (size_t)p * 256;
+            if (j >= per_m) continue;
+            const size_t i = base + j;
+            const float c = cm[p];
+            const float l = cdl_map_threshold(l0, c, tl), a1 = cdl_map_threshold(a10, c, t1);
+            const float g = gz[i], uu = u[i], pv = zp[i];
+            float el, e1, e2 = 0.0f;                                  // the element's threshold gradients (prox_bwd_span)
+            if (!F2) {
+                const Prox1 q = prox1(uu, pv, l, a1);
+                const float gm = g * st_dx(q.m, l);
+                const float ga = gm * st_dx(q.a, q.tg);
+                const float gtg = gm * st_dt(q.a, q.tg);
+                gu[i] = ga;
+                if (gzp) gzp[i] += gm - ga;
+                el = g * st_dt(q.m, l) + gtg * a1 + (gm - ga) * q.s;
+                e1 = gtg * l;
+            } else {
+                const float a2 = cdl_map_threshold(a20, c, t2);
+                const Prox2 q = prox2(uu, pv, za[i], l, a1, a2);
+                const float gm = g * st_dx(q.m, l);
+                const float gb = gm * st_dx(q.b, q.t2);
+                const float gt2 = gm * st_dt(q.b, q.t2);
+                const float ga = gb * st_dx(q.a, q.t1);
+                const float gt1 = gb * st_dt(q.a, q.t1);
+                const float gcb = gm - gb;
+                gu[i] = ga;
+                if (gzp) gzp[i] -= ga;
+                if (gza) gza[i] += gcb;
+                const float p1 = (gb - gm) * q.sa + gcb * q.sap + gt1;
+                const float p2 = -ga * q.spa + gt2;
+                el = g * st_dt(q.m, l) - ga * q.sp + gcb * q.sa_ + p1 * a1 + p2 * a2;
+                e1 = p1 * l;
+                e2 = p2 * l;
+            }
+            sq[0] += el;
+            sq[1] = fmaf(c, el, sq[1]);
+            sq[2] += e1;
+            sq[3] = fmaf(c, e1, sq[3]);
+            if (F2) {
+                sq[4] += e2;
+                sq[5] = fmaf(c, e2, sq[5]);
+            }
+            dc[p] += fmaf(t2, e2, fmaf(t1, e1, tl * el));
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            for (int off = 32; off > 0; off >>= 1) sq[q] += __shfl_down(sq[q], off, 64);
+        if (lane == 0) {
+            float *dst = part + ((row * chunks + chunk) * 4 + wv) * 6;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) dst[q] = sq[q];
+        }
+    }
+    if (!dcp) return;
+#pragma unroll
+    for (int p = 0; p < MAP_PXT; ++p) {
+        const size_t j = j0 + (size_t)p * 256;
+        if (j < per_m) dcp[((size_t)ms * N + n) * per_m + j] = dc[p];
+    }
+}
+
+// d(t[k,0,m]) = sum_{n,pix} s, d(t[k,1,m]) = sum_{n,pix} cmap s for the three families from the S wave partials of every
+// (n, m) row: one wave (a 64-thread workgroup of k_prox_fold) per channel, the lanes split the partials, a fixed exchange
+// tree adds them, samples in order.
+__device__ __forceinline__ void prox_fold_map(const float *__restrict__ part, float *__restrict__ dlam,
+                                              float *__restrict__ dg1, float *__restrict__ dg2, int N, int M, int S, int m)
+{
+    const int lane = threadIdx.x;
+    const int NQ = dg2 ? 6 : 4;
+    float a[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int n = 0; n < N; ++n) {
+        const float *pr = part + ((size_t)n * M + m) * S * 6;
+        for (int q = 0; q < NQ; ++q) {
+            float v = 0.0f;
+            for (int s = lane; s < S; s += 64) v += pr[(size_t)s * 6 + q];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            a[q] += v;
+        }
+    }
+    if (lane != 0) return;
+    dlam[m] = a[0], dlam[M + m] = a[1];
+    dg1[m] = a[2], dg1[M + m] = a[3];
+    if (dg2) dg2[m] = a[4], dg2[M + m] = a[5];
+}
+
+// dcmap[n,pix] += sum over the MS channel ranges of their partial map gradients, in order (element o of N * pixels)
+__device__ __forceinline__ void dcmap_fold(const float *__restrict__ dcp, float *__restrict__ dcmap, size_t NP, int MS, size_t o)
+{
+    if (o >= NP) return;
+    float v = 0.0f;
+    for (int ms = 0; ms < MS; ++ms) v += dcp[(size_t)ms * NP + o];
+    dcmap[o] += v;
+}
+
 // Reverse of the map for one (row, split): gu, the neighbour-code gradients (accumulated: a neighbour
 // feeds every iteration) and this split's three threshold sums into part[(row*S + split)*3 + {0,1,2}].
 // M == 0: thresholds in the row form (index = row); M > 0: in the broadcast form `bs`, M channels.  el_*: see prox_bwd_span.
+// mp.cmap: the map form (prox_bwd_map), M the channel count, the grid mp.chunks * mp.MS * mp.N workgroups.
 __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, const float *__restrict__ u,
                                                   const float *__restrict__ zp, const float *__restrict__ za,
                                                   const float *__restrict__ lam, const float *__restrict__ g1,
@@ -146,8 +289,15 @@ __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, 
                                                   float *__restrict__ gzp, float *__restrict__ gza,
                                                   float *__restrict__ part, size_t per_m, int S, int M, Bcast3 bs,
                                                   float *__restrict__ el_l, float *__restrict__ el_1,
-                                                  float *__restrict__ el_2)
+                                                  float *__restrict__ el_2, ProxMap mp)
 {
+    if (mp.cmap) {                                                   // uniform: the whole launch takes the map form
+        if (za)
+            prox_bwd_map<true>(gz, u, zp, za, lam, g1, g2, gu, gzp, gza, part, per_m, M, mp);
+        else
+            prox_bwd_map<false>(gz, u, zp, nullptr, lam, g1, nullptr, gu, gzp, nullptr, part, per_m, M, mp);
+        return;
+    }
     __shared__ float red[3][4];
     const int row = blockIdx.x / S, sp = blockIdx.x % S;
     const size_t chunk = (per_m + S - 1) / S;
@@ -184,10 +334,18 @@ __global__ __launch_bounds__(256) void k_prox_bwd(const float *__restrict__ gz, 
 
 // d(t[k,0,m]) = sum_n s[n,m], d(t[k,1,m]) = sum_n c[n] s[n,m] for each of the three threshold families
 // (lam = t[k,0] + c t[k,1] etc., net.py:444-452).  One thread per (family, m); fixed order.  slope == 0: only the first row
-// is written (the per-row sums of the broadcast form: N = 1, M = rows).
+// is written (the per-row sums of the broadcast form: N = 1, M = rows).  dsum_n (nullable): see below.
 __global__ void k_prox_fold(const float *__restrict__ part, const float *__restrict__ c, float *__restrict__ dlam,
-                            float *__restrict__ dg1, float *__restrict__ dg2, int N, int M, int S, int slope)
+                            float *__restrict__ dg1, float *__restrict__ dg2, int N, int M, int S, int slope,
+                            float *__restrict__ dsum_n, ProxMap mp)
 {
+    if (mp.cmap) {               // the map form: workgroup m < M folds channel m (S wave partials per row), the others dcmap
+        if ((int)blockIdx.x < M)
+            prox_fold_map(part, dlam, dg1, dg2, N, M, S, (int)blockIdx.x);
+        else if (mp.dcmap)
+            dcmap_fold(mp.dcp, mp.dcmap, mp.NP, mp.MS, (size_t)(blockIdx.x - M) * 64 + threadIdx.x);
+        return;
+    }
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 3 * M) return;
     const int fam = i / M, m = i % M;
@@ -197,11 +355,24 @@ __global__ void k_prox_fold(const float *__restrict__ part, const float *__restr
     for (int n = 0; n < N; ++n) {
         float v = 0.0f;
         for (int s = 0; s < S; ++s) v += part[((size_t)(n * M + m) * S + s) * 3 + fam];
+        if (dsum_n) dsum_n[((size_t)fam * N + n) * M + m] = v;      // the sums per sample, (3, N, M): dL/dc[n] is formed from them
         a0 += v;
         if (c) a1 = fmaf(c[n], v, a1);
     }
     dst[m] = a0;
     if (slope) dst[M + m] = a1;
+}
+
+size_t map_chunks(size_t per_m) { return (per_m + MAP_PIX - 1) / MAP_PIX; }
+
+// channel ranges of the map kernel: about 1024 workgroups, at least 8 channels each
+int map_msplits(int N, int M, size_t chunks)
+{
+    const size_t wgs = (size_t)N * chunks;
+    size_t MS = (1024 + wgs - 1) / wgs;
+    const size_t most = (size_t)(M + 7) / 8;
+    if (MS > most) MS = most;
+    return MS < 1 ? 1 : (int)MS;
 }
 
 int splits_for(int rows, size_t per_m)
@@ -267,25 +438,37 @@ int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, con
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return 0;
-    return (size_t)g->N * g->M * splits_for(g->N * g->M, code_elems(g)) * 3;
+    const size_t per_m = code_elems(g), chunks = map_chunks(per_m);
+    const size_t rowf = (size_t)g->N * g->M * splits_for(g->N * g->M, per_m) * 3;
+    // with a map: 4 wave partials of 6 sums per (row, pixel chunk), then the map-gradient partials of the channel ranges
+    const size_t mapf = (size_t)g->N * g->M * chunks * 4 * 6 + (size_t)map_msplits(g->N, g->M, chunks) * g->N * per_m;
+    return rowf > mapf ? rowf : mapf;
 }
 
 // The one launch pair of the reverse pass.  fold_N x fold_M = rows: (N, M) with c folds the row sums into the (2, M)
-// parameter slices; (1, rows) without slope leaves them per row.  A NULL d* is not written.
+// parameter slices; (1, rows) without slope leaves them per row.  A NULL d* is not written.  mp.cmap: the map form of
+// both kernels (prox_bwd_map; prox_fold_map with dcmap_fold behind it), each on a grid of its own shape.
 static int launch_prox_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev, const float *z_after,
                            const float *lam, const float *gam1, const float *gam2, const Bcast3 &bs, const float *c,
                            float *gu, float *gz_prev, float *gz_after, float *dlam, float *dgam1, float *dgam2,
                            float *el_l, float *el_1, float *el_2, float *scratch, int fold_N, int fold_M, int slope,
-                           void *stream)
+                           void *stream, float *dsum_n = nullptr, const ProxMap &mp = ProxMap{})
 {
     const size_t per_m = code_elems(g);
-    const int rows = g->N * g->M, Sp = splits_for(rows, per_m);
+    const int rows = g->N * g->M;
     const bool rowform = is_row(bs.lam, g->M) && is_row(bs.g1, g->M) && (!z_after || is_row(bs.g2, g->M));
-    k_prox_bwd<<<(unsigned)(rows * Sp), 256, 0, S(stream)>>>(gz, u, z_prev, z_after, lam, gam1, gam2, gu, gz_prev, gz_after,
-                                                             scratch, per_m, Sp, rowform ? 0 : g->M, bs, el_l, el_1, el_2);
+    // the partials per (n, m) row that the fold reads: the splits of the row forms, four waves per pixel chunk of the map's
+    const int Sp = mp.cmap ? mp.chunks * 4 : splits_for(rows, per_m);
+    const size_t wgs = mp.cmap ? (size_t)mp.chunks * mp.MS * mp.N : (size_t)rows * Sp;
+    size_t folds = (size_t)(3 * fold_M + 63) / 64;
+    if (mp.cmap) folds = (size_t)g->M + (mp.dcmap ? (mp.NP + 63) / 64 : 0);
+    if (wgs >= ((size_t)1 << 31) || folds >= ((size_t)1 << 31)) return CDL_EUNSUPPORTED;
+    if (mp.cmap) CDL_TRACE_NOTE("map MS=%d chunks=%d", mp.MS, mp.chunks);
+    k_prox_bwd<<<(unsigned)wgs, 256, 0, S(stream)>>>(gz, u, z_prev, z_after, lam, gam1, gam2, gu, gz_prev, gz_after, scratch,
+                                                     per_m, Sp, (rowform && !mp.cmap) ? 0 : g->M, bs, el_l, el_1, el_2, mp);
     CDL_LAUNCH_CHECK();
     if (!dlam && !dgam1 && !dgam2) return 0;
-    k_prox_fold<<<(3 * fold_M + 63) / 64, 64, 0, S(stream)>>>(scratch, c, dlam, dgam1, dgam2, fold_N, fold_M, Sp, slope);
+    k_prox_fold<<<(unsigned)folds, 64, 0, S(stream)>>>(scratch, c, dlam, dgam1, dgam2, fold_N, fold_M, Sp, slope, dsum_n, mp);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -293,16 +476,26 @@ static int launch_prox_bwd(const cdl_geom *g, const float *gz, const float *u, c
 int cdl_prox_csr_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev,
                      const float *z_after, const float *lam, const float *gam1, const float *gam2,
                      const float *c, float *gu, float *gz_prev, float *gz_after, float *dlam, float *dgam1,
-                     float *dgam2, float *scratch, size_t scratch_floats, void *stream)
+                     float *dgam2, float *scratch, size_t scratch_floats, const float *cmap, const float *tslope,
+                     float *dcmap, float *dsum_n, void *stream)
 {
     if (!cdl_geom_ok(g) || !gz || !u || !z_prev || !lam || !gam1 || !gu || !dlam || !dgam1 || !scratch)
         return CDL_EINVAL;
     if (z_after && (!gam2 || !dgam2)) return CDL_EINVAL;
     if (!z_after && gz_after) return CDL_EINVAL;
     if (scratch_floats < cdl_prox_csr_scratch_floats(g)) return CDL_EINVAL;
+    if (cmap ? (!tslope || c || dsum_n) : (tslope || dcmap)) return CDL_EINVAL;   // a map replaces c; dcmap where dsum_n was
+    ProxMap mp{};
+    if (cmap) {
+        const size_t per_m = code_elems(g), chunks = map_chunks(per_m);
+        if (chunks >= ((size_t)1 << 28)) return CDL_EUNSUPPORTED;
+        // scratch: the wave partials of every (row, pixel chunk), then the map-gradient partials of the channel ranges
+        mp = ProxMap{cmap, tslope, dcmap ? scratch + (size_t)g->N * g->M * chunks * 4 * 6 : nullptr, dcmap, g->N, (int)chunks,
+                     map_msplits(g->N, g->M, chunks), (size_t)g->N * per_m};
+    }
     const Bcast3 bs{ROW(g->M), ROW(g->M), ROW(g->M)};
     return launch_prox_bwd(g, gz, u, z_prev, z_after, lam, gam1, gam2, bs, c, gu, gz_prev, gz_after, dlam, dgam1,
-                           z_after ? dgam2 : nullptr, nullptr, nullptr, nullptr, scratch, g->N, g->M, 1, stream);
+                           z_after ? dgam2 : nullptr, nullptr, nullptr, nullptr, scratch, g->N, g->M, 1, stream, dsum_n, mp);
 }
 
 int cdl_prox_csr_b_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev, const float *z_after,

@@ -35,7 +35,7 @@ int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mas
                      const float *tslope, void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !yp || !tau || !wA || !wB || !z || !xp || (K > 1 && !r)) return CDL_EINVAL;
-    if (cmap && (!tslope || z_prev)) return CDL_EINVAL;              // noise-level maps: the plain loop only
+    if (cmap && !tslope) return CDL_EINVAL;                          // with z_prev: the (K, 3, M) slopes of lam, gam1, gam2
     if (z_prev ? (!gam1 || (z_after && !gam2)) : (z_after || u)) return CDL_EINVAL;
     const size_t NM = (size_t)g->N * g->M;
     for (int k = 0; k < K; ++k) {
@@ -50,7 +50,7 @@ int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mas
         if (z_prev)
             CDL_TRY(cdl_analysis_prox_ws(g, x, wA[k], alpha, zin, z_prev, z_after, tau + k * NM, gam1 + k * NM,
                                          gam2 ? gam2 + k * NM : nullptr, u ? u[k] : nullptr, z[k], scratch,
-                                         scratch_floats, stream));
+                                         scratch_floats, cmap, cmap ? tslope + (size_t)k * 3 * g->M : nullptr, stream));
         else
             CDL_TRY(cdl_analysis_ws(g, x, wA[k], alpha, zin, nullptr, tau + k * NM, z[k], scratch, scratch_floats,
                                     cmap, cmap ? tslope + (size_t)k * g->M : nullptr, stream));
@@ -73,12 +73,16 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
     if (!g_xp && !g_z) return CDL_EINVAL;
     if (z_prev ? (!u || !lam || !gam1 || !dg1 || (z_after && (!gam2 || !dg2))) : (z_after != nullptr)) return CDL_EINVAL;
     if (scratch_floats < cdl_ista_scratch_floats(g)) return CDL_EINVAL;
-    if (z_prev && (dyp || dtau || cmap || dcmap)) return CDL_EINVAL;   // data gradients, noise-level maps: the plain loop only
     if (cmap ? (c || dtau || (dcmap && !tslope)) : (dcmap != nullptr)) return CDL_EINVAL;   // a map replaces c; dcmap where dtau was
+    if (z_prev && cmap && !tslope) return CDL_EINVAL;                  // the CSR maps read their thresholds' slopes
     const size_t NM = (size_t)g->N * g->M, M = g->M;
     const size_t code = NM * (size_t)(g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
     const size_t flen = (size_t)g->M * g->C * g->Pd * g->Ph * g->Pw;
     float *gk = gbuf0, *other = gbuf1;
+    if (z_prev && dcmap) {       // cdl_prox_csr_bwd adds every iteration's map gradient to it
+        const hipError_t e = hipMemsetAsync(dcmap, 0, code / M * sizeof(float), S(stream));
+        if (e != hipSuccess) return -(int)e;
+    }
     // Plain loop (no neighbour codes): the analysis that produces dL/dz_k also gates it by the support of z_k and
     // reduces the threshold gradients of iteration k (cdl_analysis_rev_ws) -- the separate gate / threshold pass re-read
     // and re-wrote the tensor the analysis had just written (3 of the reverse sweep's fat passes per iteration).
@@ -103,15 +107,16 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
         if (z_prev) {            // gk: dL/dz_{k+1} -> dL/du_k in place; neighbour and threshold gradients
             CDL_TRY(cdl_prox_csr_bwd(g, gk, u[k], z_prev, z_after, lam + k * NM, gam1 + k * NM,
                                      gam2 ? gam2 + k * NM : nullptr, c, gk, gz_prev, gz_after, dt + k * 2 * M,
-                                     dg1 + k * 2 * M, dg2 ? dg2 + k * 2 * M : nullptr, scratch, scratch_floats,
-                                     stream));
+                                     dg1 + k * 2 * M, dg2 ? dg2 + k * 2 * M : nullptr, scratch, scratch_floats, cmap,
+                                     cmap ? tslope + (size_t)k * 3 * M : nullptr, dcmap,
+                                     dtau ? dtau + (size_t)k * 3 * NM : nullptr, stream));
         } else if (!gated) {
             // threshold gradients, and gk gated in place by the support of z_{k+1} in the same pass: the synthesis,
             // the filter gradient and the analysis below then read no gate (3 fat reads less per iteration)
             CDL_TRY(cdl_tau_grad_gate(g, gk, z[k], c, dt + k * 2 * M, dt + k * 2 * M + M, dtau ? dtau + k * NM : nullptr,
                                       scratch, cmap, stream));
         }
-        if (dcmap)               // gk is du_k here: dcmap (= at k = K-1, +=) sum_m t[k,1,m] (-sign(z_{k+1}) du_k)
+        if (dcmap && !z_prev)    // gk is du_k here: dcmap (= at k = K-1, +=) sum_m t[k,1,m] (-sign(z_{k+1}) du_k)
             CDL_TRY(cdl_sigma_grad(g, gk, z[k], tslope + (size_t)k * M, dcmap, k < K - 1, stream));
         if (k == 0) {
             CDL_TRY(cdl_wgrad(g, gk, gate, yp, 1.0f, dA[0], scratch, scratch_floats, stream));

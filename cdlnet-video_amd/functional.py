@@ -19,7 +19,7 @@ from torch.autograd.function import once_differentiable
 from . import loop, ops
 
 __all__ = ["analysis", "synthesis", "shrink", "ST", "prox_csr", "prox_csr_f2", "analysis_shrink", "pre_process",
-           "post_process"]
+           "post_process"]      # section 23's blocks (the list is pinned); analysis_prox and ista_csr (section 24) are public beside it
 
 
 # ------------------------------------------------------------------------------------------ argument checks
@@ -306,6 +306,133 @@ def analysis_shrink(x, w, t, stride=1, alpha=1.0, add=None):
         tau = tau.reshape(1, 1).expand(g.N, g.M).contiguous()
     _on_device("analysis_shrink", x=x, w=w, add=add)
     return _AnalysisShrink.apply(x, w, tau, add, g, float(alpha))
+
+
+# ------------------------------------------------------------------------------------------ analysis + CSR map
+@loop._arithmetic_aware
+class _AnalysisProx(torch.autograd.Function):
+    """(x, w, add | None, z_prev, z_after | None, thr, slopes | None, cmap | None) -> z = prox(add + alpha * A x), the CSR
+    map in the analysis kernel's epilogue.  Row form: thr (3,N,M) = lam, gam1, gam2 per (sample, channel).  Map form: thr
+    (3,M) the constant parts and slopes (3,M), cmap (N,1,*code grid): lam = thr[0,m] + cmap[n,pix] * slopes[0,m] etc.
+    The third plane is unread without z_after."""
+
+    @staticmethod
+    def forward(ctx, x, w, add, zp, za, thr, slopes, cmap, g, alpha):
+        x, zp = x.contiguous(), zp.contiguous()
+        za = za.contiguous() if za is not None else None
+        add = add.contiguous() if add is not None else None
+        rows = thr if cmap is None else thr[:, None, :].expand(3, g.N, g.M).contiguous()
+        keep = any(ctx.needs_input_grad)
+        u = torch.empty(g.code_shape(), device=x.device, dtype=torch.float32) if keep else None
+        mp = dict(cmap=cmap, tslope=slopes) if cmap is not None else {}
+        z = ops.analysis_prox(g, x, w, alpha, add, zp, rows[0], rows[1], za, rows[2] if za is not None else None,
+                              u_out=u, **mp)
+        ctx.g, ctx.alpha, ctx.f2, ctx.mapped = g, alpha, za is not None, cmap is not None
+        if keep:
+            empty = x.new_empty(0)
+            ctx.save_for_backward(x, w, zp, za if ctx.f2 else empty, rows, slopes if ctx.mapped else empty,
+                                  cmap if ctx.mapped else empty, u)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz):
+        g, need = ctx.g, ctx.needs_input_grad
+        x, w, zp, za, rows, slopes, cmap, u = ctx.saved_tensors
+        za = za if ctx.f2 else None
+        new = lambda *shape: torch.zeros(shape, device=gz.device, dtype=torch.float32)
+        gzp = torch.zeros_like(u) if need[3] else None
+        gza = torch.zeros_like(u) if ctx.f2 and need[4] else None
+        dt = new(3, 2, g.M)                                             # [sum s, sum cmap s] per family
+        dsum = new(3, g.N, g.M) if not ctx.mapped else None             # row form: the sums per (sample, channel)
+        dcmap = torch.zeros_like(cmap) if ctx.mapped and need[7] else None
+        mp = dict(cmap=cmap, tslope=slopes, dcmap=dcmap) if ctx.mapped else dict(dsum_n=dsum)
+        gu = ops.prox_csr_bwd(g, gz.contiguous(), u, zp, rows[0], rows[1], None, dt[0], dt[1], za,
+                              rows[2] if ctx.f2 else None, dt[2] if ctx.f2 else None, gzp, gza, **mp)
+        dx = ops.synthesis(g, gu, w, ctx.alpha) if need[0] else None
+        dw = ops.wgrad(g, gu, x, ctx.alpha) if need[1] else None
+        dthr = (dt[:, 0] if ctx.mapped else dsum) if need[5] else None
+        dslopes = dt[:, 1] if ctx.mapped and need[6] else None
+        return dx, dw, (gu if need[2] else None), gzp, gza, dthr, dslopes, dcmap, None, None
+
+
+def _is_map_form(t):
+    return isinstance(t, (tuple, list)) and len(t) == 3 and torch.is_tensor(t[1])
+
+
+def analysis_prox(x, w, z_prev, lambd, gamma1, z_after=None, gamma2=None, stride=1, alpha=1.0, add=None):
+    """prox_CSR / prox_CSR_f2 of (add + alpha * A x; z_prev[, z_after]) with the proximal map in the analysis kernel's
+    epilogue: the launch one iteration of the CSR nets' sweep makes, beside analysis_shrink.  The pre-shrinkage tensor is
+    written once, for the backward, and never read back in the forward.  Thresholds:
+
+    * numbers or tensors that broadcast to (N, M, 1, ..) -- one value per (sample, channel): the fused kernel's row form;
+    * every threshold a triple `(t0, c, t1)` meaning `t0 + c * t1` with t0, t1 per channel (broadcast forms of (1, M, 1, ..))
+      and ONE noise-level map c (the same tensor in every triple) that broadcasts to (N, 1, *code grid): the fused kernel's
+      map form, `(cmap, slopes)` at the C ABI -- no threshold and no threshold gradient of the codes' size is formed, the
+      bits are those of the tensor torch's broadcast `t0 + c * t1` would give;
+    * any other tensor that broadcasts to the code shape: analysis followed by prox_csr / prox_csr_f2 (the `_b` form).
+
+    Differentiable in x, w, add, z_prev, z_after and every threshold tensor, each gradient in the shape given."""
+    fn = "analysis_prox"
+    g = _geometry(fn, tuple(x.shape), w, stride)
+    cs = g.code_shape()
+    for name, t in (("add", add), ("z_prev", z_prev), ("z_after", z_after)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != cs):
+            raise ValueError(f"{fn}: `{name}` of shape {tuple(t.shape)} is not the code shape {cs}")
+    if z_prev is None:
+        raise ValueError(f"{fn}: z_prev is required (analysis_shrink is the block without a neighbour code)")
+    f2 = z_after is not None
+    named = [("lambd", lambd), ("gamma1" if f2 else "gamma", gamma1)] + ([("gamma2", gamma2)] if f2 else [])
+    if f2 and gamma2 is None:
+        raise ValueError(f"{fn}: gamma2 is required with z_after")
+    _on_device(fn, x=x, w=w, add=add, z_prev=z_prev, z_after=z_after)
+    dev = x.device
+    per_channel = (1,) + cs[1:]
+    zeros = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
+    if any(_is_map_form(t) for _, t in named):
+        if not all(_is_map_form(t) for _, t in named) or any(t[1] is not named[0][1][1] for _, t in named):
+            raise ValueError(f"{fn}: with a noise-level map every threshold is a triple (t0, c, t1) with the same map c")
+        c = named[0][1][1]
+        want = (g.N, 1) + cs[2:]
+        shape = (1,) * (len(want) - c.dim()) + tuple(c.shape) if c.dim() <= len(want) else None
+        if shape is None or any(a not in (1, b) for a, b in zip(shape, want)):
+            raise ValueError(f"{fn}: the map of shape {tuple(c.shape)} does not broadcast to the code grid {want}")
+        cmap = c.to(device=dev, dtype=torch.float32).reshape(shape).expand(want).contiguous()
+        row = lambda name, t: _threshold(fn, name, t, per_channel, dev, rows_only=True).reshape(-1).expand(g.M)
+        thr = [row(name + "[0]", t[0]) for name, t in named] + ([] if f2 else [zeros(g.M)])
+        slopes = [row(name + "[2]", t[2]) for name, t in named] + ([] if f2 else [zeros(g.M)])
+        return _AnalysisProx.apply(x, w, add, z_prev, z_after, torch.stack(thr).contiguous(),
+                                   torch.stack(slopes).contiguous(), cmap, g, float(alpha))
+    full = [(name, _threshold(fn, name, t, cs, dev)) for name, t in named]
+    if any(any(d != 1 for d in t.shape[2:]) for _, t in full):          # spatial extent: the broadcast form, two launches
+        u = analysis(x, w, stride, alpha, add)
+        return _prox(fn, u, z_prev, z_after, lambd, gamma1, gamma2 if f2 else None)
+    rows = [t.expand(cs[:2] + t.shape[2:]).reshape(cs[:2]) for _, t in full] + ([] if f2 else [zeros(g.N, g.M)])
+    return _AnalysisProx.apply(x, w, add, z_prev, z_after, torch.stack(rows).contiguous(), None, None, g, float(alpha))
+
+
+# ------------------------------------------------------------------------------------------ the whole CSR loop
+def ista_csr(y, z_prev, z_after, sigma, mask, t, g1, g2, A, B, stride):
+    """The K iterations of a CSR net with neighbour codes and the final synthesis, as ONE autograd node over the one-call
+    sweeps (loop.TemporalISTA): returns (xhat, z_K).
+
+    y (N,C,H,W) noisy frame; z_prev, z_after (None: the one-neighbour map prox_CSR, g2 unused) neighbour codes; t, g1, g2 the
+    (K,2,M,1,1) threshold parameters; A, B the K analysis / synthesis filters (the final synthesis is B[0]).  sigma: None
+    (no noise-adaptive part), a float, one level per sample, or a noise-level map that broadcasts to (N,1,*code grid) --
+    classified as the nets classify it (net._noise_scale), with the same ValueErrors; with a map the three threshold
+    families t, g1, g2 all follow it, as the reference's broadcast does.  Differentiable in the filters, t, g1, g2, z_prev,
+    z_after, y, and sigma (the gradient comes back in the shape sigma was given).  A mask that requires grad raises."""
+    from .net import _code_grid, _mask_tensor, _noise_scale
+    _no_mask_gradient(mask)
+    if z_prev is None:
+        raise ValueError("ista_csr: z_prev is required (without a neighbour code the loop is the plain one, loop.run)")
+    if y.dim() != 4:
+        raise ValueError("ista_csr: expected an (N,C,H,W) frame")
+    _on_device("ista_csr", y=y, z_prev=z_prev, z_after=z_after)
+    y = y.to(torch.float32)
+    c = _noise_scale(sigma, True, y.shape[0], y.device, _code_grid(y.shape[2:], int(stride)))
+    mask_t = _mask_tensor(mask.detach() if torch.is_tensor(mask) else mask, y)
+    return loop.run_csr(y, mask_t, c, z_prev, z_after, t, g1, g2 if z_after is not None else None, list(A), list(B), int(stride))
 
 
 # ------------------------------------------------------------------------------------------ pre / post

@@ -647,18 +647,29 @@ class TangentISTA(torch.autograd.Function):
 # z_{k+1}), so the training forward keeps u_k next to z_k (both written by the analysis kernel, whose
 # epilogue is the proximal map: cdl_analysis_prox); everything else is _backward_generic with the gating
 # done by cdl_prox_csr_bwd, which also accumulates the neighbour-code gradients.
-def _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep):
-    xp, z, codes, resid, us = ops.ista_forward(g, yp, mask_p, lam, A, B, keep, zp, za, gam1, gam2)
+# A noise-level map: cmap (N,1,*code grid) with tslope (K,3,M), the slopes of lam, gam1, gam2;
+# lam / gam1 / gam2 then hold the constant parts t[k,0,m], g1[k,0,m], g2[k,0,m] for every sample.
+def _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep, cmap=None, tslope=None):
+    xp, z, codes, resid, us = ops.ista_forward(g, yp, mask_p, lam, A, B, keep, zp, za, gam1, gam2, cmap=cmap, tslope=tslope)
     return xp, z, us, codes, resid
 
 
-def _forward_csr_stepwise(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep):
+def _csr_slopes(t, g1, g2):
+    """(K,3,M): t[:,1], g1[:,1], g2[:,1] (zeros without g2) -- the slopes the CSR kernels read with a noise-level map."""
+    K, M = t.shape[0], t.shape[2]
+    rows = [p.detach().reshape(K, 2, M)[:, 1] for p in (t, g1)]
+    rows.append(g2.detach().reshape(K, 2, M)[:, 1] if g2 is not None else torch.zeros_like(rows[0]))
+    return torch.stack(rows, dim=1).contiguous()
+
+
+def _forward_csr_stepwise(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep, cmap=None, tslope=None):
     K = len(A)
     us, codes, resid = [], [], []
     g2 = (lambda k: gam2[k]) if za is not None else (lambda k: None)
+    mp = (lambda k: dict(cmap=cmap, tslope=tslope[k])) if cmap is not None else (lambda k: {})
     new = lambda: torch.empty(g.code_shape(), device=yp.device, dtype=torch.float32)
     u = new() if keep else None
-    z = ops.analysis_prox(g, yp, A[0], 1.0, None, zp, lam[0], gam1[0], za, g2(0), u_out=u)
+    z = ops.analysis_prox(g, yp, A[0], 1.0, None, zp, lam[0], gam1[0], za, g2(0), u_out=u, **mp(0))
     spare = None if keep else new()                      # inference: z ping-pongs between two buffers
     for k in range(1, K):
         if keep:
@@ -666,7 +677,7 @@ def _forward_csr_stepwise(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep):
             codes.append(z)
             u = new()
         r = ops.synthesis(g, z, B[k], 1.0, None, mask_p, yp)
-        z_next = ops.analysis_prox(g, r, A[k], -1.0, z, zp, lam[k], gam1[k], za, g2(k), u_out=u, out=spare)
+        z_next = ops.analysis_prox(g, r, A[k], -1.0, z, zp, lam[k], gam1[k], za, g2(k), u_out=u, out=spare, **mp(k))
         spare, z = (None, z_next) if keep else (z, z_next)
         if keep:
             resid.append(r)
@@ -680,7 +691,9 @@ def _forward_csr_stepwise(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep):
 @_arithmetic_aware
 class TemporalISTA(torch.autograd.Function):
     """(y, mask, c, z_prev, z_after|None, t, g1, g2|None, A.., B..) -> (xhat, z_K); gradients for the
-    neighbour codes, the three threshold families and both filter banks."""
+    neighbour codes, the three threshold families and both filter banks, and -- when asked for -- for y and c.  c: None,
+    one level per sample (N,), or a noise-level map (N,1,*code grid) that all three threshold families follow; its
+    gradient comes back in the same form."""
 
     @staticmethod
     def forward(ctx, y, mask, c, zp, za, t, g1, g2, cfg, *weights):
@@ -695,12 +708,17 @@ class TemporalISTA(torch.autograd.Function):
             raise ValueError(f"neighbour code shape {tuple(zp.shape)} does not match this frame's {g.code_shape()}")
         zp = zp.contiguous()
         za = za.contiguous() if za is not None else None
-        lam, gam1 = ops.thresholds(t, c, N), ops.thresholds(g1, c, N)
-        gam2 = ops.thresholds(g2, c, N) if za is not None else None
+        ctx.is_map = c is not None and c.dim() > 1
+        cs = None if ctx.is_map else c                 # a map: the thresholds' constant parts, the slopes beside them
+        lam, gam1 = ops.thresholds(t, cs, N), ops.thresholds(g1, cs, N)
+        gam2 = ops.thresholds(g2, cs, N) if za is not None else None
+        mp = dict(cmap=c, tslope=_csr_slopes(t, g1, g2 if za is not None else None)) if ctx.is_map else {}
         ctx.set_materialize_grads(False)
-        _no_data_gradients(ctx)
+        _no_data_gradients(ctx, ((1, "mask"),))
         keep = any(ctx.needs_input_grad)
-        xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep)
+        ctx.want_y = ctx.needs_input_grad[0]
+        ctx.want_c = ctx.needs_input_grad[2] and c is not None
+        xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep, **mp)
         xhat = ops.postprocess(xp, mean, pads)
         ctx.geom, ctx.pads, ctx.K = g, pads, K
         ctx.has_mask, ctx.has_c, ctx.has_after = mask_p is not None, c is not None, za is not None
@@ -708,7 +726,8 @@ class TemporalISTA(torch.autograd.Function):
             empty = yp.new_empty(0)
             ctx.save_for_backward(yp, mask_p if mask_p is not None else empty, c if c is not None else empty,
                                   zp, za if za is not None else empty, t, g1, g2 if za is not None else empty,
-                                  lam, gam1, gam2 if za is not None else empty, *weights, *us, *codes, *resid)
+                                  lam, gam1, gam2 if za is not None else empty, *weights, *us, *codes, *resid,
+                                  mask if (ctx.want_y and mask is not None) else empty)   # preprocess_bwd's unpadded mask
         return xhat, z
 
     @staticmethod
@@ -722,7 +741,8 @@ class TemporalISTA(torch.autograd.Function):
         A, B = sv[11:11 + K], sv[11 + K:11 + 2 * K]
         us = sv[11 + 2 * K:11 + 3 * K]
         codes = sv[11 + 3 * K:11 + 4 * K]
-        resid = sv[11 + 4 * K:]
+        resid = sv[11 + 4 * K:-1]
+        y_mask = sv[-1] if (ctx.want_y and ctx.has_mask) else None
         dev = yp.device
         dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
         dg1 = torch.zeros_like(dt)
@@ -732,27 +752,44 @@ class TemporalISTA(torch.autograd.Function):
         gza = torch.zeros_like(zp) if need_za else None
         g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
         g_z = g_z.contiguous() if g_z is not None else None
+        dy = dc = None
         if g_xp is None and g_z is None:
             dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
         else:
-            dA, dB = ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z,
-                                       dt, list(us), zp, za, lam, gam1, gam2, dg1, dg2, gzp, gza)
+            # data gradients only when asked for: otherwise the sweep gets NULLs and runs the parameter-only launches
+            dyp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32) if ctx.want_y else None
+            dtau = torch.zeros((K, 3, g.N, g.M), device=dev, dtype=torch.float32) \
+                if ctx.want_c and not ctx.is_map else None
+            mp = {}
+            if ctx.is_map:
+                dc = torch.empty_like(c) if ctx.want_c else None
+                mp = dict(cmap=c, tslope=_csr_slopes(t, g1, g2 if za is not None else None), dcmap=dc)
+            dA, dB = _backward_csr(g, K, yp, mask_p, None if ctx.is_map else c, A, B, codes, resid, us, zp, za, lam, gam1,
+                                   gam2, g_xp, g_z, dt, dg1, dg2, gzp, gza, dyp=dyp, dtau=dtau, **mp)
+            if dyp is not None:                        # a loss on z only: no mean term
+                dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, y_mask)
+            if dtau is not None:                       # lam[k,n,m] = t[k,0,m] + c[n] t[k,1,m], and the same for gam1, gam2
+                dc = torch.einsum("kfnm,kfm->n", dtau, _csr_slopes(t, g1, g2 if za is not None else None))
         _queue_backward_end()
-        return (None, None, None, gzp, gza, dt.reshape(t.shape), dg1.reshape(g1.shape),
+        return (dy, None, dc, gzp, gza, dt.reshape(t.shape), dg1.reshape(g1.shape),
                 dg2.reshape(g2.shape) if dg2 is not None else None, None, *dA, *dB)
 
 
-def _backward_csr(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1, dg2, gzp, gza):
+def _backward_csr(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1, dg2, gzp, gza,
+                  dyp=None, dtau=None, cmap=None, tslope=None, dcmap=None):
     """Reverse sweep of the CSR loop from one C call (cdl_ista_backward's CSR branch): (dA, dB); fills dt, dg1[, dg2] and
-    accumulates into gzp / gza (nullable)."""
+    accumulates into gzp / gza (nullable).  dyp (thin), dtau (K,3,N,M): the data gradients; cmap / tslope (K,3,M) / dcmap:
+    a noise-level map in the place of c, and its gradient."""
     return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, list(us), zp, za,
-                             lam, gam1, gam2, dg1, dg2, gzp, gza)
+                             lam, gam1, gam2, dg1, dg2, gzp, gza, dyp, dtau, cmap=cmap, tslope=tslope, dcmap=dcmap)
 
 
 def _backward_csr_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1, dg2,
-                           gzp, gza):
+                           gzp, gza, dyp=None, dtau=None, cmap=None, tslope=None, dcmap=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
     dA, dB = [None] * K, [None] * K
+    if dcmap is not None:
+        dcmap.zero_()
     if g_xp is not None:
         dB[0] = ops.wgrad(g, codes[K - 1], g_xp, 1.0)
         gk = ops.analysis(g, g_xp, B[0], 1.0, g_z, None, None)       # B_0^T g_xp (+ g_z)
@@ -760,14 +797,22 @@ def _backward_csr_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, 
         dB[0] = torch.zeros_like(B[0])
         gk = g_z.clone()
     for k in range(K - 1, -1, -1):                                   # gk: dL/dz_{k+1} -> dL/du_k in place
+        mp = dict(cmap=cmap, tslope=tslope[k], dcmap=dcmap) if cmap is not None else {}
         ops.prox_csr_bwd(g, gk, us[k], zp, lam[k], gam1[k], c, dt[k], dg1[k], za, gam2[k] if za is not None else None,
-                         dg2[k] if za is not None else None, gzp, gza, out=gk)
+                         dg2[k] if za is not None else None, gzp, gza, out=gk, dsum_n=dtau[k] if dtau is not None else None,
+                         **mp)
         if k == 0:
             break
-        q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
+        if dyp is not None:                                          # S = A_k^T du_k; dyp (+)= S; q = -mask S
+            q = ops.synthesis(g, gk, A[k], 1.0, None, None, None)
+            ops.dyp_split(g, q, mask_p, dyp, k < K - 1)
+        else:
+            q = ops.synthesis(g, gk, A[k], -1.0, None, mask_p, None)
         dA[k], dB[k] = ops.wgrad_pair(g, gk, resid[k - 1], -1.0, codes[k - 1], q, 1.0)
         gk = ops.analysis(g, q, B[k], 1.0, gk, None, None)
     dA[0] = ops.wgrad(g, gk, yp, 1.0)
+    if dyp is not None:                                              # u_0 = A_0 yp
+        ops.dyp_split(g, ops.synthesis(g, gk, A[0], 1.0), None, dyp, K > 1, make_q=False)
     return dA, dB
 
 

@@ -500,10 +500,22 @@ def prox_csr(g: Geometry, u, z_prev, lam, gam1, z_after=None, gam2=None, out=Non
     return out
 
 
-def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None, gam2=None, u_out=None, out=None):
+def _check_csr_map(g: Geometry, cmap, tslope, rows=1):
+    """The CSR maps under a noise-level map: cmap as _check_map's, tslope `rows` x (3, M) slopes of lam, gam1, gam2."""
+    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
+    if (cmap is None) != (tslope is None):
+        raise ValueError("cmap and tslope go together")
+    _check_map(g, cmap, tslope, 3 * rows)
+    return cmap, tslope
+
+
+def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None, gam2=None, u_out=None, out=None, *,
+                  cmap=None, tslope=None):
     """cdl_analysis with the CSR map as epilogue: returns z = prox(zin + alpha*corr(x; w)); `u_out`
-    (a code-shaped tensor) receives the pre-shrinkage value when given."""
+    (a code-shaped tensor) receives the pre-shrinkage value when given.  cmap (N,1,*code_spatial) with tslope (3,M): the
+    thresholds of element (n, m, pix) are lam[n,m] + cmap[n,pix] * tslope[0,m], and the same for gam1, gam2."""
     x, w = _dev(x, "x"), _dev(w, "w")
+    cmap, tslope = _check_csr_map(g, cmap, tslope)
     zin, z_prev, z_after = _opt(zin, "zin"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
@@ -517,7 +529,8 @@ def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None
     ws = _scratch(x.device, n) if n else None
     rc = _lib.lib().cdl_analysis_prox_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(z_prev),
                                          _ptr(z_after), _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")),
-                                         _ptr(_opt(gam2, "gam2")), _ptr(u_out), _ptr(out), _ptr(ws), n, _stream())
+                                         _ptr(_opt(gam2, "gam2")), _ptr(u_out), _ptr(out), _ptr(ws), n, _ptr(cmap),
+                                         _ptr(tslope), _stream())
     _lib.check(rc, "cdl_analysis_prox_ws")
     return out
 
@@ -572,11 +585,19 @@ def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z
 
 
 def prox_csr_bwd(g: Geometry, gz, u, z_prev, lam, gam1, c, dlam, dgam1, z_after=None, gam2=None, dgam2=None,
-                 gz_prev=None, gz_after=None, out=None):
+                 gz_prev=None, gz_after=None, out=None, *, cmap=None, tslope=None, dcmap=None, dsum_n=None):
     """Reverse of prox_csr: returns gu; accumulates into gz_prev / gz_after; writes the (2,M) slices
-    dlam, dgam1[, dgam2] of the threshold gradients of this iteration."""
+    dlam, dgam1[, dgam2] of the threshold gradients of this iteration.  dsum_n (3,N,M): the threshold sums per sample.
+    cmap / tslope as analysis_prox's (c is then None): the slices receive [sum s, sum cmap*s], and dcmap
+    (N,1,*code_spatial) is accumulated into."""
     gz, u, z_prev = _dev(gz, "gz"), _dev(u, "u"), _dev(z_prev, "z_prev")
     z_after, gam2, c = _opt(z_after, "z_after"), _opt(gam2, "gam2"), _opt(c, "c")
+    cmap, tslope = _check_csr_map(g, cmap, tslope)
+    if dcmap is not None:
+        assert cmap is not None and dcmap.is_contiguous() and dcmap.dtype == torch.float32
+        _check_map(g, dcmap)
+    if dsum_n is not None:
+        assert dsum_n.is_contiguous() and dsum_n.dtype == torch.float32 and tuple(dsum_n.shape) == (3, g.N, g.M)
     for t in (dlam, dgam1, dgam2):
         assert t is None or (t.is_contiguous() and t.numel() == 2 * g.M)
     for t in (gz_prev, gz_after):
@@ -589,7 +610,8 @@ def prox_csr_bwd(g: Geometry, gz, u, z_prev, lam, gam1, c, dlam, dgam1, z_after=
     rc = _lib.lib().cdl_prox_csr_bwd(ctypes.byref(gs), _ptr(gz), _ptr(u), _ptr(z_prev), _ptr(z_after),
                                      _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")), _ptr(gam2), _ptr(c),
                                      _ptr(out), _ptr(gz_prev), _ptr(gz_after), _ptr(dlam), _ptr(dgam1),
-                                     _ptr(dgam2), _ptr(scratch), n, _stream())
+                                     _ptr(dgam2), _ptr(scratch), n, _ptr(cmap), _ptr(tslope), _ptr(dcmap), _ptr(dsum_n),
+                                     _stream())
     _lib.check(rc, "cdl_prox_csr_bwd")
     return out
 
@@ -1013,9 +1035,10 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
     return outs
 
 
-def _check_data_grads(g: Geometry, K, dyp, dtau):
-    """The optional outputs of the *_backward sweeps: dyp (thin, as yp), dtau (K,N,M); contiguous fp32."""
-    for t, shape in ((dyp, g.image_shape()), (dtau, (K, g.N, g.M))):
+def _check_data_grads(g: Geometry, K, dyp, dtau, families=1):
+    """The optional outputs of the *_backward sweeps: dyp (thin, as yp), dtau (K,N,M) -- (K,3,N,M) for the three threshold
+    families of the CSR sweep; contiguous fp32."""
+    for t, shape in ((dyp, g.image_shape()), (dtau, (K, g.N, g.M) if families == 1 else (K, families, g.N, g.M))):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
                 (tuple(t.shape), shape)
@@ -1351,12 +1374,13 @@ def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=
                  cmap=None, tslope=None):
     """Generic forward sweep in one C call.  Plain ST loop (z_prev None) or the CSR maps.  keep=True:
     every z_k, r_k (and u_k for CSR) gets its own buffer.  Returns (xp, z_K, codes, resid, us).
-    cmap (N,1,*code_spatial) with tslope (K,M) = t[:,1]: noise-level map, see analysis (plain loop only)."""
+    cmap (N,1,*code_spatial) with tslope (K,M) = t[:,1]: noise-level map, see analysis; with z_prev tslope is (K,3,M),
+    the slopes of lam, gam1, gam2, and tau / gam1 / gam2 hold the constant parts (analysis_prox)."""
     K = len(A)
     cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
     if (cmap is None) != (tslope is None):
         raise ValueError("cmap and tslope go together")
-    _check_map(g, cmap, tslope, K)
+    _check_map(g, cmap, tslope, K if z_prev is None else 3 * K)
     yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
@@ -1385,11 +1409,12 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
                   z_after=None, lam=None, gam1=None, gam2=None, dg1=None, dg2=None, gz_prev=None, gz_after=None,
                   dyp=None, dtau=None, *, cmap=None, tslope=None, dcmap=None):
     """Generic reverse sweep in one C call (cdl_ista_backward); returns (dA, dB) and fills dt [, dg1, dg2, gz_prev,
-    gz_after] [, dyp, dtau: see fused_backward; plain loop only].  cmap / tslope as ista_forward's (c is then None);
-    dcmap (N,1,*code_spatial; nullable) receives dL/dcmap where dtau would be returned."""
+    gz_after] [, dyp, dtau: see fused_backward; with z_prev dtau is (K,3,N,M), the per-sample sums of lam, gam1, gam2].
+    cmap / tslope as ista_forward's (c is then None); dcmap (N,1,*code_spatial; nullable) receives dL/dcmap where dtau
+    would be returned."""
     K = len(A)
     cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
-    _check_map(g, cmap, tslope, K)
+    _check_map(g, cmap, tslope, K if z_prev is None else 3 * K)
     if dcmap is not None:
         assert cmap is not None and tslope is not None and dcmap.is_contiguous()
         _check_map(g, dcmap)
@@ -1401,7 +1426,7 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
     g0, g1, q = _new(g.code_shape(), dev), _new(g.code_shape(), dev), _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
     gs = g.c_struct()
-    _check_data_grads(g, K, dyp, dtau)
+    _check_data_grads(g, K, dyp, dtau, 1 if z_prev is None else 3)
     rc = _lib.lib().cdl_ista_backward(
         ctypes.byref(gs), K, _ptr(_dev(yp, "yp")), _ptr(_opt(mask_p, "mask")), _ptr(_opt(c, "c")),
         _ptr(_opt(z_prev, "z_prev")), _ptr(_opt(z_after, "z_after")), _ptr(_opt(lam, "lam")),

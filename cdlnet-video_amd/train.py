@@ -16,6 +16,7 @@ import torch.nn as nn
 
 import torch.distributed as dist
 
+from . import temporal
 from .net import CDLNet, CDLNet_CSR, CDLNet_CSRf2, CDLNetVideo, GDLNet
 from .parallel import phase_consensus
 from .utils import awgn, gen_bayer_mask
@@ -189,10 +190,14 @@ def _clip_depth(net, clip):
 
 
 def _net_call(net, D):
-    """forward of a CSR net as `call(y, prev, after, sigma)`: CDLNet_CSR has no `z_after` argument."""
-    if D == 2:
-        return lambda y, prev, after, sigma: net(y, prev, sigma)
-    return lambda y, prev, after, sigma: net(y, prev, after, sigma)
+    """forward of a CSR net as `call(y, prev, after, sigma)`: CDLNet_CSR has no `z_after` argument.  A frame whose sigma is
+    a noise-level map goes through temporal.csr_step."""
+    def call(y, prev, after, sigma):
+        codes = (prev,) if D == 2 else (prev, after)
+        if temporal._is_sigma_map(sigma, y):
+            return temporal.csr_step(net, y, *codes, sigma=sigma)
+        return net(y, *codes, sigma)
+    return call
 
 
 def clip_forward(net, frames, sigmas):

@@ -238,16 +238,20 @@ int cdl_prox_csr(const cdl_geom *g, const float *u, const float *z_prev, const f
 
 /* cdl_analysis with the CSR map as its epilogue (one fat write + read per iteration less than
  * cdl_analysis followed by cdl_prox_csr):  u = zin + alpha*corr(x ; w),  out = prox(u; z_prev[, z_after]),
- * and u itself to u_out when it is not NULL (the reverse sweep needs it).  Same bits as the two-call form. */
+ * and u itself to u_out when it is not NULL (the reverse sweep needs it).  Same bits as the two-call form.
+ * Noise-level map (both NULL: none): cmap (N, code pixels) with tslope (3,M), the slopes of lam,
+ * gam1, gam2 in this order (the third plane unread without z_after).  lam / gam1 / gam2 then hold the constant parts and
+ * element (n, m, pix) takes lam[n,m] + cmap[n,pix]*tslope[0,m] etc., the product rounded before the sum. */
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha,
                       const float *zin /*nullable*/, const float *z_prev, const float *z_after /*nullable*/,
                       const float *lam, const float *gam1, const float *gam2 /*nullable*/,
-                      float *u_out /*nullable*/, float *out, void *stream);
+                      float *u_out /*nullable*/, float *out, const float *cmap /*nullable*/,
+                      const float *tslope /*3*M, nullable*/, void *stream);
 int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
                          const float *zin /*nullable*/, const float *z_prev, const float *z_after /*nullable*/,
                          const float *lam, const float *gam1, const float *gam2 /*nullable*/,
                          float *u_out /*nullable*/, float *out, float *workspace, size_t workspace_floats,
-                         void *stream);
+                         const float *cmap /*nullable*/, const float *tslope /*3*M, nullable*/, void *stream);
 
 /* Tangent of the two maps.  They are piecewise linear in (u, z_prev, z_after); with the intermediates
  * of the PRIMAL (u, z_prev[, z_after], lam, gam*) and st_dx(x,t) = (x != 0 && |x| - t > 0):
@@ -279,13 +283,23 @@ int cdl_analysis_prox_tangent_ws(const cdl_geom *g, const float *x, const float 
  * gradient): gu = dL/du (may alias gz); gz_prev / gz_after (nullable) are ACCUMULATED into, because a
  * neighbour code feeds all K iterations; dlam, dgam1, dgam2 are (2,M) and receive
  * [sum_n s, sum_n c[n]*s] of the per-(n,m) threshold sums, i.e. the gradients of t[k], g1[k], g2[k]
- * under lam = t[k,0] + c*t[k,1] (net.py:444).  scratch: cdl_prox_csr_scratch_floats(g) floats. */
+ * under lam = t[k,0] + c*t[k,1] (net.py:444).  scratch: cdl_prox_csr_scratch_floats(g) floats.
+ * dsum_n (3,N,M; nullable): the per-(n,m) sums s themselves, family by family (lam, gam1, gam2; the third plane is
+ * written only with z_after) -- dL/dc[n] is formed from them.
+ * Noise-level map: cmap (N, code pixels) with tslope (3,M) as in cdl_analysis_prox, lam / gam1 /
+ * gam2 the constant parts; c and dsum_n must then be NULL, dlam / dgam1 / dgam2 receive [sum s, sum cmap*s] over samples
+ * and pixels, and dcmap (N, code pixels; nullable) is ACCUMULATED into:
+ *     dcmap[n,pix] += sum_m tslope[0,m]*s_lam + tslope[1,m]*s_gam1 + tslope[2,m]*s_gam2
+ * Every reduction has a fixed order (no atomics); nothing of the code tensors' size is written beside gu, gz_*. */
 int cdl_prox_csr_bwd(const cdl_geom *g, const float *gz, const float *u, const float *z_prev,
                      const float *z_after /*nullable*/, const float *lam, const float *gam1,
                      const float *gam2 /*nullable*/, const float *c /*N, nullable*/, float *gu,
                      float *gz_prev /*nullable*/, float *gz_after /*nullable*/, float *dlam /*2*M*/,
                      float *dgam1 /*2*M*/, float *dgam2 /*2*M, nullable*/, float *scratch,
-                     size_t scratch_floats, void *stream);
+                     size_t scratch_floats, const float *cmap /*nullable*/, const float *tslope /*3*M, nullable*/,
+                     float *dcmap /*nullable*/, float *dsum_n /*3*N*M, nullable*/, void *stream);
+/* (covers the map form whether or not a map is passed: N*M*ceil(pixels/1024)*24 wave partials + MS*N*pixels map-gradient
+ *  partials, MS <= ceil(M/8) channel ranges -- a few MB at 8 x 256 x 256; cdl_ista_scratch_floats includes it) */
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g);
 
 /* The two maps and their reverse with thresholds of any broadcast shape (cdl_bcast above; s_gam2 is read only with
@@ -402,20 +416,24 @@ int cdl_residual_backward(const cdl_geom *g, const float *x, const float *h, con
  * cdl_ista_scratch_floats(g) floats.
  * Backward: z, r, u as saved by the forward; g_xp = dL/d(D z_K) and / or g_z = dL/dz_K; writes dA[k],
  * dB[k], dt (K,2,M) [, dg1, dg2 (K,2,M)], accumulates gz_prev / gz_after (nullable); gbuf0, gbuf1 fat
- * scratch, q thin scratch, scratch as above (required).  The gradients of the data (plain loop only: z_prev must be
- * NULL when either is given; both NULL: neither is computed):
+ * scratch, q thin scratch, scratch as above (required).  The gradients of the data (both NULL: neither is computed):
  *     dyp  (thin, as yp; nullable):  dL/dyp = sum_k A_k^T du_k  (u_0 = A_0 yp, u_k = z_k - A_k(mask B_k z_k - yp))
- *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau)
- * Noise-level map (plain loop only; all NULL: none): cmap (N, code pixels) and tslope (K,M) = t[:,1,:] as in cdl_analysis,
+ *     dtau (K,N,M; nullable):        dL/dtau[k,n,m], the per-sample threshold gradients (dL/dc = sum t[k,1,m] dtau);
+ *                                    with z_prev (K,3,N,M): those of lam, gam1, gam2 (cdl_prox_csr_bwd's dsum_n)
+ * Noise-level map (all NULL: none): cmap (N, code pixels) and tslope (K,M) = t[:,1,:] as in cdl_analysis,
  * tau then holding t[k,0,m] for every sample; in the reverse sweep cmap takes the place of c (c and dtau must be NULL) and
- *     dcmap (N, code pixels; nullable): dL/dcmap = sum_k cdl_sigma_grad(du_k, z_{k+1}, tslope[k]) */
+ *     dcmap (N, code pixels; nullable): dL/dcmap = sum_k cdl_sigma_grad(du_k, z_{k+1}, tslope[k])
+ * With z_prev tslope holds (K,3,M): the slopes of lam, gam1, gam2 of every iteration in this order
+ * (the third plane unread without z_after), tau / gam1 / gam2 (forward) resp. lam / gam1 / gam2 (reverse) the constant
+ * parts t[k,0,m], g1[k,0,m], g2[k,0,m] for every sample; dt / dg1 / dg2 receive [sum s, sum cmap*s] and dcmap the sum over
+ * the iterations of cdl_prox_csr_bwd's map gradient. */
 size_t cdl_ista_scratch_floats(const cdl_geom *g);
 int cdl_ista_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                      const float *tau, const float *z_prev /*nullable*/, const float *z_after /*nullable*/,
                      const float *gam1 /*nullable*/, const float *gam2 /*nullable*/,
                      const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                      float *const *u /*nullable*/, float *xp, float *scratch, size_t scratch_floats,
-                     const float *cmap /*nullable*/, const float *tslope /*K*M, nullable*/, void *stream);
+                     const float *cmap /*nullable*/, const float *tslope /*K*M or K*3*M, nullable*/, void *stream);
 int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                       const float *c /*N, nullable*/, const float *z_prev /*nullable*/,
                       const float *z_after /*nullable*/, const float *lam, const float *gam1, const float *gam2,
@@ -424,8 +442,8 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
                       const float *g_z /*nullable*/, float *const *dA, float *const *dB, float *dt,
                       float *dg1 /*CSR*/, float *dg2 /*CSR f2*/, float *gz_prev /*nullable*/,
                       float *gz_after /*nullable*/, float *gbuf0, float *gbuf1, float *q, float *scratch,
-                      size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M, nullable*/,
-                      const float *cmap /*nullable*/, const float *tslope /*K*M, nullable*/, float *dcmap /*nullable*/,
+                      size_t scratch_floats, float *dyp /*nullable*/, float *dtau /*K*N*M or K*3*N*M, nullable*/,
+                      const float *cmap /*nullable*/, const float *tslope /*K*M or K*3*M, nullable*/, float *dcmap /*nullable*/,
                       void *stream);
 
 /* ---- forward-mode tangent of the plain loop at the primal's supports ----
