@@ -106,16 +106,16 @@ class _Synthesis(torch.autograd.Function):
     def forward(ctx, z, w, mask, sub, g, alpha):
         z = z.contiguous()
         ctx.g, ctx.alpha = g, alpha
-        ctx.save_for_backward(z, w, mask if mask is not None else z.new_empty(0))
-        ctx.has_mask = mask is not None
+        loop._save(ctx, z=z, w=w, mask=mask)
         return ops.synthesis(g, z, w, alpha, None, mask, sub)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        z, w, mask = ctx.saved_tensors
+        sv = loop._saved(ctx)
+        z, w = sv.z, sv.w
         gout = gout.contiguous()
-        q = gout * mask if ctx.has_mask else gout                         # thin
+        q = gout * sv.mask if sv.mask is not None else gout                         # thin
         dz = ops.analysis(ctx.g, q, w, ctx.alpha) if ctx.needs_input_grad[0] else None
         dw = ops.wgrad(ctx.g, z, q, ctx.alpha) if ctx.needs_input_grad[1] else None
         return dz, dw, None, (-gout if ctx.needs_input_grad[3] else None), None, None
@@ -219,14 +219,14 @@ class _Prox(torch.autograd.Function):
         za = za.contiguous() if za is not None else None
         ctx.g = _code_geometry(u.shape)
         ctx.f2 = za is not None
-        ctx.save_for_backward(u, zp, lam, g1, *((za, g2) if ctx.f2 else ()))
+        loop._save(ctx, u=u, zp=zp, lam=lam, g1=g1, za=za, g2=g2 if ctx.f2 else None)
         return ops.prox_csr_b(ctx.g, u, zp, lam, g1, za, g2)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gz):
-        u, zp, lam, g1 = ctx.saved_tensors[:4]
-        za, g2 = ctx.saved_tensors[4:] if ctx.f2 else (None, None)
+        sv = loop._saved(ctx)
+        u, zp, lam, g1, za, g2 = sv.u, sv.zp, sv.lam, sv.g1, sv.za, sv.g2
         need = ctx.needs_input_grad
         gzp = torch.zeros_like(u) if need[1] else None
         gza = torch.zeros_like(u) if ctx.f2 and need[2] else None
@@ -329,17 +329,15 @@ class _AnalysisProx(torch.autograd.Function):
                               u_out=u, **mp)
         ctx.g, ctx.alpha, ctx.f2, ctx.mapped = g, alpha, za is not None, cmap is not None
         if keep:
-            empty = x.new_empty(0)
-            ctx.save_for_backward(x, w, zp, za if ctx.f2 else empty, rows, slopes if ctx.mapped else empty,
-                                  cmap if ctx.mapped else empty, u)
+            loop._save(ctx, x=x, w=w, zp=zp, za=za, rows=rows, slopes=slopes if ctx.mapped else None, cmap=cmap, u=u)
         return z
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gz):
         g, need = ctx.g, ctx.needs_input_grad
-        x, w, zp, za, rows, slopes, cmap, u = ctx.saved_tensors
-        za = za if ctx.f2 else None
+        sv = loop._saved(ctx)
+        x, w, zp, za, rows, slopes, cmap, u = sv.x, sv.w, sv.zp, sv.za, sv.rows, sv.slopes, sv.cmap, sv.u
         new = lambda *shape: torch.zeros(shape, device=gz.device, dtype=torch.float32)
         gzp = torch.zeros_like(u) if need[3] else None
         gza = torch.zeros_like(u) if ctx.f2 and need[4] else None
@@ -444,8 +442,7 @@ class _PreProcess(torch.autograd.Function):
     def forward(ctx, y, mask, s):
         yp, mean, pads, mask_p = ops.preprocess(y.contiguous(), s, mask)
         ctx.pads, ctx.shape = pads, tuple(y.shape)
-        ctx.save_for_backward(mask if mask is not None else yp.new_empty(0))
-        ctx.has_mask = mask is not None
+        loop._save(ctx, mask=mask)
         mask_p = mask_p if mask_p is not None else yp.new_empty(0)
         ctx.mark_non_differentiable(mask_p)
         ctx.set_materialize_grads(False)
@@ -454,7 +451,7 @@ class _PreProcess(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_yp, g_mean, _g_mask):
-        (mask,) = ctx.saved_tensors
+        mask = loop._saved(ctx).mask
         if g_yp is None and g_mean is None:
             return None, None, None
         pads = ctx.pads
@@ -470,7 +467,7 @@ class _PreProcess(torch.autograd.Function):
             for d in ctx.shape[1:]:
                 per *= d
             gx = (g_mean / per).expand(ctx.shape).contiguous()
-        return ops.preprocess_bwd(g_yp.contiguous(), pads, gx, mask if ctx.has_mask else None), None, None
+        return ops.preprocess_bwd(g_yp.contiguous(), pads, gx, mask), None, None
 
 
 @loop._arithmetic_aware

@@ -22,6 +22,8 @@ With a noise-level map c[n,pix] (a dense (N,1,*code grid) tensor; DESIGN.md sect
     dL/dy   = cdl_preprocess_bwd(dL/dyp, dL/dxhat)  (reflect pad adjoint and the mean)
 The gradient with respect to the mask is not produced (it needs mask * B_k z_k at masked-out pixels).
 """
+import types
+
 import torch
 
 from . import ops
@@ -79,7 +81,7 @@ class precision_scope:
 
 def set_code_layout(name):
     global CODE_LAYOUT
-    if name not in ops.LAYOUT:
+    if name not in ops._FUSED_LAYOUTS:              # "rsc" is the strip kernels' own, chosen by ops.fusedg_code_layout
         raise ValueError(name)
     CODE_LAYOUT = name
 
@@ -109,6 +111,37 @@ def _queue_backward_end():
             fn()
 
     torch.autograd.Variable._execution_engine.queue_callback(run)
+
+
+def _save(ctx, **named):
+    """Save tensors for backward by name: each value is None, a tensor or a sequence of tensors (possibly empty).  One
+    save_for_backward call with the tensors in order; the layout (name -> None / tensor / length) stays on ctx."""
+    flat, layout = [], {}
+    for name, v in named.items():
+        if v is None:
+            layout[name] = None
+        elif isinstance(v, torch.Tensor):
+            layout[name] = -1
+            flat.append(v)
+        else:
+            layout[name] = len(v)
+            flat.extend(v)
+    ctx.save_for_backward(*flat)
+    ctx.saved_layout = layout
+
+
+def _saved(ctx):
+    """What `_save` saved, under the same names: None as None, tensors as tensors, sequences as tuples."""
+    flat = iter(ctx.saved_tensors)
+    return types.SimpleNamespace(**{name: None if n is None else next(flat) if n < 0 else tuple(next(flat) for _ in range(n))
+                                    for name, n in ctx.saved_layout.items()})
+
+
+def _sweep_geometry(yp, A, s):
+    """Geometry of a sweep from the pre-processed input, the filter banks and the stride: padding P // 2."""
+    P = tuple(A[0].shape[2:])
+    return ops.Geometry.make(yp.shape[0], yp.shape[1], A[0].shape[0], yp.shape[2:], P, tuple(p // 2 for p in P),
+                             [s] * (yp.dim() - 2))
 
 
 def _forward_generic(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, cmap=None, tslope=None):
@@ -337,11 +370,8 @@ class UnrolledISTA(torch.autograd.Function):
         A, B = weights[:K], weights[K:]
         s = cfg["s"]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
-        N, C = yp.shape[:2]
-        M = A[0].shape[0]
-        nd = yp.dim() - 2
-        P = tuple(A[0].shape[2:])
-        g = ops.Geometry.make(N, C, M, yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        g = _sweep_geometry(yp, A, s)
+        N, M = g.N, g.M
         # a noise-level map (dense (N,1,*code grid), net._noise_scale): tau holds t[k,0,m] for every sample and the generic
         # sweeps form tau + c[n,pix] * t[k,1,m] in their shrinkage epilogues
         ctx.is_map = c is not None and c.dim() > 1
@@ -374,14 +404,10 @@ class UnrolledISTA(torch.autograd.Function):
         xhat = ops.postprocess(xp, mean, pads)
 
         ctx.geom, ctx.pads, ctx.K = g, pads, K
-        ctx.has_mask, ctx.has_c = mask_p is not None, c is not None
         if keep:
             # the adjoint of preprocess needs the unpadded mask (its per-sample sum is taken in cdl_preprocess_bwd)
-            y_mask = mask if (ctx.want_y and mask is not None) else yp.new_empty(0)
-            ctx.save_for_backward(yp, mask_p if mask_p is not None else yp.new_empty(0),
-                                  c if c is not None else yp.new_empty(0), t, *weights,
-                                  *codes, *resid, *maps, y_mask)
-            ctx.n_maps = len(maps)
+            _save(ctx, yp=yp, mask_p=mask_p, c=c, t=t, A=A, B=B, codes=codes, resid=resid, maps=maps,
+                  y_mask=mask if ctx.want_y else None)
         outs = (xhat, z)
         if want_codes:
             extra = tuple(codes[:-1])
@@ -392,17 +418,9 @@ class UnrolledISTA(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_xhat, g_z, *_unused):
         K, g = ctx.K, ctx.geom
-        saved = ctx.saved_tensors
-        yp, mask_p, c, t = saved[:4]
-        mask_p = mask_p if ctx.has_mask else None
-        c = c if ctx.has_c else None
-        A = saved[4:4 + K]
-        B = saved[4 + K:4 + 2 * K]
-        codes = saved[4 + 2 * K:4 + 3 * K]            # z_1..z_K
-        resid = saved[4 + 3 * K:4 + 3 * K + (K - 1)]  # r_1..r_{K-1}
-        maps = saved[4 + 3 * K + (K - 1):-1]          # fused path: support/sign bit maps of z_1..z_K
-        y_mask = saved[-1] if (ctx.want_y and ctx.has_mask) else None
-        assert len(maps) == ctx.n_maps
+        sv = _saved(ctx)
+        yp, mask_p, c, t, A, B, y_mask = sv.yp, sv.mask_p, sv.c, sv.t, sv.A, sv.B, sv.y_mask
+        codes, resid, maps = sv.codes, sv.resid, sv.maps      # z_1..z_K, r_1..r_{K-1}, fused tiers: the bit maps of z_1..z_K
         dt = torch.zeros((K, 2, g.M), device=yp.device, dtype=torch.float32)
         g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
         if g_z is not None:
@@ -534,11 +552,8 @@ class TangentISTA(torch.autograd.Function):
         A, B = weights[:K], weights[K:]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
         vp, vmean, _, _ = ops.preprocess(v, s, mask)          # linear: the same mean rule, mask and reflect pad
-        N, C = yp.shape[:2]
-        M = A[0].shape[0]
-        nd = yp.dim() - 2
-        P = tuple(A[0].shape[2:])
-        g = ops.Geometry.make(N, C, M, yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        g = _sweep_geometry(yp, A, s)
+        N, M = g.N, g.M
         ctx.is_map = c is not None and c.dim() > 1
         cmap = c if ctx.is_map else None
         tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
@@ -571,30 +586,16 @@ class TangentISTA(torch.autograd.Function):
         xdot = ops.postprocess(xdp, vmean, pads)
 
         ctx.geom, ctx.pads, ctx.K = g, pads, K
-        ctx.has_mask, ctx.has_c = mask_p is not None, c is not None
         if keep:
-            empty = yp.new_empty(0)
-            ctx.n_maps = len(maps)
-            ctx.save_for_backward(yp, vp, mask_p if mask_p is not None else empty, c if c is not None else empty, t,
-                                  *weights, *codes, *resid, *zd, *rd, *maps)
+            _save(ctx, yp=yp, vp=vp, mask_p=mask_p, c=c, t=t, A=A, B=B, codes=codes, resid=resid, zd=zd, rd=rd, maps=maps)
         return (xhat, xdot, z, zdK) if want_codes else (xhat, xdot)
 
     @staticmethod
     def backward(ctx, g_xhat, g_xdot, g_z=None, g_zd=None):
         K, g = ctx.K, ctx.geom
-        sv = ctx.saved_tensors
-        yp, vp, mask_p, c, t = sv[:5]
-        mask_p = mask_p if ctx.has_mask else None
-        c = c if ctx.has_c else None
-        o = 5
-        A, B = sv[o:o + K], sv[o + K:o + 2 * K]
-        o += 2 * K
-        codes, resid = sv[o:o + K], sv[o + K:o + 2 * K - 1]
-        o += 2 * K - 1
-        zd, rd = sv[o:o + K], sv[o + K:o + 2 * K - 1]
-        o += 2 * K - 1
-        maps = sv[o:]
-        assert len(maps) == ctx.n_maps
+        sv = _saved(ctx)
+        yp, vp, mask_p, c, t, A, B = sv.yp, sv.vp, sv.mask_p, sv.c, sv.t, sv.A, sv.B
+        codes, resid, zd, rd, maps = sv.codes, sv.resid, sv.zd, sv.rd, sv.maps
         dev = yp.device
         dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
         dA = dB = None
@@ -700,10 +701,8 @@ class TemporalISTA(torch.autograd.Function):
         K, s = cfg["K"], cfg["s"]
         A, B = weights[:K], weights[K:]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
-        N, C = yp.shape[:2]
-        P = tuple(A[0].shape[2:])
-        nd = yp.dim() - 2
-        g = ops.Geometry.make(N, C, A[0].shape[0], yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        g = _sweep_geometry(yp, A, s)
+        N = g.N
         if tuple(zp.shape) != g.code_shape() or (za is not None and tuple(za.shape) != g.code_shape()):
             raise ValueError(f"neighbour code shape {tuple(zp.shape)} does not match this frame's {g.code_shape()}")
         zp = zp.contiguous()
@@ -721,28 +720,18 @@ class TemporalISTA(torch.autograd.Function):
         xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, keep, **mp)
         xhat = ops.postprocess(xp, mean, pads)
         ctx.geom, ctx.pads, ctx.K = g, pads, K
-        ctx.has_mask, ctx.has_c, ctx.has_after = mask_p is not None, c is not None, za is not None
         if keep:
-            empty = yp.new_empty(0)
-            ctx.save_for_backward(yp, mask_p if mask_p is not None else empty, c if c is not None else empty,
-                                  zp, za if za is not None else empty, t, g1, g2 if za is not None else empty,
-                                  lam, gam1, gam2 if za is not None else empty, *weights, *us, *codes, *resid,
-                                  mask if (ctx.want_y and mask is not None) else empty)   # preprocess_bwd's unpadded mask
+            _save(ctx, yp=yp, mask_p=mask_p, c=c, zp=zp, za=za, t=t, g1=g1, g2=g2 if za is not None else None, lam=lam,
+                  gam1=gam1, gam2=gam2, A=A, B=B, us=us, codes=codes, resid=resid,
+                  y_mask=mask if ctx.want_y else None)       # preprocess_bwd's unpadded mask
         return xhat, z
 
     @staticmethod
     def backward(ctx, g_xhat, g_z):
         K, g = ctx.K, ctx.geom
-        sv = ctx.saved_tensors
-        yp, mask_p, c, zp, za, t, g1, g2, lam, gam1, gam2 = sv[:11]
-        mask_p = mask_p if ctx.has_mask else None
-        c = c if ctx.has_c else None
-        za, gam2 = (za, gam2) if ctx.has_after else (None, None)
-        A, B = sv[11:11 + K], sv[11 + K:11 + 2 * K]
-        us = sv[11 + 2 * K:11 + 3 * K]
-        codes = sv[11 + 3 * K:11 + 4 * K]
-        resid = sv[11 + 4 * K:-1]
-        y_mask = sv[-1] if (ctx.want_y and ctx.has_mask) else None
+        sv = _saved(ctx)
+        yp, mask_p, c, zp, za, t, g1, g2, y_mask = sv.yp, sv.mask_p, sv.c, sv.zp, sv.za, sv.t, sv.g1, sv.g2, sv.y_mask
+        lam, gam1, gam2, A, B, us, codes, resid = sv.lam, sv.gam1, sv.gam2, sv.A, sv.B, sv.us, sv.codes, sv.resid
         dev = yp.device
         dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
         dg1 = torch.zeros_like(dt)
@@ -869,10 +858,8 @@ class TangentTemporalISTA(torch.autograd.Function):
         A, B = weights[:K], weights[K:]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
         vp, vmean, _, _ = ops.preprocess(v, s, mask)          # linear: the same mean rule, mask and reflect pad
-        N, C = yp.shape[:2]
-        P = tuple(A[0].shape[2:])
-        nd = yp.dim() - 2
-        g = ops.Geometry.make(N, C, A[0].shape[0], yp.shape[2:], P, tuple(p // 2 for p in P), [s] * nd)
+        g = _sweep_geometry(yp, A, s)
+        N = g.N
         for name, x in (("z_prev", zp), ("zdot_prev", zdp), ("z_after", za), ("zdot_after", zda)):
             if x is not None and tuple(x.shape) != g.code_shape():
                 raise ValueError(f"{name}: shape {tuple(x.shape)} does not match this frame's code shape {g.code_shape()}")
@@ -888,28 +875,18 @@ class TangentTemporalISTA(torch.autograd.Function):
         xhat = ops.postprocess(xp, mean, pads)
         xdot = ops.postprocess(xdp, vmean, pads)
         ctx.geom, ctx.pads, ctx.K = g, pads, K
-        ctx.has_mask, ctx.has_c, ctx.has_after = mask_p is not None, c is not None, za is not None
         if keep:
-            e = yp.new_empty(0)
-            ctx.save_for_backward(yp, vp, mask_p if mask_p is not None else e, c if c is not None else e, zp,
-                                  za if za is not None else e, t, g1, g2 if za is not None else e, lam, gam1,
-                                  gam2 if za is not None else e, *weights, *us, *codes, *resid, *zd, *rd)
+            _save(ctx, yp=yp, vp=vp, mask_p=mask_p, c=c, zp=zp, za=za, t=t, g1=g1, g2=g2 if za is not None else None,
+                  lam=lam, gam1=gam1, gam2=gam2, A=A, B=B, us=us, codes=codes, resid=resid, zd=zd, rd=rd)
         return xhat, xdot, z, zdK
 
     @staticmethod
     def backward(ctx, g_xhat, g_xdot, g_z, g_zd):
         K, g = ctx.K, ctx.geom
-        sv = ctx.saved_tensors
-        yp, vp, mask_p, c, zp, za, t, g1, g2, lam, gam1, gam2 = sv[:12]
-        mask_p = mask_p if ctx.has_mask else None
-        c = c if ctx.has_c else None
-        za, gam2 = (za, gam2) if ctx.has_after else (None, None)
-        o = 12
-        A, B = sv[o:o + K], sv[o + K:o + 2 * K]
-        o += 2 * K
-        us, codes, resid = sv[o:o + K], sv[o + K:o + 2 * K], sv[o + 2 * K:o + 3 * K - 1]
-        o += 3 * K - 1
-        zd, rd = sv[o:o + K], sv[o + K:o + 2 * K - 1]
+        sv = _saved(ctx)
+        yp, vp, mask_p, c, zp, za, t, g1, g2 = sv.yp, sv.vp, sv.mask_p, sv.c, sv.zp, sv.za, sv.t, sv.g1, sv.g2
+        lam, gam1, gam2, A, B, us, codes, resid = sv.lam, sv.gam1, sv.gam2, sv.A, sv.B, sv.us, sv.codes, sv.resid
+        zd, rd = sv.zd, sv.rd
         dev = yp.device
         dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
         dg1 = torch.zeros_like(dt)
@@ -962,13 +939,14 @@ class _ISTAIteration(torch.autograd.Function):
             z = ops.analysis(g, r, wA, -1.0, zin, None, tau, **kw)
         ctx.g, ctx.first, ctx.t_shape = g, zin is None, tuple(t_k.shape)
         ctx.mask_p, ctx.c = mask_p, c
-        ctx.save_for_backward(zin if zin is not None else yp.new_empty(0), r, z, wA, wB)
+        _save(ctx, zin=zin, r=r, z=z, wA=wA, wB=wB)
         return z
 
     @staticmethod
     def backward(ctx, gz):
         g = ctx.g
-        zin, r, z, wA, wB = ctx.saved_tensors
+        sv = _saved(ctx)
+        zin, r, z, wA, wB = sv.zin, sv.r, sv.z, sv.wA, sv.wB
         gk = gz.contiguous()
         dt_k = torch.zeros((2, g.M), device=gk.device, dtype=torch.float32)
         if ctx.c is not None and ctx.c.dim() > 1:
@@ -1036,9 +1014,7 @@ def run_residual(y, mask, c, t, A, B, s, blocks, all_codes=False):
                                     or (c is not None and c.requires_grad)):
         raise NotImplementedError("cdlnet_video_amd: gradients with respect to y / mask / sigma are not implemented")
     yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
-    N, C = yp.shape[:2]
-    P = tuple(A[0].shape[2:])
-    g = ops.Geometry.make(N, C, A[0].shape[0], yp.shape[2:], P, tuple(p // 2 for p in P), [s] * (yp.dim() - 2))
+    g = _sweep_geometry(yp, A, s)
     z, shrunk = None, []
     for k in range(K):
         z = _ISTAIteration.apply(z, t[k], A[k], B[k], g, yp, mask_p, c)

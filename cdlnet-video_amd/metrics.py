@@ -61,13 +61,10 @@ class _SSIMPlanes(torch.autograd.Function):
         if R.shape != (P,):
             raise ValueError(f"data_range: expected one value per plane, shape ({P},), got {tuple(R.shape)}")
         R = R.contiguous()          # the kernels read R[plane]: an expanded (stride-0) view must not reach them
-        lib = _lib.lib()
-        n = int(lib.cdl_ssim_scratch_floats(P, H, W, len(win)))
+        n = int(_lib.lib().cdl_ssim_scratch_floats(P, H, W, len(win)))
         scratch = ops._scratch(x.device, n)
         out = torch.empty(P, device=x.device, dtype=torch.float32)
-        rc = lib.cdl_ssim_fwd(ops._ptr(x), ops._ptr(y), P, H, W, _window_arg(win), len(win), K1, K2, kappa,
-                              ops._ptr(R), ops._ptr(out), None, ops._ptr(scratch), n, ops._stream())
-        _lib.check(rc, "cdl_ssim_fwd")
+        ops._call("cdl_ssim_fwd", x, y, P, H, W, _window_arg(win), len(win), K1, K2, kappa, R, out, None, scratch, n)
         ctx.save_for_backward(x, y, R)
         ctx.args = (win, K1, K2, kappa)
         return out
@@ -84,13 +81,9 @@ class _SSIMPlanes(torch.autograd.Function):
         dx = torch.empty_like(x) if nx else None
         dy = torch.empty_like(y) if ny else None
         dr = torch.empty(P, device=x.device, dtype=torch.float32) if nr else None
-        lib = _lib.lib()
-        n = int(lib.cdl_ssim_scratch_floats(P, H, W, len(win)))
+        n = int(_lib.lib().cdl_ssim_scratch_floats(P, H, W, len(win)))
         scratch = ops._scratch(x.device, n)
-        rc = lib.cdl_ssim_bwd(ops._ptr(x), ops._ptr(y), P, H, W, _window_arg(win), len(win), K1, K2, kappa,
-                              ops._ptr(R), ops._ptr(g), ops._ptr(dx), ops._ptr(dy), ops._ptr(dr),
-                              ops._ptr(scratch), n, ops._stream())
-        _lib.check(rc, "cdl_ssim_bwd")
+        ops._call("cdl_ssim_bwd", x, y, P, H, W, _window_arg(win), len(win), K1, K2, kappa, R, g, dx, dy, dr, scratch, n)
         return dx, dy, dr, None, None, None, None
 
 
@@ -223,16 +216,12 @@ class _PerceptualPlanes(torch.autograd.Function):
     def forward(ctx, x, y, ws, bs):
         P, H, W = x.shape
         grads = (_VGG_DX if ctx.needs_input_grad[0] else 0) | (_VGG_DY if ctx.needs_input_grad[1] else 0)
-        lib = _lib.lib()
-        n = int(lib.cdl_vgg_scratch_floats(P, H, W, grads))
+        n = int(_lib.lib().cdl_vgg_scratch_floats(P, H, W, grads))
         if n == 0:
             raise ValueError(f"perceptual loss: {P} planes of {H} x {W} not supported")
         scratch = torch.empty(n, device=x.device, dtype=torch.float32)
         loss = torch.empty((), device=x.device, dtype=torch.float32)
-        wt, bt = ops._ptr_table(ws), ops._ptr_table(bs)
-        rc = lib.cdl_vgg_forward(ops._ptr(x), ops._ptr(y), P, H, W, wt, bt, grads, None, ops._ptr(loss),
-                                 ops._ptr(scratch), n, ops._stream())
-        _lib.check(rc, "cdl_vgg_forward")
+        ops._call("cdl_vgg_forward", x, y, P, H, W, ws, bs, grads, None, loss, scratch, n)
         ctx.state = (scratch, ws, bs, grads, (P, H, W))
         return loss
 
@@ -244,10 +233,7 @@ class _PerceptualPlanes(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         dx = torch.empty((P, H, W), device=g.device, dtype=torch.float32) if grads & _VGG_DX else None
         dy = torch.empty((P, H, W), device=g.device, dtype=torch.float32) if grads & _VGG_DY else None
-        wt, bt = ops._ptr_table(ws), ops._ptr_table(bs)
-        rc = _lib.lib().cdl_vgg_backward(P, H, W, wt, bt, grads, ops._ptr(g), ops._ptr(dx), ops._ptr(dy),
-                                         ops._ptr(scratch), scratch.numel(), ops._stream())
-        _lib.check(rc, "cdl_vgg_backward")
+        ops._call("cdl_vgg_backward", P, H, W, ws, bs, grads, g, dx, dy, scratch, scratch.numel())
         ctx.state = None
         return dx, dy, None, None
 
@@ -290,15 +276,12 @@ def vgg16_features(frames, weights):
     H4, W4 = H // 2 // 2, W // 2 // 2
     with torch.cuda.device(frames.device):
         ws, bs = _vgg_tables(weights, frames.device)
-        lib = _lib.lib()
-        n = int(lib.cdl_vgg_scratch_floats(P, H, W, 0))
+        n = int(_lib.lib().cdl_vgg_scratch_floats(P, H, W, 0))
         if n == 0:
             raise ValueError(f"vgg16_features: {P} planes of {H} x {W} not supported")
         scratch = torch.empty(n, device=frames.device, dtype=torch.float32)
         feat = torch.empty((P, 256, H4, W4), device=frames.device, dtype=torch.float32)
-        rc = lib.cdl_vgg_forward(None, ops._ptr(frames), P, H, W, ops._ptr_table(ws), ops._ptr_table(bs), 0,
-                                 ops._ptr(feat), None, ops._ptr(scratch), n, ops._stream())
-        _lib.check(rc, "cdl_vgg_forward")
+        ops._call("cdl_vgg_forward", None, frames, P, H, W, ws, bs, 0, feat, None, scratch, n)
     return feat.reshape(*lead, 256, H4, W4)
 
 

@@ -23,14 +23,12 @@ def nle_mad(y):
     if y.dim() != 4:
         raise ValueError("nle_mad expects (N, C, H, W)")
     N, C, H, W = y.shape
-    lib = _lib.lib()
-    n = int(lib.cdl_nle_mad_scratch_floats(N, C, H, W))
+    n = int(_lib.lib().cdl_nle_mad_scratch_floats(N, C, H, W))
     if n == 0:
         raise ValueError("image smaller than the 10 x 10 wavelet filter")
     scratch = ops._scratch(y.device, n)
     out = torch.empty(N, device=y.device, dtype=torch.float32)
-    rc = lib.cdl_nle_mad(ops._ptr(y), ops._ptr(out), ops._ptr(scratch), n, N, C, H, W, ops._stream())
-    _lib.check(rc, "cdl_nle_mad")
+    ops._call("cdl_nle_mad", y, out, scratch, n, N, C, H, W)
     return out.reshape(-1, 1, 1, 1)
 
 
@@ -78,13 +76,10 @@ def _cells(y, window, step):
     B, C, H, W = y.shape
     ny = len(cell_starts(band_length(H), window, step))
     nx = len(cell_starts(band_length(W), window, step))
-    lib = _lib.lib()
-    n = int(lib.cdl_nle_mad_cells_scratch_floats(B, C, H, W))
+    n = int(_lib.lib().cdl_nle_mad_cells_scratch_floats(B, C, H, W))
     scratch = ops._scratch(y.device, n)
     out = torch.empty((B, ny, nx), device=y.device, dtype=torch.float32)
-    rc = lib.cdl_nle_mad_cells(ops._ptr(y), ops._ptr(out), ops._ptr(scratch), n, B, C, H, W, window, step,
-                               ops._stream())
-    _lib.check(rc, "cdl_nle_mad_cells")
+    ops._call("cdl_nle_mad_cells", y, out, scratch, n, B, C, H, W, window, step)
     return out
 
 
@@ -208,16 +203,13 @@ def pca_gram(y, channel, patchsize, tau):
     over the patches of `channel` whose texture strength is below tau (float32; +inf keeps every patch) and count
     their number (int)."""
     N, C, H, W = y.shape
-    lib = _lib.lib()
-    n = int(lib.cdl_nle_pca_scratch_floats(N, C, H, W, patchsize))
+    n = int(_lib.lib().cdl_nle_pca_scratch_floats(N, C, H, W, patchsize))
     if n == 0:
         raise ValueError(f"nle_pca: patchsize {patchsize} outside 3..11 or larger than the image {H} x {W}")
     scratch = ops._scratch(y.device, n)
     gram = torch.empty(patchsize * patchsize, patchsize * patchsize, device=y.device, dtype=torch.float64)
     count = torch.empty(1, device=y.device, dtype=torch.int64)
-    rc = lib.cdl_nle_pca_gram(ops._ptr(y), N, C, H, W, channel, patchsize, float(tau), ops._ptr(gram),
-                              ops._ptr(count), ops._ptr(scratch), n, ops._stream())
-    _lib.check(rc, "cdl_nle_pca_gram")
+    ops._call("cdl_nle_pca_gram", y, N, C, H, W, channel, patchsize, tau, gram, count, scratch, n)
     return gram, int(count.item())
 
 

@@ -71,6 +71,96 @@ def _opt(t, name):
     return None if t is None else _dev(t, name)
 
 
+def _buf(t, name, shape=None, dtype=torch.float32):
+    """The non-copying sibling of `_dev` for outputs and work buffers the caller provides (None stays None): a kernel
+    writes through this very tensor, so a non-contiguous one is an error, never a `.contiguous()` copy."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on {t.device}: a buffer the HIP kernels write must live on the ROCm device")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor (strides {t.stride()})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+_KINDS = {}
+_PTR, _GEOM, _BCAST, _INT, _FLOAT, _ASIS = range(6)
+
+
+def _kinds(name):
+    """How `_call` converts each argument of an entry point, from its declared types (the stream, last, left out):
+    worked out once per entry point."""
+    kind = {_lib._P: _PTR, _lib._G: _GEOM, _lib._B: _BCAST, _lib._I: _INT, ctypes.c_size_t: _INT, _lib._F: _FLOAT}
+    sig = _lib.SIGNATURES[name]
+    assert sig and sig[-1] is _lib._P, f"{name} takes no stream"
+    _KINDS[name] = tuple(kind.get(t, _ASIS) for t in sig[:-1])
+    return _KINDS[name]
+
+
+def _check_pointer(t, cur, name, i):
+    """A tensor that is about to become a pointer in a kernel must be contiguous and on the current ROCm device (`cur`;
+    below -1: not asked for yet -- get_device() is -1 off the device, so a CPU tensor is refused without touching one).
+    Returns the current device."""
+    dev = t.get_device()
+    if dev < 0:
+        raise RuntimeError(f"{name}: argument {i} is on {t.device}, not on the ROCm device")
+    if dev != cur:
+        cur = torch.cuda.current_device()
+        if dev != cur:
+            raise RuntimeError(f"{name}: argument {i} is on {t.device} but this call runs on cuda:{cur}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: argument {i} is not contiguous")
+    return cur
+
+
+def _call(name, *args):
+    """The one way into a stream-taking entry point: `args` are the C arguments before the stream, converted by their
+    declared type in _lib.SIGNATURES -- Geometry / _lib.Bcast by reference, a tensor as its data pointer, None as NULL, a
+    list or tuple of tensors as a pointer table (an empty one: NULL; a None entry: NULL), Python numbers as int / float;
+    anything else (an int or float array) passes as it is.  Every tensor that becomes a pointer must be a contiguous CUDA
+    tensor of the current device: RuntimeError / ValueError here, before the library is entered, instead of a host or
+    foreign pointer in a kernel.  Appends the current stream and raises on the return code."""
+    kinds = _KINDS.get(name) or _kinds(name)
+    if len(args) != len(kinds):
+        raise TypeError(f"{name}: takes {len(kinds)} arguments before the stream, got {len(args)}")
+    cur = -2                                        # the current device: not asked for yet
+    cargs = list(args)                              # also what keeps the pointer tables alive for the call
+    for i, kind in enumerate(kinds):
+        a = cargs[i]
+        if kind == _PTR:
+            if a is None:
+                continue
+            if isinstance(a, torch.Tensor):
+                if a.get_device() != cur or not a.is_contiguous():      # the first tensor of a call, or a bad one
+                    cur = _check_pointer(a, cur, name, i)
+                cargs[i] = a.data_ptr()
+            elif isinstance(a, (list, tuple)):
+                for t in a:
+                    if t is not None:
+                        cur = _check_pointer(t, cur, name, i)
+                cargs[i] = (ctypes.c_void_p * len(a))(*[None if t is None else t.data_ptr() for t in a]) if a else None
+        elif kind == _GEOM:
+            cargs[i] = a._c_ref()
+        elif kind == _INT:
+            cargs[i] = int(a)
+        elif kind == _FLOAT:
+            cargs[i] = float(a)
+        elif kind == _BCAST:
+            cargs[i] = ctypes.byref(a)
+    _lib.check(getattr(_lib.lib(), name)(*cargs, _stream()), name)
+
+
+def _size(name, g):
+    """A size query of the library for geometry `g` (_lib.SIZE_T_FUNCS: host only, no stream)."""
+    return int(getattr(_lib.lib(), name)(g._c_ref()))
+
+
 def _three(v, fill):
     v = [int(x) for x in v]
     return [fill] * (3 - len(v)) + v
@@ -113,6 +203,14 @@ class Geometry:
 
     def c_struct(self):
         return _lib.Geom(self.N, self.C, self.M, *self.dims, *self.P, *self.pad, *self.stride)
+
+    def _c_ref(self):
+        """`const cdl_geom *` for a call: one struct per Geometry, made at first use (no entry point writes to it)."""
+        gs = self.__dict__.get("_gs")
+        if gs is None:
+            gs = self.c_struct()
+            object.__setattr__(self, "_gs", gs)
+        return ctypes.byref(gs)
 
     def code_shape(self):
         return (self.N, self.M) + self.code_spatial
@@ -166,9 +264,7 @@ def preprocess(y, s, mask=None):
     yp = torch.empty((N, C) + padded, device=y.device, dtype=torch.float32)
     mask_p = torch.empty_like(yp) if mask is not None else None
     mean = torch.empty(N, device=y.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_preprocess(_ptr(y), _ptr(mask), _ptr(yp), _ptr(mask_p), _ptr(mean),
-                                   N, C, *sp, p6, _stream())
-    _lib.check(rc, "cdl_preprocess")
+    _call("cdl_preprocess", y, mask, yp, mask_p, mean, N, C, *sp, p6)
     return yp, mean, pads, mask_p
 
 
@@ -181,8 +277,7 @@ def postprocess(xp, mean, pads):
     spp = _three(xp.shape[2:], 1)
     sp = [spp[i] - p6[2 * i] - p6[2 * i + 1] for i in range(3)]
     out = torch.empty((N, C) + tuple(sp[3 - nd:]), device=xp.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_postprocess(_ptr(xp), _ptr(mean), _ptr(out), N, C, *sp, p6, _stream())
-    _lib.check(rc, "cdl_postprocess")
+    _call("cdl_postprocess", xp, mean, out, N, C, *sp, p6)
     return out
 
 
@@ -194,8 +289,7 @@ def postprocess_bwd(gxhat, pads):
     sp = _three(gxhat.shape[2:], 1)
     spp = [sp[i] + p6[2 * i] + p6[2 * i + 1] for i in range(3)]
     out = torch.empty((N, C) + tuple(spp[3 - nd:]), device=gxhat.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_postprocess_bwd(_ptr(gxhat), _ptr(out), N, C, *sp, p6, _stream())
-    _lib.check(rc, "cdl_postprocess_bwd")
+    _call("cdl_postprocess_bwd", gxhat, out, N, C, *sp, p6)
     return out
 
 
@@ -212,8 +306,7 @@ def preprocess_bwd(dyp, pads, g_xhat=None, mask=None):
     dy = torch.empty((N, C) + tuple(sp[3 - nd:]), device=dyp.device, dtype=torch.float32)
     for t in (g_xhat, mask):
         assert t is None or tuple(t.shape) == tuple(dy.shape)
-    rc = _lib.lib().cdl_preprocess_bwd(_ptr(dyp), _ptr(g_xhat), _ptr(mask), _ptr(dy), N, C, *sp, p6, _stream())
-    _lib.check(rc, "cdl_preprocess_bwd")
+    _call("cdl_preprocess_bwd", dyp, g_xhat, mask, dy, N, C, *sp, p6)
     return dy
 
 
@@ -223,8 +316,7 @@ def thresholds(t, c, N):
     K, two, M = t.shape[:3]
     c = _opt(c, "c")
     tau = torch.empty((K, N, M), device=t.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_thresholds(_ptr(t), _ptr(c), _ptr(tau), K, N, M, _stream())
-    _lib.check(rc, "cdl_thresholds")
+    _call("cdl_thresholds", t, c, tau, K, N, M)
     return tau
 
 
@@ -234,8 +326,7 @@ def shrink(x, tau):
     rows = x.shape[0] * x.shape[1]
     assert tau.numel() == rows
     out = torch.empty_like(x)
-    rc = _lib.lib().cdl_shrink(_ptr(x), _ptr(tau), _ptr(out), rows, x.numel() // rows, _stream())
-    _lib.check(rc, "cdl_shrink")
+    _call("cdl_shrink", x, tau, out, rows, x.numel() // rows)
     return out
 
 
@@ -269,8 +360,7 @@ def shrink_b(x, tau):
     tau, st = _thr(tau, "tau", x.shape)
     N, M = x.shape[:2]
     out = torch.empty_like(x)
-    rc = _lib.lib().cdl_shrink_b(_ptr(x), _ptr(tau), ctypes.byref(st), _ptr(out), N, M, x.numel() // (N * M), _stream())
-    _lib.check(rc, "cdl_shrink_b")
+    _call("cdl_shrink_b", x, tau, st, out, N, M, x.numel() // (N * M))
     return out
 
 
@@ -279,12 +369,11 @@ def shrink_b_bwd(gup, x, tau, dtau_el=None):
     gradient per code element (cdl_shrink_b_bwd)."""
     gup, x = _dev(gup, "gup"), _dev(x, "x")
     tau, st = _thr(tau, "tau", x.shape)
-    assert gup.shape == x.shape and (dtau_el is None or (dtau_el.is_contiguous() and dtau_el.shape == x.shape))
+    dtau_el = _buf(dtau_el, "dtau_el", x.shape)
+    assert gup.shape == x.shape
     N, M = x.shape[:2]
     gx = torch.empty_like(x)
-    rc = _lib.lib().cdl_shrink_b_bwd(_ptr(gup), _ptr(x), _ptr(tau), ctypes.byref(st), _ptr(gx), _ptr(dtau_el), N, M,
-                                     x.numel() // (N * M), _stream())
-    _lib.check(rc, "cdl_shrink_b_bwd")
+    _call("cdl_shrink_b_bwd", gup, x, tau, st, gx, dtau_el, N, M, x.numel() // (N * M))
     return gx
 
 
@@ -295,10 +384,7 @@ def prox_csr_b(g: Geometry, u, z_prev, lam, gam1, z_after=None, gam2=None):
     (lam, sl), (gam1, s1) = _thr(lam, "lam", g.code_shape()), _thr(gam1, "gam1", g.code_shape())
     gam2, s2 = _thr(gam2, "gam2", g.code_shape()) if z_after is not None else (None, _lib.Bcast(0, 0, 0))
     out = torch.empty_like(u)
-    rc = _lib.lib().cdl_prox_csr_b(ctypes.byref(g.c_struct()), _ptr(u), _ptr(z_prev), _ptr(z_after), _ptr(lam),
-                                   ctypes.byref(sl), _ptr(gam1), ctypes.byref(s1), _ptr(gam2), ctypes.byref(s2), _ptr(out),
-                                   _stream())
-    _lib.check(rc, "cdl_prox_csr_b")
+    _call("cdl_prox_csr_b", g, u, z_prev, z_after, lam, sl, gam1, s1, gam2, s2, out)
     return out
 
 
@@ -308,7 +394,8 @@ def prox_csr_b_bwd(g: Geometry, gz, u, z_prev, lam, gam1, z_after=None, gam2=Non
     into.  Each threshold gradient asked for in `want` comes before the reduction over the threshold's broadcast axes:
     (N, M, 1..) row sums for a threshold without spatial extent, the code shape for one with."""
     gz, u, z_prev, z_after = _dev(gz, "gz"), _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
-    _check_codes(g, gz=gz, u=u, z_prev=z_prev, z_after=z_after, gz_prev=gz_prev, gz_after=gz_after)
+    gz_prev, gz_after = _buf(gz_prev, "gz_prev", g.code_shape()), _buf(gz_after, "gz_after", g.code_shape())
+    _check_codes(g, gz=gz, u=u, z_prev=z_prev, z_after=z_after)
     (lam, sl), (gam1, s1) = _thr(lam, "lam", g.code_shape()), _thr(gam1, "gam1", g.code_shape())
     gam2, s2 = _thr(gam2, "gam2", g.code_shape()) if z_after is not None else (None, _lib.Bcast(0, 0, 0))
     rows = (g.N, g.M) + (1,) * g.ndim
@@ -319,14 +406,10 @@ def prox_csr_b_bwd(g: Geometry, gz, u, z_prev, lam, gam1, z_after=None, gam2=Non
     dl, d1 = buf(want[0], sl), buf(want[1], s1)
     d2 = buf(want[2], s2) if z_after is not None else None
     gu = torch.empty_like(gz)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_prox_csr_scratch_floats(ctypes.byref(gs)))
+    n = _size("cdl_prox_csr_scratch_floats", g)
     scratch = torch.empty(n, device=gz.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_prox_csr_b_bwd(ctypes.byref(gs), _ptr(gz), _ptr(u), _ptr(z_prev), _ptr(z_after), _ptr(lam),
-                                       ctypes.byref(sl), _ptr(gam1), ctypes.byref(s1), _ptr(gam2), ctypes.byref(s2), _ptr(gu),
-                                       _ptr(gz_prev), _ptr(gz_after), _ptr(dl), _ptr(d1), _ptr(d2), _ptr(scratch), n,
-                                       _stream())
-    _lib.check(rc, "cdl_prox_csr_b_bwd")
+    _call("cdl_prox_csr_b_bwd", g, gz, u, z_prev, z_after, lam, sl, gam1, s1, gam2, s2, gu, gz_prev, gz_after, dl, d1, d2,
+          scratch, n)
     return gu, dl, d1, d2
 
 
@@ -338,25 +421,39 @@ def _check_map(g: Geometry, cmap, tslope=None, rows=1):
         raise ValueError(f"tslope: expected {rows * g.M} values, got {tslope.numel()}")
 
 
+def _check_map_pair(g: Geometry, cmap, tslope, rows=1):
+    """A noise-level map and its slope row(s) go together: both through `_opt` and `_check_map`, or both None."""
+    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
+    if (cmap is None) != (tslope is None):
+        raise ValueError("cmap and tslope go together")
+    _check_map(g, cmap, tslope, rows)
+    return cmap, tslope
+
+
+def _check_rows(g: Geometry, **thresholds):
+    """Thresholds of the (N, M) row form: one value per (sample, channel)."""
+    for name, t in thresholds.items():
+        if t is not None and t.numel() != g.N * g.M:
+            raise ValueError(f"{name}: expected {g.N * g.M} per-(sample, channel) thresholds")
+
+
+def _check_codes(g: Geometry, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (tuple(t.shape) != g.code_shape() or not t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous tensor of the code shape {g.code_shape()}")
+
+
 def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=None, *, cmap=None, tslope=None):
     """cdl_analysis_ws.  cmap (N,1,*code_spatial) with tslope (M): the threshold of element (n, m, pix) is
     tau[n,m] + cmap[n,pix] * tslope[m] (tau then holds t[k,0,m])."""
     x, w = _dev(x, "x"), _dev(w, "w")
     zin, gate, tau = _opt(zin, "zin"), _opt(gate, "gate"), _opt(tau, "tau")
-    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
-    if (cmap is None) != (tslope is None):
-        raise ValueError("cmap and tslope go together")
-    _check_map(g, cmap, tslope)
+    cmap, tslope = _check_map_pair(g, cmap, tslope)
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
-    if out is None:
-        out = torch.empty(g.code_shape(), device=x.device, dtype=torch.float32)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_analysis_workspace_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n) if n else None
-    rc = _lib.lib().cdl_analysis_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin),
-                                    _ptr(gate), _ptr(tau), _ptr(out), _ptr(ws), n, _ptr(cmap), _ptr(tslope), _stream())
-    _lib.check(rc, "cdl_analysis_ws")
+    out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
+    ws, n = _analysis_workspace(g, x.device)
+    _call("cdl_analysis_ws", g, x, w, alpha, zin, gate, tau, out, ws, n, cmap, tslope)
     return out
 
 
@@ -365,14 +462,9 @@ def synthesis(g: Geometry, z, w, alpha=1.0, gate=None, mask=None, sub=None, out=
     gate, mask, sub = _opt(gate, "gate"), _opt(mask, "mask"), _opt(sub, "sub")
     assert tuple(z.shape) == g.code_shape(), (z.shape, g.code_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
-    if out is None:
-        out = torch.empty(g.image_shape(), device=z.device, dtype=torch.float32)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_synthesis_workspace_floats(ctypes.byref(gs)))
-    ws = _scratch(z.device, n) if n else None
-    rc = _lib.lib().cdl_synthesis_ws(ctypes.byref(gs), _ptr(z), _ptr(gate), _ptr(w), float(alpha),
-                                     _ptr(mask), _ptr(sub), _ptr(out), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_synthesis_ws")
+    out = _new(g.image_shape(), z.device) if out is None else _buf(out, "out")
+    n = _size("cdl_synthesis_workspace_floats", g)
+    _call("cdl_synthesis_ws", g, z, gate, w, alpha, mask, sub, out, _scratch(z.device, n) if n else None, n)
     return out
 
 
@@ -391,18 +483,34 @@ def _scratch(device, n):
     return buf
 
 
+def _analysis_workspace(g: Geometry, device):
+    """(scratch or None, floats) for the analysis entry points that take a workspace."""
+    n = _size("cdl_analysis_workspace_floats", g)
+    return (_scratch(device, n) if n else None), n
+
+
+def _wgrad_workspace(g: Geometry, device):
+    """(buffer, floats): the filter-gradient workspace, one per (device, stream, size), reused."""
+    n = _size("cdl_wgrad_workspace_floats", g)
+    key = (device, torch.cuda.current_stream(device).cuda_stream, n)
+    ws = _WGRAD_WS.get(key)
+    if ws is None:
+        ws = _WGRAD_WS[key] = torch.empty(max(n, 1), device=device, dtype=torch.float32)
+    return ws, n
+
+
+def _filter_grads(g: Geometry, K, device):
+    """(dA list, dB list) of a reverse sweep: one allocation, 2K views (at cfg1's size the allocator calls cost more
+    than the kernels)."""
+    dAB = torch.empty((2 * K,) + g.filter_shape(), device=device, dtype=torch.float32)
+    return list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
+
+
 def wgrad(g: Geometry, z, x, alpha=1.0, gate=None):
     z, x, gate = _dev(z, "z"), _dev(x, "x"), _opt(gate, "gate")
     dw = torch.empty(g.filter_shape(), device=z.device, dtype=torch.float32)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_wgrad_workspace_floats(ctypes.byref(gs)))
-    key = (z.device, torch.cuda.current_stream(z.device).cuda_stream, n)
-    ws = _WGRAD_WS.get(key)                       # one scratch buffer per (device, stream, size), reused
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(max(n, 1), device=z.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_wgrad(ctypes.byref(gs), _ptr(z), _ptr(gate), _ptr(x), float(alpha), _ptr(dw),
-                              _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_wgrad")
+    ws, n = _wgrad_workspace(g, z.device)
+    _call("cdl_wgrad", g, z, gate, x, alpha, dw, ws, n)
     return dw
 
 
@@ -412,16 +520,24 @@ def wgrad_pair(g: Geometry, z0, x0, alpha0, z1, x1, alpha1):
     z0, x0, z1, x1 = _dev(z0, "z0"), _dev(x0, "x0"), _dev(z1, "z1"), _dev(x1, "x1")
     dw0 = torch.empty(g.filter_shape(), device=z0.device, dtype=torch.float32)
     dw1 = torch.empty_like(dw0)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_wgrad_workspace_floats(ctypes.byref(gs)))
-    key = (z0.device, torch.cuda.current_stream(z0.device).cuda_stream, n)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = _WGRAD_WS[key] = torch.empty(max(n, 1), device=z0.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_wgrad_pair(ctypes.byref(gs), _ptr(z0), _ptr(x0), float(alpha0), _ptr(dw0), _ptr(z1), _ptr(x1),
-                                   float(alpha1), _ptr(dw1), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_wgrad_pair")
+    ws, n = _wgrad_workspace(g, z0.device)
+    _call("cdl_wgrad_pair", g, z0, x0, alpha0, dw0, z1, x1, alpha1, dw1, ws, n)
     return dw0, dw1
+
+
+def _dt_halves(g: Geometry, dt_k, name="dt_k"):
+    """The (2, M) threshold-gradient slice of one iteration as its two rows (views: the kernels take them separately)."""
+    halves = _buf(dt_k, name).reshape(2, -1)
+    if halves.shape[1] != g.M:
+        raise ValueError(f"{name}: expected 2 x {g.M} values, got {dt_k.numel()}")
+    return halves[0], halves[1]
+
+
+def _dtau_rows(g: Geometry, dtau_n):
+    """The optional per-sample (N, M) threshold gradient of one iteration."""
+    if _buf(dtau_n, "dtau_n") is not None and dtau_n.numel() != g.N * g.M:
+        raise ValueError(f"dtau_n: expected {g.N * g.M} values, got {dtau_n.numel()}")
+    return dtau_n
 
 
 def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None, *, cmap=None, gate=False):
@@ -430,34 +546,26 @@ def tau_grad(g: Geometry, gup, zout, c, dt_k, dtau_n=None, *, cmap=None, gate=Fa
     of `zout` (cdl_tau_grad_gate)."""
     gup, zout, c, cmap = _dev(gup, "g"), _dev(zout, "zout"), _opt(c, "c"), _opt(cmap, "cmap")
     _check_map(g, cmap)
+    dt0, dt1 = _dt_halves(g, dt_k)
+    dtau_n = _dtau_rows(g, dtau_n)
     # CDL_TAU_SPLITS * N * M (twice with a map)
     scratch = torch.empty((32 if cmap is not None else 16) * g.N * g.M, device=gup.device, dtype=torch.float32)
-    assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
-    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
-    gs = g.c_struct()
-    base = dt_k.data_ptr()
-    fn = _lib.lib().cdl_tau_grad_gate if gate else _lib.lib().cdl_tau_grad
-    rc = fn(ctypes.byref(gs), _ptr(gup), _ptr(zout), _ptr(c), ctypes.c_void_p(base),
-            ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n), _ptr(scratch), _ptr(cmap), _stream())
-    _lib.check(rc, "cdl_tau_grad_gate" if gate else "cdl_tau_grad")
+    _call("cdl_tau_grad_gate" if gate else "cdl_tau_grad", g, gup, zout, c, dt0, dt1, dtau_n, scratch, cmap)
 
 
 def sigma_grad(g: Geometry, du, z, tslope, dcmap, acc_add):
     """dcmap (N,1,*code_spatial) (+)= -sum_m tslope[m] sign(z) du: the noise-level map's gradient of one iteration
     (cdl_sigma_grad); du is the gated dL/du_k, z = z_{k+1}."""
     du, z, tslope = _dev(du, "du"), _dev(z, "z"), _dev(tslope, "tslope")
-    assert tuple(du.shape) == g.code_shape() == tuple(z.shape) and dcmap.is_contiguous()
-    _check_map(g, dcmap, tslope)
-    rc = _lib.lib().cdl_sigma_grad(ctypes.byref(g.c_struct()), _ptr(du), _ptr(z), _ptr(tslope), _ptr(dcmap),
-                                   int(bool(acc_add)), _stream())
-    _lib.check(rc, "cdl_sigma_grad")
+    _check_map(g, _buf(dcmap, "dcmap"), tslope)
+    assert tuple(du.shape) == g.code_shape() == tuple(z.shape)
+    _call("cdl_sigma_grad", g, du, z, tslope, dcmap, bool(acc_add))
 
 
 def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
     """Generic reverse sweep: q holds S = A_k^T du_k (unmasked); dyp (+)= S, then q = -mask * S in place (cdl_dyp_split)."""
-    rc = _lib.lib().cdl_dyp_split(ctypes.byref(g.c_struct()), _ptr(q), _ptr(_opt(mask, "mask")), _ptr(dyp),
-                                  int(bool(acc_add)), int(bool(make_q)), _stream())
-    _lib.check(rc, "cdl_dyp_split")
+    q, dyp = _buf(q, "q", g.image_shape()), _buf(dyp, "dyp", g.image_shape())
+    _call("cdl_dyp_split", g, q, _opt(mask, "mask"), dyp, bool(acc_add), bool(make_q))
 
 
 def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None, *, cmap=None):
@@ -467,17 +575,10 @@ def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None, *, cmap
     x, w, zin, zsup, c = _dev(x, "x"), _dev(w, "w"), _opt(zin, "zin"), _dev(zsup, "zsup"), _opt(c, "c")
     cmap = _opt(cmap, "cmap")                                  # the noise-level map in place of c (dt_k[1] weighted by it)
     _check_map(g, cmap)
-    if out is None:
-        out = _new(g.code_shape(), x.device)
-    assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_analysis_rev_workspace_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n)
-    base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_analysis_rev_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(zsup), _ptr(c),
-                                        ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), None, _ptr(out), _ptr(ws),
-                                        n, _ptr(cmap), _stream())
-    _lib.check(rc, "cdl_analysis_rev_ws")
+    dt0, dt1 = _dt_halves(g, dt_k)
+    out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
+    n = _size("cdl_analysis_rev_workspace_floats", g)
+    _call("cdl_analysis_rev_ws", g, x, w, alpha, zin, zsup, c, dt0, dt1, None, out, _scratch(x.device, n), n, cmap)
     return out
 
 
@@ -485,28 +586,11 @@ def prox_csr(g: Geometry, u, z_prev, lam, gam1, z_after=None, gam2=None, out=Non
     """prox_CSR (z_after None) / prox_CSR_f2 of net.py:229-262; lam, gam* are (N,M) like tau."""
     u, z_prev, lam, gam1 = _dev(u, "u"), _dev(z_prev, "z_prev"), _dev(lam, "lam"), _dev(gam1, "gam1")
     z_after, gam2 = _opt(z_after, "z_after"), _opt(gam2, "gam2")
-    for name, t in (("u", u), ("z_prev", z_prev), ("z_after", z_after)):
-        if t is not None and tuple(t.shape) != g.code_shape():
-            raise ValueError(f"{name}: shape {tuple(t.shape)} is not the code shape {g.code_shape()}")
-    for name, t in (("lam", lam), ("gam1", gam1), ("gam2", gam2)):
-        if t is not None and t.numel() != g.N * g.M:
-            raise ValueError(f"{name}: expected {g.N * g.M} per-(sample, channel) thresholds")
-    if out is None:
-        out = torch.empty_like(u)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_prox_csr(ctypes.byref(gs), _ptr(u), _ptr(z_prev), _ptr(z_after), _ptr(lam), _ptr(gam1),
-                                 _ptr(gam2), _ptr(out), _stream())
-    _lib.check(rc, "cdl_prox_csr")
+    _check_codes(g, u=u, z_prev=z_prev, z_after=z_after)
+    _check_rows(g, lam=lam, gam1=gam1, gam2=gam2)
+    out = torch.empty_like(u) if out is None else _buf(out, "out", g.code_shape())
+    _call("cdl_prox_csr", g, u, z_prev, z_after, lam, gam1, gam2, out)
     return out
-
-
-def _check_csr_map(g: Geometry, cmap, tslope, rows=1):
-    """The CSR maps under a noise-level map: cmap as _check_map's, tslope `rows` x (3, M) slopes of lam, gam1, gam2."""
-    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
-    if (cmap is None) != (tslope is None):
-        raise ValueError("cmap and tslope go together")
-    _check_map(g, cmap, tslope, 3 * rows)
-    return cmap, tslope
 
 
 def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None, gam2=None, u_out=None, out=None, *,
@@ -515,30 +599,17 @@ def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None
     (a code-shaped tensor) receives the pre-shrinkage value when given.  cmap (N,1,*code_spatial) with tslope (3,M): the
     thresholds of element (n, m, pix) are lam[n,m] + cmap[n,pix] * tslope[0,m], and the same for gam1, gam2."""
     x, w = _dev(x, "x"), _dev(w, "w")
-    cmap, tslope = _check_csr_map(g, cmap, tslope)
+    cmap, tslope = _check_map_pair(g, cmap, tslope, 3)          # the slopes of lam, gam1, gam2
     zin, z_prev, z_after = _opt(zin, "zin"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
-    for name, t in (("zin", zin), ("z_prev", z_prev), ("z_after", z_after), ("u_out", u_out)):
-        if t is not None and (tuple(t.shape) != g.code_shape() or not t.is_contiguous()):
-            raise ValueError(f"{name}: expected a contiguous tensor of the code shape {g.code_shape()}")
-    if out is None:
-        out = torch.empty(g.code_shape(), device=x.device, dtype=torch.float32)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_analysis_workspace_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n) if n else None
-    rc = _lib.lib().cdl_analysis_prox_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(z_prev),
-                                         _ptr(z_after), _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")),
-                                         _ptr(_opt(gam2, "gam2")), _ptr(u_out), _ptr(out), _ptr(ws), n, _ptr(cmap),
-                                         _ptr(tslope), _stream())
-    _lib.check(rc, "cdl_analysis_prox_ws")
+    _check_codes(g, zin=zin, z_prev=z_prev, z_after=z_after)
+    u_out = _buf(u_out, "u_out", g.code_shape())
+    out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
+    ws, n = _analysis_workspace(g, x.device)
+    _call("cdl_analysis_prox_ws", g, x, w, alpha, zin, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
+          _opt(gam2, "gam2"), u_out, out, ws, n, cmap, tslope)
     return out
-
-
-def _check_codes(g: Geometry, **tensors):
-    for name, t in tensors.items():
-        if t is not None and (tuple(t.shape) != g.code_shape() or not t.is_contiguous()):
-            raise ValueError(f"{name}: expected a contiguous tensor of the code shape {g.code_shape()}")
 
 
 def prox_csr_tangent(g: Geometry, ud, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None, zd_after=None,
@@ -548,16 +619,10 @@ def prox_csr_tangent(g: Geometry, ud, u, z_prev, lam, gam1, z_after=None, gam2=N
     ud, u, z_prev, lam, gam1 = _dev(ud, "ud"), _dev(u, "u"), _dev(z_prev, "z_prev"), _dev(lam, "lam"), _dev(gam1, "gam1")
     z_after, gam2 = _opt(z_after, "z_after"), _opt(gam2, "gam2")
     zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
-    _check_codes(g, ud=ud, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, out=out)
-    for name, t in (("lam", lam), ("gam1", gam1), ("gam2", gam2)):
-        if t is not None and t.numel() != g.N * g.M:
-            raise ValueError(f"{name}: expected {g.N * g.M} per-(sample, channel) thresholds")
-    if out is None:
-        out = torch.empty_like(ud)
-    rc = _lib.lib().cdl_prox_csr_tangent(ctypes.byref(g.c_struct()), _ptr(ud), _ptr(u), _ptr(z_prev), _ptr(z_after),
-                                         _ptr(lam), _ptr(gam1), _ptr(gam2), _ptr(zd_prev), _ptr(zd_after), _ptr(out),
-                                         _stream())
-    _lib.check(rc, "cdl_prox_csr_tangent")
+    _check_codes(g, ud=ud, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after)
+    _check_rows(g, lam=lam, gam1=gam1, gam2=gam2)
+    out = torch.empty_like(ud) if out is None else _buf(out, "out", g.code_shape())
+    _call("cdl_prox_csr_tangent", g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out)
     return out
 
 
@@ -570,17 +635,11 @@ def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z
     zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
-    _check_codes(g, zin=zin, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, out=out)
-    if out is None:
-        out = torch.empty(g.code_shape(), device=x.device, dtype=torch.float32)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_analysis_workspace_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n) if n else None
-    rc = _lib.lib().cdl_analysis_prox_tangent_ws(ctypes.byref(gs), _ptr(x), _ptr(w), float(alpha), _ptr(zin), _ptr(u),
-                                                 _ptr(z_prev), _ptr(z_after), _ptr(_dev(lam, "lam")),
-                                                 _ptr(_dev(gam1, "gam1")), _ptr(_opt(gam2, "gam2")), _ptr(zd_prev),
-                                                 _ptr(zd_after), _ptr(out), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_analysis_prox_tangent_ws")
+    _check_codes(g, zin=zin, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after)
+    out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out", g.code_shape())
+    ws, n = _analysis_workspace(g, x.device)
+    _call("cdl_analysis_prox_tangent_ws", g, x, w, alpha, zin, u, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
+          _opt(gam2, "gam2"), zd_prev, zd_after, out, ws, n)
     return out
 
 
@@ -592,27 +651,21 @@ def prox_csr_bwd(g: Geometry, gz, u, z_prev, lam, gam1, c, dlam, dgam1, z_after=
     (N,1,*code_spatial) is accumulated into."""
     gz, u, z_prev = _dev(gz, "gz"), _dev(u, "u"), _dev(z_prev, "z_prev")
     z_after, gam2, c = _opt(z_after, "z_after"), _opt(gam2, "gam2"), _opt(c, "c")
-    cmap, tslope = _check_csr_map(g, cmap, tslope)
-    if dcmap is not None:
-        assert cmap is not None and dcmap.is_contiguous() and dcmap.dtype == torch.float32
+    cmap, tslope = _check_map_pair(g, cmap, tslope, 3)
+    if _buf(dcmap, "dcmap") is not None:
+        if cmap is None:
+            raise ValueError("dcmap: there is no cmap to take the gradient of")
         _check_map(g, dcmap)
-    if dsum_n is not None:
-        assert dsum_n.is_contiguous() and dsum_n.dtype == torch.float32 and tuple(dsum_n.shape) == (3, g.N, g.M)
-    for t in (dlam, dgam1, dgam2):
-        assert t is None or (t.is_contiguous() and t.numel() == 2 * g.M)
-    for t in (gz_prev, gz_after):
-        assert t is None or (t.is_contiguous() and tuple(t.shape) == g.code_shape())
-    if out is None:
-        out = torch.empty_like(gz)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_prox_csr_scratch_floats(ctypes.byref(gs)))
+    dsum_n = _buf(dsum_n, "dsum_n", (3, g.N, g.M))
+    for name, t in (("dlam", dlam), ("dgam1", dgam1), ("dgam2", dgam2)):
+        if _buf(t, name) is not None and t.numel() != 2 * g.M:
+            raise ValueError(f"{name}: expected 2 x {g.M} values, got {t.numel()}")
+    gz_prev, gz_after = _buf(gz_prev, "gz_prev", g.code_shape()), _buf(gz_after, "gz_after", g.code_shape())
+    out = torch.empty_like(gz) if out is None else _buf(out, "out", g.code_shape())
+    n = _size("cdl_prox_csr_scratch_floats", g)
     scratch = torch.empty(n, device=gz.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_prox_csr_bwd(ctypes.byref(gs), _ptr(gz), _ptr(u), _ptr(z_prev), _ptr(z_after),
-                                     _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")), _ptr(gam2), _ptr(c),
-                                     _ptr(out), _ptr(gz_prev), _ptr(gz_after), _ptr(dlam), _ptr(dgam1),
-                                     _ptr(dgam2), _ptr(scratch), n, _ptr(cmap), _ptr(tslope), _ptr(dcmap), _ptr(dsum_n),
-                                     _stream())
-    _lib.check(rc, "cdl_prox_csr_bwd")
+    _call("cdl_prox_csr_bwd", g, gz, u, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"), gam2, c, out, gz_prev,
+          gz_after, dlam, dgam1, dgam2, scratch, n, cmap, tslope, dcmap, dsum_n)
     return out
 
 
@@ -630,12 +683,8 @@ def residual_forward(g: Geometry, x, w1, w2):
     x, w1, w2 = _dev(x, "x"), _dev(w1, "w1"), _dev(w2, "w2")
     assert tuple(x.shape) == g.code_shape() and tuple(w1.shape) == g.filter_shape() == tuple(w2.shape)
     h, out = torch.empty_like(x), torch.empty_like(x)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_residual_scratch_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n) if n else None
-    rc = _lib.lib().cdl_residual_forward(ctypes.byref(gs), _ptr(x), _ptr(w1), _ptr(w2), _ptr(h), _ptr(out),
-                                         _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_residual_forward")
+    n = _size("cdl_residual_scratch_floats", g)
+    _call("cdl_residual_forward", g, x, w1, w2, h, out, _scratch(x.device, n) if n else None, n)
     return h, out
 
 
@@ -646,13 +695,8 @@ def residual_backward(g: Geometry, x, h, out, w1, w2, g_out):
     new = lambda t: torch.empty(t.shape, device=t.device, dtype=torch.float32)      # contiguous, whatever t's strides
     dx, dh = new(x), new(x)
     dw1, dw2 = new(w1), new(w2)
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_residual_scratch_floats(ctypes.byref(gs)))
-    ws = _scratch(x.device, n) if n else None
-    rc = _lib.lib().cdl_residual_backward(ctypes.byref(gs), _ptr(x), _ptr(h), _ptr(out), _ptr(w1), _ptr(w2),
-                                          _ptr(g_out), _ptr(dx), _ptr(dw1), _ptr(dw2), _ptr(dh), _ptr(ws), n,
-                                          _stream())
-    _lib.check(rc, "cdl_residual_backward")
+    n = _size("cdl_residual_scratch_floats", g)
+    _call("cdl_residual_backward", g, x, h, out, w1, w2, g_out, dx, dw1, dw2, dh, _scratch(x.device, n) if n else None, n)
     return dx, dw1, dw2
 
 
@@ -662,8 +706,7 @@ def project_filters_(w):
         raise RuntimeError("project(): parameters must live on the ROCm device (no CPU path)")
     assert w.dtype == torch.float32 and w.is_contiguous()
     nf = w.shape[0] * w.shape[1]
-    rc = _lib.lib().cdl_project_filters(_ptr(w), nf, w.numel() // nf, _stream())
-    _lib.check(rc, "cdl_project_filters")
+    _call("cdl_project_filters", w, nf, w.numel() // nf)
     return w
 
 
@@ -678,17 +721,14 @@ def project_filter_banks_(banks):
             raise RuntimeError("project(): parameters must live on the ROCm device (no CPU path)")
         assert w.dtype == torch.float32 and w.is_contiguous() and w.shape == w0.shape
     nf = w0.shape[0] * w0.shape[1]
-    rc = _lib.lib().cdl_project_filter_banks(_ptr_table(banks), len(banks), nf, w0.numel() // nf, _stream())
-    _lib.check(rc, "cdl_project_filter_banks")
+    _call("cdl_project_filter_banks", banks, len(banks), nf, w0.numel() // nf)
 
 
 def gabor_filters(alpha, a, w0, psi, P, transpose):
     alpha, a, w0, psi = (_dev(v, n) for v, n in ((alpha, "alpha"), (a, "a"), (w0, "w0"), (psi, "psi")))
     order, M, C = psi.shape
     w = torch.empty((M, C, P, P), device=psi.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_gabor_filters(_ptr(alpha), _ptr(a), _ptr(w0), _ptr(psi), _ptr(w), order, M, C,
-                                      P, int(bool(transpose)), _stream())
-    _lib.check(rc, "cdl_gabor_filters")
+    _call("cdl_gabor_filters", alpha, a, w0, psi, w, order, M, C, P, bool(transpose))
     return w
 
 
@@ -697,10 +737,7 @@ def gabor_filters_bwd(alpha, a, w0, psi, dw, P, transpose):
                                                       (psi, "psi"), (dw, "dw")))
     order, M, C = psi.shape
     outs = [torch.empty_like(v) for v in (alpha, a, w0, psi)]
-    rc = _lib.lib().cdl_gabor_filters_bwd(_ptr(alpha), _ptr(a), _ptr(w0), _ptr(psi), _ptr(dw),
-                                          *(_ptr(o) for o in outs), order, M, C, P,
-                                          int(bool(transpose)), _stream())
-    _lib.check(rc, "cdl_gabor_filters_bwd")
+    _call("cdl_gabor_filters_bwd", alpha, a, w0, psi, dw, *outs, order, M, C, P, bool(transpose))
     return outs
 
 
@@ -713,9 +750,7 @@ def gabor_filter_banks(params, P, transposes):
     out = torch.empty((nb, M, C, P, P), device=params[0][3].device, dtype=torch.float32)
     ws = list(out.unbind(0))
     flags = (ctypes.c_int * nb)(*[int(bool(t)) for t in transposes])
-    rc = _lib.lib().cdl_gabor_filter_banks(nb, *(_ptr_table([pr[i] for pr in params]) for i in range(4)), flags,
-                                           _ptr_table(ws), order, M, C, P, _stream())
-    _lib.check(rc, "cdl_gabor_filter_banks")
+    _call("cdl_gabor_filter_banks", nb, *zip(*params), flags, ws, order, M, C, P)
     return ws
 
 
@@ -729,10 +764,7 @@ def gabor_filter_banks_bwd(params, dws, P, transposes):
     dev = params[0][3].device
     blocks = torch.empty((nb, 6 * nq), device=dev, dtype=torch.float32)
     flags = (ctypes.c_int * nb)(*[int(bool(t)) for t in transposes])
-    dwtab = (ctypes.c_void_p * nb)(*[None if d is None else d.data_ptr() for d in dws])
-    rc = _lib.lib().cdl_gabor_filter_banks_bwd(nb, *(_ptr_table([pr[i] for pr in params]) for i in range(4)), flags,
-                                               dwtab, _ptr_table(list(blocks.unbind(0))), order, M, C, P, _stream())
-    _lib.check(rc, "cdl_gabor_filter_banks_bwd")
+    _call("cdl_gabor_filter_banks_bwd", nb, *zip(*params), flags, dws, blocks.unbind(0), order, M, C, P)
     outs = []
     for k, pr in enumerate(params):
         b = blocks[k]
@@ -844,6 +876,7 @@ class trace:
 # reference's layout, "blocked" the pixel-blocked fp32 layout (same values, 16-byte accesses, the default),
 # "blocked_bf16" opt-in bf16 STORAGE of the codes (half the bytes; outside the 1e-5 parity gate)
 LAYOUT = {"nchw": 0, "blocked": 1, "blocked_bf16": 2, "rsc": 3}
+_FUSED_LAYOUTS = ("nchw", "blocked", "blocked_bf16")     # of the fused 2-D kernels; "rsc": the strip kernels' (fusedg_*)
 TILES_REVERSED = 16
 
 
@@ -859,8 +892,7 @@ def fused_code_buffer(g: "Geometry", layout, device, count=1):
     """`count` code tensors in `layout`: NCHW tensors for "nchw", flat byte-sized fp32 / bf16 buffers otherwise."""
     if layout == "nchw":
         return torch.empty((count,) + g.code_shape(), device=device, dtype=torch.float32)
-    gs = g.c_struct()
-    nbytes = int(_lib.lib().cdl_fused2d_code_bytes(ctypes.byref(gs), LAYOUT[layout]))
+    nbytes = int(_lib.lib().cdl_fused2d_code_bytes(ctypes.byref(g.c_struct()), LAYOUT[layout]))
     assert nbytes > 0
     if layout == "blocked":
         return torch.empty((count, nbytes // 4), device=device, dtype=torch.float32)
@@ -889,8 +921,7 @@ def fused_from_nchw(g: "Geometry", z, layout):
 
 
 def fused_supported(g: Geometry) -> bool:
-    gs = g.c_struct()
-    return bool(_lib.lib().cdl_fused2d_supported(ctypes.byref(gs)))
+    return bool(_size("cdl_fused2d_supported", g))
 
 
 def fused_prep(wA, wB):
@@ -900,22 +931,17 @@ def fused_prep(wA, wB):
     M, P = wA.shape[0], wA.shape[-1]
     nbytes = _lib.lib().cdl_fused2d_frag_bytes(M)
     frags = torch.empty(nbytes, device=wA.device, dtype=torch.uint8)
-    rc = _lib.lib().cdl_fused2d_prep(_ptr(wA), _ptr(wB), _ptr(frags), M, P, _stream())
-    _lib.check(rc, "cdl_fused2d_prep")
+    _call("cdl_fused2d_prep", wA, wB, frags, M, P)
     return frags
 
 
 def fused_patches(g: Geometry, device):
-    gs = g.c_struct()
-    n = _lib.lib().cdl_fused2d_patch_floats(ctypes.byref(gs))
-    return torch.empty(n, device=device, dtype=torch.float32)
+    return torch.empty(_size("cdl_fused2d_patch_floats", g), device=device, dtype=torch.float32)
 
 
 def fused_map(g: Geometry, device):
     """Empty support/sign bit map of one code tensor: (N, 4, H, W) int32 words (cdl_fused2d_map_words)."""
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_fused2d_map_words(ctypes.byref(gs)))
-    assert n == g.N * 4 * g.dims[1] * g.dims[2]
+    assert _size("cdl_fused2d_map_words", g) == g.N * 4 * g.dims[1] * g.dims[2]
     return torch.empty((g.N, 4, g.dims[1], g.dims[2]), device=device, dtype=torch.int32)
 
 
@@ -924,11 +950,8 @@ def fused_support_map(g: Geometry, z, out=None):
     gets it for free from cdl_fused2d_iter_fwd)."""
     z = _dev(z, "z")
     assert tuple(z.shape) == g.code_shape()
-    if out is None:
-        out = fused_map(g, z.device)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_support_map(ctypes.byref(gs), _ptr(z), _ptr(out), _stream())
-    _lib.check(rc, "cdl_fused2d_support_map")
+    out = fused_map(g, z.device) if out is None else _buf(out, "out", dtype=torch.int32)
+    _call("cdl_fused2d_support_map", g, z, out)
     return out
 
 
@@ -939,13 +962,20 @@ def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3"
     if zin is not None and lay_in == "nchw":
         zin = _dev(zin, "zin")
     assert tuple(r.shape) == g.image_shape()
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    map_out = _buf(map_out, "map_out", dtype=torch.int32)
     if out is None:
         out = fused_code_buffer(g, lay_out, r.device)[0]
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_iter_fwd(ctypes.byref(gs), _ptr(r), _ptr(zin), _ptr(tau), _ptr(frags),
-                                         float(sgn), _ptr(out), _ptr(patches), _ptr(map_out),
-                                         PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out), _stream())
-    _lib.check(rc, "cdl_fused2d_iter_fwd")
+    _call("cdl_fused2d_iter_fwd", g, r, zin, tau, frags, sgn, out, patches, map_out,
+          PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
+    return out
+
+
+def _assemble(symbol, g, patches, mask, sub, alpha, out, acc, acc_add, write_out):
+    patches, acc = _buf(patches, "patches"), _buf(acc, "acc", g.image_shape())
+    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
+    out = (_new(g.image_shape(), patches.device) if out is None else _buf(out, "out")) if write_out else None
+    _call(symbol, g, patches, mask, sub, alpha, out, acc, bool(acc_add))
     return out
 
 
@@ -953,20 +983,11 @@ def fused_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=Non
                    write_out=True):
     """out = mask * alpha * (overlap-sum of the patches) - sub [and acc = S or acc += S with S the unmasked, unscaled
     overlap-sum]; write_out=False: acc only.  Returns out (None without write_out)."""
-    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    assert acc is None or (acc.is_contiguous() and tuple(acc.shape) == g.image_shape())
-    if write_out and out is None:
-        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_fused2d_assemble(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub),
-                                         float(alpha), _ptr(out if write_out else None), _ptr(acc),
-                                         int(bool(acc_add)), _stream())
-    _lib.check(rc, "cdl_fused2d_assemble")
-    return out if write_out else None
+    return _assemble("cdl_fused2d_assemble", g, patches, mask, sub, alpha, out, acc, acc_add, write_out)
 
 
 def fused_tiles(g: Geometry) -> int:
-    gs = g.c_struct()
-    return int(_lib.lib().cdl_fused2d_tiles(ctypes.byref(gs)))
+    return _size("cdl_fused2d_tiles", g)
 
 
 def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
@@ -980,36 +1001,32 @@ def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial,
         base = _dev(base, "base")
     if gate.dtype != torch.int32:
         gate = fused_support_map(g, gate)
-    assert gate.is_cuda and gate.is_contiguous() and gate.numel() == g.N * 4 * g.dims[1] * g.dims[2]
+    gate = _buf(gate, "gate", dtype=torch.int32)
+    assert gate.numel() == g.N * 4 * g.dims[1] * g.dims[2]
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    dtau_partial, workspace = _buf(dtau_partial, "dtau_partial"), _buf(workspace, "workspace")
     if out is None:
         out = fused_code_buffer(g, lay_out, thin.device)[0]
-    gs = g.c_struct()
     flags = PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out)
     r2 = _opt(r2, "r2")
     dA = None if r2 is None else torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_fused2d_stage_bwd(ctypes.byref(gs), _ptr(thin), _ptr(base), _ptr(gate), _ptr(frags), _ptr(out),
-                                          _ptr(patches), _ptr(dtau_partial), int(bool(do_synth)), _ptr(r2),
-                                          float(alpha), _ptr(dA), _ptr(workspace), flags, _stream())
-    _lib.check(rc, "cdl_fused2d_stage_bwd")
+    _call("cdl_fused2d_stage_bwd", g, thin, base, gate, frags, out, patches, dtau_partial, bool(do_synth), r2, alpha, dA,
+          workspace, flags)
     return out if dA is None else (out, dA)
+
+
+def _dtau_reduce(symbol, g, dtau_partial, c, dt_k, dtau_n):
+    dt0, dt1 = _dt_halves(g, dt_k)
+    _call(symbol, g, _buf(dtau_partial, "dtau_partial"), _opt(c, "c"), dt0, dt1, _dtau_rows(g, dtau_n))
 
 
 def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
     """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`]."""
-    assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
-    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
-    gs = g.c_struct()
-    base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fused2d_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                            ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
-                                            _stream())
-    _lib.check(rc, "cdl_fused2d_dtau_reduce")
+    _dtau_reduce("cdl_fused2d_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
 
 
 def fused_wgrad_workspace(g: Geometry, device):
-    gs = g.c_struct()
-    n = _lib.lib().cdl_fused2d_wgrad_workspace_floats(ctypes.byref(gs))
-    return torch.empty(n, device=device, dtype=torch.float32)
+    return torch.empty(_size("cdl_fused2d_wgrad_workspace_floats", g), device=device, dtype=torch.float32)
 
 
 def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T1=None, alpha1=1.0,
@@ -1024,29 +1041,49 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
             args += [None, None, 0.0, None]
         else:
             X, T = (_dev(X, "X") if layout == "nchw" else X), _dev(T, "T")
-            dw = torch.empty(g.filter_shape(), device=X.device, dtype=torch.float32)
-            outs.append(dw)
-            args += [_ptr(X), _ptr(T), float(al), _ptr(dw)]
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_wgrad(ctypes.byref(gs), *args, _ptr(workspace),
-                                      PRECISION[precision] | _lay_in(layout) | (TILES_REVERSED if tiles_reversed else 0),
-                                      _stream())
-    _lib.check(rc, "cdl_fused2d_wgrad")
+            outs.append(torch.empty(g.filter_shape(), device=X.device, dtype=torch.float32))
+            args += [X, T, al, outs[-1]]
+    _call("cdl_fused2d_wgrad", g, *args, _buf(workspace, "workspace"),
+          PRECISION[precision] | _lay_in(layout) | (TILES_REVERSED if tiles_reversed else 0))
     return outs
 
 
 def _check_data_grads(g: Geometry, K, dyp, dtau, families=1):
     """The optional outputs of the *_backward sweeps: dyp (thin, as yp), dtau (K,N,M) -- (K,3,N,M) for the three threshold
     families of the CSR sweep; contiguous fp32."""
-    for t, shape in ((dyp, g.image_shape()), (dtau, (K, g.N, g.M) if families == 1 else (K, families, g.N, g.M))):
-        if t is not None:
-            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
-                (tuple(t.shape), shape)
+    _buf(dyp, "dyp", g.image_shape())
+    _buf(dtau, "dtau", (K, g.N, g.M) if families == 1 else (K, families, g.N, g.M))
+
+
+def _dt_sweep(g: Geometry, K, dt, name="dt"):
+    """The (K, 2, M) threshold gradient a reverse sweep fills (None stays None)."""
+    if _buf(dt, name) is not None and dt.numel() != K * 2 * g.M:
+        raise ValueError(f"{name}: expected {K} x 2 x {g.M} values, got {dt.numel()}")
+    return dt
+
+
+def _thin(g: Geometry, device, count):
+    """`count` image-shaped (thin) tensors in one allocation."""
+    return torch.empty((count,) + g.image_shape(), device=device, dtype=torch.float32)
 
 
 def _ptr_table(tensors):
     """Host array of device pointers (kept alive by the caller for the duration of the call)."""
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _sweep_tables(K, keep, alloc_z, alloc_r, z_K=None):
+    """The code and residual tables of a K-iteration forward or tangent sweep: (z, r), with z[k] the buffer iteration k
+    writes and r[k - 1] the residual it reads.  keep: every entry gets a buffer of its own (training); otherwise two
+    ping-pong buffers each, so consecutive entries never alias (the C side refuses zout == zin).  z_K: the last code's own
+    tensor where the sweep keeps it apart from the internal codes (the fused tiers: other layout).  alloc_z / alloc_r(count):
+    `count` code / thin buffers (one allocation, indexable); at least one is asked for even where none is used (K == 1)."""
+    inner = K if z_K is None else K - 1
+    nz = inner if keep else min(inner, 2)
+    nr = (K - 1) if keep else min(K - 1, 2)
+    zbuf, rbuf = alloc_z(max(nz, 1)), alloc_r(max(nr, 1))
+    z = [zbuf[k % nz] for k in range(inner)] + ([] if z_K is None else [z_K])
+    return z, [rbuf[k % nr] for k in range(K - 1)]
 
 
 def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False):
@@ -1062,25 +1099,15 @@ def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", 
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
     dev = yp.device
-    nz = (K - 1) if keep else min(K - 1, 2)              # inner codes z_1..z_{K-1}
-    nr = (K - 1) if keep else min(K - 1, 2)
     # one allocation per family (views into it): at cfg1's size the allocator calls cost more than the kernels
-    zK = torch.empty(g.code_shape(), device=dev, dtype=torch.float32)
-    zbuf = fused_code_buffer(g, layout, dev, max(nz, 1))
-    rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
-    z = [zbuf[k % nz] for k in range(K - 1)] + [zK]
-    r = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
+    z, r = _sweep_tables(K, keep, lambda n: fused_code_buffer(g, layout, dev, n), lambda n: _thin(g, dev, n),
+                         z_K=_new(g.code_shape(), dev))
     maps = list(torch.empty((K, g.N, 4, g.dims[1], g.dims[2]), device=dev, dtype=torch.int32).unbind(0)) \
         if (keep or keep_maps) else []
-    xp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
+    xp = _new(g.image_shape(), dev)
     frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    patches = fused_patches(g, dev)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fused2d_forward(ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(tau), _ptr_table(A),
-                                        _ptr_table(B), _ptr_table(z), _ptr_table(r) if r else None,
-                                        _ptr_table(maps) if maps else None, _ptr(xp), _ptr(frags), _ptr(patches),
-                                        PRECISION[precision] | _lay_in(layout), _stream())
-    _lib.check(rc, "cdl_fused2d_forward")
+    _call("cdl_fused2d_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, fused_patches(g, dev),
+          PRECISION[precision] | _lay_in(layout))
     return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), maps
 
 
@@ -1102,25 +1129,14 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
     if g_xp is None:
         g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
     g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
-    dAB = torch.empty((2 * K,) + g.filter_shape(), device=dev, dtype=torch.float32)     # one allocation, 2K views
-    dA, dB = list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
-    dub = fused_code_buffer(g, layout, dev, 2 if K > 1 else 1)
-    du0, du1 = dub[0], dub[1 if K > 1 else 0]
-    q = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
-    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    patches = fused_patches(g, dev)
-    dtp = torch.empty((fused_tiles(g), g.M), device=dev, dtype=torch.float32)
-    ws = fused_wgrad_workspace(g, dev)
-    assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
-    gs = g.c_struct()
+    dt = _dt_sweep(g, K, dt)
     _check_data_grads(g, K, dyp, dtau)
-    rc = _lib.lib().cdl_fused2d_backward(
-        ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
-        _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
-        _ptr_table(dB), _ptr(dt),
-        _ptr(du0), _ptr(du1), _ptr(q), _ptr(frags), _ptr(patches), _ptr(dtp), _ptr(ws),
-        PRECISION[precision] | _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
-    _lib.check(rc, "cdl_fused2d_backward")
+    dA, dB = _filter_grads(g, K, dev)
+    dub = fused_code_buffer(g, layout, dev, 2 if K > 1 else 1)
+    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
+    _call("cdl_fused2d_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt,
+          dub[0], dub[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, fused_patches(g, dev),
+          _new((fused_tiles(g), g.M), dev), fused_wgrad_workspace(g, dev), PRECISION[precision] | _lay_in(layout), dyp, dtau)
     return dA, dB
 
 
@@ -1130,15 +1146,12 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
 # (the shipped CDLNet-s2030 architecture); same call structure as the 2-D flagship path above, codes in the
 # reference's (N,M,[D,]H,W) layout.
 def fusedg_supported(g: Geometry) -> bool:
-    gs = g.c_struct()
-    return bool(_lib.lib().cdl_fusedg_supported(ctypes.byref(gs)))
+    return bool(_size("cdl_fusedg_supported", g))
 
 
 def _fusedg_sizes(g: Geometry):
-    gs = g.c_struct()
-    L = _lib.lib()
-    return (int(L.cdl_fusedg_frag_bytes(ctypes.byref(gs))), int(L.cdl_fusedg_patch_floats(ctypes.byref(gs))),
-            int(L.cdl_fusedg_tiles(ctypes.byref(gs))), int(L.cdl_fusedg_map_words(ctypes.byref(gs))))
+    """(fragment bytes, patch floats, tiles, map words)."""
+    return tuple(_size("cdl_fusedg_" + q, g) for q in ("frag_bytes", "patch_floats", "tiles", "map_words"))
 
 
 def _fusedg_map_shape(g: Geometry):
@@ -1159,8 +1172,7 @@ def fusedg_map(g: Geometry, device):
 def fusedg_prep(g: Geometry, wA, wB):
     wA, wB = _dev(wA, "wA"), _dev(wB, "wB")
     frags = torch.empty(_fusedg_sizes(g)[0], device=wA.device, dtype=torch.uint8)
-    gs = g.c_struct()
-    _lib.check(_lib.lib().cdl_fusedg_prep(ctypes.byref(gs), _ptr(wA), _ptr(wB), _ptr(frags), _stream()), "cdl_fusedg_prep")
+    _call("cdl_fusedg_prep", g, wA, wB, frags)
     return frags
 
 
@@ -1204,25 +1216,16 @@ def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out
     if out is None:
         out = (torch.empty(g.code_shape(), device=r.device, dtype=torch.float32) if lay_out == "nchw"
                else fusedg_rsc_buffer(g, r.device)[0])
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fusedg_iter_fwd(ctypes.byref(gs), _ptr(r), _ptr(zin), _ptr(tau), _ptr(frags), float(sgn),
-                                        _ptr(out), _ptr(patches), _ptr(map_out), _lay_in(lay_in) | _lay_out(lay_out),
-                                        _stream())
-    _lib.check(rc, "cdl_fusedg_iter_fwd")
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    _call("cdl_fusedg_iter_fwd", g, r, zin, tau, frags, sgn, _buf(out, "out"), patches,
+          _buf(map_out, "map_out", dtype=torch.int32), _lay_in(lay_in) | _lay_out(lay_out))
     return out
 
 
 def fusedg_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None, acc=None, acc_add=False,
                     write_out=True):
     """As fused_assemble (the optional unmasked sum into `acc` included)."""
-    mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
-    assert acc is None or (acc.is_contiguous() and tuple(acc.shape) == g.image_shape())
-    if write_out and out is None:
-        out = torch.empty(g.image_shape(), device=patches.device, dtype=torch.float32)
-    rc = _lib.lib().cdl_fusedg_assemble(ctypes.byref(g.c_struct()), _ptr(patches), _ptr(mask), _ptr(sub), float(alpha),
-                                        _ptr(out if write_out else None), _ptr(acc), int(bool(acc_add)), _stream())
-    _lib.check(rc, "cdl_fusedg_assemble")
-    return out if write_out else None
+    return _assemble("cdl_fusedg_assemble", g, patches, mask, sub, alpha, out, acc, acc_add, write_out)
 
 
 def fusedg_support_map(g: Geometry, z):
@@ -1252,35 +1255,26 @@ def fusedg_support_map(g: Geometry, z):
 def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_partial, do_synth, out=None,
                      lay_in="nchw", lay_out="nchw"):
     thin, base = _dev(thin, "thin"), _opt(base, "base")
-    assert gate_map.dtype == torch.int32 and gate_map.is_contiguous()
+    gate_map = _buf(gate_map, "gate_map", dtype=torch.int32)
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
     if out is None:
         out = (torch.empty(g.code_shape(), device=thin.device, dtype=torch.float32) if lay_out == "nchw"
                else fusedg_rsc_buffer(g, thin.device)[0])
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fusedg_stage_bwd(ctypes.byref(gs), _ptr(thin), _ptr(base), _ptr(gate_map), _ptr(frags),
-                                         _ptr(out), _ptr(patches), _ptr(dtau_partial), int(bool(do_synth)),
-                                         _lay_in(lay_in) | _lay_out(lay_out), _stream())
-    _lib.check(rc, "cdl_fusedg_stage_bwd")
+    _call("cdl_fusedg_stage_bwd", g, thin, base, gate_map, frags, _buf(out, "out"), patches,
+          _buf(dtau_partial, "dtau_partial"), bool(do_synth), _lay_in(lay_in) | _lay_out(lay_out))
     return out
 
 
 def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
-    assert dt_k.is_contiguous() and dt_k.numel() == 2 * g.M
-    assert dtau_n is None or (dtau_n.is_contiguous() and dtau_n.numel() == g.N * g.M)
-    gs = g.c_struct()
-    base = dt_k.data_ptr()
-    rc = _lib.lib().cdl_fusedg_dtau_reduce(ctypes.byref(gs), _ptr(dtau_partial), _ptr(_opt(c, "c")),
-                                           ctypes.c_void_p(base), ctypes.c_void_p(base + 4 * g.M), _ptr(dtau_n),
-                                           _stream())
-    _lib.check(rc, "cdl_fusedg_dtau_reduce")
+    _dtau_reduce("cdl_fusedg_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
 
 
 def fusedg_code_layout(g: Geometry, training=True) -> str:
     """Layout the fused generic sweeps keep their internal codes in: "rsc" for the strip kernels' shapes (with
     `training`: when the matrix-core filter-gradient kernel takes the geometry, since its VALU fallbacks read the
     reference layout only), else "nchw" (cdl_fusedg_code_layout)."""
-    gs = g.c_struct()
-    return "rsc" if int(_lib.lib().cdl_fusedg_code_layout(ctypes.byref(gs), int(bool(training)))) == LAYOUT["rsc"] else "nchw"
+    code = _lib.lib().cdl_fusedg_code_layout(ctypes.byref(g.c_struct()), int(bool(training)))
+    return "rsc" if int(code) == LAYOUT["rsc"] else "nchw"
 
 
 def _fusedg_code_buffers(g: Geometry, layout, device, count):
@@ -1299,24 +1293,13 @@ def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep
     B = [_dev(w, "B") for w in B]
     dev = yp.device
     fb, pf, tiles, mw = _fusedg_sizes(g)
-    nz = (K - 1) if keep else min(K - 1, 2)                 # internal codes z_1..z_{K-1}; z_K has its own tensor
-    nr = (K - 1) if keep else min(K - 1, 2)
-    zint = _fusedg_code_buffers(g, layout, dev, nz)
-    zK = torch.empty(g.code_shape(), device=dev, dtype=torch.float32)
-    rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
-    z = [zint[k % nz] for k in range(K - 1)] + [zK]
-    r = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
+    zK = _new(g.code_shape(), dev)                          # the internal codes z_1..z_{K-1} are in `layout`
+    z, r = _sweep_tables(K, keep, lambda n: _fusedg_code_buffers(g, layout, dev, n), lambda n: _thin(g, dev, n), z_K=zK)
     maps = list(torch.empty((K,) + _fusedg_map_shape(g), device=dev, dtype=torch.int32).unbind(0)) \
         if (keep or keep_maps) else []                      # keep_maps: see fused_forward
-    xp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
+    xp = _new(g.image_shape(), dev)
     frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    patches = torch.empty(pf, device=dev, dtype=torch.float32)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_fusedg_forward(ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(tau), _ptr_table(A),
-                                       _ptr_table(B), _ptr_table(z), _ptr_table(r) if r else None,
-                                       _ptr_table(maps) if maps else None, _ptr(xp), _ptr(frags), _ptr(patches),
-                                       _lay_in(layout), _stream())
-    _lib.check(rc, "cdl_fusedg_forward")
+    _call("cdl_fusedg_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, _new((pf,), dev), _lay_in(layout))
     return xp, zK, (z if keep else [zK]), (r if keep else []), maps
 
 
@@ -1337,24 +1320,15 @@ def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, d
         g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
     g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
     fb, pf, tiles, mw = _fusedg_sizes(g)
-    dAB = torch.empty((2 * K,) + g.filter_shape(), device=dev, dtype=torch.float32)
-    dA, dB = list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
-    du = _fusedg_code_buffers(g, layout, dev, 2 if K > 1 else 1)
-    q = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
-    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    patches = torch.empty(pf, device=dev, dtype=torch.float32)
-    dtp = torch.empty((tiles, g.M), device=dev, dtype=torch.float32)
-    gs = g.c_struct()
-    nws = int(_lib.lib().cdl_wgrad_workspace_floats(ctypes.byref(gs)))
-    ws = torch.empty(max(nws, 1), device=dev, dtype=torch.float32)
-    assert dt.is_contiguous() and dt.numel() == K * 2 * g.M
+    dt = _dt_sweep(g, K, dt)
     _check_data_grads(g, K, dyp, dtau)
-    rc = _lib.lib().cdl_fusedg_backward(
-        ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(c), _ptr_table(A), _ptr_table(B), _ptr_table(codes),
-        _ptr_table(resid) if resid else None, _ptr_table(list(maps)), _ptr(g_xp), _ptr(g_z), _ptr_table(dA),
-        _ptr_table(dB), _ptr(dt), _ptr(du[0]), _ptr(du[1 if K > 1 else 0]), _ptr(q), _ptr(frags), _ptr(patches),
-        _ptr(dtp), _ptr(ws), nws, _lay_in(layout), _ptr(dyp), _ptr(dtau), _stream())
-    _lib.check(rc, "cdl_fusedg_backward")
+    dA, dB = _filter_grads(g, K, dev)
+    du = _fusedg_code_buffers(g, layout, dev, 2 if K > 1 else 1)
+    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
+    nws = _size("cdl_wgrad_workspace_floats", g)
+    _call("cdl_fusedg_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt, du[0],
+          du[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, _new((pf,), dev), _new((tiles, g.M), dev),
+          _new((max(nws, 1),), dev), nws, _lay_in(layout), dyp, dtau)
     return dA, dB
 
 
@@ -1365,9 +1339,13 @@ def _new(shape, device):
 
 
 def ista_scratch(g: Geometry, device):
-    gs = g.c_struct()
-    n = int(_lib.lib().cdl_ista_scratch_floats(ctypes.byref(gs)))
+    n = _size("cdl_ista_scratch_floats", g)
     return _scratch(device, max(n, 1)), n
+
+
+def _generic_tables(g: Geometry, K, keep, device):
+    """_sweep_tables of the generic tier: all K codes in the reference's layout, one allocation per family."""
+    return _sweep_tables(K, keep, lambda n: _new((n,) + g.code_shape(), device), lambda n: _thin(g, device, n))
 
 
 def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=None, gam1=None, gam2=None, *,
@@ -1377,31 +1355,18 @@ def ista_forward(g: Geometry, yp, mask_p, tau, A, B, keep, z_prev=None, z_after=
     cmap (N,1,*code_spatial) with tslope (K,M) = t[:,1]: noise-level map, see analysis; with z_prev tslope is (K,3,M),
     the slopes of lam, gam1, gam2, and tau / gam1 / gam2 hold the constant parts (analysis_prox)."""
     K = len(A)
-    cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
-    if (cmap is None) != (tslope is None):
-        raise ValueError("cmap and tslope go together")
-    _check_map(g, cmap, tslope, K if z_prev is None else 3 * K)
+    cmap, tslope = _check_map_pair(g, cmap, tslope, K if z_prev is None else 3 * K)
     yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
     z_prev, z_after = _opt(z_prev, "z_prev"), _opt(z_after, "z_after")
     gam1, gam2 = _opt(gam1, "gam1"), _opt(gam2, "gam2")
     dev = yp.device
-    nz = K if keep else min(K, 2)
-    nr = (K - 1) if keep else min(K - 1, 2)
-    zbuf = _new((nz,) + g.code_shape(), dev)
-    rbuf = _new((max(nr, 1),) + g.image_shape(), dev)
-    z = [zbuf[k % nz] for k in range(K)]
-    r = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
+    z, r = _generic_tables(g, K, keep, dev)
     u = list(_new((K,) + g.code_shape(), dev).unbind(0)) if (keep and z_prev is not None) else []
     xp = _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
-    gs = g.c_struct()
-    rc = _lib.lib().cdl_ista_forward(ctypes.byref(gs), K, _ptr(yp), _ptr(mask_p), _ptr(tau), _ptr(z_prev),
-                                     _ptr(z_after), _ptr(gam1), _ptr(gam2), _ptr_table(A), _ptr_table(B),
-                                     _ptr_table(z), _ptr_table(r) if r else None, _ptr_table(u) if u else None,
-                                     _ptr(xp), _ptr(ws), n, _ptr(cmap), _ptr(tslope), _stream())
-    _lib.check(rc, "cdl_ista_forward")
+    _call("cdl_ista_forward", g, K, yp, mask_p, tau, z_prev, z_after, gam1, gam2, A, B, z, r, u, xp, ws, n, cmap, tslope)
     return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), u
 
 
@@ -1413,40 +1378,31 @@ def ista_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt,
     cmap / tslope as ista_forward's (c is then None); dcmap (N,1,*code_spatial; nullable) receives dL/dcmap where dtau
     would be returned."""
     K = len(A)
+    dt, dg1, dg2 = _dt_sweep(g, K, dt), _dt_sweep(g, K, dg1, "dg1"), _dt_sweep(g, K, dg2, "dg2")
+    gz_prev, gz_after = _buf(gz_prev, "gz_prev", g.code_shape()), _buf(gz_after, "gz_after", g.code_shape())
+    _check_data_grads(g, K, dyp, dtau, 1 if z_prev is None else 3)
     cmap, tslope = _opt(cmap, "cmap"), _opt(tslope, "tslope")
     _check_map(g, cmap, tslope, K if z_prev is None else 3 * K)
-    if dcmap is not None:
-        assert cmap is not None and tslope is not None and dcmap.is_contiguous()
+    if _buf(dcmap, "dcmap") is not None:
+        if cmap is None or tslope is None:
+            raise ValueError("dcmap: there is no cmap / tslope to take the gradient of")
         _check_map(g, dcmap)
     dev = yp.device
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
-    dAB = _new((2 * K,) + g.filter_shape(), dev)
-    dA, dB = list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
+    dA, dB = _filter_grads(g, K, dev)
     g0, g1, q = _new(g.code_shape(), dev), _new(g.code_shape(), dev), _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
-    gs = g.c_struct()
-    _check_data_grads(g, K, dyp, dtau, 1 if z_prev is None else 3)
-    rc = _lib.lib().cdl_ista_backward(
-        ctypes.byref(gs), K, _ptr(_dev(yp, "yp")), _ptr(_opt(mask_p, "mask")), _ptr(_opt(c, "c")),
-        _ptr(_opt(z_prev, "z_prev")), _ptr(_opt(z_after, "z_after")), _ptr(_opt(lam, "lam")),
-        _ptr(_opt(gam1, "gam1")), _ptr(_opt(gam2, "gam2")), _ptr_table(A), _ptr_table(B),
-        _ptr_table([_dev(t, "z") for t in codes]), _ptr_table([_dev(t, "r") for t in resid]) if resid else None,
-        _ptr_table([_dev(t, "u") for t in us]) if us else None, _ptr(_opt(g_xp, "g_xp")), _ptr(_opt(g_z, "g_z")),
-        _ptr_table(dA), _ptr_table(dB), _ptr(dt), _ptr(dg1), _ptr(dg2), _ptr(gz_prev), _ptr(gz_after),
-        _ptr(g0), _ptr(g1), _ptr(q), _ptr(ws), n, _ptr(dyp), _ptr(dtau), _ptr(cmap), _ptr(tslope), _ptr(dcmap), _stream())
-    _lib.check(rc, "cdl_ista_backward")
+    _call("cdl_ista_backward", g, K, _dev(yp, "yp"), _opt(mask_p, "mask"), _opt(c, "c"), _opt(z_prev, "z_prev"),
+          _opt(z_after, "z_after"), _opt(lam, "lam"), _opt(gam1, "gam1"), _opt(gam2, "gam2"), A, B,
+          [_dev(t, "z") for t in codes], [_dev(t, "r") for t in resid], [_dev(t, "u") for t in us or ()],
+          _opt(g_xp, "g_xp"), _opt(g_z, "g_z"), dA, dB, dt, dg1, dg2, gz_prev, gz_after, g0, g1, q, ws, n, dyp, dtau,
+          cmap, tslope, dcmap)
     return dA, dB
 
 
 # ------------------------------------------------------------------------------------------
 # forward-mode tangent sweeps at the primal's supports (DESIGN.md section 21)
-def _tangent_tables(K, keep, zbufs, rbufs):
-    nz = K if keep else min(K, 2)
-    nr = (K - 1) if keep else min(K - 1, 2)
-    return [zbufs[k % nz] for k in range(K)], ([rbufs[k % nr] for k in range(K - 1)] if K > 1 else [])
-
-
 def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep, last=False):
     """Generic tangent sweep in one C call (cdl_tangent_forward): gates = the primal's z_1..z_K (N,M,..); vp the
     pre-processed direction.  Returns (xdp, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else [] (with
@@ -1458,16 +1414,10 @@ def tangent_forward(g: Geometry, vp, mask_p, A, B, gates, keep, last=False):
     gates = [_dev(t, "gate") for t in gates]
     assert len(gates) == K and all(tuple(t.shape) == g.code_shape() for t in gates)
     dev = vp.device
-    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
-    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
-    zd, rd = _tangent_tables(K, keep, zbuf, rbuf)
+    zd, rd = _generic_tables(g, K, keep, dev)
     xdp = _new(g.image_shape(), dev)
-    dts = _new((2 * g.M,), dev)
     ws, n = ista_scratch(g, dev)
-    rc = _lib.lib().cdl_tangent_forward(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(mask_p), _ptr_table(A),
-                                        _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
-                                        _ptr_table(rd) if rd else None, _ptr(xdp), _ptr(dts), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_tangent_forward")
+    _call("cdl_tangent_forward", g, K, vp, mask_p, A, B, gates, zd, rd, xdp, _new((2 * g.M,), dev), ws, n)
     return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (rd if keep else [])
 
 
@@ -1482,17 +1432,11 @@ def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp, g_zd=No
     zd = [_dev(t, "zd") for t in zd]
     rd = [_dev(t, "rd") for t in rd]
     assert len(gates) == K == len(zd) and len(rd) == K - 1
-    dAB = _new((2 * K,) + g.filter_shape(), dev)
-    dA, dB = list(dAB[:K].unbind(0)), list(dAB[K:].unbind(0))
+    dA, dB = _filter_grads(g, K, dev)
     g0, g1, q = _new(g.code_shape(), dev), _new(g.code_shape(), dev), _new(g.image_shape(), dev)
-    dts = _new((2 * g.M,), dev)
     ws, n = ista_scratch(g, dev)
-    rc = _lib.lib().cdl_tangent_backward(ctypes.byref(g.c_struct()), K, _ptr(_dev(vp, "vp")), _ptr(_opt(mask_p, "mask")),
-                                         _ptr_table(A), _ptr_table(B), _ptr_table(gates), _ptr_table(zd),
-                                         _ptr_table(rd) if rd else None, _ptr(_dev(g_xp, "g_xp")),
-                                         _ptr(_opt(g_zd, "g_zd")), _ptr_table(dA), _ptr_table(dB), _ptr(g0), _ptr(g1),
-                                         _ptr(q), _ptr(dts), _ptr(ws), n, _stream())
-    _lib.check(rc, "cdl_tangent_backward")
+    _call("cdl_tangent_backward", g, K, _dev(vp, "vp"), _opt(mask_p, "mask"), A, B, gates, zd, rd, _dev(g_xp, "g_xp"),
+          _opt(g_zd, "g_zd"), dA, dB, g0, g1, q, _new((2 * g.M,), dev), ws, n)
     return dA, dB
 
 
@@ -1510,17 +1454,11 @@ def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_afte
     assert len(us) == K
     _check_codes(g, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after, **{f"u[{k}]": t for k, t in enumerate(us)})
     dev = vp.device
-    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
-    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
-    zd, rd = _tangent_tables(K, keep, zbuf, rbuf)
+    zd, rd = _generic_tables(g, K, keep, dev)
     xdp = _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
-    rc = _lib.lib().cdl_csr_tangent_forward(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(mask_p), _ptr(z_prev), _ptr(z_after),
-                                            _ptr(_dev(lam, "lam")), _ptr(_dev(gam1, "gam1")), _ptr(_opt(gam2, "gam2")),
-                                            _ptr(zd_prev), _ptr(zd_after), _ptr_table(A), _ptr_table(B), _ptr_table(us),
-                                            _ptr_table(zd), _ptr_table(rd) if rd else None, _ptr(xdp), _ptr(ws), n,
-                                            _stream())
-    _lib.check(rc, "cdl_csr_tangent_forward")
+    _call("cdl_csr_tangent_forward", g, K, vp, mask_p, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
+          _opt(gam2, "gam2"), zd_prev, zd_after, A, B, us, zd, rd, xdp, ws, n)
     return xdp, zd[K - 1], (zd if keep else []), (rd if keep else [])
 
 
@@ -1535,22 +1473,12 @@ def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3",
     assert len(maps) == K
     dev = vp.device
     nvp = torch.neg(vp)                                      # thin: the assemble subtracts it
-    nz = (K - 1) if keep else min(K - 1, 2)
-    nr = nz
-    zK = torch.empty(g.code_shape(), device=dev, dtype=torch.float32)
-    zbuf = fused_code_buffer(g, layout, dev, max(nz, 1))
-    rbuf = torch.empty((max(nr, 1),) + g.image_shape(), device=dev, dtype=torch.float32)
-    zd = [zbuf[k % nz] for k in range(K - 1)] + [zK]
-    nrd = [rbuf[k % nr] for k in range(K - 1)] if K > 1 else []
-    xdp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32)
+    zd, nrd = _sweep_tables(K, keep, lambda n: fused_code_buffer(g, layout, dev, n), lambda n: _thin(g, dev, n),
+                            z_K=_new(g.code_shape(), dev))
+    xdp = _new(g.image_shape(), dev)
     frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    patches = fused_patches(g, dev)
-    dtp = torch.empty((fused_tiles(g), g.M), device=dev, dtype=torch.float32)
-    rc = _lib.lib().cdl_fused2d_tangent(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(nvp), _ptr(mask_p), _ptr_table(A),
-                                        _ptr_table(B), _ptr_table(list(maps)), _ptr_table(zd),
-                                        _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
-                                        PRECISION[precision] | _lay_in(layout), _stream())
-    _lib.check(rc, "cdl_fused2d_tangent")
+    _call("cdl_fused2d_tangent", g, K, vp, nvp, mask_p, A, B, list(maps), zd, nrd, xdp, frags, fused_patches(g, dev),
+          _new((fused_tiles(g), g.M), dev), PRECISION[precision] | _lay_in(layout))
     return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
@@ -1564,18 +1492,11 @@ def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, last=False):
     dev = vp.device
     nvp = torch.neg(vp)
     fb, pf, tiles, mw = _fusedg_sizes(g)
-    zbuf = _new((K if keep else min(K, 2),) + g.code_shape(), dev)
-    rbuf = _new((max((K - 1) if keep else min(K - 1, 2), 1),) + g.image_shape(), dev)
-    zd, nrd = _tangent_tables(K, keep, zbuf, rbuf)
+    zd, nrd = _generic_tables(g, K, keep, dev)
     xdp = _new(g.image_shape(), dev)
     frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    patches = _new((pf,), dev)
-    dtp = _new((tiles, g.M), dev)
-    rc = _lib.lib().cdl_fusedg_tangent(ctypes.byref(g.c_struct()), K, _ptr(vp), _ptr(nvp), _ptr(mask_p), _ptr_table(A),
-                                       _ptr_table(B), _ptr_table(list(maps)), _ptr_table(zd),
-                                       _ptr_table(nrd) if nrd else None, _ptr(xdp), _ptr(frags), _ptr(patches), _ptr(dtp),
-                                       0, _stream())
-    _lib.check(rc, "cdl_fusedg_tangent")
+    _call("cdl_fusedg_tangent", g, K, vp, nvp, mask_p, A, B, list(maps), zd, nrd, xdp, frags, _new((pf,), dev),
+          _new((tiles, g.M), dev), 0)
     return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
