@@ -5,7 +5,10 @@ and the local forms of the MAD estimate that produce a noise-level map: `nle_mad
 `nle_mad` runs in libcdlnet_hip.so (cdl_nle_mad): depthwise stride-2 correlation with the 'bior4.4'
 diagonal (HH) analysis filter and an exact per-sample median.  `nle_pca` (weak-texture PCA) forms, per pass and
 channel, the second moment of the weak-texture patches in one HIP sweep (cdl_nle_pca_gram); the host keeps only the
-p^2 x p^2 eigenvalue problem and the constants of the patch size.
+p^2 x p^2 eigenvalue problem and the constants of the patch size.  `nle_pca_cells`, `nle_pca_map` and `nle_pca_frames`
+are that estimate per region and per frame: every cell of a regular grid its own domain, all
+Grams of a pass from one launch chain (cdl_nle_pca_gram_cells); `noise_level_map` dispatches between the two map
+estimators.
 """
 import functools
 import math
@@ -267,6 +270,183 @@ def nle_pca(img, patchsize=7, conf=1 - 1e-6, itr=3):
     if C == 1:
         return nlevel[0], th[0], num[0]
     return nlevel, th, num
+
+
+# ------------------------------------------------------------- weak-texture PCA per region
+def _pca_grid(y, window, step, patchsize, name):
+    """Checked (images (B,C,H,W), leading shape, window, step, p) of a cells call; every refusal is made here, before
+    any device work.  window None: the whole frame is one cell."""
+    if not torch.is_tensor(y):
+        raise TypeError(f"{name}: expected a tensor")
+    if y.dim() not in (4, 5):
+        raise ValueError(f"{name} expects (N, C, H, W) or (N, C, D, H, W)")
+    p = int(patchsize)
+    if p != patchsize or not 3 <= p <= 11:
+        raise ValueError(f"{name}: patchsize {patchsize!r} outside 3..11")
+    H, W = y.shape[-2:]
+    if H < p or W < p:
+        raise ValueError(f"{name}: image {H} x {W} smaller than the {p} x {p} patch")
+    if window is None:
+        window = step = max(H, W)
+    if int(window) != window or window < p:
+        raise ValueError(f"{name}: window {window!r}: expected an integer >= patchsize {p} (pixels)")
+    step = int(window) // 2 if step is None else step
+    if int(step) != step or step < 1:
+        raise ValueError(f"{name}: step {step!r}: expected an integer >= 1 (pixels)")
+    y = ops._dev(y, "y")
+    if y.dim() == 4:
+        lead = tuple(y.shape[:2])
+    else:
+        lead = (y.shape[0], y.shape[1], y.shape[2])
+        y = y.transpose(1, 2).reshape((-1, y.shape[1]) + tuple(y.shape[3:]))      # frames are samples: never mixed
+    return y.contiguous(), lead, int(window), int(step), p
+
+
+def pca_gram_cells(y, channel, patchsize, window, step, tau):
+    """One pass over every cell on the device (cdl_nle_pca_gram_cells): (G (B, ny, nx, p^2, p^2) float64, count
+    (B, ny, nx) int64) for images y (B,C,H,W), cells of `window` pixels `step` apart by the rule of cell_starts; a
+    cell's G sums x x^T over the patches wholly inside it whose texture strength is below the cell's own
+    tau (B, ny, nx) (float32, on the device; +inf keeps every patch).  No copy to the host."""
+    B, C, H, W = y.shape
+    ny, nx = len(cell_starts(H, window, step)), len(cell_starts(W, window, step))
+    n = int(_lib.lib().cdl_nle_pca_gram_cells_scratch_floats(B, C, H, W, patchsize, window, step))
+    if n == 0:
+        raise ValueError(f"nle_pca_cells: patchsize {patchsize}, window {window}, step {step} refused for {H} x {W}")
+    if tuple(tau.shape) != (B, ny, nx) or tau.dtype != torch.float32:
+        raise ValueError(f"tau: expected float32 {(B, ny, nx)}")
+    scratch = ops._scratch(y.device, n)
+    P2 = patchsize * patchsize
+    gram = torch.empty((B, ny, nx, P2, P2), device=y.device, dtype=torch.float64)
+    count = torch.empty((B, ny, nx), device=y.device, dtype=torch.int64)
+    ops._call("cdl_nle_pca_gram_cells", y, B, C, H, W, channel, patchsize, window, step, tau, gram, count, scratch, n)
+    return gram, count
+
+
+def _smallest_eigenvalues(cov):
+    """Smallest eigenvalue of every matrix of cov (..., n, n) float64, by the device's batched symmetric solver: no
+    Gram leaves the device.  (torch reads the solver's status back, one host synchronisation per pass; DESIGN.md
+    section 25.)"""
+    return torch.linalg.eigvalsh(cov)[..., 0]
+
+
+def _pca_cells(imgs, window, step, p, conf, itr):
+    """(sig2, th, num) float64 (B, C, ny, nx) on the device: the steps of nle_pca for every cell at once."""
+    B, C, H, W = imgs.shape
+    ny, nx = len(cell_starts(H, window, step)), len(cell_starts(W, window, step))
+    total = (min(window, H) - p + 1) * (min(window, W) - p + 1)          # patches of a cell: the same for all
+    tau0 = pca_constants(p, conf)[0]
+    f64 = dict(device=imgs.device, dtype=torch.float64)
+    if total < p * p:                   # sig2 = 0: the first refinement's tau = 0 keeps nothing and stops the cell
+        zero = torch.zeros((B, C, ny, nx), **f64)
+        if itr > 2:
+            return zero, zero.clone(), zero.clone()
+        return zero, torch.full_like(zero, math.inf), torch.full_like(zero, float(total))
+    P2 = p * p
+    out = []
+    for c in range(C):
+        tau = torch.full((B, ny, nx), math.inf, **f64)
+        gram, kept = pca_gram_cells(imgs, c, p, window, step, tau.float())
+        sig2 = _smallest_eigenvalues(gram / (kept - 1)[..., None, None])
+        alive = torch.ones_like(kept, dtype=torch.bool)
+        for _ in range(2, itr):
+            tau = torch.where(alive, sig2 * tau0, tau)
+            gram, cnt = pca_gram_cells(imgs, c, p, window, step, tau.float())
+            kept = torch.where(alive, cnt, kept)
+            alive = alive & (cnt >= P2)                  # a cell that keeps fewer than p^2 patches stops here
+            eig = _smallest_eigenvalues(gram / (cnt - 1).clamp(min=1)[..., None, None])
+            sig2 = torch.where(alive, eig, sig2)
+        out.append((sig2, tau, kept.double()))
+    return tuple(torch.stack([o[i] for o in out], dim=1) for i in range(3))
+
+
+def nle_pca_cells(y, window=64, step=None, patchsize=7, conf=1 - 1e-6, itr=3):
+    """The weak-texture PCA estimate of nle_pca over windows of the image: (nlevel, th, num), float64 device tensors,
+    one value per channel and cell -- (N, C, ny, nx) for y (N,C,H,W), (N, C, D, ny, nx) for a clip (N,C,D,H,W), every
+    frame on its own.  Cells are `window` x `window` pixels, `step` apart (default window // 2), the last of an axis
+    flush with the border, an axis no longer than the window one cell (cell_starts, in pixels); window=None is the
+    whole frame as one cell per sample.
+
+    Every cell is its own domain and follows the steps of nle_pca on its crop: only the (window - p + 1)^2 patches
+    wholly inside it, samples never pooled; the first pass keeps every patch, then for _ in range(2, itr):
+    tau = sig2 * tau0, keep Xtr < tau; a cell whose kept count falls below p^2 stops there with its previous sig2 and
+    reports the tau and the count that stopped it; fewer than p^2 patches in a cell give (0, 0, 0).  The Gram
+    matrices of all cells form in one launch chain per pass and channel (cdl_nle_pca_gram_cells); the refinement is
+    vectorised over cells with device masks.  In y's scale."""
+    imgs, lead, window, step, p = _pca_grid(y, window, step, patchsize, "nle_pca_cells")
+    sig2, th, num = _pca_cells(imgs, window, step, p, conf, int(itr))
+    out = (sig2.sqrt(), th, num)
+    if len(lead) == 3:                                   # (N*D, C, ny, nx) -> (N, C, D, ny, nx)
+        out = tuple(t.reshape((lead[0], lead[2]) + tuple(t.shape[1:])).transpose(1, 2).contiguous() for t in out)
+    return out
+
+
+def _pca_levels(y, window, step, patchsize, conf, itr, name):
+    """(levels (B, ny, nx) float64: the root mean square over channels of the cells' estimates, images' shape info)."""
+    imgs, lead, window, step, p = _pca_grid(y, window, step, patchsize, name)
+    sig2 = _pca_cells(imgs, window, step, p, conf, int(itr))[0]
+    return sig2.mean(dim=1).clamp(min=0.0).sqrt(), imgs, lead, window, step     # a flat cell's eigenvalue may round below 0
+
+
+def nle_pca_frames(clip, patchsize=7, conf=1 - 1e-6, itr=3):
+    """One weak-texture PCA estimate per frame of a clip (N,C,D,H,W): (N,1,D,1,1) float32, the root mean square over
+    channels of the frame's whole-image levels; the per-frame form of `sigma` the nets take (times 255)."""
+    if not torch.is_tensor(clip) or clip.dim() != 5:
+        raise ValueError("nle_pca_frames expects (N, C, D, H, W)")
+    lev, _, lead, _, _ = _pca_levels(clip, None, None, patchsize, conf, itr, "nle_pca_frames")
+    return lev.float().reshape(lead[0], 1, lead[2], 1, 1)
+
+
+@functools.lru_cache(maxsize=64)
+def _pca_interp_plan(L, window, step, device):
+    """(lo, hi, t) on `device` for one axis of L pixels: pixel x takes (1 - t) * cell[lo] + t * cell[hi], piecewise
+    linear between the cell centres r0 + (w - 1) / 2, constant beyond the first and the last.  Device ops only."""
+    w = min(window, L)
+    n = len(cell_starts(L, window, step))
+    r0 = (torch.arange(n, device=device) * step).clamp(max=L - w)
+    centre = r0.double() + (w - 1) / 2
+    x = torch.arange(L, device=device, dtype=torch.float64)
+    hi = torch.bucketize(x, centre).clamp(max=n - 1)            # first centre >= x
+    lo = (hi - 1).clamp(min=0)
+    gap = centre[hi] - centre[lo]
+    t = torch.where(gap > 0, (x - centre[lo]) / gap.clamp(min=0.5), torch.zeros_like(x)).clamp(0.0, 1.0)
+    return lo, hi, t
+
+
+def _pca_interpolate(cells, H, W, window, step):
+    """cells (B, ny, nx) float64 -> (B, H, W) float64, separable."""
+    lo, hi, t = _pca_interp_plan(H, window, step, cells.device)
+    rows = torch.lerp(cells.index_select(1, lo), cells.index_select(1, hi), t[:, None])
+    lo, hi, t = _pca_interp_plan(W, window, step, cells.device)
+    return torch.lerp(rows.index_select(2, lo), rows.index_select(2, hi), t)
+
+
+def nle_pca_map(y, window=64, step=None, s=1, patchsize=7, conf=1 - 1e-6, itr=3):
+    """A blind noise-level map for `net(y, 255 * nle_pca_map(y, s=net.s))` from the weak-texture PCA estimate, which
+    texture inside a window does not inflate as it does the MAD estimate of nle_mad_map: the cell levels of
+    nle_pca_cells (root mean square over channels) interpolated to the image grid (separable, piecewise linear
+    between the cell centres r0 + (window - 1) / 2, constant beyond the outermost), then taken to the code grid of a
+    stride-`s` net by utils.sigma_to_code_grid.  float32; y (N,C,H,W) gives (N,1,ceil(H/s),ceil(W/s)), a clip
+    (N,C,D,H,W) a map per frame on the clip's code grid.  window=None is one level per image (N,1,1,1) or per frame,
+    nle_pca_frames(y) (N,1,D,1,1).  In y's scale."""
+    if window is None:
+        if torch.is_tensor(y) and y.dim() == 5:
+            return nle_pca_frames(y, patchsize, conf, itr)
+        lev, _, lead, _, _ = _pca_levels(y, None, None, patchsize, conf, itr, "nle_pca_map")
+        return lev.float().reshape(lead[0], 1, 1, 1)
+    lev, imgs, lead, window, step = _pca_levels(y, window, step, patchsize, conf, itr, "nle_pca_map")
+    H, W = imgs.shape[-2:]
+    img_map = _pca_interpolate(lev, H, W, window, step).float()
+    return utils.sigma_to_code_grid(img_map.reshape((lead[0], 1) + tuple(lead[2:]) + (H, W)), s)
+
+
+def noise_level_map(y, method="MAD", **kwargs):
+    """The one dispatcher of the two blind map estimators: nle_mad_map(y, **kwargs) for "MAD", nle_pca_map(y, **kwargs)
+    for "PCA".  (noise_level itself stays the MAD estimate of a whole image.)"""
+    if method == "MAD":
+        return nle_mad_map(y, **kwargs)
+    if method == "PCA":
+        return nle_pca_map(y, **kwargs)
+    raise NotImplementedError(f"noise_level_map method {method!r}: expected 'MAD' or 'PCA'")
 
 
 def noise_level(y, method="MAD", **kwargs):

@@ -348,6 +348,21 @@ int cdl_nle_pca_gram(const float *y, int N, int C, int H, int W, int channel, in
                      double *gram /*p^2 x p^2*/, long long *count /*1*/, float *scratch, size_t scratch_floats,
                      void *stream);
 
+/* The same pass over a regular grid of cells, every cell of every sample its own domain:
+ * along an axis of L pixels there is one cell [0, L) if L <= window, otherwise ceil((L - window) / step) + 1 cells of
+ * `window` pixels, cell i starting at min(i * step, L - window).  Cell (n, iy, ix) takes only the patches that lie
+ * wholly inside it ((window - p + 1)^2 origins for a full cell; samples never pool, overlapping cells each form
+ * their own Gram) whose Xtr < tau[n][iy][ix] (fp32, device; +inf keeps every patch), and gives
+ * gram[n][iy][ix] = sum x x^T (fp64, p^2 x p^2, both triangles) and count[n][iy][ix] (int64).  Same kernels and the
+ * same fixed reduction order per cell as cdl_nle_pca_gram, with shorter fp32 chains (8 patches) between the fp64
+ * additions, since a cell has few patches to average the rounding over: repeated calls are bit-identical.
+ * CDL_EINVAL before any launch: null pointers, patchsize outside 3..11, window < patchsize, step < 1, H or W <
+ * patchsize.  scratch: cdl_nle_pca_gram_cells_scratch_floats(N,C,H,W,patchsize,window,step) floats. */
+size_t cdl_nle_pca_gram_cells_scratch_floats(int N, int C, int H, int W, int patchsize, int window, int step);
+int cdl_nle_pca_gram_cells(const float *y, int N, int C, int H, int W, int channel, int patchsize, int window,
+                           int step, const float *tau /*N x ny x nx*/, double *gram /*N x ny x nx x p^2 x p^2*/,
+                           long long *count /*N x ny x nx*/, float *scratch, size_t scratch_floats, void *stream);
+
 /* ---- SSIM (the evaluation metric of analyzemri.py and the loss term of loss.py's CombinedLossWithSSIM) ----------
  * P independent contiguous H x W planes of x and y; the window is `taps` host-side 1-D weights `win` (odd, 3..15,
  * H, W >= taps) that sum to 1 (within 1e-5; otherwise CDL_EINVAL: the kernels centre each tile on one pixel, which is
