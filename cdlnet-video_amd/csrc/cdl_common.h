@@ -189,6 +189,14 @@ int cdl_current_device();
 int cdl_cu_count();                                              // compute units of the CURRENT device
 int cdl_ensure_dynamic_lds(const void *kernel, int bytes);       // per (device, kernel): keep the dynamic-LDS limit >= bytes
 
+// The alignment contract (include/cdlnet_hip.h): a caller's pointer needs only the alignment of its element type, so a
+// launcher selects a 16-byte form only after this test of EVERY pointer that form vector-accesses (NULL counts as aligned).
+static inline bool cdl_aligned16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr)
+{
+    return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c) |
+             reinterpret_cast<size_t>(d)) & 15) == 0;
+}
+
 static inline bool cdl_geom_ok(const cdl_geom *g)
 {
     if (!g) return false;

@@ -1651,8 +1651,10 @@ int iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *t
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
+    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     const Flags f = parse_flags(precision);
     if (!f.ok) return CDL_EINVAL;
+    if ((f.lin && !cdl_aligned16(zin)) || (f.lout && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;     // blocked codes: 16-byte accesses
     FusedParams p = stage_params<WY>(g, f, frags, patches);
     p.r = r; p.zin = zin; p.zout = zout; p.tau = tau; p.map = map_out;
     p.sgn = sgn; p.do_synth = 1;
@@ -1676,10 +1678,12 @@ int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const uns
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
+    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     if (do_synth && !patches) return CDL_EINVAL;
     if (r2 && (!dA || !workspace)) return CDL_EINVAL;
     const Flags f = parse_flags(precision);
     if (!f.ok) return CDL_EINVAL;
+    if ((f.lin && !cdl_aligned16(base)) || (f.lout && !cdl_aligned16(du_out))) return CDL_EUNSUPPORTED;  // blocked codes: 16-byte accesses
     FusedParams p = stage_params<WY>(g, f, frags, patches);
     p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
     p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0;
@@ -1701,6 +1705,7 @@ int wgrad_partials(const cdl_geom *g, const float *X0, const float *T0, float al
     if ((X0 && (!T0 || !dw0)) || (X1 && (!T1 || !dw1))) return CDL_EINVAL;
     const Flags f = parse_flags(precision);
     if (!f.ok) return CDL_EINVAL;
+    if (f.lin && !cdl_aligned16(X0, X1)) return CDL_EUNSUPPORTED;                                         // blocked codes: 16-byte accesses
     WgradParams p = {};
     p.rev = f.rev;
     p.X[0] = X0; p.T[0] = T0; p.X[1] = X1; p.T[1] = T1;
@@ -1734,7 +1739,8 @@ int assemble(const cdl_geom *g, const float *patches, const float *mask, const f
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!patches || (!out && !acc)) return CDL_EINVAL;
     const int tx = tiles_x(g), ty = tiles_y<WY>(g);
-    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
+    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) &&
+        !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
         k_assemble_v4<WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
         CDL_LAUNCH_CHECK();
@@ -1802,6 +1808,7 @@ struct TimingScope {
 int prep_pairs(const float *const *w1, const float *const *w2, int K, int shift2, void *frags, int M, int P,
                hipStream_t st)
 {
+    if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // the library-sized fragment buffer is written 16 bytes at a time (cdlnet_hip.h)
     const int MT = M / 32, threads = 8 * MT * 64;
     const int frag_uint4 = (int)(cdl_fused2d_frag_bytes(M) / 16);
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
@@ -1997,6 +2004,7 @@ size_t cdl_fused2d_tiles(const cdl_geom *g)
 int cdl_fused2d_prep(const float *wA, const float *wB, void *frags, int M, int P, void *stream)
 {
     if (!wA || !wB || !frags || (M != 32 && M != 64) || P < 1 || P > 7 || !(P & 1)) return CDL_EINVAL;
+    if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // a library-sized fragment buffer: 16-byte accesses (cdlnet_hip.h)
     const int MT = M / 32, threads = 8 * MT * 64;
     k_prep<<<(threads + 255) / 256, 256, 0, S(stream)>>>(wA, wB, reinterpret_cast<uint4 *>(frags), MT, P);
     CDL_LAUNCH_CHECK();

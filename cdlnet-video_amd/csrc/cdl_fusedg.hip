@@ -965,6 +965,7 @@ int dispatch(const cdl_geom *g, GParams &p, const Plan &pl, int mode, int precis
 int prep_pairs(const cdl_geom *g, const Plan &pl, const float *const *w1, const float *const *w2, int K, int shift2,
                void *frags, hipStream_t st)
 {
+    if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // the library-sized fragment buffer is written 16 bytes at a time (cdlnet_hip.h)
     const int threads = (int)(pl.frag_uint4 / 2);           // one thread per (fragment, lane); hi and lo together
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
         const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
@@ -1105,10 +1106,12 @@ int cdl_fusedg_iter_fwd(const cdl_geom *g, const float *r, const float *zin, con
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
     const Plan &pl = rt.pl;
     if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
+    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     if (rt.kind != 0) {
         int li, lo;
         if (!strip_layouts(precision, &li, &lo)) return CDL_EINVAL;
         if ((precision & 15) != 0) return CDL_EUNSUPPORTED;
+        if ((li && !cdl_aligned16(zin)) || (lo && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;       // rsc codes: 16-byte accesses
         if (rt.kind == 1)
             return cdl_strip_stage(g, rt.sp, zin ? 0 : 1, r, zin, tau, frags, sgn, zout, patches, map_out, nullptr, 1,
                                    (precision >> 4) & 1, li, lo, S(stream));
@@ -1130,11 +1133,13 @@ int cdl_fusedg_stage_bwd(const cdl_geom *g, const float *thin, const float *base
     if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
     const Plan &pl = rt.pl;
     if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
+    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     if (do_synth && !patches) return CDL_EINVAL;
     if (rt.kind != 0) {
         int li, lo;
         if (!strip_layouts(precision, &li, &lo)) return CDL_EINVAL;
         if ((precision & 15) != 0) return CDL_EUNSUPPORTED;
+        if ((li && !cdl_aligned16(base)) || (lo && !cdl_aligned16(du_out))) return CDL_EUNSUPPORTED;    // rsc codes: 16-byte accesses
         if (rt.kind == 1)
             return cdl_strip_stage(g, rt.sp, 2, thin, base, nullptr, frags, 1.0f, du_out, patches, const_cast<unsigned *>(map),
                                    dtau_partial, do_synth ? 1 : 0, (precision >> 4) & 1, li, lo, S(stream));
@@ -1157,7 +1162,7 @@ int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *ma
     if (!patches || (!out && !acc)) return CDL_EINVAL;
     if (rt.kind == 1) return cdl_strip_assemble(g, rt.sp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
     if (rt.kind == 2) return cdl_stripg_assemble(g, rt.gp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
-    if ((g->W & 3) == 0 && !cdl_opts().scalar_assemble) {
+    if ((g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) && !cdl_opts().scalar_assemble) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)(g->N * g->C * g->D));
 #define CDL_ASM4(P_) k_assemble_g4<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
         CDL_TRACE_NOTE("k_assemble_g4<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);

@@ -61,6 +61,7 @@ int relu_inplace(float *v, size_t n, hipStream_t st)
 {
     const size_t n4 = ((reinterpret_cast<size_t>(v) & 15) == 0) ? n / 4 : 0;
     const size_t threads = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
+    CDL_TRACE_NOTE("vec4=%d", n4 ? 1 : 0);
     k_relu<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(v, n4, n);
     CDL_LAUNCH_CHECK();
     return 0;

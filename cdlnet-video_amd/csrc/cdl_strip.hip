@@ -693,6 +693,7 @@ bool cdl_strip_plan_for(const cdl_geom *g, cdl_strip_plan *pl)
 int cdl_strip_prep_pairs(const cdl_geom *g, const cdl_strip_plan &pl, const float *const *w1, const float *const *w2,
                          int K, int shift2, void *frags, hipStream_t st)
 {
+    if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // the library-sized fragment buffer is written 16 bytes at a time (cdlnet_hip.h)
     const int threads = (int)(pl.frag_uint4 / 2);
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
         const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
@@ -740,7 +741,8 @@ size_t cdl_strip_rsc_floats(const cdl_geom *g, const cdl_strip_plan &pl)
 int cdl_strip_assemble(const cdl_geom *g, const cdl_strip_plan &pl, const float *patches, const float *mask,
                        const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st)
 {
-    const bool v4 = (g->W & 3) == 0 && !cdl_opts().scalar_assemble;      // (CDL_SCALAR_ASSEMBLE=1: the scalar form, for tests)
+    // (CDL_SCALAR_ASSEMBLE=1: the scalar form, for tests)
+    const bool v4 = (g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) && !cdl_opts().scalar_assemble;
     dim3 grid((unsigned)(((v4 ? g->W / 4 : g->W) + 255) / 256), (unsigned)g->H, (unsigned)g->N);
 #define CDL_ASM_S(P_, S_)                                                                                                   \
     do {                                                                                                                    \

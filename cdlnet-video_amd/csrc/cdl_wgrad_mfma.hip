@@ -553,7 +553,12 @@ int launch_ct(const cdl_geom *g, const Plan &p, const float *F, const float *gat
     while (gz < passes && wgs * (gz + 1) <= cus) ++gz;
     const int gspan = ((passes + gz - 1) / gz) * NG;
     gz = (G + gspan - 1) / gspan;
-    CDL_TRACE_NOTE("rs=%d gz=%d tpw=%d pair=%d rsc=%d tiles=%zu", p.rs, gz, p.tpw, F1 ? 1 : 0, rsc, p.tiles);
+    // vec4 / vec4b: the host's PREDICTION of the test k_wgm makes per operand (its `vec4`: 16-byte loads of F / gate), for
+    // the first operand and for the second of a pair (-1: none).  The kernel decides for itself; this only says which of
+    // its two load forms the pointers of this call select.
+    const bool w4 = ((g->W / g->sw) & 3) == 0;
+    CDL_TRACE_NOTE("rs=%d gz=%d tpw=%d pair=%d rsc=%d tiles=%zu vec4=%d vec4b=%d", p.rs, gz, p.tpw, F1 ? 1 : 0, rsc, p.tiles,
+                   w4 && cdl_aligned16(F, gate) ? 1 : 0, F1 ? (w4 && cdl_aligned16(F1, gate) ? 1 : 0) : -1);
     k_wgm<PH, PW, SW, NG, CT><<<dim3((unsigned)p.blocks, F1 ? 2 : 1, (unsigned)gz), GNT, p.lds, st>>>(
         *g, F, gate, x, ws, p.tilesX, p.tilesY, p.nct, p.MP CDL_DBG_COMMA(cdl_opts().fused_debug & (1024 | 2048 | 4096)), (int)(p.tiles * p.rs),
         p.tpw, F1, x1, rsc, gspan, p.rs);

@@ -25,6 +25,15 @@
  *   - return 0 on success, a negative value on error: -(hipError_t) for runtime errors,
  *     CDL_EINVAL / CDL_EUNSUPPORTED for argument errors.  Nothing throws.
  *   - in-place is allowed only where a parameter says "inout".
+ *   - alignment: a pointer argument needs only the alignment of its element type (4 bytes for float / int / unsigned):
+ *     a contiguous view at any element offset of an allocation is a valid tensor argument -- a frame of an unbound
+ *     clip, one bank of a stacked filter-gradient tensor, one row of a (K,N,M) threshold table.  A launcher selects a
+ *     form of a kernel with 16-byte accesses only after it has tested every pointer that form vector-accesses, and
+ *     takes the scalar form of the same kernel otherwise (same terms in the same order: same bits).
+ *     The exception is what the LIBRARY sizes and only it reads: the workspaces (`ws`, `workspace`, `scratch`), the
+ *     fragment buffers (`frags`), the patch buffers the fused stages write (`patches`) and code buffers in an internal
+ *     layout (CDL_LAY_BLOCKED*, CDL_LAY_RSC) need 16 bytes, and the call returns CDL_EUNSUPPORTED (cdl_vgg_*:
+ *     CDL_EINVAL) otherwise.  DESIGN.md section 26 lists the launchers that gate on alignment.
  */
 #ifndef CDLNET_HIP_H
 #define CDLNET_HIP_H
