@@ -197,6 +197,39 @@ static inline bool cdl_aligned16(const void *a, const void *b = nullptr, const v
              reinterpret_cast<size_t>(d)) & 15) == 0;
 }
 
+// May a patch assemble use its 16-byte form (four pixels per thread)?  The row length AND every thin pointer decide;
+// CDL_SCALAR_ASSEMBLE=1 forces the one-pixel form (tests).
+static inline bool cdl_assemble16(int W, const float *out, const float *mask, const float *sub, const float *acc)
+{
+    return (W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) && !cdl_opts().scalar_assemble;
+}
+
+// Persistent workgroups of the fused stage kernels: one per CU of the current device, striding over the work items;
+// CDL_FUSED_GRID=n caps the count (probes).
+static inline unsigned cdl_persistent_grid(size_t work_items)
+{
+    size_t cus = (size_t)cdl_cu_count();
+    const int cap = cdl_opts().fused_grid;
+    if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
+    return (unsigned)(work_items < cus ? work_items : cus);
+}
+
+// One batch of a sweep's K (first bank, second bank) weight pairs for a k_prep_* launch, pairs k0 .. k0 + nb - 1 (nb is
+// returned).  The shifted bank is index shift2 -- forward (1): (w1[k], w2[k+1 mod K]); reverse (0): (w1[k+1 mod K], w2[k]).
+template <class Batch>
+static inline int cdl_pair_batch(Batch *b, const float *const *w1, const float *const *w2, int K, int shift2, int k0)
+{
+    constexpr int cap = (int)(sizeof(b->wA) / sizeof(b->wA[0]));
+    const int nb = K - k0 < cap ? K - k0 : cap;
+    *b = Batch{};
+    for (int i = 0; i < nb; ++i) {
+        const int k = k0 + i;
+        b->wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
+        b->wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
+    }
+    return nb;
+}
+
 static inline bool cdl_geom_ok(const cdl_geom *g)
 {
     if (!g) return false;

@@ -48,9 +48,9 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "cdl_wave_dev.h"
+
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int WX = 2;                       // waves per workgroup along x
 constexpr int RB = 8;                       // row blocks (image rows) per wave
@@ -114,8 +114,6 @@ struct FusedParams {
     const float *r2;         // reverse stage with DA: (N,H,W) thin operand of dA_k = alpha * du_k (x) im2col(r2) (r_k or yp)
     float *da_partial;       // (gridDim.x, 2, M, 64): per-workgroup partial of dA_k in operator slot 0 (k_wgrad_reduce's layout)
 };
-
-enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
 
 // ------------------------------------------------------------------------------------------
 // Weight preparation: fp32 filters -> bf16 hi/lo MFMA A-operand fragments.
@@ -213,7 +211,6 @@ __device__ __forceinline__ void buf_st(float v, __amdgpu_buffer_rsrc_t r, int vo
 {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, CDL_FAT_ST_AUX);
 }
-constexpr int OOB = 0x7fff0000;              // byte offset beyond any descriptor range
 
 // ---- layouts of the fat tensors ------------------------------------------------------------------------
 // LAY_NCHW : the reference's (N, M, H, W) fp32.  A wave instruction of the MFMA C/D layout (lane = pixel,
@@ -227,7 +224,6 @@ constexpr int OOB = 0x7fff0000;              // byte offset beyond any descripto
 // LAY_BLK16: the same blocking with bf16 elements (8 bytes per lane): opt-in reduced-precision STORAGE
 //            (half the fat bytes; the 1e-5 parity gate does not hold in this mode).
 enum { LAY_NCHW = 0, LAY_BLK = 1, LAY_BLK16 = 2 };
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 __host__ __device__ inline size_t blk_image_elems(int M, int H, int W) { return (size_t)H * ((W + 31) / 32) * M * 32; }
@@ -315,29 +311,7 @@ __device__ __forceinline__ void blk_store4(float a0, float a1, float a2, float a
     }
 }
 
-// Sum over the 32 pixel lanes of each half-wave of N per-lane values, leaving total #i on lane
-// (c with c mod N == i): a halving butterfly, N-1 exchanges instead of 5N.  Template recursion keeps
-// every register index static.
-template <int N>
-struct LaneTransposeSum {
-    static __device__ __forceinline__ float run(const float (&v)[N], int c)
-    {
-        constexpr int n = N / 2;
-        const bool up = (c & n) != 0;
-        float w[n];
-#pragma unroll
-        for (int k = 0; k < n; ++k) {
-            const float keep = up ? v[k + n] : v[k];
-            const float send = up ? v[k] : v[k + n];
-            w[k] = keep + __shfl_xor(send, n, 64);
-        }
-        return LaneTransposeSum<n>::run(w, c);
-    }
-};
-template <>
-struct LaneTransposeSum<1> {
-    static __device__ __forceinline__ float run(const float (&v)[1], int) { return v[0]; }
-};
+// LaneTransposeSum (cdl_wave_dev.h) with the two halves of each of 16 totals joined
 template <int N>
 __device__ __forceinline__ float lane_transpose_sum(const float (&v)[N], int c)
 {
@@ -346,22 +320,6 @@ __device__ __forceinline__ float lane_transpose_sum(const float (&v)[N], int c)
     return r;
 }
 
-// lane i <- lane i-1 over the whole wave (lane 0 <- 0): one DPP modifier on the consuming add
-__device__ __forceinline__ float wave_shr1(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-// lanes 0..31 receive the value held by lanes 32..63 (lanes 32..63 receive 0).
-// v_permlane32_swap vdst, src exchanges vdst[32..63] with src[0..31]; with src = 0 the new src is
-// {v.hi, 0}.  Inline asm because hipcc (ROCm 7.2) returns the SAME register for both results of
-// __builtin_amdgcn_permlane32_swap (tools/probes/probe_dpp.hip); s_nop 1 = the two wait states the
-// instruction needs after a VALU write of either operand.
-__device__ __forceinline__ float upper_half_to_lower(float v)
-{
-    float lo = 0.0f;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(v), "+v"(lo));
-    return lo;
-}
 // col2im, column direction, for one halo row: lane (c, h) holds tap columns j = 4h + (0..3) of pixel
 // column c; returns on lane L (0..37) the sum over j of the value of column L - j.  The upper half's
 // taps are first moved onto the lower lanes, then a 6-step Horner chain of DPP wave shifts lets the
@@ -1579,11 +1537,7 @@ int launch_stage(const FusedParams &p, int mode, int lin, int lout, dim3 grid, h
 // persistent workgroups: one per CU (most of its LDS each), striding over the tiles
 int stage_grid(const cdl_geom *, const FusedParams &p)
 {
-    const size_t tiles = (size_t)p.N * p.tilesX * p.tilesY;
-    size_t cus = (size_t)cdl_cu_count();
-    const int cap = cdl_opts().fused_grid;                   // experiments only: fewer persistent workgroups
-    if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
-    return (int)(tiles < cus ? tiles : cus);
+    return (int)cdl_persistent_grid((size_t)p.N * p.tilesX * p.tilesY);
 }
 
 template <int WY>
@@ -1739,8 +1693,7 @@ int assemble(const cdl_geom *g, const float *patches, const float *mask, const f
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!patches || (!out && !acc)) return CDL_EINVAL;
     const int tx = tiles_x(g), ty = tiles_y<WY>(g);
-    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && (g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) &&
-        !cdl_opts().scalar_assemble) {
+    if ((size_t)g->N * g->H * g->W >= ((size_t)1 << 20) && cdl_assemble16(g->W, out, mask, sub, acc)) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 7) / 8), (unsigned)g->N);
         k_assemble_v4<WY><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->H, g->W, tx, ty, acc, acc_add);
         CDL_LAUNCH_CHECK();
@@ -1812,14 +1765,8 @@ int prep_pairs(const float *const *w1, const float *const *w2, int K, int shift2
     const int MT = M / 32, threads = 8 * MT * 64;
     const int frag_uint4 = (int)(cdl_fused2d_frag_bytes(M) / 16);
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
-        const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
-        PrepBatch b = {};
-        for (int i = 0; i < nb; ++i) {
-            const int k = k0 + i;
-            // forward: (A_k, B_{k+1 mod K});  backward: (B_{k+1 mod K}, A_k) -- the shifted bank is index shift2
-            b.wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
-            b.wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
-        }
+        PrepBatch b;
+        const int nb = cdl_pair_batch(&b, w1, w2, K, shift2, k0);       // forward: (A_k, B_{k+1 mod K});  backward: (B_{k+1 mod K}, A_k)
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         k_prep_batch<<<grid, 256, 0, st>>>(b, reinterpret_cast<uint4 *>(frags) + (size_t)k0 * frag_uint4, frag_uint4, MT, P);
         CDL_LAUNCH_CHECK();

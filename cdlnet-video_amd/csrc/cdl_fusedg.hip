@@ -37,27 +37,12 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "cdl_wave_dev.h"
 
 constexpr int WX = 2, WY = 4, NW = WX * WY, NT = 64 * NW;   // 8 waves: 2 (x) x 4 (y)
 constexpr int RB = 4;                                      // image rows per wave
 constexpr int TW = 32 * WX, TH = RB * WY;                  // 64 x 16 pixel tile of one (n, depth) plane
-constexpr int OOB = 0x7fff0000;
 // groups g = (c, kd) are a template parameter (their col2im rings live in registers): G = C * Pd in {1, 3, 5, 7}
-
-enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
-
-// ---- tap packing of the synthesis-like GEMM's M dimension ------------------------------------------------------
-// Row t of a 32-row accumulator tile sits in register v = 4*((t>>3)&3) + (t&3) of lane half h = (t>>2)&1.  The taps
-// (i, j) of a P x P filter plane are assigned rows so that the column-direction col2im is a short static sequence:
-// P = 3, 7: t = 8 i + j (as cdl_fused2d.hip); P = 5: 25 taps packed into ONE 32-row tile (8i + j would need two).
-template <int P> __host__ __device__ constexpr int tap_slot(int i, int j)
-{
-    if (P == 5) return (i < 4 && j < 4) ? 8 * i + j : (i < 4 ? 8 * i + 4 : (j < 4 ? 8 * j + 5 : 6));
-    return 8 * i + j;
-}
-template <int P> struct TapTiles { static constexpr int RT = (P == 7) ? 2 : 1; };
 
 struct GParams {
     const float *r;          // (N,C,D,H,W) thin input of the analysis-like half
@@ -75,41 +60,6 @@ struct GParams {
     CDL_DBG_FIELD(int dbg;)  // probe build only (CDL_FUSED_DEBUG; results are wrong): 1 no thin staging after the
                              // first tile, 2 no analysis GEMM, 4 no synthesis / col2im, 8 no fat loads, 16 no fat stores,
                              // 32 no patch combine
-};
-
-__device__ __forceinline__ float wave_shr1(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-// lanes 0..31 receive the value of lanes 32..63 (which receive 0); see cdl_fused2d.hip for why this is inline asm
-__device__ __forceinline__ float upper_half_to_lower(float v)
-{
-    float lo = 0.0f;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(v), "+v"(lo));
-    return lo;
-}
-
-// Sum over the 32 pixel lanes of each half-wave of N per-lane values (N = 16 or 32), leaving total #i on lane c with
-// c mod N == i (cdl_fused2d.hip)
-template <int N>
-struct LaneTransposeSum {
-    static __device__ __forceinline__ float run(const float (&v)[N], int c)
-    {
-        constexpr int n = N / 2;
-        const bool up = (c & n) != 0;
-        float w[n];
-#pragma unroll
-        for (int k = 0; k < n; ++k) {
-            const float keep = up ? v[k + n] : v[k];
-            const float send = up ? v[k] : v[k + n];
-            w[k] = keep + __shfl_xor(send, n, 64);
-        }
-        return LaneTransposeSum<n>::run(w, c);
-    }
-};
-template <>
-struct LaneTransposeSum<1> {
-    static __device__ __forceinline__ float run(const float (&v)[1], int) { return v[0]; }
 };
 
 // ---- weight preparation ------------------------------------------------------------------------------------------
@@ -866,41 +816,41 @@ __global__ __launch_bounds__(1024) void k_dtau_reduce_g(const float *__restrict_
     if (part == 0 && m < M) { dt0[m] = r0[0][mi]; dt1[m] = r1[0][mi]; }
 }
 
+
 inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-struct Plan {
-    int P, MT, KS, KQ, G, tilesX, tilesY;
-    size_t tiles, frag_uint4, patch_floats;
-};
+typedef cdl_fusedg_plan Plan;                               // cdl_strip.h: one plan for the three kernels
 
-bool plan_for(const cdl_geom *g, Plan *pl)
+bool tile_plan_for(const cdl_geom *g, Plan *pl)
 {
-    if (!cdl_geom_ok(g)) return false;
-    if (g->sd != 1 || g->sh != 1 || g->sw != 1) return false;
-    if (g->Ph != g->Pw || (g->Ph != 3 && g->Ph != 5 && g->Ph != 7)) return false;
-    if ((g->Pd & 1) == 0 || g->pd != g->Pd / 2 || g->ph != g->Ph / 2 || g->pw != g->Pw / 2) return false;
-    if (g->M > 64 || g->M < 8 || (g->M & 7)) return false;  // whole register quads of channels (see k_stage_g)
-    pl->P = g->Ph;
-    pl->G = g->C * g->Pd;
-    if (pl->G != 1 && pl->G != 3 && pl->G != 5 && pl->G != 7) return false;
-    if (g->Ph == 7 && pl->G == 7) return false;             // 49 ring registers on top of the tiles: spills to scratch
-    pl->MT = (g->M + 31) / 32;
-    pl->KS = (pl->G * g->Ph * g->Pw + 15) / 16;
-    pl->KQ = (g->M + 15) / 16;
+    if (!cdl_grouped_plan_base(g, pl)) return false;
+    pl->kind = CDL_PLAN_TILE;
     pl->tilesX = (g->W + TW - 1) / TW;
     pl->tilesY = (g->H + TH - 1) / TH;
-    pl->tiles = (size_t)g->N * g->D * pl->tilesX * pl->tilesY;
-    const int RT = g->Ph == 7 ? 2 : 1;
-    pl->frag_uint4 = (size_t)2 * (pl->MT * pl->KS + pl->G * RT * pl->KQ) * 64;
-    pl->patch_floats = pl->tiles * pl->G * (TH + g->Ph - 1) * (TW + g->Pw - 1);
-    if ((size_t)g->M * g->D * g->H * g->W * 4 >= ((size_t)1 << 31)) return false;      // per-sample buffer descriptor range
-    if (pl->tiles >= ((size_t)1 << 30) || g->H > 65535 || (size_t)g->N * g->C * g->D > 65535) return false;
+    pl->items = (size_t)g->N * g->D * pl->tilesX * pl->tilesY;
+    pl->per_img = (int)(pl->items / g->N);
+    pl->prows = TH + g->Ph - 1;
+    pl->pxw = TW + g->Pw - 1;
+    pl->patch_floats = pl->items * pl->G * pl->prows * pl->pxw;
+    if (pl->items >= ((size_t)1 << 30)) return false;
     int lds = 0;
     if (g->Ph == 3) lds = carve<3>(pl->MT, pl->KS, pl->KQ, pl->G, 0).total;
     if (g->Ph == 5) lds = carve<5>(pl->MT, pl->KS, pl->KQ, pl->G, 0).total;
     if (g->Ph == 7) lds = carve<7>(pl->MT, pl->KS, pl->KQ, pl->G, 0).total;
-    if (lds > 160 * 1024) return false;
-    return true;
+    return lds <= 160 * 1024;
+}
+
+// The first plan that accepts the geometry: the tile kernel's -- cdl_stripg.hip's in its place with CDL_FUSEDG_STRIP=1,
+// where that accepts too (measured at parity with the tile kernel forward and behind it in the reverse mode, DESIGN.md
+// section 5.2d) --, else cdl_strip.hip's.
+bool route_for(const cdl_geom *g, Plan *pl)
+{
+    if (tile_plan_for(g, pl)) {
+        Plan sg;
+        if (cdl_opts().fusedg_strip && cdl_stripg_plan_for(g, &sg)) *pl = sg;
+        return true;
+    }
+    return cdl_strip_plan_for(g, pl);
 }
 
 template <int P, int G, int MT, int MODE, bool FOUR = false>
@@ -908,10 +858,7 @@ int launch_one(const GParams &p, const Plan &pl, hipStream_t st)
 {
     const int lds = carve<P>(MT, pl.KS, pl.KQ, G, 0).total;
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage_g<P, G, MT, MODE, FOUR>, lds)) return rc;
-    size_t cus = (size_t)cdl_cu_count();
-    const int cap = cdl_opts().fused_grid;
-    if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
-    const unsigned grid = (unsigned)(pl.tiles < cus ? pl.tiles : cus);
+    const unsigned grid = cdl_persistent_grid(pl.items);
     k_stage_g<P, G, MT, MODE, FOUR><<<grid, NT, lds, st>>>(p);
     CDL_LAUNCH_CHECK();
     return 0;
@@ -946,35 +893,15 @@ int launch_p(const GParams &p, const Plan &pl, int mode, hipStream_t st)
 
 std::atomic<unsigned long long *> g_timeline{nullptr};
 
-int dispatch(const cdl_geom *g, GParams &p, const Plan &pl, int mode, int precision, hipStream_t st)
-{
-    p.tl = g_timeline.load();
-    p.rev = (precision >> 4) & 1;
-    CDL_DBG_FIELD(p.dbg = cdl_opts().fused_debug;)
-    if ((precision >> 5) != 0) return CDL_EINVAL;
-    if ((precision & 15) == 2) mode += 3;                    // split-bf16 x4
-    else if ((precision & 15) != 0) return CDL_EUNSUPPORTED;  // otherwise split-bf16 x3
-    p.N = g->N; p.C = g->C; p.M = g->M; p.D = g->D; p.H = g->H; p.W = g->W; p.Pd = g->Pd;
-    p.tilesX = pl.tilesX; p.tilesY = pl.tilesY; p.KS = pl.KS;
-    if (pl.P == 3) return launch_p<3>(p, pl, mode, st);
-    if (pl.P == 5) return launch_p<5>(p, pl, mode, st);
-    return launch_p<7>(p, pl, mode, st);
-}
-
-// fragments of K (analysis-like, synthesis-like) pairs, pair k at frags + k * frag bytes
+// fragments of K (analysis-like, synthesis-like) pairs of the tile and the stripg kernel, pair k at frags + k * frag bytes
 int prep_pairs(const cdl_geom *g, const Plan &pl, const float *const *w1, const float *const *w2, int K, int shift2,
                void *frags, hipStream_t st)
 {
     if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // the library-sized fragment buffer is written 16 bytes at a time (cdlnet_hip.h)
     const int threads = (int)(pl.frag_uint4 / 2);           // one thread per (fragment, lane); hi and lo together
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
-        const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
-        PrepBatch b = {};
-        for (int i = 0; i < nb; ++i) {
-            const int k = k0 + i;
-            b.wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
-            b.wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
-        }
+        PrepBatch b;
+        const int nb = cdl_pair_batch(&b, w1, w2, K, shift2, k0);
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         uint4 *out = reinterpret_cast<uint4 *>(frags) + (size_t)k0 * pl.frag_uint4;
         CDL_TRACE_NOTE("k_prep_g<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
@@ -986,38 +913,71 @@ int prep_pairs(const cdl_geom *g, const Plan &pl, const float *const *w1, const 
     return 0;
 }
 
-// Which kernel serves a geometry: 0 = the tile kernel k_stage_g (this file), 1 = cdl_strip.hip (one image channel, stride
-// 1 / 2, M <= 192), 2 = cdl_stripg.hip (the tile kernel's shapes in the strip decomposition, reading the same prepared
-// fragments; opt-in with CDL_FUSEDG_STRIP=1: measured at parity with the tile kernel forward and behind it in the reverse
-// mode).
-struct Route {
-    int kind;
-    Plan pl;
-    cdl_strip_plan sp;
-    cdl_stripg_plan gp;
-};
-bool route_for(const cdl_geom *g, Route *rt)
+int prep(const cdl_geom *g, const Plan &pl, const float *const *w1, const float *const *w2, int K, int shift2, void *frags,
+         hipStream_t st)
 {
-    if (plan_for(g, &rt->pl)) {
-        rt->kind = (cdl_opts().fusedg_strip && cdl_stripg_plan_for(g, &rt->gp)) ? 2 : 0;
-        return true;
-    }
-    if (cdl_strip_plan_for(g, &rt->sp)) {
-        rt->kind = 1;
-        return true;
-    }
-    return false;
+    return pl.kind == CDL_PLAN_STRIP ? cdl_strip_prep_pairs(g, pl, w1, w2, K, shift2, frags, st)
+                                     : prep_pairs(g, pl, w1, w2, K, shift2, frags, st);
 }
 
-// layouts of the strip kernel's fat operands from the precision word: CDL_LAY_NCHW or CDL_LAY_RSC on either side
-bool strip_layouts(int precision, int *lay_in, int *lay_out)
+// One stage launch behind cdl_fusedg_iter_fwd (MODE_FWD, MODE_FIRST: z' = ST(zin + sgn * A r, tau); map nullable) and
+// cdl_fusedg_stage_bwd (MODE_BWD: du = [map](zin + acc), dtau).  precision: the entry points' word -- arithmetic in
+// bits 0-3 (tile kernel: 0 = split-bf16 x3, 2 = x4; strip kernels: 0), CDL_TILES_REVERSED, and for the strip kernels
+// CDL_LAYOUT_IN / CDL_LAYOUT_OUT (CDL_LAY_NCHW or CDL_LAY_RSC) of zin / zout.
+int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const float *zin, const float *tau,
+          const void *frags, float sgn, float *zout, float *patches, unsigned *map, float *dtau, int do_synth,
+          int precision, hipStream_t st)
 {
-    const int li = (precision >> 5) & 3, lo = (precision >> 7) & 3;
-    if ((precision >> 9) != 0) return false;
-    if ((li != CDL_LAY_NCHW && li != CDL_LAY_RSC) || (lo != CDL_LAY_NCHW && lo != CDL_LAY_RSC)) return false;
-    *lay_in = li == CDL_LAY_RSC;
-    *lay_out = lo == CDL_LAY_RSC;
-    return true;
+    if (!r || !frags || !zout || zout == zin) return CDL_EINVAL;
+    if (mode == MODE_BWD ? (!map || !dtau) : (!tau || !patches)) return CDL_EINVAL;
+    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
+    if (do_synth && !patches) return CDL_EINVAL;
+    const int rev = (precision >> 4) & 1;
+    if (pl.kind != CDL_PLAN_TILE) {
+        const int li = (precision >> 5) & 3, lo = (precision >> 7) & 3;
+        if ((precision >> 9) != 0) return CDL_EINVAL;
+        if ((li != CDL_LAY_NCHW && li != CDL_LAY_RSC) || (lo != CDL_LAY_NCHW && lo != CDL_LAY_RSC)) return CDL_EINVAL;
+        if ((precision & 15) != 0) return CDL_EUNSUPPORTED;
+        const int rsc_in = li == CDL_LAY_RSC, rsc_out = lo == CDL_LAY_RSC;
+        if ((rsc_in && !cdl_aligned16(zin)) || (rsc_out && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;   // rsc codes: 16-byte accesses
+        if (pl.kind == CDL_PLAN_STRIP)
+            return cdl_strip_stage(g, pl, mode, r, zin, tau, frags, sgn, zout, patches, map, dtau, do_synth, rev, rsc_in, rsc_out, st);
+        return cdl_stripg_stage(g, pl, mode, r, zin, tau, frags, sgn, zout, patches, map, dtau, do_synth, rev, rsc_in, rsc_out, st);
+    }
+    if ((precision >> 5) != 0) return CDL_EINVAL;
+    if ((precision & 15) == 2) mode += 3;                    // split-bf16 x4
+    else if ((precision & 15) != 0) return CDL_EUNSUPPORTED;  // otherwise split-bf16 x3
+    GParams p = {};
+    p.r = r; p.zin = zin; p.map = map; p.zout = zout; p.tau = tau; p.dtau = dtau;
+    p.frags = reinterpret_cast<const uint4 *>(frags);
+    p.patches = patches; p.sgn = sgn; p.do_synth = do_synth;
+    p.tl = g_timeline.load();
+    p.rev = rev;
+    CDL_DBG_FIELD(p.dbg = cdl_opts().fused_debug;)
+    p.N = g->N; p.C = g->C; p.M = g->M; p.D = g->D; p.H = g->H; p.W = g->W; p.Pd = g->Pd;
+    p.tilesX = pl.tilesX; p.tilesY = pl.tilesY; p.KS = pl.KS;
+    if (pl.P == 3) return launch_p<3>(p, pl, mode, st);
+    if (pl.P == 5) return launch_p<5>(p, pl, mode, st);
+    return launch_p<7>(p, pl, mode, st);
+}
+
+// CDL_LAYOUT_IN(precision) of a whole sweep: the layout of the codes that stay inside it (z[0..K-2], the du buffers);
+// CDL_LAY_RSC for the strip kernels only, and only where the caller's other kernels read it (rsc_ok)
+bool sweep_layout(const Plan &pl, int precision, bool rsc_ok, int *lay)
+{
+    *lay = (precision >> 5) & 3;
+    return (precision >> 7) == 0 && (*lay == CDL_LAY_NCHW || (pl.kind != CDL_PLAN_TILE && *lay == CDL_LAY_RSC && rsc_ok));
+}
+
+// The precision word of one stage launch of a sweep.  Arithmetic of the tile kernel: split-bf16 x3 unless the caller
+// (precision 2) or CDL_FUSEDG_PREC=2 asks for all four products.  (Round 3 tested the round-2 hypothesis that the dropped
+// lo * lo products are what shows as 2e-4 in cfg4's dB_k: with x4 in both sweeps the figure does not move --
+// tools/debug_cfg4.py, DESIGN.md section 3 -- so x3 stays.)  reversed: the snake order of cdl_fused2d.hip's sweeps.
+int sweep_flags(const Plan &pl, int precision, bool reversed, int lay_in, int lay_out)
+{
+    const int forced = cdl_opts().fusedg_bwd_prec;
+    const int prec = (pl.kind == CDL_PLAN_TILE && (forced == 0 || forced == 2)) ? forced : (precision & 15);
+    return prec | (reversed ? CDL_TILES_REVERSED : 0) | CDL_LAYOUT_IN(lay_in) | CDL_LAYOUT_OUT(lay_out);
 }
 
 }  // namespace
@@ -1032,137 +992,94 @@ int cdl_fusedg_set_timeline(void *buf)
     return 0;
 }
 
-/* Shapes outside plan_for() that the strip kernel takes (cdl_strip.hip: one image channel, stride 1 or 2, up to 192
- * subbands -- the shipped CDLNet-s2030 architecture) go through the same entry points. */
+/* Shapes outside the tile kernel's that the strip kernel takes (cdl_strip.hip: one image channel, stride 1 or 2, up to 192
+ * subbands -- the shipped CDLNet-s2030 architecture) go through the same entry points.  The size queries: 0 when no
+ * kernel takes the geometry. */
 int cdl_fusedg_supported(const cdl_geom *g)
 {
-    Route rt;
-    return route_for(g, &rt) ? 1 : 0;
+    Plan pl;
+    return route_for(g, &pl) ? 1 : 0;
 }
 
 size_t cdl_fusedg_frag_bytes(const cdl_geom *g)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return 0;
-    return (rt.kind == 1 ? rt.sp.frag_uint4 : rt.pl.frag_uint4) * 16;
+    Plan pl;
+    return route_for(g, &pl) ? pl.frag_uint4 * 16 : 0;
 }
 
 size_t cdl_fusedg_patch_floats(const cdl_geom *g)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return 0;
-    return rt.kind == 1 ? rt.sp.patch_floats : rt.kind == 2 ? rt.gp.patch_floats : rt.pl.patch_floats;
+    Plan pl;
+    return route_for(g, &pl) ? pl.patch_floats : 0;
 }
 
 size_t cdl_fusedg_tiles(const cdl_geom *g)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return 0;
-    return rt.kind == 1 ? rt.sp.items : rt.kind == 2 ? rt.gp.items : rt.pl.tiles;
+    Plan pl;
+    return route_for(g, &pl) ? pl.items : 0;
 }
 
 size_t cdl_fusedg_map_words(const cdl_geom *g)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return 0;
-    return rt.kind == 1 ? rt.sp.map_words : (size_t)g->N * 4 * g->D * g->H * g->W;
+    Plan pl;
+    return route_for(g, &pl) ? pl.map_words : 0;
 }
 
-/* The layout the sweeps should keep z[0..K-2] and the du buffers in: CDL_LAY_RSC for the strip kernel's shapes (training:
+/* The layout the sweeps should keep z[0..K-2] and the du buffers in: CDL_LAY_RSC for the strip kernels' shapes (training:
  * when the matrix-core filter-gradient kernel takes the geometry), CDL_LAY_NCHW otherwise; cdl_fusedg_code_floats: floats of one
  * code tensor in that layout. */
 int cdl_fusedg_code_layout(const cdl_geom *g, int training)
 {
-    Route rt;
-    if (!route_for(g, &rt) || rt.kind == 0) return CDL_LAY_NCHW;
+    Plan pl;
+    if (!route_for(g, &pl) || pl.kind == CDL_PLAN_TILE) return CDL_LAY_NCHW;
     // a forward-only sweep has no filter gradients to feed: the strip kernels' own layout always
     return (!training || cdl_mfma_wgrad_takes(g)) ? CDL_LAY_RSC : CDL_LAY_NCHW;
 }
 
 size_t cdl_fusedg_code_floats(const cdl_geom *g, int layout)
 {
-    Route rt;
-    if (layout == CDL_LAY_RSC) {
-        if (!route_for(g, &rt)) return 0;
-        return rt.kind == 1 ? cdl_strip_rsc_floats(g, rt.sp) : rt.kind == 2 ? cdl_stripg_rsc_floats(g, rt.gp) : 0;
-    }
+    Plan pl;
+    if (layout == CDL_LAY_RSC) return route_for(g, &pl) ? pl.rsc_floats : 0;
     return (size_t)g->N * g->M * (g->D / g->sd) * (g->H / g->sh) * (g->W / g->sw);
 }
 
 int cdl_fusedg_prep(const cdl_geom *g, const float *wA, const float *wB, void *frags, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (!wA || !wB || !frags) return CDL_EINVAL;
     const float *a[1] = {wA}, *b[1] = {wB};
-    if (rt.kind == 1) return cdl_strip_prep_pairs(g, rt.sp, a, b, 1, 1, frags, S(stream));
-    return prep_pairs(g, rt.pl, a, b, 1, 1, frags, S(stream));
+    return prep(g, pl, a, b, 1, 1, frags, S(stream));
 }
 
 int cdl_fusedg_iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *tau, const void *frags,
                         float sgn, float *zout, float *patches, unsigned *map_out, int precision, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const Plan &pl = rt.pl;
-    if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
-    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
-    if (rt.kind != 0) {
-        int li, lo;
-        if (!strip_layouts(precision, &li, &lo)) return CDL_EINVAL;
-        if ((precision & 15) != 0) return CDL_EUNSUPPORTED;
-        if ((li && !cdl_aligned16(zin)) || (lo && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;       // rsc codes: 16-byte accesses
-        if (rt.kind == 1)
-            return cdl_strip_stage(g, rt.sp, zin ? 0 : 1, r, zin, tau, frags, sgn, zout, patches, map_out, nullptr, 1,
-                                   (precision >> 4) & 1, li, lo, S(stream));
-        return cdl_stripg_stage(g, rt.gp, zin ? 0 : 1, r, zin, tau, frags, sgn, zout, patches, map_out, nullptr, 1,
-                                (precision >> 4) & 1, li, lo, S(stream));
-    }
-    GParams p = {};
-    p.r = r; p.zin = zin; p.zout = zout; p.tau = tau; p.map = map_out;
-    p.frags = reinterpret_cast<const uint4 *>(frags);
-    p.patches = patches; p.sgn = sgn; p.do_synth = 1;
-    return dispatch(g, p, pl, zin ? MODE_FWD : MODE_FIRST, precision, S(stream));
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
+    return stage(g, pl, zin ? MODE_FWD : MODE_FIRST, r, zin, tau, frags, sgn, zout, patches, map_out, nullptr, 1, precision,
+                 S(stream));
 }
 
 int cdl_fusedg_stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
                          const void *frags, float *du_out, float *patches, float *dtau_partial, int do_synth,
                          int precision, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const Plan &pl = rt.pl;
-    if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
-    if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
-    if (do_synth && !patches) return CDL_EINVAL;
-    if (rt.kind != 0) {
-        int li, lo;
-        if (!strip_layouts(precision, &li, &lo)) return CDL_EINVAL;
-        if ((precision & 15) != 0) return CDL_EUNSUPPORTED;
-        if ((li && !cdl_aligned16(base)) || (lo && !cdl_aligned16(du_out))) return CDL_EUNSUPPORTED;    // rsc codes: 16-byte accesses
-        if (rt.kind == 1)
-            return cdl_strip_stage(g, rt.sp, 2, thin, base, nullptr, frags, 1.0f, du_out, patches, const_cast<unsigned *>(map),
-                                   dtau_partial, do_synth ? 1 : 0, (precision >> 4) & 1, li, lo, S(stream));
-        return cdl_stripg_stage(g, rt.gp, 2, thin, base, nullptr, frags, 1.0f, du_out, patches, const_cast<unsigned *>(map),
-                                dtau_partial, do_synth ? 1 : 0, (precision >> 4) & 1, li, lo, S(stream));
-    }
-    GParams p = {};
-    p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
-    p.frags = reinterpret_cast<const uint4 *>(frags);
-    p.patches = patches; p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0;
-    return dispatch(g, p, pl, MODE_BWD, precision, S(stream));
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
+    return stage(g, pl, MODE_BWD, thin, base, nullptr, frags, 1.0f, du_out, patches, const_cast<unsigned *>(map),
+                 dtau_partial, do_synth ? 1 : 0, precision, S(stream));
 }
 
 int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *mask, const float *sub, float alpha,
                         float *out, float *acc, int acc_add, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const Plan &pl = rt.pl;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (!patches || (!out && !acc)) return CDL_EINVAL;
-    if (rt.kind == 1) return cdl_strip_assemble(g, rt.sp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
-    if (rt.kind == 2) return cdl_stripg_assemble(g, rt.gp, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
-    if ((g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) && !cdl_opts().scalar_assemble) {
+    if (pl.kind == CDL_PLAN_STRIP) return cdl_strip_assemble(g, pl, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
+    if (pl.kind == CDL_PLAN_STRIPG) return cdl_stripg_assemble(g, pl, patches, mask, sub, alpha, out, acc, acc_add, S(stream));
+    if (cdl_assemble16(g->W, out, mask, sub, acc)) {
         dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)((g->H + 3) / 4), (unsigned)(g->N * g->C * g->D));
 #define CDL_ASM4(P_) k_assemble_g4<P_><<<grid, 256, 0, S(stream)>>>(patches, mask, sub, alpha, out, g->N, g->C, g->D, g->H, g->W, g->Pd, pl.tilesX, pl.tilesY, acc, acc_add)
         CDL_TRACE_NOTE("k_assemble_g4<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
@@ -1182,16 +1099,14 @@ int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *ma
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
                            float *dtau_n, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
-    const int per_img = rt.kind == 1 ? rt.sp.nsx * rt.sp.nsy
-                        : rt.kind == 2 ? g->D * rt.gp.nsx * rt.gp.nsy : g->D * rt.pl.tilesX * rt.pl.tilesY;
-    k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, per_img, g->M);
+    k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, pl.per_img, g->M);
     CDL_LAUNCH_CHECK();
     if (!dtau_n) return 0;
     // partial rows: [n][tile][m], as k_dtau_reduce_g reads them
-    return cdl_dtau_per_sample(dtau_partial, g->N, g->M, per_img, (size_t)per_img * g->M, 1, g->M, dtau_n, stream);
+    return cdl_dtau_per_sample(dtau_partial, g->N, g->M, pl.per_img, (size_t)pl.per_img * g->M, 1, g->M, dtau_n, stream);
 }
 
 /* ---- whole sweeps (one C call each), the counterparts of cdl_fused2d_forward / _backward ------------------------ */
@@ -1199,34 +1114,21 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
                        const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                        unsigned *const *maps, float *xp, void *frags, float *patches, int precision, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const Plan &pl = rt.pl;
-    const cdl_strip_plan &sp = rt.sp;
-    const bool strip = rt.kind == 1;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !tau || !wA || !wB || !z || !xp || !frags || !patches || (K > 1 && !r)) return CDL_EINVAL;
     const size_t nm = (size_t)g->N * g->M;
     const int snake = cdl_opts().fused_snake;
     const float *thin = yp;
-    const size_t fb = (strip ? sp.frag_uint4 : pl.frag_uint4) * 16;
-    int rc = strip ? cdl_strip_prep_pairs(g, sp, wA, wB, K, 1, frags, S(stream))
-                   : prep_pairs(g, pl, wA, wB, K, 1, frags, S(stream));     // (A_k, B_{k+1}) for every k
+    int rc = prep(g, pl, wA, wB, K, 1, frags, S(stream));             // (A_k, B_{k+1}) for every k
     if (rc) return rc;
-    // CDL_LAYOUT_IN(precision): the layout of z[0..K-2] (strip shapes: CDL_LAY_RSC allowed); z[K-1] is always the
-    // reference's (N,M,..) layout
-    const int lay = (precision >> 5) & 3;
-    // arithmetic of the tile kernel: split-bf16 x3 unless the caller (precision 2) or CDL_FUSEDG_PREC=2 asks for all four
-    // products.  (Round 3 tested the round-2 hypothesis that the dropped lo * lo products are what shows as 2e-4 in cfg4's
-    // dB_k: with x4 in both sweeps the figure does not move -- tools/debug_cfg4.py, DESIGN.md section 3 -- so x3 stays.)
-    const int forced = cdl_opts().fusedg_bwd_prec;
-    const int pbase = (rt.kind == 0 && (forced == 0 || forced == 2)) ? forced : (precision & 15);
-    if ((precision >> 7) != 0 || (lay != CDL_LAY_NCHW && !(rt.kind != 0 && lay == CDL_LAY_RSC))) return CDL_EINVAL;
+    int lay;                                                 // of z[0..K-2]; z[K-1] is always the reference's (N,M,..) layout
+    if (!sweep_layout(pl, precision, true, &lay)) return CDL_EINVAL;
     for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        const int flags = pbase | ((k & 1) && snake ? CDL_TILES_REVERSED : 0) | CDL_LAYOUT_IN(k ? lay : CDL_LAY_NCHW) |
-                          CDL_LAYOUT_OUT(k < K - 1 ? lay : CDL_LAY_NCHW);
-        rc = cdl_fusedg_iter_fwd(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k], patches,
-                                 maps ? maps[k] : nullptr, flags, stream);
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * pl.frag_uint4 * 16;
+        rc = stage(g, pl, k ? MODE_FWD : MODE_FIRST, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k],
+                   patches, maps ? maps[k] : nullptr, nullptr, 1,
+                   sweep_flags(pl, precision, (k & 1) && snake, k ? lay : CDL_LAY_NCHW, k < K - 1 ? lay : CDL_LAY_NCHW), S(stream));
         if (rc) return rc;
         if (k < K - 1) {
             rc = cdl_fusedg_assemble(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
@@ -1248,24 +1150,20 @@ int cdl_fusedg_tangent(const cdl_geom *g, int K, const float *vp, const float *n
                        float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, int precision,
                        void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const bool strip = rt.kind == 1;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (K < 1 || !vp || !nvp || !wA || !wB || !maps || !zd || !xdp || !frags || !patches || !dtau_partial || (K > 1 && !nrd))
         return CDL_EINVAL;
     if ((precision >> 5) != 0) return CDL_EINVAL;             // CDL_LAY_NCHW codes only
     const int snake = cdl_opts().fused_snake;
-    const int forced = cdl_opts().fusedg_bwd_prec;            // (see cdl_fusedg_forward)
-    const int pbase = (rt.kind == 0 && (forced == 0 || forced == 2)) ? forced : (precision & 15);
-    const size_t fb = (strip ? rt.sp.frag_uint4 : rt.pl.frag_uint4) * 16;
-    int rc = strip ? cdl_strip_prep_pairs(g, rt.sp, wA, wB, K, 1, frags, S(stream))
-                   : prep_pairs(g, rt.pl, wA, wB, K, 1, frags, S(stream));  // (A_k, B_{k+1}), the forward's pairs
+    int rc = prep(g, pl, wA, wB, K, 1, frags, S(stream));             // (A_k, B_{k+1}), the forward's pairs
     if (rc) return rc;
     const float *thin = vp;
     for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        rc = cdl_fusedg_stage_bwd(g, thin, k ? zd[k - 1] : nullptr, maps[k], fk, zd[k], patches, dtau_partial, 1,
-                                  pbase | ((k & 1) && snake ? CDL_TILES_REVERSED : 0), stream);
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * pl.frag_uint4 * 16;
+        rc = stage(g, pl, MODE_BWD, thin, k ? zd[k - 1] : nullptr, nullptr, fk, 1.0f, zd[k], patches,
+                   const_cast<unsigned *>(maps[k]), dtau_partial, 1,
+                   sweep_flags(pl, precision, (k & 1) && snake, CDL_LAY_NCHW, CDL_LAY_NCHW), S(stream));
         if (rc) return rc;
         if (k < K - 1) {
             rc = cdl_fusedg_assemble(g, patches, mask, nvp, -1.0f, nrd[k], nullptr, 0, stream);
@@ -1288,39 +1186,32 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
                         float *dtau_partial, float *wgrad_ws, size_t wgrad_ws_floats, int precision, float *dyp,
                         float *dtau, void *stream)
 {
-    Route rt;
-    if (!route_for(g, &rt)) return CDL_EUNSUPPORTED;
-    const Plan &pl = rt.pl;
-    const cdl_strip_plan &sp = rt.sp;
-    const bool strip = rt.kind == 1;
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
         !patches || !dtau_partial || (K > 1 && !r))
         return CDL_EINVAL;
     const int M = g->M;
     float *du[2] = {du0, du1};
-    const int snake = cdl_opts().fused_snake;
-    const int sdir = snake ? (((K - 1) & 1) ? CDL_TILES_REVERSED : 0) : 0;
-    // CDL_LAYOUT_IN(precision): the layout of z[0..K-2] and of the du buffers (strip shapes: CDL_LAY_RSC allowed, when
-    // the matrix-core filter-gradient kernel takes the geometry: its VALU fallbacks read the reference layout only)
-    const int lay = (precision >> 5) & 3;
-    if ((precision >> 7) != 0 || (lay != CDL_LAY_NCHW && !(rt.kind != 0 && lay == CDL_LAY_RSC && cdl_mfma_wgrad_takes(g))))
-        return CDL_EINVAL;
+    // the layout of z[0..K-2] and of the du buffers: CDL_LAY_RSC when the matrix-core filter-gradient kernel takes the
+    // geometry (its VALU fallbacks read the reference layout only)
+    int lay;
+    if (!sweep_layout(pl, precision, cdl_mfma_wgrad_takes(g), &lay)) return CDL_EINVAL;
     const int rsc = lay == CDL_LAY_RSC;
-    const int forced = cdl_opts().fusedg_bwd_prec;            // (see cdl_fusedg_forward)
-    const int bprec = (rt.kind == 0 && (forced == 0 || forced == 2)) ? forced : (precision & 15);
+    const int snake = cdl_opts().fused_snake;
     int rc = cdl_wgrad(g, z[K - 1], nullptr, g_xp, 1.0f, dB[0], wgrad_ws, wgrad_ws_floats, stream);      // dB_0 = z_K (x) dL/d(D z_K)
     if (rc) return rc;
     const float *thin = g_xp, *base = g_z;
-    const size_t fb = (strip ? sp.frag_uint4 : pl.frag_uint4) * 16;
-    rc = strip ? cdl_strip_prep_pairs(g, sp, wB, wA, K, 0, frags, S(stream))
-               : prep_pairs(g, pl, wB, wA, K, 0, frags, S(stream));         // (B_{k+1}, A_k) for every k
+    rc = prep(g, pl, wB, wA, K, 0, frags, S(stream));                 // (B_{k+1}, A_k) for every k
     if (rc) return rc;
     for (int k = K - 1, flip = 0; k >= 0; --k, flip ^= 1) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
+        const void *fk = static_cast<const char *>(frags) + (size_t)k * pl.frag_uint4 * 16;
         float *duk = du[flip];
-        rc = cdl_fusedg_stage_bwd(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
-                                  bprec | (((K - 1 - k) & 1) ? (sdir ^ CDL_TILES_REVERSED) : sdir) |
-                                      CDL_LAYOUT_IN(k == K - 1 ? CDL_LAY_NCHW : lay) | CDL_LAYOUT_OUT(lay), stream);
+        // stage k walks the way the forward's stage k did; with the snake off the direction still alternates from the
+        // first reverse stage on
+        const bool reversed = snake ? (k & 1) : ((K - 1 - k) & 1);
+        rc = stage(g, pl, MODE_BWD, thin, base, nullptr, fk, 1.0f, duk, patches, const_cast<unsigned *>(maps[k]), dtau_partial,
+                   k >= 1 || dyp, sweep_flags(pl, precision, reversed, k == K - 1 ? CDL_LAY_NCHW : lay, lay), S(stream));
         if (rc) return rc;
         rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
                                     dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);

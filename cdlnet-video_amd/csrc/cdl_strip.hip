@@ -602,22 +602,18 @@ __global__ __launch_bounds__(256) void k_assemble_s(const float *__restrict__ pa
 }
 
 template <int P, int S, int MTP, int MODE, bool MAPPED>
-int launch_one(const SParams &p, const cdl_strip_plan &pl, hipStream_t st)
+int launch_one(const SParams &p, const cdl_fusedg_plan &pl, hipStream_t st)
 {
     const int lds = carve<P, S>(pl.MT, pl.KQ).total;
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_strip<P, S, MTP, MODE, MAPPED>, lds)) return rc;
-    size_t cus = (size_t)cdl_cu_count();
-    const int cap = cdl_opts().fused_grid;
-    if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
-    const size_t wgs = (pl.items + NWV - 1) / NWV;
-    const unsigned grid = (unsigned)(wgs < cus ? wgs : cus);
+    const unsigned grid = cdl_persistent_grid((pl.items + NWV - 1) / NWV);
     k_strip<P, S, MTP, MODE, MAPPED><<<grid, NTS, lds, st>>>(p);
     CDL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int P, int S, int MTP>
-int launch_mode(const SParams &p, const cdl_strip_plan &pl, int mode, hipStream_t st)
+int launch_mode(const SParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     if (mode == MODE_FWD)
         return p.map ? launch_one<P, S, MTP, MODE_FWD, true>(p, pl, st) : launch_one<P, S, MTP, MODE_FWD, false>(p, pl, st);
@@ -627,7 +623,7 @@ int launch_mode(const SParams &p, const cdl_strip_plan &pl, int mode, hipStream_
 }
 
 template <int P, int S>
-int launch_mt(const SParams &p, const cdl_strip_plan &pl, int mode, hipStream_t st)
+int launch_mt(const SParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     const int mtp = (pl.MT + 1) / 2;
     if (mtp == 1) return launch_mode<P, S, 1>(p, pl, mode, st);
@@ -636,20 +632,26 @@ int launch_mt(const SParams &p, const cdl_strip_plan &pl, int mode, hipStream_t 
 }
 
 template <int P>
-int launch_s(const SParams &p, const cdl_strip_plan &pl, int mode, hipStream_t st)
+int launch_s(const SParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     return pl.S == 2 ? launch_mt<P, 2>(p, pl, mode, st) : launch_mt<P, 1>(p, pl, mode, st);
 }
 
 template <int P>
-int lds_for(const cdl_strip_plan &pl)
+int lds_for(const cdl_fusedg_plan &pl)
 {
     return pl.S == 2 ? carve<P, 2>(pl.MT, pl.KQ).total : carve<P, 1>(pl.MT, pl.KQ).total;
 }
 
+// one sample's code tensor in CDL_LAY_RSC must stay inside a buffer descriptor's 2^31 bytes
+bool strip_rsc_out_of_range(const cdl_geom *g, const cdl_fusedg_plan &pl)
+{
+    return (size_t)g->M * pl.Hz * pl.nsx * 128 >= ((size_t)1 << 31);
+}
+
 }  // namespace
 
-bool cdl_strip_plan_for(const cdl_geom *g, cdl_strip_plan *pl)
+bool cdl_strip_plan_for(const cdl_geom *g, cdl_fusedg_plan *pl)
 {
     if (!cdl_geom_ok(g)) return false;
     if (g->C != 1 || g->D != 1 || g->Pd != 1 || g->sd != 1 || g->pd != 0) return false;
@@ -657,7 +659,10 @@ bool cdl_strip_plan_for(const cdl_geom *g, cdl_strip_plan *pl)
     if (g->Ph != g->Pw || (g->Ph != 3 && g->Ph != 5 && g->Ph != 7)) return false;
     if (g->ph != g->Ph / 2 || g->pw != g->Pw / 2) return false;
     if (g->M < 8 || g->M > 64 * MAXP) return false;
+    *pl = cdl_fusedg_plan{};
+    pl->kind = CDL_PLAN_STRIP;
     pl->P = g->Ph;
+    pl->G = 1;
     pl->S = g->sh;
     pl->MT = (g->M + 31) / 32;
     pl->KS = (g->Ph * g->Pw + 15) / 16;
@@ -678,31 +683,29 @@ bool cdl_strip_plan_for(const cdl_geom *g, cdl_strip_plan *pl)
     pl->SEG = seg;
     pl->nsy = (pl->Hz + seg - 1) / seg;
     pl->items = (size_t)g->N * pl->nsy * pl->nsx;
+    pl->per_img = (int)(pl->items / g->N);
     const int JM = (pl->P + pl->S - 1) / pl->S;
     pl->prows = seg + JM - 1;
     pl->pxw = 32 + JM - 1;
     pl->frag_uint4 = (size_t)2 * (pl->MT * pl->KS + pl->RT * pl->KQ) * 64;
     pl->patch_floats = pl->items * pl->S * pl->S * pl->prows * pl->pxw;
     pl->map_words = (size_t)g->N * 4 * ((pl->MT + 1) / 2) * pl->Hz * pl->Wz;
-    if ((size_t)g->M * pl->Hz * pl->Wz * 4 >= ((size_t)1 << 31)) return false;        // per-sample buffer descriptor range
+    pl->rsc_floats = (size_t)g->N * g->M * pl->Hz * pl->nsx * 32;
+    // per-sample buffer descriptor range, in the reference's layout and in CDL_LAY_RSC
+    if ((size_t)g->M * pl->Hz * pl->Wz * 4 >= ((size_t)1 << 31) || strip_rsc_out_of_range(g, *pl)) return false;
     if ((size_t)g->H * g->W >= ((size_t)1 << 29) || pl->items >= ((size_t)1 << 30) || g->H > 65535 || g->N > 65535) return false;
     const int lds = pl->P == 3 ? lds_for<3>(*pl) : pl->P == 5 ? lds_for<5>(*pl) : lds_for<7>(*pl);
     return lds <= 160 * 1024;
 }
 
-int cdl_strip_prep_pairs(const cdl_geom *g, const cdl_strip_plan &pl, const float *const *w1, const float *const *w2,
+int cdl_strip_prep_pairs(const cdl_geom *g, const cdl_fusedg_plan &pl, const float *const *w1, const float *const *w2,
                          int K, int shift2, void *frags, hipStream_t st)
 {
     if (!cdl_aligned16(frags)) return CDL_EUNSUPPORTED;      // the library-sized fragment buffer is written 16 bytes at a time (cdlnet_hip.h)
     const int threads = (int)(pl.frag_uint4 / 2);
     for (int k0 = 0; k0 < K; k0 += PREP_BATCH) {
-        const int nb = K - k0 < PREP_BATCH ? K - k0 : PREP_BATCH;
-        PrepBatch b = {};
-        for (int i = 0; i < nb; ++i) {
-            const int k = k0 + i;
-            b.wA[i] = shift2 == 0 ? w1[(k + 1) % K] : w1[k];
-            b.wB[i] = shift2 == 0 ? w2[k] : w2[(k + 1) % K];
-        }
+        PrepBatch b;
+        const int nb = cdl_pair_batch(&b, w1, w2, K, shift2, k0);
         dim3 grid((unsigned)((threads + 255) / 256), (unsigned)nb);
         uint4 *out = reinterpret_cast<uint4 *>(frags) + (size_t)k0 * pl.frag_uint4;
         CDL_TRACE_NOTE("k_prep_s<%d>", pl.P == 3 || pl.P == 5 ? pl.P : 7);
@@ -714,7 +717,7 @@ int cdl_strip_prep_pairs(const cdl_geom *g, const cdl_strip_plan &pl, const floa
     return 0;
 }
 
-int cdl_strip_stage(const cdl_geom *g, const cdl_strip_plan &pl, int mode, const float *r, const float *zin,
+int cdl_strip_stage(const cdl_geom *g, const cdl_fusedg_plan &pl, int mode, const float *r, const float *zin,
                     const float *tau, const void *frags, float sgn, float *zout, float *patches, unsigned *map,
                     float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, hipStream_t st)
 {
@@ -726,23 +729,17 @@ int cdl_strip_stage(const cdl_geom *g, const cdl_strip_plan &pl, int mode, const
     p.N = g->N; p.M = g->M; p.H = g->H; p.W = g->W; p.Hz = pl.Hz; p.Wz = pl.Wz; p.MT = pl.MT; p.KQ = pl.KQ;
     p.nsx = pl.nsx; p.nsy = pl.nsy; p.SEG = pl.SEG; p.prows = pl.prows; p.rev = rev; p.items = (int)pl.items;
     p.lay_in = lay_in; p.lay_out = lay_out;
-    if ((size_t)g->M * pl.Hz * pl.nsx * 128 >= ((size_t)1 << 31)) return CDL_EUNSUPPORTED;
+    if (strip_rsc_out_of_range(g, pl)) return CDL_EUNSUPPORTED;      // cdl_strip_plan_for refuses it; here so that nothing out of range can launch
     CDL_DBG_FIELD(p.dbg = cdl_opts().fused_debug;)
     if (pl.P == 3) return launch_s<3>(p, pl, mode, st);
     if (pl.P == 5) return launch_s<5>(p, pl, mode, st);
     return launch_s<7>(p, pl, mode, st);
 }
 
-size_t cdl_strip_rsc_floats(const cdl_geom *g, const cdl_strip_plan &pl)
-{
-    return (size_t)g->N * g->M * pl.Hz * pl.nsx * 32;
-}
-
-int cdl_strip_assemble(const cdl_geom *g, const cdl_strip_plan &pl, const float *patches, const float *mask,
+int cdl_strip_assemble(const cdl_geom *g, const cdl_fusedg_plan &pl, const float *patches, const float *mask,
                        const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st)
 {
-    // (CDL_SCALAR_ASSEMBLE=1: the scalar form, for tests)
-    const bool v4 = (g->W & 3) == 0 && cdl_aligned16(out, mask, sub, acc) && !cdl_opts().scalar_assemble;
+    const bool v4 = cdl_assemble16(g->W, out, mask, sub, acc);
     dim3 grid((unsigned)(((v4 ? g->W / 4 : g->W) + 255) / 256), (unsigned)g->H, (unsigned)g->N);
 #define CDL_ASM_S(P_, S_)                                                                                                   \
     do {                                                                                                                    \

@@ -2,28 +2,17 @@
 // cdl_stripg.hip: channel / depth groups, unit stride, M <= 64).  Included inside each file's anonymous namespace.
 #pragma once
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+#include "cdl_wave_dev.h"
+
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int NWV = 8;                 // waves per workgroup (they share the weights, nothing else)
 constexpr int NTS = 64 * NWV;
-constexpr int OOB = 0x7fff0000;
 constexpr int MAXP = 3;                // channel-tile pairs: M <= 192
 
-enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
-
-// tap (i, j) -> row of the synthesis-like accumulator tiles (as cdl_fusedg.hip): row t of a 32-row tile sits in
-// register v = 4*((t>>3)&3) + (t&3) of lane half (t>>2)&1
-template <int P> __host__ __device__ constexpr int tap_slot(int i, int j)
-{
-    if (P == 5) return (i < 4 && j < 4) ? 8 * i + j : (i < 4 ? 8 * i + 4 : (j < 4 ? 8 * j + 5 : 6));
-    return 8 * i + j;
-}
 template <int P> struct Shape {
-    static constexpr int RT = (P == 7) ? 2 : 1;
+    static constexpr int RT = TapTiles<P>::RT;
     static constexpr int KS = (P * P + 15) / 16;
     static constexpr int RC = 8;                       // circular rows of the thin buffer (>= P, power of two)
     static constexpr int RBUF = RC + P - 1;            // + mirror rows so that a P-row window never wraps
@@ -35,34 +24,6 @@ template <int P, int S> struct Strip {
     static constexpr int PXW = 32 + JM - 1;            // half-resolution patch columns
     static constexpr int NLD = (S * XW + 63) / 64;     // thin loads per lane and code row
     static constexpr int NPRE = (P - S + S - 1) / S;   // row groups before the first code row's own
-};
-
-__device__ __forceinline__ float wave_shr1(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-
-// (cdl_fusedg.hip) totals of 16 per-lane values over the 32 pixel lanes of each half-wave; lanes c and c ^ 16 end up
-// with the two halves of total #(c mod 16)
-template <int N>
-struct LaneTransposeSum {
-    static __device__ __forceinline__ float run(const float (&v)[N], int c)
-    {
-        constexpr int n = N / 2;
-        const bool up = (c & n) != 0;
-        float w[n];
-#pragma unroll
-        for (int k = 0; k < n; ++k) {
-            const float keep = up ? v[k + n] : v[k];
-            const float send = up ? v[k] : v[k + n];
-            w[k] = keep + __shfl_xor(send, n, 64);
-        }
-        return LaneTransposeSum<n>::run(w, c);
-    }
-};
-template <>
-struct LaneTransposeSum<1> {
-    static __device__ __forceinline__ float run(const float (&v)[1], int) { return v[0]; }
 };
 
 // Epilogue of one channel tile (a plain function, not a closure inside the step: a nested closure kept the accumulator

@@ -502,22 +502,18 @@ __global__ __launch_bounds__(256) void k_assemble_sg(const float *__restrict__ p
 }
 
 template <int P, int G, int MT, int MODE, bool MAPPED>
-int launch_one(const GSParams &p, const cdl_stripg_plan &pl, hipStream_t st)
+int launch_one(const GSParams &p, const cdl_fusedg_plan &pl, hipStream_t st)
 {
     const int lds = gcarve<P>(MT, pl.KS, pl.KQ, G).total;
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_stripg<P, G, MT, MODE, MAPPED>, lds)) return rc;
-    size_t cus = (size_t)cdl_cu_count();
-    const int cap = cdl_opts().fused_grid;
-    if (cap > 0 && (size_t)cap < cus) cus = (size_t)cap;
-    const size_t wgs = (pl.items + NWV - 1) / NWV;
-    const unsigned grid = (unsigned)(wgs < cus ? wgs : cus);
+    const unsigned grid = cdl_persistent_grid((pl.items + NWV - 1) / NWV);
     k_stripg<P, G, MT, MODE, MAPPED><<<grid, NTS, lds, st>>>(p);
     CDL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int P, int G, int MT>
-int launch_mode(const GSParams &p, const cdl_stripg_plan &pl, int mode, hipStream_t st)
+int launch_mode(const GSParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     if (mode == MODE_FWD)
         return p.map ? launch_one<P, G, MT, MODE_FWD, true>(p, pl, st) : launch_one<P, G, MT, MODE_FWD, false>(p, pl, st);
@@ -527,13 +523,13 @@ int launch_mode(const GSParams &p, const cdl_stripg_plan &pl, int mode, hipStrea
 }
 
 template <int P, int G>
-int launch_g(const GSParams &p, const cdl_stripg_plan &pl, int mode, hipStream_t st)
+int launch_g(const GSParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     return pl.MT == 2 ? launch_mode<P, G, 2>(p, pl, mode, st) : launch_mode<P, G, 1>(p, pl, mode, st);
 }
 
 template <int P>
-int launch_p(const GSParams &p, const cdl_stripg_plan &pl, int mode, hipStream_t st)
+int launch_p(const GSParams &p, const cdl_fusedg_plan &pl, int mode, hipStream_t st)
 {
     if (pl.G == 1) return launch_g<P, 1>(p, pl, mode, st);
     if (pl.G == 3) return launch_g<P, 3>(p, pl, mode, st);
@@ -542,27 +538,19 @@ int launch_p(const GSParams &p, const cdl_stripg_plan &pl, int mode, hipStream_t
 }
 
 template <int P>
-int lds_for(const cdl_stripg_plan &pl)
+int lds_for(const cdl_fusedg_plan &pl)
 {
     return gcarve<P>(pl.MT, pl.KS, pl.KQ, pl.G).total;
 }
 
 }  // namespace
 
-bool cdl_stripg_plan_for(const cdl_geom *g, cdl_stripg_plan *pl)
+bool cdl_stripg_plan_for(const cdl_geom *g, cdl_fusedg_plan *pl)
 {
-    if (!cdl_geom_ok(g)) return false;
-    if (g->sd != 1 || g->sh != 1 || g->sw != 1) return false;
-    if (g->Ph != g->Pw || (g->Ph != 3 && g->Ph != 5 && g->Ph != 7)) return false;
-    if ((g->Pd & 1) == 0 || g->pd != g->Pd / 2 || g->ph != g->Ph / 2 || g->pw != g->Pw / 2) return false;
-    if (g->M > 64 || g->M < 8 || (g->M & 7)) return false;             // whole register quads of channels (see k_stripg)
-    pl->P = g->Ph;
-    pl->G = g->C * g->Pd;
-    if (pl->G != 1 && pl->G != 3 && pl->G != 5 && pl->G != 7) return false;
-    if (g->Ph == 7 && pl->G == 7) return false;                          // 49 ring registers
-    pl->MT = (g->M + 31) / 32;
-    pl->KS = (pl->G * g->Ph * g->Pw + 15) / 16;
-    pl->KQ = (g->M + 15) / 16;
+    if (!cdl_grouped_plan_base(g, pl)) return false;
+    pl->kind = CDL_PLAN_STRIPG;
+    pl->Hz = g->H;
+    pl->Wz = g->W;
     pl->nsx = (g->W + 31) / 32;
     // segment length from the SAMPLE's geometry only (never the batch size: cdl_strip.hip); 16 rows when that still gives
     // a sample 256 items, else 8 (ring tails of P - 1 rows must end inside the next segment: >= 8 for P = 7)
@@ -572,17 +560,18 @@ bool cdl_stripg_plan_for(const cdl_geom *g, cdl_stripg_plan *pl)
     pl->SEG = seg;
     pl->nsy = (g->H + seg - 1) / seg;
     pl->items = (size_t)g->N * g->D * pl->nsy * pl->nsx;
+    pl->per_img = (int)(pl->items / g->N);
     pl->prows = seg + g->Ph - 1;
     pl->pxw = 32 + g->Ph - 1;
     pl->patch_floats = pl->items * pl->G * pl->prows * pl->pxw;
-    const size_t vox = (size_t)g->D * g->H * g->W;
-    if ((size_t)g->M * vox * 4 >= ((size_t)1 << 31) || (size_t)g->M * g->D * g->H * pl->nsx * 128 >= ((size_t)1 << 31)) return false;
-    if (pl->items >= ((size_t)1 << 30) || g->H > 65535 || (size_t)g->N * g->C * g->D > 65535) return false;
+    pl->rsc_floats = (size_t)g->N * g->M * g->D * g->H * pl->nsx * 32;
+    if ((size_t)g->M * g->D * g->H * pl->nsx * 128 >= ((size_t)1 << 31)) return false;      // a sample in CDL_LAY_RSC: descriptor range
+    if (pl->items >= ((size_t)1 << 30)) return false;
     const int lds = pl->P == 3 ? lds_for<3>(*pl) : pl->P == 5 ? lds_for<5>(*pl) : lds_for<7>(*pl);
     return lds <= 160 * 1024;
 }
 
-int cdl_stripg_stage(const cdl_geom *g, const cdl_stripg_plan &pl, int mode, const float *r, const float *zin,
+int cdl_stripg_stage(const cdl_geom *g, const cdl_fusedg_plan &pl, int mode, const float *r, const float *zin,
                      const float *tau, const void *frags, float sgn, float *zout, float *patches, unsigned *map,
                      float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, hipStream_t st)
 {
@@ -600,7 +589,7 @@ int cdl_stripg_stage(const cdl_geom *g, const cdl_stripg_plan &pl, int mode, con
     return launch_p<7>(p, pl, mode, st);
 }
 
-int cdl_stripg_assemble(const cdl_geom *g, const cdl_stripg_plan &pl, const float *patches, const float *mask,
+int cdl_stripg_assemble(const cdl_geom *g, const cdl_fusedg_plan &pl, const float *patches, const float *mask,
                         const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st)
 {
     dim3 grid((unsigned)((g->W + 255) / 256), (unsigned)g->H, (unsigned)(g->N * g->C * g->D));
@@ -610,9 +599,4 @@ int cdl_stripg_assemble(const cdl_geom *g, const cdl_stripg_plan &pl, const floa
 #undef CDL_ASM_G
     CDL_LAUNCH_CHECK();
     return 0;
-}
-
-size_t cdl_stripg_rsc_floats(const cdl_geom *g, const cdl_stripg_plan &pl)
-{
-    return (size_t)g->N * g->M * g->D * g->H * pl.nsx * 32;
 }

@@ -1,0 +1,63 @@
+// Device-side pieces shared by the fused kernels (cdl_fused2d.hip, cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip).
+// Included inside each file's anonymous namespace, so every object keeps its own internal copies.
+#pragma once
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+constexpr int OOB = 0x7fff0000;              // byte offset beyond any buffer descriptor range
+
+enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
+
+// ---- tap packing of the synthesis-like GEMM's M dimension (cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip) ---------
+// Row t of a 32-row accumulator tile sits in register v = 4*((t>>3)&3) + (t&3) of lane half h = (t>>2)&1.  The taps
+// (i, j) of a P x P filter plane are assigned rows so that the column-direction col2im is a short static sequence:
+// P = 3, 7: t = 8 i + j (as cdl_fused2d.hip); P = 5: 25 taps packed into ONE 32-row tile (8i + j would need two).
+template <int P> __host__ __device__ constexpr int tap_slot(int i, int j)
+{
+    if (P == 5) return (i < 4 && j < 4) ? 8 * i + j : (i < 4 ? 8 * i + 4 : (j < 4 ? 8 * j + 5 : 6));
+    return 8 * i + j;
+}
+template <int P> struct TapTiles { static constexpr int RT = (P == 7) ? 2 : 1; };     // 32-slot tap tiles
+
+// lane i <- lane i-1 over the whole wave (lane 0 <- 0): one DPP modifier on the consuming add
+__device__ __forceinline__ float wave_shr1(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
+}
+// lanes 0..31 receive the value held by lanes 32..63 (lanes 32..63 receive 0).
+// v_permlane32_swap vdst, src exchanges vdst[32..63] with src[0..31]; with src = 0 the new src is
+// {v.hi, 0}.  Inline asm because hipcc (ROCm 7.2) returns the SAME register for both results of
+// __builtin_amdgcn_permlane32_swap (tools/probes/probe_dpp.hip); s_nop 1 = the two wait states the
+// instruction needs after a VALU write of either operand.
+__device__ __forceinline__ float upper_half_to_lower(float v)
+{
+    float lo = 0.0f;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(v), "+v"(lo));
+    return lo;
+}
+
+// Sum over the 32 pixel lanes of each half-wave of N per-lane values, leaving total #i on lane
+// (c with c mod N == i): a halving butterfly, N-1 exchanges instead of 5N.  Template recursion keeps
+// every register index static.  (N = 16: lanes c and c ^ 16 end up with the two halves of total #(c mod 16).)
+template <int N>
+struct LaneTransposeSum {
+    static __device__ __forceinline__ float run(const float (&v)[N], int c)
+    {
+        constexpr int n = N / 2;
+        const bool up = (c & n) != 0;
+        float w[n];
+#pragma unroll
+        for (int k = 0; k < n; ++k) {
+            const float keep = up ? v[k + n] : v[k];
+            const float send = up ? v[k] : v[k + n];
+            w[k] = keep + __shfl_xor(send, n, 64);
+        }
+        return LaneTransposeSum<n>::run(w, c);
+    }
+};
+template <>
+struct LaneTransposeSum<1> {
+    static __device__ __forceinline__ float run(const float (&v)[1], int) { return v[0]; }
+};
