@@ -7,7 +7,7 @@ from . import _lib, functional, loss, metrics, nle, ops, parallel, train, utils
 from ._lib import HipKernelError, HipLibraryMissing
 from .gabor import ConvAdjoint2dGabor
 from .loss import CombinedLossWithSSIM, load_vgg16_weights
-from .metrics import ssim
+from .metrics import ms_ssim, ssim
 from .net import ST, CDLNet, CDLNet_CSR, CDLNet_CSRf2, CDLNetVideo, GDLNet, ResidualBlock, prox_CSR, prox_CSR_f2
 from .temporal import csr_inference_loop, csr_inference_v2
 from .train import (build_model, fit, init_model, load_ckpt, mcsure_loss, save_args, save_ckpt, sure_loss, sure_loss_clip,
@@ -21,5 +21,5 @@ __all__ = ["CDLNet", "CDLNetVideo", "ResidualBlock", "GDLNet", "JDD_CDLNet", "CD
            "build_model", "init_model", "load_ckpt", "save_ckpt", "train_step", "fit", "mcsure_loss", "sure_loss",
            "sure_loss_clip", "train_step_clip",
            "save_args",
-           "awgn", "awgn3d", "gen_bayer_mask", "psnr", "ssim", "CombinedLossWithSSIM", "load_vgg16_weights", "functional", "loss", "metrics", "nle", "ops", "parallel", "train", "utils",
+           "awgn", "awgn3d", "gen_bayer_mask", "psnr", "ssim", "ms_ssim", "CombinedLossWithSSIM", "load_vgg16_weights", "functional", "loss", "metrics", "nle", "ops", "parallel", "train", "utils",
            "HipLibraryMissing", "HipKernelError"]

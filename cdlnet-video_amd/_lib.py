@@ -71,6 +71,8 @@ SIGNATURES = {
     "cdl_nle_pca_gram_cells": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_bwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_msssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_msssim_bwd": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_vgg_forward": [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_vgg_backward": [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_residual_forward": [_G, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -130,7 +132,8 @@ SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G
                 "cdl_nle_mad_scratch_floats": [_I, _I, _I, _I], "cdl_nle_mad_cells_scratch_floats": [_I, _I, _I, _I],
                 "cdl_nle_pca_scratch_floats": [_I, _I, _I, _I, _I], "cdl_nle_pca_gram_cells_scratch_floats": [_I] * 7,
                 "cdl_residual_scratch_floats": [_G],
-                "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_vgg_scratch_floats": [_I, _I, _I, _I],
+                "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_msssim_pyramid_floats": [_I, _I, _I, _I],
+                "cdl_msssim_scratch_floats": [_I, _I, _I, _I, _I], "cdl_vgg_scratch_floats": [_I, _I, _I, _I],
                 "cdl_trace_read": [_P, ctypes.c_size_t]}
 
 _lib = None

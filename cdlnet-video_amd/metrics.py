@@ -3,6 +3,9 @@
 * `ssim(X, Y, ...)`: pytorch_msssim's `ssim` for (N, C, H, W), differentiable in X, Y and data_range (the SSIM
   term of loss.py's CombinedLossWithSSIM is built on it);
 * `ssim_frames(output, target)`: that term for (N, C, D, H, W) clips, every frame in one launch;
+* `ms_ssim(X, Y, ...)`: pytorch_msssim's `ms_ssim` (multi-scale SSIM) for (N, C, H, W), differentiable in X, Y and
+  data_range; `ms_ssim_frames(output, target)`: mean_t (1 - ms_ssim) of the frames of (N, C, D, H, W) clips, all
+  frames in one pyramid (`cdl_msssim_fwd` / `cdl_msssim_bwd`: the SSIM kernels, two launches per level);
 * `structural_similarity(x, y, ...)`: skimage's `structural_similarity` (analyzemri.py's metric), per plane;
 * `video_ssim(video, denoised)`: analyzemri.py's `ssim_total / frame_count` for one batch, one host sync;
 * `perceptual_frames(output, target, weights)`: the VGG16 relu3_3 perceptual term of CombinedLossWithSSIM for
@@ -128,6 +131,20 @@ def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, K=
     return per_channel.mean() if size_average else per_channel.mean(1)
 
 
+def _frames_range(output, data_range):
+    """data_range of the (n, c, t) planes of a clip (N, C, D, H, W) on the device, (N * C * D,): None is the per-frame
+    max - min of `output`, a number or a tensor broadcastable to (D,) is used as given."""
+    N, C, D = output.shape[:3]
+    if data_range is None:
+        R_t = output.amax(dim=(0, 1, 3, 4)) - output.amin(dim=(0, 1, 3, 4))
+    elif torch.is_tensor(data_range):
+        r = data_range.to(device=output.device, dtype=torch.float32)
+        R_t = r.reshape(()).expand(D) if r.numel() == 1 else r.reshape(D)
+    else:
+        R_t = torch.full((D,), float(data_range), device=output.device, dtype=torch.float32)
+    return R_t.reshape(1, 1, D).expand(N, C, D).contiguous().reshape(-1)
+
+
 def ssim_frames(output, target, data_range=None):
     """The SSIM term of loss.py's CombinedLossWithSSIM for (N, C, D, H, W) clips:
     mean_t (1 - ssim(output[:, :, t], target[:, :, t], data_range=R_t)), pytorch_msssim's defaults otherwise.
@@ -150,18 +167,154 @@ def ssim_frames(output, target, data_range=None):
         raise ValueError(f"ssim_frames expects (N, C, D, H, W), got {tuple(output.shape)}")
     _check_window(11, output.shape[-2], output.shape[-1])
     output, target = ops._dev(output, "output"), ops._dev(target, "target")
-    N, C, D = output.shape[:3]
-    if data_range is None:
-        R_t = output.amax(dim=(0, 1, 3, 4)) - output.amin(dim=(0, 1, 3, 4))
-    elif torch.is_tensor(data_range):
-        r = data_range.to(device=output.device, dtype=torch.float32)
-        R_t = r.reshape(()).expand(D) if r.numel() == 1 else r.reshape(D)
-    else:
-        R_t = torch.full((D,), float(data_range), device=output.device, dtype=torch.float32)
-    R = R_t.reshape(1, 1, D).expand(N, C, D).contiguous().reshape(-1)
+    R = _frames_range(output, data_range)
     per_plane = _plane_ssim(output, target, R, _gaussian_window(11, 1.5), 0.01, 0.03, 1.0)   # (N, C, D)
     ssim_t = per_plane.mean(dim=(0, 1))
     return (1 - ssim_t).mean()
+
+
+# ------------------------------------------------------------------------------ MS-SSIM (pytorch_msssim's ms_ssim)
+MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+_LEVELS_MAX = 8
+
+
+def _level_sizes(H, W, levels):
+    """[(H_i, W_i)] of the pyramid: avg_pool2d(kernel 2, padding [H % 2, W % 2]) halves an axis rounding up."""
+    out = []
+    for _ in range(levels):
+        out.append((H, W))
+        H, W = (H + 1) // 2, (W + 1) // 2
+    return out
+
+
+def _ms_weights(weights):
+    w = list(MS_WEIGHTS) if weights is None else [float(v) for v in weights]
+    if not 1 <= len(w) <= _LEVELS_MAX:
+        raise ValueError(f"weights: expected 1 to {_LEVELS_MAX} levels, got {len(w)}")
+    return w
+
+
+def _check_pyramid(win_size, H, W, levels):
+    _check_window(win_size, H, W)
+    h, w = _level_sizes(H, W, levels)[-1]
+    if min(h, w) < win_size:
+        raise ValueError(f"image {H} x {W}: level {levels - 1} of the pyramid is {h} x {w}, smaller than win_size "
+                         f"{win_size}; the smaller side should be larger than (win_size - 1) * 2**{levels - 1} = "
+                         f"{(win_size - 1) * 2 ** (levels - 1)}")
+
+
+class _MSSSIMPlanes(torch.autograd.Function):
+    """(x, y, R) of P planes (P, H, W), R (P,) -> the (levels, P, 2) table of the raw per-plane means (ssim_i, cs_i) of
+    every level of the 2x2 average-pooling pyramid.  Saves the pooled planes of both sides (a third of the input
+    again) for the backward, which takes the gradient of the whole table."""
+
+    @staticmethod
+    def forward(ctx, x, y, R, win, K1, K2, levels):
+        P, H, W = x.shape
+        if R.shape != (P,):
+            raise ValueError(f"data_range: expected one value per plane, shape ({P},), got {tuple(R.shape)}")
+        R = R.contiguous()
+        lib = _lib.lib()
+        n = int(lib.cdl_msssim_scratch_floats(P, H, W, len(win), levels))
+        if n == 0:
+            raise ValueError(f"ms_ssim: {levels} levels of {H} x {W} planes with a {len(win)}-tap window not supported")
+        npyr = int(lib.cdl_msssim_pyramid_floats(P, H, W, levels))
+        scratch = ops._scratch(x.device, n)
+        pyr_x = torch.empty(npyr, device=x.device, dtype=torch.float32) if levels > 1 else None
+        pyr_y = torch.empty(npyr, device=x.device, dtype=torch.float32) if levels > 1 else None
+        vals = torch.empty((levels, P, 2), device=x.device, dtype=torch.float32)
+        ops._call("cdl_msssim_fwd", x, y, P, H, W, _window_arg(win), len(win), K1, K2, R, levels, pyr_x, pyr_y, vals,
+                  scratch, n)
+        ctx.save_for_backward(x, y, R, pyr_x, pyr_y)
+        ctx.args = (win, K1, K2, levels, npyr)
+        return vals
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, y, R, pyr_x, pyr_y = ctx.saved_tensors
+        win, K1, K2, levels, npyr = ctx.args
+        nx, ny, nr = ctx.needs_input_grad[:3]
+        if not (nx or ny or nr):
+            return (None,) * 7
+        P, H, W = x.shape
+        g = g.to(torch.float32).contiguous()
+        dx = torch.empty_like(x) if nx else None
+        dy = torch.empty_like(y) if ny else None
+        dr = torch.empty(P, device=x.device, dtype=torch.float32) if nr else None
+        work = torch.empty(2 * npyr, device=x.device, dtype=torch.float32) if levels > 1 and (nx or ny) else None
+        n = int(_lib.lib().cdl_msssim_scratch_floats(P, H, W, len(win), levels))
+        scratch = ops._scratch(x.device, n)
+        ops._call("cdl_msssim_bwd", x, y, pyr_x, pyr_y, P, H, W, _window_arg(win), len(win), K1, K2, R, levels, g, dx, dy,
+                  dr, work, scratch, n)
+        return dx, dy, dr, None, None, None, None
+
+
+def _plane_ms_ssim(x, y, R, win, K1, K2, weights):
+    """x, y (..., H, W) device float32, R (P,) -> per-plane MS-SSIM shaped like the leading dims.  The combination is
+    pytorch_msssim's, in torch ops on the (levels, P) means: relu, powers, product -- the product as L - 1
+    multiplications in level order, because torch.prod's backward counts zeros on the host (a synchronisation)."""
+    lead, (H, W) = x.shape[:-2], x.shape[-2:]
+    P = math.prod(lead)
+    L = len(weights)
+    with torch.cuda.device(x.device):
+        vals = _MSSSIMPlanes.apply(x.reshape(P, H, W), y.reshape(P, H, W), R, win, float(K1), float(K2), L)
+    v = torch.relu(torch.cat([vals[:-1, :, 1], vals[-1:, :, 0]]))               # cs of the finer levels, ssim of the last
+    ms = v[0] ** weights[0]
+    for i in range(1, L):
+        ms = ms * v[i] ** weights[i]
+    return ms.reshape(lead)
+
+
+def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
+    """pytorch_msssim.ms_ssim for 4-D (N, C, H, W) input: with L = len(weights) levels (default
+    [0.0448, 0.2856, 0.3001, 0.2363, 0.1333]), level i + 1 = avg_pool2d(level i, 2, padding=[H_i % 2, W_i % 2]),
+        ms = prod_i relu(v_i) ** weights_i,   v_i = cs mean of level i for i < L - 1, SSIM mean of level L - 1,
+    per (n, c); returns ms.mean(), or ms.mean(1) per image when size_average=False.  Differentiable (once) in X, Y and
+    data_range (a python number or a tensor).  `weights`: a sequence of python numbers (or a CPU tensor).
+
+    Raised before any device work: the refusals of `ssim` (a side smaller than the window, 5-D input -- per-frame
+    MS-SSIM of (N, C, D, H, W) clips is `ms_ssim_frames`), and ValueError when the coarsest level's smaller side is below
+    win_size.  For five levels that is exactly pytorch_msssim's assertion `smaller_side > (win_size - 1) * 2**4`: an axis
+    of length s has ceil(s / 2**k) pixels at level k, and ceil(s / 2**k) >= win_size is s > (win_size - 1) * 2**k; the
+    same rule is applied for any number of levels (1 to 8).
+    """
+    if not (torch.is_tensor(X) and torch.is_tensor(Y)):
+        raise TypeError("ms_ssim: expected tensors")
+    if X.shape != Y.shape:
+        raise ValueError(f"input images should have the same dimensions, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if X.dim() == 5:
+        raise NotImplementedError("ms_ssim takes (N, C, H, W); pytorch_msssim's 3-D window for 5-D input is not "
+                                  "implemented -- for the per-frame MS-SSIM of (N, C, D, H, W) clips use ms_ssim_frames")
+    if X.dim() != 4:
+        raise ValueError(f"expected 4-D (N, C, H, W) input, got {tuple(X.shape)}")
+    weights = _ms_weights(weights)
+    _check_pyramid(win_size, X.shape[-2], X.shape[-1], len(weights))
+    X, Y = ops._dev(X, "X"), ops._dev(Y, "Y")
+    N, C = X.shape[:2]
+    R = _planes_range(data_range, N * C, X)
+    ms = _plane_ms_ssim(X, Y, R, _gaussian_window(win_size, win_sigma), K[0], K[1], weights)    # (N, C)
+    return ms.mean() if size_average else ms.mean(1)
+
+
+def ms_ssim_frames(output, target, data_range=None, weights=None):
+    """mean_t (1 - ms_ssim(output[:, :, t], target[:, :, t], data_range=R_t)) for (N, C, D, H, W) clips, pytorch_msssim's
+    defaults otherwise: the multi-scale sibling of `ssim_frames`, with its data_range semantics (None: R_t =
+    output[:, :, t].max() - output[:, :, t].min(); a number or a tensor broadcastable to (D,) is used as given).  All
+    N * C * D planes go through one pyramid, with no host synchronisation."""
+    if not (torch.is_tensor(output) and torch.is_tensor(target)):
+        raise TypeError("ms_ssim_frames: expected tensors")
+    if output.shape != target.shape:
+        raise ValueError(f"input clips should have the same dimensions, got {tuple(output.shape)} and "
+                         f"{tuple(target.shape)}")
+    if output.dim() != 5:
+        raise ValueError(f"ms_ssim_frames expects (N, C, D, H, W), got {tuple(output.shape)}")
+    weights = _ms_weights(weights)
+    _check_pyramid(11, output.shape[-2], output.shape[-1], len(weights))
+    output, target = ops._dev(output, "output"), ops._dev(target, "target")
+    R = _frames_range(output, data_range)
+    ms = _plane_ms_ssim(output, target, R, _gaussian_window(11, 1.5), 0.01, 0.03, weights)        # (N, C, D)
+    return (1 - ms.mean(dim=(0, 1))).mean()
 
 
 # ------------------------------------------------------------------------------ perceptual term (VGG16 relu3_3)

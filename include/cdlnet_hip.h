@@ -393,6 +393,33 @@ int cdl_ssim_bwd(const float *x, const float *y, int P, int H, int W, const floa
                  float *dx /*nullable*/, float *dy /*nullable*/, float *d_range /*P, nullable*/, float *scratch,
                  size_t scratch_floats, void *stream);
 
+/* ---- MS-SSIM (pytorch_msssim's ms_ssim): the SSIM kernels above over a 2x2 average-pooling pyramid ---------------
+ * Level 0 is the caller's P planes of H x W; level i + 1 is torch's avg_pool2d(level i, 2, padding = [H_i % 2, W_i % 2])
+ * (count_include_pad: an odd axis gets one zero row / column in FRONT and the divisor stays 4), H_{i+1} = (H_i + 1) / 2.
+ * kappa is 1; win, taps, K1, K2, data_range as above, the same at every level.
+ * cdl_msssim_pyramid_floats: floats of the levels 1 .. levels-1 of P planes, stored back to back (0: levels outside
+ * 1..8, or a level below 3 x 3).  cdl_msssim_scratch_floats: the scratch of both calls (0: taps not supported, levels
+ * outside 1..8, or a level smaller than the window).
+ * cdl_msssim_fwd: one call for the whole pyramid, two launches per level.  Writes vals[level][plane] = {mean of S, mean
+ * of cs} (raw: the relu, the powers and the product of ms_ssim stay with the caller) and, for levels > 1, the pooled
+ * planes pyr_x, pyr_y (cdl_msssim_pyramid_floats each; the level's own forward launch writes the next level).
+ * cdl_msssim_bwd: g_vals[level][plane] = upstream gradients of {S mean, cs mean}; writes dx, dy (H x W planes) and the
+ * per-plane dL/dR summed over the levels, each nullable, at least one given.  Coarsest level first, one launch per level
+ * (two when d_range is given); a level's dx, dy land in `work` (2 x cdl_msssim_pyramid_floats floats, x side first;
+ * needed when levels > 1 and dx or dy is given) and the next finer level adds a quarter of them to its own pixels.
+ * Deterministic like the calls above.  CDL_EINVAL before any launch: a null pointer that is needed, a window that does
+ * not sum to 1, a scratch shorter than cdl_msssim_scratch_floats, a shape that function refuses.  pyr_*, vals and work
+ * are caller tensors: 4-byte alignment is enough. */
+size_t cdl_msssim_pyramid_floats(int P, int H, int W, int levels);
+size_t cdl_msssim_scratch_floats(int P, int H, int W, int taps, int levels);
+int cdl_msssim_fwd(const float *x, const float *y, int P, int H, int W, const float *win /*host, taps*/, int taps,
+                   float K1, float K2, const float *data_range /*P*/, int levels, float *pyr_x, float *pyr_y,
+                   float *vals /*levels x P x 2*/, float *scratch, size_t scratch_floats, void *stream);
+int cdl_msssim_bwd(const float *x, const float *y, const float *pyr_x, const float *pyr_y, int P, int H, int W,
+                   const float *win /*host, taps*/, int taps, float K1, float K2, const float *data_range /*P*/,
+                   int levels, const float *g_vals /*levels x P x 2*/, float *dx /*nullable*/, float *dy /*nullable*/,
+                   float *d_range /*P, nullable*/, float *work, float *scratch, size_t scratch_floats, void *stream);
+
 /* ---- perceptual term of loss.py's CombinedLossWithSSIM: VGG16 features[:16] (relu3_3) -------------------------
  * P independent contiguous one-channel H x W planes (H, W >= 4) of the output x and the target y; every frame is the
  * reference's three-channel repeat, so conv1_1 runs on the filters summed over their input channels.  The seven
