@@ -360,6 +360,35 @@ def _no_data_gradients(ctx, names=((0, "y"), (1, "mask"), (2, "sigma"))):
                                       f"(the HIP reverse sweep returns parameter gradients only); detach() it")
 
 
+def _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, want_codes):
+    """The tier choice and the forward sweep of one pre-processed batch: (xp, z, codes, resid, maps).  `ctx` (an autograd
+    context, or any namespace carrying `exact`) receives what the reverse sweep reads: is_map, fused, fusedg and, on the
+    fused tiers, layout / precision.  UnrolledISTA.forward and run_windows both go through here, so a window takes
+    exactly the tier a sample of its geometry takes."""
+    K, N, M = len(A), g.N, g.M
+    # a noise-level map (dense (N,1,*code grid), net._noise_scale): tau holds t[k,0,m] for every sample and the generic
+    # sweeps form tau + c[n,pix] * t[k,1,m] in their shrinkage epilogues
+    ctx.is_map = c is not None and c.dim() > 1
+    cmap = c if ctx.is_map else None
+    tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
+    tau = ops.thresholds(t, None if ctx.is_map else c, N)
+    auto = BACKEND == "auto" and not ctx.exact     # "fp32": the fused kernels are matrix-core kernels
+    auto = auto and not ctx.is_map                 # the fused kernels read tau[n,m]: a map runs the generic sweep
+    ctx.fused = auto and ops.fused_supported(g)
+    ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
+    if ctx.fusedg:
+        # codes handed to the caller (forward_generator) must be (N,M,..); otherwise they stay in the sweeps' layout
+        ctx.layout = "nchw" if want_codes else ops.fusedg_code_layout(g, training=keep)
+        return _forward_fusedg(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
+    if ctx.fused:
+        # codes handed to the caller (forward_generator) must be (N,M,H,W); otherwise they stay internal
+        ctx.layout = "nchw" if want_codes else CODE_LAYOUT
+        ctx.precision = PRECISION                  # the reverse sweep runs in the forward's arithmetic
+        return _forward_fused(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
+    return _forward_generic(g, yp, mask_p, tau, A, B, keep or want_codes, keep,
+                            **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
+
+
 @_arithmetic_aware
 class UnrolledISTA(torch.autograd.Function):
     """(y, mask, c, t, A_0..A_{K-1}, B_0..B_{K-1}) -> (xhat, z_K[, z_1..z_{K-1}])."""
@@ -371,13 +400,6 @@ class UnrolledISTA(torch.autograd.Function):
         s = cfg["s"]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
         g = _sweep_geometry(yp, A, s)
-        N, M = g.N, g.M
-        # a noise-level map (dense (N,1,*code grid), net._noise_scale): tau holds t[k,0,m] for every sample and the generic
-        # sweeps form tau + c[n,pix] * t[k,1,m] in their shrinkage epilogues
-        ctx.is_map = c is not None and c.dim() > 1
-        cmap = c if ctx.is_map else None
-        tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
-        tau = ops.thresholds(t, None if ctx.is_map else c, N)
 
         ctx.set_materialize_grads(False)          # an unused z output must not cost a fat zero tensor
         _no_data_gradients(ctx, ((1, "mask"),))   # y and sigma (through c): dL/dyp and dtau from the sweeps
@@ -385,22 +407,7 @@ class UnrolledISTA(torch.autograd.Function):
         ctx.want_y = ctx.needs_input_grad[0]
         ctx.want_c = ctx.needs_input_grad[2] and c is not None
         want_codes = cfg.get("all_codes", False)
-        auto = BACKEND == "auto" and not ctx.exact     # "fp32": the fused kernels are matrix-core kernels
-        auto = auto and not ctx.is_map                 # the fused kernels read tau[n,m]: a map runs the generic sweep
-        ctx.fused = auto and ops.fused_supported(g)
-        ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
-        if ctx.fusedg:
-            # codes handed to the caller (forward_generator) must be (N,M,..); otherwise they stay in the sweeps' layout
-            ctx.layout = "nchw" if want_codes else ops.fusedg_code_layout(g, training=keep)
-            xp, z, codes, resid, maps = _forward_fusedg(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
-        elif ctx.fused:
-            # codes handed to the caller (forward_generator) must be (N,M,H,W); otherwise they stay internal
-            ctx.layout = "nchw" if want_codes else CODE_LAYOUT
-            ctx.precision = PRECISION                  # the reverse sweep runs in the forward's arithmetic
-            xp, z, codes, resid, maps = _forward_fused(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
-        else:
-            xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, keep or want_codes, keep,
-                                                         **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
+        xp, z, codes, resid, maps = _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, want_codes)
         xhat = ops.postprocess(xp, mean, pads)
 
         ctx.geom, ctx.pads, ctx.K = g, pads, K
@@ -1046,3 +1053,39 @@ def run(y, mask, c, t, A, B, s, all_codes=False):
     """Convenience front end used by the modules."""
     cfg = {"K": len(A), "s": int(s), "all_codes": bool(all_codes)}
     return UnrolledISTA.apply(y, mask, c, t, cfg, *A, *B)
+
+
+def run_windows(yp, mask_p, c, t, A, B, s, plan, *, blend="crop", max_batch=None, sweep=None):
+    """Inference on a PRE-PROCESSED frame cut into the windows of `plan` (windowed.plan_windows):
+    xp, shaped like yp.  The windows -- one shape per plan -- are stacked along the batch axis, at most `max_batch`
+    (sample, window) pairs per sweep (None: all of them), each batch runs the forward sweep of the tier its geometry takes
+    (_forward_sweep: what a sample of that shape takes in UnrolledISTA), and the results are cropped to their cores or
+    cross-faded into xp (`blend`: windowed.Plan.assemble).  c: None, one level per sample (N,), or a map (N,1,*code grid),
+    which is cropped with its window.  No autograd graph is built.
+    `sweep(yp_w, mask_w, c_w) -> xp_w` replaces the device sweep (t, A, B are then not read): the planner and the assembly
+    against a restatement of the loop, on the CPU."""
+    N = yp.shape[0]
+    if sweep is None:
+        def sweep(yp_w, mask_w, c_w):
+            st = types.SimpleNamespace(exact=PRECISION == "fp32")
+            with ops.exact_fp32(st.exact):
+                return _forward_sweep(st, _sweep_geometry(yp_w, A, s), yp_w, mask_w, c_w, t, A, B, False, False)[0]
+    is_map = c is not None and c.dim() > 1
+    with torch.no_grad():
+        if len(plan.windows) == 1 and (max_batch is None or max_batch >= N):      # the frame itself: nothing to copy
+            return sweep(yp, mask_p, c)
+        pairs = [(w, n) for w in range(len(plan.windows)) for n in range(N)]
+        step = len(pairs) if max_batch is None else max(1, int(max_batch))
+        outs = [[None] * N for _ in plan.windows]
+        for i in range(0, len(pairs), step):
+            group = pairs[i:i + step]
+            yp_w = plan.gather(yp, group)
+            mask_w = plan.gather(mask_p, group) if mask_p is not None else None
+            if is_map:
+                c_w = plan.gather(c, group, scale=s)
+            else:
+                c_w = c[[n for _, n in group]].contiguous() if c is not None else None
+            xp_w = sweep(yp_w, mask_w, c_w)
+            for j, (w, n) in enumerate(group):
+                outs[w][n] = xp_w[j:j + 1]
+        return plan.assemble([torch.cat(per_sample, 0) for per_sample in outs], blend)
