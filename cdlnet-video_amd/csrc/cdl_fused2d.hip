@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "cdl_common.h"
+#include "cdl_fused_sweep.h"
 
 // Two tile shapes, one template argument.  Everything that works on the stage's tiles takes WY, the wave rows per workgroup
 // (Shape<WY> below): WY = 2 is the shape described above and the one every step-wise entry point uses; WY = 4 is rounds
@@ -1785,32 +1786,19 @@ int forward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask, 
                   unsigned *const *maps, float *xp, void *frags, float *patches, const Flags &f, void *stream)
 {
     const size_t nm = (size_t)g->N * g->M;
-    const int snake = snake_enabled();
     const int L = f.lin;
-    const float *thin = yp;
-    const size_t fb = cdl_fused2d_frag_bytes(g->M);
     int rc = prep_pairs(wA, wB, K, 1, frags, g->M, g->Ph, S(stream));       // (A_k, B_{k+1}) for every k, one launch
     if (rc) return rc;
-    for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        {
-            TimingScope ts(k ? 0 : 3, S(stream));
-            rc = iter_fwd<WY>(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k],
-                              patches, maps ? maps[k] : nullptr,
-                              f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(k == K - 1 ? LAY_NCHW : L) |
-                                  ((k & 1) && snake ? CDL_TILES_REVERSED : 0),
-                              stream);
-        }
-        if (rc) return rc;
-        if (k < K - 1) {
-            rc = assemble<WY>(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
-            thin = r[k];
-        } else {
-            rc = assemble<WY>(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return cdl_forward_order_sweep(
+        K, frags, cdl_fused2d_frag_bytes(g->M), yp, mask, yp, 1.0f, r, xp, snake_enabled(), L, LAY_NCHW,
+        [&](int k, const void *fk, const float *thin, bool reversed, int, int lay_out) {
+            TimingScope ts(k ? 0 : 3, S(stream));               // (the input layout is L at k = 0 too, where no code is read)
+            return iter_fwd<WY>(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k], patches, maps ? maps[k] : nullptr,
+                                f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(lay_out) | (reversed ? CDL_TILES_REVERSED : 0), stream);
+        },
+        [&](const float *m, const float *sub, float alpha, float *out) {
+            return assemble<WY>(g, patches, m, sub, alpha, out, nullptr, 0, stream);
+        });
 }
 
 template <int WY>
@@ -1902,28 +1890,18 @@ int tangent_sweep(const cdl_geom *g, int K, const float *vp, const float *nvp, c
                   float *const *nrd, float *xdp, void *frags, float *patches, float *dtau_partial, const Flags &f,
                   void *stream)
 {
-    const int snake = snake_enabled();
-    const int L = f.lin;
-    const float *thin = vp;
-    const size_t fb = cdl_fused2d_frag_bytes(g->M);
     int rc = prep_pairs(wA, wB, K, 1, frags, g->M, g->Ph, S(stream));       // (A_k, B_{k+1}), the forward's pairs
     if (rc) return rc;
-    for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * fb;
-        rc = stage_bwd<WY>(g, thin, k ? zd[k - 1] : nullptr, maps[k], fk, zd[k], patches, dtau_partial, 1,
-                           f.prec | CDL_LAYOUT_IN(k ? L : LAY_NCHW) | CDL_LAYOUT_OUT(k == K - 1 ? LAY_NCHW : L) |
-                               ((k & 1) && snake ? CDL_TILES_REVERSED : 0),
-                           nullptr, 0.0f, nullptr, nullptr, stream);
-        if (rc) return rc;
-        if (k < K - 1) {
-            rc = assemble<WY>(g, patches, mask, nvp, -1.0f, nrd[k], nullptr, 0, stream);
-            thin = nrd[k];
-        } else {
-            rc = assemble<WY>(g, patches, nullptr, nullptr, 1.0f, xdp, nullptr, 0, stream);
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return cdl_forward_order_sweep(
+        K, frags, cdl_fused2d_frag_bytes(g->M), vp, mask, nvp, -1.0f, nrd, xdp, snake_enabled(), f.lin, LAY_NCHW,
+        [&](int k, const void *fk, const float *thin, bool reversed, int lay_in, int lay_out) {
+            return stage_bwd<WY>(g, thin, k ? zd[k - 1] : nullptr, maps[k], fk, zd[k], patches, dtau_partial, 1,
+                                 f.prec | CDL_LAYOUT_IN(lay_in) | CDL_LAYOUT_OUT(lay_out) | (reversed ? CDL_TILES_REVERSED : 0),
+                                 nullptr, 0.0f, nullptr, nullptr, stream);
+        },
+        [&](const float *m, const float *sub, float alpha, float *out) {
+            return assemble<WY>(g, patches, m, sub, alpha, out, nullptr, 0, stream);
+        });
 }
 
 }  // namespace

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "cdl_common.h"
+#include "cdl_fused_sweep.h"
 #include "cdl_strip.h"
 
 namespace {
@@ -1118,27 +1119,20 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
     if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !tau || !wA || !wB || !z || !xp || !frags || !patches || (K > 1 && !r)) return CDL_EINVAL;
     const size_t nm = (size_t)g->N * g->M;
-    const int snake = cdl_opts().fused_snake;
-    const float *thin = yp;
     int rc = prep(g, pl, wA, wB, K, 1, frags, S(stream));             // (A_k, B_{k+1}) for every k
     if (rc) return rc;
     int lay;                                                 // of z[0..K-2]; z[K-1] is always the reference's (N,M,..) layout
     if (!sweep_layout(pl, precision, true, &lay)) return CDL_EINVAL;
-    for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * pl.frag_uint4 * 16;
-        rc = stage(g, pl, k ? MODE_FWD : MODE_FIRST, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k],
-                   patches, maps ? maps[k] : nullptr, nullptr, 1,
-                   sweep_flags(pl, precision, (k & 1) && snake, k ? lay : CDL_LAY_NCHW, k < K - 1 ? lay : CDL_LAY_NCHW), S(stream));
-        if (rc) return rc;
-        if (k < K - 1) {
-            rc = cdl_fusedg_assemble(g, patches, mask, yp, 1.0f, r[k], nullptr, 0, stream);
-            thin = r[k];
-        } else {
-            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, xp, nullptr, 0, stream);
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return cdl_forward_order_sweep(
+        K, frags, pl.frag_uint4 * 16, yp, mask, yp, 1.0f, r, xp, cdl_opts().fused_snake, lay, CDL_LAY_NCHW,
+        [&](int k, const void *fk, const float *thin, bool reversed, int lay_in, int lay_out) {
+            return stage(g, pl, k ? MODE_FWD : MODE_FIRST, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f,
+                         z[k], patches, maps ? maps[k] : nullptr, nullptr, 1,
+                         sweep_flags(pl, precision, reversed, lay_in, lay_out), S(stream));
+        },
+        [&](const float *m, const float *sub, float alpha, float *out) {
+            return cdl_fusedg_assemble(g, patches, m, sub, alpha, out, nullptr, 0, stream);
+        });
 }
 
 /* Forward-mode tangent sweep at the primal's supports: the reverse stage with the FORWARD's prepared
@@ -1155,25 +1149,18 @@ int cdl_fusedg_tangent(const cdl_geom *g, int K, const float *vp, const float *n
     if (K < 1 || !vp || !nvp || !wA || !wB || !maps || !zd || !xdp || !frags || !patches || !dtau_partial || (K > 1 && !nrd))
         return CDL_EINVAL;
     if ((precision >> 5) != 0) return CDL_EINVAL;             // CDL_LAY_NCHW codes only
-    const int snake = cdl_opts().fused_snake;
     int rc = prep(g, pl, wA, wB, K, 1, frags, S(stream));             // (A_k, B_{k+1}), the forward's pairs
     if (rc) return rc;
-    const float *thin = vp;
-    for (int k = 0; k < K; ++k) {
-        const void *fk = static_cast<const char *>(frags) + (size_t)k * pl.frag_uint4 * 16;
-        rc = stage(g, pl, MODE_BWD, thin, k ? zd[k - 1] : nullptr, nullptr, fk, 1.0f, zd[k], patches,
-                   const_cast<unsigned *>(maps[k]), dtau_partial, 1,
-                   sweep_flags(pl, precision, (k & 1) && snake, CDL_LAY_NCHW, CDL_LAY_NCHW), S(stream));
-        if (rc) return rc;
-        if (k < K - 1) {
-            rc = cdl_fusedg_assemble(g, patches, mask, nvp, -1.0f, nrd[k], nullptr, 0, stream);
-            thin = nrd[k];
-        } else {
-            rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, xdp, nullptr, 0, stream);
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return cdl_forward_order_sweep(
+        K, frags, pl.frag_uint4 * 16, vp, mask, nvp, -1.0f, nrd, xdp, cdl_opts().fused_snake, CDL_LAY_NCHW, CDL_LAY_NCHW,
+        [&](int k, const void *fk, const float *thin, bool reversed, int lay_in, int lay_out) {
+            return stage(g, pl, MODE_BWD, thin, k ? zd[k - 1] : nullptr, nullptr, fk, 1.0f, zd[k], patches,
+                         const_cast<unsigned *>(maps[k]), dtau_partial, 1, sweep_flags(pl, precision, reversed, lay_in, lay_out),
+                         S(stream));
+        },
+        [&](const float *m, const float *sub, float alpha, float *out) {
+            return cdl_fusedg_assemble(g, patches, m, sub, alpha, out, nullptr, 0, stream);
+        });
 }
 
 /* Reverse sweep: the fused stage produces du_k (one fat write), the threshold partials and the patches of q_k; the

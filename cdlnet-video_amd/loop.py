@@ -22,6 +22,7 @@ With a noise-level map c[n,pix] (a dense (N,1,*code grid) tensor; DESIGN.md sect
     dL/dy   = cdl_preprocess_bwd(dL/dyp, dL/dxhat)  (reflect pad adjoint and the mean)
 The gradient with respect to the mask is not produced (it needs mask * B_k z_k at masked-out pixels).
 """
+import collections
 import types
 
 import torch
@@ -144,6 +145,26 @@ def _sweep_geometry(yp, A, s):
                              [s] * (yp.dim() - 2))
 
 
+def _map_args(c, t):
+    """(cmap, tslope): a noise-level map c -- a dense (N,1,*code grid) tensor (net._noise_scale) -- and the slopes t[:,1]
+    as (K,M), what the generic sweeps read beside tau = t[k,0,m]; (None, None) for one level per sample, or none."""
+    if c is None or c.dim() <= 1:
+        return None, None
+    return c, t.detach().reshape(t.shape[0], 2, t.shape[2])[:, 1].contiguous()
+
+
+def _zero_grads(A, B):
+    """The filter gradients of a reverse sweep that got no upstream gradient."""
+    return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+
+
+def _add_sweeps(first, second):
+    """(dA, dB) of two reverse sweeps of one node, summed; `first` is (None, None) where only the second ran."""
+    if first[0] is None:
+        return second
+    return tuple([a + b for a, b in zip(x, y)] for x, y in zip(first, second))
+
+
 def _forward_generic(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, cmap=None, tslope=None):
     """Whole sweep from one C call (cdl_ista_forward): same launches as the stepwise form below.  cmap (N,1,*code grid)
     with tslope (K,M): the noise-level map; tau then holds t[k,0,m]."""
@@ -170,14 +191,15 @@ def _forward_generic_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, 
     return xp, z, codes, resid, []
 
 
-def _forward_fused(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout=None):
+def _forward_fused(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout=None, *, keep_maps=False):
     """The whole sweep from one C call (cdl_fused2d_forward): per iteration one fused launch + a thin
     assemble, enqueued back to back with no per-launch host work.  codes[:-1] come back in `layout`
-    (default CODE_LAYOUT), codes[-1] = z_K as (N,M,H,W)."""
+    (default CODE_LAYOUT), codes[-1] = z_K as (N,M,H,W).  keep_maps: the bit maps although nothing is kept (what a
+    tangent sweep needs of the primal)."""
     keep = keep_codes or keep_resid
     xp, z, codes, resid, maps = ops.fused_forward(g, yp, mask_p, tau, A, B, keep, PRECISION,
-                                                  layout or CODE_LAYOUT)
-    return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid else [])
+                                                  layout or CODE_LAYOUT, keep_maps=keep_maps)
+    return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid or keep_maps else [])
 
 
 def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw"):
@@ -203,20 +225,21 @@ def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, la
     return xp, z, codes, resid, maps
 
 
-def _forward_fusedg(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw"):
+def _forward_fusedg(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw", *, keep_maps=False):
     """cdl_fusedg_forward: the fused iteration for C > 1 / 3-D / P in {3,5,7} / M <= 64, and (the strip kernel) for one
     image channel, stride 1 / 2, M <= 192: one fused launch + a thin assemble per iteration.  codes[:-1] come back in
-    `layout` ("nchw", or "rsc" where ops.fusedg_code_layout(g) says so), codes[-1] = z_K as (N,M,..)."""
+    `layout` ("nchw", or "rsc" where ops.fusedg_code_layout(g) says so), codes[-1] = z_K as (N,M,..).  keep_maps: as
+    _forward_fused's."""
     keep = keep_codes or keep_resid
-    xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, layout)
-    return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid else [])
+    xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, layout, keep_maps=keep_maps)
+    return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid or keep_maps else [])
 
 
 def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw", dyp=None, dtau=None):
     """cdl_fusedg_backward: per iteration one fused reverse stage (du_k, threshold partials, patches of q_k), a thin
     assemble and the two filter gradients.  `layout`: that of codes[:-1]."""
     if g_xp is None and g_z is None:
-        return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+        return _zero_grads(A, B)
     return ops.fusedg_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
                                maps=list(maps) if maps else None, layout=layout, dyp=dyp, dtau=dtau)
 
@@ -226,7 +249,7 @@ def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, ma
     """Reverse sweep from one C call (cdl_ista_backward; dyp / dtau: see ops.fused_backward).  cmap / tslope: the noise-level
     map of the forward in place of c (then None, as dtau); dcmap (nullable) receives dL/dcmap."""
     if g_xp is None and g_z is None:
-        return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+        return _zero_grads(A, B)
     return ops.ista_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt, dyp=dyp,
                              dtau=dtau, cmap=cmap, tslope=tslope, dcmap=dcmap)
 
@@ -297,7 +320,7 @@ def _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps
     the 2-bit map of z_{k+1}, 1 fat write; dA_k rides in it), a thin assemble, one MFMA filter-gradient launch (dB_k: 1 fat
     read) and one launch that reduces dA_k, dB_k and dt[k].  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1]."""
     if g_xp is None and g_z is None:
-        return [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+        return _zero_grads(A, B)
     return ops.fused_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
                               precision or PRECISION, maps=list(maps) if maps else None, layout=layout or CODE_LAYOUT,
                               dyp=dyp, dtau=dtau)
@@ -338,6 +361,7 @@ def _arithmetic_aware(cls):
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *args):
+        _queued[0] = False                        # a backward pass that raised after queueing its end must not mute the next
         ctx.exact = PRECISION == "fp32"
         with ops.exact_fp32(ctx.exact):
             return fwd(ctx, *args)
@@ -360,33 +384,102 @@ def _no_data_gradients(ctx, names=((0, "y"), (1, "mask"), (2, "sigma"))):
                                       f"(the HIP reverse sweep returns parameter gradients only); detach() it")
 
 
-def _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, want_codes):
+def _route(g, exact, is_map):
+    """The tier of a sweep: "fused" (the 2-D MFMA kernels), "fusedg" (the tile / strip kernels) or "generic".  The fused
+    tiers are matrix-core kernels that read tau[n,m]: the "fp32" arithmetic (`exact`) and a noise-level map run the generic."""
+    if BACKEND != "auto" or exact or is_map:
+        return "generic"
+    if ops.fused_supported(g):
+        return "fused"
+    return "fusedg" if ops.fusedg_supported(g) else "generic"
+
+
+# What the nodes below need of a tier, one argument convention per role.  `st` is the routed context (it carries layout and
+# precision); mp the map keywords of _map_args (generic tier only); keep_gates: keep what gates a tangent sweep although
+# nothing else is kept -- the bit maps on the fused tiers, all K codes on the generic one.  The entries name the sweeps
+# through the module when they are CALLED: a test that replaces loop._forward_generic by its stepwise twin reaches every node.
+#   layout(g, keep, handed_out, tangent) -> layout of the codes that stay inside the sweeps (None: the reference's only)
+#   forward(st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates, **mp) -> (xp, z, codes, resid, maps)
+#   reverse(st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp, dtau, **mp) -> (dA, dB)
+#   tangent(st, g, vp, mask_p, A, B, codes, maps, keep, last) -> (xdp, zd, rd)           (codes, maps: the primal's)
+#   tangent_reverse(st, g, K, vp, mask_p, A, B, codes, maps, zd, rd, g_xdp, g_zd) -> (dA, dB)
+#   negated_dA: the tangent sweep keeps -rd_k, so its reverse sweep's dA_k (k >= 1) comes out negated
+_Tier = collections.namedtuple("_Tier", "layout forward reverse tangent tangent_reverse negated_dA")
+
+
+def _tangent_reverse_fused(name):
+    """The tangent net is linear: on the fused tiers its reverse sweep is the tier's own with vp, zd, -rd for yp, codes,
+    resid, the primal's maps, and neither thresholds (their output is never returned) nor data gradients."""
+    return lambda st, g, K, vp, mask_p, A, B, codes, maps, zd, rd, g_xdp, g_zd: _TIERS[name].reverse(
+        st, g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, vp.new_empty((K, 2, g.M)), maps)
+
+
+_TIERS = {
+    "fused": _Tier(
+        layout=lambda g, keep, handed_out, tangent: "nchw" if handed_out else CODE_LAYOUT,
+        forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False: _forward_fused(
+            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates),
+        reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None: _backward_fused(
+            g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=st.layout, precision=st.precision,
+            dyp=dyp, dtau=dtau),
+        tangent=lambda st, g, vp, mask_p, A, B, codes, maps, keep, last: _tangent_fused(
+            g, vp, mask_p, A, B, maps, keep, st.layout, st.precision, last=last),
+        tangent_reverse=_tangent_reverse_fused("fused"), negated_dA=True),
+    "fusedg": _Tier(                               # handed-out codes are (N,M,..), and cdl_fusedg_tangent takes nothing else
+        layout=lambda g, keep, handed_out, tangent: "nchw" if handed_out or tangent else ops.fusedg_code_layout(g, training=keep),
+        forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False: _forward_fusedg(
+            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates),
+        reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None: _backward_fusedg(
+            g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=st.layout, dyp=dyp, dtau=dtau),
+        tangent=lambda st, g, vp, mask_p, A, B, codes, maps, keep, last: _tangent_fusedg(
+            g, vp, mask_p, A, B, maps, keep, last=last),
+        tangent_reverse=_tangent_reverse_fused("fusedg"), negated_dA=True),
+    "generic": _Tier(
+        layout=lambda g, keep, handed_out, tangent: None,
+        forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False, **mp: _forward_generic(
+            g, yp, mask_p, tau, A, B, keep_codes or keep_gates, keep_resid, **mp),
+        reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None, **mp:
+            _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, dtau=dtau, **mp),
+        tangent=lambda st, g, vp, mask_p, A, B, codes, maps, keep, last: _tangent_generic(
+            g, vp, mask_p, A, B, codes, keep, last=last),
+        tangent_reverse=lambda st, g, K, vp, mask_p, A, B, codes, maps, zd, rd, g_xdp, g_zd: _tangent_backward_generic(
+            g, K, vp, mask_p, A, B, codes, zd, rd, g_xdp if g_xdp is not None else torch.zeros_like(vp), g_zd),
+        negated_dA=False),                         # (g_xdp None, a loss on zd_K alone: a zero image gradient to the sweep)
+}
+
+
+def _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, want_codes, keep_maps=False, tangent=False):
     """The tier choice and the forward sweep of one pre-processed batch: (xp, z, codes, resid, maps).  `ctx` (an autograd
-    context, or any namespace carrying `exact`) receives what the reverse sweep reads: is_map, fused, fusedg and, on the
-    fused tiers, layout / precision.  UnrolledISTA.forward and run_windows both go through here, so a window takes
-    exactly the tier a sample of its geometry takes."""
-    K, N, M = len(A), g.N, g.M
-    # a noise-level map (dense (N,1,*code grid), net._noise_scale): tau holds t[k,0,m] for every sample and the generic
-    # sweeps form tau + c[n,pix] * t[k,1,m] in their shrinkage epilogues
-    ctx.is_map = c is not None and c.dim() > 1
-    cmap = c if ctx.is_map else None
-    tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
-    tau = ops.thresholds(t, None if ctx.is_map else c, N)
-    auto = BACKEND == "auto" and not ctx.exact     # "fp32": the fused kernels are matrix-core kernels
-    auto = auto and not ctx.is_map                 # the fused kernels read tau[n,m]: a map runs the generic sweep
-    ctx.fused = auto and ops.fused_supported(g)
-    ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
-    if ctx.fusedg:
-        # codes handed to the caller (forward_generator) must be (N,M,..); otherwise they stay in the sweeps' layout
-        ctx.layout = "nchw" if want_codes else ops.fusedg_code_layout(g, training=keep)
-        return _forward_fusedg(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
-    if ctx.fused:
-        # codes handed to the caller (forward_generator) must be (N,M,H,W); otherwise they stay internal
-        ctx.layout = "nchw" if want_codes else CODE_LAYOUT
-        ctx.precision = PRECISION                  # the reverse sweep runs in the forward's arithmetic
-        return _forward_fused(g, yp, mask_p, tau, A, B, keep or want_codes, keep, ctx.layout)
-    return _forward_generic(g, yp, mask_p, tau, A, B, keep or want_codes, keep,
-                            **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
+    context, or any namespace carrying `exact`) receives what the reverse sweep reads: tier (and fused / fusedg as flags),
+    is_map, layout, precision.  UnrolledISTA.forward, TangentISTA.forward and run_windows all go through here, so a window
+    and a tangent's primal take exactly the tier a sample of their geometry takes.  want_codes: the codes are handed to the
+    caller (forward_generator), as (N,M,..); tangent: a tangent sweep follows, in a layout it reads; keep_maps: _Tier's keep_gates."""
+    cmap, tslope = _map_args(c, t)                 # with a map tau holds t[k,0,m] for every sample
+    ctx.is_map = cmap is not None
+    tau = ops.thresholds(t, None if ctx.is_map else c, g.N)
+    ctx.tier = _route(g, ctx.exact, ctx.is_map)
+    ctx.fused, ctx.fusedg = ctx.tier == "fused", ctx.tier == "fusedg"
+    tier = _TIERS[ctx.tier]
+    ctx.layout = tier.layout(g, keep, want_codes, tangent)
+    ctx.precision = PRECISION                      # the reverse sweep runs in the forward's arithmetic
+    return tier.forward(ctx, g, yp, mask_p, tau, A, B, keep or want_codes, keep, keep_maps,
+                        **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
+
+
+def _reverse_sweep(ctx, sv, g_xp, g_z, dt, want_y=False, want_c=False):
+    """The primal's reverse sweep of a routed context (what _forward_sweep left on ctx; sv: what the node saved): (dA, dB,
+    dyp, dtau, dcmap), dt (K,2,M) filled in place.  dyp (with want_y), dtau (K,N,M) or -- with a noise-level map -- dcmap (with
+    want_c) only when asked for: otherwise the sweeps get NULLs and run exactly the parameter-only launches."""
+    K, g, dev = ctx.K, ctx.geom, sv.yp.device
+    live = g_xp is not None or g_z is not None
+    dyp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32) if want_y and live else None
+    dtau = torch.empty((K, g.N, g.M), device=dev, dtype=torch.float32) if want_c and live and not ctx.is_map else None
+    cmap, tslope = _map_args(sv.c, sv.t)
+    dcmap = torch.empty_like(cmap) if want_c and live and ctx.is_map else None      # dL/dc comes back as a map
+    mp = dict(cmap=cmap, tslope=tslope, dcmap=dcmap) if ctx.is_map else {}
+    dA, dB = _TIERS[ctx.tier].reverse(ctx, g, K, sv.yp, sv.mask_p, None if ctx.is_map else sv.c, sv.A, sv.B, sv.codes,
+                                      sv.resid, g_xp, g_z, dt, sv.maps, dyp, dtau, **mp)
+    return dA, dB, dyp, dtau, dcmap
 
 
 @_arithmetic_aware
@@ -395,9 +488,8 @@ class UnrolledISTA(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, mask, c, t, cfg, *weights):
-        K = cfg["K"]
+        K, s = cfg["K"], cfg["s"]
         A, B = weights[:K], weights[K:]
-        s = cfg["s"]
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
         g = _sweep_geometry(yp, A, s)
 
@@ -425,40 +517,19 @@ class UnrolledISTA(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_xhat, g_z, *_unused):
         K, g = ctx.K, ctx.geom
-        sv = _saved(ctx)
-        yp, mask_p, c, t, A, B, y_mask = sv.yp, sv.mask_p, sv.c, sv.t, sv.A, sv.B, sv.y_mask
-        codes, resid, maps = sv.codes, sv.resid, sv.maps      # z_1..z_K, r_1..r_{K-1}, fused tiers: the bit maps of z_1..z_K
-        dt = torch.zeros((K, 2, g.M), device=yp.device, dtype=torch.float32)
+        sv = _saved(ctx)       # codes z_1..z_K, resid r_1..r_{K-1}, fused tiers: maps, the bit maps of z_1..z_K
+        dt = torch.zeros((K, 2, g.M), device=sv.yp.device, dtype=torch.float32)
         g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
-        if g_z is not None:
-            g_z = g_z.contiguous()
-        live = g_xp is not None or g_z is not None
-        # data gradients only when asked for: otherwise the sweeps get NULLs and run exactly the parameter-only launches
-        dyp = torch.empty(g.image_shape(), device=yp.device, dtype=torch.float32) if ctx.want_y and live else None
-        dtau = torch.empty((K, g.N, g.M), device=yp.device, dtype=torch.float32) \
-            if ctx.want_c and live and not ctx.is_map else None
-        if ctx.fusedg:
-            dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=ctx.layout,
-                                      dyp=dyp, dtau=dtau)
-        elif ctx.fused:                                # a loss on z only is a zero image gradient to the sweep
-            dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
-                                     layout=ctx.layout, precision=ctx.precision, dyp=dyp, dtau=dtau)
-        elif ctx.is_map:                               # dL/dc comes back as a map, through the slot of c
-            dcmap = torch.empty_like(c) if ctx.want_c and live else None
-            dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, cmap=c,
-                                       tslope=t.detach().reshape(K, 2, g.M)[:, 1].contiguous(), dcmap=dcmap)
-        else:
-            dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, dyp=dyp, dtau=dtau)
-        dy = dc = None
-        if ctx.is_map:
-            dc = dcmap
+        g_z = g_z.contiguous() if g_z is not None else None
+        dA, dB, dyp, dtau, dc = _reverse_sweep(ctx, sv, g_xp, g_z, dt, ctx.want_y, ctx.want_c)
+        dy = None
         if dyp is not None:                            # a loss on z only: no mean term
-            dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, y_mask)
+            dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, sv.y_mask)
         if dtau is not None:                           # tau[k,n,m] = t[k,0,m] + c[n] t[k,1,m]
-            dc = torch.einsum("knm,km->n", dtau, t.detach().reshape(K, 2, g.M)[:, 1])
+            dc = torch.einsum("knm,km->n", dtau, sv.t.detach().reshape(K, 2, g.M)[:, 1])
 
         _queue_backward_end()
-        return (dy, None, dc, dt.reshape(t.shape), None, *dA, *dB)
+        return (dy, None, dc, dt.reshape(sv.t.shape), None, *dA, *dB)
 
 
 # ------------------------------------------------------------------------------------------
@@ -540,11 +611,6 @@ def _tangent_fusedg(g, vp, mask_p, A, B, maps, keep, last=False):
     return ops.fusedg_tangent(g, vp, mask_p, A, B, maps, keep, last=last)
 
 
-def _negate_dA_tail(dA):
-    """The fused tangent sweeps keep -rd_k: the reverse sweep's dA_k = -du_k (x) r_k (k >= 1) comes out negated."""
-    return [dA[0]] + [torch.neg(w) for w in dA[1:]]
-
-
 @_arithmetic_aware
 class TangentISTA(torch.autograd.Function):
     """(y, v, mask, c, t, A_0..A_{K-1}, B_0..B_{K-1}) -> (xhat, xdot): the primal of UnrolledISTA and its directional
@@ -560,32 +626,14 @@ class TangentISTA(torch.autograd.Function):
         yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
         vp, vmean, _, _ = ops.preprocess(v, s, mask)          # linear: the same mean rule, mask and reflect pad
         g = _sweep_geometry(yp, A, s)
-        N, M = g.N, g.M
-        ctx.is_map = c is not None and c.dim() > 1
-        cmap = c if ctx.is_map else None
-        tslope = t.detach().reshape(K, 2, M)[:, 1].contiguous() if ctx.is_map else None
-        tau = ops.thresholds(t, None if ctx.is_map else c, N)
 
         ctx.set_materialize_grads(False)
         _no_data_gradients(ctx, ((0, "y"), (1, "v"), (2, "mask"), (3, "sigma")))
         keep = any(ctx.needs_input_grad)
         want_codes = cfg.get("codes", False)
-        auto = BACKEND == "auto" and not ctx.exact and not ctx.is_map
-        ctx.fused = auto and ops.fused_supported(g)
-        ctx.fusedg = auto and not ctx.fused and ops.fusedg_supported(g)
-        if ctx.fused:
-            ctx.layout, ctx.precision = CODE_LAYOUT, PRECISION        # net.jvp refuses blocked_bf16; so does the C sweep
-            xp, z, codes, resid, maps = ops.fused_forward(g, yp, mask_p, tau, A, B, keep, PRECISION, ctx.layout,
-                                                          keep_maps=True)
-            xdp, zd, rd = _tangent_fused(g, vp, mask_p, A, B, maps, keep, ctx.layout, ctx.precision, last=want_codes)
-        elif ctx.fusedg:
-            ctx.layout = "nchw"
-            xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, ctx.layout, keep_maps=True)
-            xdp, zd, rd = _tangent_fusedg(g, vp, mask_p, A, B, maps, keep, last=want_codes)
-        else:                                          # the gates are the primal's codes: all K are kept
-            xp, z, codes, resid, maps = _forward_generic(g, yp, mask_p, tau, A, B, True, keep,
-                                                         **(dict(cmap=cmap, tslope=tslope) if ctx.is_map else {}))
-            xdp, zd, rd = _tangent_generic(g, vp, mask_p, A, B, codes, keep, last=want_codes)
+        # the primal, as UnrolledISTA runs it (net.jvp refuses blocked_bf16; so does the C sweep), then its tier's tangent
+        xp, z, codes, resid, maps = _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, False, keep_maps=True, tangent=True)
+        xdp, zd, rd = _TIERS[ctx.tier].tangent(ctx, g, vp, mask_p, A, B, codes, maps, keep, want_codes)
         zdK = zd[-1] if want_codes else None           # (N,M,..) on every tier; the ping-pong table's last when nothing is kept
         if not keep:
             zd = []
@@ -601,49 +649,24 @@ class TangentISTA(torch.autograd.Function):
     def backward(ctx, g_xhat, g_xdot, g_z=None, g_zd=None):
         K, g = ctx.K, ctx.geom
         sv = _saved(ctx)
-        yp, vp, mask_p, c, t, A, B = sv.yp, sv.vp, sv.mask_p, sv.c, sv.t, sv.A, sv.B
-        codes, resid, zd, rd, maps = sv.codes, sv.resid, sv.zd, sv.rd, sv.maps
-        dev = yp.device
-        dt = torch.zeros((K, 2, g.M), device=dev, dtype=torch.float32)
+        tier = _TIERS[ctx.tier]
+        dt = torch.zeros((K, 2, g.M), device=sv.yp.device, dtype=torch.float32)
         dA = dB = None
         g_z = g_z.contiguous() if g_z is not None else None
         g_zd = g_zd.contiguous() if g_zd is not None else None
         if g_xhat is not None or g_z is not None:      # the primal's reverse sweep, as UnrolledISTA runs it
             g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
-            if ctx.fusedg:
-                dA, dB = _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
-                                          layout=ctx.layout)
-            elif ctx.fused:
-                dA, dB = _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps,
-                                         layout=ctx.layout, precision=ctx.precision)
-            elif ctx.is_map:
-                dA, dB = _backward_generic(g, K, yp, mask_p, None, A, B, codes, resid, g_xp, g_z, dt, cmap=c,
-                                           tslope=t.detach().reshape(K, 2, g.M)[:, 1].contiguous())
-            else:
-                dA, dB = _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt)
+            dA, dB = _reverse_sweep(ctx, sv, g_xp, g_z, dt)[:2]
         if g_xdot is not None or g_zd is not None:     # the tangent's: same sweep, other operands, the primal's gates
             g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads) if g_xdot is not None else None
-            scratch = torch.empty_like(dt)             # its threshold output: never returned
-            if ctx.fusedg:
-                tA, tB = _backward_fusedg(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, scratch, maps=maps,
-                                          layout=ctx.layout)
-                tA = _negate_dA_tail(tA)
-            elif ctx.fused:
-                tA, tB = _backward_fused(g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, scratch, maps=maps,
-                                         layout=ctx.layout, precision=ctx.precision)
-                tA = _negate_dA_tail(tA)
-            else:                                      # (a loss on zd_K alone: a zero image gradient to the sweep)
-                tA, tB = _tangent_backward_generic(g, K, vp, mask_p, A, B, codes, zd, rd,
-                                                   g_xdp if g_xdp is not None else torch.zeros_like(vp), g_zd)
-            if dA is None:
-                dA, dB = tA, tB
-            else:
-                dA = [a + b for a, b in zip(dA, tA)]
-                dB = [a + b for a, b in zip(dB, tB)]
+            tA, tB = tier.tangent_reverse(ctx, g, K, sv.vp, sv.mask_p, sv.A, sv.B, sv.codes, sv.maps, sv.zd, sv.rd, g_xdp, g_zd)
+            if tier.negated_dA:
+                tA = [tA[0]] + [torch.neg(w) for w in tA[1:]]
+            dA, dB = _add_sweeps((dA, dB), (tA, tB))
         if dA is None:
-            dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+            dA, dB = _zero_grads(sv.A, sv.B)
         _queue_backward_end()
-        return (None, None, None, None, dt.reshape(t.shape), None, *dA, *dB)
+        return (None, None, None, None, dt.reshape(sv.t.shape), None, *dA, *dB)
 
 
 # ------------------------------------------------------------------------------------------
@@ -750,7 +773,7 @@ class TemporalISTA(torch.autograd.Function):
         g_z = g_z.contiguous() if g_z is not None else None
         dy = dc = None
         if g_xp is None and g_z is None:
-            dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+            dA, dB = _zero_grads(A, B)
         else:
             # data gradients only when asked for: otherwise the sweep gets NULLs and runs the parameter-only launches
             dyp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32) if ctx.want_y else None
@@ -913,13 +936,9 @@ class TangentTemporalISTA(torch.autograd.Function):
             g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads) if g_xdot is not None else None
             tA, tB = _tangent_backward_csr(g, K, vp, mask_p, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, gzdp,
                                            gzda)
-            if dA is None:
-                dA, dB = tA, tB
-            else:
-                dA = [a + b for a, b in zip(dA, tA)]
-                dB = [a + b for a, b in zip(dB, tB)]
+            dA, dB = _add_sweeps((dA, dB), (tA, tB))
         if dA is None:
-            dA, dB = [torch.zeros_like(w) for w in A], [torch.zeros_like(w) for w in B]
+            dA, dB = _zero_grads(A, B)
         _queue_backward_end()
         return (None, None, None, None, gzp, gzdp, gza, gzda, dt.reshape(t.shape), dg1.reshape(g1.shape),
                 dg2.reshape(g2.shape) if dg2 is not None else None, None, *dA, *dB)

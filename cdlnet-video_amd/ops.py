@@ -3,6 +3,7 @@
 PyTorch supplies device memory and the stream; every operation here is a call into
 libcdlnet_hip.so.  Inputs must be CUDA (ROCm) fp32 tensors -- there is no CPU path.
 """
+import collections
 import ctypes
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -955,22 +956,6 @@ def fused_support_map(g: Geometry, z, out=None):
     return out
 
 
-def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3", out=None, map_out=None,
-               lay_in="nchw", lay_out="nchw"):
-    """One fused iteration.  lay_in / lay_out: layouts of zin / the result (a flat buffer unless "nchw")."""
-    r, tau = _dev(r, "r"), _dev(tau, "tau")
-    if zin is not None and lay_in == "nchw":
-        zin = _dev(zin, "zin")
-    assert tuple(r.shape) == g.image_shape()
-    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
-    map_out = _buf(map_out, "map_out", dtype=torch.int32)
-    if out is None:
-        out = fused_code_buffer(g, lay_out, r.device)[0]
-    _call("cdl_fused2d_iter_fwd", g, r, zin, tau, frags, sgn, out, patches, map_out,
-          PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
-    return out
-
-
 def _assemble(symbol, g, patches, mask, sub, alpha, out, acc, acc_add, write_out):
     patches, acc = _buf(patches, "patches"), _buf(acc, "acc", g.image_shape())
     mask, sub = _opt(mask, "mask"), _opt(sub, "sub")
@@ -988,31 +973,6 @@ def fused_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=Non
 
 def fused_tiles(g: Geometry) -> int:
     return _size("cdl_fused2d_tiles", g)
-
-
-def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
-                    precision="split3", out=None, lay_in="nchw", lay_out="nchw", r2=None, alpha=1.0, workspace=None):
-    """One reverse-sweep stage: du = [z' != 0] * (base + corr(thin; W1)); patches = W2^T du.  `gate` is the
-    bit map of z' (int32, from the forward or fused_support_map) or z' itself (the map is built first).
-    With `r2` (thin) and `workspace` (fused_wgrad_workspace) the launch also accumulates dA = alpha * du (x) im2col(r2)
-    and (du, dA) is returned."""
-    thin = _dev(thin, "thin")
-    if base is not None and lay_in == "nchw":
-        base = _dev(base, "base")
-    if gate.dtype != torch.int32:
-        gate = fused_support_map(g, gate)
-    gate = _buf(gate, "gate", dtype=torch.int32)
-    assert gate.numel() == g.N * 4 * g.dims[1] * g.dims[2]
-    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
-    dtau_partial, workspace = _buf(dtau_partial, "dtau_partial"), _buf(workspace, "workspace")
-    if out is None:
-        out = fused_code_buffer(g, lay_out, thin.device)[0]
-    flags = PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out)
-    r2 = _opt(r2, "r2")
-    dA = None if r2 is None else torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
-    _call("cdl_fused2d_stage_bwd", g, thin, base, gate, frags, out, patches, dtau_partial, bool(do_synth), r2, alpha, dA,
-          workspace, flags)
-    return out if dA is None else (out, dA)
 
 
 def _dtau_reduce(symbol, g, dtau_partial, c, dt_k, dtau_n):
@@ -1086,60 +1046,6 @@ def _sweep_tables(K, keep, alloc_z, alloc_r, z_K=None):
     return z, [rbuf[k % nr] for k in range(K - 1)]
 
 
-def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False):
-    """Whole forward sweep in one C call.  keep=True: every z_k and r_k gets its own buffer (training) and
-    each launch also writes the support/sign bit map of its z_{k+1}; keep=False: two ping-pong buffers
-    each, no maps.  `layout`: how z_1..z_{K-1} are stored (they never leave the sweeps; z_K is always NCHW).
-    keep_maps (with keep=False): the K bit maps are written although every code and residual ping-pongs (what a tangent
-    sweep under no_grad needs of the primal).
-    Returns (xp, z_K, codes, resid, maps); codes[:-1] are flat buffers in `layout` unless it is "nchw"."""
-    K = len(A)
-    yp, tau = _dev(yp, "yp"), _dev(tau, "tau")
-    mask_p = _opt(mask_p, "mask")
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    dev = yp.device
-    # one allocation per family (views into it): at cfg1's size the allocator calls cost more than the kernels
-    z, r = _sweep_tables(K, keep, lambda n: fused_code_buffer(g, layout, dev, n), lambda n: _thin(g, dev, n),
-                         z_K=_new(g.code_shape(), dev))
-    maps = list(torch.empty((K, g.N, 4, g.dims[1], g.dims[2]), device=dev, dtype=torch.int32).unbind(0)) \
-        if (keep or keep_maps) else []
-    xp = _new(g.image_shape(), dev)
-    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    _call("cdl_fused2d_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, fused_patches(g, dev),
-          PRECISION[precision] | _lay_in(layout))
-    return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), maps
-
-
-def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision="split3", maps=None,
-                   layout="blocked", dyp=None, dtau=None):
-    """Whole reverse sweep in one C call; returns (dA list, dB list); dt (K,2,M) is written in place.
-    maps: the forward's bit maps of z_1..z_K (built here from the codes when not given).  `layout`: that of
-    codes[:-1] (as fused_forward returned them) and of the du work buffers; codes[-1] = z_K, g_z: NCHW.
-    g_xp None (a loss on the code only) is a zero image gradient.  dyp (thin, as yp) / dtau (K,N,M): filled with
-    dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward; None: the plain sweep)."""
-    K = len(A)
-    dev = yp.device
-    if not maps:
-        maps = [fused_support_map(g, fused_to_nchw(g, t, layout if k < K - 1 else "nchw")) for k, t in enumerate(codes)]
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    codes = [(_dev(t, "z") if (layout == "nchw" or k == K - 1) else t) for k, t in enumerate(codes)]
-    resid = [_dev(t, "r") for t in resid]
-    if g_xp is None:
-        g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
-    g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
-    dt = _dt_sweep(g, K, dt)
-    _check_data_grads(g, K, dyp, dtau)
-    dA, dB = _filter_grads(g, K, dev)
-    dub = fused_code_buffer(g, layout, dev, 2 if K > 1 else 1)
-    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    _call("cdl_fused2d_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt,
-          dub[0], dub[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, fused_patches(g, dev),
-          _new((fused_tiles(g), g.M), dev), fused_wgrad_workspace(g, dev), PRECISION[precision] | _lay_in(layout), dyp, dtau)
-    return dA, dB
-
-
 # ------------------------------------------------------------------------------------------ fused generic path
 # cdl_fusedg.hip: the fused iteration for any C, 2-D / 3-D, unit stride, P in {3,5,7}, M <= 64 (BASELINE configs[2]
 # and [3]), and -- behind the same entry points -- cdl_strip.hip: one image channel, stride 1 or 2, up to 192 subbands
@@ -1210,18 +1116,6 @@ def fusedg_from_rsc(g: Geometry, buf):
     return z[..., :wz].contiguous().reshape(g.code_shape())
 
 
-def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw"):
-    r, zin, tau = _dev(r, "r"), _opt(zin, "zin"), _dev(tau, "tau")
-    assert tuple(r.shape) == g.image_shape()
-    if out is None:
-        out = (torch.empty(g.code_shape(), device=r.device, dtype=torch.float32) if lay_out == "nchw"
-               else fusedg_rsc_buffer(g, r.device)[0])
-    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
-    _call("cdl_fusedg_iter_fwd", g, r, zin, tau, frags, sgn, _buf(out, "out"), patches,
-          _buf(map_out, "map_out", dtype=torch.int32), _lay_in(lay_in) | _lay_out(lay_out))
-    return out
-
-
 def fusedg_assemble(g: Geometry, patches, mask=None, sub=None, alpha=1.0, out=None, acc=None, acc_add=False,
                     write_out=True):
     """As fused_assemble (the optional unmasked sum into `acc` included)."""
@@ -1252,19 +1146,6 @@ def fusedg_support_map(g: Geometry, z):
     return out.to(torch.int32).contiguous()
 
 
-def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_partial, do_synth, out=None,
-                     lay_in="nchw", lay_out="nchw"):
-    thin, base = _dev(thin, "thin"), _opt(base, "base")
-    gate_map = _buf(gate_map, "gate_map", dtype=torch.int32)
-    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
-    if out is None:
-        out = (torch.empty(g.code_shape(), device=thin.device, dtype=torch.float32) if lay_out == "nchw"
-               else fusedg_rsc_buffer(g, thin.device)[0])
-    _call("cdl_fusedg_stage_bwd", g, thin, base, gate_map, frags, _buf(out, "out"), patches,
-          _buf(dtau_partial, "dtau_partial"), bool(do_synth), _lay_in(lay_in) | _lay_out(lay_out))
-    return out
-
-
 def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
     _dtau_reduce("cdl_fusedg_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
 
@@ -1284,52 +1165,193 @@ def _fusedg_code_buffers(g: Geometry, layout, device, count):
     return list(fusedg_rsc_buffer(g, device, max(count, 1)).unbind(0))
 
 
+# ------------------------------------------------------------------------------------------ sweeps of the two fused tiers
+# What the wrappers of the two fused tiers differ in (the rest is one implementation per role, _fused_* below): the prefix of
+# the entry points; code_buffers(g, layout, device, count) -> `count` indexable code buffers; to_nchw(g, t, layout) and
+# support_map(g, z), which rebuild a bit map from a stored code; map_shape(g) of one bit map; frag_bytes(g) of one prepared
+# pair, patch_floats(g), tiles(g) (rows of the stages' threshold partials); reverse_ws(g, device) -> the trailing workspace
+# arguments of the reverse sweep (cdl_fusedg_backward's filter gradients are the shape-generic cdl_wgrad's).
+_FusedTier = collections.namedtuple(
+    "_FusedTier", "prefix code_buffers to_nchw support_map map_shape frag_bytes patch_floats tiles reverse_ws")
+
+
+def _fusedg_wgrad_workspace(g: Geometry, device):
+    nws = _size("cdl_wgrad_workspace_floats", g)
+    return _new((max(nws, 1),), device), nws
+
+
+_FUSED2D = _FusedTier(
+    prefix="cdl_fused2d", code_buffers=fused_code_buffer, to_nchw=fused_to_nchw, support_map=fused_support_map,
+    map_shape=lambda g: (g.N, 4, g.dims[1], g.dims[2]), frag_bytes=lambda g: _lib.lib().cdl_fused2d_frag_bytes(g.M),
+    patch_floats=lambda g: _size("cdl_fused2d_patch_floats", g), tiles=fused_tiles,
+    reverse_ws=lambda g, device: (fused_wgrad_workspace(g, device),))
+_FUSEDG = _FusedTier(
+    prefix="cdl_fusedg", code_buffers=_fusedg_code_buffers,
+    to_nchw=lambda g, t, layout: t if layout == "nchw" else fusedg_from_rsc(g, t), support_map=fusedg_support_map,
+    map_shape=_fusedg_map_shape, frag_bytes=lambda g: _size("cdl_fusedg_frag_bytes", g),
+    patch_floats=lambda g: _size("cdl_fusedg_patch_floats", g), tiles=lambda g: _size("cdl_fusedg_tiles", g),
+    reverse_ws=_fusedg_wgrad_workspace)
+
+
+def _code(t, name, layout):
+    """A code tensor stored in `layout` that a kernel reads (None stays None): checked like any input, except the flat
+    pixel-blocked buffers of the fused 2-D sweeps (fp32 or bf16; K - 1 of them per reverse sweep), which `_call` checks."""
+    return t if t is None or layout.startswith("blocked") else _dev(t, name)
+
+
+def _fused_iter(tier, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out):
+    r, zin, tau = _dev(r, "r"), _code(zin, "zin", lay_in), _dev(tau, "tau")
+    assert tuple(r.shape) == g.image_shape()
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    if out is None:
+        out = tier.code_buffers(g, lay_out, r.device, 1)[0]
+    _call(tier.prefix + "_iter_fwd", g, r, zin, tau, frags, sgn, _buf(out, "out", dtype=out.dtype), patches,
+          _buf(map_out, "map_out", dtype=torch.int32), PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
+    return out
+
+
+def _fused_stage_bwd(tier, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, precision, out, lay_in, lay_out, rider=()):
+    """`rider`: the arguments an entry point takes between do_synth and the flags (cdl_fused2d_stage_bwd's dA_k)."""
+    thin, base = _dev(thin, "thin"), _code(base, "base", lay_in)
+    gate_map = _buf(gate_map, "gate_map", dtype=torch.int32)
+    frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    if out is None:
+        out = tier.code_buffers(g, lay_out, thin.device, 1)[0]
+    _call(tier.prefix + "_stage_bwd", g, thin, base, gate_map, frags, _buf(out, "out", dtype=out.dtype), patches,
+          _buf(dtau_partial, "dtau_partial"), bool(do_synth), *rider, PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
+    return out
+
+
+def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps):
+    K = len(A)
+    yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
+    A, B = [_dev(w, "A") for w in A], [_dev(w, "B") for w in B]
+    dev = yp.device
+    # one allocation per family (views into it): at cfg1's size the allocator calls cost more than the kernels
+    z, r = _sweep_tables(K, keep, lambda n: tier.code_buffers(g, layout, dev, n), lambda n: _thin(g, dev, n),
+                         z_K=_new(g.code_shape(), dev))
+    maps = list(torch.empty((K,) + tuple(tier.map_shape(g)), device=dev, dtype=torch.int32).unbind(0)) \
+        if (keep or keep_maps) else []
+    xp = _new(g.image_shape(), dev)
+    frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
+    _call(tier.prefix + "_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, _new((tier.patch_floats(g),), dev),
+          PRECISION[precision] | _lay_in(layout))
+    return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), maps
+
+
+def _fused_tangent(tier, g, vp, mask_p, A, B, maps, keep, precision, layout, last):
+    K = len(A)
+    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
+    A, B = [_dev(w, "A") for w in A], [_dev(w, "B") for w in B]
+    assert len(maps) == K
+    dev = vp.device
+    nvp = torch.neg(vp)                                      # thin: the assemble subtracts it
+    zd, nrd = _sweep_tables(K, keep, lambda n: tier.code_buffers(g, layout, dev, n), lambda n: _thin(g, dev, n),
+                            z_K=_new(g.code_shape(), dev))
+    xdp = _new(g.image_shape(), dev)
+    frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
+    _call(tier.prefix + "_tangent", g, K, vp, nvp, mask_p, A, B, list(maps), zd, nrd, xdp, frags,
+          _new((tier.patch_floats(g),), dev), _new((tier.tiles(g), g.M), dev), PRECISION[precision] | _lay_in(layout))
+    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
+
+
+def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau):
+    K = len(A)
+    dev = yp.device
+    lay = lambda k: layout if k < K - 1 else "nchw"          # codes[-1] = z_K is always (N,M,..)
+    if not maps:
+        maps = [tier.support_map(g, tier.to_nchw(g, t, lay(k))) for k, t in enumerate(codes)]
+    A, B = [_dev(w, "A") for w in A], [_dev(w, "B") for w in B]
+    codes = [_code(t, "z", lay(k)) for k, t in enumerate(codes)]
+    resid = [_dev(t, "r") for t in resid]
+    if g_xp is None:
+        g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
+    g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
+    dt = _dt_sweep(g, K, dt)
+    _check_data_grads(g, K, dyp, dtau)
+    dA, dB = _filter_grads(g, K, dev)
+    du = tier.code_buffers(g, layout, dev, 2 if K > 1 else 1)
+    frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
+    _call(tier.prefix + "_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt, du[0],
+          du[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, _new((tier.patch_floats(g),), dev),
+          _new((tier.tiles(g), g.M), dev), *tier.reverse_ws(g, dev), PRECISION[precision] | _lay_in(layout), dyp, dtau)
+    return dA, dB
+
+
+def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3", out=None, map_out=None,
+               lay_in="nchw", lay_out="nchw"):
+    """One fused iteration.  lay_in / lay_out: layouts of zin / the result (a flat buffer unless "nchw")."""
+    return _fused_iter(_FUSED2D, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out)
+
+
+def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw"):
+    return _fused_iter(_FUSEDG, g, r, zin, tau, frags, sgn, patches, "split3", out, map_out, lay_in, lay_out)
+
+
+def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
+                    precision="split3", out=None, lay_in="nchw", lay_out="nchw", r2=None, alpha=1.0, workspace=None):
+    """One reverse-sweep stage: du = [z' != 0] * (base + corr(thin; W1)); patches = W2^T du.  `gate` is the
+    bit map of z' (int32, from the forward or fused_support_map) or z' itself (the map is built first).
+    With `r2` (thin) and `workspace` (fused_wgrad_workspace) the launch also accumulates dA = alpha * du (x) im2col(r2)
+    and (du, dA) is returned."""
+    if gate.dtype != torch.int32:
+        gate = fused_support_map(g, gate)
+    assert gate.numel() == g.N * 4 * g.dims[1] * g.dims[2]
+    r2 = _opt(r2, "r2")
+    dA = None if r2 is None else torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
+    out = _fused_stage_bwd(_FUSED2D, g, thin, base, gate, frags, patches, dtau_partial, do_synth, precision, out, lay_in,
+                           lay_out, rider=(r2, alpha, dA, _buf(workspace, "workspace")))
+    return out if dA is None else (out, dA)
+
+
+def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_partial, do_synth, out=None,
+                     lay_in="nchw", lay_out="nchw"):
+    return _fused_stage_bwd(_FUSEDG, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, "split3", out, lay_in, lay_out)
+
+
+def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False):
+    """Whole forward sweep in one C call.  keep=True: every z_k and r_k gets its own buffer (training) and
+    each launch also writes the support/sign bit map of its z_{k+1}; keep=False: two ping-pong buffers
+    each, no maps.  `layout`: how z_1..z_{K-1} are stored (they never leave the sweeps; z_K is always NCHW).
+    keep_maps (with keep=False): the K bit maps are written although every code and residual ping-pongs (what a tangent
+    sweep under no_grad needs of the primal).
+    Returns (xp, z_K, codes, resid, maps); codes[:-1] are flat buffers in `layout` unless it is "nchw"."""
+    return _fused_forward(_FUSED2D, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps)
+
+
 def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep_maps=False):
     """Whole forward sweep in one C call (cdl_fusedg_forward); same contract as fused_forward: codes[:-1] come back
     in `layout` ("nchw", or "rsc" where fusedg_code_layout allows it), codes[-1] = z_K as (N,M,..)."""
-    K = len(A)
-    yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    dev = yp.device
-    fb, pf, tiles, mw = _fusedg_sizes(g)
-    zK = _new(g.code_shape(), dev)                          # the internal codes z_1..z_{K-1} are in `layout`
-    z, r = _sweep_tables(K, keep, lambda n: _fusedg_code_buffers(g, layout, dev, n), lambda n: _thin(g, dev, n), z_K=zK)
-    maps = list(torch.empty((K,) + _fusedg_map_shape(g), device=dev, dtype=torch.int32).unbind(0)) \
-        if (keep or keep_maps) else []                      # keep_maps: see fused_forward
-    xp = _new(g.image_shape(), dev)
-    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    _call("cdl_fusedg_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, _new((pf,), dev), _lay_in(layout))
-    return xp, zK, (z if keep else [zK]), (r if keep else []), maps
+    return _fused_forward(_FUSEDG, g, yp, mask_p, tau, A, B, keep, "split3", layout, keep_maps)
+
+
+def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision="split3", maps=None,
+                   layout="blocked", dyp=None, dtau=None):
+    """Whole reverse sweep in one C call; returns (dA list, dB list); dt (K,2,M) is written in place.
+    maps: the forward's bit maps of z_1..z_K (built here from the codes when not given).  `layout`: that of
+    codes[:-1] (as fused_forward returned them) and of the du work buffers; codes[-1] = z_K, g_z: NCHW.
+    g_xp None (a loss on the code only) is a zero image gradient.  dyp (thin, as yp) / dtau (K,N,M): filled with
+    dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward; None: the plain sweep)."""
+    return _fused_backward(_FUSED2D, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau)
 
 
 def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
                     dyp=None, dtau=None):
     """Whole reverse sweep in one C call (cdl_fusedg_backward); returns (dA list, dB list), fills dt (K,2,M) [and
     dyp, dtau: see fused_backward].  `layout`: that of codes[:-1] (and of the du buffers allocated here)."""
-    K = len(A)
-    dev = yp.device
-    if not maps:
-        nchw = [t if (layout == "nchw" or i == K - 1) else fusedg_from_rsc(g, t) for i, t in enumerate(codes)]
-        maps = [fusedg_support_map(g, t) for t in nchw]
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    codes = [_dev(t, "z") for t in codes]
-    resid = [_dev(t, "r") for t in resid]
-    if g_xp is None:
-        g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
-    g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
-    fb, pf, tiles, mw = _fusedg_sizes(g)
-    dt = _dt_sweep(g, K, dt)
-    _check_data_grads(g, K, dyp, dtau)
-    dA, dB = _filter_grads(g, K, dev)
-    du = _fusedg_code_buffers(g, layout, dev, 2 if K > 1 else 1)
-    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    nws = _size("cdl_wgrad_workspace_floats", g)
-    _call("cdl_fusedg_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt, du[0],
-          du[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, _new((pf,), dev), _new((tiles, g.M), dev),
-          _new((max(nws, 1),), dev), nws, _lay_in(layout), dyp, dtau)
-    return dA, dB
+    return _fused_backward(_FUSEDG, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, "split3", maps, layout, dyp, dtau)
+
+
+def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked", last=False):
+    """Tangent sweep on the fused 2-D kernels in one C call (cdl_fused2d_tangent).  maps: the primal's
+    K bit maps.  Returns (xdp, zd, nrd): with keep the tangent codes (zd[:-1] in `layout`, zd[-1] NCHW) and the NEGATED
+    tangent residuals -rd_1..-rd_{K-1} (what the stages read), else [] (with `last`, zd = [zd_K] when nothing is kept)."""
+    return _fused_tangent(_FUSED2D, g, vp, mask_p, A, B, maps, keep, precision, layout, last)
+
+
+def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, last=False):
+    """cdl_fusedg_tangent: as fused_tangent for the tile / strip kernels' shapes; codes in the reference's layout."""
+    return _fused_tangent(_FUSEDG, g, vp, mask_p, A, B, maps, keep, "split3", "nchw", last)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1460,44 +1482,6 @@ def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_afte
     _call("cdl_csr_tangent_forward", g, K, vp, mask_p, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
           _opt(gam2, "gam2"), zd_prev, zd_after, A, B, us, zd, rd, xdp, ws, n)
     return xdp, zd[K - 1], (zd if keep else []), (rd if keep else [])
-
-
-def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked", last=False):
-    """Tangent sweep on the fused 2-D kernels in one C call (cdl_fused2d_tangent).  maps: the primal's K bit maps.
-    Returns (xdp, zd, nrd): with keep the tangent codes (zd[:-1] in `layout`, zd[-1] NCHW) and the NEGATED tangent
-    residuals -rd_1..-rd_{K-1} (what the stages read), else []."""
-    K = len(A)
-    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    assert len(maps) == K
-    dev = vp.device
-    nvp = torch.neg(vp)                                      # thin: the assemble subtracts it
-    zd, nrd = _sweep_tables(K, keep, lambda n: fused_code_buffer(g, layout, dev, n), lambda n: _thin(g, dev, n),
-                            z_K=_new(g.code_shape(), dev))
-    xdp = _new(g.image_shape(), dev)
-    frags = torch.empty(K * _lib.lib().cdl_fused2d_frag_bytes(g.M), device=dev, dtype=torch.uint8)
-    _call("cdl_fused2d_tangent", g, K, vp, nvp, mask_p, A, B, list(maps), zd, nrd, xdp, frags, fused_patches(g, dev),
-          _new((fused_tiles(g), g.M), dev), PRECISION[precision] | _lay_in(layout))
-    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
-
-
-def fusedg_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, last=False):
-    """cdl_fusedg_tangent: as fused_tangent for the tile / strip kernels' shapes; codes in the reference's layout."""
-    K = len(A)
-    vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
-    A = [_dev(w, "A") for w in A]
-    B = [_dev(w, "B") for w in B]
-    assert len(maps) == K
-    dev = vp.device
-    nvp = torch.neg(vp)
-    fb, pf, tiles, mw = _fusedg_sizes(g)
-    zd, nrd = _generic_tables(g, K, keep, dev)
-    xdp = _new(g.image_shape(), dev)
-    frags = torch.empty(K * fb, device=dev, dtype=torch.uint8)
-    _call("cdl_fusedg_tangent", g, K, vp, nvp, mask_p, A, B, list(maps), zd, nrd, xdp, frags, _new((pf,), dev),
-          _new((tiles, g.M), dev), 0)
-    return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
 def fused_timing(enable: bool):

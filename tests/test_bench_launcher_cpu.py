@@ -138,6 +138,41 @@ def test_backward_end_hook_runs_once_per_pass_after_the_gradients_exist():
     assert len(seen) == 2
 
 
+def test_backward_end_hook_runs_again_after_a_backward_pass_that_raised():
+    """_queue_backward_end latches a module-wide flag that only the engine's callback clears; a pass that raises after
+    queueing never runs the callback.  Every node's forward (loop._arithmetic_aware wraps them all) clears the flag, so the
+    next pass runs the hook -- once."""
+    import pytest
+    from cdlnet_video_amd import loop
+
+    @loop._arithmetic_aware
+    class Sweep(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, w, fail):
+            ctx.fail = fail
+            return w * 2
+
+        @staticmethod
+        def backward(ctx, g):
+            loop._queue_backward_end()
+            if ctx.fail:
+                raise RuntimeError("the reverse sweep failed")
+            return g * 2, None
+
+    w = torch.ones(3, requires_grad=True)
+    seen = []
+    remove = loop.on_backward_end(lambda: seen.append(w.grad.clone()))
+    try:
+        with pytest.raises(RuntimeError, match="the reverse sweep failed"):
+            Sweep.apply(w, True).sum().backward()
+        assert seen == [] and loop._queued[0]           # queued, never run: the flag is still set
+        (Sweep.apply(w, False).sum() + Sweep.apply(w, False).sum()).backward()
+        assert len(seen) == 1 and torch.equal(seen[0], torch.full((3,), 4.0)) and not loop._queued[0]
+    finally:
+        remove()
+        loop._queued[0] = False
+
+
 def test_dump_outputs_writes_the_last_step_as_float32_npy(tmp_path, monkeypatch):
     """--dump-outputs DIR: loss, sigma, every parameter and its gradient, one float32 .npy each; --steps < 1 is refused."""
     import numpy as np

@@ -1,7 +1,8 @@
 """The host side of every launch, without a device: ops._call is the one way into a stream-taking entry point and
 refuses a tensor that is no contiguous tensor of the current ROCm device before the library is entered; ops._buf checks
 the outputs and work buffers a caller provides; ops._sweep_tables builds the ping-pong tables of the seven one-call
-sweeps; loop._save / loop._saved name what an autograd node keeps."""
+sweeps; loop._save / loop._saved name what an autograd node keeps; loop._route and loop._TIERS choose a sweep's tier and
+name what the nodes call on it."""
 import ast
 import os
 
@@ -193,6 +194,106 @@ def test_named_saves_round_trip_through_a_function():
     assert isinstance(seen["three"], tuple) and len(seen["three"]) == 3
     assert all(got is want for got, want in zip(seen["three"], (a, b, c)))
     assert torch.equal(x.grad, torch.full((3,), 2.0))
+
+
+# ------------------------------------------------------------------------------------------ the route and the tier table
+def _parent_rule(backend, exact, is_map, fused_ok, fusedg_ok):
+    """The routing rule as the commit before the table spelled it (in _forward_sweep and again in TangentISTA.forward)."""
+    auto = backend == "auto" and not exact
+    auto = auto and not is_map
+    fused = auto and fused_ok
+    fusedg = auto and not fused and fusedg_ok
+    return "fusedg" if fusedg else "fused" if fused else "generic"
+
+
+@pytest.fixture
+def sweep_spies(monkeypatch):
+    """The sweeps of the three tiers replaced by recorders, and the one launch before them (the thresholds) by a stub:
+    calls[i] = (name of the loop-level function reached, its arguments, its keywords)."""
+    calls = []
+
+    def spy(name, result):
+        def run(*args, **kw):
+            calls.append((name, args, kw))
+            return result
+        return run
+
+    z = _code()
+    monkeypatch.setattr(ops, "thresholds", lambda t, c, n: torch.zeros(K, n, M))
+    for name in ("_forward_generic", "_forward_fused", "_forward_fusedg"):
+        monkeypatch.setattr(loop, name, spy(name, (_thin(), z, [z], [], ["maps"])))
+    for name in ("_tangent_generic", "_tangent_fused", "_tangent_fusedg"):
+        monkeypatch.setattr(loop, name, spy(name, (_thin(), [z], [])))
+    return calls
+
+
+@pytest.mark.parametrize("fusedg_ok", [False, True])
+@pytest.mark.parametrize("fused_ok", [False, True])
+@pytest.mark.parametrize("is_map", [False, True])
+@pytest.mark.parametrize("arithmetic", ["split3", "fp32"])
+@pytest.mark.parametrize("backend", ["auto", "generic"])
+def test_route_truth_table(monkeypatch, sweep_spies, backend, arithmetic, is_map, fused_ok, fusedg_ok):
+    monkeypatch.setattr(ops, "fused_supported", lambda g: fused_ok)
+    monkeypatch.setattr(ops, "fusedg_supported", lambda g: fusedg_ok)
+    monkeypatch.setattr(ops, "fusedg_code_layout", lambda g, training=True: "rsc")
+    monkeypatch.setattr(loop, "BACKEND", backend)
+    want = _parent_rule(backend, arithmetic == "fp32", is_map, fused_ok, fusedg_ok)
+    t = torch.rand(K, 2, M, 1, 1)
+    c = torch.rand(N, 1, H, W) if is_map else torch.rand(N)
+    w = [torch.zeros(G.filter_shape())] * K
+    with loop.precision_scope(arithmetic):
+        st = type("Ctx", (), {"exact": loop.PRECISION == "fp32"})()         # what _arithmetic_aware leaves on a context
+        assert loop._route(G, st.exact, is_map) == want
+        loop._forward_sweep(st, G, _thin(), None, c, t, w, w, False, False)
+    assert (st.tier, st.fused, st.fusedg, st.is_map) == (want, want == "fused", want == "fusedg", is_map)
+    (name, args, kw), = sweep_spies
+    assert name == "_forward_" + want
+    if is_map:                                           # the generic sweep gets the map and the slopes t[:, 1]
+        assert kw["cmap"] is c and torch.equal(kw["tslope"], t[:, 1, :, 0, 0])
+    else:
+        assert "cmap" not in kw
+        assert st.layout == {"fused": loop.CODE_LAYOUT, "fusedg": "rsc", "generic": None}[want]
+
+
+def test_table_entries_follow_a_patched_sweep(monkeypatch):
+    """The entries name loop._forward_generic & co. through the module when they are called: a test that swaps in the
+    stepwise twin (tests/test_gpu_sigmamap.py) reaches every node that goes through the table."""
+    seen = []
+    monkeypatch.setattr(loop, "_forward_generic", lambda *a, **kw: seen.append(("fwd", a[0], kw)))
+    monkeypatch.setattr(loop, "_backward_generic", lambda *a, **kw: seen.append(("bwd", a[0], kw)))
+    st = type("Ctx", (), {})()
+    tier = loop._TIERS["generic"]
+    tier.forward(st, G, "yp", None, "tau", [], [], True, False, True, cmap="c", tslope="s")
+    tier.reverse(st, G, K, "yp", None, None, [], [], [], [], "g_xp", None, "dt", [], "dyp", None, cmap="c", tslope="s", dcmap="d")
+    assert seen == [("fwd", G, dict(cmap="c", tslope="s")),
+                    ("bwd", G, dict(dyp="dyp", dtau=None, cmap="c", tslope="s", dcmap="d"))]
+
+
+@pytest.mark.parametrize("tier", ["fused", "fusedg", "generic"])
+def test_tangent_primal_goes_through_the_loop_level_forward(monkeypatch, sweep_spies, tier):
+    """TangentISTA.forward obtains its primal through _forward_sweep and the table -- loop._forward_fused / _fusedg /
+    _generic -- not from ops directly; and in the three ways it differs from UnrolledISTA's primal: the bit maps although
+    nothing is kept, "nchw" codes on the fused generic tier, all K codes on the generic tier."""
+    monkeypatch.setattr(ops, "fused_supported", lambda g: tier == "fused")
+    monkeypatch.setattr(ops, "fusedg_supported", lambda g: tier == "fusedg")
+    monkeypatch.setattr(ops, "fusedg_code_layout", lambda g, training=True: "rsc")
+    monkeypatch.setattr(ops, "preprocess", lambda y, s, mask=None: (y, None, None, None))
+    monkeypatch.setattr(ops, "postprocess", lambda xp, mean, pads: xp)
+    w = [torch.zeros(G.filter_shape())] * K
+    with torch.no_grad():
+        out = loop.run_tangent(_thin(), _thin(), None, torch.rand(N), torch.rand(K, 2, M, 1, 1), w, w, 1, codes=True)
+    assert len(out) == 4
+    (fname, fargs, fkw), (tname, targs, tkw) = sweep_spies
+    assert (fname, tname) == ("_forward_" + tier, "_tangent_" + tier)
+    keep_codes, keep_resid = fargs[6], fargs[7]
+    if tier == "generic":
+        assert (keep_codes, keep_resid) == (True, False) and fkw == {}
+        assert len(targs[5]) == 1 and torch.is_tensor(targs[5][0])      # gated by the primal's codes
+    else:
+        assert (keep_codes, keep_resid) == (False, False) and fkw == {"keep_maps": True}
+        assert fargs[8] == (loop.CODE_LAYOUT if tier == "fused" else "nchw")
+        assert targs[5] == ["maps"]                      # gated by the primal's bit maps
+    assert tkw == {"last": True}
 
 
 def test_code_layout_setter_takes_the_fused_2d_layouts_only():
