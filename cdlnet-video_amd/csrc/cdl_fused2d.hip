@@ -91,7 +91,6 @@ struct Shape {
     static constexpr int LDS_STAGE = LDS_RT + LDS_RSUM + LDS_W + LDS_TAU + LDS_TACC;
     static constexpr int LDS_DA_THIN = 2 * 4 * TCOPY * 2;      // reverse stage with dA_k: r_k as [hl][shift] copies   (26496)
     static constexpr int LDS_DA = LDS_DA_THIN + NW * 2 * 2 * IMG_ELEMS * 2;   // + [wave][channel tile][hl] transposition images
-    static constexpr int NSTG = (RTH * RTW + NT - 1) / NT;     // thin-tile elements staged per thread
     // One wave per SIMD: every weight fragment of the launch lives in the wave's registers; two: read from LDS where used
     static constexpr bool WREG = WY == 2;
 };
@@ -109,11 +108,13 @@ struct FusedParams {
     float sgn;               // u = zin + sgn * acc
     int do_synth;            // 0: skip the synthesis-like half (last backward stage)
     CDL_DBG_FIELD(int dbg;)  // probe build only (CDL_FUSED_DEBUG): 1 no stores, 2 no synthesis, 32 no LDS adds, 64 no ST,
-                             // 4 no analysis MFMAs, 8 no thin staging, 16 no fat loads; results are wrong
+                             // 4 no analysis MFMAs, 8 no thin loads (both operands), 16 no fat loads, 128 no per-tile phase
+                             // behind the row loop (patch write-out, staging stores); results are wrong
     int N, H, W, tilesX, tilesY;
     int rev;                 // walk the tiles from the last to the first (see "snake order" at the sweeps)
     const float *r2;         // reverse stage with DA: (N,H,W) thin operand of dA_k = alpha * du_k (x) im2col(r2) (r_k or yp)
     float *da_partial;       // (gridDim.x, 2, M, 64): per-workgroup partial of dA_k in operator slot 0 (k_wgrad_reduce's layout)
+    int drop_zout;           // backward: zout is not written (the sweep's last stage: du_0 is consumed in registers only)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -341,6 +342,47 @@ __device__ __forceinline__ float col2im_row(const float (&rv)[4], int h)
     return s;
 }
 
+// Thin-tile staging: a thread stages a RUN of 8 elements along the contiguous axis of the shifted LDS copies (rows of one
+// column for the row-shifted copies of the stage's thin input, columns of one row for the column-shifted copies of dA_k's).
+// store_run<S> writes one run into the copy shifted by S (0..3): element j lands on dst[j - S]; dst is 8-byte aligned, so
+// the stores are as wide as the shift allows -- 2 + 4 + 3 + 4 = 13 for the four copies of a run where one element at a
+// time took 32.  low: the run starts at the copy's edge and the S elements that would land in front of it are dropped.
+constexpr int RUN = 8;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+template <int S>
+__device__ __forceinline__ void store_run(__bf16 *dst, const __bf16 (&v)[RUN], bool low)
+{
+    static_assert(S >= 0 && S <= 3, "four shifted copies");
+    if (!low) {
+        if constexpr (S == 1) dst[-1] = v[0];
+        if constexpr (S == 2) *reinterpret_cast<bf16x2 *>(dst - 2) = bf16x2{v[0], v[1]};
+        if constexpr (S == 3) { dst[-3] = v[0]; *reinterpret_cast<bf16x2 *>(dst - 2) = bf16x2{v[1], v[2]}; }
+    }
+    *reinterpret_cast<bf16x4 *>(dst) = bf16x4{v[S], v[S + 1], v[S + 2], v[S + 3]};
+    if constexpr (S == 0) *reinterpret_cast<bf16x4 *>(dst + 4) = bf16x4{v[4], v[5], v[6], v[7]};
+    if constexpr (S == 1) { *reinterpret_cast<bf16x2 *>(dst + 4) = bf16x2{v[5], v[6]}; dst[6] = v[7]; }
+    if constexpr (S == 2) *reinterpret_cast<bf16x2 *>(dst + 4) = bf16x2{v[6], v[7]};
+    if constexpr (S == 3) dst[4] = v[7];
+}
+// the hi / lo split of a run and its four shifted copies: copy S of half hl at dst + (4 * hl + S) * copy_elems
+template <int PREC>
+__device__ __forceinline__ void store_run_copies(__bf16 *dst, int copy_elems, const float (&f)[RUN], bool low)
+{
+    __bf16 hh[RUN], ll[RUN];
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) {
+        hh[j] = (__bf16)f[j];
+        ll[j] = (__bf16)(f[j] - (float)hh[j]);
+    }
+    store_run<0>(dst, hh, low); store_run<1>(dst + copy_elems, hh, low);
+    store_run<2>(dst + 2 * copy_elems, hh, low); store_run<3>(dst + 3 * copy_elems, hh, low);
+    if (PREC != 1) {
+        dst += 4 * copy_elems;
+        store_run<0>(dst, ll, low); store_run<1>(dst + copy_elems, ll, low);
+        store_run<2>(dst + 2 * copy_elems, ll, low); store_run<3>(dst + 3 * copy_elems, ll, low);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // MODE_FWD / MODE_FIRST: zout = ST(zin + sgn * A r, tau)              (net.py:85,87)
 // MODE_BWD            : zout = [z_{k+1} != 0] * (zin + A-like r),  dtau partials   (reverse sweep);
@@ -368,7 +410,6 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
     constexpr int M = 32 * MT;
     constexpr int FA = MT * 4, FB = 4 * MT;
     constexpr int NFRAG = (PREC != 1 ? 2 : 1) * (FA + FB);   // bf16 mode stages only the hi fragments
-    constexpr int NSTG = G::NSTG;                            // thin-tile elements staged per thread
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wxi = wid % WX, wyi = wid / WX;
     const int c = lane & 31, h = lane >> 5;
@@ -389,75 +430,63 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
     }
     // thin-tile staging: registers first (so the next tile's loads fly during this tile's GEMMs), then
     // 4 row-shifted bf16 hi/lo copies in LDS.  Every in-tile word is rewritten per tile (zeros outside
-    // the image); the pad words stay zero from the pass above.
-    float stg[NSTG];
+    // the image); the pad words stay zero from the pass above.  A thread owns the same run of every tile -- RUN rows of
+    // one column (store_run) -- so what depends on (tid) alone is computed here, once: only the tile origin changes.
+    // Rows RTH.. of a column's last run are staged as zeros: they land on pad words.
+    constexpr int RT_RUNS = (RTH + RUN - 1) / RUN;           // runs per column (3)
+    static_assert(RTW * RT_RUNS <= NT && RT_RUNS * RUN <= PITCH, "one run per thread; a column's runs stay inside its pitch");
+    const int rt_xx = tid % RTW, rt_y0 = (tid / RTW) * RUN;
+    const bool rt_on = tid < RTW * RT_RUNS;
+    __bf16 *const rt_dst = rt + rt_xx * PITCH + rt_y0;
+    float stg[RUN];
     auto stage_load = [&](int t) {
         int bid = p.rev ? numTiles - 1 - t : t;
         const int txi = bid % p.tilesX; bid /= p.tilesX;
         const int tyi = bid % p.tilesY;
         const int n = bid / p.tilesY;
         const float *rimg = p.r + (size_t)n * HW;
+        const int gy0 = tyi * TH - HALO + rt_y0, gx = txi * TW - HALO + rt_xx;
+        const bool colok = rt_on && t < numTiles && !CDL_DBG(p.dbg, 8) && gx >= 0 && gx < p.W;
 #pragma unroll
-        for (int k = 0; k < NSTG; ++k) {
-            const int i = tid + k * NT;
-            const int yy = i / RTW, xx = i % RTW;
-            const int gy = tyi * TH - HALO + yy, gx = txi * TW - HALO + xx;
+        for (int j = 0; j < RUN; ++j) {
+            const int gy = gy0 + j;
             float v = 0.0f;
-            if (i < RTH * RTW && t < numTiles && !CDL_DBG(p.dbg, 8) && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
-                v = rimg[(size_t)gy * p.W + gx];
-            stg[k] = v;
+            if (colok && rt_y0 + j < RTH && gy >= 0 && gy < p.H) v = rimg[(size_t)gy * p.W + gx];
+            stg[j] = v;
         }
     };
     auto stage_store = [&]() {
-#pragma unroll
-        for (int k = 0; k < NSTG; ++k) {
-            const int i = tid + k * NT;
-            if (i >= RTH * RTW) continue;
-            const int yy = i / RTW, xx = i % RTW;
-            const __bf16 hh = (__bf16)stg[k];
-            const __bf16 ll = (__bf16)(stg[k] - (float)hh);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (yy - q >= 0) {
-                    rt[(0 * 4 + q) * COPY + xx * PITCH + (yy - q)] = hh;
-                    if (PREC != 1) rt[(1 * 4 + q) * COPY + xx * PITCH + (yy - q)] = ll;
-                }
-        }
+        if (rt_on) store_run_copies<PREC>(rt_dst, COPY, stg, rt_y0 == 0);
     };
     // DA: the tile of r2 under this tile (22 x 70 with the halo), as 4 column-shifted bf16 hi/lo copies (k_wgrad2d's
-    // format: every 8-pixel window of an im2col row 8-byte aligned); loaded a tile ahead like the thin input
-    constexpr int NSTG2 = DA ? (GW_RTH * RTW + NT - 1) / NT : 1;
-    float stg2[NSTG2];
+    // format: every 8-pixel window of an im2col row 8-byte aligned); loaded a tile ahead like the thin input: into
+    // registers in front of the row loop, into LDS behind the barrier that ends it.  A run is RUN columns of one row;
+    // columns RTW.. of a row's last run are staged as zeros (pad words)
+    constexpr int T2_RUNS = (RTW + RUN - 1) / RUN;           // runs per row (9)
+    static_assert(!DA || (GW_RTH * T2_RUNS <= NT && T2_RUNS * RUN <= TPITCH), "one run per thread; a row's runs stay inside its pitch");
+    const int t2_x0 = (tid % T2_RUNS) * RUN, t2_yy = tid / T2_RUNS;
+    const bool t2_on = tid < GW_RTH * T2_RUNS;
+    __bf16 *const t2_dst = thin2 + t2_yy * TPITCH + t2_x0;
+    float stg2[DA ? RUN : 1];
     auto stage2_load = [&](int t) {
         int bid = p.rev ? numTiles - 1 - t : t;
         const int txi = bid % p.tilesX; bid /= p.tilesX;
         const int tyi = bid % p.tilesY;
         const int n = bid / p.tilesY;
         const float *timg = p.r2 + (t < numTiles ? (size_t)n * HW : 0);      // (past the last tile: nothing is read)
+        const int gy = tyi * TH - HALO + t2_yy, gx0 = txi * TW - HALO + t2_x0;
+        const bool rowok = t2_on && t < numTiles && !CDL_DBG(p.dbg, 8) && gy >= 0 && gy < p.H;
 #pragma unroll
-        for (int k = 0; k < NSTG2; ++k) {
-            const int i = tid + k * NT;
-            const int yy = i / RTW, xx = i % RTW;
-            const int gy = tyi * TH - HALO + yy, gx = txi * TW - HALO + xx;
-            const bool ok = i < GW_RTH * RTW && t < numTiles && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
+        for (int j = 0; j < (DA ? RUN : 1); ++j) {
+            const int gx = gx0 + j;
+            const bool ok = rowok && t2_x0 + j < RTW && gx >= 0 && gx < p.W;
             const float v = timg[ok ? (size_t)gy * p.W + gx : 0];
-            stg2[k] = ok ? v : 0.0f;
+            stg2[j] = ok ? v : 0.0f;
         }
     };
     auto stage2_store = [&]() {
-#pragma unroll
-        for (int k = 0; k < NSTG2; ++k) {
-            const int i = tid + k * NT;
-            if (i >= GW_RTH * RTW) continue;
-            const int yy = i / RTW, xx = i % RTW;
-            const __bf16 hh = (__bf16)stg2[k];
-            const __bf16 ll = (__bf16)(stg2[k] - (float)hh);
-#pragma unroll
-            for (int sft = 0; sft < 4; ++sft)
-                if (xx - sft >= 0) {
-                    thin2[(0 * 4 + sft) * TCOPY + yy * TPITCH + xx - sft] = hh;
-                    if (PREC != 1) thin2[(1 * 4 + sft) * TCOPY + yy * TPITCH + xx - sft] = ll;
-                }
+        if constexpr (DA) {
+            if (t2_on) store_run_copies<PREC>(t2_dst, TCOPY, stg2, t2_x0 == 0);
         }
     };
     f32x16 dacc[DA ? MT : 1][2];              // DA: dA_k[channel tile][tap tile], over every tile of this workgroup
@@ -512,7 +541,14 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
     const int x = tx0 + xl;
     if (MODE != MODE_BWD && tid < M) tau_s[tid] = p.tau[(size_t)n * M + tid];
     __syncthreads();                         // thin copies + tau of this tile are in place
-    if (MODE != MODE_BWD) stage_load(t + gridDim.x);   // next tile's thin loads fly during the GEMMs below
+    // next tile's thin loads fly during the GEMMs below: the registers (a run of 8, with DA two) stay live across the row
+    // loop and are stored behind its barrier.  The reverse stage on 64 x 32 tiles (two waves per SIMD, 256 registers)
+    // loads behind that barrier as it always did: its partner wave covers the wait, and loading ahead cost it scratch
+    constexpr bool LOAD_AHEAD = MODE != MODE_BWD || WY == 2;
+    if (LOAD_AHEAD) {
+        stage_load(t + gridDim.x);
+        if constexpr (DA) stage2_load(t + gridDim.x);
+    }
 
     float ring[7][4];                        // row-direction col2im sums for halo rows yl .. yl+6, by (j & 3)
 #pragma unroll
@@ -560,7 +596,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
         const int voff = valid ? lane_off + y * p.W * 4 : OOB;
         const int blk = (y * XB + xb) * (M / 4) * 32;            // first [px][4 ch] slot of the block
         const int voff_in = LIN == LAY_NCHW ? voff : (valid ? blk * EB_IN + lane_blk_in : OOB);
-        const int voff_st = CDL_DBG(p.dbg, 1) ? OOB : (LOUT == LAY_NCHW ? voff : (valid ? blk * EB_OUT + lane_blk_out : OOB));
+        const int voff_st = (CDL_DBG(p.dbg, 1) || (MODE == MODE_BWD && p.drop_zout)) ? OOB : (LOUT == LAY_NCHW ? voff : (valid ? blk * EB_OUT + lane_blk_out : OOB));
 
         // -- fat inputs of this block, issued first: the analysis MFMAs below (and the partner
         //    wave on this SIMD) run while they are in flight
@@ -880,22 +916,30 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
         }
     }
     __syncthreads();                         // every wave is done with the thin copies and the slabs
-    if (MODE == MODE_BWD) stage_load(t + gridDim.x);   // (the backward stage has no registers to spare earlier)
-    if constexpr (DA) stage2_load(t + gridDim.x);
+    if (!LOAD_AHEAD) stage_load(t + gridDim.x);
     if (MODE == MODE_BWD && tid < M) {
         float sacc = 0.0f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) sacc += tacc_s[w * 64 + tid];
         p.dtau[(size_t)tile * M + tid] = sacc;
     }
+    if CDL_DBG(p.dbg, 128) continue;
     if (MODE != MODE_BWD || p.do_synth) {    // patch out (fixed slab order), slabs re-zeroed for the next tile
-        float *patch = p.patches + (size_t)tile * SLAB;
-        for (int i = tid; i < SLAB; i += NT) {
-            patch[i] = (rsum_all[i] + rsum_all[SLAB + i]) + (rsum_all[2 * SLAB + i] + rsum_all[3 * SLAB + i]);
-            rsum_all[i] = 0.0f; rsum_all[SLAB + i] = 0.0f; rsum_all[2 * SLAB + i] = 0.0f; rsum_all[3 * SLAB + i] = 0.0f;
+        // One wave per SIMD: 16 bytes per access -- a slab is a whole number of them and so is a patch (p.patches is 16-byte
+        // aligned), 2 passes over the 64 x 16 tile's slabs instead of 7.  (Two waves per SIMD: a dword, as before -- the
+        // wider form added scratch to a 256-register reverse stage when tried.)  Element by element the same sum either way.
+        typedef __attribute__((ext_vector_type(4))) float f32x4;
+        using PV = std::conditional_t<WY == 2, f32x4, float>;
+        constexpr int NV = SLAB * 4 / (int)sizeof(PV);
+        static_assert(SLAB * 4 % sizeof(PV) == 0 && LDS_RT % sizeof(PV) == 0, "slabs and patches are whole vectors");
+        PV *patch = reinterpret_cast<PV *>(p.patches + (size_t)tile * SLAB);
+        PV *rs = reinterpret_cast<PV *>(rsum_all);
+        for (int i = tid; i < NV; i += NT) {
+            patch[i] = (rs[i] + rs[NV + i]) + (rs[2 * NV + i] + rs[3 * NV + i]);
+            rs[i] = (PV)(0.0f); rs[NV + i] = (PV)(0.0f); rs[2 * NV + i] = (PV)(0.0f); rs[3 * NV + i] = (PV)(0.0f);
         }
     }
-    stage_store();                           // next tile's thin copies (registers loaded above)
+    stage_store();                           // next tile's thin copies (registers loaded in front of the row loop)
     if constexpr (DA) stage2_store();
     }   // tile loop
     if constexpr (DA) {
@@ -1629,7 +1673,7 @@ int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t s
 template <int WY>
 int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map, const void *frags,
               float *du_out, float *patches, float *dtau_partial, int do_synth, int precision, const float *r2,
-              float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr)
+              float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr, bool drop_out = false)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
@@ -1643,6 +1687,7 @@ int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const uns
     p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
     p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0;
     p.r2 = r2; p.da_partial = workspace;
+    p.drop_zout = drop_out ? 1 : 0;
     int rc = dispatch_stage<WY>(g, p, MODE_BWD, f, S(stream));
     if (rc || !r2) return rc;
     const WgradReduce job = {workspace, stage_grid(g, p), dA, nullptr, alpha, 0.0f, 0};
@@ -1838,10 +1883,13 @@ int backward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask,
         const bool ride = Shape<WY>::TH == GW_TH && cdl_opts().fused_da;
         SweepReduce red = {};
         {
+            // with the ride nobody reads du_0 from memory (dA_0 and the patches for dyp come out of the stage's registers, and
+            // no stage follows): the last stage does not write it -- one fat write per sweep less
             TimingScope ts(1, S(stream));
             rc = stage_bwd<WY>(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
                                sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
-                               ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0]);
+                               ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0],
+                               ride && k == 0);
         }
         if (rc) return rc;
         if (ride) red.wblocks[0] = wgrad_reduce_blocks(red.w[0], M, g->Ph);

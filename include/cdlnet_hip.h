@@ -666,7 +666,8 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
  * xp receives D z_K.  frags: K * cdl_fused2d_frag_bytes(M) bytes (every pair is prepared up front, one launch).
  * Backward (net.py forward lines in reverse): z[k] = z_{k+1}, r[k] = r_{k+1}, maps[k] as saved by the forward,
  * g_xp = dL/d(D z_K), g_z = dL/dz_K or NULL; writes dA[k], dB[k] (filter shapes) and dt (K,2,M);
- * du0/du1 fat scratch, q thin scratch, dtau_partial (tiles x M), wgrad_ws (workspace_floats).
+ * du0/du1 fat scratch (contents unspecified on return: when dA_0 rides in the last stage, du_0 is never written),
+ * q thin scratch, dtau_partial (tiles x M), wgrad_ws (workspace_floats).
  * Per iteration four launches: stage (with dA_k's partials), assemble, dB_k's partials, and ONE reduction of dA_k, dB_k
  * and dt[k] -- each summed in the order of its stand-alone entry point (bit-identical to them).
  * The gradients of the data, as cdl_ista_backward's (both NULL: neither is computed): dyp (thin, nullable) receives
