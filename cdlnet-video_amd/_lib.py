@@ -67,6 +67,7 @@ SIGNATURES = {
     "cdl_csr_tangent_forward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P],
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_mad_cells": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _I, _P],
+    "cdl_nle_nlf_bins": [_P, _P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _F, _F, _P],
     "cdl_nle_pca_gram": [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_nle_pca_gram_cells": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
     "cdl_ssim_fwd": [_P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
@@ -130,6 +131,7 @@ SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G
                 "cdl_wgrad_workspace_floats": [_G], "cdl_prox_csr_scratch_floats": [_G],
                 "cdl_synthesis_workspace_floats": [_G], "cdl_ista_scratch_floats": [_G], "cdl_analysis_workspace_floats": [_G], "cdl_analysis_rev_workspace_floats": [_G],
                 "cdl_nle_mad_scratch_floats": [_I, _I, _I, _I], "cdl_nle_mad_cells_scratch_floats": [_I, _I, _I, _I],
+                "cdl_nle_nlf_bins_scratch_floats": [_I, _I, _I, _I],
                 "cdl_nle_pca_scratch_floats": [_I, _I, _I, _I, _I], "cdl_nle_pca_gram_cells_scratch_floats": [_I] * 7,
                 "cdl_residual_scratch_floats": [_G],
                 "cdl_ssim_scratch_floats": [_I, _I, _I, _I], "cdl_msssim_pyramid_floats": [_I, _I, _I, _I],

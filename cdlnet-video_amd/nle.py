@@ -8,7 +8,9 @@ channel, the second moment of the weak-texture patches in one HIP sweep (cdl_nle
 p^2 x p^2 eigenvalue problem and the constants of the patch size.  `nle_pca_cells`, `nle_pca_map` and `nle_pca_frames`
 are that estimate per region and per frame: every cell of a regular grid its own domain, all
 Grams of a pass from one launch chain (cdl_nle_pca_gram_cells); `noise_level_map` dispatches between the two map
-estimators.
+estimators.  `nlf_bins`, `nlf_fit_bins`, `nlf_fit` and `nlf_map` estimate signal-dependent noise, var(y | x) = a x + b
+(DESIGN.md section 29): the band of the MAD estimate binned by local intensity on the device (cdl_nle_nlf_bins), a
+constrained line fit of the bins' variances, and the map sqrt(a m + b) the nets take.
 """
 import functools
 import math
@@ -149,6 +151,146 @@ def nle_mad_map(y, window=32, step=None, s=1):
     H, W = imgs.shape[-2:]
     img_map = _interpolate(_cells(imgs, window, step), H, W, window, step).reshape(lead + (H, W))
     return utils.sigma_to_code_grid(img_map, s)
+
+
+# ------------------------------------------------- signal-dependent noise: var(y | x) = a x + b
+NLF_TINY = 1e-12                       # floor of a variance inside a weight of the fit
+
+
+def _nlf_args(bins, lo, hi):
+    if int(bins) != bins or bins < 1:
+        raise ValueError(f"bins {bins!r}: expected an integer >= 1")
+    lo, hi = float(lo), float(hi)
+    if not hi > lo:
+        raise ValueError(f"hi {hi!r} <= lo {lo!r}: the bins need a range")
+    return int(bins), lo, hi
+
+
+def _nlf_centres(bins, lo, hi, device):
+    return lo + (torch.arange(bins, device=device, dtype=torch.float64) + 0.5) * ((hi - lo) / bins)
+
+
+def _nlf_images(y, pool_frames, name):
+    """(images (B,C',H,W), leading shape, leading shape of a fit): with pool_frames the frames of a clip join the
+    channel axis (a reshape), so every selection pools the whole clip."""
+    if pool_frames and torch.is_tensor(y) and y.dim() == 5:
+        imgs, _ = _frames(y.reshape((y.shape[0], -1) + tuple(y.shape[3:])), name)
+        return imgs, (y.shape[0], 1), (y.shape[0], 1, 1)
+    imgs, lead = _frames(y, name)
+    return imgs, lead, lead
+
+
+def _nlf_bins(imgs, bins, lo, hi):
+    """cdl_nle_nlf_bins on images (B,C,H,W): (sigma (B, bins) float32, count (B, bins) int32)."""
+    B, C, H, W = imgs.shape
+    n = int(_lib.lib().cdl_nle_nlf_bins_scratch_floats(B, C, H, W))
+    scratch = ops._scratch(imgs.device, n)
+    sigma = torch.empty((B, bins), device=imgs.device, dtype=torch.float32)
+    count = torch.empty((B, bins), device=imgs.device, dtype=torch.int32)
+    ops._call("cdl_nle_nlf_bins", imgs, sigma, count, scratch, n, B, C, H, W, bins, lo, hi)
+    return sigma, count
+
+
+def nlf_bins(y, bins=32, lo=0.0, hi=1.0, pool_frames=False):
+    """The noise level of y by local intensity instead of position: (sigma, count, centre).  Every sample of the band
+    of nle_mad carries d = |HHy| and m, the mean of the 7 x 7 pixels under the filter's non-zero taps; `bins` equal
+    bins on [lo, hi) collect the samples by m (all channels pool; m outside [lo, hi) belongs to no bin), and
+    sigma[..., k] is the lower median of d over bin k / 0.6745, count[..., k] (int32) the number of its members, an
+    empty bin 0 and 0; centre (bins,) float64 are the bins' centres.  y (N,C,H,W) gives (N,1,bins); a clip
+    (N,C,D,H,W) gives (N,1,D,bins), every frame on its own, or (N,1,bins) with pool_frames, the whole clip in one set
+    of bins (a sensor's noise-level function does not change within a clip).  In y's scale; exact selection, repeated
+    calls return the same bits; no copy to the host."""
+    bins, lo, hi = _nlf_args(bins, lo, hi)
+    imgs, lead, _ = _nlf_images(y, pool_frames, "nlf_bins")
+    sigma, count = _nlf_bins(imgs, bins, lo, hi)
+    centre = _nlf_centres(bins, lo, hi, imgs.device)
+    return sigma.reshape(lead + (bins,)), count.reshape(lead + (bins,)), centre
+
+
+def nlf_fit_bins(sigma, count, centre, min_count=64, iters=2, fallback=None):
+    """(a, b) of var = a x + b from the bins of nlf_bins, float64, shaped like sigma without its last axis.  Plain
+    torch on whatever device the bins are on, batched, no copy to the host:
+      1. only bins with count >= min_count (and at least one member) are used;
+      2. weighted least squares of v = sigma^2 against x = centre with w = count / max(v, tiny)^2 (the variance of a
+         bin's v is proportional to v^2 / count);
+      3. `iters` reweightings with w = count / max(a x + b, tiny)^2, the fitted variance in place of the noisy one;
+      4. after every solve the constraints a >= 0, b >= 0: a < 0 gives a = 0, b = sum(w v) / sum(w); otherwise b < 0
+         gives b = 0, a = sum(w x v) / sum(w x x);
+      5. fewer than two usable bins: a = 0 and b the usable bin's v; none: b = fallback (a variance, broadcast against
+         the result; None: 0)."""
+    v = sigma.double() ** 2
+    x = centre.double().expand_as(v)
+    use = (count >= max(int(min_count), 1))
+    cnt = torch.where(use, count.double(), torch.zeros_like(v))
+    nuse = use.sum(dim=-1)
+
+    def solve(var):
+        w = cnt / var.clamp(min=NLF_TINY) ** 2
+        w = w / w.amax(dim=-1, keepdim=True).clamp(min=1e-300)        # the fit does not depend on the scale of w
+        sw, swx, swxx = w.sum(-1), (w * x).sum(-1), (w * x * x).sum(-1)
+        swv, swxv = (w * v).sum(-1), (w * x * v).sum(-1)
+        det = sw * swxx - swx * swx
+        det = torch.where(nuse >= 2, det, torch.ones_like(det))
+        a, b = (sw * swxv - swx * swv) / det, (swxx * swv - swx * swxv) / det
+        zero = torch.zeros_like(a)
+        flat = swv / sw.clamp(min=1e-300)
+        through = swxv / swxx.clamp(min=1e-300)
+        neg_a, neg_b = a < 0, (a >= 0) & (b < 0)
+        a, b = torch.where(neg_a, zero, torch.where(neg_b, through, a)), torch.where(neg_a, flat, torch.where(neg_b, zero, b))
+        return a, b
+
+    a, b = solve(v)
+    for _ in range(int(iters)):
+        a, b = solve(a[..., None] * x + b[..., None])
+    one = torch.where(use, v, torch.zeros_like(v)).sum(-1)              # the usable bin's variance where there is one
+    fb = torch.zeros_like(one) if fallback is None else torch.as_tensor(fallback, dtype=torch.float64, device=v.device).expand_as(one)
+    a = torch.where(nuse >= 2, a, torch.zeros_like(a))
+    b = torch.where(nuse >= 2, b, torch.where(nuse == 1, one, fb))
+    return a, b
+
+
+def nlf_fit(y, bins=32, lo=0.0, hi=1.0, min_count=64, iters=2, pool_frames=False):
+    """The noise-level function var(y | x) = a x + b of Poisson-Gaussian noise, blind: (a, b), float32, each (N,1,1,1)
+    for y (N,C,H,W) and (N,1,D,1,1) for a clip (N,C,D,H,W), a fit per frame, or (N,1,1,1,1) with pool_frames, one fit
+    for the clip.  nlf_bins, then nlf_fit_bins with the square of the image's MAD estimate (nle_mad) where no bin is
+    usable.  a, b >= 0.  In y's scale (b a variance, a a variance per unit of intensity); no copy to the host, no
+    synchronisation."""
+    bins, lo, hi = _nlf_args(bins, lo, hi)
+    imgs, _, lead = _nlf_images(y, pool_frames, "nlf_fit")
+    sigma, count = _nlf_bins(imgs, bins, lo, hi)
+    centre = _nlf_centres(bins, lo, hi, imgs.device)
+    mad = nle_mad(imgs).reshape(-1)
+    a, b = nlf_fit_bins(sigma, count, centre, min_count, iters, fallback=mad.double() ** 2)
+    shape = lead + (1, 1)
+    return a.float().reshape(shape), b.float().reshape(shape)
+
+
+def nlf_map(y, a=None, b=None, s=1, smooth=7, floor=1e-3, **fit_kw):
+    """A blind noise-level map for signal-dependent noise, `net(y, 255 * nlf_map(y, s=net.s))`: the noise-level function
+    (a, b) -- given, or fitted by nlf_fit(y, **fit_kw) when a is None -- evaluated on the local intensity,
+    sigma_img = sqrt(max(a m + b, floor^2)) with m the channel mean of y smoothed by a `smooth` x `smooth` box (odd;
+    reflect padding) at the image grid, then taken to the code grid of a stride-`s` net by utils.sigma_to_code_grid.
+    y (N,C,H,W) gives (N,1,ceil(H/s),ceil(W/s)), a clip (N,C,D,H,W) a map per frame on the clip's code grid.  In y's
+    scale; thin torch ops, no copy to the host, no synchronisation."""
+    if int(smooth) != smooth or smooth < 1 or smooth % 2 == 0:
+        raise ValueError(f"smooth {smooth!r}: expected an odd integer >= 1")
+    if (a is None) != (b is None):
+        raise ValueError("a and b are given together or not at all")
+    if a is None:
+        a, b = nlf_fit(y, **fit_kw)
+    elif fit_kw:
+        raise TypeError(f"nlf_map: {sorted(fit_kw)} belong to the fit, but a and b were given")
+    imgs, lead = _frames(y, "nlf_map")                               # a clip: its frames, (N*D, C, H, W)
+    H, W = imgs.shape[-2:]
+    r = int(smooth) // 2
+    if r >= min(H, W):
+        raise ValueError(f"smooth {smooth}: the reflect padding needs an image larger than {r} pixels")
+    m = imgs.mean(dim=1, keepdim=True)
+    if r:
+        m = torch.nn.functional.avg_pool2d(torch.nn.functional.pad(m, (r, r, r, r), mode="reflect"), int(smooth), stride=1)
+    m = m.reshape(lead + (H, W))
+    var = a * m + b                                                   # numbers, or device tensors that broadcast
+    return utils.sigma_to_code_grid(var.clamp(min=float(floor) ** 2).sqrt().float(), s)
 
 
 def _derivative_matrix(p, horizontal):

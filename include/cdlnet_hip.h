@@ -345,6 +345,18 @@ size_t cdl_nle_mad_cells_scratch_floats(int N, int C, int H, int W);
 int cdl_nle_mad_cells(const float *y, float *cells /*N x ny x nx*/, float *scratch, size_t scratch_floats, int N,
                       int C, int H, int W, int window, int step, void *stream);
 
+/* The noise-level function of signal-dependent noise, var(y | x) = a x + b: the same band
+ * binned by local intensity instead of position.  Band sample (i, j) carries d = |HHy| and the key m = the mean of
+ * the 7 x 7 pixels under the non-zero taps (rows 2i+2 .. 2i+8, columns 2j+2 .. 2j+8; an fp32 sum / 49).  With
+ * scale = (float)(bins / (hi - lo)) a sample belongs to bin k = (int)floorf((m - lo) * scale) if lo <= m < hi and
+ * k < bins, otherwise to none; all C channels of an image pool.  count_bins[n][k] = members (int32),
+ * sigma_bins[n][k] = their lower median of d (rank (count - 1) / 2) / 0.6745, exact; an empty bin gives 0, 0.
+ * Integer counting only: repeated calls are bit-identical.  CDL_EINVAL before any launch: null pointers, H or W <
+ * 10, bins < 1, hi <= lo, scratch too small.  scratch: cdl_nle_nlf_bins_scratch_floats(N,C,H,W) floats (two bands). */
+size_t cdl_nle_nlf_bins_scratch_floats(int N, int C, int H, int W);
+int cdl_nle_nlf_bins(const float *y, float *sigma_bins /*N x bins*/, int *count_bins /*N x bins*/, float *scratch,
+                     size_t scratch_floats, int N, int C, int H, int W, int bins, float lo, float hi, void *stream);
+
 /* model/nle.py:29-89 (nle_pca), the per-pass work of one channel: over every patchsize x patchsize patch of channel
  * `channel` of y (N,C,H,W), pooled over the batch, its texture strength Xtr (the sums of the squared half-differences
  * ((x[i][j] - x[i][j+2]) / 2)^2 over the patch's p x (p-2) window plus those along rows over its (p-2) x p window),
