@@ -302,9 +302,17 @@ __device__ __forceinline__ void blk_store4(float a0, float a1, float a2, float a
     constexpr int EB = LAY == LAY_BLK ? 16 : 8;
     const int soff = quad_pair * 32 * EB;
     if constexpr (LAY == LAY_BLK) {
+        // The quad's constant offset goes into the VECTOR offset (the compiler folds it into the instruction's immediate
+        // field, or one add), the scalar offset stays the literal 0.  A store of more than 64 bits reads its data registers
+        // late: a vector instruction that writes one of them needs a wait state behind the store.  The compiler's hazard
+        // recogniser pads that only when the store has no scalar-offset REGISTER; with the offset in an SGPR it let the
+        // reverse stage <M = 64, plain bf16, blocked -> blocked, no dA_k> refill a staging quad in the instruction after
+        // the store that read it, and du_k arrived with another quad's values, differently from call to call (DESIGN.md
+        // sections 6b and 30).  (voff = OOB plus these offsets stays beyond every descriptor.)
+        // Any further store of more than 8 bytes through a buffer descriptor must likewise keep its scalar offset an immediate.
         typedef __attribute__((ext_vector_type(4))) float f32x4;
         const f32x4 f = {a0, a1, a2, a3};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), rs, voff, soff, CDL_FAT_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), rs, voff + soff, 0, CDL_FAT_ST_AUX);
     } else {
         u32x2 u;
         u.x = (__builtin_bit_cast(unsigned, a0) >> 16) | (__builtin_bit_cast(unsigned, a1) & 0xffff0000u);

@@ -130,6 +130,11 @@ def test_fused2d_split4_and_fp32_scope_vs_oracle():
         _vs_oracle("fused2d split4", net, sd, x, y, sigma, mask, w, SPLIT_TOL)
     with loop.precision_scope("fp32"):            # no fused kernels: the generic sweep on the fp32 VALU kernels
         _vs_oracle("fp32 scope", net, sd, x, y, sigma, mask, w, FP32_TOL)
+    # four products at M = 64 in the default blocked layout (split4 ran at M = 32 only)
+    net, sd, x, y, sigma, mask, w = _case("2d", 13, (2, 1, 45, 39), 1, True, K=4, M=64, P=7)
+    assert ops.fused_supported(_geom(net, y, 1)) and loop.CODE_LAYOUT == "blocked"
+    with loop.precision_scope("split4"):
+        _vs_oracle("fused2d split4 M64 blocked", net, sd, x, y, sigma, mask, w, SPLIT_TOL)
 
 
 @pytest.mark.parametrize("label,kind,shape,s,masked,kw", [

@@ -354,16 +354,62 @@ def test_c_sweeps_match_stepwise_launches_at_one_iteration(layout):
     _sweeps_against_stepwise_launches(layout, 1)
 
 
-def _sweeps_against_stepwise_launches(layout, K):
+@pytest.mark.parametrize("M,P", [(64, 7), (32, 5)])
+@pytest.mark.parametrize("precision", ["split3", "bf16", "split4"])
+@pytest.mark.parametrize("layout", ["nchw", "blocked", "blocked_bf16"])
+def test_c_sweeps_equal_stepwise_launches_in_every_arithmetic(layout, precision, M, P):
+    """test_c_sweeps_are_bit_identical_to_stepwise_launches in the three arithmetics (loop.precision_scope) at M = 64 and 32:
+    bit for bit in the fp32 layouts, 5e-3 with bf16 code storage; the reverse sweep run twice is bit-identical."""
+    # (split3 at M = 64 and K = 4 is the test above: here the shortest sweep with an inner code)
+    _traced_sweeps(layout, 2 if (precision, M) == ("split3", 64) else 4, precision, M, P, ride=layout != "blocked_bf16")
+
+
+@pytest.mark.parametrize("M,P", [(64, 7), (32, 5)])
+@pytest.mark.parametrize("precision", ["split3", "bf16", "split4"])
+@pytest.mark.parametrize("layout", ["nchw", "blocked", "blocked_bf16"])
+def test_c_sweeps_without_the_da_ride_equal_stepwise_launches(layout, precision, M, P, hip_env):
+    """CDL_FUSED_DA=0: the reverse sweep launches the non-riding reverse stages and k_wgrad2d, as the step-wise loop does
+    (with plain-bf16 arithmetic, fp32 blocked storage and M = 64 the instance whose 16-byte stores were refilled too
+    early: DESIGN.md section 6b).  What is bit for bit in the fp32 layouts: the forward outputs and dt -- the sums of
+    -sign(z') du_k over every element, the only form in which a sweep exposes its du_k.  dA_k / dB_k stay at the 2e-6 of
+    the riding form: the sweep walks the tiles in snake order, which regroups k_wgrad2d's partial sums."""
+    hip_env("CDL_FUSED_DA", "0")
+    _traced_sweeps(layout, 3, precision, M, P, ride=False)
+
+
+def _traced_sweeps(layout, K, precision, M, P, ride):
+    """_sweeps_against_stepwise_launches under a launch trace: every stage launch in the arithmetic and width asked for,
+    dA_k riding in a reverse stage of the sweep or in none."""
+    import cdlnet_video_amd as cva
+    o = cva.ops
+    with o.trace() as t:
+        _sweeps_against_stepwise_launches(layout, K, precision, M, P)
+        torch.cuda.synchronize()
+    sites = launch_sites(t)
+    stages = {k: [r.template() for r in v] for k, v in sites.items() if k.startswith("cdl_fused2d.hip:k_stage<")}
+    assert stages and all(tp["PREC"] == o.PRECISION[precision] and tp["MT"] == M // 32 for v in stages.values() for tp in v), stages
+    assert any(",true," in k for k in stages) == ride, list(stages)
+    seen = sorted({(tp["WY"], tp["MODE"], tp["LIN"], tp["LOUT"], ",true," in k) for k, v in stages.items() for tp in v})
+    log(f"sweeps vs step-wise launches {layout} {precision} M{M}P{P} K{K} ride={ride}: MT={M // 32} PREC={o.PRECISION[precision]} "
+        f"(WY, MODE, LIN, LOUT, DA) launched: {seen}")
+
+
+def _sweeps_against_stepwise_launches(layout, K, precision="split3", M=64, P=7):
+    from cdlnet_video_amd import loop
+    with loop.precision_scope(precision):
+        _sweeps_against_stepwise_launches_in_scope(layout, K, M, P)
+
+
+def _sweeps_against_stepwise_launches_in_scope(layout, K, M, P):
     import cdlnet_video_amd as cva
     from cdlnet_video_amd import loop
     o = cva.ops
     torch.manual_seed(31)
-    M, P, N, H, W = 64, 7, 2, 40, 72
+    N, H, W = 2, 40, 72
     net = cva.CDLNet(K=K, M=M, P=P, s=1, C=1, t0=5e-3, adaptive=True, init=True).cuda()
     y = torch.rand(N, 1, H, W, generator=torch.Generator().manual_seed(1)).cuda()
     yp, mean, pads, _ = o.preprocess(y, 1, None)
-    g = o.Geometry.make(N, 1, M, (H, W), (P, P), (3, 3), 1)
+    g = o.Geometry.make(N, 1, M, (H, W), (P, P), (P // 2, P // 2), 1)
     c = torch.tensor([0.08, 0.11]).cuda()
     tau = o.thresholds(net.t.detach(), c, N)
     A = [m.weight.detach() for m in net.A]

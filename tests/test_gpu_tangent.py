@@ -91,6 +91,11 @@ def test_fused2d_split4_and_fp32_scope_vs_oracle():
         _vs_oracle("fused2d split4", net, sd, x, y, sigma, mask, SPLIT_TOL)
     with loop.precision_scope("fp32"):            # no fused kernels: the generic tangent sweep on the fp32 VALU kernels
         _vs_oracle("fp32 scope", net, sd, x, y, sigma, mask, FP32_TOL)
+    # four products at M = 64 in the default blocked layout (split4 ran at M = 32 only)
+    net, sd, x, y, sigma, mask, w = _case("2d", 13, (2, 1, 45, 39), 1, True, K=4, M=64, P=7)
+    assert ops.fused_supported(_geom(net, y, 1)) and loop.CODE_LAYOUT == "blocked"
+    with loop.precision_scope("split4"):
+        _vs_oracle("fused2d split4 M64 blocked", net, sd, x, y, sigma, mask, SPLIT_TOL)
 
 
 @pytest.mark.parametrize("label,kind,shape,s,masked,kw", [
@@ -273,6 +278,65 @@ def test_fused_stepwise_equals_the_c_sweep_and_launches_only_its_file(masked, la
     assert all(torch.equal(a, b) for a, b in zip(nchw(zd) + list(nrd), nchw(zs) + list(ns)))
     x0, z0, n0 = loop._tangent_fused(g, vp, mask_p, A, B, maps, False, layout=layout)       # ping-pong buffers
     assert torch.equal(x0, xdp) and z0 == [] and n0 == []
+
+
+@pytest.mark.parametrize("M,P", [(32, 5), (64, 7)])
+@pytest.mark.parametrize("precision", ["split3", "bf16", "split4"])
+@pytest.mark.parametrize("layout", ["nchw", "blocked"])
+def test_fused_tangent_sweep_in_every_arithmetic(layout, precision, M, P):
+    """The tangent sweep's stages are non-riding reverse stages in the sweep's layout (with plain-bf16 arithmetic, blocked
+    storage and M = 64 the instance of DESIGN.md section 6b): in every arithmetic the C sweep equals the step-wise launches
+    bit for bit, and run twice it is bit-identical."""
+    from cdlnet_video_amd import loop, ops
+    with loop.precision_scope(precision):
+        g, K, vp, mask_p, A, B, codes, maps, g_xp = _sweep_inputs(True, layout, M=M, P=P)
+        with ops.trace() as t:
+            xdp, zd, nrd = loop._tangent_fused(g, vp, mask_p, A, B, maps, True, layout=layout)
+            torch.cuda.synchronize()
+        xd2, zd2, nrd2 = loop._tangent_fused(g, vp, mask_p, A, B, maps, True, layout=layout)
+        xs, zs, ns = loop._tangent_fused_stepwise(g, vp, mask_p, A, B, maps, True, layout=layout)
+    assert t.files() == {"cdl_fused2d.hip"}, t.files()
+    stages = [r.template() for sid, recs in launch_sites(t).items() if "k_stage<" in sid for r in recs]
+    assert len(stages) == K and all((tp["MT"], tp["PREC"], tp["MODE"], tp["WY"]) == (M // 32, ops.PRECISION[precision], 2, 2)
+                                    for tp in stages), stages
+    log(f"tangent sweep {layout} {precision} M{M}P{P}: MT={M // 32} PREC={ops.PRECISION[precision]} (LIN, LOUT) launched "
+        f"{[(tp['LIN'], tp['LOUT']) for tp in stages]}")
+    nchw = lambda codes: [ops.fused_to_nchw(g, c, layout) for c in codes[:-1]] + [codes[-1]]    # image pixels only
+    first = [xdp] + nchw(zd) + list(nrd)
+    assert all(torch.equal(a, b) for a, b in zip(first, [xd2] + nchw(zd2) + list(nrd2))), "the sweep does not repeat itself"
+    assert all(torch.equal(a, b) for a, b in zip(first, [xs] + nchw(zs) + list(ns))), "sweep and step-wise launches differ"
+
+
+def test_bf16_arithmetic_m64_blocked_is_reproducible_through_the_net():
+    """Plain-bf16 arithmetic with the default blocked storage at M = 64: net.jvp plus backward, and a training backward, give
+    the same bits in a second call (what the arithmetic computes is held cell by cell in test_gpu_fused_cells.py)."""
+    from cdlnet_video_amd import loop, ops
+    net, sd, x, y, sigma, mask, w = _case("2d", 14, (2, 1, 45, 39), 1, True, K=4, M=64, P=7)
+    assert ops.fused_supported(_geom(net, y, 1)) and loop.CODE_LAYOUT == "blocked"
+    v, w1, w2 = _direction(y, mask, 43)
+    yc, sc, mc, xc = y.cuda(), sigma.cuda(), mask.cuda(), x.cuda()
+
+    def jvp_step():
+        net.zero_grad(set_to_none=True)
+        xhat, xdot = net.jvp(yc, v.cuda(), sc, mask=mc)
+        (torch.mean(w1.cuda() * xdot) + torch.mean((xhat - xc) ** 2)).backward()
+        return [xhat.detach(), xdot.detach()] + [gr.clone() for _, gr in sorted(_grads(net).items())]
+
+    def train_step():
+        net.zero_grad(set_to_none=True)
+        xhat, _ = net(yc, sc, mask=mc)
+        torch.mean((xhat - xc) ** 2).backward()
+        return [xhat.detach()] + [gr.clone() for _, gr in sorted(_grads(net).items())]
+
+    with loop.precision_scope("bf16"):
+        for step in (jvp_step, train_step):
+            with ops.trace() as t:
+                a = step()
+                torch.cuda.synchronize()
+            b = step()
+            stages = [r.template() for sid, recs in launch_sites(t).items() if "cdl_fused2d.hip:k_stage<" in sid for r in recs]
+            assert stages and all(tp["PREC"] == 1 and tp["MT"] == 2 for tp in stages), stages
+            assert len(a) == len(b) and all(torch.equal(p, q) for p, q in zip(a, b)), step.__name__
 
 
 @pytest.mark.parametrize("masked", [False, True])
