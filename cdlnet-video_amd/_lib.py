@@ -99,16 +99,16 @@ SIGNATURES = {
     "cdl_gabor_filter_banks_bwd": [_I, _P, _P, _P, _P, _IP, _P, _P, _I, _I, _I, _I, _P],
     "cdl_fused2d_supported": [_G],
     "cdl_fused2d_prep": [_P, _P, _P, _I, _I, _P],
-    "cdl_fused2d_iter_fwd": [_G, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P],
+    "cdl_fused2d_iter_fwd": [_G, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P, _P, _P],          # .., cmap, tslope, stream
     "cdl_fused2d_support_map": [_G, _P, _P, _P],
     "cdl_fused2d_timing": [_I],
     "cdl_fused2d_timing_read": [ctypes.POINTER(ctypes.c_double), _IP],
     "cdl_fused2d_assemble": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
-    "cdl_fused2d_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _I, _P],
-    "cdl_fused2d_dtau_reduce": [_G, _P, _P, _P, _P, _P, _P],
+    "cdl_fused2d_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _P, _F, _P, _P, _I, _P, _P, _P, _I, _P],   # .., cmap, tslope, dcmap, dcmap_add, stream
+    "cdl_fused2d_dtau_reduce": [_G, _P, _P, _P, _P, _P, _P, _P],                             # .., dtau_partial_w, stream
     "cdl_fused2d_wgrad": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, _I, _P],
-    "cdl_fused2d_forward": [_G, _I] + [_P] * 11 + [_I, _P],
-    "cdl_fused2d_backward": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P],
+    "cdl_fused2d_forward": [_G, _I] + [_P] * 11 + [_I, _P, _P, _P],                           # .., cmap, tslope, stream
+    "cdl_fused2d_backward": [_G, _I] + [_P] * 20 + [_I, _P, _P, _P, _P, _P, _P],              # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_fused2d_tangent": [_G, _I] + [_P] * 12 + [_I, _P],
     "cdl_fusedg_tangent": [_G, _I] + [_P] * 12 + [_I, _P],
     "cdl_fusedg_supported": [_G],
@@ -127,7 +127,7 @@ SIGNATURES = {
 }
 SIZE_T_FUNCS = {"cdl_fusedg_code_floats": [_G, _I], "cdl_fusedg_frag_bytes": [_G], "cdl_fusedg_patch_floats": [_G], "cdl_fusedg_tiles": [_G],
                 "cdl_fusedg_map_words": [_G], "cdl_fused2d_frag_bytes": [_I], "cdl_fused2d_patch_floats": [_G], "cdl_fused2d_code_bytes": [_G, _I],
-                "cdl_fused2d_tiles": [_G], "cdl_fused2d_map_words": [_G], "cdl_fused2d_wgrad_workspace_floats": [_G],
+                "cdl_fused2d_tiles": [_G], "cdl_fused2d_dtau_partial_floats": [_G, _I], "cdl_fused2d_map_words": [_G], "cdl_fused2d_wgrad_workspace_floats": [_G],
                 "cdl_wgrad_workspace_floats": [_G], "cdl_prox_csr_scratch_floats": [_G],
                 "cdl_synthesis_workspace_floats": [_G], "cdl_ista_scratch_floats": [_G], "cdl_analysis_workspace_floats": [_G], "cdl_analysis_rev_workspace_floats": [_G],
                 "cdl_nle_mad_scratch_floats": [_I, _I, _I, _I], "cdl_nle_mad_cells_scratch_floats": [_I, _I, _I, _I],

@@ -116,6 +116,21 @@ struct FusedParams {
     float *da_partial;       // (gridDim.x, 2, M, 64): per-workgroup partial of dA_k in operator slot 0 (k_wgrad_reduce's layout)
     int drop_zout;           // backward: zout is not written (the sweep's last stage: du_0 is consumed in registers only)
 };
+// What the noise-level map modes take on top (MODE_*_MAP).  The host fills one FusedMapParams per
+// launch; a kernel of another mode is declared with the base and receives the base part: its argument block is what it was.
+struct FusedMapParams : FusedParams {
+    const float *cmap;      // (N,H,W): forward threshold tau[n,m] + cmap[n,y,x] * tslope[m]; reverse: weight of the second partial
+    const float *tslope;     // (M): the slopes t[k,1,:]
+    float *dtau_w;           // backward: (numTiles, M) partial sums of -cmap * sign(z_{k+1}) * du_k, rows as dtau's
+    float *dcmap;            // backward, nullable: (N,H,W) dL/dcmap, = or += (dc_add) sum_m tslope[m] * (-sign(z_{k+1}) du_k)
+    int dc_add;
+};
+
+// The map modes are the three base modes with this bit set: the same kernel, a threshold per code element.
+// (ints, not an unnamed enum: MODE_MAP enters the kernels' mangled names through StageParams, and the host and device
+//  passes number unnamed types differently -- the host then registers a kernel name the code object does not hold)
+constexpr int MODE_MAP = 4, MODE_FWD_MAP = MODE_FWD | MODE_MAP, MODE_FIRST_MAP = MODE_FIRST | MODE_MAP, MODE_BWD_MAP = MODE_BWD | MODE_MAP;
+template <int MODE_M> using StageParams = std::conditional_t<(MODE_M & MODE_MAP) != 0, FusedMapParams, FusedParams>;
 
 // ------------------------------------------------------------------------------------------
 // Weight preparation: fp32 filters -> bf16 hi/lo MFMA A-operand fragments.
@@ -399,9 +414,16 @@ __device__ __forceinline__ void store_run_copies(__bf16 *dst, int copy_elems, co
 //   DA (reverse stage only): the filter gradient dA_k = du_k (x) im2col(r2) rides in the launch -- du_k is transposed per row
 //   block through wave-private LDS images exactly as k_wgrad2d does it, and accumulated in 2 x MT more accumulator tiles
 //   WY: the tile shape (Shape<WY>)
-template <int MT, int PREC, int MODE, int LIN, int LOUT, bool DA = false, int WY = 2>
-__global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
+//   MODE_M | MODE_MAP: a noise-level map.  Forward: p.tau holds t[k,0,:] (for every sample), the slopes
+//   t[k,1,:] sit in the lane's registers beside them and each lane loads cm = cmap[n,y,x] once per row block: the threshold of
+//   channel m at its pixel is cdl_map_threshold(t0[m], cm, t1[m]), the reference's bit for bit.  Reverse: a second, map-weighted
+//   set of threshold partials (p.dtau_w) and, with p.dcmap, dL/dcmap = sum_m t1[m] g[m] over the lane's channels and its
+//   partner half's.  Everything map-specific is behind `if constexpr (MAP)`: the other modes compile to what they were.
+template <int MT, int PREC, int MODE_M, int LIN, int LOUT, bool DA = false, int WY = 2>
+__global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
 {
+    constexpr int MODE = MODE_M & ~MODE_MAP;
+    constexpr bool MAP = (MODE_M & MODE_MAP) != 0;
     using G = Shape<WY>;
     constexpr int NW = G::NW, NT = G::NT, TH = G::TH, RTH = G::RTH, PITCH = G::PITCH, COPY = G::COPY, SLAB = G::SLAB;
     constexpr int LDS_RT = G::LDS_RT, LDS_RSUM = G::LDS_RSUM, LDS_STAGE = G::LDS_STAGE, LDS_DA_THIN = G::LDS_DA_THIN;
@@ -414,6 +436,10 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
     float *tacc_s = tau_s + 64;                                                   // backward: [wave][64]
     __bf16 *thin2 = reinterpret_cast<__bf16 *>(smem + LDS_STAGE);                 // DA: [hl][s][TCOPY] copies of r2's tile
     __bf16 *imgs2 = reinterpret_cast<__bf16 *>(smem + LDS_STAGE + LDS_DA_THIN);   // DA: [wave][R][hl][IMG_ELEMS]
+    // MAP: the slopes live where the mode has no use for the area -- forward: tacc_s[0..M), reverse: tau_s; the reverse's
+    // weighted [wave][64] sums behind everything else (stage_lds_bytes)
+    float *slope_s = MODE == MODE_BWD ? tau_s : tacc_s;
+    float *tacc_w_s = reinterpret_cast<float *>(smem + LDS_STAGE + (DA ? G::LDS_DA : 0));
 
     constexpr int M = 32 * MT;
     constexpr int FA = MT * 4, FB = 4 * MT;
@@ -434,6 +460,9 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
         } else {                                            // [A hi | B hi] compacted
             for (int i = tid; i < FA * 64; i += NT) wdst[i] = p.frags[i];
             for (int i = tid; i < FB * 64; i += NT) wdst[FA * 64 + i] = p.frags[2 * FA * 64 + i];
+        }
+        if constexpr (MAP) {
+            if (tid < M) slope_s[tid] = p.tslope[tid];       // one launch, one iteration: the slopes never change
         }
     }
     // thin-tile staging: registers first (so the next tile's loads fly during this tile's GEMMs), then
@@ -533,6 +562,23 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
         else return __builtin_bit_cast(bf16x8, wl[f * 64 + lane]);
     };
 
+    // MAP forward: this lane's 16 MT slopes, for the whole launch (the map's register cost: 16 MT), and whether every slope
+    // is a finite number >= 0 -- with t0 >= 0 and a finite map value >= 0 the threshold is then >= 0 (never NaN: no inf * 0)
+    constexpr bool MAP_FWD = MAP && MODE != MODE_BWD;
+    float tslr[MAP_FWD ? MT * 16 : 1];
+    bool slope_any = false;
+    if constexpr (MAP_FWD) {
+#pragma unroll
+        for (int R = 0; R < MT; ++R)
+#pragma unroll
+            for (int qv = 0; qv < 4; ++qv) {
+                const float4 s4 = *reinterpret_cast<const float4 *>(&slope_s[32 * R + 8 * qv + 4 * h]);
+                tslr[16 * R + 4 * qv + 0] = s4.x; tslr[16 * R + 4 * qv + 1] = s4.y;
+                tslr[16 * R + 4 * qv + 2] = s4.z; tslr[16 * R + 4 * qv + 3] = s4.w;
+            }
+        slope_any = __ballot(lane < M && !(slope_s[lane] >= 0.0f && slope_s[lane] < __builtin_inff())) != 0ull;
+    }
+
     const int xl = wxi * 32 + c;             // tile-local pixel column of this lane
     float *rsum = rsum_all + ((wxi & 1) + 2 * (wyi & 1)) * SLAB;
     const bool has_base = (MODE == MODE_FWD) || (MODE == MODE_BWD && p.zin != nullptr);
@@ -566,10 +612,16 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
     float tsum[MT * 16];                     // backward: per-lane partial threshold gradients
 #pragma unroll
     for (int i = 0; i < MT * 16; ++i) tsum[i] = 0.0f;
+    constexpr bool MAP_BWD = MAP && MODE == MODE_BWD;
+    float tsum_w[MAP_BWD ? MT * 16 : 1];     // MAP backward: the same partials weighted by the map (dt[k,1,:])
+    if constexpr (MAP_BWD) {
+#pragma unroll
+        for (int i = 0; i < MT * 16; ++i) tsum_w[i] = 0.0f;
+    }
     // thresholds are >= 0 whenever project() runs (net.py:70); a negative one (3-D trainer, never projected) sends
     // the whole tile through the general shrinkage -- wave-uniform, so the common case pays 3 instructions per
     // element (u - clamp(u, -t, t)) instead of 10
-    const bool tau_neg = MODE != MODE_BWD && __ballot(lane < M && !(tau_s[lane] >= 0.0f)) != 0ull;   // negative OR NaN: the general, NaN-preserving form
+    const bool tau_neg = (MODE != MODE_BWD && __ballot(lane < M && !(tau_s[lane] >= 0.0f)) != 0ull) || slope_any;   // negative OR NaN: the general, NaN-preserving form
     float taur[MT * 16];                     // forward: this lane's 16 MT thresholds
     if (MODE != MODE_BWD) {
 #pragma unroll
@@ -632,6 +684,10 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
         if (MODE == MODE_BWD && valid) {
             sup = map_n[(size_t)y * p.W + x];
             sgb = map_n[HW + (size_t)y * p.W + x];
+        }
+        float cm = 0.0f;                     // MAP: the noise-level map at this lane's pixel (0 outside the image)
+        if constexpr (MAP) {
+            if (valid) cm = p.cmap[(size_t)n * HW + (size_t)y * p.W + x];
         }
 
         // -- im2col fragments of the thin input: 8 consecutive rows yl..yl+7 of column xl + j
@@ -713,12 +769,15 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
                 if (MODE == MODE_BWD) {
                     const bool on = (sup >> (16 * R + v)) & 1u;         // never for out-of-image lanes
                     zz = on ? zbase + acc[R][v] : 0.0f;
-                    tsum[16 * R + v] += ((sgb >> (16 * R + v)) & 1u) ? zz : -zz;      // -sign(z') * du
+                    const float gt = ((sgb >> (16 * R + v)) & 1u) ? zz : -zz;        // -sign(z') * du
+                    tsum[16 * R + v] += gt;
+                    if constexpr (MAP_BWD) tsum_w[16 * R + v] = fmaf(cm, gt, tsum_w[16 * R + v]);
                 } else {
                     const float base = (MODE == MODE_FWD) ? zbase : 0.0f;
                     const float u = fmaf(p.sgn, acc[R][v], base);
                     // t >= 0: sign(u) relu(|u| - t) == u - clamp(u, -t, t) with the same rounding; NaN in u stays NaN
-                    const float tt = taur[16 * R + v];
+                    float tt = taur[16 * R + v];
+                    if constexpr (MAP_FWD) tt = cdl_map_threshold(tt, cm, tslr[16 * R + v]);
                     const float st = decltype(general_shrink)::value ? cdl_shrink(u, tt)
                                                                      : u - __builtin_amdgcn_fmed3f(u, -tt, tt);
                     zz = CDL_DBG(p.dbg, 64) ? u : (valid ? st : 0.0f);
@@ -728,7 +787,11 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
                 acc[R][v] = zz;
             }
         };
-        if (tau_neg) epilogue(std::true_type{});   // wave-uniform
+        // MAP: the clamp form needs every threshold of the row block >= 0 -- t0 and the slopes (tau_neg, per tile) and
+        // the map values of this row block (a ballot: negative, NaN and infinite ones go to the general form)
+        bool general = tau_neg;
+        if constexpr (MAP_FWD) general = general || __ballot(!(cm >= 0.0f && cm < __builtin_inff())) != 0ull;
+        if (general) epilogue(std::true_type{});   // wave-uniform
         else epilogue(std::false_type{});
         if (LOUT != LAY_NCHW) {
 #pragma unroll
@@ -751,6 +814,31 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
             if (valid && !CDL_DBG(p.dbg, 1)) {
                 map_n[(size_t)y * p.W + x] = ws;
                 map_n[HW + (size_t)y * p.W + x] = wg;
+            }
+        }
+        if constexpr (MAP_BWD) {
+            // dL/dcmap[n,y,x] (+)= sum_m t1[m] g[m], g = -sign(z') * du as in tsum: the lane's 16 MT channels (du_k stands in
+            // acc, the slopes come from LDS: two addresses per read, broadcast), plus the partner half's
+            if (p.dcmap) {                   // launch-uniform
+                float dcs = 0.0f;
+#pragma unroll
+                for (int R = 0; R < MT; ++R)
+#pragma unroll
+                    for (int qv = 0; qv < 4; ++qv) {
+                        const float4 s4 = *reinterpret_cast<const float4 *>(&slope_s[32 * R + 8 * qv + 4 * h]);
+                        const float sl[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int v = 4 * qv + e;
+                            const float zz = acc[R][v];
+                            dcs = fmaf(sl[e], ((sgb >> (16 * R + v)) & 1u) ? zz : -zz, dcs);
+                        }
+                    }
+                dcs += __shfl_xor(dcs, 32, 64);
+                if (h == 0 && valid) {
+                    float *dst = p.dcmap + (size_t)n * HW + (size_t)y * p.W + x;
+                    *dst = p.dc_add ? *dst + dcs : dcs;
+                }
             }
         }
         if constexpr (DA) {
@@ -922,6 +1010,13 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
             const int R = c >> 4, v = c & 15;
             tacc_s[wid * 64 + 32 * R + 8 * (v >> 2) + 4 * h + (v & 3)] = tacc;
         }
+        if constexpr (MAP_BWD) {             // the weighted sums take the same road, into their own [wave][64]
+            const float taccw = lane_transpose_sum(tsum_w, c);
+            if (c < MT * 16) {
+                const int R = c >> 4, v = c & 15;
+                tacc_w_s[wid * 64 + 32 * R + 8 * (v >> 2) + 4 * h + (v & 3)] = taccw;
+            }
+        }
     }
     __syncthreads();                         // every wave is done with the thin copies and the slabs
     if (!LOAD_AHEAD) stage_load(t + gridDim.x);
@@ -930,6 +1025,12 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(FusedParams p)
 #pragma unroll
         for (int w = 0; w < NW; ++w) sacc += tacc_s[w * 64 + tid];
         p.dtau[(size_t)tile * M + tid] = sacc;
+        if constexpr (MAP_BWD) {
+            float saccw = 0.0f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) saccw += tacc_w_s[w * 64 + tid];
+            p.dtau_w[(size_t)tile * M + tid] = saccw;
+        }
     }
     if CDL_DBG(p.dbg, 128) continue;
     if (MODE != MODE_BWD || p.do_synth) {    // patch out (fixed slab order), slabs re-zeroed for the next tile
@@ -1443,16 +1544,23 @@ struct DtauReduce {
     const float *c;
     float *dt0, *dt1;
     int N, per_img;
+    const float *partial_w;  // nullable, never with c: the map-weighted partials (rows as partial's); dt1[m] = their sum
 };
 __device__ __forceinline__ void dtau_reduce_block(float (*r0)[4], float (*r1)[4], int block, const DtauReduce &q, int M)
 {
     const float *__restrict__ partial = q.partial;
     const float *__restrict__ c = q.c;
+    const float *__restrict__ pw = q.partial_w;
     const int mi = threadIdx.x & 3, part = threadIdx.x >> 2;
     const int m = block * 4 + mi;
     float a0 = 0.0f, a1 = 0.0f;
     const int rows = q.N * q.per_img;
-    if (m < M)
+    if (m < M && pw) {
+        for (int row = part; row < rows; row += 256) {
+            a0 += partial[(size_t)row * M + m];
+            a1 += pw[(size_t)row * M + m];
+        }
+    } else if (m < M)
         for (int row = part; row < rows; row += 256) {
             const float v = partial[(size_t)row * M + m];
             a0 += v;
@@ -1534,21 +1642,23 @@ inline Flags parse_flags(int precision)
 }
 
 template <int WY, int MT, int PREC, int MODE, int LIN, int LOUT>
-int launch_stage_one(const FusedParams &p, dim3 grid, hipStream_t st)
+int launch_stage_one(const FusedMapParams &p, dim3 grid, hipStream_t st)
 {
     using G = Shape<WY>;
+    constexpr int BASE = MODE & ~MODE_MAP;
+    constexpr int LDS_MAP = MODE == MODE_BWD_MAP ? G::LDS_TACC : 0;        // the weighted [wave][64] sums, behind the rest
     // (blocked in, NCHW out) is the tangent sweep's last stage, which carries no dA ride: no such instance of it
-    if constexpr (MODE == MODE_BWD && G::TH == GW_TH && !(LIN == LAY_BLK && LOUT == LAY_NCHW)) {
+    if constexpr (BASE == MODE_BWD && G::TH == GW_TH && !(LIN == LAY_BLK && LOUT == LAY_NCHW)) {
         if (p.r2) {                                          // the reverse stage that also accumulates dA_k
-            if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true, WY>, G::LDS_STAGE + G::LDS_DA)) return rc;
-            k_stage<MT, PREC, MODE, LIN, LOUT, true, WY><<<grid, G::NT, G::LDS_STAGE + G::LDS_DA, st>>>(p);
+            if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, true, WY>, G::LDS_STAGE + G::LDS_DA + LDS_MAP)) return rc;
+            k_stage<MT, PREC, MODE, LIN, LOUT, true, WY><<<grid, G::NT, G::LDS_STAGE + G::LDS_DA + LDS_MAP, st>>>(p);
             CDL_LAUNCH_CHECK();
             return 0;
         }
     }
     if (p.r2) return CDL_EUNSUPPORTED;
-    if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, false, WY>, G::LDS_STAGE)) return rc;
-    k_stage<MT, PREC, MODE, LIN, LOUT, false, WY><<<grid, G::NT, G::LDS_STAGE, st>>>(p);
+    if (int rc = cdl_ensure_dynamic_lds((const void *)k_stage<MT, PREC, MODE, LIN, LOUT, false, WY>, G::LDS_STAGE + LDS_MAP)) return rc;
+    k_stage<MT, PREC, MODE, LIN, LOUT, false, WY><<<grid, G::NT, G::LDS_STAGE + LDS_MAP, st>>>(p);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -1559,42 +1669,57 @@ int launch_stage_one(const FusedParams &p, dim3 grid, hipStream_t st)
 //   FIRST (BLK16, BLK16) k = 0 of K > 1     FWD (BLK16, BLK16) 0 < k < K-1     BWD (NCHW, BLK16)  k = K-1
 //   FIRST (NCHW, NCHW)   k = 0 of K = 1     FWD (BLK16, NCHW)  k = K-1 > 0     BWD (BLK16, BLK16) k < K-1
 template <int WY, int MT, int PREC, int MODE>
-int launch_stage_lay(const FusedParams &p, int lin, int lout, dim3 grid, hipStream_t st)
+int launch_stage_lay(const FusedMapParams &p, int lin, int lout, dim3 grid, hipStream_t st)
 {
-    if (MODE == MODE_FIRST) lin = lout;
+    if ((MODE & ~MODE_MAP) == MODE_FIRST) lin = lout;
 #define CDL_LAY_CASE(a, b) if (lin == a && lout == b) return launch_stage_one<WY, MT, PREC, MODE, a, b>(p, grid, st)
-    if constexpr (WY == 2 || MODE == MODE_FIRST) CDL_LAY_CASE(LAY_NCHW, LAY_NCHW);
-    if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_BLK);
-    CDL_LAY_CASE(LAY_BLK16, LAY_BLK16);
-    if constexpr (MODE == MODE_FWD) {
-        if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);
-        CDL_LAY_CASE(LAY_BLK16, LAY_NCHW);
-    }
-    if constexpr (MODE == MODE_BWD) {
-        if constexpr (WY == 2) CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
-        if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);      // the tangent sweep's last stage: zd_K leaves it as NCHW
-        CDL_LAY_CASE(LAY_NCHW, LAY_BLK16);
+    // A noise-level map: 64 x 16 tiles, split3 and fp32 storage only, in the layout pairs a default sweep launches --
+    //   FIRST (NCHW, NCHW) (BLK, BLK)     FWD (NCHW, NCHW) (BLK, BLK) (BLK, NCHW)     BWD (NCHW, NCHW) (BLK, BLK) (NCHW, BLK)
+    if constexpr ((MODE & MODE_MAP) != 0) {
+        if constexpr (WY == 2 && PREC == 0) {
+            CDL_LAY_CASE(LAY_NCHW, LAY_NCHW);
+            CDL_LAY_CASE(LAY_BLK, LAY_BLK);
+            if constexpr (MODE == MODE_FWD_MAP) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);
+            if constexpr (MODE == MODE_BWD_MAP) CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
+        }
+        return CDL_EUNSUPPORTED;
+    } else {
+        if constexpr (WY == 2 || MODE == MODE_FIRST) CDL_LAY_CASE(LAY_NCHW, LAY_NCHW);
+        if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_BLK);
+        CDL_LAY_CASE(LAY_BLK16, LAY_BLK16);
+        if constexpr (MODE == MODE_FWD) {
+            if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);
+            CDL_LAY_CASE(LAY_BLK16, LAY_NCHW);
+        }
+        if constexpr (MODE == MODE_BWD) {
+            if constexpr (WY == 2) CDL_LAY_CASE(LAY_NCHW, LAY_BLK);
+            if constexpr (WY == 2) CDL_LAY_CASE(LAY_BLK, LAY_NCHW);      // the tangent sweep's last stage: zd_K leaves it as NCHW
+            CDL_LAY_CASE(LAY_NCHW, LAY_BLK16);
+        }
+        return CDL_EUNSUPPORTED;
     }
 #undef CDL_LAY_CASE
-    return CDL_EUNSUPPORTED;
 }
 
 template <int WY, int MT, int PREC>
-int launch_stage(const FusedParams &p, int mode, int lin, int lout, dim3 grid, hipStream_t st)
+int launch_stage(const FusedMapParams &p, int mode, int lin, int lout, dim3 grid, hipStream_t st)
 {
     if (mode == MODE_FWD) return launch_stage_lay<WY, MT, PREC, MODE_FWD>(p, lin, lout, grid, st);
     if (mode == MODE_FIRST) return launch_stage_lay<WY, MT, PREC, MODE_FIRST>(p, lin, lout, grid, st);
+    if (mode == MODE_FWD_MAP) return launch_stage_lay<WY, MT, PREC, MODE_FWD_MAP>(p, lin, lout, grid, st);
+    if (mode == MODE_FIRST_MAP) return launch_stage_lay<WY, MT, PREC, MODE_FIRST_MAP>(p, lin, lout, grid, st);
+    if (mode == MODE_BWD_MAP) return launch_stage_lay<WY, MT, PREC, MODE_BWD_MAP>(p, lin, lout, grid, st);
     return launch_stage_lay<WY, MT, PREC, MODE_BWD>(p, lin, lout, grid, st);
 }
 
 // persistent workgroups: one per CU (most of its LDS each), striding over the tiles
-int stage_grid(const cdl_geom *, const FusedParams &p)
+int stage_grid(const cdl_geom *, const FusedMapParams &p)
 {
     return (int)cdl_persistent_grid((size_t)p.N * p.tilesX * p.tilesY);
 }
 
 template <int WY>
-int dispatch_stage(const cdl_geom *g, const FusedParams &p, int mode, const Flags &f, hipStream_t st)
+int dispatch_stage(const cdl_geom *g, const FusedMapParams &p, int mode, const Flags &f, hipStream_t st)
 {
     dim3 grid((unsigned)stage_grid(g, p));
     if (g->M == 64)
@@ -1641,9 +1766,9 @@ template <int WY> inline size_t shape_tiles(const cdl_geom *g) { return (size_t)
 // ---- the bodies behind the entry points that depend on the tile shape ------------------------------------
 // what every stage launch sets, forward or reverse
 template <int WY>
-FusedParams stage_params(const cdl_geom *g, const Flags &f, const void *frags, float *patches)
+FusedMapParams stage_params(const cdl_geom *g, const Flags &f, const void *frags, float *patches)
 {
-    FusedParams p = {};
+    FusedMapParams p = {};
     p.rev = f.rev;
     p.frags = reinterpret_cast<const uint4 *>(frags);
     p.patches = patches; CDL_DBG_FIELD(p.dbg = debug_flags();)
@@ -1654,18 +1779,20 @@ FusedParams stage_params(const cdl_geom *g, const Flags &f, const void *frags, f
 
 template <int WY>
 int iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *tau, const void *frags, float sgn,
-             float *zout, float *patches, unsigned *map_out, int precision, void *stream)
+             float *zout, float *patches, unsigned *map_out, int precision, void *stream, const float *cmap = nullptr,
+             const float *tslope = nullptr)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!r || !tau || !frags || !zout || !patches || zout == zin) return CDL_EINVAL;
+    if (!r || !tau || !frags || !zout || !patches || zout == zin || !cmap != !tslope) return CDL_EINVAL;
     if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     const Flags f = parse_flags(precision);
     if (!f.ok) return CDL_EINVAL;
     if ((f.lin && !cdl_aligned16(zin)) || (f.lout && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;     // blocked codes: 16-byte accesses
-    FusedParams p = stage_params<WY>(g, f, frags, patches);
+    FusedMapParams p = stage_params<WY>(g, f, frags, patches);
     p.r = r; p.zin = zin; p.zout = zout; p.tau = tau; p.map = map_out;
     p.sgn = sgn; p.do_synth = 1;
-    return dispatch_stage<WY>(g, p, zin ? MODE_FWD : MODE_FIRST, f, S(stream));
+    p.cmap = cmap; p.tslope = tslope;
+    return dispatch_stage<WY>(g, p, (zin ? MODE_FWD : MODE_FIRST) | (cmap ? MODE_MAP : 0), f, S(stream));
 }
 
 int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t st)
@@ -1678,25 +1805,39 @@ int launch_wgrad_reduce(const cdl_geom *g, const WgradReduce &job, hipStream_t s
 // r2 != nullptr: the launch also produces dA = alpha * du_out (x) im2col(r2) (cdl_fused2d_wgrad's first operator pair, same
 // arithmetic), through `workspace` (cdl_fused2d_wgrad_workspace_floats) -- one fat read of du_out less than the two-launch form
 // defer: the reduction of the dA partials is not launched but described there
+// A noise-level map in a reverse stage: the forward's map and slopes, dL/dcmap (nullable; add: accumulated, else written).
+// With a map dtau_partial holds cdl_fused2d_dtau_partial_floats(g, 1) floats -- two arrays of cdl_fused2d_tiles(g) * M:
+// the plain partials, then the weighted ones.
+struct MapBwd {
+    const float *cmap, *tslope;
+    float *dcmap;
+    int add;
+};
+inline float *weighted_partials(const cdl_geom *g, float *dtau_partial) { return dtau_partial + cdl_fused2d_tiles(g) * g->M; }
+
 template <int WY>
 int stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map, const void *frags,
               float *du_out, float *patches, float *dtau_partial, int do_synth, int precision, const float *r2,
-              float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr, bool drop_out = false)
+              float alpha, float *dA, float *workspace, void *stream, WgradReduce *defer = nullptr, bool drop_out = false,
+              const MapBwd &mb = MapBwd{})
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (!thin || !map || !frags || !du_out || !dtau_partial || du_out == base) return CDL_EINVAL;
+    if (!mb.cmap != !mb.tslope || (mb.dcmap && !mb.cmap)) return CDL_EINVAL;
     if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     if (do_synth && !patches) return CDL_EINVAL;
     if (r2 && (!dA || !workspace)) return CDL_EINVAL;
     const Flags f = parse_flags(precision);
     if (!f.ok) return CDL_EINVAL;
     if ((f.lin && !cdl_aligned16(base)) || (f.lout && !cdl_aligned16(du_out))) return CDL_EUNSUPPORTED;  // blocked codes: 16-byte accesses
-    FusedParams p = stage_params<WY>(g, f, frags, patches);
+    FusedMapParams p = stage_params<WY>(g, f, frags, patches);
     p.r = thin; p.zin = base; p.map = const_cast<unsigned *>(map); p.zout = du_out; p.dtau = dtau_partial;
     p.sgn = 1.0f; p.do_synth = do_synth ? 1 : 0;
     p.r2 = r2; p.da_partial = workspace;
     p.drop_zout = drop_out ? 1 : 0;
-    int rc = dispatch_stage<WY>(g, p, MODE_BWD, f, S(stream));
+    p.cmap = mb.cmap; p.tslope = mb.tslope; p.dcmap = mb.dcmap; p.dc_add = mb.add;
+    p.dtau_w = mb.cmap ? weighted_partials(g, dtau_partial) : nullptr;
+    int rc = dispatch_stage<WY>(g, p, mb.cmap ? MODE_BWD_MAP : MODE_BWD, f, S(stream));
     if (rc || !r2) return rc;
     const WgradReduce job = {workspace, stage_grid(g, p), dA, nullptr, alpha, 0.0f, 0};
     if (defer) { *defer = job; return 0; }                  // the sweep reduces it with the iteration's other sums
@@ -1836,7 +1977,8 @@ int snake_enabled() { return cdl_opts().fused_snake; }
 template <int WY>
 int forward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                   const float *const *wA, const float *const *wB, float *const *z, float *const *r,
-                  unsigned *const *maps, float *xp, void *frags, float *patches, const Flags &f, void *stream)
+                  unsigned *const *maps, float *xp, void *frags, float *patches, const Flags &f, void *stream,
+                  const float *cmap = nullptr, const float *tslope = nullptr)
 {
     const size_t nm = (size_t)g->N * g->M;
     const int L = f.lin;
@@ -1847,7 +1989,8 @@ int forward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask, 
         [&](int k, const void *fk, const float *thin, bool reversed, int, int lay_out) {
             TimingScope ts(k ? 0 : 3, S(stream));               // (the input layout is L at k = 0 too, where no code is read)
             return iter_fwd<WY>(g, thin, k ? z[k - 1] : nullptr, tau + k * nm, fk, k ? -1.0f : 1.0f, z[k], patches, maps ? maps[k] : nullptr,
-                                f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(lay_out) | (reversed ? CDL_TILES_REVERSED : 0), stream);
+                                f.prec | CDL_LAYOUT_IN(L) | CDL_LAYOUT_OUT(lay_out) | (reversed ? CDL_TILES_REVERSED : 0), stream,
+                                cmap, cmap ? tslope + (size_t)k * g->M : nullptr);
         },
         [&](const float *m, const float *sub, float alpha, float *out) {
             return assemble<WY>(g, patches, m, sub, alpha, out, nullptr, 0, stream);
@@ -1861,7 +2004,8 @@ int backward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask,
                    const float *g_z, float *const *dA,
                    float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
                    float *patches, float *dtau_partial, float *wgrad_ws, const Flags &f, float *dyp,
-                   float *dtau, void *stream)
+                   float *dtau, void *stream, const float *cmap = nullptr, const float *tslope = nullptr,
+                   float *dcmap = nullptr)
 {
     const int M = g->M;
     float *du[2] = {du0, du1};
@@ -1897,11 +2041,13 @@ int backward_sweep(const cdl_geom *g, int K, const float *yp, const float *mask,
             rc = stage_bwd<WY>(g, thin, base, maps[k], fk, duk, patches, dtau_partial, k >= 1 || dyp,
                                sprec | CDL_LAYOUT_IN(k == K - 1 ? LAY_NCHW : L) | CDL_LAYOUT_OUT(L),
                                ride ? (k >= 1 ? r[k - 1] : yp) : nullptr, k >= 1 ? -1.0f : 1.0f, dA[k], ws_a, stream, &red.w[0],
-                               ride && k == 0);
+                               ride && k == 0,
+                               MapBwd{cmap, cmap ? tslope + (size_t)k * M : nullptr, dcmap, k < K - 1});   // dcmap: = at k = K-1, += after
         }
         if (rc) return rc;
         if (ride) red.wblocks[0] = wgrad_reduce_blocks(red.w[0], M, g->Ph);
-        red.t = DtauReduce{dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, g->N, per_img};
+        red.t = DtauReduce{dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M, g->N, per_img,
+                           cmap ? weighted_partials(g, dtau_partial) : nullptr};
         if (dtau) {
             rc = cdl_dtau_per_sample(dtau_partial, g->N, M, per_img, (size_t)per_img * M, 1, M, dtau + (size_t)k * g->N * M, stream);
             if (rc) return rc;
@@ -1970,6 +2116,12 @@ int cdl_fused2d_supported(const cdl_geom *g) { return fused_shape_ok(g) ? 1 : 0;
 size_t cdl_fused2d_frag_bytes(int M) { return (size_t)2 * (M / 32) * 8 * 64 * 16; }
 
 // (buffers a caller sizes with these serve sweeps on either tile shape: the larger of the two needs)
+// floats of a reverse stage's dtau_partial: one (tiles, M) array, and with a noise-level map the weighted one behind it
+size_t cdl_fused2d_dtau_partial_floats(const cdl_geom *g, int with_map)
+{
+    return (with_map ? 2 : 1) * cdl_fused2d_tiles(g) * (fused_shape_ok(g) ? (size_t)g->M : 0);
+}
+
 size_t cdl_fused2d_patch_floats(const cdl_geom *g)
 {
     if (!fused_shape_ok(g)) return 0;
@@ -2019,27 +2171,28 @@ int cdl_fused2d_support_map(const cdl_geom *g, const float *z, unsigned *map, vo
 
 int cdl_fused2d_iter_fwd(const cdl_geom *g, const float *r, const float *zin, const float *tau,
                          const void *frags, float sgn, float *zout, float *patches, unsigned *map_out,
-                         int precision, void *stream)
+                         int precision, const float *cmap, const float *tslope, void *stream)
 {
-    return iter_fwd<2>(g, r, zin, tau, frags, sgn, zout, patches, map_out, precision, stream);
+    return iter_fwd<2>(g, r, zin, tau, frags, sgn, zout, patches, map_out, precision, stream, cmap, tslope);
 }
 
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base, const unsigned *map,
                           const void *frags, float *du_out, float *patches, float *dtau_partial, int do_synth,
-                          const float *r2, float alpha, float *dA, float *workspace, int precision, void *stream)
+                          const float *r2, float alpha, float *dA, float *workspace, int precision, const float *cmap,
+                          const float *tslope, float *dcmap, int dcmap_add, void *stream)
 {
     if (!r2 != !dA || !r2 != !workspace) return CDL_EINVAL;     // the filter gradient: all three set, or none
     return stage_bwd<2>(g, thin, base, map, frags, du_out, patches, dtau_partial, do_synth, precision, r2, alpha, dA, workspace,
-                        stream);
+                        stream, nullptr, false, MapBwd{cmap, tslope, dcmap, dcmap_add});
 }
 
 int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
-                            float *dtau_n, void *stream)
+                            float *dtau_n, const float *dtau_partial_w, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
-    if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
+    if (!dtau_partial || !dt0 || !dt1 || (c && dtau_partial_w)) return CDL_EINVAL;
     const int per_img = tiles_x(g) * tiles_y<2>(g);          // partial rows: [n][tile][m]
-    const DtauReduce job = {dtau_partial, c, dt0, dt1, g->N, per_img};
+    const DtauReduce job = {dtau_partial, c, dt0, dt1, g->N, per_img, dtau_partial_w};
     k_dtau_reduce<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(job, g->M);
     CDL_LAUNCH_CHECK();
     if (!dtau_n) return 0;
@@ -2103,15 +2256,16 @@ int cdl_fused2d_timing_read(double *ms_sum, int *count)
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask, const float *tau,
                         const float *const *wA, const float *const *wB, float *const *z, float *const *r,
                         unsigned *const *maps, float *xp, void *frags, float *patches, int precision,
-                        void *stream)
+                        const float *cmap, const float *tslope, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !tau || !wA || !wB || !z || !xp || !frags || !patches || (K > 1 && !r)) return CDL_EINVAL;
+    if (!cmap != !tslope) return CDL_EINVAL;
     const Flags f = parse_flags(precision);
     if (!f.ok || f.lout != 0) return CDL_EINVAL;
     if (f.lin == LAY_BLK16)                  // bf16 code storage: 64 x 32 tiles, two waves per SIMD (see the top of the file)
-        return forward_sweep<4>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
-    return forward_sweep<2>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream);
+        return forward_sweep<4>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream, cmap, tslope);
+    return forward_sweep<2>(g, K, yp, mask, tau, wA, wB, z, r, maps, xp, frags, patches, f, stream, cmap, tslope);
 }
 
 int cdl_fused2d_tangent(const cdl_geom *g, int K, const float *vp, const float *nvp, const float *mask,
@@ -2134,19 +2288,21 @@ int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float 
                          const float *g_z, float *const *dA,
                          float *const *dB, float *dt, float *du0, float *du1, float *q, void *frags,
                          float *patches, float *dtau_partial, float *wgrad_ws, int precision, float *dyp,
-                         float *dtau, void *stream)
+                         float *dtau, const float *cmap, const float *tslope, float *dcmap, void *stream)
 {
     if (!fused_shape_ok(g)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
         !patches || !dtau_partial || !wgrad_ws || (K > 1 && !r))
         return CDL_EINVAL;
+    // a map: the thresholds' gradients are dt and dcmap -- no per-sample level c, no per-sample (K,N,M) dtau
+    if (!cmap != !tslope || (dcmap && !cmap) || (cmap && (c || dtau))) return CDL_EINVAL;
     const Flags f = parse_flags(precision);
     if (!f.ok || f.lout != 0) return CDL_EINVAL;
     if (f.lin == LAY_BLK16)
         return backward_sweep<4>(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags, patches,
-                                 dtau_partial, wgrad_ws, f, dyp, dtau, stream);
+                                 dtau_partial, wgrad_ws, f, dyp, dtau, stream, cmap, tslope, dcmap);
     return backward_sweep<2>(g, K, yp, mask, c, wA, wB, z, r, maps, g_xp, g_z, dA, dB, dt, du0, du1, q, frags, patches,
-                             dtau_partial, wgrad_ws, f, dyp, dtau, stream);
+                             dtau_partial, wgrad_ws, f, dyp, dtau, stream, cmap, tslope, dcmap);
 }
 
 }  // extern "C"

@@ -43,6 +43,37 @@ PRECISION = "split3"
 # fp32: same values as "nchw", wider memory accesses; the default), "nchw", or "blocked_bf16" (opt-in bf16
 # STORAGE: half the bytes of the dominant tensors, outside the 1e-5 parity gate -- PSNR parity only).
 CODE_LAYOUT = "blocked"
+# Where a sweep with a noise-level map runs: "generic" (the three-launch tier: the default) or "fused" -- the map forms of the
+# fused 2-D kernels wherever _route allows them, the generic tier everywhere else.
+MAP_TIER = "generic"
+_MAP_TIERS = ("generic", "fused")
+
+
+def set_map_tier(name):
+    global MAP_TIER
+    if name not in _MAP_TIERS:
+        raise ValueError(name)
+    MAP_TIER = name
+
+
+class map_tier_scope:
+    """`with map_tier_scope("fused"): ...` -- sweeps with a noise-level map started inside take that tier (their reverse
+    sweeps follow their forward whenever backward() is called); restored on exit, also when the block raises."""
+
+    def __init__(self, name):
+        if name not in _MAP_TIERS:
+            raise ValueError(name)
+        self.name = name
+
+    def __enter__(self):
+        global MAP_TIER
+        self.saved, MAP_TIER = MAP_TIER, self.name
+        return self
+
+    def __exit__(self, *exc):
+        global MAP_TIER
+        MAP_TIER = self.saved
+        return False
 
 
 def set_backend(name):
@@ -191,18 +222,18 @@ def _forward_generic_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, 
     return xp, z, codes, resid, []
 
 
-def _forward_fused(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout=None, *, keep_maps=False):
+def _forward_fused(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout=None, *, keep_maps=False, cmap=None, tslope=None):
     """The whole sweep from one C call (cdl_fused2d_forward): per iteration one fused launch + a thin
     assemble, enqueued back to back with no per-launch host work.  codes[:-1] come back in `layout`
     (default CODE_LAYOUT), codes[-1] = z_K as (N,M,H,W).  keep_maps: the bit maps although nothing is kept (what a
-    tangent sweep needs of the primal)."""
+    tangent sweep needs of the primal).  cmap / tslope: the noise-level map, as _forward_generic's."""
     keep = keep_codes or keep_resid
     xp, z, codes, resid, maps = ops.fused_forward(g, yp, mask_p, tau, A, B, keep, PRECISION,
-                                                  layout or CODE_LAYOUT, keep_maps=keep_maps)
+                                                  layout or CODE_LAYOUT, keep_maps=keep_maps, cmap=cmap, tslope=tslope)
     return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid or keep_maps else [])
 
 
-def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw"):
+def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw", *, cmap=None, tslope=None):
     """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
     K = len(A)
     frags = [ops.fused_prep(A[k], B[(k + 1) % K]) for k in range(K)]   # last one pairs A_{K-1} with D = B_0
@@ -212,7 +243,8 @@ def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, la
     for k in range(K):
         bits = ops.fused_map(g, yp.device) if keep_resid else None
         z = ops.fused_iter(g, r, z, tau[k], frags[k], 1.0 if k == 0 else -1.0, patches, PRECISION, map_out=bits,
-                           lay_in=layout, lay_out="nchw" if k == K - 1 else layout)
+                           lay_in=layout, lay_out="nchw" if k == K - 1 else layout, cmap=cmap,
+                           tslope=tslope[k] if cmap is not None else None)
         if keep_codes or k == 0:
             codes.append(z)
         if keep_resid:
@@ -315,19 +347,20 @@ def _backward_generic_stepwise_map(g, K, yp, mask_p, A, B, codes, resid, g_xp, g
 
 
 def _backward_fused(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout=None, precision=None,
-                    dyp=None, dtau=None):
+                    dyp=None, dtau=None, cmap=None, tslope=None, dcmap=None):
     """Reverse sweep from one C call (cdl_fused2d_backward): per iteration one stage launch (1 fat read +
     the 2-bit map of z_{k+1}, 1 fat write; dA_k rides in it), a thin assemble, one MFMA filter-gradient launch (dB_k: 1 fat
-    read) and one launch that reduces dA_k, dB_k and dt[k].  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1]."""
+    read) and one launch that reduces dA_k, dB_k and dt[k].  maps: the forward's bit maps (rebuilt from the codes when absent); `layout`: that of codes[:-1].
+    cmap / tslope / dcmap: as _backward_generic's."""
     if g_xp is None and g_z is None:
         return _zero_grads(A, B)
     return ops.fused_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
                               precision or PRECISION, maps=list(maps) if maps else None, layout=layout or CODE_LAYOUT,
-                              dyp=dyp, dtau=dtau)
+                              dyp=dyp, dtau=dtau, cmap=cmap, tslope=tslope, dcmap=dcmap)
 
 
 def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
-                             dyp=None, dtau=None):
+                             dyp=None, dtau=None, cmap=None, tslope=None, dcmap=None):
     """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
     assert maps or layout == "nchw"
     prec = PRECISION
@@ -335,14 +368,18 @@ def _backward_fused_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z,
     dA, dB = [None] * K, [None] * K
     patches = ops.fused_patches(g, dev)
     ws = ops.fused_wgrad_workspace(g, dev)
-    dtp = torch.empty((ops.fused_tiles(g), g.M), device=dev, dtype=torch.float32)
+    tiles = ops.fused_tiles(g)                    # with a map: the weighted partials behind the plain ones
+    dtp = torch.empty(((2 if cmap is not None else 1) * tiles, g.M), device=dev, dtype=torch.float32)
+    mp = (lambda k: dict(cmap=cmap, tslope=tslope[k], dcmap=dcmap, dcmap_add=k < K - 1)) if cmap is not None else (lambda k: {})
     thin, du_next = g_xp, g_z
     (dB[0],) = ops.fused_wgrad(g, ws, codes[K - 1], g_xp, 1.0, precision=prec)[:1]
     for k in range(K - 1, -1, -1):
         frags = ops.fused_prep(B[(k + 1) % K], A[k])          # analysis-like bank, synthesis-like bank
         du = ops.fused_stage_bwd(g, thin, du_next, maps[k] if maps else codes[k], frags, patches, dtp,
-                                 k >= 1 or dyp is not None, prec, lay_in="nchw" if k == K - 1 else layout, lay_out=layout)
-        ops.fused_dtau_reduce(g, dtp, c, dt[k], dtau[k] if dtau is not None else None)
+                                 k >= 1 or dyp is not None, prec, lay_in="nchw" if k == K - 1 else layout, lay_out=layout,
+                                 **mp(k))
+        ops.fused_dtau_reduce(g, dtp[:tiles], c, dt[k], dtau[k] if dtau is not None else None,
+                              weighted=dtp[tiles:] if cmap is not None else None)
         if k == 0 and dyp is not None:                              # u_0 = A_0 yp
             ops.fused_assemble(g, patches, acc=dyp, acc_add=K > 1, write_out=False)
         if k >= 1:
@@ -386,16 +423,21 @@ def _no_data_gradients(ctx, names=((0, "y"), (1, "mask"), (2, "sigma"))):
 
 def _route(g, exact, is_map):
     """The tier of a sweep: "fused" (the 2-D MFMA kernels), "fusedg" (the tile / strip kernels) or "generic".  The fused
-    tiers are matrix-core kernels that read tau[n,m]: the "fp32" arithmetic (`exact`) and a noise-level map run the generic."""
-    if BACKEND != "auto" or exact or is_map:
+    tiers are matrix-core kernels that read tau[n,m]: the "fp32" arithmetic (`exact`) and a noise-level map run the generic --
+    unless MAP_TIER is "fused" and the sweep is one the 2-D kernels' map forms exist for: split3 arithmetic, fp32 code storage,
+    a geometry of the 2-D tier (the tile / strip kernels take no map)."""
+    if BACKEND != "auto" or exact:
         return "generic"
+    if is_map:
+        fused_map = MAP_TIER == "fused" and PRECISION == "split3" and CODE_LAYOUT in ("nchw", "blocked")
+        return "fused" if fused_map and ops.fused_supported(g) else "generic"
     if ops.fused_supported(g):
         return "fused"
     return "fusedg" if ops.fusedg_supported(g) else "generic"
 
 
 # What the nodes below need of a tier, one argument convention per role.  `st` is the routed context (it carries layout and
-# precision); mp the map keywords of _map_args (generic tier only); keep_gates: keep what gates a tangent sweep although
+# precision); mp the map keywords of _map_args (the generic tier and the fused 2-D one: what _route sends a map to); keep_gates: keep what gates a tangent sweep although
 # nothing else is kept -- the bit maps on the fused tiers, all K codes on the generic one.  The entries name the sweeps
 # through the module when they are CALLED: a test that replaces loop._forward_generic by its stepwise twin reaches every node.
 #   layout(g, keep, handed_out, tangent) -> layout of the codes that stay inside the sweeps (None: the reference's only)
@@ -417,11 +459,11 @@ def _tangent_reverse_fused(name):
 _TIERS = {
     "fused": _Tier(
         layout=lambda g, keep, handed_out, tangent: "nchw" if handed_out else CODE_LAYOUT,
-        forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False: _forward_fused(
-            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates),
-        reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None: _backward_fused(
+        forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False, **mp: _forward_fused(
+            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates, **mp),
+        reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None, **mp: _backward_fused(
             g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=st.layout, precision=st.precision,
-            dyp=dyp, dtau=dtau),
+            dyp=dyp, dtau=dtau, **mp),
         tangent=lambda st, g, vp, mask_p, A, B, codes, maps, keep, last: _tangent_fused(
             g, vp, mask_p, A, B, maps, keep, st.layout, st.precision, last=last),
         tangent_reverse=_tangent_reverse_fused("fused"), negated_dA=True),

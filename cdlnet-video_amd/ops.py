@@ -975,14 +975,19 @@ def fused_tiles(g: Geometry) -> int:
     return _size("cdl_fused2d_tiles", g)
 
 
-def _dtau_reduce(symbol, g, dtau_partial, c, dt_k, dtau_n):
+def _dtau_reduce(symbol, g, dtau_partial, c, dt_k, dtau_n, *more):
     dt0, dt1 = _dt_halves(g, dt_k)
-    _call(symbol, g, _buf(dtau_partial, "dtau_partial"), _opt(c, "c"), dt0, dt1, _dtau_rows(g, dtau_n))
+    _call(symbol, g, _buf(dtau_partial, "dtau_partial"), _opt(c, "c"), dt0, dt1, _dtau_rows(g, dtau_n), *more)
 
 
-def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
-    """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`]."""
-    _dtau_reduce("cdl_fused2d_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
+def fused_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None, *, weighted=None):
+    """(2,M) `dt_k` [and the per-image (N,M) `dtau_n`].  weighted (in place of c): the map-weighted partials of a reverse
+    stage that ran with a noise-level map -- rows fused_tiles(g).. of its dtau_partial; dt_k[1] is their sum."""
+    if weighted is not None and c is not None:
+        raise ValueError("the weighted partials replace the per-sample level c")
+    if _buf(weighted, "weighted") is not None and weighted.numel() < fused_tiles(g) * g.M:
+        raise ValueError(f"weighted: expected {fused_tiles(g)} x {g.M} values, got {weighted.numel()}")
+    _dtau_reduce("cdl_fused2d_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n, weighted)
 
 
 def fused_wgrad_workspace(g: Geometry, device):
@@ -1171,8 +1176,9 @@ def _fusedg_code_buffers(g: Geometry, layout, device, count):
 # support_map(g, z), which rebuild a bit map from a stored code; map_shape(g) of one bit map; frag_bytes(g) of one prepared
 # pair, patch_floats(g), tiles(g) (rows of the stages' threshold partials); reverse_ws(g, device) -> the trailing workspace
 # arguments of the reverse sweep (cdl_fusedg_backward's filter gradients are the shape-generic cdl_wgrad's).
+# takes_map: the tier's entry points end in the noise-level map arguments (the 2-D tier's do: DESIGN.md section 31).
 _FusedTier = collections.namedtuple(
-    "_FusedTier", "prefix code_buffers to_nchw support_map map_shape frag_bytes patch_floats tiles reverse_ws")
+    "_FusedTier", "prefix code_buffers to_nchw support_map map_shape frag_bytes patch_floats tiles reverse_ws takes_map")
 
 
 def _fusedg_wgrad_workspace(g: Geometry, device):
@@ -1184,13 +1190,24 @@ _FUSED2D = _FusedTier(
     prefix="cdl_fused2d", code_buffers=fused_code_buffer, to_nchw=fused_to_nchw, support_map=fused_support_map,
     map_shape=lambda g: (g.N, 4, g.dims[1], g.dims[2]), frag_bytes=lambda g: _lib.lib().cdl_fused2d_frag_bytes(g.M),
     patch_floats=lambda g: _size("cdl_fused2d_patch_floats", g), tiles=fused_tiles,
-    reverse_ws=lambda g, device: (fused_wgrad_workspace(g, device),))
+    reverse_ws=lambda g, device: (fused_wgrad_workspace(g, device),), takes_map=True)
 _FUSEDG = _FusedTier(
     prefix="cdl_fusedg", code_buffers=_fusedg_code_buffers,
     to_nchw=lambda g, t, layout: t if layout == "nchw" else fusedg_from_rsc(g, t), support_map=fusedg_support_map,
     map_shape=_fusedg_map_shape, frag_bytes=lambda g: _size("cdl_fusedg_frag_bytes", g),
     patch_floats=lambda g: _size("cdl_fusedg_patch_floats", g), tiles=lambda g: _size("cdl_fusedg_tiles", g),
-    reverse_ws=_fusedg_wgrad_workspace)
+    reverse_ws=_fusedg_wgrad_workspace, takes_map=False)
+
+
+def _tier_map(tier, g, cmap, tslope, rows=1, more=()):
+    """The noise-level map arguments an entry point of `tier` ends in: (cmap, tslope) + more for the 2-D tier -- checked
+    as on the generic tier, `rows` slope rows -- and none for the tile / strip kernels, which take no map."""
+    cmap, tslope = _check_map_pair(g, cmap, tslope, rows)
+    if tier.takes_map:
+        return (cmap, tslope) + tuple(more)
+    if cmap is not None or any(torch.is_tensor(m) for m in more):
+        raise ValueError(f"{tier.prefix}: this tier takes no noise-level map (the generic sweeps do)")
+    return ()
 
 
 def _code(t, name, layout):
@@ -1199,31 +1216,52 @@ def _code(t, name, layout):
     return t if t is None or layout.startswith("blocked") else _dev(t, name)
 
 
-def _fused_iter(tier, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out):
+def _fused_iter(tier, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, cmap=None, tslope=None):
     r, zin, tau = _dev(r, "r"), _code(zin, "zin", lay_in), _dev(tau, "tau")
     assert tuple(r.shape) == g.image_shape()
     frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    mp = _tier_map(tier, g, cmap, tslope)
     if out is None:
         out = tier.code_buffers(g, lay_out, r.device, 1)[0]
     _call(tier.prefix + "_iter_fwd", g, r, zin, tau, frags, sgn, _buf(out, "out", dtype=out.dtype), patches,
-          _buf(map_out, "map_out", dtype=torch.int32), PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
+          _buf(map_out, "map_out", dtype=torch.int32), PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out), *mp)
     return out
 
 
-def _fused_stage_bwd(tier, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, precision, out, lay_in, lay_out, rider=()):
+def _dtau_partial_floats(tier, g, with_map):
+    """Floats of a reverse stage's threshold partials: the library's own figure where the tier takes a map."""
+    if tier.takes_map:
+        return int(_lib.lib().cdl_fused2d_dtau_partial_floats(g._c_ref(), int(bool(with_map))))
+    return tier.tiles(g) * g.M
+
+
+def _map_partials(tier, g, dtau_partial, with_map):
+    """A reverse stage's threshold partials: (tiles, M) floats, and with a noise-level map the weighted ones behind them."""
+    n = _dtau_partial_floats(tier, g, with_map)
+    if _buf(dtau_partial, "dtau_partial").numel() < n:
+        raise ValueError(f"dtau_partial: {dtau_partial.numel()} floats, this stage writes {n}")
+    return dtau_partial
+
+
+def _fused_stage_bwd(tier, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, precision, out, lay_in, lay_out, rider=(),
+                     cmap=None, tslope=None, dcmap=None, dcmap_add=False):
     """`rider`: the arguments an entry point takes between do_synth and the flags (cdl_fused2d_stage_bwd's dA_k)."""
     thin, base = _dev(thin, "thin"), _code(base, "base", lay_in)
     gate_map = _buf(gate_map, "gate_map", dtype=torch.int32)
     frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
+    _check_map(g, _buf(dcmap, "dcmap"))
+    mp = _tier_map(tier, g, cmap, tslope, more=(dcmap, bool(dcmap_add)))
     if out is None:
         out = tier.code_buffers(g, lay_out, thin.device, 1)[0]
     _call(tier.prefix + "_stage_bwd", g, thin, base, gate_map, frags, _buf(out, "out", dtype=out.dtype), patches,
-          _buf(dtau_partial, "dtau_partial"), bool(do_synth), *rider, PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out))
+          _map_partials(tier, g, dtau_partial, cmap is not None), bool(do_synth), *rider,
+          PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out), *mp)
     return out
 
 
-def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps):
+def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps, cmap=None, tslope=None):
     K = len(A)
+    mp = _tier_map(tier, g, cmap, tslope, rows=K)
     yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
     A, B = [_dev(w, "A") for w in A], [_dev(w, "B") for w in B]
     dev = yp.device
@@ -1235,7 +1273,7 @@ def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep
     xp = _new(g.image_shape(), dev)
     frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
     _call(tier.prefix + "_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, _new((tier.patch_floats(g),), dev),
-          PRECISION[precision] | _lay_in(layout))
+          PRECISION[precision] | _lay_in(layout), *mp)
     return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), maps
 
 
@@ -1255,9 +1293,14 @@ def _fused_tangent(tier, g, vp, mask_p, A, B, maps, keep, precision, layout, las
     return xdp, (zd if keep else ([zd[K - 1]] if last else [])), (nrd if keep else [])
 
 
-def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau):
+def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau,
+                    cmap=None, tslope=None, dcmap=None):
     K = len(A)
     dev = yp.device
+    _check_map(g, _buf(dcmap, "dcmap"))
+    mp = _tier_map(tier, g, cmap, tslope, rows=K, more=(dcmap,))
+    if cmap is not None and (c is not None or dtau is not None):
+        raise ValueError("a noise-level map replaces the per-sample level c; its gradient is dcmap, not dtau")
     lay = lambda k: layout if k < K - 1 else "nchw"          # codes[-1] = z_K is always (N,M,..)
     if not maps:
         maps = [tier.support_map(g, tier.to_nchw(g, t, lay(k))) for k, t in enumerate(codes)]
@@ -1274,14 +1317,17 @@ def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, p
     frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
     _call(tier.prefix + "_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt, du[0],
           du[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, _new((tier.patch_floats(g),), dev),
-          _new((tier.tiles(g), g.M), dev), *tier.reverse_ws(g, dev), PRECISION[precision] | _lay_in(layout), dyp, dtau)
+          _new((_dtau_partial_floats(tier, g, cmap is not None),), dev), *tier.reverse_ws(g, dev),
+          PRECISION[precision] | _lay_in(layout), dyp, dtau, *mp)
     return dA, dB
 
 
 def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3", out=None, map_out=None,
-               lay_in="nchw", lay_out="nchw"):
-    """One fused iteration.  lay_in / lay_out: layouts of zin / the result (a flat buffer unless "nchw")."""
-    return _fused_iter(_FUSED2D, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out)
+               lay_in="nchw", lay_out="nchw", *, cmap=None, tslope=None):
+    """One fused iteration.  lay_in / lay_out: layouts of zin / the result (a flat buffer unless "nchw").
+    cmap (N,1,H,W) with tslope (M): a noise-level map -- the threshold of element (n, m, pix) is
+    tau[n,m] + cmap[n,pix] * tslope[m], as `analysis` forms it (split3, "nchw" / "blocked" only)."""
+    return _fused_iter(_FUSED2D, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, cmap, tslope)
 
 
 def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw"):
@@ -1289,18 +1335,23 @@ def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out
 
 
 def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
-                    precision="split3", out=None, lay_in="nchw", lay_out="nchw", r2=None, alpha=1.0, workspace=None):
+                    precision="split3", out=None, lay_in="nchw", lay_out="nchw", r2=None, alpha=1.0, workspace=None, *,
+                    cmap=None, tslope=None, dcmap=None, dcmap_add=False):
     """One reverse-sweep stage: du = [z' != 0] * (base + corr(thin; W1)); patches = W2^T du.  `gate` is the
     bit map of z' (int32, from the forward or fused_support_map) or z' itself (the map is built first).
     With `r2` (thin) and `workspace` (fused_wgrad_workspace) the launch also accumulates dA = alpha * du (x) im2col(r2)
-    and (du, dA) is returned."""
+    and (du, dA) is returned.
+    cmap / tslope: the forward's noise-level map -- `dtau_partial` is then (2 * fused_tiles(g), M), the map-weighted
+    partials behind the plain ones (fused_dtau_reduce's `weighted`); dcmap (N,1,H,W): this iteration's dL/dcmap, written
+    or (dcmap_add) added."""
     if gate.dtype != torch.int32:
         gate = fused_support_map(g, gate)
     assert gate.numel() == g.N * 4 * g.dims[1] * g.dims[2]
     r2 = _opt(r2, "r2")
     dA = None if r2 is None else torch.empty(g.filter_shape(), device=thin.device, dtype=torch.float32)
     out = _fused_stage_bwd(_FUSED2D, g, thin, base, gate, frags, patches, dtau_partial, do_synth, precision, out, lay_in,
-                           lay_out, rider=(r2, alpha, dA, _buf(workspace, "workspace")))
+                           lay_out, rider=(r2, alpha, dA, _buf(workspace, "workspace")), cmap=cmap, tslope=tslope,
+                           dcmap=dcmap, dcmap_add=dcmap_add)
     return out if dA is None else (out, dA)
 
 
@@ -1309,14 +1360,16 @@ def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_par
     return _fused_stage_bwd(_FUSEDG, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, "split3", out, lay_in, lay_out)
 
 
-def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False):
+def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False, *,
+                  cmap=None, tslope=None):
     """Whole forward sweep in one C call.  keep=True: every z_k and r_k gets its own buffer (training) and
     each launch also writes the support/sign bit map of its z_{k+1}; keep=False: two ping-pong buffers
     each, no maps.  `layout`: how z_1..z_{K-1} are stored (they never leave the sweeps; z_K is always NCHW).
     keep_maps (with keep=False): the K bit maps are written although every code and residual ping-pongs (what a tangent
     sweep under no_grad needs of the primal).
+    cmap (N,1,H,W) with tslope (K,M): a noise-level map, tau then holding t[k,0,m] for every sample (as ista_forward's).
     Returns (xp, z_K, codes, resid, maps); codes[:-1] are flat buffers in `layout` unless it is "nchw"."""
-    return _fused_forward(_FUSED2D, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps)
+    return _fused_forward(_FUSED2D, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps, cmap, tslope)
 
 
 def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep_maps=False):
@@ -1326,13 +1379,16 @@ def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep
 
 
 def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision="split3", maps=None,
-                   layout="blocked", dyp=None, dtau=None):
+                   layout="blocked", dyp=None, dtau=None, *, cmap=None, tslope=None, dcmap=None):
     """Whole reverse sweep in one C call; returns (dA list, dB list); dt (K,2,M) is written in place.
+    cmap / tslope (K,M): the forward's noise-level map in place of c (then None, as dtau); dcmap (N,1,H,W, nullable)
+    receives dL/dcmap.
     maps: the forward's bit maps of z_1..z_K (built here from the codes when not given).  `layout`: that of
     codes[:-1] (as fused_forward returned them) and of the du work buffers; codes[-1] = z_K, g_z: NCHW.
     g_xp None (a loss on the code only) is a zero image gradient.  dyp (thin, as yp) / dtau (K,N,M): filled with
     dL/dyp and the per-image threshold gradients when given (cdl_fused2d_backward; None: the plain sweep)."""
-    return _fused_backward(_FUSED2D, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau)
+    return _fused_backward(_FUSED2D, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau,
+                           cmap, tslope, dcmap)
 
 
 def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",

@@ -293,7 +293,8 @@ def denoise(net, y, sigma=None, mask=1, *, window=None, halo="exact", blend="cro
 
     net       CDLNet (JDD: C = 3 with a mask), GDLNet or CDLNetVideo(residual=False).
     sigma     every form net(y, sigma) takes; a map is classified on the whole code grid and cropped per window (those
-              windows run the generic tier, as a map does in net(y)).
+              windows take the tier a map takes in net(y): the generic one, or under loop.set_map_tier("fused") the map
+              forms of the fused 2-D kernels where the window's geometry has them).
     mask      1 or a tensor shaped like y; pre-processed with the frame, cropped per window.
     window    core extent per spatial axis: an int or a tuple (None in a slot: the whole axis), multiples of the stride.
               None plans automatically (module docstring); a frame a fused tier takes whole is one window, and the

@@ -618,10 +618,16 @@ size_t cdl_fused2d_code_bytes(const cdl_geom *g, int layout);   /* bytes of one 
 /* fp32 filters (M,1,P,P) -> bf16 hi/lo MFMA operand fragments for one launch (A_k with B_next). */
 int cdl_fused2d_prep(const float *wA, const float *wB, void *frags, int M, int P, void *stream);
 /* map_out (nullable, cdl_fused2d_map_words(g) words): support / sign bit planes of z_{k+1} for the reverse
- * sweep (2 bits per code element, written by the same launch). */
+ * sweep (2 bits per code element, written by the same launch).
+ * A noise-level map -- cmap (N,1,H,W) with tslope (M), both or neither (a mix is CDL_EINVAL): the
+ * threshold of code element (n, m, y, x) is tau[n,m] + cmap[n,y,x] * tslope[m], product rounded before the sum as on the
+ * generic tier (cdl_analysis), tau then holding t[k,0,m] for every sample.  Split-bf16 x3 arithmetic and the layouts
+ * CDL_LAY_NCHW / CDL_LAY_BLK only (anything else with a map: CDL_EUNSUPPORTED); cmap needs float alignment only.  With
+ * both NULL the call enqueues exactly the launch it enqueued without these arguments. */
 int cdl_fused2d_iter_fwd(const cdl_geom *g, const float *r, const float *zin /*nullable*/,
                          const float *tau /*N*M*/, const void *frags, float sgn, float *zout,
-                         float *patches, unsigned *map_out /*nullable*/, int precision, void *stream);
+                         float *patches, unsigned *map_out /*nullable*/, int precision,
+                         const float *cmap /*nullable*/, const float *tslope /*nullable*/, void *stream);
 /* The map of a code tensor, (N,4,H,W) 32-bit words: plane 2h holds [z != 0], plane 2h+1 the sign bit, bit
  * 16R + v of a word = channel 32R + 8(v>>2) + 4h + (v&3) of that pixel (the MFMA accumulator layout).  The
  * reverse stage reads it instead of the fat z_{k+1}: 16 B per pixel against 4*M.  cdl_fused2d_support_map
@@ -644,21 +650,35 @@ int cdl_fused2d_assemble(const cdl_geom *g, const float *patches, const float *m
  *     patches : partial W2^T du_k (W2 = A_k)    -> cdl_fused2d_assemble(alpha = -1, mask) gives q_k
  * frags = cdl_fused2d_prep(W1, W2).  do_synth = 0 for k = 0 (no q_0 is needed). */
 size_t cdl_fused2d_tiles(const cdl_geom *g);               /* workgroups (= dtau_partial rows) per launch */
+/* Floats of the dtau_partial buffer of cdl_fused2d_stage_bwd / _backward: cdl_fused2d_tiles(g) * M, and twice that when the
+ * call passes a noise-level map (with_map != 0: the map-weighted partials sit behind the plain ones).  A caller that adds
+ * cmap to an existing call MUST resize the buffer with this: the stage writes both arrays. */
+size_t cdl_fused2d_dtau_partial_floats(const cdl_geom *g, int with_map);
 /* r2, dA, workspace (all three set, or all three NULL; a mix is CDL_EINVAL): the analysis-filter gradient of the
  * iteration rides in the stage (what autograd of net.py:87 computes from du_k and r_k): dA = alpha * sum_px du_out (x)
  * im2col(r2) -- cdl_fused2d_wgrad's product, taken from the stage's registers instead of a second fat read of du_out.
  * du_out / patches / dtau_partial do not depend on whether it rides; workspace: cdl_fused2d_wgrad_workspace_floats(g).
  * The whole-sweep entry point cdl_fused2d_backward uses it (5.1 instead of 6.1 fat passes per iteration;
- * CDL_FUSED_DA=0 restores the two-launch form for A/B runs). */
+ * CDL_FUSED_DA=0 restores the two-launch form for A/B runs).
+ * A noise-level map -- the forward's cmap and tslope (both or neither), as cdl_fused2d_iter_fwd's: du_out, patches and the
+ * partials in dtau_partial are what they are without it (the stage gates on `map`, it reads no threshold); dtau_partial
+ * then holds cdl_fused2d_dtau_partial_floats(g, 1) floats, TWO arrays of cdl_fused2d_tiles(g) * M, and the second receives the map-weighted partials
+ * -sum cmap * sign(z_{k+1}) * du_k (cdl_fused2d_dtau_reduce's dtau_partial_w).  dcmap (nullable, only with a map; (N,1,H,W),
+ * float alignment): dL/dcmap of this iteration, sum_m tslope[m] * (-sign(z_{k+1}) du_k)[m] per pixel -- written
+ * (dcmap_add = 0) or added to what dcmap holds (dcmap_add != 0: every reverse iteration after the first). */
 int cdl_fused2d_stage_bwd(const cdl_geom *g, const float *thin, const float *base /*nullable*/,
                           const unsigned *map /*of z_{k+1}*/, const void *frags, float *du_out, float *patches,
                           float *dtau_partial, int do_synth, const float *r2 /*(N,1,H,W), nullable*/, float alpha,
                           float *dA /*(M,1,P,P), nullable*/, float *workspace /*nullable*/, int precision,
-                          void *stream);
+                          const float *cmap /*nullable*/, const float *tslope /*nullable*/, float *dcmap /*nullable*/,
+                          int dcmap_add, void *stream);
 /* dt0[m] = sum over workgroups; dt1[m] = sum_n c[n] * (sum over the workgroups of image n); c nullable.
- * dtau_n (nullable) receives the per-image sums dtau_n[n,m] of the partial rows, tiles in order. */
+ * dtau_n (nullable) receives the per-image sums dtau_n[n,m] of the partial rows, tiles in order.
+ * dtau_partial_w (nullable; together with c: CDL_EINVAL): the map-weighted partials of a reverse stage that ran with a
+ * noise-level map; dt1[m] is then their sum over the workgroups, in dt0's order. */
 int cdl_fused2d_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N*/, float *dt0 /*M*/,
-                            float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/, void *stream);
+                            float *dt1 /*M*/, float *dtau_n /*N,M, nullable*/, const float *dtau_partial_w /*nullable*/,
+                            void *stream);
 
 /* Filter gradients on the matrix cores: up to two independent reductions per launch
  *     dw_a[m,i,j] = alpha_a * sum_{n,y,x} Xa[n,m,y,x] * Ta[n,y-p+i,x-p+j]     (a = 0, 1; either may be absent)
@@ -684,18 +704,24 @@ int cdl_fused2d_wgrad(const cdl_geom *g, const float *X0, const float *T0, float
  * and dt[k] -- each summed in the order of its stand-alone entry point (bit-identical to them).
  * The gradients of the data, as cdl_ista_backward's (both NULL: neither is computed): dyp (thin, nullable) receives
  * sum_k A_k^T du_k -- the unmasked sum each assemble already forms, plus the k = 0 synthesis half (its stage then runs
- * with do_synth = 1) and one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients. */
+ * with do_synth = 1) and one assemble into dyp only; dtau (K,N,M, nullable) the per-image threshold gradients.
+ * A noise-level map (both sweeps; cmap (N,1,H,W) with tslope (K,M), both or neither): the stage launches become their map
+ * forms (see cdl_fused2d_iter_fwd / _stage_bwd), the launch count stays.  The reverse sweep then takes c = NULL and
+ * dtau = NULL (either with a map: CDL_EINVAL), dtau_partial of cdl_fused2d_dtau_partial_floats(g, 1) floats, writes dt[k,1,m] as the sum of the weighted
+ * partials, and fills dcmap (nullable) with dL/dcmap.  All three NULL: exactly the launches of the sweep without a map. */
 int cdl_fused2d_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                         const float *tau /*K,N,M*/, const float *const *wA, const float *const *wB,
                         float *const *z, float *const *r, unsigned *const *maps /*nullable*/, float *xp,
-                        void *frags, float *patches, int precision, void *stream);
+                        void *frags, float *patches, int precision, const float *cmap /*nullable*/,
+                        const float *tslope /*K,M, nullable*/, void *stream);
 int cdl_fused2d_backward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/,
                          const float *c /*N, nullable*/, const float *const *wA, const float *const *wB,
                          const float *const *z, const float *const *r, const unsigned *const *maps,
                          const float *g_xp, const float *g_z /*nullable*/, float *const *dA, float *const *dB,
                          float *dt, float *du0, float *du1, float *q, void *frags, float *patches,
                          float *dtau_partial, float *wgrad_ws, int precision, float *dyp /*nullable*/,
-                         float *dtau /*K*N*M, nullable*/, void *stream);
+                         float *dtau /*K*N*M, nullable*/, const float *cmap /*nullable*/,
+                         const float *tslope /*K,M, nullable*/, float *dcmap /*nullable*/, void *stream);
 
 /* Tangent sweep on the fused 2-D kernels: per iteration one reverse-stage launch with the FORWARD's
  * prepared pair (A_k, B_{k+1}), base = zd_k, thin = -rd_k and maps[k] = the primal's bit map of z_{k+1}, then one assemble
