@@ -48,18 +48,15 @@ SIGNATURES = {
     "cdl_postprocess_bwd": [_P, _P, _I, _I, _I, _I, _I, _IP, _P],
     "cdl_thresholds": [_P, _P, _P, _I, _I, _I, _P],
     "cdl_shrink": [_P, _P, _P, _I, ctypes.c_size_t, _P],
-    "cdl_analysis": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P],               # .., out, cmap, tslope, stream
-    "cdl_synthesis": [_G, _P, _P, _P, _F, _P, _P, _P, _P],
-    "cdl_synthesis_ws": [_G, _P, _P, _P, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],
+    "cdl_analysis": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],         # .., out, workspace, floats, cmap, tslope, stream
+    "cdl_synthesis": [_G, _P, _P, _P, _F, _P, _P, _P, _P, ctypes.c_size_t, _P],                # .., out, workspace, floats, stream
     "cdl_wgrad": [_G, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
     "cdl_wgrad_pair": [_G, _P, _P, _F, _P, _P, _P, _F, _P, _P, ctypes.c_size_t, _P],
     "cdl_tau_grad": [_G, _P, _P, _P, _P, _P, _P, _P, _P, _P],                   # .., scratch, cmap, stream
     "cdl_tau_grad_gate": [_G, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_sigma_grad": [_G, _P, _P, _P, _P, _I, _P],
-    "cdl_analysis_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],      # .., cmap, tslope, stream
-    "cdl_analysis_rev_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P],   # .., cmap, stream
-    "cdl_analysis_prox_ws": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],   # .., cmap, tslope, stream
-    "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],                            # .., cmap, tslope, stream
+    "cdl_analysis_rev": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P],      # .., cmap, stream
+    "cdl_analysis_prox": [_G, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, _P, _P],   # .., cmap, tslope, stream
     "cdl_ista_forward": [_G, _I] + [_P] * 14 + [ctypes.c_size_t, _P, _P, _P],                  # .., cmap, tslope, stream
     "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_tangent_forward": [_G, _I] + [_P] * 10 + [ctypes.c_size_t, _P],
@@ -86,12 +83,8 @@ SIGNATURES = {
     "cdl_shrink_b_bwd": [_P, _P, _P, _B, _P, _P, _I, _I, ctypes.c_size_t, _P],
     "cdl_prox_csr_b": [_G, _P, _P, _P, _P, _B, _P, _B, _P, _B, _P, _P],
     "cdl_prox_csr_b_bwd": [_G, _P, _P, _P, _P, _P, _B, _P, _B, _P, _B] + [_P] * 7 + [ctypes.c_size_t, _P],
-    "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11,
-    "cdl_analysis_prox_tangent_ws": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P],
-    "cdl_project_filters": [_P, _I, _I, _P],
+    "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_project_filter_banks": [_P, _I, _I, _I, _P],
-    "cdl_gabor_filters": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "cdl_gabor_filters_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cdl_options_reload": [],
     "cdl_set_exact_fp32": [_I],
     "cdl_trace": [_I],

@@ -14,8 +14,6 @@
 // M = 169 against 0.67 ms for the VALU kernel).
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(512) void k_ana_tau_final(const float *__restrict__
 
 // Reverse-sweep form: out = [zsup != 0] (zin + alpha A x) and (dt0, dt1) = cdl_tau_grad(out, zsup, c), one fat launch.
 // Workspace: cdl_mfma_analysis_rev_ws_floats(g) (fragments + N M S tile partials).  CDL_EUNSUPPORTED: the caller composes
-// cdl_analysis_ws and cdl_tau_grad_gate.
+// cdl_analysis and cdl_tau_grad_gate.
 size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g)
 {
     Plan p;

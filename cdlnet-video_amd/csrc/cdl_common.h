@@ -25,6 +25,16 @@ void cdl_trace_note(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
         if (e_ != hipSuccess) return -(int)e_;               \
     } while (0)
 
+// ---- host plumbing every launcher uses: the ABI's opaque stream, a status that ends the caller, the larger size ----
+static inline hipStream_t S(void *s) { return (hipStream_t)s; }
+static inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+#define CDL_TRY(expr)              \
+    do {                           \
+        const int rc_ = (expr);    \
+        if (rc_ != 0) return rc_;  \
+    } while (0)
+
 // sign(u) * relu(|u| - t): exactly the reference's x.sign()*relu(|x|-t) (model/net.py:11-14), including
 // t < 0 (|u|-t > 0 everywhere, sign(0) = 0) and non-finite values: a NaN in u or t comes out as NaN (torch's
 // sign and relu both keep it; fmaxf would turn it into 0 and hide a diverging net from the trainer's nan / inf

@@ -6,8 +6,6 @@
 
 namespace {
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 // dtau_n[n,m] = sum_{j<R} partial[n sN + m sM + j sR], j in order: one thread per (n, m), deterministic
 __global__ __launch_bounds__(256) void k_dtau_per_sample(const float *__restrict__ partial, float *__restrict__ dtau_n,
                                                          int N, int M, int R, size_t sN, size_t sM, size_t sR)

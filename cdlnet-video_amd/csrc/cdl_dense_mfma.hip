@@ -32,8 +32,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 constexpr int DTX = 32, DTY = 16, DNT = 512, DKC = 16;

@@ -1606,8 +1606,6 @@ __global__ __launch_bounds__(1024) void k_sweep_reduce(SweepReduce q, int M, int
     dtau_reduce_block(reinterpret_cast<float (*)[4]>(sm), reinterpret_cast<float (*)[4]>(sm + 256 * 4), block, q.t, M);
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 inline bool fused_shape_ok(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return false;

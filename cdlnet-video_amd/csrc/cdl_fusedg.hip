@@ -818,8 +818,6 @@ __global__ __launch_bounds__(1024) void k_dtau_reduce_g(const float *__restrict_
 }
 
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 typedef cdl_fusedg_plan Plan;                               // cdl_strip.h: one plan for the three kernels
 
 bool tile_plan_for(const cdl_geom *g, Plan *pl)

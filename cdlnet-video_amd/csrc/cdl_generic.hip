@@ -537,20 +537,8 @@ __global__ void k_embed(const float *__restrict__ gx, float *__restrict__ gxp, i
 }
 
 // ------------------------------------------------------------------------------------------
-// unit-ball projection: one wave per filter
-__global__ __launch_bounds__(64) void k_project(float *__restrict__ w, int flen)
-{
-    float *f = w + (size_t)blockIdx.x * flen;
-    float ss = 0.0f;
-    for (int i = threadIdx.x; i < flen; i += 64) ss = fmaf(f[i], f[i], ss);
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-    float scale = fminf(1.0f / sqrtf(ss), 1.0f);
-    if (scale < 1.0f)
-        for (int i = threadIdx.x; i < flen; i += 64) f[i] *= scale;
-}
-
-// the same for up to 64 banks of identical shape in one launch (bank = blockIdx.y): project() of a K = 30 net
-// is 60 banks, i.e. 60 launches of a 4 us kernel otherwise
+// unit-ball projection: one wave per filter, up to 64 banks of identical shape in one launch (bank = blockIdx.y):
+// project() of a K = 30 net is 60 banks, i.e. 60 launches of a 4 us kernel otherwise
 constexpr int PROJECT_BATCH = 64;
 struct ProjectBatch {
     float *w[PROJECT_BATCH];
@@ -567,62 +555,7 @@ __global__ __launch_bounds__(64) void k_project_batch(ProjectBatch b, int flen)
 }
 
 // ------------------------------------------------------------------------------------------
-// Gabor dictionary synthesis and its adjoint
-__global__ void k_gabor(const float *__restrict__ alpha, const float *__restrict__ a,
-                        const float *__restrict__ w0, const float *__restrict__ psi,
-                        float *__restrict__ w, int order, int MC, int P, float sgn)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= MC * P * P) return;
-    int kj = i % P, ki = (i / P) % P, mc = i / (P * P);
-    float gy = (float)ki - 0.5f * (P - 1), gx = (float)kj - 0.5f * (P - 1);
-    float acc = 0.0f;
-    for (int o = 0; o < order; ++o) {
-        int q = o * MC + mc;
-        float e0 = a[2 * q] * gy, e1 = a[2 * q + 1] * gx;
-        float env = expf(-(e0 * e0 + e1 * e1));
-        float ph = sgn * w0[2 * q] * gy + sgn * w0[2 * q + 1] * gx + sgn * psi[q];
-        acc += alpha[q] * (env * cosf(ph));
-    }
-    w[i] = acc;
-}
-
-__global__ void k_gabor_bwd(const float *__restrict__ alpha, const float *__restrict__ a,
-                            const float *__restrict__ w0, const float *__restrict__ psi,
-                            const float *__restrict__ dw, float *__restrict__ dalpha,
-                            float *__restrict__ da, float *__restrict__ dw0,
-                            float *__restrict__ dpsi, int order, int MC, int P, float sgn)
-{
-    int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= order * MC) return;
-    int mc = q % MC;
-    float al = alpha[q], a0 = a[2 * q], a1 = a[2 * q + 1];
-    float f0 = sgn * w0[2 * q], f1 = sgn * w0[2 * q + 1], ps = sgn * psi[q];
-    float g_al = 0, g_a0 = 0, g_a1 = 0, g_f0 = 0, g_f1 = 0, g_ps = 0;
-    for (int ki = 0; ki < P; ++ki)
-        for (int kj = 0; kj < P; ++kj) {
-            float gy = (float)ki - 0.5f * (P - 1), gx = (float)kj - 0.5f * (P - 1);
-            float e0 = a0 * gy, e1 = a1 * gx;
-            float env = expf(-(e0 * e0 + e1 * e1));
-            float ph = f0 * gy + f1 * gx + ps;
-            float cs = cosf(ph), sn = sinf(ph);
-            float up = dw[(size_t)mc * P * P + ki * P + kj];
-            g_al += up * env * cs;
-            float de = up * al * cs * env;            // d/d(env exponent) carrier
-            g_a0 += de * (-2.0f * a0 * gy * gy);
-            g_a1 += de * (-2.0f * a1 * gx * gx);
-            float dp = -up * al * env * sn;           // d/d(phase)
-            g_f0 += dp * sgn * gy;
-            g_f1 += dp * sgn * gx;
-            g_ps += dp * sgn;
-        }
-    dalpha[q] = g_al;
-    da[2 * q] = g_a0; da[2 * q + 1] = g_a1;
-    dw0[2 * q] = g_f0; dw0[2 * q + 1] = g_f1;
-    dpsi[q] = g_ps;
-}
-
-// every bank of a net in ONE launch (blockIdx.y = bank): GDLNet re-synthesises its 2K banks on every forward
+// Gabor dictionary synthesis and its adjoint: every bank of a net in ONE launch (blockIdx.y = bank): GDLNet re-synthesises its 2K banks on every forward
 // (gabor.py:46-51 via net.py:659-675) -- per-bank launches made that 2K launches + 2K autograd nodes per sweep
 constexpr int GABOR_BATCH = 48;
 struct GaborBatch {
@@ -688,8 +621,6 @@ __global__ void k_gabor_bwd_batch(GaborBatch b, int order, int MC, int P)
     out[3 * nq + 2 * q] = g_f0; out[3 * nq + 2 * q + 1] = g_f1;
     out[5 * nq + q] = g_ps;
 }
-
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 
@@ -818,15 +749,8 @@ size_t cdl_analysis_workspace_floats(const cdl_geom *g)
 }
 
 int cdl_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                 const float *gate, const float *tau, float *out, const float *cmap, const float *tslope, void *stream)
-{
-    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, nullptr, 0, stream,
-                         cdl_map_args{cmap, tslope});
-}
-
-int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                    const float *gate, const float *tau, float *out, float *workspace, size_t workspace_floats,
-                    const float *cmap, const float *tslope, void *stream)
+                 const float *gate, const float *tau, float *out, float *workspace, size_t workspace_floats,
+                 const float *cmap, const float *tslope, void *stream)
 {
     return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, workspace, workspace_floats, stream,
                          cdl_map_args{cmap, tslope});
@@ -835,7 +759,7 @@ int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alp
 /* Reverse-sweep step: out = [zsup != 0] (zin + alpha A x)  and  (dt0, dt1) = cdl_tau_grad(out, zsup, c) -- the gradient
  * with respect to z_k, gated by z_k's support, together with the threshold gradients it yields.  One launch where the
  * matrix-core analysis covers the geometry (the gate and the per-tile threshold partials ride in its epilogue);
- * otherwise cdl_analysis_ws followed by cdl_tau_grad_gate.  workspace: cdl_analysis_rev_workspace_floats(g). */
+ * otherwise cdl_analysis followed by cdl_tau_grad_gate.  workspace: cdl_analysis_rev_workspace_floats(g). */
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
 {
     if (!cdl_geom_ok(g)) return 0;
@@ -846,9 +770,9 @@ size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
     return r > n ? r : n;
 }
 
-int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                        const float *zsup, const float *c, float *dt0, float *dt1, float *dtau_n, float *out,
-                        float *workspace, size_t workspace_floats, const float *cmap, void *stream)
+int cdl_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+                     const float *zsup, const float *c, float *dt0, float *dt1, float *dtau_n, float *out,
+                     float *workspace, size_t workspace_floats, const float *cmap, void *stream)
 {
     if (!cdl_geom_ok(g) || !x || !w || !out || !zsup || !dt0 || !dt1 || !workspace) return CDL_EINVAL;
     if (cmap && (c || dtau_n)) return CDL_EINVAL;               // a map replaces the per-sample scale
@@ -859,24 +783,16 @@ int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float
                                                dtau_n, cmap);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
-    const int rc = cdl_analysis_ws(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, nullptr, nullptr,
-                                   stream);
+    const int rc = cdl_analysis(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, nullptr, nullptr,
+                                stream);
     if (rc) return rc;
     return cdl_tau_grad_gate(g, out, zsup, c, dt0, dt1, dtau_n, workspace, cmap, stream);
 }
 
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                      const float *gam2, float *u_out, float *out, const float *cmap, const float *tslope, void *stream)
-{
-    return cdl_analysis_prox_ws(g, x, w, alpha, zin, z_prev, z_after, lam, gam1, gam2, u_out, out, nullptr, 0, cmap, tslope,
-                                stream);
-}
-
-int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                         const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                         const float *gam2, float *u_out, float *out, float *workspace, size_t workspace_floats,
-                         const float *cmap, const float *tslope, void *stream)
+                      const float *gam2, float *u_out, float *out, float *workspace, size_t workspace_floats,
+                      const float *cmap, const float *tslope, void *stream)
 {
     if (!z_prev || !lam || !gam1 || (z_after && !gam2)) return CDL_EINVAL;
     if (u_out && (u_out == out || u_out == zin)) return CDL_EINVAL;
@@ -889,16 +805,7 @@ int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, floa
 int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                               const float *u, const float *z_prev, const float *z_after, const float *lam,
                               const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                              float *out, void *stream)
-{
-    return cdl_analysis_prox_tangent_ws(g, x, w, alpha, zin, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out,
-                                        nullptr, 0, stream);
-}
-
-int cdl_analysis_prox_tangent_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                                 const float *u, const float *z_prev, const float *z_after, const float *lam,
-                                 const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                                 float *out, float *workspace, size_t workspace_floats, void *stream)
+                              float *out, float *workspace, size_t workspace_floats, void *stream)
 {
     if (!u || !z_prev || !lam || !gam1) return CDL_EINVAL;
     if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
@@ -968,14 +875,8 @@ size_t cdl_synthesis_workspace_floats(const cdl_geom *g)
 }
 
 int cdl_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                  const float *mask, const float *sub, float *out, void *stream)
-{
-    return cdl_synthesis_ws(g, z, gate, w, alpha, mask, sub, out, nullptr, 0, stream);
-}
-
-int cdl_synthesis_ws(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                     const float *mask, const float *sub, float *out, float *workspace,
-                     size_t workspace_floats, void *stream)
+                  const float *mask, const float *sub, float *out, float *workspace,
+                  size_t workspace_floats, void *stream)
 {
     if (!cdl_geom_ok(g) || !z || !w || !out) return CDL_EINVAL;
     if (!cdl_opts().no_tiled) {
@@ -1138,14 +1039,6 @@ int cdl_sigma_grad(const cdl_geom *g, const float *du, const float *z, const flo
     return 0;
 }
 
-int cdl_project_filters(float *w, int nfilters, int flen, void *stream)
-{
-    if (!w || nfilters <= 0 || flen <= 0) return CDL_EINVAL;
-    k_project<<<nfilters, 64, 0, S(stream)>>>(w, flen);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
 int cdl_project_filter_banks(float *const *w, int nbanks, int nfilters, int flen, void *stream)
 {
     if (!w || nbanks <= 0 || nfilters <= 0 || flen <= 0) return CDL_EINVAL;
@@ -1159,17 +1052,6 @@ int cdl_project_filter_banks(float *const *w, int nbanks, int nfilters, int flen
         k_project_batch<<<dim3((unsigned)nfilters, (unsigned)nb), 64, 0, S(stream)>>>(pb, flen);
         CDL_LAUNCH_CHECK();
     }
-    return 0;
-}
-
-int cdl_gabor_filters(const float *alpha, const float *a, const float *w0, const float *psi, float *w,
-                      int order, int M, int C, int P, int transpose, void *stream)
-{
-    if (!alpha || !a || !w0 || !psi || !w || order <= 0 || M <= 0 || C <= 0 || P <= 0) return CDL_EINVAL;
-    int total = M * C * P * P;
-    k_gabor<<<(total + 255) / 256, 256, 0, S(stream)>>>(alpha, a, w0, psi, w, order, M * C, P,
-                                                        transpose ? -1.0f : 1.0f);
-    CDL_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1214,19 +1096,6 @@ int cdl_gabor_filter_banks_bwd(int nbanks, const float *const *alpha, const floa
         k_gabor_bwd_batch<<<dim3((unsigned)((total + 63) / 64), (unsigned)nb), 64, 0, S(stream)>>>(b, order, M * C, P);
         CDL_LAUNCH_CHECK();
     }
-    return 0;
-}
-
-int cdl_gabor_filters_bwd(const float *alpha, const float *a, const float *w0, const float *psi,
-                          const float *dw, float *dalpha, float *da, float *dw0, float *dpsi,
-                          int order, int M, int C, int P, int transpose, void *stream)
-{
-    if (!alpha || !a || !w0 || !psi || !dw || !dalpha || !da || !dw0 || !dpsi) return CDL_EINVAL;
-    if (order <= 0 || M <= 0 || C <= 0 || P <= 0) return CDL_EINVAL;
-    int total = order * M * C;
-    k_gabor_bwd<<<(total + 63) / 64, 64, 0, S(stream)>>>(alpha, a, w0, psi, dw, dalpha, da, dw0, dpsi,
-                                                         order, M * C, P, transpose ? -1.0f : 1.0f);
-    CDL_LAUNCH_CHECK();
     return 0;
 }
 

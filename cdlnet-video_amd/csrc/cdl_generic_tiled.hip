@@ -724,8 +724,6 @@ __global__ void k_synth_fold(const float *__restrict__ part, const float *__rest
     out[i] = v;
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 // A launch with few workgroups (single frames, small crops) leaves most of the 256 CUs idle: split the
 // code channels over blockIdx.z until there are about 1024 workgroups.  Returns channels per slice.
 inline int channel_split(int M, long blocks, int *chunks)

@@ -15,8 +15,6 @@
 // pin it through the perfect-reconstruction identity with the matching low-pass / reconstruction filters.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 constexpr int TAPS = 10;

@@ -34,8 +34,6 @@
 // are those of the one-chain-per-tile form), CELL_CHAIN patches for a cell, each chain added into the fp64 registers.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 constexpr int P_MIN = 3, P_MAX = 11;

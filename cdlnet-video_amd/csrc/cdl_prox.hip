@@ -7,8 +7,6 @@
 // re-association that moves an intermediate across 0 by one ulp would change the result by |t|.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 __device__ __forceinline__ float sgn(float x) { return cdl_sgn(x); }

@@ -11,15 +11,6 @@
 // The relu gates are the `gate` arguments of the operators (pass where gate != 0; relu outputs are >= 0).
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-static inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-#define CDL_TRY(expr)              \
-    do {                           \
-        const int rc_ = (expr);    \
-        if (rc_ != 0) return rc_;  \
-    } while (0)
-
 namespace {
 
 __global__ __launch_bounds__(256) void k_relu(float *__restrict__ v, size_t n4, size_t n)
@@ -95,9 +86,9 @@ int cdl_residual_forward(const cdl_geom *g, const float *x, const float *w1, con
                                   scratch_floats, stream);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
-    CDL_TRY(cdl_analysis_ws(g, x, w1, 1.0f, nullptr, nullptr, nullptr, h, scratch, scratch_floats, nullptr, nullptr, stream));
+    CDL_TRY(cdl_analysis(g, x, w1, 1.0f, nullptr, nullptr, nullptr, h, scratch, scratch_floats, nullptr, nullptr, stream));
     CDL_TRY(relu_inplace(h, n, S(stream)));
-    CDL_TRY(cdl_analysis_ws(g, h, w2, 1.0f, x, nullptr, nullptr, out, scratch, scratch_floats, nullptr, nullptr, stream));
+    CDL_TRY(cdl_analysis(g, h, w2, 1.0f, x, nullptr, nullptr, out, scratch, scratch_floats, nullptr, nullptr, stream));
     return relu_inplace(out, n, S(stream));
 }
 
@@ -125,10 +116,10 @@ int cdl_residual_backward(const cdl_geom *g, const float *x, const float *h, con
                                   scratch, scratch_floats, stream);
         }
     }
-    CDL_TRY(cdl_synthesis_ws(g, g_out, out, w2, 1.0f, nullptr, nullptr, dh, scratch, scratch_floats, stream));
+    CDL_TRY(cdl_synthesis(g, g_out, out, w2, 1.0f, nullptr, nullptr, dh, scratch, scratch_floats, stream));
     CDL_TRY(cdl_wgrad(g, g_out, out, h, 1.0f, dw2, scratch, scratch_floats, stream));
     CDL_TRY(cdl_wgrad(g, dh, h, x, 1.0f, dw1, scratch, scratch_floats, stream));
-    CDL_TRY(cdl_synthesis_ws(g, dh, h, w1, 1.0f, nullptr, nullptr, dx, scratch, scratch_floats, stream));
+    CDL_TRY(cdl_synthesis(g, dh, h, w1, 1.0f, nullptr, nullptr, dx, scratch, scratch_floats, stream));
     k_add_gated<<<(unsigned)((n + 255) / 256), 256, 0, S(stream)>>>(dx, g_out, out, n);
     CDL_LAUNCH_CHECK();
     return 0;

@@ -30,8 +30,6 @@
 // K2^2 L (1 - cs) / B2), summed over the positions the workgroup owns (its own tile's) in fp64, per plane in order.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 constexpr int T_MIN = 3, T_MAX = 15;

@@ -14,8 +14,6 @@
 // fixed order (deterministic, no atomics) and applies alpha, mask and sub.  The fat tensor is read with no halo.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -21,14 +21,6 @@
 // No atomics: repeated calls are bit-identical.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
-#define CDL_TRY(expr)              \
-    do {                           \
-        const int rc_ = (expr);    \
-        if (rc_ != 0) return rc_;  \
-    } while (0)
-
 namespace {
 
 constexpr int CX = 64, CY = 4;                 // k_vgg_conv11 tile: 64 columns x 4 rows, one thread per pixel
@@ -248,7 +240,7 @@ int backward(const Dims &d, const float *const *w, const Set &s, const float *se
                               nullptr, unp[k], nullptr, nullptr, nullptr, nullptr, ws, wsn, stream));
     }
     cdl_geom g1 = layer_geom(d, 1, 64, 0);
-    return cdl_synthesis(&g1, gb, s.a1, w11_of(scratch, L), 1.0f, nullptr, nullptr, dimg, stream);
+    return cdl_synthesis(&g1, gb, s.a1, w11_of(scratch, L), 1.0f, nullptr, nullptr, dimg, nullptr, 0, stream);
 }
 
 }  // namespace

@@ -12,8 +12,6 @@
 // partial bank to the workspace and k_wgm_fold adds all partials in a fixed order: deterministic, no atomics.
 #include "cdl_common.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -134,7 +134,7 @@ def analysis(x, w, stride=1, alpha=1.0, add=None):
 
 def synthesis(z, w, stride=1, alpha=1.0, mask=None, sub=None):
     """mask * (alpha * B z) - sub: the transposed correlation of the codes z (N,M,*sp) back to the image grid sp * stride
-    (what cdl_synthesis_ws computes).  Differentiable in z (ops.analysis of the masked upstream gradient), w (ops.wgrad)
+    (what cdl_synthesis computes).  Differentiable in z (ops.analysis of the masked upstream gradient), w (ops.wgrad)
     and sub; a mask that requires grad raises."""
     _no_mask_gradient(mask)
     if not torch.is_tensor(w) or w.dim() != z.dim() or z.shape[1] != w.shape[0]:

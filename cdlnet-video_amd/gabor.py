@@ -2,28 +2,13 @@
 
 `ConvAdjoint2dGabor` keeps the reference's parameter names and shapes
 (alpha (order,M,C,1,1), a / w0 (order,M,C,2), psi (order,M,C)) so GDLNet state_dicts load
-unchanged.  The filter bank is synthesised on the device by `cdl_gabor_filters` (one kernel
-instead of the reference's ~10 ATen launches per call) with a hand-written adjoint.
+unchanged.  The filter banks are synthesised on the device by `cdl_gabor_filter_banks` (one kernel
+instead of the reference's ~10 ATen launches per call and bank) with a hand-written adjoint.
 """
 import torch
 import torch.nn as nn
 
 from . import ops
-
-
-class _GaborBank(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, alpha, a, w0, psi, P, transpose):
-        ctx.P, ctx.transpose = P, transpose
-        ctx.save_for_backward(alpha, a, w0, psi)
-        return ops.gabor_filters(alpha, a, w0, psi, P, transpose)
-
-    @staticmethod
-    def backward(ctx, dw):
-        alpha, a, w0, psi = ctx.saved_tensors
-        dal, da, dw0, dpsi = ops.gabor_filters_bwd(alpha, a, w0, psi, dw.contiguous(), ctx.P,
-                                                   ctx.transpose)
-        return dal, da, dw0, dpsi, None, None
 
 
 class _GaborBanks(torch.autograd.Function):
@@ -63,7 +48,7 @@ def filter_banks(modules, transposes):
 
 def gabor_kernel_cpu(alpha, a, w0, psi, ks, transpose=False):
     """Init-time CPU evaluation of the same formula (gabor.py:7-28,46-51) for the constructor's
-    power method; the device path is `cdl_gabor_filters`."""
+    power method; the device path is `cdl_gabor_filter_banks`."""
     if transpose:
         w0, psi = -w0, -psi
     ax = torch.arange(ks, dtype=alpha.dtype) - (ks - 1) / 2.0
@@ -90,10 +75,7 @@ class ConvAdjoint2dGabor(nn.Module):
         nn.ConvTranspose2d(1, 1, ks, stride=stride)
 
     def get_filter(self, transpose=False):
-        if self.psi.is_cuda:
-            return _GaborBank.apply(self.alpha, self.a, self.w0, self.psi, self.ks, bool(transpose))
-        raise RuntimeError("ConvAdjoint2dGabor.get_filter: parameters are on the CPU; the filter "
-                           "synthesis kernel runs on the ROCm device only (use .to('cuda'))")
+        return filter_banks([self], [transpose])[0]
 
     def _geom(self, N, H, W):
         p = self._pad[0]

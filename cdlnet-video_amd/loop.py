@@ -288,7 +288,10 @@ def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, ma
 
 def _backward_generic_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None,
                                cmap=None, tslope=None, dcmap=None):
-    """Same reverse sweep driven launch by launch from Python (kept for tests and experiments)."""
+    """The same gradients from an independent composition, launch by launch from Python.  cdl_ista_backward runs
+    cdl_analysis_rev (the analysis with the gate and the threshold sums in one step) and cdl_wgrad_pair per iteration; this
+    twin runs tau_grad (ungated), the gated synthesis, two gated / plain wgrad calls and the gated analysis.  That it shares
+    no launch sequence with the C sweep is why it is kept: the tests compare the two, and reach the gated kernels through it."""
     if cmap is not None:
         return _backward_generic_stepwise_map(g, K, yp, mask_p, A, B, codes, resid, g_xp, g_z, dt, dyp, cmap, tslope, dcmap)
     dA, dB = [None] * K, [None] * K

@@ -445,7 +445,7 @@ def _check_codes(g: Geometry, **tensors):
 
 
 def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=None, *, cmap=None, tslope=None):
-    """cdl_analysis_ws.  cmap (N,1,*code_spatial) with tslope (M): the threshold of element (n, m, pix) is
+    """cdl_analysis.  cmap (N,1,*code_spatial) with tslope (M): the threshold of element (n, m, pix) is
     tau[n,m] + cmap[n,pix] * tslope[m] (tau then holds t[k,0,m])."""
     x, w = _dev(x, "x"), _dev(w, "w")
     zin, gate, tau = _opt(zin, "zin"), _opt(gate, "gate"), _opt(tau, "tau")
@@ -454,7 +454,7 @@ def analysis(g: Geometry, x, w, alpha=1.0, zin=None, gate=None, tau=None, out=No
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
     out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
     ws, n = _analysis_workspace(g, x.device)
-    _call("cdl_analysis_ws", g, x, w, alpha, zin, gate, tau, out, ws, n, cmap, tslope)
+    _call("cdl_analysis", g, x, w, alpha, zin, gate, tau, out, ws, n, cmap, tslope)
     return out
 
 
@@ -465,7 +465,7 @@ def synthesis(g: Geometry, z, w, alpha=1.0, gate=None, mask=None, sub=None, out=
     assert tuple(w.shape) == g.filter_shape(), (w.shape, g.filter_shape())
     out = _new(g.image_shape(), z.device) if out is None else _buf(out, "out")
     n = _size("cdl_synthesis_workspace_floats", g)
-    _call("cdl_synthesis_ws", g, z, gate, w, alpha, mask, sub, out, _scratch(z.device, n) if n else None, n)
+    _call("cdl_synthesis", g, z, gate, w, alpha, mask, sub, out, _scratch(z.device, n) if n else None, n)
     return out
 
 
@@ -570,7 +570,7 @@ def dyp_split(g: Geometry, q, mask, dyp, acc_add, make_q=True):
 
 
 def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None, *, cmap=None):
-    """One reverse-sweep step (cdl_analysis_rev_ws): out = [zsup != 0] (zin + alpha A x), and the (2, M) threshold
+    """One reverse-sweep step (cdl_analysis_rev): out = [zsup != 0] (zin + alpha A x), and the (2, M) threshold
     gradient slice `dt_k` of `out` with respect to the code `zsup` -- cdl_analysis followed by cdl_tau_grad_gate, as one
     fat launch where the matrix-core analysis covers the geometry."""
     x, w, zin, zsup, c = _dev(x, "x"), _dev(w, "w"), _opt(zin, "zin"), _dev(zsup, "zsup"), _opt(c, "c")
@@ -579,7 +579,7 @@ def analysis_rev(g: Geometry, x, w, alpha, zin, zsup, c, dt_k, out=None, *, cmap
     dt0, dt1 = _dt_halves(g, dt_k)
     out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
     n = _size("cdl_analysis_rev_workspace_floats", g)
-    _call("cdl_analysis_rev_ws", g, x, w, alpha, zin, zsup, c, dt0, dt1, None, out, _scratch(x.device, n), n, cmap)
+    _call("cdl_analysis_rev", g, x, w, alpha, zin, zsup, c, dt0, dt1, None, out, _scratch(x.device, n), n, cmap)
     return out
 
 
@@ -608,7 +608,7 @@ def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None
     u_out = _buf(u_out, "u_out", g.code_shape())
     out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out")
     ws, n = _analysis_workspace(g, x.device)
-    _call("cdl_analysis_prox_ws", g, x, w, alpha, zin, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
+    _call("cdl_analysis_prox", g, x, w, alpha, zin, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
           _opt(gam2, "gam2"), u_out, out, ws, n, cmap, tslope)
     return out
 
@@ -629,7 +629,7 @@ def prox_csr_tangent(g: Geometry, ud, u, z_prev, lam, gam1, z_after=None, gam2=N
 
 def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None,
                           zd_after=None, out=None):
-    """cdl_analysis followed by the tangent of the CSR map in place (cdl_analysis_prox_tangent_ws): with ud = zin +
+    """cdl_analysis followed by the tangent of the CSR map in place (cdl_analysis_prox_tangent): with ud = zin +
     alpha*corr(x; w), returns Jprox(u; z_prev[, z_after]) (ud, zd_prev, zd_after) -- the bits of analysis, then prox_csr_tangent."""
     x, w = _dev(x, "x"), _dev(w, "w")
     zin, u, z_prev, z_after = _opt(zin, "zin"), _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
@@ -639,7 +639,7 @@ def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z
     _check_codes(g, zin=zin, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after)
     out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out", g.code_shape())
     ws, n = _analysis_workspace(g, x.device)
-    _call("cdl_analysis_prox_tangent_ws", g, x, w, alpha, zin, u, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
+    _call("cdl_analysis_prox_tangent", g, x, w, alpha, zin, u, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
           _opt(gam2, "gam2"), zd_prev, zd_after, out, ws, n)
     return out
 
@@ -702,12 +702,8 @@ def residual_backward(g: Geometry, x, h, out, w1, w2, g_out):
 
 
 def project_filters_(w):
-    """In-place unit-ball projection of every (m,c) filter of w (M,C,*P)."""
-    if not w.is_cuda:
-        raise RuntimeError("project(): parameters must live on the ROCm device (no CPU path)")
-    assert w.dtype == torch.float32 and w.is_contiguous()
-    nf = w.shape[0] * w.shape[1]
-    _call("cdl_project_filters", w, nf, w.numel() // nf)
+    """In-place unit-ball projection of every (m,c) filter of w (M,C,*P): project_filter_banks_ of one bank."""
+    project_filter_banks_([w])
     return w
 
 
@@ -726,20 +722,13 @@ def project_filter_banks_(banks):
 
 
 def gabor_filters(alpha, a, w0, psi, P, transpose):
-    alpha, a, w0, psi = (_dev(v, n) for v, n in ((alpha, "alpha"), (a, "a"), (w0, "w0"), (psi, "psi")))
-    order, M, C = psi.shape
-    w = torch.empty((M, C, P, P), device=psi.device, dtype=torch.float32)
-    _call("cdl_gabor_filters", alpha, a, w0, psi, w, order, M, C, P, bool(transpose))
-    return w
+    """The (M,C,P,P) filters of one bank: gabor_filter_banks of one bank."""
+    return gabor_filter_banks([(alpha, a, w0, psi)], P, [transpose])[0]
 
 
 def gabor_filters_bwd(alpha, a, w0, psi, dw, P, transpose):
-    alpha, a, w0, psi, dw = (_dev(v, n) for v, n in ((alpha, "alpha"), (a, "a"), (w0, "w0"),
-                                                      (psi, "psi"), (dw, "dw")))
-    order, M, C = psi.shape
-    outs = [torch.empty_like(v) for v in (alpha, a, w0, psi)]
-    _call("cdl_gabor_filters_bwd", alpha, a, w0, psi, dw, *outs, order, M, C, P, bool(transpose))
-    return outs
+    """[dalpha, da, dw0, dpsi] of one bank for the upstream dw: gabor_filter_banks_bwd of one bank."""
+    return list(gabor_filter_banks_bwd([(alpha, a, w0, psi)], [dw], P, [transpose])[0])
 
 
 def gabor_filter_banks(params, P, transposes):

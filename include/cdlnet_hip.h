@@ -150,44 +150,37 @@ int cdl_shrink_b_bwd(const float *gup, const float *x, const float *tau, const c
  * (alpha=+1, zin=g_{k+1}, gate=z_{k+1}, tau=NULL).  out must not alias zin.
  * Noise-level map (net.py:82-87 with a sigma that varies over the code grid; both NULL: none): cmap (N, code pixels)
  * and tslope (M) turn the threshold of element (n, m, pix) into tau[n,m] + cmap[n,pix] * tslope[m] -- tau then holds
- * t[k,0,m], tslope t[k,1,m], cmap sigma/255; the product is rounded before the sum, as torch's broadcast does. */
+ * t[k,0,m], tslope t[k,1,m], cmap sigma/255; the product is rounded before the sum, as torch's broadcast does.
+ * workspace (cdl_analysis_workspace_floats(g) floats, 0 when no kernel wants it) lets the matrix-core kernel of the
+ * shape-generic path stage its prepared filter fragments.  workspace == NULL: VALU. */
 int cdl_analysis(const cdl_geom *g, const float *x, const float *w, float alpha,
                  const float *zin /*nullable*/, const float *gate /*nullable*/,
-                 const float *tau /*N*M, nullable*/, float *out, const float *cmap /*nullable*/,
-                 const float *tslope /*M, nullable*/, void *stream);
-/* cdl_analysis with scratch (cdl_analysis_workspace_floats(g) floats, 0 when no kernel wants it): lets the
- * matrix-core kernel of the shape-generic path stage its prepared filter fragments.  workspace == NULL: VALU. */
-int cdl_analysis_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
-                    const float *zin /*nullable*/, const float *gate /*nullable*/,
-                    const float *tau /*N*M, nullable*/, float *out, float *workspace, size_t workspace_floats,
-                    const float *cmap /*nullable*/, const float *tslope /*M, nullable*/, void *stream);
+                 const float *tau /*N*M, nullable*/, float *out, float *workspace /*nullable*/, size_t workspace_floats,
+                 const float *cmap /*nullable*/, const float *tslope /*M, nullable*/, void *stream);
 size_t cdl_analysis_workspace_floats(const cdl_geom *g);
 /* One step of the reverse sweep (autograd of net.py:87 / 205 through the shrinkage of the previous iteration):
  *   out = [zsup != 0] * (zin + alpha * A x),   (dt0, dt1[, dtau_n]) = cdl_tau_grad(out, zsup, c)
- * i.e. cdl_analysis_ws followed by cdl_tau_grad_gate, as ONE fat launch where the matrix-core analysis covers the
+ * i.e. cdl_analysis followed by cdl_tau_grad_gate, as ONE fat launch where the matrix-core analysis covers the
  * geometry (gate and threshold partials in its epilogue).  dtau_n NULL: no per-sample threshold gradients.
- * out must differ from zin and zsup.  cmap (nullable; then c and dtau_n must be NULL): as cdl_tau_grad's. */
-int cdl_analysis_rev_ws(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
-                        const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
-                        float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
-                        const float *cmap /*N, code pixels; nullable*/, void *stream);
+ * out must differ from zin and zsup.  cmap (nullable; then c and dtau_n must be NULL): as cdl_tau_grad's.
+ * workspace: required, cdl_analysis_rev_workspace_floats(g) floats. */
+int cdl_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin /*nullable*/,
+                     const float *zsup, const float *c /*N, nullable*/, float *dt0 /*M*/, float *dt1 /*M*/,
+                     float *dtau_n /*N,M, nullable*/, float *out, float *workspace, size_t workspace_floats,
+                     const float *cmap /*N, code pixels; nullable*/, void *stream);
 size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g);
 
 /* ---- synthesis half: F.conv_transpose2d/3d at net.py:87,90,205,210 and gabor.py:64 ----------
  *   v   = alpha * corrT( gate ? [gate!=0]*z : z ; w )   z fat, v thin, output_padding = s-1
  *   out = (mask ? mask*v : v) - (sub ? sub : 0)
  * Forward residual r_k = mask*B_k z_k - yp: (alpha=1, mask, sub=yp).  Dictionary synthesis
- * D z_K: (alpha=1, NULL, NULL).  Backward q_k = mask * (-A_k^T du): (z=g, gate=z_{k+1}, alpha=-1, mask). */
-int cdl_synthesis(const cdl_geom *g, const float *z, const float *gate /*nullable*/,
-                  const float *w, float alpha, const float *mask /*nullable*/,
-                  const float *sub /*nullable*/, float *out, void *stream);
-
-/* cdl_synthesis with scratch for launches too small to fill the GPU (single frames, crops): the code
- * channels are then split over extra workgroups whose partial images (cdl_synthesis_workspace_floats(g)
- * floats, 0 when no split is worthwhile) are added in a fixed order.  workspace == NULL: no split. */
-int cdl_synthesis_ws(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                     const float *mask, const float *sub, float *out, float *workspace,
-                     size_t workspace_floats, void *stream);
+ * D z_K: (alpha=1, NULL, NULL).  Backward q_k = mask * (-A_k^T du): (z=g, gate=z_{k+1}, alpha=-1, mask).
+ * workspace: scratch for launches too small to fill the GPU (single frames, crops): the code channels are then split
+ * over extra workgroups whose partial images (cdl_synthesis_workspace_floats(g) floats, 0 when no split is worthwhile)
+ * are added in a fixed order.  workspace == NULL: no split. */
+int cdl_synthesis(const cdl_geom *g, const float *z, const float *gate /*nullable*/, const float *w, float alpha,
+                  const float *mask /*nullable*/, const float *sub /*nullable*/, float *out,
+                  float *workspace /*nullable*/, size_t workspace_floats, void *stream);
 size_t cdl_synthesis_workspace_floats(const cdl_geom *g);
 
 /* ---- filter gradients (autograd of the two conv calls above; train.py:98) --------------------
@@ -250,17 +243,13 @@ int cdl_prox_csr(const cdl_geom *g, const float *u, const float *z_prev, const f
  * and u itself to u_out when it is not NULL (the reverse sweep needs it).  Same bits as the two-call form.
  * Noise-level map (both NULL: none): cmap (N, code pixels) with tslope (3,M), the slopes of lam,
  * gam1, gam2 in this order (the third plane unread without z_after).  lam / gam1 / gam2 then hold the constant parts and
- * element (n, m, pix) takes lam[n,m] + cmap[n,pix]*tslope[0,m] etc., the product rounded before the sum. */
+ * element (n, m, pix) takes lam[n,m] + cmap[n,pix]*tslope[0,m] etc., the product rounded before the sum.
+ * workspace: as cdl_analysis's (NULL: VALU). */
 int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha,
                       const float *zin /*nullable*/, const float *z_prev, const float *z_after /*nullable*/,
                       const float *lam, const float *gam1, const float *gam2 /*nullable*/,
-                      float *u_out /*nullable*/, float *out, const float *cmap /*nullable*/,
-                      const float *tslope /*3*M, nullable*/, void *stream);
-int cdl_analysis_prox_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
-                         const float *zin /*nullable*/, const float *z_prev, const float *z_after /*nullable*/,
-                         const float *lam, const float *gam1, const float *gam2 /*nullable*/,
-                         float *u_out /*nullable*/, float *out, float *workspace, size_t workspace_floats,
-                         const float *cmap /*nullable*/, const float *tslope /*3*M, nullable*/, void *stream);
+                      float *u_out /*nullable*/, float *out, float *workspace /*nullable*/, size_t workspace_floats,
+                      const float *cmap /*nullable*/, const float *tslope /*3*M, nullable*/, void *stream);
 
 /* Tangent of the two maps.  They are piecewise linear in (u, z_prev, z_after); with the intermediates
  * of the PRIMAL (u, z_prev[, z_after], lam, gam*) and st_dx(x,t) = (x != 0 && |x| - t > 0):
@@ -273,20 +262,16 @@ int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, con
                          const float *gam2 /*nullable iff z_after is*/, const float *zd_prev /*nullable*/,
                          const float *zd_after /*nullable*/, float *out, void *stream);
 
-/* The tangent step of one iteration: ud = zin + alpha*corr(x ; w) (cdl_analysis_ws into out), then
+/* The tangent step of one iteration: ud = zin + alpha*corr(x ; w) (cdl_analysis into out), then
  * out = Jprox(u; z_prev[, z_after])(ud, zd_prev, zd_after) in place (cdl_prox_csr_tangent): two launches, the bits of the
- * two calls.  (As a branch of the kernels' CSR epilogue it slowed the primal epilogue: DESIGN.md section 22.) */
+ * two calls.  (As a branch of the kernels' CSR epilogue it slowed the primal epilogue: DESIGN.md section 22.)
+ * workspace: as cdl_analysis's (NULL: VALU). */
 int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha,
                               const float *zin /*nullable*/, const float *u, const float *z_prev,
                               const float *z_after /*nullable*/, const float *lam, const float *gam1,
                               const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
-                              const float *zd_after /*nullable*/, float *out, void *stream);
-int cdl_analysis_prox_tangent_ws(const cdl_geom *g, const float *x, const float *w, float alpha,
-                                 const float *zin /*nullable*/, const float *u, const float *z_prev,
-                                 const float *z_after /*nullable*/, const float *lam, const float *gam1,
-                                 const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
-                                 const float *zd_after /*nullable*/, float *out, float *workspace,
-                                 size_t workspace_floats, void *stream);
+                              const float *zd_after /*nullable*/, float *out, float *workspace /*nullable*/,
+                              size_t workspace_floats, void *stream);
 
 /* Reverse of cdl_prox_csr as autograd differentiates the reference expression (sign() has zero
  * gradient): gu = dL/du (may alias gz); gz_prev / gz_after (nullable) are ACCUMULATED into, because a
@@ -468,8 +453,8 @@ int cdl_residual_backward(const cdl_geom *g, const float *x, const float *h, con
                           float *scratch, size_t scratch_floats, void *stream);
 
 /* ---- whole sweeps of the shape-generic loop in one call ------------------------------------------
- * The same launches as K x (cdl_synthesis_ws, cdl_analysis | cdl_analysis_prox) + the final synthesis,
- * resp. the reverse sweep (cdl_tau_grad | cdl_prox_csr_bwd, cdl_synthesis_ws, 2 x cdl_wgrad, cdl_analysis
+ * The same launches as K x (cdl_synthesis, cdl_analysis | cdl_analysis_prox) + the final synthesis,
+ * resp. the reverse sweep (cdl_tau_grad | cdl_prox_csr_bwd, cdl_synthesis, 2 x cdl_wgrad, cdl_analysis
  * per iteration), enqueued from C: single frames and crops are launch-bound, a host round trip per
  * launch would dominate.  Pointer tables are HOST arrays of device pointers.
  * Forward (net.py:76-92 / 192-212 / 426-463 / 525-568): tau (K,N,M) thresholds (CSR: lam); z_prev NULL =
@@ -512,7 +497,7 @@ int cdl_ista_backward(const cdl_geom *g, int K, const float *yp, const float *ma
 /* ---- forward-mode tangent of the plain loop at the primal's supports ----
  * With G_k = [zgate[k] != 0] (zgate[k] = z_{k+1} of the primal) and a direction vp in the padded observation:
  *   zd_1 = G_0 (A_0 vp),  rd_k = mask B_k zd_k - vp,  zd_{k+1} = G_k (zd_k - A_k rd_k),  xdp = B_0 zd_K
- * -- no threshold appears.  The launches of cdl_ista_forward with cdl_analysis_rev_ws as the gated step.  zd: K code
+ * -- no threshold appears.  The launches of cdl_ista_forward with cdl_analysis_rev as the gated step.  zd: K code
  * buffers, rd: K-1 thin ones (consecutive entries must differ; two each suffice when nothing is kept).  dt_scratch: 2*M
  * floats nobody reads; scratch: cdl_ista_scratch_floats(g). */
 int cdl_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
@@ -534,7 +519,7 @@ int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float 
  * the tangents of the neighbour codes:
  *   ud_0 = A_0 vp,  rd_k = mask B_k zd_k - vp,  ud_k = zd_k - A_k rd_k,  zd_{k+1} = Jprox_k(ud_k; zd_prev, zd_after),
  *   xdp = B_0 zd_K.
- * Per iteration cdl_synthesis_ws + cdl_analysis_prox_tangent_ws.  zd: K code buffers,
+ * Per iteration cdl_synthesis + cdl_analysis_prox_tangent.  zd: K code buffers,
  * rd: K-1 thin ones (two each suffice when nothing is kept).  The reverse sweep is cdl_ista_backward's CSR branch with
  * yp -> vp, z -> zd, r -> rd, the primal's u / lam / gam*, c = NULL: gz_prev / gz_after then receive dL/dzd_prev, dL/dzd_after
  * and dt / dg1 / dg2 sums nobody reads (the gates are piecewise constant: no threshold gradient through the tangent). */
@@ -546,19 +531,14 @@ int cdl_csr_tangent_forward(const cdl_geom *g, int K, const float *vp, const flo
                             size_t scratch_floats, void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
- * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere.  w inout. */
-int cdl_project_filters(float *w, int nfilters, int flen, void *stream);
-/* The same for `nbanks` banks of identical shape (HOST array of device pointers) in one launch per 64 banks:
- * net.py:72-73 projects A[k] and B[k] for every k. */
+ * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere, in place, for `nbanks` banks of identical
+ * shape (w: HOST array of device pointers) in one launch per 64 banks: net.py:72-73 projects A[k] and B[k] for every k. */
 int cdl_project_filter_banks(float *const *w, int nbanks, int nfilters, int flen, void *stream);
 
 /* model/gabor.py:7-28,46-51 (gabor_kernel, get_filter): w[m,c,i,j] = sum_o alpha[o,m,c] *
  * exp(-(a0*(i-x0))^2 - (a1*(j-x0))^2) * cos(sgn*(w00*(i-x0) + w01*(j-x0) + psi)),
- * x0=(P-1)/2, sgn=-1 for the analysis ("transpose") filter.  alpha (O,M,C), a,w0 (O,M,C,2), psi (O,M,C). */
-int cdl_gabor_filters(const float *alpha, const float *a, const float *w0, const float *psi,
-                      float *w /*M,C,P,P*/, int order, int M, int C, int P, int transpose, void *stream);
-
-/* Every bank of a net in ONE launch (GDLNet.forward re-synthesises its 2K banks per call, net.py:659-675):
+ * x0=(P-1)/2, sgn=-1 for the analysis ("transpose") filter.  alpha (O,M,C), a,w0 (O,M,C,2), psi (O,M,C), w (M,C,P,P).
+ * Every bank of a net in ONE launch (GDLNet.forward re-synthesises its 2K banks per call, net.py:659-675):
  * bank k reads alpha[k], a[k], w0[k], psi[k] (aliased pointers are fine: shared parameters, net.py:607-622), writes
  * w[k]; transpose[k] != 0 selects the analysis filter.  _bwd: grads[k] receives the block
  * [dalpha (order*M*C) | da (2*order*M*C) | dw0 (2*order*M*C) | dpsi (order*M*C)] for upstream dw[k] (zeros when
@@ -569,10 +549,6 @@ int cdl_gabor_filter_banks(int nbanks, const float *const *alpha, const float *c
 int cdl_gabor_filter_banks_bwd(int nbanks, const float *const *alpha, const float *const *a, const float *const *w0,
                                const float *const *psi, const int *transpose, const float *const *dw,
                                float *const *grads, int order, int M, int C, int P, void *stream);
-/* Backward of cdl_gabor_filters: given dw (M,C,P,P) writes dalpha, da, dw0, dpsi (overwritten). */
-int cdl_gabor_filters_bwd(const float *alpha, const float *a, const float *w0, const float *psi,
-                          const float *dw, float *dalpha, float *da, float *dw0, float *dpsi,
-                          int order, int M, int C, int P, int transpose, void *stream);
 
 /* OR-ed into the `precision` argument of cdl_fused2d_iter_fwd / _stage_bwd / _wgrad: walk the tiles from
  * the last to the first.  Stage results are identical; the filter gradients' per-workgroup partial sums

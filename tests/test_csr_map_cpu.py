@@ -46,8 +46,7 @@ def test_oracle_reproduces_the_fixture(kind):
 
 # ------------------------------------------------------------------------------------------ the C ABI
 NEW_ARGS = {  # entry point: (its argument count before, the pointers it gained in front of the stream)
-    "cdl_analysis_prox": (13, ("cmap", "tslope")),
-    "cdl_analysis_prox_ws": (15, ("cmap", "tslope")),
+    "cdl_analysis_prox": (15, ("cmap", "tslope")),
     "cdl_prox_csr_bwd": (18, ("cmap", "tslope", "dcmap", "dsum_n")),
 }
 SAME_ARGC = {"cdl_ista_forward": 20, "cdl_ista_backward": 35}       # the sweeps reuse their nullable arguments

@@ -45,15 +45,20 @@ def test_data_gradients_are_nullable_arguments_of_one_entry_point():
     from cdlnet_video_amd import _lib
     for name in ("cdl_preprocess_bwd", "cdl_ista_backward", "cdl_fused2d_backward", "cdl_fusedg_backward",
                  "cdl_fused2d_assemble", "cdl_fusedg_assemble", "cdl_fused2d_dtau_reduce", "cdl_fusedg_dtau_reduce",
-                 "cdl_tau_grad", "cdl_tau_grad_gate", "cdl_analysis_rev_ws", "cdl_fused2d_stage_bwd", "cdl_dyp_split"):
+                 "cdl_tau_grad", "cdl_tau_grad_gate", "cdl_analysis_rev", "cdl_fused2d_stage_bwd", "cdl_dyp_split"):
         assert name in _lib.SIGNATURES, name
     # the retired siblings, spelled as (survivor, suffix) so that a grep for the suffixed names finds nothing
     header = open(os.path.join(ROOT, "include", "cdlnet_hip.h")).read()
-    for base, suffix in (("cdl_tau_grad", "_x"), ("cdl_tau_grad_gate", "_x"), ("cdl_analysis_rev_ws", "_x"),
+    for base, suffix in (("cdl_tau_grad", "_x"), ("cdl_tau_grad_gate", "_x"), ("cdl_analysis_rev", "_x"),
                          ("cdl_ista_backward", "_x"), ("cdl_fused2d_backward", "_x"), ("cdl_fusedg_backward", "_x"),
                          ("cdl_fused2d_assemble", "_acc"), ("cdl_fusedg_assemble", "_acc"),
                          ("cdl_fused2d_dtau_reduce", "_x"), ("cdl_fusedg_dtau_reduce", "_x"),
-                         ("cdl_fused2d_stage_bwd", "_da")):
+                         ("cdl_fused2d_stage_bwd", "_da"),
+                         # the workspace is a nullable argument of the operator, not a sibling of it
+                         ("cdl_analysis", "_ws"), ("cdl_synthesis", "_ws"), ("cdl_analysis_prox", "_ws"),
+                         ("cdl_analysis_prox_tangent", "_ws"), ("cdl_analysis_rev", "_ws"),
+                         # the single-bank forms: one bank of cdl_project_filter_banks / cdl_gabor_filter_banks(_bwd)
+                         ("cdl_project_filter", "s"), ("cdl_gabor_filter", "s"), ("cdl_gabor_filter", "s_bwd")):
         name = base + suffix
         assert name not in _lib.SIGNATURES, name
         assert not re.search(rf"\b{name}\b", header), name

@@ -371,7 +371,7 @@ def test_synthesis_assemble_vector_form_is_bit_identical(hip_env):
 @pytest.mark.parametrize("path", ["mfma", "valu"])
 @pytest.mark.parametrize("N,C,M,sp,P,s", [SHAPES[1], SHAPES[3], SHAPES[5], SHAPES[10], SHAPES[11], SHAPES[12], SHAPES[14], SHAPES[18]])
 def test_reverse_analysis_step(N, C, M, sp, P, s, path, hip_env):
-    """cdl_analysis_rev_ws: out = [zsup != 0] (zin + alpha A x) with the threshold gradients of `out` -- fused into the
+    """cdl_analysis_rev: out = [zsup != 0] (zin + alpha A x) with the threshold gradients of `out` -- fused into the
     matrix-core analysis epilogue where that kernel exists, composed (analysis, then gate + threshold pass) elsewhere --
     against the oracle."""
     hip_env("CDL_MFMA_ANALYSIS", "1" if path == "mfma" else "0")

@@ -98,7 +98,7 @@ def test_record_parsing():
 def test_first_rung_of_the_analysis_ladder_at_the_workgroup_minimum():
     """Without a device cdl_cu_count() falls back to 256, the value the shapes of tests/test_gpu_dispatch.py were
     chosen for, and the first launch of the chosen tier is recorded before it fails: 96 workgroups take the
-    matrix-core analysis, 72 the tiled fp32 kernel."""
+    matrix-core analysis, 72 the tiled fp32 kernel -- and so do the 96 without a workspace ("workspace == NULL: VALU")."""
     lib = cva._lib.lib()
     buf = ctypes.create_string_buffer(256)
     p = ctypes.cast(buf, ctypes.c_void_p)
@@ -107,9 +107,13 @@ def test_first_rung_of_the_analysis_ladder_at_the_workgroup_minimum():
         gs = cva.ops.Geometry.make(N, 1, 16, (6, 30, 61), (3, 5, 5), (1, 2, 2), 1).c_struct()
         n = lib.cdl_analysis_workspace_floats(ctypes.byref(gs))
         with cva.ops.trace() as t:
-            lib.cdl_analysis_ws(ctypes.byref(gs), p, p, 1.0, None, None, None, p, p, n, None, None, None)
+            lib.cdl_analysis(ctypes.byref(gs), p, p, 1.0, None, None, None, p, p, n, None, None, None)
         first[N] = t[0].file
     assert first == {4: "cdl_analysis_mfma.hip", 3: "cdl_generic_tiled.hip"}
+    gs = cva.ops.Geometry.make(4, 1, 16, (6, 30, 61), (3, 5, 5), (1, 2, 2), 1).c_struct()
+    with cva.ops.trace() as t:
+        lib.cdl_analysis(ctypes.byref(gs), p, p, 1.0, None, None, None, p, None, 0, None, None, None)
+    assert t[0].file == "cdl_generic_tiled.hip"
 
 
 # ------------------------------------------------------------------------------------------------- launch sites

@@ -114,11 +114,11 @@ def test_sigma_to_code_grid(shape, s):
 
 # ------------------------------------------------------------------------------------------ the C ABI
 MAP_ARGS = {  # entry point: arguments it gained (pointers, in front of the stream)
-    "cdl_analysis": ("cmap", "tslope"), "cdl_analysis_ws": ("cmap", "tslope"), "cdl_analysis_rev_ws": ("cmap",),
+    "cdl_analysis": ("cmap", "tslope"), "cdl_analysis_rev": ("cmap",),
     "cdl_tau_grad": ("cmap",), "cdl_tau_grad_gate": ("cmap",), "cdl_ista_forward": ("cmap", "tslope"),
     "cdl_ista_backward": ("cmap", "tslope", "dcmap"),
 }
-PARENT_ARGC = {"cdl_analysis": 9, "cdl_analysis_ws": 11, "cdl_analysis_rev_ws": 14, "cdl_tau_grad": 9,
+PARENT_ARGC = {"cdl_analysis": 11, "cdl_analysis_rev": 14, "cdl_tau_grad": 9,
                "cdl_tau_grad_gate": 9, "cdl_ista_forward": 18, "cdl_ista_backward": 32}
 
 
@@ -138,7 +138,7 @@ def test_map_is_a_nullable_argument_of_the_existing_entry_points():
     assert "cdl_sigma_grad" in _lib.SIGNATURES and re.search(r"\bint cdl_sigma_grad\(", header)
     # no suffixed sibling, in the bindings or in the header
     for base in MAP_ARGS:
-        for suffix in ("_map", "_cmap", "_smap", "_sigma"):
+        for suffix in ("_map", "_cmap", "_smap", "_sigma", "_ws"):
             name = base + suffix
             assert name not in _lib.SIGNATURES and name not in _lib.SIZE_T_FUNCS, name
             assert not re.search(rf"\b{name}\b", header), name
