@@ -209,24 +209,42 @@ __global__ void k_prep_batch(PrepBatch b, uint4 *__restrict__ out, int frag_uint
 // block, the per-lane part of the address is ONE 32-bit VGPR byte offset shared by every channel of
 // the block and the channel stride goes in an SGPR -- no 64-bit per-access address registers, and an
 // out-of-image lane simply carries an out-of-range offset (loads return 0, stores are dropped).
-// cache-policy bits of the fat buffer accesses (0 = default; 2 = nt, streaming): build-time experiment knobs
-#ifndef CDL_FAT_LD_AUX
-#define CDL_FAT_LD_AUX 0
+// Cache policy per stream: the aux immediate of the buffer builtins (0 plain; 1 sc0; 2 nt, streaming; 16 sc1 -- a store
+// writes through the XCD's L2, a load goes past the CU's L1; 17 sc0 sc1; 18 nt sc1).  A policy changes where a line is
+// kept, never a value.  One constant per stream, each the winner of tools/probes/probe_stream.hip "policy" and of an A/B of
+// the training step against the parent; the -D overrides are for A/B builds.  A fat tensor is read
+// once per launch and is 34 times the L2s' size: its loads stream (nt) -- the read-only k_wgrad2d gains 16 %, the stages
+// 3 %; no store policy measured a gain.  Streams that are not named here go through plain pointers and keep the default
+// policy (the support map, patches, partial banks, k_assemble: the dependent boundary behind 30 MB of 16-byte stores
+// costs 17 us under every policy, and a write-through patch store moved nothing).
+#ifndef CDL_POL_STAGE_FAT_LD
+#define CDL_POL_STAGE_FAT_LD 2
 #endif
-#ifndef CDL_FAT_ST_AUX
-#define CDL_FAT_ST_AUX 0
+#ifndef CDL_POL_STAGE_FAT_ST
+#define CDL_POL_STAGE_FAT_ST 0
 #endif
+#ifndef CDL_POL_WGRAD_FAT_LD
+#define CDL_POL_WGRAD_FAT_LD 2
+#endif
+struct CachePolicy {
+    static constexpr int stage_fat_ld = CDL_POL_STAGE_FAT_LD;   // k_stage: z_k / du_{k+1}, 16 B per lane (LAY_BLK)
+    static constexpr int stage_fat_st = CDL_POL_STAGE_FAT_ST;   // k_stage: z_{k+1} / du_k, 16 B per lane (LAY_BLK)
+    static constexpr int wgrad_fat_ld = CDL_POL_WGRAD_FAT_LD;   // k_wgrad2d: z_{k-1} / du_k, 16 B per lane (LAY_BLK)
+    // accesses narrower than 16 B -- NCHW dwords, bf16 storage (LAY_BLK16) -- in every kernel: never measured with a
+    // policy, and a write-through store of 4 or 8 bytes is a fabric write of its own
+    static constexpr int narrow = 0;
+};
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fat_rsrc(const float *base, size_t img_floats)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)(img_floats * 4), 0x00020000);
 }
 __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int voff, int soff)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, CDL_FAT_LD_AUX));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, CachePolicy::narrow));
 }
 __device__ __forceinline__ void buf_st(float v, __amdgpu_buffer_rsrc_t r, int voff, int soff)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, CDL_FAT_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, CachePolicy::narrow);
 }
 
 // ---- layouts of the fat tensors ------------------------------------------------------------------------
@@ -279,7 +297,7 @@ __device__ __forceinline__ void blk16_load_raw(u32x2 (&z)[MT][4], __amdgpu_buffe
     for (int R = 0; R < MT; ++R)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            z[R][q] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (8 * R + 2 * q) * 32 * 8, CDL_FAT_LD_AUX));
+            z[R][q] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, (8 * R + 2 * q) * 32 * 8, CachePolicy::narrow));
 }
 __device__ __forceinline__ float blk16_decode(const u32x2 &u, int e)
 {
@@ -287,7 +305,8 @@ __device__ __forceinline__ float blk16_decode(const u32x2 &u, int e)
     return __builtin_bit_cast(float, (e & 1) ? (w & 0xffff0000u) : (w << 16));
 }
 
-template <int LAY, int MT>
+// POL: the stream's CachePolicy constant (16-byte accesses only)
+template <int LAY, int MT, int POL>
 __device__ __forceinline__ void blk_load(float (&z)[MT][16], __amdgpu_buffer_rsrc_t rs, int voff)
 {
     constexpr int EB = LAY == LAY_BLK ? 16 : 8;
@@ -298,10 +317,10 @@ __device__ __forceinline__ void blk_load(float (&z)[MT][16], __amdgpu_buffer_rsr
             const int soff = (8 * R + 2 * q) * 32 * EB;
             if constexpr (LAY == LAY_BLK) {
                 typedef __attribute__((ext_vector_type(4))) float f32x4;
-                const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, CDL_FAT_LD_AUX));
+                const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, POL));
                 z[R][4 * q + 0] = f.x; z[R][4 * q + 1] = f.y; z[R][4 * q + 2] = f.z; z[R][4 * q + 3] = f.w;
             } else {
-                const u32x2 u = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, CDL_FAT_LD_AUX));
+                const u32x2 u = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, CachePolicy::narrow));
                 z[R][4 * q + 0] = __builtin_bit_cast(float, u.x << 16);
                 z[R][4 * q + 1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
                 z[R][4 * q + 2] = __builtin_bit_cast(float, u.y << 16);
@@ -311,7 +330,7 @@ __device__ __forceinline__ void blk_load(float (&z)[MT][16], __amdgpu_buffer_rsr
 }
 // (values of a LAY_BLK16 store must already be bf16-representable: the caller rounds, so that the value it goes
 //  on computing with is the stored one)
-template <int LAY>
+template <int LAY, int POL>
 __device__ __forceinline__ void blk_store4(float a0, float a1, float a2, float a3, __amdgpu_buffer_rsrc_t rs, int voff, int quad_pair)
 {
     constexpr int EB = LAY == LAY_BLK ? 16 : 8;
@@ -327,12 +346,12 @@ __device__ __forceinline__ void blk_store4(float a0, float a1, float a2, float a
         // Any further store of more than 8 bytes through a buffer descriptor must likewise keep its scalar offset an immediate.
         typedef __attribute__((ext_vector_type(4))) float f32x4;
         const f32x4 f = {a0, a1, a2, a3};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), rs, voff + soff, 0, CDL_FAT_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f), rs, voff + soff, 0, POL);
     } else {
         u32x2 u;
         u.x = (__builtin_bit_cast(unsigned, a0) >> 16) | (__builtin_bit_cast(unsigned, a1) & 0xffff0000u);
         u.y = (__builtin_bit_cast(unsigned, a2) >> 16) | (__builtin_bit_cast(unsigned, a3) & 0xffff0000u);
-        __builtin_amdgcn_raw_buffer_store_b64(u, rs, voff, soff, CDL_FAT_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b64(u, rs, voff, soff, CachePolicy::narrow);
     }
 }
 
@@ -670,7 +689,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) zc[R][v] = 0.25f;
         } else if (MODE != MODE_FIRST && LIN != LAY_NCHW) {
-            blk_load<LIN, MT>(zc, rs_in, voff_in);
+            blk_load<LIN, MT, CachePolicy::stage_fat_ld>(zc, rs_in, voff_in);
         } else if (MODE != MODE_FIRST) {
 #pragma unroll
             for (int R = 0; R < MT; ++R)
@@ -798,7 +817,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
             for (int R = 0; R < MT; ++R)
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    blk_store4<LOUT>(acc[R][4 * q], acc[R][4 * q + 1], acc[R][4 * q + 2], acc[R][4 * q + 3], rs_out,
+                    blk_store4<LOUT, CachePolicy::stage_fat_st>(acc[R][4 * q], acc[R][4 * q + 1], acc[R][4 * q + 2], acc[R][4 * q + 3], rs_out,
                                      voff_st, 8 * R + 2 * q);
         }
         if (MODE != MODE_BWD && map_n) {      // training forward: 2 bits per code element for the reverse sweep
@@ -1351,7 +1370,7 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
             blk16_load_raw<MT>(f.xr, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 8 : OOB);
         } else if (LAY == LAY_BLK) {
             const int XB = (p.W + 31) / 32, xb = (q.tx0 >> 5) + wxi;
-            blk_load<LAY_BLK, MT>(f.xv, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 16 : OOB);
+            blk_load<LAY_BLK, MT, CachePolicy::wgrad_fat_ld>(f.xv, rs, valid ? ((y * XB + xb) * (M / 4) * 32 + h * 32 + c) * 16 : OOB);
         } else {
             const int voff = valid ? (int)((4 * h) * HW + (size_t)y * p.W + x) * 4 : OOB;
 #pragma unroll

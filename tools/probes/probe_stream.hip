@@ -250,10 +250,197 @@ static void rw_probes(int reps)
     CK(hipFree(a)); CK(hipFree(b)); CK(hipFree(sink));
 }
 
+// ---- cache policy per stream (./probe_stream REPS policy) ------------------------------------------------------------
+// The aux immediate of the buffer builtins on gfx950: 0 plain, 1 sc0, 2 nt, 16 sc1 (stores: write-through; loads: past
+// the CU's L1), 17 sc0 sc1, 18 nt sc1.  Nothing but buffer loads and stores carries a policy here.
+//   stage64x16 : k_stage's fat streams as the flagship runs them -- 4 waves, 64 x 16 tiles with stride gridDim.x from the
+//                first tile (rev 0) or the last (rev 1), blocked layout, 8 x 16 B per lane and row block; the forms are
+//                read-only, write-only and copy (copy ping-pongs between the two tensors and alternates rev from launch
+//                to launch, as the stages of a sweep do)
+//   wgrad64x16 : k_wgrad2d's fat load -- 8 waves, the two wave groups on alternate tiles, loads one row block ahead
+//   boundary   : a kernel that leaves 30 MB behind as patch-like 16-byte stores (6160-byte runs per tile, every
+//                workgroup) and a dependent kernel that reads them back
+// The variants are interleaved: one launch of each per round, REPS rounds per direction; median and min per variant.
+constexpr int POL[6] = {0, 1, 2, 16, 17, 18};
+enum { F_READ = 0, F_WRITE = 1, F_COPY = 2 };
+constexpr int PTH = 16, PXB = W / 32, PQ = M / 4;
+constexpr int PROWBLK = PQ * 32 * 16;                          // 8 KiB: one (y, xb) block
+constexpr size_t PIMG = (size_t)H * PXB * PROWBLK;             // 16 MiB per image: every offset fits the descriptor
+constexpr int PTILES = N * (W / TW) * (H / PTH);
+
+template <int FORM, int LD, int ST>
+__global__ __launch_bounds__(256) void k_pol_stage(const char *__restrict__ in, char *__restrict__ out, float *__restrict__ sink, int rev)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wxi = wid % 2, wyi = wid / 2, c = lane & 31, h = lane >> 5;
+    constexpr int tilesX = W / TW, tilesY = H / PTH;
+    unsigned acc = 0;
+    for (int t = blockIdx.x; t < PTILES; t += gridDim.x) {
+        int bid = rev ? PTILES - 1 - t : t;
+        const int txi = bid % tilesX; bid /= tilesX;
+        const int tyi = bid % tilesY;
+        const int n = bid / tilesY;
+        const int xb = txi * 2 + wxi;
+        const __amdgpu_buffer_rsrc_t ri = rsrc(in + (size_t)n * PIMG, PIMG), ro = rsrc(out + (size_t)n * PIMG, PIMG);
+#pragma unroll 1
+        for (int b = 0; b < RB; ++b) {
+            const int y = tyi * PTH + wyi * RB + b;
+            const int voff = (y * PXB + xb) * PROWBLK + (h * 32 + c) * 16;
+            u32x4 v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (FORM != F_WRITE) v[i] = __builtin_amdgcn_raw_buffer_load_b128(ri, voff, i * 2 * 32 * 16, LD);
+                else v[i] = u32x4{(unsigned)t, (unsigned)b, (unsigned)i, (unsigned)rev};
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (FORM == F_READ) { acc += v[i].x ^ v[i].y ^ v[i].z ^ v[i].w; continue; }
+                v[i].x += 1u;
+                // a store of more than 8 bytes keeps its scalar offset an immediate (cdl_fused2d.hip, blk_store4)
+                __builtin_amdgcn_raw_buffer_store_b128(v[i], ro, voff + i * 2 * 32 * 16, 0, ST);
+            }
+        }
+    }
+    if (FORM == F_READ && acc == 0x12345678u) sink[tid] = 1.0f;     // keeps the loads alive
+}
+
+template <int LD>
+__global__ __launch_bounds__(512) void k_pol_wgrad(const char *__restrict__ in, char *__restrict__, float *__restrict__ sink, int rev)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int op = wid >> 2, wq = wid & 3, wxi = wq & 1, wyi = wq >> 1, c = lane & 31, h = lane >> 5;
+    constexpr int tilesX = W / TW, tilesY = H / PTH, nsteps = (PTILES + 1) / 2;
+    unsigned acc = 0;
+    auto load = [&](u32x4 (&v)[8], int t0, int b) {
+        const int t = 2 * t0 + op;
+        const bool active = t0 < nsteps && t < PTILES;
+        int bid = rev ? PTILES - 1 - t : t;
+        const int txi = bid % tilesX; bid /= tilesX;
+        const int tyi = bid % tilesY;
+        const int n = active ? bid / tilesY : 0;
+        const int y = tyi * PTH + wyi * RB + b, xb = txi * 2 + wxi;
+        const __amdgpu_buffer_rsrc_t ri = rsrc(in + (size_t)n * PIMG, PIMG);
+        const int voff = active ? (y * PXB + xb) * PROWBLK + (h * 32 + c) * 16 : OOB;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(ri, voff, i * 2 * 32 * 16, LD);
+    };
+    auto use = [&](const u32x4 (&v)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc += v[i].x ^ v[i].y ^ v[i].z ^ v[i].w;
+    };
+    u32x4 va[8], vb[8];
+    load(va, blockIdx.x, 0);
+    for (int t0 = blockIdx.x; t0 < nsteps; t0 += gridDim.x) {
+#pragma unroll 1
+        for (int b = 0; b < RB; b += 2) {
+            load(vb, t0, b + 1);
+            use(va);
+            if (b + 2 < RB) load(va, t0, b + 2); else load(va, t0 + gridDim.x, 0);
+            use(vb);
+        }
+    }
+    if (acc == 0x12345678u) sink[tid] = 1.0f;
+}
+
+constexpr int BCHUNK = 385;                                    // 16-byte vectors of one 22 x 70 patch (6160 B)
+constexpr int BTILES = 4870;                                   // x 6160 B = 30.0 MB
+template <int ST>
+__global__ __launch_bounds__(256) void k_bnd_write(const char *__restrict__, char *__restrict__ out, float *__restrict__, int rev)
+{
+    const __amdgpu_buffer_rsrc_t ro = rsrc(out, (size_t)BTILES * BCHUNK * 16);
+    for (int t = blockIdx.x; t < BTILES; t += gridDim.x)
+        for (int i = threadIdx.x; i < BCHUNK; i += 256)
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)t, (unsigned)i, (unsigned)rev, 1u}, ro, (t * BCHUNK + i) * 16, 0, ST);
+}
+__global__ __launch_bounds__(256) void k_bnd_read(const char *__restrict__ in, char *__restrict__, float *__restrict__ sink, int)
+{
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(in);
+    const size_t n = (size_t)BTILES * BCHUNK;
+    unsigned acc = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const u32x4 v = src[i];
+        acc += v.x ^ v.y ^ v.z ^ v.w;
+    }
+    if (acc == 0x12345678u) sink[threadIdx.x] = 1.0f;
+}
+
+typedef void (*pol_kernel)(const char *, char *, float *, int);
+struct Variant {
+    const char *shape, *form;
+    int ld, st, block;
+    pol_kernel k, k2;                    // k2: the dependent reader of the boundary pair (nullptr elsewhere)
+    double bytes;
+    std::vector<float> ms[2];            // per direction
+};
+template <int LI = 0, int SI = 0>
+static void add_copies(std::vector<Variant> &v, double bytes)
+{
+    if constexpr (LI < 6) {
+        v.push_back({"stage64x16", "copy", POL[LI], POL[SI], 256, k_pol_stage<F_COPY, POL[LI], POL[SI]>, nullptr, 2 * bytes, {}});
+        if constexpr (SI + 1 < 6) add_copies<LI, SI + 1>(v, bytes); else add_copies<LI + 1, 0>(v, bytes);
+    }
+}
+template <int I = 0>
+static void add_singles(std::vector<Variant> &v, double bytes)
+{
+    if constexpr (I < 6) {
+        v.push_back({"stage64x16", "read-only", POL[I], -1, 256, k_pol_stage<F_READ, POL[I], 0>, nullptr, bytes, {}});
+        v.push_back({"stage64x16", "write-only", -1, POL[I], 256, k_pol_stage<F_WRITE, 0, POL[I]>, nullptr, bytes, {}});
+        v.push_back({"wgrad64x16", "read-only", POL[I], -1, 512, k_pol_wgrad<POL[I]>, nullptr, bytes, {}});
+        const double bb = (double)BTILES * BCHUNK * 16;
+        v.push_back({"boundary", "write-30MB", -1, POL[I], 256, k_bnd_write<POL[I]>, nullptr, bb, {}});
+        v.push_back({"boundary", "write-30MB+dependent-read", -1, POL[I], 256, k_bnd_write<POL[I]>, k_bnd_read, 2 * bb, {}});
+        add_singles<I + 1>(v, bytes);
+    }
+}
+
+static void policy_probes(int reps)
+{
+    char *a, *b;
+    float *sink;
+    const size_t bytes = (size_t)N * PIMG;
+    CK(hipMalloc(&a, bytes)); CK(hipMalloc(&b, bytes)); CK(hipMalloc(&sink, 4096));
+    CK(hipMemset(a, 0x3c, bytes)); CK(hipMemset(b, 0, bytes));
+    std::vector<Variant> vs;
+    add_singles(vs, (double)bytes);
+    add_copies(vs, (double)bytes);
+    vs.push_back({"boundary", "dependent-read-alone", 0, -1, 256, k_bnd_read, nullptr, (double)BTILES * BCHUNK * 16, {}});
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    const int grid = 256;
+    for (int r = -2; r < 2 * reps; ++r) {                      // two warm-up rounds
+        const int rev = r & 1;
+        for (Variant &v : vs) {
+            const char *src = rev ? b : a;                     // ping-pong, as z_k / z_{k+1} do
+            char *dst = rev ? a : b;
+            CK(hipEventRecord(e0, 0));
+            v.k<<<grid, v.block>>>(src, dst, sink, rev);
+            if (v.k2) v.k2<<<grid, v.block>>>(dst, nullptr, sink, rev);
+            CK(hipEventRecord(e1, 0));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            if (r >= 0) v.ms[rev].push_back(ms);
+        }
+    }
+    CK(hipGetLastError());
+    for (Variant &v : vs)
+        for (int rev = 0; rev < 2; ++rev) {
+            std::vector<float> &m = v.ms[rev];
+            std::sort(m.begin(), m.end());
+            const double med = m[m.size() / 2], mn = m[0];
+            printf("{\"probe\": \"cache-policy\", \"shape\": \"%s\", \"form\": \"%s\", \"ld_aux\": %d, \"st_aux\": %d, \"rev\": %d, "
+                   "\"launches\": %zu, \"median_ms\": %.4f, \"min_ms\": %.4f, \"median_GBps\": %.1f, \"best_GBps\": %.1f}\n",
+                   v.shape, v.form, v.ld, v.st, rev, m.size(), med, mn, v.bytes / med * 1e-6, v.bytes / mn * 1e-6);
+        }
+    CK(hipFree(a)); CK(hipFree(b)); CK(hipFree(sink));
+}
+
 int main(int argc, char **argv)
 {
     const int reps = argc > 1 ? atoi(argv[1]) : 15;
     if (argc > 2 && argv[2][0] == 'r') { rw_probes(reps); return 0; }     // ./probe_stream 15 rw
+    if (argc > 2 && argv[2][0] == 'p') { policy_probes(reps); return 0; } // ./probe_stream 15 policy
     const size_t floats = (size_t)N * M * (H * W + 64);         // room for the padded planes
     float *in, *out;
     CK(hipMalloc(&in, floats * 4)); CK(hipMalloc(&out, floats * 4));
