@@ -1319,8 +1319,11 @@ def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3"
     return _fused_iter(_FUSED2D, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, cmap, tslope)
 
 
-def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw"):
-    return _fused_iter(_FUSEDG, g, r, zin, tau, frags, sgn, patches, "split3", out, map_out, lay_in, lay_out)
+def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw",
+                precision="split3"):
+    """precision: "split4" asks the tile kernel for its four-product instances; the strip kernels take "split3" only
+    (CDL_EUNSUPPORTED otherwise)."""
+    return _fused_iter(_FUSEDG, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out)
 
 
 def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
@@ -1345,8 +1348,8 @@ def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial,
 
 
 def fusedg_stage_bwd(g: Geometry, thin, base, gate_map, frags, patches, dtau_partial, do_synth, out=None,
-                     lay_in="nchw", lay_out="nchw"):
-    return _fused_stage_bwd(_FUSEDG, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, "split3", out, lay_in, lay_out)
+                     lay_in="nchw", lay_out="nchw", precision="split3"):
+    return _fused_stage_bwd(_FUSEDG, g, thin, base, gate_map, frags, patches, dtau_partial, do_synth, precision, out, lay_in, lay_out)
 
 
 def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", layout="blocked", keep_maps=False, *,
