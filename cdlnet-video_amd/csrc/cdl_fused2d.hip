@@ -176,9 +176,10 @@ __device__ __forceinline__ void prep_one(const float *__restrict__ wA, const flo
     bf16x8 hi, lo;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
-        __bf16 hh = (__bf16)v[jj];
+        __bf16 hh, ll;
+        split_bf16(v[jj], hh, ll);
         hi[jj] = hh;
-        lo[jj] = (__bf16)(v[jj] - (float)hh);
+        lo[jj] = ll;
     }
     uint4 *hi_dst, *lo_dst;
     if (f < FA) { hi_dst = out + (size_t)f * 64; lo_dst = out + (size_t)(FA + f) * 64; }
@@ -412,16 +413,193 @@ __device__ __forceinline__ void store_run_copies(__bf16 *dst, int copy_elems, co
 {
     __bf16 hh[RUN], ll[RUN];
 #pragma unroll
-    for (int j = 0; j < RUN; ++j) {
-        hh[j] = (__bf16)f[j];
-        ll[j] = (__bf16)(f[j] - (float)hh[j]);
-    }
+    for (int j = 0; j < RUN; ++j) split_bf16(f[j], hh[j], ll[j]);
     store_run<0>(dst, hh, low); store_run<1>(dst + copy_elems, hh, low);
     store_run<2>(dst + 2 * copy_elems, hh, low); store_run<3>(dst + 3 * copy_elems, hh, low);
     if (PREC != 1) {
         dst += 4 * copy_elems;
         store_run<0>(dst, ll, low); store_run<1>(dst + copy_elems, ll, low);
         store_run<2>(dst + 2 * copy_elems, ll, low); store_run<3>(dst + 3 * copy_elems, ll, low);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Phases k_stage and k_wgrad2d share, one copy each.  Plain functions with the accumulator arrays
+// passed by reference, not closures: cdl_strip_dev.h records what a closure around an accumulator set cost.  dA_k from
+// the stage's ride and from k_wgrad2d are compared bit for bit: both call the SAME product sequence below.
+
+// tile t of a launch's walk (from the last tile to the first with rev): its index, image and tile row / column.  t may
+// lie past the last tile (a load a tile ahead): the caller then uses none of the fields.
+struct TileAt { int tile, n, tyi, txi; };
+__device__ __forceinline__ TileAt tile_decode(int t, int numTiles, int tilesX, int tilesY, int rev)
+{
+    TileAt q;
+    q.tile = rev ? numTiles - 1 - t : t;
+    int bid = q.tile;
+    q.txi = bid % tilesX; bid /= tilesX;
+    q.tyi = bid % tilesY;
+    q.n = bid / tilesY;
+    return q;
+}
+
+// eight consecutive bf16 from an 8-byte aligned LDS element (two b64 reads: the shifted copies guarantee no more)
+__device__ __forceinline__ bf16x8 lds_window8(const __bf16 *p)
+{
+    const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(p);
+    const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(p + 4);
+    return __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <int N>
+__device__ __forceinline__ void zero_tiles(f32x16 (&a)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) a[i][v] = 0.0f;
+}
+
+// Per-channel values of an LDS [64] array in accumulator-register order: register v of tile R on a lane of half h is
+// channel 32R + 8(v>>2) + 4h + (v&3).  One float4 quad (registers 4qv .. 4qv + 3), or all of the lane's 16 MT values.
+__device__ __forceinline__ float4 lane_channel_quad(const float *src, int R, int qv, int h)
+{
+    return *reinterpret_cast<const float4 *>(&src[32 * R + 8 * qv + 4 * h]);
+}
+template <int MT>
+__device__ __forceinline__ void lane_channel_values(float (&out)[MT * 16], const float *src, int h)
+{
+#pragma unroll
+    for (int R = 0; R < MT; ++R)
+#pragma unroll
+        for (int qv = 0; qv < 4; ++qv) {
+            const float4 s4 = lane_channel_quad(src, R, qv, h);
+            out[16 * R + 4 * qv + 0] = s4.x; out[16 * R + 4 * qv + 1] = s4.y;
+            out[16 * R + 4 * qv + 2] = s4.z; out[16 * R + 4 * qv + 3] = s4.w;
+        }
+}
+
+// Filter gradient, step 1: one channel quad of a row block -- channels 8qv + 4h .. + 3 of a 32-channel tile at pixel
+// column c -- into the tile's [pixel][32 ch] transposition image (64-B rows, 8-byte slots XOR-swizzled by (pixel>>1)&7:
+// conflict-free stores); the lo image follows the hi image.  ALO: the fat operand has a lo part.
+template <bool ALO>
+__device__ __forceinline__ void wgrad_transpose_store(__bf16 *img, int qv, int c, int h, bf16x4 hi4, bf16x4 lo4)
+{
+    const int slot = (2 * qv + h) ^ ((c >> 1) & 7);      // 8-byte slot of channels 8qv+4h..+3
+    __bf16 *dst = img + c * 32 + slot * 4;
+    *reinterpret_cast<bf16x4 *>(dst) = hi4;
+    if (ALO) *reinterpret_cast<bf16x4 *>(dst + IMG_ELEMS) = lo4;
+}
+template <bool ALO>
+__device__ __forceinline__ void wgrad_transpose_store(__bf16 *img, int qv, int c, int h, float v0, float v1, float v2, float v3)
+{
+    const float val[4] = {v0, v1, v2, v3};
+    bf16x4 hi4, lo4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        __bf16 hh, ll;
+        split_bf16(val[e], hh, ll);
+        hi4[e] = hh;
+        lo4[e] = ll;
+    }
+    wgrad_transpose_store<ALO>(img, qv, c, h, hi4, lo4);
+}
+
+// Filter gradient, step 2: acc[R][tt] += X[32 ch of tile R][32 px] * im2col(T)[32 px][32 taps of tile tt] for one row
+// block of a wave, behind the wave barrier that follows the stores above.  wimg: the wave's [R][hl] images; thin_hi: the
+// four column-shifted hi copies of the thin tile ([s][TCOPY], the lo copies 4 * TCOPY behind); yl: tile-local image row.
+// The order of the products per (R, tt) -- lo*hi, hi*lo, [lo*lo], hi*hi -- is part of the result's bits.  Every lane of
+// the wave must be active (the transposed reads gather across lanes).
+template <int MT, int PREC, bool ALO>
+__device__ __forceinline__ void wgrad_products(f32x16 (&acc)[MT][2], const __bf16 *wimg, const __bf16 *thin_hi, int yl,
+                                               int wxi, int lane)
+{
+    const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        // B fragments: tap column of this lane, 8 consecutive pixels 16kk + 8h + (0..7)
+        bf16x8 Bh[2], Bl[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const int tap = 32 * tt + c, ti = tap >> 3, tj = tap & 7;
+            const int e0 = wxi * 32 + 16 * kk + 8 * h + (tj & 4);
+            const __bf16 *ph = thin_hi + (tj & 3) * TCOPY + (yl + ti) * TPITCH + e0;
+            Bh[tt] = lds_window8(ph);
+            if (PREC != 1) Bl[tt] = lds_window8(ph + 4 * TCOPY);
+        }
+#pragma unroll
+        for (int R = 0; R < MT; ++R) {
+            // A fragments by transposed reads: lane (i = lane&15 of group g) gets channel
+            // 16(g&1) + i, pixels 16kk + 8h + 4*half + (0..3)
+            const int gg = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
+            bf16x4 part[2][2];
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int row = 16 * kk + 8 * h + 4 * half + qq;
+                const int slot = (4 * gg + pp) ^ ((row >> 1) & 7);
+                const __bf16 *src = wimg + (size_t)(R * 2) * IMG_ELEMS + row * 32 + slot * 4;
+                part[0][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                    (__attribute__((address_space(3))) bf16x4 *)(src));
+                if (ALO)
+                    part[1][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                        (__attribute__((address_space(3))) bf16x4 *)(src + IMG_ELEMS));
+            }
+            const bf16x8 Ah = __builtin_shufflevector(part[0][0], part[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
+            bf16x8 Al;
+            if (ALO) Al = __builtin_shufflevector(part[1][0], part[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                if (PREC != 1) {
+                    if (ALO) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[tt], acc[R][tt], 0, 0, 0);
+                    acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[tt], acc[R][tt], 0, 0, 0);
+                    if (PREC == 2 && ALO) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bl[tt], acc[R][tt], 0, 0, 0);
+                }
+                acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[tt], acc[R][tt], 0, 0, 0);
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Filter gradient, step 3: the NWS waves of a sum add their [ch][tap] accumulators through LDS -- wave 0 stores, the
+// others add in turn: a fixed order, every lane owns its words -- into operator slot `slot` of red ([NSLOT][M][64]),
+// and the workgroup (64 * NWS * NSLOT threads, all of which call this) copies red out as its partial, in
+// k_wgrad_reduce's layout.  w: this wave's place in its sum.
+template <int MT, int NWS, int NSLOT>
+__device__ __forceinline__ void wgrad_wave_sum(const f32x16 (&acc)[MT][2], float *red, int slot, int w_mine, int tid,
+                                               float *dst)
+{
+    constexpr int M = 32 * MT;
+    const int c = tid & 31, h = (tid >> 5) & 1;
+    for (int w = 0; w < NWS; ++w) {
+        __syncthreads();
+        if (w_mine == w) {
+#pragma unroll
+            for (int R = 0; R < MT; ++R)
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int ch = 32 * R + (v & 3) + 8 * (v >> 2) + 4 * h;
+                        float *dstw = &red[(slot * M + ch) * 64 + 32 * tt + c];
+                        *dstw = (w == 0 ? 0.0f : *dstw) + acc[R][tt][v];
+                    }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < NSLOT * M * 64; i += 64 * NWS * NSLOT) dst[i] = red[i];
+}
+
+// reverse stage: the wave's sum of each per-lane threshold partial, into the wave's [64] row of an LDS [wave][64] array.
+// lane c of each half holds the wave's sum for accumulator index i = c mod (16 MT):
+// register v = i & 15 of tile R = i >> 4  ->  channel 32R + 8(v>>2) + 4h + (v&3)
+template <int MT>
+__device__ __forceinline__ void tsum_to_lds(const float (&tsum)[MT * 16], float *tacc_wave, int c, int h)
+{
+    const float tacc = lane_transpose_sum(tsum, c);
+    if (c < MT * 16) {
+        const int R = c >> 4, v = c & 15;
+        tacc_wave[32 * R + 8 * (v >> 2) + 4 * h + (v & 3)] = tacc;
     }
 }
 
@@ -496,12 +674,9 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     __bf16 *const rt_dst = rt + rt_xx * PITCH + rt_y0;
     float stg[RUN];
     auto stage_load = [&](int t) {
-        int bid = p.rev ? numTiles - 1 - t : t;
-        const int txi = bid % p.tilesX; bid /= p.tilesX;
-        const int tyi = bid % p.tilesY;
-        const int n = bid / p.tilesY;
-        const float *rimg = p.r + (size_t)n * HW;
-        const int gy0 = tyi * TH - HALO + rt_y0, gx = txi * TW - HALO + rt_xx;
+        const TileAt q = tile_decode(t, numTiles, p.tilesX, p.tilesY, p.rev);
+        const float *rimg = p.r + (size_t)q.n * HW;
+        const int gy0 = q.tyi * TH - HALO + rt_y0, gx = q.txi * TW - HALO + rt_xx;
         const bool colok = rt_on && t < numTiles && !CDL_DBG(p.dbg, 8) && gx >= 0 && gx < p.W;
 #pragma unroll
         for (int j = 0; j < RUN; ++j) {
@@ -525,12 +700,9 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     __bf16 *const t2_dst = thin2 + t2_yy * TPITCH + t2_x0;
     float stg2[DA ? RUN : 1];
     auto stage2_load = [&](int t) {
-        int bid = p.rev ? numTiles - 1 - t : t;
-        const int txi = bid % p.tilesX; bid /= p.tilesX;
-        const int tyi = bid % p.tilesY;
-        const int n = bid / p.tilesY;
-        const float *timg = p.r2 + (t < numTiles ? (size_t)n * HW : 0);      // (past the last tile: nothing is read)
-        const int gy = tyi * TH - HALO + t2_yy, gx0 = txi * TW - HALO + t2_x0;
+        const TileAt q = tile_decode(t, numTiles, p.tilesX, p.tilesY, p.rev);
+        const float *timg = p.r2 + (t < numTiles ? (size_t)q.n * HW : 0);    // (past the last tile: nothing is read)
+        const int gy = q.tyi * TH - HALO + t2_yy, gx0 = q.txi * TW - HALO + t2_x0;
         const bool rowok = t2_on && t < numTiles && !CDL_DBG(p.dbg, 8) && gy >= 0 && gy < p.H;
 #pragma unroll
         for (int j = 0; j < (DA ? RUN : 1); ++j) {
@@ -548,11 +720,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     f32x16 dacc[DA ? MT : 1][2];              // DA: dA_k[channel tile][tap tile], over every tile of this workgroup
     if constexpr (DA) {
 #pragma unroll
-        for (int R = 0; R < MT; ++R)
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) dacc[R][tt][v] = 0.0f;
+        for (int R = 0; R < MT; ++R) zero_tiles(dacc[R]);
         // pad elements of the copies are read (into ignored tap columns) and must stay finite
         for (int i = tid; i < LDS_DA_THIN / 16; i += NT) reinterpret_cast<uint4 *>(thin2)[i] = make_uint4(0, 0, 0, 0);
         stage2_load(blockIdx.x);
@@ -587,14 +755,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     float tslr[MAP_FWD ? MT * 16 : 1];
     bool slope_any = false;
     if constexpr (MAP_FWD) {
-#pragma unroll
-        for (int R = 0; R < MT; ++R)
-#pragma unroll
-            for (int qv = 0; qv < 4; ++qv) {
-                const float4 s4 = *reinterpret_cast<const float4 *>(&slope_s[32 * R + 8 * qv + 4 * h]);
-                tslr[16 * R + 4 * qv + 0] = s4.x; tslr[16 * R + 4 * qv + 1] = s4.y;
-                tslr[16 * R + 4 * qv + 2] = s4.z; tslr[16 * R + 4 * qv + 3] = s4.w;
-            }
+        lane_channel_values<MT>(tslr, slope_s, h);
         slope_any = __ballot(lane < M && !(slope_s[lane] >= 0.0f && slope_s[lane] < __builtin_inff())) != 0ull;
     }
 
@@ -605,12 +766,9 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
 
 #pragma unroll 1
     for (int t = blockIdx.x; t < numTiles; t += gridDim.x) {
-    const int tile = p.rev ? numTiles - 1 - t : t;
-    int bid = tile;
-    const int txi = bid % p.tilesX; bid /= p.tilesX;
-    const int tyi = bid % p.tilesY;
-    const int n = bid / p.tilesY;
-    const int tx0 = txi * TW, ty0 = tyi * TH;
+    const TileAt at = tile_decode(t, numTiles, p.tilesX, p.tilesY, p.rev);
+    const int tile = at.tile, n = at.n;
+    const int tx0 = at.txi * TW, ty0 = at.tyi * TH;
     const int x = tx0 + xl;
     if (MODE != MODE_BWD && tid < M) tau_s[tid] = p.tau[(size_t)n * M + tid];
     __syncthreads();                         // thin copies + tau of this tile are in place
@@ -642,16 +800,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     // element (u - clamp(u, -t, t)) instead of 10
     const bool tau_neg = (MODE != MODE_BWD && __ballot(lane < M && !(tau_s[lane] >= 0.0f)) != 0ull) || slope_any;   // negative OR NaN: the general, NaN-preserving form
     float taur[MT * 16];                     // forward: this lane's 16 MT thresholds
-    if (MODE != MODE_BWD) {
-#pragma unroll
-        for (int R = 0; R < MT; ++R)
-#pragma unroll
-            for (int qv = 0; qv < 4; ++qv) {
-                const float4 t4 = *reinterpret_cast<const float4 *>(&tau_s[32 * R + 8 * qv + 4 * h]);
-                taur[16 * R + 4 * qv + 0] = t4.x; taur[16 * R + 4 * qv + 1] = t4.y;
-                taur[16 * R + 4 * qv + 2] = t4.z; taur[16 * R + 4 * qv + 3] = t4.w;
-            }
-    }
+    if (MODE != MODE_BWD) lane_channel_values<MT>(taur, tau_s, h);
 
     // register v of accumulator tile R is channel 32R + 8(v>>2) + 4h + (v&3) of pixel column c
     const bool xok = x < p.W;
@@ -715,16 +864,8 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int col = xl + 2 * ks + h;
-            const __bf16 *ph = rt + (0 * 4 + q) * COPY + col * PITCH + e;
-            const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(ph);
-            const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(ph + 4);
-            rh[ks] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-            if (PREC != 1) {
-                const __bf16 *pl = rt + (1 * 4 + q) * COPY + col * PITCH + e;
-                const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(pl);
-                const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(pl + 4);
-                rl[ks] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            rh[ks] = lds_window8(rt + (0 * 4 + q) * COPY + col * PITCH + e);
+            if (PREC != 1) rl[ks] = lds_window8(rt + (1 * 4 + q) * COPY + col * PITCH + e);
         }
 
         __builtin_amdgcn_sched_barrier(0);   // phase fences: keep the scheduler from hoisting every LDS
@@ -735,10 +876,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
         // outer / k-step inner was 12 dependent products per accumulator, each fragment read followed by a full LDS
         // wait: cdl_fusedg.hip's timeline study)
         f32x16 acc[MT];
-#pragma unroll
-        for (int R = 0; R < MT; ++R)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[R][v] = 0.0f;
+        zero_tiles(acc);
         if CDL_DBG(p.dbg, 4) {
 #pragma unroll
             for (int R = 0; R < MT; ++R) acc[R][0] = (float)rh[0][0] + (float)rl[1][1];
@@ -844,7 +982,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                 for (int R = 0; R < MT; ++R)
 #pragma unroll
                     for (int qv = 0; qv < 4; ++qv) {
-                        const float4 s4 = *reinterpret_cast<const float4 *>(&slope_s[32 * R + 8 * qv + 4 * h]);
+                        const float4 s4 = lane_channel_quad(slope_s, R, qv, h);
                         const float sl[4] = {s4.x, s4.y, s4.z, s4.w};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -865,74 +1003,16 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
             // accumulator registers (register v of tile R = channel 32R + 8(v>>2) + 4h + (v&3) of pixel column c: the
             // layout its loads have) instead of from memory
             __bf16 *wimg = imgs2 + (size_t)wid * (MT * 2) * IMG_ELEMS;
+            constexpr bool ALO = PREC != 1 && LOUT != LAY_BLK16;          // a bf16-stored du_k has no lo part
 #pragma unroll
             for (int R = 0; R < MT; ++R)
 #pragma unroll
-                for (int qv = 0; qv < 4; ++qv) {
-                    bf16x4 hi4, lo4;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float val = acc[R][4 * qv + e];
-                        const __bf16 hh = (__bf16)val;
-                        hi4[e] = hh;
-                        lo4[e] = (__bf16)(val - (float)hh);
-                    }
-                    const int slot = (2 * qv + h) ^ ((c >> 1) & 7);      // 8-byte slot of channels 8qv+4h..+3
-                    __bf16 *dst = wimg + (size_t)(R * 2) * IMG_ELEMS + c * 32 + slot * 4;
-                    *reinterpret_cast<bf16x4 *>(dst) = hi4;
-                    if (PREC != 1 && LOUT != LAY_BLK16) *reinterpret_cast<bf16x4 *>(dst + IMG_ELEMS) = lo4;
-                }
+                for (int qv = 0; qv < 4; ++qv)
+                    wgrad_transpose_store<ALO>(wimg + (size_t)(R * 2) * IMG_ELEMS, qv, c, h, acc[R][4 * qv], acc[R][4 * qv + 1],
+                                               acc[R][4 * qv + 2], acc[R][4 * qv + 3]);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 Bh[2], Bl[2];
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    const int tap = 32 * tt + c, ti = tap >> 3, tj = tap & 7;
-                    const int e0 = wxi * 32 + 16 * kk + 8 * h + (tj & 4);
-                    const __bf16 *ph = thin2 + (0 * 4 + (tj & 3)) * TCOPY + (yl + ti) * TPITCH + e0;
-                    const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(ph);
-                    const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(ph + 4);
-                    Bh[tt] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    if (PREC != 1) {
-                        const __bf16 *pl = ph + 4 * TCOPY;
-                        const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(pl);
-                        const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(pl + 4);
-                        Bl[tt] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    }
-                }
-#pragma unroll
-                for (int R = 0; R < MT; ++R) {
-                    const int gg = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
-                    bf16x4 part[2][2];
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        const int row = 16 * kk + 8 * h + 4 * half + qq;
-                        const int slot = (4 * gg + pp) ^ ((row >> 1) & 7);
-                        const __bf16 *src = wimg + (size_t)(R * 2) * IMG_ELEMS + row * 32 + slot * 4;
-                        part[0][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4 *)(src));
-                        if (PREC != 1 && LOUT != LAY_BLK16)
-                            part[1][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                                (__attribute__((address_space(3))) bf16x4 *)(src + IMG_ELEMS));
-                    }
-                    const bf16x8 Ah = __builtin_shufflevector(part[0][0], part[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    bf16x8 Al;
-                    if (PREC != 1 && LOUT != LAY_BLK16) Al = __builtin_shufflevector(part[1][0], part[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) {
-                        if (PREC != 1) {
-                            if (LOUT != LAY_BLK16) dacc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[tt], dacc[R][tt], 0, 0, 0);
-                            dacc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[tt], dacc[R][tt], 0, 0, 0);
-                            if (PREC == 2 && LOUT != LAY_BLK16) dacc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bl[tt], dacc[R][tt], 0, 0, 0);
-                        }
-                        dacc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[tt], dacc[R][tt], 0, 0, 0);
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wgrad_products<MT, PREC, ALO>(dacc, wimg, thin2, yl, wxi, lane);
         }
         if (MODE == MODE_BWD && !p.do_synth) continue;
         if CDL_DBG(p.dbg, 2) { ring[0][0] += acc[0][0] + acc[MT - 1][15]; continue; }
@@ -940,10 +1020,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
         __builtin_amdgcn_sched_barrier(0);
         // -- synthesis-like GEMM: the accumulator tiles are the B operand (k = channel) as they stand
         f32x16 D[2];
-#pragma unroll
-        for (int Rp = 0; Rp < 2; ++Rp)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) D[Rp][v] = 0.0f;
+        zero_tiles(D);
         {
             // 16-channel k-steps q = 2R + s; the weight fragments of step q+1 (both tap tiles) are read while the products
             // of step q issue, and the products alternate between the two tap tiles
@@ -966,10 +1043,10 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                 bf16x8 zh, zl;
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) {
-                    const float val = acc[R][8 * s + jj];
-                    const __bf16 hh = (__bf16)val;
+                    __bf16 hh, ll;
+                    split_bf16(acc[R][8 * s + jj], hh, ll);
                     zh[jj] = hh;
-                    if (PREC != 1 && LOUT != LAY_BLK16) zl[jj] = (__bf16)(val - (float)hh);   // a bf16-stored code has no lo part
+                    if (PREC != 1 && LOUT != LAY_BLK16) zl[jj] = ll;      // a bf16-stored code has no lo part
                 }
                 if (PREC != 1) {
 #pragma unroll
@@ -1022,20 +1099,8 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
         }
     }
     if (MODE == MODE_BWD) {
-        // lane c of each half holds the wave's sum for accumulator index i = c mod (16 MT):
-        // register v = i & 15 of tile R = i >> 4  ->  channel 32R + 8(v>>2) + 4h + (v&3)
-        const float tacc = lane_transpose_sum(tsum, c);
-        if (c < MT * 16) {
-            const int R = c >> 4, v = c & 15;
-            tacc_s[wid * 64 + 32 * R + 8 * (v >> 2) + 4 * h + (v & 3)] = tacc;
-        }
-        if constexpr (MAP_BWD) {             // the weighted sums take the same road, into their own [wave][64]
-            const float taccw = lane_transpose_sum(tsum_w, c);
-            if (c < MT * 16) {
-                const int R = c >> 4, v = c & 15;
-                tacc_w_s[wid * 64 + 32 * R + 8 * (v >> 2) + 4 * h + (v & 3)] = taccw;
-            }
-        }
+        tsum_to_lds<MT>(tsum, tacc_s + wid * 64, c, h);
+        if constexpr (MAP_BWD) tsum_to_lds<MT>(tsum_w, tacc_w_s + wid * 64, c, h);   // the weighted sums: their own [wave][64]
     }
     __syncthreads();                         // every wave is done with the thin copies and the slabs
     if (!LOAD_AHEAD) stage_load(t + gridDim.x);
@@ -1074,24 +1139,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
         // sum the waves through LDS (wave 0 stores, the others add in turn: fixed order, every lane owns its words) and
         // write this workgroup's partial in k_wgrad_reduce's layout, operator slot 0
         float *red = reinterpret_cast<float *>(smem);                           // [M][64] over the thin copies
-        for (int w = 0; w < NW; ++w) {
-            __syncthreads();
-            if (wid == w) {
-#pragma unroll
-                for (int R = 0; R < MT; ++R)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                        for (int v = 0; v < 16; ++v) {
-                            const int ch = 32 * R + (v & 3) + 8 * (v >> 2) + 4 * h;
-                            float *dstw = &red[ch * 64 + 32 * tt + c];
-                            *dstw = (w == 0 ? 0.0f : *dstw) + dacc[R][tt][v];
-                        }
-            }
-        }
-        __syncthreads();
-        float *dst = p.da_partial + (size_t)blockIdx.x * 2 * M * 64;
-        for (int i = tid; i < M * 64; i += NT) dst[i] = red[i];
+        wgrad_wave_sum<MT, NW, 1>(dacc, red, 0, wid, tid, p.da_partial + (size_t)blockIdx.x * 2 * M * 64);
     }
 }
 
@@ -1292,11 +1340,7 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
     __bf16 *wimg = imgs + (size_t)wid * (MT * 2) * IMG_ELEMS;
     f32x16 acc[MT][2];
 #pragma unroll
-    for (int R = 0; R < MT; ++R)
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[R][tt][v] = 0.0f;
+    for (int R = 0; R < MT; ++R) zero_tiles(acc[R]);
 
     // zero the thin copies once: pad elements are read (into ignored tap columns) and must stay finite
     for (int i = tid; i < WG_THIN_BYTES / 16; i += 512) reinterpret_cast<uint4 *>(dsm)[i] = make_uint4(0, 0, 0, 0);
@@ -1317,11 +1361,9 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
         const int t = p.single ? 2 * t0 + op : t0;         // single operator: the wave groups take alternate tiles
         Tile q;
         q.active = present && t0 < nsteps && t < p.numTiles;                  // (per wave group)
-        int bid = p.rev ? p.numTiles - 1 - t : t;
-        const int txi = bid % p.tilesX; bid /= p.tilesX;
-        const int tyi = bid % p.tilesY;
-        q.n = q.active ? bid / p.tilesY : 0;
-        q.tx0 = txi * TW; q.ty0 = tyi * GW_TH;
+        const TileAt at = tile_decode(t, p.numTiles, p.tilesX, p.tilesY, p.rev);
+        q.n = q.active ? at.n : 0;
+        q.tx0 = at.txi * TW; q.ty0 = at.tyi * GW_TH;
         return q;
     };
     // each group of 256 threads stages its own thin tile: all of a thread's elements are loaded (clamped addresses, no
@@ -1345,8 +1387,8 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
             const int i = (tid & 255) + k * 256;
             if (i >= GW_RTH * RTW) continue;
             const int yy = i / RTW, xx = i % RTW;
-            const __bf16 hh = (__bf16)tv[k];
-            const __bf16 ll = (__bf16)(tv[k] - (float)hh);
+            __bf16 hh, ll;
+            split_bf16(tv[k], hh, ll);
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 if (xx - s >= 0) {
@@ -1381,83 +1423,24 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
         }
     };
     // ---- one row block: bf16 hi/lo -> transposition images -> MFMAs against the thin tile's windows
+    // op stays the wave-uniform scalar it is (above) where the base of its thin copies is formed
+    constexpr bool ALO = PREC != 1 && LAY != LAY_BLK16;
+    const __bf16 *thin_hi = thin + op * 8 * TCOPY;
     auto row_block = [&](const Fat &f, int b) {
-        const int yl = wyi * RB + b;
 #pragma unroll
         for (int R = 0; R < MT; ++R)
 #pragma unroll
             for (int qv = 0; qv < 4; ++qv) {
-                bf16x4 hi4, lo4;
-                if (LAY == LAY_BLK16) {
-                    hi4 = __builtin_bit_cast(bf16x4, f.xr[R][qv]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float val = f.xv[R][4 * qv + e];
-                        const __bf16 hh = (__bf16)val;
-                        hi4[e] = hh;
-                        lo4[e] = (__bf16)(val - (float)hh);
-                    }
-                }
-                const int slot = (2 * qv + h) ^ ((c >> 1) & 7);      // 8-byte slot of channels 8qv+4h..+3
-                __bf16 *dst = wimg + (size_t)(R * 2) * IMG_ELEMS + c * 32 + slot * 4;
-                *reinterpret_cast<bf16x4 *>(dst) = hi4;
-                if (PREC != 1 && LAY != LAY_BLK16) *reinterpret_cast<bf16x4 *>(dst + IMG_ELEMS) = lo4;
+                __bf16 *img = wimg + (size_t)(R * 2) * IMG_ELEMS;
+                if (LAY == LAY_BLK16)
+                    wgrad_transpose_store<false>(img, qv, c, h, __builtin_bit_cast(bf16x4, f.xr[R][qv]), bf16x4{});
+                else
+                    wgrad_transpose_store<ALO>(img, qv, c, h, f.xv[R][4 * qv], f.xv[R][4 * qv + 1], f.xv[R][4 * qv + 2],
+                                               f.xv[R][4 * qv + 3]);
             }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            // B fragments: tap column of this lane, 8 consecutive pixels 16kk + 8h + (0..7)
-            bf16x8 Bh[2], Bl[2];
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                const int tap = 32 * tt + c, ti = tap >> 3, tj = tap & 7;
-                const int e0 = wxi * 32 + 16 * kk + 8 * h + (tj & 4);
-                const __bf16 *ph = thin + ((op * 2 + 0) * 4 + (tj & 3)) * TCOPY + (yl + ti) * TPITCH + e0;
-                const bf16x4 a0 = *reinterpret_cast<const bf16x4 *>(ph);
-                const bf16x4 a1 = *reinterpret_cast<const bf16x4 *>(ph + 4);
-                Bh[tt] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                if (PREC != 1) {
-                    const __bf16 *pl = ph + 4 * TCOPY;
-                    const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(pl);
-                    const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(pl + 4);
-                    Bl[tt] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-            }
-#pragma unroll
-            for (int R = 0; R < MT; ++R) {
-                // A fragments by transposed reads: lane (i = lane&15 of group g) gets channel
-                // 16(g&1) + i, pixels 16kk + 8h + 4*half + (0..3)
-                const int gg = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
-                bf16x4 part[2][2];
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int row = 16 * kk + 8 * h + 4 * half + qq;
-                    const int slot = (4 * gg + pp) ^ ((row >> 1) & 7);
-                    const __bf16 *src = wimg + (size_t)(R * 2) * IMG_ELEMS + row * 32 + slot * 4;
-                    part[0][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4 *)(src));
-                    if (PREC != 1 && LAY != LAY_BLK16)
-                        part[1][half] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4 *)(src + IMG_ELEMS));
-                }
-                const bf16x8 Ah = __builtin_shufflevector(part[0][0], part[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                bf16x8 Al;
-                if (PREC != 1 && LAY != LAY_BLK16) Al = __builtin_shufflevector(part[1][0], part[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    if (PREC != 1) {
-                        if (LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh[tt], acc[R][tt], 0, 0, 0);
-                        acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl[tt], acc[R][tt], 0, 0, 0);
-                        if (PREC == 2 && LAY != LAY_BLK16) acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bl[tt], acc[R][tt], 0, 0, 0);
-                    }
-                    acc[R][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh[tt], acc[R][tt], 0, 0, 0);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wgrad_products<MT, PREC, ALO>(acc, wimg, thin_hi, wyi * RB + b, wxi, lane);
     };
 
     static_assert(RB % 2 == 0, "the row loop alternates between two landing sets");
@@ -1487,24 +1470,7 @@ __global__ __launch_bounds__(512) void k_wgrad2d(WgradParams p)
     // ---- sum the four waves of each group through LDS (wave 0 stores, 1..3 add in turn: fixed
     //      order, every lane owns its own words) and write this workgroup's partial
     float *red = reinterpret_cast<float *>(dsm);                               // [2][M][64]
-    for (int w = 0; w < 4; ++w) {
-        __syncthreads();
-        if (wq == w) {
-#pragma unroll
-            for (int R = 0; R < MT; ++R)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        const int ch = 32 * R + (v & 3) + 8 * (v >> 2) + 4 * h;
-                        float *dstw = &red[(op * M + ch) * 64 + 32 * tt + c];
-                        *dstw = (w == 0 ? 0.0f : *dstw) + acc[R][tt][v];
-                    }
-        }
-    }
-    __syncthreads();
-    float *dst = p.partial + (size_t)blockIdx.x * 2 * M * 64;
-    for (int i = tid; i < 2 * M * 64; i += 512) dst[i] = red[i];
+    wgrad_wave_sum<MT, 4, 2>(acc, red, op, wq, tid, p.partial + (size_t)blockIdx.x * 2 * M * 64);
 }
 
 // dw[ch][i'][j'] = alpha * sum_g partial[g][op][ch][8(i'+off) + (j'+off)].  32 outputs per workgroup,
@@ -1729,6 +1695,19 @@ int launch_stage(const FusedMapParams &p, int mode, int lin, int lout, dim3 grid
     return launch_stage_lay<WY, MT, PREC, MODE_BWD>(p, lin, lout, grid, st);
 }
 
+// fn(MT, PREC) as integral constants, for M = 64 or 32 and the arithmetic f.prec (0 split3, 1 bf16, 2 split4): the one ladder
+// over the template arguments every kernel of this file takes
+template <class F>
+int dispatch_mt_prec(int M, int prec, F &&fn)
+{
+    auto by_prec = [&](auto mt) {
+        return prec == 0   ? fn(mt, std::integral_constant<int, 0>{})
+               : prec == 1 ? fn(mt, std::integral_constant<int, 1>{})
+                           : fn(mt, std::integral_constant<int, 2>{});
+    };
+    return M == 64 ? by_prec(std::integral_constant<int, 2>{}) : by_prec(std::integral_constant<int, 1>{});
+}
+
 // persistent workgroups: one per CU (most of its LDS each), striding over the tiles
 int stage_grid(const cdl_geom *, const FusedMapParams &p)
 {
@@ -1739,13 +1718,9 @@ template <int WY>
 int dispatch_stage(const cdl_geom *g, const FusedMapParams &p, int mode, const Flags &f, hipStream_t st)
 {
     dim3 grid((unsigned)stage_grid(g, p));
-    if (g->M == 64)
-        return f.prec == 0   ? launch_stage<WY, 2, 0>(p, mode, f.lin, f.lout, grid, st)
-               : f.prec == 1 ? launch_stage<WY, 2, 1>(p, mode, f.lin, f.lout, grid, st)
-                             : launch_stage<WY, 2, 2>(p, mode, f.lin, f.lout, grid, st);
-    return f.prec == 0   ? launch_stage<WY, 1, 0>(p, mode, f.lin, f.lout, grid, st)
-           : f.prec == 1 ? launch_stage<WY, 1, 1>(p, mode, f.lin, f.lout, grid, st)
-                         : launch_stage<WY, 1, 2>(p, mode, f.lin, f.lout, grid, st);
+    return dispatch_mt_prec(g->M, f.prec, [&](auto mt, auto prec) {
+        return launch_stage<WY, decltype(mt)::value, decltype(prec)::value>(p, mode, f.lin, f.lout, grid, st);
+    });
 }
 
 // persistent workgroups, one per CU (117 KB of LDS each: a CU holds one).  More than that -- it was 512 -- runs in
@@ -1886,13 +1861,9 @@ int wgrad_partials(const cdl_geom *g, const float *X0, const float *T0, float al
     p.numTiles = p.N * p.tilesX * p.tilesY;
     int G = wgrad_grid(g);
     if (p.single && G > (p.numTiles + 1) / 2) G = (p.numTiles + 1) / 2;
-    int rc;
-    if (g->M == 64)
-        rc = f.prec == 0 ? launch_wgrad<2, 0>(p, f.lin, G, S(stream))
-             : f.prec == 1 ? launch_wgrad<2, 1>(p, f.lin, G, S(stream)) : launch_wgrad<2, 2>(p, f.lin, G, S(stream));
-    else
-        rc = f.prec == 0 ? launch_wgrad<1, 0>(p, f.lin, G, S(stream))
-             : f.prec == 1 ? launch_wgrad<1, 1>(p, f.lin, G, S(stream)) : launch_wgrad<1, 2>(p, f.lin, G, S(stream));
+    const int rc = dispatch_mt_prec(g->M, f.prec, [&](auto mt, auto prec) {
+        return launch_wgrad<decltype(mt)::value, decltype(prec)::value>(p, f.lin, G, S(stream));
+    });
     if (rc) return rc;
     *job = WgradReduce{workspace, G, X0 ? dw0 : nullptr, X1 ? dw1 : nullptr, alpha0, alpha1, p.single};
     return 0;

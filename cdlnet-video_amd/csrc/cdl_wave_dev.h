@@ -10,6 +10,13 @@ constexpr int OOB = 0x7fff0000;              // byte offset beyond any buffer de
 
 enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
 
+// v = hi + lo as two bf16 (round to nearest even, then the rounded remainder): the operand split of the split-bf16 products
+__device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo)
+{
+    hi = (__bf16)v;
+    lo = (__bf16)(v - (float)hi);
+}
+
 // ---- tap packing of the synthesis-like GEMM's M dimension (cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip) ---------
 // Row t of a 32-row accumulator tile sits in register v = 4*((t>>3)&3) + (t&3) of lane half h = (t>>2)&1.  The taps
 // (i, j) of a P x P filter plane are assigned rows so that the column-direction col2im is a short static sequence:
