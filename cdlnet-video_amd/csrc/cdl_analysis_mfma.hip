@@ -16,8 +16,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "cdl_wave_dev.h"
 
 constexpr int ALX = 32, ALY = 8;          // output-pixel tile: 8 rows of 32 pixels, one row per wave
 constexpr int ANT = 64 * ALY;
@@ -33,26 +32,29 @@ __global__ void k_ana_prep(const float *__restrict__ w, uint4 *__restrict__ frag
     if (t >= MT * KS * 64) return;
     const int lane = t & 63, ks = (t >> 6) % KS, R = (t >> 6) / KS;
     const int m = 32 * R + (lane & 31), h = lane >> 5;
-    bf16x8 hi, lo;
+    float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int k = 16 * ks + 8 * h + i;
-        const float v = (m < M && k < K) ? w[(size_t)m * K + k] : 0.0f;
-        const __bf16 hh = (__bf16)v;
-        hi[i] = hh;
-        lo[i] = (__bf16)(v - (float)hh);
+        v[i] = (m < M && k < K) ? w[(size_t)m * K + k] : 0.0f;
     }
+    bf16x8 hi, lo;
+    split_bf16(v, hi, lo);
     frags[((size_t)(R * KS + ks) * 2 + 0) * 64 + lane] = __builtin_bit_cast(uint4, hi);
     frags[((size_t)(R * KS + ks) * 2 + 1) * 64 + lane] = __builtin_bit_cast(uint4, lo);
 }
 
-constexpr int OOB = 0x7fff0000;       // a vector offset beyond any descriptor: loads return 0, stores are dropped
-// buffer descriptor over [base, base + bytes) with the base made provably wave-uniform (cdl_fused2d.hip)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const float *base, size_t bytes)
+// The epilogue value where the CSR map is off: ST under the noise-level map's threshold (MAP: the general shrinkage --
+// deciding the clamp form per tile from the signs of t0, the slopes and the tile's map values was measured: 473 us against
+// 460 us per launch at cfg2, for its barrier and registers) | ST(u, tau), in the clamp form unless a threshold of the
+// workgroup is negative | u.  ch: the channel's slot in the workgroup's LDS thresholds (unused when tau == nullptr).
+template <bool MAP>
+__device__ __forceinline__ float ana_value(float u, const float *tau_s, const float *ts_s, int ch, float cm, bool has_tau,
+                                           bool tau_neg)
 {
-    const size_t a = reinterpret_cast<size_t>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((size_t)hi << 32) | lo), 0, (int)bytes, 0x00020000);
+    const float ts = tau_s[ch];
+    if (MAP) return cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[ch]));
+    return has_tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u;
 }
 
 // MAP: the thresholds follow a noise-level map (cdl_map_args: thr = tau[n,m] + cmap[n,pix] * tslope[m], every thread
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
 #pragma unroll
                 for (int u = 0; u < ITS; ++u) {
                     const int i = threadIdx.x + u * ANT;
-                    if (i < XH * XW) {
+                    if (i < XH * XW) {                                   // (written out, not split_bf16: DESIGN.md section 36)
                         const __bf16 hh = (__bf16)v[pp][u];
                         xh[(p0 + pp) * PS + i] = hh;
                         xl[(p0 + pp) * PS + i] = (__bf16)(v[pp][u] - (float)hh);
@@ -251,13 +253,13 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                 // out-of-range elements are dropped by the range check (only the vector offset is checked: channels
                 // beyond M are masked per thread in the last channel tile)
                 const size_t sb = (size_t)n * g.M * slab;
-                const __amdgpu_buffer_rsrc_t rs_in = uniform_rsrc(zin ? zin + sb : out + sb, (size_t)g.M * slab * 4);
-                const __amdgpu_buffer_rsrc_t rs_g = uniform_rsrc((zin && gate) ? gate + sb : out + sb, (size_t)g.M * slab * 4);
-                const __amdgpu_buffer_rsrc_t rs_out = uniform_rsrc(out + sb, (size_t)g.M * slab * 4);
+                const __amdgpu_buffer_rsrc_t rs_in = uniform_rsrc<true>(zin ? zin + sb : out + sb, (size_t)g.M * slab * 4);
+                const __amdgpu_buffer_rsrc_t rs_g = uniform_rsrc<true>((zin && gate) ? gate + sb : out + sb, (size_t)g.M * slab * 4);
+                const __amdgpu_buffer_rsrc_t rs_out = uniform_rsrc<true>(out + sb, (size_t)g.M * slab * 4);
                 // reverse mode (zsup): out = [zsup != 0] (zin + alpha A x), and the threshold-gradient partial of this
                 // tile, sum over its pixels of -sign(zsup) * out, per channel -- what cdl_tau_grad_gate computes from
                 // the tensor this launch writes (three fat passes of the generic reverse sweep)
-                const __amdgpu_buffer_rsrc_t rs_sup = uniform_rsrc(zsup ? zsup + sb : out + sb, (size_t)g.M * slab * 4);
+                const __amdgpu_buffer_rsrc_t rs_sup = uniform_rsrc<true>(zsup ? zsup + sb : out + sb, (size_t)g.M * slab * 4);
                 const int voff = okp ? (int)(((size_t)chh * slab + (size_t)zd * Hz * Wz + (size_t)oy * Wz + ox) * 4) : OOB;
                 const int slab4 = (int)slab * 4;
                 const int soff0 = __builtin_amdgcn_readfirstlane(32 * (r0 + R) * slab4);
@@ -329,11 +331,7 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                 for (int jj = 0; jj < NE; ++jj) {
                     const float base = gv[jj] == 0.0f ? 0.0f : bv[jj];
                     const float u = fmaf(alpha, stage[threadIdx.x + jj * ANT], base);
-                    const float ts = tau_s[32 * R + chh + 2 * jj];          // (unused when tau == nullptr)
-                    // (MAP: the general shrinkage.  Deciding the clamp form per tile from the signs of t0, the slopes and
-                    // the tile's map values was measured: 473 us against 460 us per launch at cfg2, for its barrier and registers)
-                    const float val = MAP ? cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[32 * R + chh + 2 * jj]))
-                                          : (tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u);
+                    const float val = ana_value<MAP>(u, tau_s, ts_s, 32 * R + chh + 2 * jj, cm, tau != nullptr, tau_neg);
                     const int vo = (tailR && m0 + 2 * jj >= g.M) ? OOB : voff;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rs_out, vo, soff0 + 2 * jj * slab4, 0);
                 }
@@ -357,12 +355,10 @@ __global__ __launch_bounds__(ANT) void k_ana_m(cdl_geom g, const float *__restri
                     const float base = gv[j] == 0.0f ? 0.0f : bv[j];
                     const float u = fmaf(alpha, stage[e], base);
                     const int row = n * g.M + m;
-                    const float ts = tau_s[32 * R + chh + 2 * (j0 + j)];     // (unused when tau == nullptr)
                     if (ix[j] >= 0)
                         out_n[ix[j]] = PROX ? (MAP ? cdl_prox_apply_map(px, mp, u, nbase + ix[j], row, m, g.M, cm)
                                                    : cdl_prox_apply(px, u, nbase + ix[j], row))
-                                     : MAP ? cdl_shrink(u, cdl_map_threshold(ts, cm, ts_s[32 * R + chh + 2 * (j0 + j)]))
-                                            : (tau ? (tau_neg ? cdl_shrink(u, ts) : u - __builtin_amdgcn_fmed3f(u, -ts, ts)) : u);
+                                            : ana_value<MAP>(u, tau_s, ts_s, 32 * R + chh + 2 * (j0 + j), cm, tau != nullptr, tau_neg);
                 }
             }
         }
@@ -377,10 +373,7 @@ struct Plan {
 
 bool plan_for(const cdl_geom *g, Plan *p)
 {
-    if (g->sw != g->sh || (g->sw != 1 && g->sw != 2)) return false;
-    if (g->Pw != 3 && g->Pw != 5 && g->Pw != 7 && g->Pw != 9) return false;
-    if (g->Ph != g->Pw && !(g->Ph == 9 && g->Pw == 5)) return false;      // rectangular planes: the shipped 9 x 9 x 5 net
-    if (g->pw != g->Pw / 2 || g->ph != g->Ph / 2) return false;
+    if (!cdl_mfma_plane_ok(g)) return false;
     const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
     p->MT = (g->M + 31) / 32;
     if (p->MT > 16) return false;                          // M <= 512
@@ -425,47 +418,65 @@ bool map_lds(Plan *p)
     return p->lds <= LDS_MAX;
 }
 
+// The operands of one launch as the entry point received them.  The form follows from them: px.zp -> PROX, else zsup ->
+// REV (with its partials dtp and, under a map, dtpw), mp.cmap -> MAP.  The kernel keeps its flat parameter list (a
+// bundle would move its SGPR loads); launch_mtp hands a form only the operands it reads.
+struct Args {
+    const float *x, *w;
+    float alpha;
+    const float *zin, *gate, *tau;
+    float *out;
+    cdl_prox_args px;
+    cdl_map_args mp;
+    const float *zsup;
+    float *dtp, *dtpw;
+};
+
 template <int PH, int PW, int SW, int MT, bool PROX, bool REV, bool MAP>
-int launch_mtp(const cdl_geom *g, const Plan &p, const float *x, const uint4 *frags, float alpha, const float *zin,
-               const float *gate, const float *tau, float *out, const cdl_prox_args &px, hipStream_t st,
-               const float *zsup, float *dtp, const cdl_map_args &mp, float *dtpw)
+int launch_mtp(const cdl_geom *g, const Plan &p, const Args &a, const uint4 *frags, hipStream_t st)
 {
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_ana_m<PH, PW, SW, MT, PROX, REV, MAP>, p.lds > 96 * 1024 ? LDS_MAX : 96 * 1024))
         return rc;
     CDL_TRACE_NOTE("MTW=%d tpw=%d ngy=%d lds_over_96k=%d wgs=%zu", p.MTW, p.tpw, p.ngy, p.lds > 96 * 1024 ? 1 : 0,
                    p.groups * p.ngy);
     k_ana_m<PH, PW, SW, MT, PROX, REV, MAP><<<dim3((unsigned)p.groups, (unsigned)p.ngy), ANT, p.lds, st>>>(
-        *g, x, frags, alpha, zin, gate, tau, out, px, p.tilesX, p.tilesY, p.KS, zsup, dtp, p.tpw, mp, dtpw);
+        *g, a.x, frags, a.alpha, a.zin, a.gate, a.tau, a.out, a.px, p.tilesX, p.tilesY, p.KS, REV ? a.zsup : nullptr,
+        REV ? a.dtp : nullptr, p.tpw, MAP ? a.mp : cdl_map_args{nullptr, nullptr}, REV && MAP ? a.dtpw : nullptr);
     CDL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int PH, int PW, int SW, int MT>
-int launch_mt(const cdl_geom *g, const Plan &p, const float *x, const uint4 *frags, float alpha, const float *zin,
-              const float *gate, const float *tau, float *out, const cdl_prox_args &px, hipStream_t st,
-              const float *zsup, float *dtp, const cdl_map_args &mp, float *dtpw)
+int launch_mt(const cdl_geom *g, const Plan &p, const Args &a, const uint4 *frags, hipStream_t st)
 {
-    const cdl_map_args none{nullptr, nullptr};
-    if (px.zp && mp.cmap) return launch_mtp<PH, PW, SW, MT, true, false, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, mp, nullptr);
-    if (px.zp) return launch_mtp<PH, PW, SW, MT, true, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, none, nullptr);
-    if (zsup && mp.cmap) return launch_mtp<PH, PW, SW, MT, false, true, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
-    if (zsup) return launch_mtp<PH, PW, SW, MT, false, true, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, none, nullptr);
-    if (mp.cmap) return launch_mtp<PH, PW, SW, MT, false, false, true>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, mp, nullptr);
-    return launch_mtp<PH, PW, SW, MT, false, false, false>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, nullptr, nullptr, none, nullptr);
+    const bool map = a.mp.cmap != nullptr;
+    if (a.px.zp)
+        return map ? launch_mtp<PH, PW, SW, MT, true, false, true>(g, p, a, frags, st)
+                   : launch_mtp<PH, PW, SW, MT, true, false, false>(g, p, a, frags, st);
+    if (a.zsup)
+        return map ? launch_mtp<PH, PW, SW, MT, false, true, true>(g, p, a, frags, st)
+                   : launch_mtp<PH, PW, SW, MT, false, true, false>(g, p, a, frags, st);
+    return map ? launch_mtp<PH, PW, SW, MT, false, false, true>(g, p, a, frags, st)
+               : launch_mtp<PH, PW, SW, MT, false, false, false>(g, p, a, frags, st);
 }
 
 template <int PH, int PW, int SW>
-int launch(const cdl_geom *g, const Plan &p, const float *x, const float *w, float alpha, const float *zin,
-           const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws, hipStream_t st,
-           const cdl_map_args &mp, const float *zsup = nullptr, float *dtp = nullptr, float *dtpw = nullptr)
+int launch(const cdl_geom *g, const Plan &p, const Args &a, float *ws, hipStream_t st)
 {
     uint4 *frags = reinterpret_cast<uint4 *>(ws);
     const int ntile = p.ngy * p.MTW;
     const int nprep = ntile * p.KS * 64;
-    k_ana_prep<<<(nprep + 255) / 256, 256, 0, st>>>(w, frags, g->M, g->C * g->Pd * g->Ph * g->Pw, ntile, p.KS);
+    k_ana_prep<<<(nprep + 255) / 256, 256, 0, st>>>(a.w, frags, g->M, g->C * g->Pd * g->Ph * g->Pw, ntile, p.KS);
     CDL_LAUNCH_CHECK();
-    if (p.MTW == 1) return launch_mt<PH, PW, SW, 1>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
-    return launch_mt<PH, PW, SW, 2>(g, p, x, frags, alpha, zin, gate, tau, out, px, st, zsup, dtp, mp, dtpw);
+    return p.MTW == 1 ? launch_mt<PH, PW, SW, 1>(g, p, a, frags, st) : launch_mt<PH, PW, SW, 2>(g, p, a, frags, st);
+}
+
+// the plane ladder of both entry points
+int launch_plane(const cdl_geom *g, const Plan &p, const Args &a, float *ws, void *stream)
+{
+    return cdl_mfma_dispatch_plane(g, [&](auto ph, auto pw, auto sw) {
+        return launch<decltype(ph)::value, decltype(pw)::value, decltype(sw)::value>(g, p, a, ws, S(stream));
+    });
 }
 
 // dt0[m] = sum_n sum_k s[(n M + m) S + k], dt1[m] = sum_n c[n] (...): one wave per channel; the lanes split the S tile
@@ -533,16 +544,8 @@ int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, flo
     float *dtp = ws + p.frag_uint4 * 4;
     const int S_ = (g->D / g->sd) * p.tilesY * p.tilesX;
     float *dtpw = dtp + (size_t)g->N * g->M * S_;
-    const cdl_map_args mp{cmap, nullptr};
-    int rc = CDL_EUNSUPPORTED;
-#define CDL_M(PH_, P_, S2_) \
-    if (g->Ph == PH_ && g->Pw == P_ && g->sw == S2_) \
-        rc = launch<PH_, P_, S2_>(g, p, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, ws, S(stream), mp, zsup, dtp, dtpw)
-    CDL_M(3, 3, 1); else CDL_M(5, 5, 1); else CDL_M(7, 7, 1); else CDL_M(9, 9, 1);
-    else CDL_M(3, 3, 2); else CDL_M(5, 5, 2); else CDL_M(7, 7, 2); else CDL_M(9, 9, 2);
-    else CDL_M(9, 5, 1); else CDL_M(9, 5, 2);
-#undef CDL_M
-    if (rc) return rc;
+    CDL_TRY(launch_plane(g, p, Args{x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, cdl_map_args{cmap, nullptr}, zsup, dtp, dtpw},
+                         ws, stream));
     if (cmap) {
         k_ana_tau_final<true><<<dim3(g->M, 2), 512, 0, S(stream)>>>(dtp, nullptr, dt0, dt1, g->N, g->M, S_, dtpw);
         CDL_LAUNCH_CHECK();
@@ -570,12 +573,5 @@ int cdl_mfma_analysis(const cdl_geom *g, const float *x, const float *w, float a
     if (!plan_for(g, &p) || !ws || ws_floats < p.frag_uint4 * 4) return CDL_EUNSUPPORTED;
     if ((reinterpret_cast<size_t>(ws) & 15) != 0) return CDL_EUNSUPPORTED;
     if (mp.cmap && !map_lds(&p)) return CDL_EUNSUPPORTED;
-#define CDL_M(PH_, P_, S_) \
-    if (g->Ph == PH_ && g->Pw == P_ && g->sw == S_) \
-        return launch<PH_, P_, S_>(g, p, x, w, alpha, zin, gate, tau, out, px, ws, S(stream), mp)
-    CDL_M(3, 3, 1); CDL_M(5, 5, 1); CDL_M(7, 7, 1); CDL_M(9, 9, 1);
-    CDL_M(3, 3, 2); CDL_M(5, 5, 2); CDL_M(7, 7, 2); CDL_M(9, 9, 2);
-    CDL_M(9, 5, 1); CDL_M(9, 5, 2);
-#undef CDL_M
-    return CDL_EUNSUPPORTED;
+    return launch_plane(g, p, Args{x, w, alpha, zin, gate, tau, out, px, mp, nullptr, nullptr, nullptr}, ws, stream);
 }

@@ -1,6 +1,7 @@
 // Shared helpers for the gfx950 kernels of libcdlnet_hip.so.
 #pragma once
 #include <atomic>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 #include "../../include/cdlnet_hip.h"
 
@@ -264,6 +265,38 @@ static inline bool cdl_bcast_ok(const cdl_bcast *s, int M, size_t per_m)
     return s->n == 0 || s->n == dn;
 }
 
+// ---- the filter planes of the sparse matrix-core tier (cdl_analysis_mfma.hip, cdl_synth_mfma.hip, cdl_wgrad_mfma.hip) ----
+// One gate and one ladder for the three files: a new plane is added here, and cdl_mfma_wgrad_takes agrees with the other
+// two by construction.  Equal stride 1 or 2 in the plane, odd square planes up to 9 x 9 or the 9 x 5 planes of the shipped
+// 9 x 9 x 5 net, "same" padding.
+static inline bool cdl_mfma_plane_ok(const cdl_geom *g)
+{
+    if (g->sw != g->sh || (g->sw != 1 && g->sw != 2)) return false;
+    if (g->Pw != 3 && g->Pw != 5 && g->Pw != 7 && g->Pw != 9) return false;
+    if (g->Ph != g->Pw && !(g->Ph == 9 && g->Pw == 5)) return false;
+    return g->pw == g->Pw / 2 && g->ph == g->Ph / 2;
+}
+
+// fn(PH, PW, SW) as integral constants for the ten planes of the gate (the idiom of cdl_fused2d.hip's dispatch_mt_prec);
+// CDL_EUNSUPPORTED for any other plane
+template <class F>
+static inline int cdl_mfma_dispatch_plane(const cdl_geom *g, F &&fn)
+{
+    using std::integral_constant;
+    auto by_stride = [&](auto ph, auto pw) {
+        return g->sw == 1   ? fn(ph, pw, integral_constant<int, 1>{})
+               : g->sw == 2 ? fn(ph, pw, integral_constant<int, 2>{})
+                            : CDL_EUNSUPPORTED;
+    };
+    if (g->Ph == 9 && g->Pw == 5) return by_stride(integral_constant<int, 9>{}, integral_constant<int, 5>{});
+    if (g->Ph != g->Pw) return CDL_EUNSUPPORTED;
+    if (g->Pw == 3) return by_stride(integral_constant<int, 3>{}, integral_constant<int, 3>{});
+    if (g->Pw == 5) return by_stride(integral_constant<int, 5>{}, integral_constant<int, 5>{});
+    if (g->Pw == 7) return by_stride(integral_constant<int, 7>{}, integral_constant<int, 7>{});
+    if (g->Pw == 9) return by_stride(integral_constant<int, 9>{}, integral_constant<int, 9>{});
+    return CDL_EUNSUPPORTED;
+}
+
 // register-tiled variants (cdl_generic_tiled.hip): CDL_EUNSUPPORTED means "use the untiled kernel"
 int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                        const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
@@ -305,17 +338,19 @@ size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g);
 int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                           const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *ws,
                           size_t ws_floats, void *stream, float *dtau_n = nullptr, const float *cmap = nullptr);
-// matrix-core filter gradients (cdl_wgrad_mfma.hip), same convention
-int cdl_mfma_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
-                   float *ws, size_t ws_floats, void *stream);
-int cdl_mfma_wgrad_pair(const cdl_geom *g, const float *F0, const float *x0, float alpha0, float *dw0, const float *F1,
-                        const float *x1, float alpha1, float *dw1, float *ws, size_t ws_floats, void *stream);
+// matrix-core filter gradients (cdl_wgrad_mfma.hip), same convention: dw = alpha * F (x) x for one operand set, or for two
+// ungated ones of the same geometry (dA_k and dB_k of one iteration) in ONE launch + ONE fold.  gate: support gate of a
+// single F (nullable).  rsc != 0: the fat operands F are in the strip kernel's row-strip channel-major layout (cdl_strip.hip,
+// CDL_LAY_RSC; ungated).  cdl_mfma_wgrad_takes: this kernel (and not a VALU fallback, which reads the reference layout
+// only) is what cdl_wgrad would run for the geometry.
+struct cdl_wgrad_op {
+    const float *F, *x;
+    float alpha;
+    float *dw;
+};
+int cdl_mfma_wgrad(const cdl_geom *g, const cdl_wgrad_op *ops, int nops, const float *gate, int rsc, float *ws,
+                   size_t ws_floats, void *stream);
 size_t cdl_mfma_wgrad_ws_floats(const cdl_geom *g);
 bool cdl_mfma_wgrad_takes(const cdl_geom *g);
-int cdl_mfma_wgrad_lay(const cdl_geom *g, const float *F, const float *x, float alpha, float *dw, float *ws,
-                       size_t ws_floats, int rsc, void *stream);
-int cdl_mfma_wgrad_pair_lay(const cdl_geom *g, const float *F0, const float *x0, float alpha0, float *dw0,
-                            const float *F1, const float *x1, float alpha1, float *dw1, float *ws, size_t ws_floats,
-                            int rsc, void *stream);
 int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha,
                     float *dw, float *workspace, size_t workspace_floats, void *stream);

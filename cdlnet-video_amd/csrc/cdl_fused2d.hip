@@ -268,19 +268,7 @@ template <int LAY> __host__ __device__ inline size_t lay_image_bytes(int M, int 
     return LAY == LAY_NCHW ? (size_t)M * H * W * 4 : blk_image_elems(M, H, W) * (LAY == LAY_BLK ? 4 : 2);
 }
 
-// Buffer descriptor from a WAVE-UNIFORM pointer.  hipcc cannot prove uniformity of anything derived from
-// threadIdx (a wave index, an operator picked per wave group): it then wraps EVERY buffer access in a
-// readfirstlane "waterfall" loop, which serialises the accesses (seen in k_wgrad2d: each of the 8-32 loads of
-// a row block had its own loop; with bf16 storage each was followed by s_waitcnt vmcnt(0)).  Reading the
-// pointer words through readfirstlane makes the descriptor provably scalar.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base, size_t bytes)
-{
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    void *b = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(b, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
+// (buffer descriptors from wave-uniform pointers: uniform_rsrc, cdl_wave_dev.h)
 
 // round-to-nearest-even fp32 -> bf16 -> fp32 (what a bf16-stored code tensor holds)
 __device__ __forceinline__ float bf16_round(float v) { return (float)(__bf16)v; }

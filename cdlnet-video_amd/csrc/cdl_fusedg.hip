@@ -1209,12 +1209,13 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
             // q_k = -mask A_k^T du_k; with dyp the same sum, unmasked, goes to dyp (= at k = K-1, += after)
             rc = cdl_fusedg_assemble(g, patches, mask, nullptr, -1.0f, q, dyp, k < K - 1, stream);
             if (rc) return rc;
-            rc = rsc ? cdl_mfma_wgrad_pair_lay(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], wgrad_ws,
-                                               wgrad_ws_floats, 1, stream)
+            const cdl_wgrad_op ops[2] = {{duk, r[k - 1], -1.0f, dA[k]}, {z[k - 1], q, 1.0f, dB[k]}};
+            rc = rsc ? cdl_mfma_wgrad(g, ops, 2, nullptr, 1, wgrad_ws, wgrad_ws_floats, stream)
                      : cdl_wgrad_pair(g, duk, r[k - 1], -1.0f, dA[k], z[k - 1], q, 1.0f, dB[k], wgrad_ws, wgrad_ws_floats, stream);
             thin = q;
         } else {
-            rc = rsc ? cdl_mfma_wgrad_lay(g, duk, yp, 1.0f, dA[0], wgrad_ws, wgrad_ws_floats, 1, stream)
+            const cdl_wgrad_op op{duk, yp, 1.0f, dA[0]};
+            rc = rsc ? cdl_mfma_wgrad(g, &op, 1, nullptr, 1, wgrad_ws, wgrad_ws_floats, stream)
                      : cdl_wgrad(g, duk, nullptr, yp, 1.0f, dA[0], wgrad_ws, wgrad_ws_floats, stream);
         }
         if (rc) return rc;

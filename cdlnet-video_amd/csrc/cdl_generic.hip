@@ -944,7 +944,8 @@ int cdl_wgrad(const cdl_geom *g, const float *z, const float *gate, const float 
             if (rcd != CDL_EUNSUPPORTED) return rcd;
         }
         if (mfma_wgrad_enabled()) {
-            const int rcm = cdl_mfma_wgrad(g, z, gate, x, alpha, dw, workspace, workspace_floats, stream);
+            const cdl_wgrad_op op{z, x, alpha, dw};
+            const int rcm = cdl_mfma_wgrad(g, &op, 1, gate, 0, workspace, workspace_floats, stream);
             if (rcm != CDL_EUNSUPPORTED) return rcm;
         }
         const int rc = cdl_tiled_wgrad(g, z, gate, x, alpha, dw, workspace, workspace_floats, stream);
@@ -964,7 +965,8 @@ int cdl_wgrad_pair(const cdl_geom *g, const float *z0, const float *x0, float al
     if (!cdl_geom_ok(g) || !z0 || !x0 || !dw0 || !z1 || !x1 || !dw1) return CDL_EINVAL;
     if (g->Pw <= PWMAX && !cdl_opts().no_tiled && mfma_wgrad_enabled() &&
         !(mfma_dense_enabled() && cdl_dense_wgrad_ws_floats(g) > 0)) {
-        const int rc = cdl_mfma_wgrad_pair(g, z0, x0, alpha0, dw0, z1, x1, alpha1, dw1, workspace, workspace_floats, stream);
+        const cdl_wgrad_op ops[2] = {{z0, x0, alpha0, dw0}, {z1, x1, alpha1, dw1}};
+        const int rc = cdl_mfma_wgrad(g, ops, 2, nullptr, 0, workspace, workspace_floats, stream);
         if (rc != CDL_EUNSUPPORTED) return rc;
     }
     const int rc = cdl_wgrad(g, z0, nullptr, x0, alpha0, dw0, workspace, workspace_floats, stream);

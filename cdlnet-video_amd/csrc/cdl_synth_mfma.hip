@@ -16,12 +16,10 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "cdl_wave_dev.h"
 
 constexpr int TCX = 32, TCY = 8;      // code-pixel tile of a workgroup: 8 blocks of 32 pixels, one per wave
 constexpr int SNT = 64 * TCY;         // 8 waves: with 64-108 KB of LDS only one workgroup fits a CU
-constexpr int OOB = 0x7fff0000;       // a vector offset beyond any descriptor: the load returns 0
 constexpr int KSC = 4;                // k-steps whose code values are loaded together (32 loads in flight per lane)
 
 // ------------------------------------------------------------------------------------------
@@ -41,28 +39,17 @@ __global__ void k_synth_prep(const float *__restrict__ w, uint4 *__restrict__ fr
     const int g = r;                                        // c * Pd + kd
     const int row = lane & 31, h = lane >> 5;
     const int tap = 32 * R + row;
-    bf16x8 hi, lo;
+    float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int m = 16 * ks + 8 * h + i;
-        float v = 0.0f;
-        if (m < M && tap < taps) v = w[((size_t)m * C * Pd + g) * taps + tap];
-        const __bf16 hh = (__bf16)v;
-        hi[i] = hh;
-        lo[i] = (__bf16)(v - (float)hh);
+        v[i] = (m < M && tap < taps) ? w[((size_t)m * C * Pd + g) * taps + tap] : 0.0f;
     }
+    bf16x8 hi, lo;
+    split_bf16(v, hi, lo);
     const size_t base = (((size_t)g * RT + R) * KS + ks) * 2;
     frags[(base + 0) * 64 + lane] = __builtin_bit_cast(uint4, hi);
     frags[(base + 1) * 64 + lane] = __builtin_bit_cast(uint4, lo);
-}
-
-// buffer descriptor over [base, base + bytes) with the base made provably wave-uniform (otherwise every access gets a
-// waterfall loop, cdl_fused2d.hip)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const float *base, size_t bytes)
-{
-    const size_t a = reinterpret_cast<size_t>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((size_t)hi << 32) | lo), 0, (int)bytes, 0x00020000);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -105,8 +92,8 @@ __global__ __launch_bounds__(SNT) void k_synth_m(cdl_geom g, const float *__rest
     // load costs no address arithmetic (64-bit pointer math per element was a quarter of the kernel's VALU work at
     // M = 169).  Only the vector offset is range-checked: channels beyond M are masked per lane in the last k-step.
     const size_t sbase = (size_t)n * g.M * slab;
-    const __amdgpu_buffer_rsrc_t rz = uniform_rsrc(z + sbase, (size_t)g.M * slab * 4);
-    const __amdgpu_buffer_rsrc_t rg = uniform_rsrc(gate ? gate + sbase : z + sbase, (size_t)g.M * slab * 4);
+    const __amdgpu_buffer_rsrc_t rz = uniform_rsrc<true>(z + sbase, (size_t)g.M * slab * 4);
+    const __amdgpu_buffer_rsrc_t rg = uniform_rsrc<true>(gate ? gate + sbase : z + sbase, (size_t)g.M * slab * 4);
     const int slab4 = (int)slab * 4;
 
     // KSM > 0: the code values of this wave's pixel row are loaded and split ONCE (KS <= KSM k-steps in registers) and
@@ -135,12 +122,7 @@ __global__ __launch_bounds__(SNT) void k_synth_m(cdl_geom g, const float *__rest
         for (int q = 0; q < KSM; ++q) {
             float zv[8];
             load8(q, zv);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const __bf16 hh = (__bf16)zv[i];
-                cbh[q][i] = hh;
-                cbl[q][i] = (__bf16)(zv[i] - (float)hh);
-            }
+            split_bf16(zv, cbh[q], cbl[q]);
         }
     }
 
@@ -174,9 +156,7 @@ __global__ __launch_bounds__(SNT) void k_synth_m(cdl_geom g, const float *__rest
                     for (int R = 0; R < RT; ++R) {
                         const bf16x8 ah = __builtin_bit_cast(bf16x8, wl[((R * KCH + q) * 2 + 0) * 64 + lane]);
                         const bf16x8 al = __builtin_bit_cast(bf16x8, wl[((R * KCH + q) * 2 + 1) * 64 + lane]);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, cbh[q], acc[R], 0, 0, 0);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, cbl[q], acc[R], 0, 0, 0);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, cbh[q], acc[R], 0, 0, 0);
+                        mfma_split3(acc[R], ah, al, cbh[q], cbl[q]);
                     }
                 }
             } else
@@ -189,19 +169,12 @@ __global__ __launch_bounds__(SNT) void k_synth_m(cdl_geom g, const float *__rest
                     const int ks = ks0 + q;
                     if (ks >= kc0 + kcn) break;
                     bf16x8 bh, bl;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const __bf16 hh = (__bf16)zv[q][i];
-                        bh[i] = hh;
-                        bl[i] = (__bf16)(zv[q][i] - (float)hh);
-                    }
+                    split_bf16(zv[q], bh, bl);
 #pragma unroll
                     for (int R = 0; R < RT; ++R) {
                         const bf16x8 ah = __builtin_bit_cast(bf16x8, wl[((R * KCH + ks - kc0) * 2 + 0) * 64 + lane]);
                         const bf16x8 al = __builtin_bit_cast(bf16x8, wl[((R * KCH + ks - kc0) * 2 + 1) * 64 + lane]);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[R], 0, 0, 0);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[R], 0, 0, 0);
-                        acc[R] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[R], 0, 0, 0);
+                        mfma_split3(acc[R], ah, al, bh, bl);
                     }
                 }
             }
@@ -380,10 +353,7 @@ struct Plan {
 
 bool plan_for(const cdl_geom *g, Plan *p)
 {
-    if (g->sw != g->sh || (g->sw != 1 && g->sw != 2)) return false;
-    if (g->Pw != 3 && g->Pw != 5 && g->Pw != 7 && g->Pw != 9) return false;
-    if (g->Ph != g->Pw && !(g->Ph == 9 && g->Pw == 5)) return false;      // rectangular planes: the shipped 9 x 9 x 5 net
-    if (g->pw != g->Pw / 2 || g->ph != g->Ph / 2) return false;
+    if (!cdl_mfma_plane_ok(g)) return false;
     const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
     p->tilesX = (Wz + TCX - 1) / TCX;
     p->tilesY = (Hz + TCY - 1) / TCY;
@@ -462,12 +432,7 @@ int cdl_mfma_synthesis(const cdl_geom *g, const float *z, const float *gate, con
     Plan p;
     if (!plan_for(g, &p) || !ws || ws_floats < p.frag_uint4 * 4 + p.patch_floats) return CDL_EUNSUPPORTED;
     if ((reinterpret_cast<size_t>(ws) & 15) != 0) return CDL_EUNSUPPORTED;
-#define CDL_M(PH_, P_, S_)                                                  \
-    if (g->Ph == PH_ && g->Pw == P_ && g->sw == S_)                         \
-        return launch<PH_, P_, S_>(g, p, z, gate, w, alpha, mask, sub, out, ws, S(stream))
-    CDL_M(3, 3, 1); CDL_M(5, 5, 1); CDL_M(7, 7, 1); CDL_M(9, 9, 1);
-    CDL_M(3, 3, 2); CDL_M(5, 5, 2); CDL_M(7, 7, 2); CDL_M(9, 9, 2);
-    CDL_M(9, 5, 1); CDL_M(9, 5, 2);
-#undef CDL_M
-    return CDL_EUNSUPPORTED;
+    return cdl_mfma_dispatch_plane(g, [&](auto ph, auto pw, auto sw) {
+        return launch<decltype(ph)::value, decltype(pw)::value, decltype(sw)::value>(g, p, z, gate, w, alpha, mask, sub, out, ws, S(stream));
+    });
 }

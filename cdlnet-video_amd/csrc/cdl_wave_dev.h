@@ -1,4 +1,5 @@
-// Device-side pieces shared by the fused kernels (cdl_fused2d.hip, cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip).
+// Device-side pieces shared by the fused kernels (cdl_fused2d.hip, cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip) and by
+// the sparse matrix-core tier (cdl_analysis_mfma.hip, cdl_synth_mfma.hip, cdl_wgrad_mfma.hip).
 // Included inside each file's anonymous namespace, so every object keeps its own internal copies.
 #pragma once
 
@@ -6,15 +7,53 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-constexpr int OOB = 0x7fff0000;              // byte offset beyond any buffer descriptor range
+constexpr int OOB = 0x7fff0000;              // byte offset beyond any buffer descriptor range: loads return 0, stores are dropped
 
 enum { MODE_FWD = 0, MODE_FIRST = 1, MODE_BWD = 2 };
+
+// Buffer descriptor from a WAVE-UNIFORM pointer.  hipcc cannot prove uniformity of anything derived from
+// threadIdx (a wave index, an operator picked per wave group): it then wraps EVERY buffer access in a
+// readfirstlane "waterfall" loop, which serialises the accesses (seen in k_wgrad2d: each of the 8-32 loads of
+// a row block had its own loop; with bf16 storage each was followed by s_waitcnt vmcnt(0)).  Reading the
+// pointer words through readfirstlane makes the descriptor provably scalar.
+// SCALAR_SIZE: `bytes` is formed from kernel arguments alone, which hipcc does see as scalar, and is taken as it is (the
+// sparse matrix-core tier: the readfirstlane of a scalar goes through a VGPR, which cost seven instances of k_ana_m and
+// k_synth_m an occupancy step).
+template <bool SCALAR_SIZE = false>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base, size_t bytes)
+{
+    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    void *b = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
+    return __builtin_amdgcn_make_buffer_rsrc(b, 0, SCALAR_SIZE ? (int)bytes : __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
 
 // v = hi + lo as two bf16 (round to nearest even, then the rounded remainder): the operand split of the split-bf16 products
 __device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo)
 {
     hi = (__bf16)v;
     lo = (__bf16)(v - (float)hi);
+}
+// the same for the 8 values of one MFMA operand fragment
+__device__ __forceinline__ void split_bf16(const float (&v)[8], bf16x8 &hi, bf16x8 &lo)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        __bf16 h, l;
+        split_bf16(v[i], h, l);
+        hi[i] = h;
+        lo[i] = l;
+    }
+}
+
+// acc += a b by three bf16 products of the parts, lo.hi, hi.lo, hi.hi in that order (split3: no lo.lo).  The order is part of
+// the bits.  (k_ana_m issues the same three interleaved across its accumulator tiles and does not call this.)
+__device__ __forceinline__ void mfma_split3(f32x16 &acc, const bf16x8 &ah, const bf16x8 &al, const bf16x8 &bh, const bf16x8 &bl)
+{
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
 // ---- tap packing of the synthesis-like GEMM's M dimension (cdl_fusedg.hip, cdl_strip.hip, cdl_stripg.hip) ---------

@@ -14,8 +14,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "cdl_wave_dev.h"
 
 constexpr int GLX = 64, GLY = 32;          // code-pixel tile of a workgroup
 constexpr int GNT = 512;                   // 8 waves
@@ -36,13 +35,12 @@ constexpr int eo_plane_dwords(int sw, int ph, int pw)
 {
     return pad_to(((GLY - 1) * sw + ph) * eo_row_dwords(sw, pw), (pw + 1) / 2);
 }
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-__device__ __forceinline__ unsigned int pack_bf16(float a, float b)
+__device__ __forceinline__ unsigned int pack_bf16(__bf16 a, __bf16 b)
 {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     bf16x2 v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
+    v[0] = a;
+    v[1] = b;
     return __builtin_bit_cast(unsigned int, v);
 }
 
@@ -159,12 +157,9 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
         for (int it = 0; it < ITG; ++it) {
             const int i = threadIdx.x + it * GNT;
             if (i < NPAIR) {
-                float hi[3], lo[3];
+                __bf16 hi[3], lo[3];
 #pragma unroll
-                for (int e = 0; e < 3; ++e) {
-                    hi[e] = (float)(__bf16)v[it][e];
-                    lo[e] = v[it][e] - hi[e];
-                }
+                for (int e = 0; e < 3; ++e) split_bf16(v[it][e], hi[e], lo[e]);
                 dstw[i] = pack_bf16(hi[0], hi[1]);
                 dstw[PD + i] = pack_bf16(hi[1], hi[2]);
                 dstw[2 * PD + i] = pack_bf16(lo[0], lo[1]);
@@ -232,13 +227,10 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
             for (int q = 0; q < CT; ++q) {
                 const int m = 32 * (CT * cg + q) + l32;
                 const bool ok = m < g.M && cy < Hz && cx0 < Wz;
+                float fv[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float v = ok ? fr[q][i >> 2][i & 3] : 0.0f;
-                    const __bf16 hh = (__bf16)v;
-                    bh[q][i] = hh;
-                    bl[q][i] = (__bf16)(v - (float)hh);
-                }
+                for (int i = 0; i < 8; ++i) fv[i] = ok ? fr[q][i >> 2][i & 3] : 0.0f;
+                split_bf16(fv, bh[q], bl[q]);
             }
             // the im2col rows of tile t+1 are read from LDS while the products of tile t issue (a wait for every
             // group's reads right before its MFMAs left the matrix pipe idle half of the k-loop)
@@ -248,12 +240,7 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
             for (int t = 0; t < NG * RT; ++t) {
                 if (t + 1 < NG * RT) gather((t + 1) / RT, (t + 1) % RT, zy, zx0, ah[(t + 1) & 1], al[(t + 1) & 1]);
 #pragma unroll
-                for (int q = 0; q < CT; ++q) {
-                    f32x16 &a = acc[t / RT][t % RT][q];
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t & 1], bh[q], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t & 1], bl[q], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t & 1], bh[q], a, 0, 0, 0);
-                }
+                for (int q = 0; q < CT; ++q) mfma_split3(acc[t / RT][t % RT][q], ah[t & 1], al[t & 1], bh[q], bl[q]);
             }
         };
         const int k0 = (kpart * npx + pp) * kpw, k1 = k0 + kpw;   // kpw is a power of two >= 8
@@ -301,11 +288,7 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
 #pragma unroll
                     for (int u = 0; u < SBW; ++u) {
                         const int i = i0 + u * GNT;
-                        if (i < XH * XW) {
-                            const __bf16 hh = (__bf16)v[u];
-                            xh[gi * XE + i] = hh;
-                            xl[gi * XE + i] = (__bf16)(v[u] - (float)hh);
-                        }
+                        if (i < XH * XW) split_bf16(v[u], xh[gi * XE + i], xl[gi * XE + i]);
                     }
                 }
             }
@@ -359,12 +342,7 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
                             fv[i] = ok ? v : 0.0f;
                         }
                     }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const __bf16 hh = (__bf16)fv[i];
-                        bh[q][i] = hh;
-                        bl[q][i] = (__bf16)(fv[i] - (float)hh);
-                    }
+                    split_bf16(fv, bh[q], bl[q]);
                 }
                 // ---- A: im2col rows of this lane's taps, gathered from LDS, and the products
 #pragma unroll
@@ -374,11 +352,7 @@ __global__ __launch_bounds__(GNT) void k_wgm(cdl_geom g, const float *__restrict
                         bf16x8 ah, al;
                         gather(gi, R, zy, zx0, ah, al);
 #pragma unroll
-                        for (int q = 0; q < CT; ++q) {
-                            acc[gi][R][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[q], acc[gi][R][q], 0, 0, 0);
-                            acc[gi][R][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[q], acc[gi][R][q], 0, 0, 0);
-                            acc[gi][R][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[q], acc[gi][R][q], 0, 0, 0);
-                        }
+                        for (int q = 0; q < CT; ++q) mfma_split3(acc[gi][R][q], ah, al, bh[q], bl[q]);
                     }
             }
         }
@@ -489,10 +463,7 @@ struct Plan {
 
 bool plan_for(const cdl_geom *g, Plan *p)
 {
-    if (g->sw != g->sh || (g->sw != 1 && g->sw != 2)) return false;
-    if (g->Pw != 3 && g->Pw != 5 && g->Pw != 7 && g->Pw != 9) return false;
-    if (g->Ph != g->Pw && !(g->Ph == 9 && g->Pw == 5)) return false;      // rectangular planes: the shipped 9 x 9 x 5 net
-    if (g->pw != g->Pw / 2 || g->ph != g->Ph / 2) return false;
+    if (!cdl_mfma_plane_ok(g)) return false;
     const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
     const int MT = (g->M + 31) / 32;
     // one channel tile per wave whenever the waves divide evenly: half the accumulators (room for the fat
@@ -539,14 +510,25 @@ bool plan_for(const cdl_geom *g, Plan *p)
     return true;
 }
 
+// One call's operands: ops[0 .. nops-1] (nops = 2: a paired launch, dA_k and dB_k of one iteration), the support gate of a
+// single operand, the layout of the fat operands and the partial banks.
+struct Job {
+    const cdl_wgrad_op *ops;
+    int nops;
+    const float *gate;
+    int rsc;
+    float *ws;
+};
+
 template <int PH, int PW, int SW, int NG, int CT>
-int launch_ct(const cdl_geom *g, const Plan &p, const float *F, const float *gate, const float *x, float *ws,
-              hipStream_t st, const float *F1, const float *x1, int rsc)
+int launch_ct(const cdl_geom *g, const Plan &p, const Job &j, hipStream_t st)
 {
     if (int rc = cdl_ensure_dynamic_lds((const void *)k_wgm<PH, PW, SW, NG, CT>, LDS_MAX)) return rc;
+    const bool pair = j.nops == 2;
+    const float *F = j.ops[0].F, *F1 = pair ? j.ops[1].F : nullptr;
     // group passes over workgroups while the launch would leave CUs idle (gspan a multiple of NG)
     const int G = g->C * g->Pd, passes = (G + NG - 1) / NG;
-    const size_t wgs = p.blocks * (F1 ? 2 : 1), cus = (size_t)cdl_cu_count();
+    const size_t wgs = p.blocks * j.nops, cus = (size_t)cdl_cu_count();
     int gz = 1;
     while (gz < passes && wgs * (gz + 1) <= cus) ++gz;
     const int gspan = ((passes + gz - 1) / gz) * NG;
@@ -555,36 +537,35 @@ int launch_ct(const cdl_geom *g, const Plan &p, const float *F, const float *gat
     // the first operand and for the second of a pair (-1: none).  The kernel decides for itself; this only says which of
     // its two load forms the pointers of this call select.
     const bool w4 = ((g->W / g->sw) & 3) == 0;
-    CDL_TRACE_NOTE("rs=%d gz=%d tpw=%d pair=%d rsc=%d tiles=%zu vec4=%d vec4b=%d", p.rs, gz, p.tpw, F1 ? 1 : 0, rsc, p.tiles,
-                   w4 && cdl_aligned16(F, gate) ? 1 : 0, F1 ? (w4 && cdl_aligned16(F1, gate) ? 1 : 0) : -1);
-    k_wgm<PH, PW, SW, NG, CT><<<dim3((unsigned)p.blocks, F1 ? 2 : 1, (unsigned)gz), GNT, p.lds, st>>>(
-        *g, F, gate, x, ws, p.tilesX, p.tilesY, p.nct, p.MP CDL_DBG_COMMA(cdl_opts().fused_debug & (1024 | 2048 | 4096)), (int)(p.tiles * p.rs),
-        p.tpw, F1, x1, rsc, gspan, p.rs);
+    CDL_TRACE_NOTE("rs=%d gz=%d tpw=%d pair=%d rsc=%d tiles=%zu vec4=%d vec4b=%d", p.rs, gz, p.tpw, pair ? 1 : 0, j.rsc, p.tiles,
+                   w4 && cdl_aligned16(F, j.gate) ? 1 : 0, pair ? (w4 && cdl_aligned16(F1, j.gate) ? 1 : 0) : -1);
+    k_wgm<PH, PW, SW, NG, CT><<<dim3((unsigned)p.blocks, (unsigned)j.nops, (unsigned)gz), GNT, p.lds, st>>>(
+        *g, F, j.gate, j.ops[0].x, j.ws, p.tilesX, p.tilesY, p.nct, p.MP CDL_DBG_COMMA(cdl_opts().fused_debug & (1024 | 2048 | 4096)),
+        (int)(p.tiles * p.rs), p.tpw, F1, pair ? j.ops[1].x : nullptr, j.rsc, gspan, p.rs);
     CDL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int PH, int PW, int SW, int NG>
-int launch_ng(const cdl_geom *g, const Plan &p, const float *F, const float *gate, const float *x, float *ws,
-              hipStream_t st, const float *F1, const float *x1, int rsc)
+int launch_ng(const cdl_geom *g, const Plan &p, const Job &j, hipStream_t st)
 {
-    return p.ct == 1 ? launch_ct<PH, PW, SW, NG, 1>(g, p, F, gate, x, ws, st, F1, x1, rsc)
-                     : launch_ct<PH, PW, SW, NG, 2>(g, p, F, gate, x, ws, st, F1, x1, rsc);
+    return p.ct == 1 ? launch_ct<PH, PW, SW, NG, 1>(g, p, j, st) : launch_ct<PH, PW, SW, NG, 2>(g, p, j, st);
 }
 
 template <int PH, int PW, int SW>
-int launch(const cdl_geom *g, const Plan &p, const float *F, const float *gate, const float *x, float alpha,
-           float *dw, float *ws, hipStream_t st, const float *F1, const float *x1, float alpha1, float *dw1, int rsc)
+int launch(const cdl_geom *g, const Plan &p, const Job &j, hipStream_t st)
 {
     constexpr int RT = (PH * PW + 31) / 32;
     int rc;
-    if (RT == 1 && p.ng == 5) rc = launch_ng<PH, PW, SW, (RT == 1 ? 5 : 1)>(g, p, F, gate, x, ws, st, F1, x1, rsc);
-    else if (RT <= 2 && p.ng == 3) rc = launch_ng<PH, PW, SW, (RT <= 2 ? 3 : 1)>(g, p, F, gate, x, ws, st, F1, x1, rsc);
-    else rc = launch_ng<PH, PW, SW, 1>(g, p, F, gate, x, ws, st, F1, x1, rsc);
+    if (RT == 1 && p.ng == 5) rc = launch_ng<PH, PW, SW, (RT == 1 ? 5 : 1)>(g, p, j, st);
+    else if (RT <= 2 && p.ng == 3) rc = launch_ng<PH, PW, SW, (RT <= 2 ? 3 : 1)>(g, p, j, st);
+    else rc = launch_ng<PH, PW, SW, 1>(g, p, j, st);
     if (rc) return rc;
     const int G = g->C * g->Pd, T = g->Ph * g->Pw;
-    k_wgm_fold<<<dim3(G * T * ((g->M + 15) / 16), F1 ? 2 : 1), 256, 0, st>>>(ws, dw, alpha, (int)p.blocks, G, g->M, T,
-                                                                             p.TP, p.MP, dw1, alpha1);
+    const bool pair = j.nops == 2;
+    k_wgm_fold<<<dim3(G * T * ((g->M + 15) / 16), j.nops), 256, 0, st>>>(j.ws, j.ops[0].dw, j.ops[0].alpha, (int)p.blocks, G, g->M, T,
+                                                                         p.TP, p.MP, pair ? j.ops[1].dw : nullptr,
+                                                                         pair ? j.ops[1].alpha : 0.0f);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -597,61 +578,28 @@ size_t cdl_mfma_wgrad_ws_floats(const cdl_geom *g)
     return plan_for(g, &p) ? p.part_floats : 0;
 }
 
-// CDL_EUNSUPPORTED: the caller falls back to the VALU kernels
-static int wgrad_entry(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
-                       const float *F1, const float *x1, float alpha1, float *dw1, float *ws, size_t ws_floats,
-                       void *stream, int rsc = 0)
-{
-    Plan p;
-    if (!plan_for(g, &p) || !ws) return CDL_EUNSUPPORTED;
-    if (rsc && gate) return CDL_EUNSUPPORTED;
-    const size_t jobs = F1 ? 2 : 1;
-    const size_t cus = (size_t)cdl_cu_count();              // one workgroup per CU at a time (registers): tiles per
-    const size_t items = p.tiles * p.rs;                    // (tile, row part) work items
-    p.tpw = (int)((jobs * items + cus - 1) / cus);          // workgroup = the number of rounds an item-per-workgroup grid takes
-    p.blocks = (items + p.tpw - 1) / p.tpw;
-    if (ws_floats < jobs * p.blocks * ((size_t)g->C * g->Pd * p.TP * p.MP)) return CDL_EUNSUPPORTED;
-#define CDL_M(PH_, P_, S_)                                   \
-    if (g->Ph == PH_ && g->Pw == P_ && g->sw == S_)          \
-        return launch<PH_, P_, S_>(g, p, F, gate, x, alpha, dw, ws, S(stream), F1, x1, alpha1, dw1, rsc)
-    CDL_M(3, 3, 1); CDL_M(5, 5, 1); CDL_M(7, 7, 1); CDL_M(9, 9, 1);
-    CDL_M(3, 3, 2); CDL_M(5, 5, 2); CDL_M(7, 7, 2); CDL_M(9, 9, 2);
-    CDL_M(9, 5, 1); CDL_M(9, 5, 2);
-#undef CDL_M
-    return CDL_EUNSUPPORTED;
-}
-
-int cdl_mfma_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
-                   float *ws, size_t ws_floats, void *stream)
-{
-    return wgrad_entry(g, F, gate, x, alpha, dw, nullptr, nullptr, 0.0f, nullptr, ws, ws_floats, stream);
-}
-
-// Two ungated filter gradients of the same geometry (dA_k = a0 F0 (x) x0, dB_k = a1 F1 (x) x1) in ONE launch + ONE fold
-int cdl_mfma_wgrad_pair(const cdl_geom *g, const float *F0, const float *x0, float alpha0, float *dw0, const float *F1,
-                        const float *x1, float alpha1, float *dw1, float *ws, size_t ws_floats, void *stream)
-{
-    return wgrad_entry(g, F0, nullptr, x0, alpha0, dw0, F1, x1, alpha1, dw1, ws, ws_floats, stream);
-}
-
-// The same with the fat operands in the strip kernel's row-strip channel-major layout (cdl_strip.hip; rsc != 0), for the
-// reverse sweep of the strip shapes.  cdl_mfma_wgrad_takes: this kernel (and not a VALU fallback, which reads the
-// reference layout only) is what cdl_wgrad would run for the geometry.
 bool cdl_mfma_wgrad_takes(const cdl_geom *g)
 {
     Plan p;
     return cdl_opts().mfma_wgrad && plan_for(g, &p);
 }
 
-int cdl_mfma_wgrad_lay(const cdl_geom *g, const float *F, const float *x, float alpha, float *dw, float *ws,
-                       size_t ws_floats, int rsc, void *stream)
+// CDL_EUNSUPPORTED: the caller falls back to the VALU kernels (a gate with the rsc layout or with a pair, a short workspace)
+int cdl_mfma_wgrad(const cdl_geom *g, const cdl_wgrad_op *ops, int nops, const float *gate, int rsc, float *ws,
+                   size_t ws_floats, void *stream)
 {
-    return wgrad_entry(g, F, nullptr, x, alpha, dw, nullptr, nullptr, 0.0f, nullptr, ws, ws_floats, stream, rsc);
-}
-
-int cdl_mfma_wgrad_pair_lay(const cdl_geom *g, const float *F0, const float *x0, float alpha0, float *dw0,
-                            const float *F1, const float *x1, float alpha1, float *dw1, float *ws, size_t ws_floats,
-                            int rsc, void *stream)
-{
-    return wgrad_entry(g, F0, nullptr, x0, alpha0, dw0, F1, x1, alpha1, dw1, ws, ws_floats, stream, rsc);
+    Plan p;
+    if (!ops || (nops != 1 && nops != 2)) return CDL_EINVAL;
+    if (!plan_for(g, &p) || !ws) return CDL_EUNSUPPORTED;
+    if (gate && (rsc || nops == 2)) return CDL_EUNSUPPORTED;
+    const size_t jobs = (size_t)nops;
+    const size_t cus = (size_t)cdl_cu_count();              // one workgroup per CU at a time (registers): tiles per
+    const size_t items = p.tiles * p.rs;                    // (tile, row part) work items
+    p.tpw = (int)((jobs * items + cus - 1) / cus);          // workgroup = the number of rounds an item-per-workgroup grid takes
+    p.blocks = (items + p.tpw - 1) / p.tpw;
+    if (ws_floats < jobs * p.blocks * ((size_t)g->C * g->Pd * p.TP * p.MP)) return CDL_EUNSUPPORTED;
+    const Job j{ops, nops, gate, rsc, ws};
+    return cdl_mfma_dispatch_plane(g, [&](auto ph, auto pw, auto sw) {
+        return launch<decltype(ph)::value, decltype(pw)::value, decltype(sw)::value>(g, p, j, S(stream));
+    });
 }

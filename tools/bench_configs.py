@@ -6,7 +6,8 @@ which measures the headline configs[1]).  One JSON line per configuration:
 
 For each config: forward-only and forward+backward (loss.backward(), no optimiser) Mpix/s through the
 product modules, the CPU oracle on a bounded sample of the same workload (same box, host threads), the
-max relative error of xhat against the oracle on that sample and both PSNRs.
+max relative error of xhat against the oracle on that sample and both PSNRs.  --no-cpu-oracle: the device timings only (A/B
+runs of two builds of the library).
 """
 import json
 import os
@@ -86,6 +87,9 @@ def run(name):
 
     reps = 3 if pix > 2e6 else 10
     f_ms, fb_ms = ev(fwd, reps), ev(fwdbwd, reps)
+    if NO_CPU:
+        print(json.dumps({"config": name, "input": list(shape), "fwd_ms": round(f_ms, 3), "fwdbwd_ms": round(fb_ms, 3)}), flush=True)
+        return
     xhat = fwd()[0].cpu()
 
     # CPU oracle on a bounded sample of the same workload
@@ -149,6 +153,10 @@ def run_csr(name):
         (mse(clean[0], xp) + mse(clean[1], xc) + mse(clean[2], xa) + mse(clean[1], xc2) + mse(clean[0], xp2)).backward()
 
     trn_ms = ev(chain, 3)
+    if NO_CPU:
+        print(json.dumps({"config": name, "clip": [T, H, W], "infer_ms_per_clip": round(inf_ms, 2), "train_chain_ms": round(trn_ms, 2)}),
+              flush=True)
+        return
 
     torch.set_num_threads(host_cores())
     okw = dict(K=30, P=9, s=2, sigma=25.0, adaptive=True, variant="f2")
@@ -174,7 +182,9 @@ def run_csr(name):
         "psnr_noisy": round(O.psnr(vid[:, :, 1], frames[1]), 3)}), flush=True)
 
 
+NO_CPU = "--no-cpu-oracle" in sys.argv[1:]
+
 if __name__ == "__main__":
-    for cfg in (sys.argv[1:] or list(CONFIGS) + ["csr-f2"]):
+    for cfg in ([a for a in sys.argv[1:] if a != "--no-cpu-oracle"] or list(CONFIGS) + ["csr-f2"]):
         print(f"[{cfg}] ...", file=sys.stderr, flush=True)
         run_csr(cfg) if cfg == "csr-f2" else run(cfg)
