@@ -297,28 +297,22 @@ static inline int cdl_mfma_dispatch_plane(const cdl_geom *g, F &&fn)
     return CDL_EUNSUPPORTED;
 }
 
-// register-tiled variants (cdl_generic_tiled.hip): CDL_EUNSUPPORTED means "use the untiled kernel"
-int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
-                       const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
-int cdl_tiled_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                        const float *mask, const float *sub, float *out, float *ws, size_t ws_floats,
-                        void *stream);
-size_t cdl_tiled_synthesis_ws_floats(const cdl_geom *g);
-// matrix-core synthesis (cdl_synth_mfma.hip): CDL_EUNSUPPORTED / 0 floats when the shape has no such kernel
-int cdl_mfma_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                       const float *mask, const float *sub, float *out, float *ws, size_t ws_floats, void *stream);
-size_t cdl_mfma_synthesis_ws_floats(const cdl_geom *g);
-// matrix-core analysis (cdl_analysis_mfma.hip), same convention
-// cdl_dense_mfma.hip: many-channel unit-stride convolution (C >= 16 on both sides), analysis or synthesis role
+// ---- the four tiers behind cdl_analysis*, cdl_synthesis and cdl_wgrad*, in the order cdl_operators.hip walks them -----
+// One face per tier and operator: a launcher that returns CDL_EUNSUPPORTED when it does not serve the call, and
+// ..._ws_floats(g), the floats that launcher may use (0: none, or no plan; no such function: no workspace).  ..._takes(g):
+// the tier's plan serves the geometry -- its launcher can still refuse a short or misaligned workspace.
+// 1. dense matrix-core tier (cdl_dense_mfma.hip): many-channel unit-stride convolution (C >= 16 on both sides), analysis
+// (transpose = 0) or synthesis role
+bool cdl_dense_takes(const cdl_geom *g, int transpose);
 size_t cdl_dense_ws_floats(const cdl_geom *g, int transpose);
-size_t cdl_dense_wgrad_ws_floats(const cdl_geom *g);
-int cdl_dense_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
-                    float *ws, size_t ws_floats, void *stream);
 int cdl_dense_conv(const cdl_geom *g, int transpose, const float *x, const float *in_gate, const float *w,
                    float alpha, const float *add, const float *add_gate, const float *mask, const float *sub,
                    const float *tau, int relu, const float *out_gate, float *out, float *ws, size_t ws_floats,
                    void *stream);
+bool cdl_dense_wgrad_takes(const cdl_geom *g);
+size_t cdl_dense_wgrad_ws_floats(const cdl_geom *g);
+int cdl_dense_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,
+                    float *ws, size_t ws_floats, void *stream);
 // the VGG16 layers of the perceptual loss (cdl_vgg.hip) on the dense tier: forms of cdl_dense_vgg
 enum { CDL_VGG_PLAIN = 0, CDL_VGG_BIAS = 1, CDL_VGG_POOL = 2, CDL_VGG_DIFF = 3, CDL_VGG_UNPOOL = 4 };
 size_t cdl_dense_vgg_workgroups(const cdl_geom *g, int transpose);
@@ -326,23 +320,26 @@ int cdl_dense_vgg(const cdl_geom *g, int transpose, int form, const float *x, co
                   const float *out_gate, float *out, unsigned char *pool_arg, const unsigned char *unpool_arg,
                   const float *fy, float *seed_x, float *seed_y, double *partial, float *ws, size_t ws_floats,
                   void *stream);
+// the dense switch as cdl_residual.hip reads it (cdl_operators.hip): CDL_MFMA_DENSE and CDL_NO_TILED, NOT the exact-fp32
+// request (DESIGN.md section 37 has what follows from that)
+bool cdl_dense_switch_on();
+// 2. sparse matrix-core tier (cdl_analysis_mfma.hip, cdl_synth_mfma.hip, cdl_wgrad_mfma.hip)
 int cdl_mfma_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
                       size_t ws_floats, void *stream, const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
 size_t cdl_mfma_analysis_ws_floats(const cdl_geom *g);
-// per-sample threshold gradients from a sweep's partial sums (cdl_datagrad.hip):
-// dtau_n[n,m] = sum_{j<R} partial[n sN + m sM + j sR], j in order
-int cdl_dtau_per_sample(const float *partial, int N, int M, int R, size_t sN, size_t sM, size_t sR, float *dtau_n,
-                        void *stream);
 size_t cdl_mfma_analysis_rev_ws_floats(const cdl_geom *g);
 int cdl_mfma_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                           const float *zsup, const float *c, float *dt0, float *dt1, float *out, float *ws,
                           size_t ws_floats, void *stream, float *dtau_n = nullptr, const float *cmap = nullptr);
-// matrix-core filter gradients (cdl_wgrad_mfma.hip), same convention: dw = alpha * F (x) x for one operand set, or for two
-// ungated ones of the same geometry (dA_k and dB_k of one iteration) in ONE launch + ONE fold.  gate: support gate of a
-// single F (nullable).  rsc != 0: the fat operands F are in the strip kernel's row-strip channel-major layout (cdl_strip.hip,
-// CDL_LAY_RSC; ungated).  cdl_mfma_wgrad_takes: this kernel (and not a VALU fallback, which reads the reference layout
-// only) is what cdl_wgrad would run for the geometry.
+int cdl_mfma_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
+                       const float *mask, const float *sub, float *out, float *ws, size_t ws_floats, void *stream);
+size_t cdl_mfma_synthesis_ws_floats(const cdl_geom *g);
+// dw = alpha * F (x) x for one operand set, or for two ungated ones of the same geometry (dA_k and dB_k of one iteration) in
+// ONE launch + ONE fold.  gate: support gate of a single F (nullable).  rsc != 0: the fat operands F are in the strip
+// kernel's row-strip channel-major layout (cdl_strip.hip, CDL_LAY_RSC; ungated).  cdl_mfma_wgrad_takes: this kernel (and not
+// a VALU fallback, which reads the reference layout only) is what the fused generic sweeps count on; it reads CDL_MFMA_WGRAD
+// and its own plan, not CDL_NO_TILED, the exact-fp32 request or the dense tier ahead of it.
 struct cdl_wgrad_op {
     const float *F, *x;
     float alpha;
@@ -352,5 +349,25 @@ int cdl_mfma_wgrad(const cdl_geom *g, const cdl_wgrad_op *ops, int nops, const f
                    size_t ws_floats, void *stream);
 size_t cdl_mfma_wgrad_ws_floats(const cdl_geom *g);
 bool cdl_mfma_wgrad_takes(const cdl_geom *g);
+// 3. register-tiled VALU tier (cdl_generic_tiled.hip)
+int cdl_tiled_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
+                       const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
+int cdl_tiled_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
+                        const float *mask, const float *sub, float *out, float *ws, size_t ws_floats,
+                        void *stream);
+size_t cdl_tiled_synthesis_ws_floats(const cdl_geom *g);
 int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha,
                     float *dw, float *workspace, size_t workspace_floats, void *stream);
+size_t cdl_tiled_wgrad_ws_floats(const cdl_geom *g);
+// 4. plain VALU tier (cdl_generic.hip): no workspace
+int cdl_plain_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
+                       const float *gate, const float *tau, float *out, const cdl_prox_args &px, void *stream,
+                       const cdl_map_args &mp);
+int cdl_plain_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
+                        const float *mask, const float *sub, float *out, void *stream);
+int cdl_plain_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha, float *dw, void *stream);
+// per-sample threshold gradients from a sweep's partial sums (cdl_datagrad.hip):
+// dtau_n[n,m] = sum_{j<R} partial[n sN + m sM + j sR], j in order
+int cdl_dtau_per_sample(const float *partial, int N, int M, int R, size_t sN, size_t sM, size_t sR, float *dtau_n,
+                        void *stream);

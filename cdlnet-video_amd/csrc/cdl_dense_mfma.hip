@@ -28,11 +28,9 @@
 //     DM_UNPOOL  staging reads a pooled gradient (H/2, W/2) and places it at its argmax (the backward's unpool)
 #include "cdl_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
+
+#include "cdl_wave_dev.h"                                  // bf16x8, f32x16, u32x4, split_bf16
 
 constexpr int DTX = 32, DTY = 16, DNT = 512, DKC = 16;
 
@@ -339,13 +337,15 @@ __global__ __launch_bounds__(DNT, 4) void k_dense_vgg(DenseArgs a, DenseExt ex) 
 }
 
 struct DensePlan {
+    int in, out;                                           // channels on the input and on the output side
     int tilesX, tilesY, NCC, MTT, MT, ngy;
     size_t frag_uint4, lds, tiles;
 };
 
-// in: channels on the input side, out: on the output side (analysis role: C -> M; synthesis role: M -> C)
-bool dense_plan(const cdl_geom *g, int in, int out, DensePlan *p)
+// transpose = 0, the analysis role: C -> M channels; transpose = 1, the synthesis role: M -> C
+bool dense_plan(const cdl_geom *g, int transpose, DensePlan *p)
 {
+    const int in = p->in = transpose ? g->M : g->C, out = p->out = transpose ? g->C : g->M;
     if (g->sd != 1 || g->sh != 1 || g->sw != 1) return false;
     if (in < 16 || out < 16) return false;                 // few channels: the sparse-dictionary kernels
     if (g->Ph > 5 || g->Pw > 5 || !(g->Pd & 1) || !(g->Ph & 1) || !(g->Pw & 1)) return false;
@@ -368,26 +368,45 @@ bool dense_plan(const cdl_geom *g, int in, int out, DensePlan *p)
     return p->lds <= 160 * 1024;
 }
 
+// What cdl_dense_conv and cdl_dense_vgg do ahead of their launches: the plan, the workspace test (size and 16-byte
+// alignment: the fragments are uint4) and the kernel's arguments with alpha = 1 and an empty epilogue, which the caller
+// fills.  false: not this tier's call.  The k_dense_prep launch stays with each caller, where the launch trace has it.
+bool dense_setup(const cdl_geom *g, int transpose, const float *x, float *out, float *ws, size_t ws_floats, DensePlan *p,
+                 DenseArgs *a)
+{
+    if (!dense_plan(g, transpose, p)) return false;
+    if (!ws || ws_floats < p->frag_uint4 * 4 || (reinterpret_cast<size_t>(ws) & 15)) return false;
+    *a = DenseArgs{x, nullptr, reinterpret_cast<const uint4 *>(ws), 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                   out, g->N, p->in, p->out, g->D, g->H, g->W, g->Pd, g->Ph, g->Pw, p->tilesX, p->tilesY, p->NCC, p->MTT
+                   CDL_DBG_COMMA(0)};
+    return true;
+}
+
+int dense_prep_threads(const DenseArgs &a) { return a.NCC * a.Pd * a.Ph * a.Pw * a.MTT * 64; }   // of the k_dense_prep launch
+
 template <int MT>
 int launch_dense(const DensePlan &p, const DenseArgs &a, hipStream_t st)
 {
-    if (p.lds > 64 * 1024) {
-        const int rc = cdl_ensure_dynamic_lds((const void *)k_dense<MT>, 160 * 1024);      // per device
-        if (rc) return rc;
-    }
+    if (p.lds > 64 * 1024) CDL_TRY(cdl_ensure_dynamic_lds((const void *)k_dense<MT>, 160 * 1024));      // per device
     k_dense<MT><<<dim3((unsigned)p.tiles, (unsigned)p.ngy), DNT, p.lds, st>>>(a);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int MODE>
+int launch_dense_vgg(const DensePlan &p, const DenseArgs &a, const DenseExt &ex, hipStream_t st)
+{
+    if (p.lds > 64 * 1024) CDL_TRY(cdl_ensure_dynamic_lds((const void *)k_dense_vgg<MODE>, 160 * 1024));
+    k_dense_vgg<MODE><<<dim3((unsigned)p.tiles, (unsigned)p.ngy), DNT, p.lds, st>>>(a, ex);
     CDL_LAUNCH_CHECK();
     return 0;
 }
 
 }  // namespace
 
-size_t cdl_dense_ws_floats(const cdl_geom *g, int transpose)
-{
-    DensePlan p;
-    const int in = transpose ? g->M : g->C, out = transpose ? g->C : g->M;
-    return dense_plan(g, in, out, &p) ? p.frag_uint4 * 4 : 0;
-}
+// cdl_dense_conv serves this geometry and role, given its workspace (it can still refuse a short or misaligned one)
+bool cdl_dense_takes(const cdl_geom *g, int transpose) { DensePlan p; return dense_plan(g, transpose, &p); }
+size_t cdl_dense_ws_floats(const cdl_geom *g, int transpose) { DensePlan p; return dense_plan(g, transpose, &p) ? p.frag_uint4 * 4 : 0; }
 
 // transpose = 0: x (N,C,..) -> out (N,M,..) with filters (M,C,P) (the analysis role)
 // transpose = 1: x (N,M,..) -> out (N,C,..), the conv-transpose with the same filters (the synthesis role)
@@ -397,44 +416,19 @@ int cdl_dense_conv(const cdl_geom *g, int transpose, const float *x, const float
                    const float *tau, int relu, const float *out_gate, float *out, float *ws, size_t ws_floats,
                    void *stream)
 {
-    DensePlan p;
-    const int in = transpose ? g->M : g->C, outc = transpose ? g->C : g->M;
-    if (!dense_plan(g, in, outc, &p)) return CDL_EUNSUPPORTED;
-    if (!ws || ws_floats < p.frag_uint4 * 4 || (reinterpret_cast<size_t>(ws) & 15)) return CDL_EUNSUPPORTED;
-    uint4 *frags = reinterpret_cast<uint4 *>(ws);
-    const int nprep = p.NCC * g->Pd * g->Ph * g->Pw * p.MTT * 64;
-    k_dense_prep<<<(nprep + 255) / 256, 256, 0, S(stream)>>>(w, frags, outc, in, g->Pd, g->Ph, g->Pw, p.MTT, p.NCC,
-                                                              transpose);
+    DensePlan p; DenseArgs a;
+    if (!dense_setup(g, transpose, x, out, ws, ws_floats, &p, &a)) return CDL_EUNSUPPORTED;
+    k_dense_prep<<<(dense_prep_threads(a) + 255) / 256, 256, 0, S(stream)>>>(w, reinterpret_cast<uint4 *>(ws), a.O, a.I, a.Pd,
+                                                                             a.Ph, a.Pw, a.MTT, a.NCC, transpose);
     CDL_LAUNCH_CHECK();
-    const DenseArgs a{x, in_gate, frags, alpha, add, add_gate, mask, sub, tau, out_gate, relu, out,
-                      g->N, in, outc, g->D, g->H, g->W, g->Pd, g->Ph, g->Pw, p.tilesX, p.tilesY, p.NCC, p.MTT
-                      CDL_DBG_COMMA(cdl_opts().dense_debug)};
+    a.in_gate = in_gate, a.alpha = alpha, a.add = add, a.add_gate = add_gate, a.mask = mask, a.sub = sub, a.tau = tau;
+    a.out_gate = out_gate, a.relu = relu;
+    CDL_DBG_FIELD(a.dbg = cdl_opts().dense_debug;)
     return p.MT == 2 ? launch_dense<2>(p, a, S(stream)) : launch_dense<1>(p, a, S(stream));
 }
 
-namespace {
-
-template <int MODE>
-int launch_dense_vgg(const DensePlan &p, const DenseArgs &a, const DenseExt &ex, hipStream_t st)
-{
-    if (p.lds > 64 * 1024) {
-        const int rc = cdl_ensure_dynamic_lds((const void *)k_dense_vgg<MODE>, 160 * 1024);
-        if (rc) return rc;
-    }
-    k_dense_vgg<MODE><<<dim3((unsigned)p.tiles, (unsigned)p.ngy), DNT, p.lds, st>>>(a, ex);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-}  // namespace
-
 // Workgroups of one cdl_dense_vgg launch (the partial sums of CDL_VGG_DIFF); 0: not a dense-tier geometry
-size_t cdl_dense_vgg_workgroups(const cdl_geom *g, int transpose)
-{
-    DensePlan p;
-    const int in = transpose ? g->M : g->C, out = transpose ? g->C : g->M;
-    return dense_plan(g, in, out, &p) ? p.tiles * p.ngy : 0;
-}
+size_t cdl_dense_vgg_workgroups(const cdl_geom *g, int transpose) { DensePlan p; return dense_plan(g, transpose, &p) ? p.tiles * p.ngy : 0; }
 
 // The VGG16 layers on the dense tier (cdl_vgg.hip): one 3x3 convolution with ReLU, in one of the forms
 //     CDL_VGG_PLAIN    cdl_dense_conv's synthesis role with out_gate (the backward's transposed layers)
@@ -448,19 +442,12 @@ int cdl_dense_vgg(const cdl_geom *g, int transpose, int form, const float *x, co
                   const float *fy, float *seed_x, float *seed_y, double *partial, float *ws, size_t ws_floats,
                   void *stream)
 {
-    DensePlan p;
-    const int in = transpose ? g->M : g->C, outc = transpose ? g->C : g->M;
-    if (!dense_plan(g, in, outc, &p) || p.MT != 2) return CDL_EUNSUPPORTED;
-    if (!ws || ws_floats < p.frag_uint4 * 4 || (reinterpret_cast<size_t>(ws) & 15)) return CDL_EUNSUPPORTED;
-    uint4 *frags = reinterpret_cast<uint4 *>(ws);
-    const int nprep = p.NCC * g->Pd * g->Ph * g->Pw * p.MTT * 64;
-    k_dense_prep<<<(nprep + 255) / 256, 256, 0, S(stream)>>>(w, frags, outc, in, g->Pd, g->Ph, g->Pw, p.MTT, p.NCC,
-                                                              transpose);
+    DensePlan p; DenseArgs a;
+    if (!dense_setup(g, transpose, x, out, ws, ws_floats, &p, &a) || p.MT != 2) return CDL_EUNSUPPORTED;
+    k_dense_prep<<<(dense_prep_threads(a) + 255) / 256, 256, 0, S(stream)>>>(w, reinterpret_cast<uint4 *>(ws), a.O, a.I, a.Pd,
+                                                                             a.Ph, a.Pw, a.MTT, a.NCC, transpose);
     CDL_LAUNCH_CHECK();
-    const int relu = form == CDL_VGG_BIAS;
-    const DenseArgs a{x, nullptr, frags, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, out_gate, relu, out,
-                      g->N, in, outc, g->D, g->H, g->W, g->Pd, g->Ph, g->Pw, p.tilesX, p.tilesY, p.NCC, p.MTT
-                      CDL_DBG_COMMA(0)};
+    a.out_gate = out_gate, a.relu = form == CDL_VGG_BIAS;
     const DenseExt ex{bias, pool_arg, unpool_arg, fy, seed_x, seed_y, partial};
     switch (form) {
     case CDL_VGG_PLAIN: return launch_dense<2>(p, a, S(stream));
@@ -503,23 +490,10 @@ __device__ __forceinline__ void split8(const float (&v)[8], uint4 &hi, uint4 &lo
     lo = __builtin_bit_cast(uint4, b);
 }
 
-// the 8 elements starting one element before (kj == 0) / after (kj == 2) the aligned chunk c at element e0
-__device__ __forceinline__ uint4 shifted(const __bf16 *plane, int e0, uint4 c, int kj)
-{
-    if (kj == 1) return c;
-    if (kj == 0) {
-        const unsigned p = *reinterpret_cast<const unsigned *>(plane + e0 - 2);
-        return uint4{__builtin_amdgcn_alignbyte(c.x, p, 2), __builtin_amdgcn_alignbyte(c.y, c.x, 2),
-                     __builtin_amdgcn_alignbyte(c.z, c.y, 2), __builtin_amdgcn_alignbyte(c.w, c.z, 2)};
-    }
-    const unsigned nx = *reinterpret_cast<const unsigned *>(plane + e0 + 8);
-    return uint4{__builtin_amdgcn_alignbyte(c.y, c.x, 2), __builtin_amdgcn_alignbyte(c.z, c.y, 2),
-                 __builtin_amdgcn_alignbyte(c.w, c.z, 2), __builtin_amdgcn_alignbyte(nx, c.w, 2)};
-}
-
 // the 8 k-steps of one tile for the taps TAP0 .. TAP0+NTAP-1 (compile-time: the operand reads of a k-step -- 2 + 2*NTAP
 // 16-byte chunks and the halo dwords -- are issued together, no branch between them; with run-time taps every
 // shifted operand was a branch and an exposed LDS round trip, 4x the matrix time)
+// shifted_c: the 8 elements starting one element before (KJ == 0) / after (KJ == 2) the aligned chunk c at element e0
 template <int KJ>
 __device__ __forceinline__ uint4 shifted_c(const __bf16 *plane, int e0, uint4 c)
 {
@@ -803,11 +777,9 @@ bool wgrad_plan(const cdl_geom *g, WgradPlan *p)
 
 }  // namespace
 
-size_t cdl_dense_wgrad_ws_floats(const cdl_geom *g)
-{
-    WgradPlan p;
-    return wgrad_plan(g, &p) ? p.ws : 0;
-}
+// cdl_dense_wgrad serves this geometry, given its workspace
+bool cdl_dense_wgrad_takes(const cdl_geom *g) { WgradPlan p; return wgrad_plan(g, &p); }
+size_t cdl_dense_wgrad_ws_floats(const cdl_geom *g) { WgradPlan p; return wgrad_plan(g, &p) ? p.ws : 0; }
 
 // dw (M,C,Pd,3,3) = alpha * correlation of F (N,M,..) [gate != 0] with x (N,C,..); CDL_EUNSUPPORTED: fall back
 int cdl_dense_wgrad(const cdl_geom *g, const float *F, const float *gate, const float *x, float alpha, float *dw,

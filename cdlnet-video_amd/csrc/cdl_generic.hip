@@ -2,7 +2,6 @@
 // LDS-tiled direct correlation on the vector ALUs: the always-available path and the
 // on-device yardstick for the MFMA kernels in cdl_fused2d.hip.  One code path serves
 // CDLNet (D = 1), the Bayer-masked JDD variant (C = 3, mask), CDLNetVideo and GDLNet.
-#include <cstdlib>
 #include "cdl_common.h"
 
 namespace {
@@ -624,6 +623,55 @@ __global__ void k_gabor_bwd_batch(GaborBatch b, int order, int MC, int P)
 
 }  // namespace
 
+// ---- the plain tier: the last rung of the operators' ladder (cdl_operators.hip, which has checked the arguments).  No
+// workspace; CDL_EUNSUPPORTED where a tile's patch exceeds the LDS or the filter row the kernel's registers.
+int cdl_plain_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin, const float *gate,
+                       const float *tau, float *out, const cdl_prox_args &px, void *stream, const cdl_map_args &mp)
+{
+    const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
+    const int tilesX = (Wz + TILE - 1) / TILE, tilesY = (Hz + TILE - 1) / TILE;
+    const int PH = (TILE - 1) * g->sh + g->Ph, PW = (TILE - 1) * g->sw + g->Pw;
+    size_t lds = (size_t)g->C * g->Pd * PH * PW * sizeof(float);
+    if (lds > 160 * 1024) return CDL_EUNSUPPORTED;
+    if (lds > 64 * 1024)
+        CDL_TRY(cdl_ensure_dynamic_lds(mp.cmap ? (const void *)k_analysis<true> : (const void *)k_analysis<false>, (int)lds));
+    dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N);
+    CDL_TRACE_NOTE("k_analysis<%s>", mp.cmap ? "true" : "false");
+    if (mp.cmap)
+        k_analysis<true><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
+    else
+        k_analysis<false><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+int cdl_plain_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
+                        const float *mask, const float *sub, float *out, void *stream)
+{
+    const int tilesX = (g->W + TILE - 1) / TILE, tilesY = (g->H + TILE - 1) / TILE;
+    // upper bound on the code patch a 16x16 output tile (one d) can touch, per axis
+    const int PZD = (g->Pd - 1) / g->sd + 2;
+    const int PZH = (TILE - 1 + g->Ph - 1) / g->sh + 2;
+    const int PZW = (TILE - 1 + g->Pw - 1) / g->sw + 2;
+    size_t lds = (size_t)MCHUNK * PZD * PZH * PZW * sizeof(float);
+    if (lds > 160 * 1024) return CDL_EUNSUPPORTED;
+    if (lds > 64 * 1024) CDL_TRY(cdl_ensure_dynamic_lds((const void *)k_synthesis, (int)lds));
+    dim3 grid((unsigned)(tilesX * tilesY * g->D), (unsigned)g->N);
+    k_synthesis<<<grid, 256, lds, S(stream)>>>(*g, z, gate, w, alpha, mask, sub, out, tilesX, tilesY,
+                                                PZD, PZH, PZW);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
+int cdl_plain_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha, float *dw, void *stream)
+{
+    if (g->Pw > PWMAX) return CDL_EUNSUPPORTED;
+    dim3 grid((unsigned)g->M, (unsigned)(g->C * g->Pd * g->Ph));
+    k_wgrad<<<grid, 256, 0, S(stream)>>>(*g, z, gate, x, alpha, dw);
+    CDL_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 const char *cdl_version(void) { return "cdlnet_hip 0.1 (gfx950)"; }
@@ -721,257 +769,6 @@ int cdl_shrink_b_bwd(const float *gup, const float *x, const float *tau, const c
     if (!gup || !x || !tau || !gx || N <= 0 || M <= 0 || per_m == 0 || !cdl_bcast_ok(s_tau, M, per_m))
         return CDL_EINVAL;
     return launch_shrink(x, tau, gx, (size_t)N * M, per_m, M, *s_tau, gup, dtau_el, stream);
-}
-
-static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                         const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                         size_t ws_floats, void *stream, const cdl_map_args &mp = cdl_map_args{nullptr, nullptr});
-
-// the matrix-core analysis (cdl_analysis_mfma.hip) is the default wherever it has a kernel and the launch is large
-// enough; CDL_MFMA_ANALYSIS=0 selects the VALU kernels (read per call)
-static bool mfma_analysis_enabled(const cdl_geom *g)
-{
-    return cdl_opts().mfma_analysis != 0 && !cdl_exact_fp32();
-}
-
-// the dense many-channel tier (cdl_dense_mfma.hip; C >= 16 on both sides, unit stride); CDL_MFMA_DENSE=0 disables
-static bool mfma_dense_enabled()
-{
-    return cdl_opts().mfma_dense != 0 && !cdl_exact_fp32();
-}
-
-size_t cdl_analysis_workspace_floats(const cdl_geom *g)
-{
-    if (!cdl_geom_ok(g) || cdl_opts().no_tiled) return 0;
-    const size_t a = mfma_analysis_enabled(g) ? cdl_mfma_analysis_ws_floats(g) : 0;
-    const size_t b = mfma_dense_enabled() ? cdl_dense_ws_floats(g, 0) : 0;
-    return a > b ? a : b;
-}
-
-int cdl_analysis(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                 const float *gate, const float *tau, float *out, float *workspace, size_t workspace_floats,
-                 const float *cmap, const float *tslope, void *stream)
-{
-    return analysis_impl(g, x, w, alpha, zin, gate, tau, out, cdl_prox_args{}, workspace, workspace_floats, stream,
-                         cdl_map_args{cmap, tslope});
-}
-
-/* Reverse-sweep step: out = [zsup != 0] (zin + alpha A x)  and  (dt0, dt1) = cdl_tau_grad(out, zsup, c) -- the gradient
- * with respect to z_k, gated by z_k's support, together with the threshold gradients it yields.  One launch where the
- * matrix-core analysis covers the geometry (the gate and the per-tile threshold partials ride in its epilogue);
- * otherwise cdl_analysis followed by cdl_tau_grad_gate.  workspace: cdl_analysis_rev_workspace_floats(g). */
-size_t cdl_analysis_rev_workspace_floats(const cdl_geom *g)
-{
-    if (!cdl_geom_ok(g)) return 0;
-    size_t n = (size_t)2 * CDL_TAU_SPLITS * g->N * g->M;       // (twice: the map-weighted partials of a map call)
-    const size_t a = cdl_analysis_workspace_floats(g);
-    if (a > n) n = a;
-    const size_t r = (!cdl_opts().no_tiled && mfma_analysis_enabled(g)) ? cdl_mfma_analysis_rev_ws_floats(g) : 0;
-    return r > n ? r : n;
-}
-
-int cdl_analysis_rev(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                     const float *zsup, const float *c, float *dt0, float *dt1, float *dtau_n, float *out,
-                     float *workspace, size_t workspace_floats, const float *cmap, void *stream)
-{
-    if (!cdl_geom_ok(g) || !x || !w || !out || !zsup || !dt0 || !dt1 || !workspace) return CDL_EINVAL;
-    if (cmap && (c || dtau_n)) return CDL_EINVAL;               // a map replaces the per-sample scale
-    if (out == zin || out == zsup) return CDL_EINVAL;
-    if (workspace_floats < cdl_analysis_rev_workspace_floats(g)) return CDL_EINVAL;
-    if (!cdl_opts().no_tiled && mfma_analysis_enabled(g) && !(mfma_dense_enabled() && cdl_dense_ws_floats(g, 0) > 0)) {
-        const int rc = cdl_mfma_analysis_rev(g, x, w, alpha, zin, zsup, c, dt0, dt1, out, workspace, workspace_floats, stream,
-                                               dtau_n, cmap);
-        if (rc != CDL_EUNSUPPORTED) return rc;
-    }
-    const int rc = cdl_analysis(g, x, w, alpha, zin, nullptr, nullptr, out, workspace, workspace_floats, nullptr, nullptr,
-                                stream);
-    if (rc) return rc;
-    return cdl_tau_grad_gate(g, out, zsup, c, dt0, dt1, dtau_n, workspace, cmap, stream);
-}
-
-int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                      const float *z_prev, const float *z_after, const float *lam, const float *gam1,
-                      const float *gam2, float *u_out, float *out, float *workspace, size_t workspace_floats,
-                      const float *cmap, const float *tslope, void *stream)
-{
-    if (!z_prev || !lam || !gam1 || (z_after && !gam2)) return CDL_EINVAL;
-    if (u_out && (u_out == out || u_out == zin)) return CDL_EINVAL;
-    if ((cmap == nullptr) != (tslope == nullptr)) return CDL_EINVAL;
-    const cdl_prox_args px{z_prev, z_after, lam, gam1, gam2, u_out};
-    return analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, px, workspace, workspace_floats, stream,
-                         cdl_map_args{cmap, tslope});
-}
-
-int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                              const float *u, const float *z_prev, const float *z_after, const float *lam,
-                              const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                              float *out, float *workspace, size_t workspace_floats, void *stream)
-{
-    if (!u || !z_prev || !lam || !gam1) return CDL_EINVAL;
-    if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
-    if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
-    // Two launches: the analysis writes ud into `out`, the pointwise tangent rewrites it in place.  (The tangent as a branch
-    // of the kernels' CSR epilogue cost the PRIMAL epilogue scalar-register spills: DESIGN.md section 22.)
-    const int rc = analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, workspace, workspace_floats, stream);
-    if (rc) return rc;
-    return cdl_prox_csr_tangent(g, out, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, stream);
-}
-
-static int analysis_impl(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
-                         const float *gate, const float *tau, float *out, const cdl_prox_args &px, float *ws,
-                         size_t ws_floats, void *stream, const cdl_map_args &mp)
-{
-    if (!cdl_geom_ok(g) || !x || !w || !out) return CDL_EINVAL;
-    if (out == zin) return CDL_EINVAL;
-    if (gate && !zin) return CDL_EINVAL;
-    if (mp.cmap && (!mp.tslope || (!tau && !px.zp))) return CDL_EINVAL;   // the map needs its slopes and constant parts
-    if (!cdl_opts().no_tiled) {
-        if (!px.zp && !mp.cmap && mfma_dense_enabled()) {   // (the dense tier's analyses carry no shrinkage map)
-            const int rcd = cdl_dense_conv(g, 0, x, nullptr, w, alpha, zin, gate, nullptr, nullptr, tau, 0, nullptr, out, ws,
-                                           ws_floats, stream);
-            if (rcd != CDL_EUNSUPPORTED) return rcd;
-        }
-        if (mfma_analysis_enabled(g)) {
-            const int rcm = cdl_mfma_analysis(g, x, w, alpha, zin, gate, tau, out, px, ws, ws_floats, stream, mp);
-            if (rcm != CDL_EUNSUPPORTED) return rcm;
-        }
-        const int rc = cdl_tiled_analysis(g, x, w, alpha, zin, gate, tau, out, px, stream, mp);
-        if (rc != CDL_EUNSUPPORTED) return rc;
-    }
-    const int Dz = g->D / g->sd, Hz = g->H / g->sh, Wz = g->W / g->sw;
-    const int tilesX = (Wz + TILE - 1) / TILE, tilesY = (Hz + TILE - 1) / TILE;
-    const int PH = (TILE - 1) * g->sh + g->Ph, PW = (TILE - 1) * g->sw + g->Pw;
-    size_t lds = (size_t)g->C * g->Pd * PH * PW * sizeof(float);
-    if (lds > 160 * 1024) return CDL_EUNSUPPORTED;
-    if (lds > 64 * 1024) {
-        const int rc_ = cdl_ensure_dynamic_lds(mp.cmap ? (const void *)k_analysis<true> : (const void *)k_analysis<false>, (int)lds);
-        if (rc_) return rc_;
-    }
-    dim3 grid((unsigned)(tilesX * tilesY * Dz), (unsigned)g->N);
-    CDL_TRACE_NOTE("k_analysis<%s>", mp.cmap ? "true" : "false");
-    if (mp.cmap)
-        k_analysis<true><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
-    else
-        k_analysis<false><<<grid, 256, lds, S(stream)>>>(*g, x, w, alpha, zin, gate, tau, out, tilesX, tilesY, px, mp);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-// the matrix-core synthesis (cdl_synth_mfma.hip) is the default wherever it has a kernel; CDL_MFMA_SYNTHESIS=0
-// selects the fp32 VALU kernels (read per call, so one process can compare both)
-static bool mfma_synthesis_enabled()
-{
-    return cdl_opts().mfma_synthesis != 0 && !cdl_exact_fp32();
-}
-
-size_t cdl_synthesis_workspace_floats(const cdl_geom *g)
-{
-    if (!cdl_geom_ok(g) || cdl_opts().no_tiled) return 0;
-    const size_t a = cdl_tiled_synthesis_ws_floats(g);
-    size_t b = mfma_synthesis_enabled() ? cdl_mfma_synthesis_ws_floats(g) : 0;
-    const size_t d = mfma_dense_enabled() ? cdl_dense_ws_floats(g, 1) : 0;
-    if (d > b) b = d;
-    return a > b ? a : b;
-}
-
-int cdl_synthesis(const cdl_geom *g, const float *z, const float *gate, const float *w, float alpha,
-                  const float *mask, const float *sub, float *out, float *workspace,
-                  size_t workspace_floats, void *stream)
-{
-    if (!cdl_geom_ok(g) || !z || !w || !out) return CDL_EINVAL;
-    if (!cdl_opts().no_tiled) {
-        if (mfma_dense_enabled()) {
-            const int rcd = cdl_dense_conv(g, 1, z, gate, w, alpha, nullptr, nullptr, mask, sub, nullptr, 0, nullptr, out,
-                                           workspace, workspace_floats, stream);
-            if (rcd != CDL_EUNSUPPORTED) return rcd;
-        }
-        if (mfma_synthesis_enabled()) {
-            const int rcm = cdl_mfma_synthesis(g, z, gate, w, alpha, mask, sub, out, workspace, workspace_floats, stream);
-            if (rcm != CDL_EUNSUPPORTED) return rcm;
-        }
-        const int rc = cdl_tiled_synthesis(g, z, gate, w, alpha, mask, sub, out, workspace, workspace_floats,
-                                           stream);
-        if (rc != CDL_EUNSUPPORTED) return rc;
-    }
-    const int tilesX = (g->W + TILE - 1) / TILE, tilesY = (g->H + TILE - 1) / TILE;
-    // upper bound on the code patch a 16x16 output tile (one d) can touch, per axis
-    const int PZD = (g->Pd - 1) / g->sd + 2;
-    const int PZH = (TILE - 1 + g->Ph - 1) / g->sh + 2;
-    const int PZW = (TILE - 1 + g->Pw - 1) / g->sw + 2;
-    size_t lds = (size_t)MCHUNK * PZD * PZH * PZW * sizeof(float);
-    if (lds > 160 * 1024) return CDL_EUNSUPPORTED;
-    if (lds > 64 * 1024) {
-        const int rc_ = cdl_ensure_dynamic_lds((const void *)k_synthesis, (int)lds);
-        if (rc_) return rc_;
-    }
-    dim3 grid((unsigned)(tilesX * tilesY * g->D), (unsigned)g->N);
-    k_synthesis<<<grid, 256, lds, S(stream)>>>(*g, z, gate, w, alpha, mask, sub, out, tilesX, tilesY,
-                                                PZD, PZH, PZW);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-// matrix-core filter gradients are the default wherever they have a kernel; CDL_MFMA_WGRAD=0 selects the VALU ones
-static bool mfma_wgrad_enabled()
-{
-    return cdl_opts().mfma_wgrad != 0 && !cdl_exact_fp32();
-}
-
-size_t cdl_wgrad_workspace_floats(const cdl_geom *g)
-{
-    if (!cdl_geom_ok(g)) return 0;
-    const size_t total = (size_t)g->M * g->C * g->Pd * g->Ph * g->Pw;
-    size_t chunks = 2048 / ((size_t)g->M * g->C * g->Pd);
-    const size_t by_rows = total * (chunks < 1 ? 1 : chunks);                    // k_wgrad_p
-    // k_wgrad_l: one partial filter bank per 64 x 32 tile of code pixels (cdl_generic_tiled.hip)
-    const size_t tiles = (size_t)g->N * (g->D / g->sd) * ((g->W / g->sw + 63) / 64) * ((g->H / g->sh + 31) / 32);
-    const size_t by_tiles = tiles <= 4096 ? tiles * total : 0;                   // <= a few tens of MB
-    const size_t by_mfma = mfma_wgrad_enabled() ? 2 * cdl_mfma_wgrad_ws_floats(g) : 0;  // cdl_wgrad_mfma.hip (room for a paired launch)
-    size_t a = by_rows > by_tiles ? by_rows : by_tiles;
-    const size_t by_dense = mfma_dense_enabled() ? cdl_dense_wgrad_ws_floats(g) : 0;     // cdl_dense_mfma.hip
-    if (by_dense > a) a = by_dense;
-    return a > by_mfma ? a : by_mfma;
-}
-
-int cdl_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha,
-              float *dw, float *workspace, size_t workspace_floats, void *stream)
-{
-    if (!cdl_geom_ok(g) || !z || !x || !dw) return CDL_EINVAL;
-    if (g->Pw > PWMAX) return CDL_EUNSUPPORTED;
-    if (!cdl_opts().no_tiled) {
-        if (mfma_dense_enabled()) {
-            const int rcd = cdl_dense_wgrad(g, z, gate, x, alpha, dw, workspace, workspace_floats, stream);
-            if (rcd != CDL_EUNSUPPORTED) return rcd;
-        }
-        if (mfma_wgrad_enabled()) {
-            const cdl_wgrad_op op{z, x, alpha, dw};
-            const int rcm = cdl_mfma_wgrad(g, &op, 1, gate, 0, workspace, workspace_floats, stream);
-            if (rcm != CDL_EUNSUPPORTED) return rcm;
-        }
-        const int rc = cdl_tiled_wgrad(g, z, gate, x, alpha, dw, workspace, workspace_floats, stream);
-        if (rc != CDL_EUNSUPPORTED) return rc;
-    }
-    dim3 grid((unsigned)g->M, (unsigned)(g->C * g->Pd * g->Ph));
-    k_wgrad<<<grid, 256, 0, S(stream)>>>(*g, z, gate, x, alpha, dw);
-    CDL_LAUNCH_CHECK();
-    return 0;
-}
-
-/* dw0 = alpha0 * z0 (x) x0 and dw1 = alpha1 * z1 (x) x1 (both ungated, same geometry): one paired matrix-core launch
- * where the shape has one (cdl_wgrad_mfma.hip), two cdl_wgrad calls otherwise.  Same workspace as cdl_wgrad. */
-int cdl_wgrad_pair(const cdl_geom *g, const float *z0, const float *x0, float alpha0, float *dw0, const float *z1,
-                   const float *x1, float alpha1, float *dw1, float *workspace, size_t workspace_floats, void *stream)
-{
-    if (!cdl_geom_ok(g) || !z0 || !x0 || !dw0 || !z1 || !x1 || !dw1) return CDL_EINVAL;
-    if (g->Pw <= PWMAX && !cdl_opts().no_tiled && mfma_wgrad_enabled() &&
-        !(mfma_dense_enabled() && cdl_dense_wgrad_ws_floats(g) > 0)) {
-        const cdl_wgrad_op ops[2] = {{z0, x0, alpha0, dw0}, {z1, x1, alpha1, dw1}};
-        const int rc = cdl_mfma_wgrad(g, ops, 2, nullptr, 0, workspace, workspace_floats, stream);
-        if (rc != CDL_EUNSUPPORTED) return rc;
-    }
-    const int rc = cdl_wgrad(g, z0, nullptr, x0, alpha0, dw0, workspace, workspace_floats, stream);
-    if (rc) return rc;
-    return cdl_wgrad(g, z1, nullptr, x1, alpha1, dw1, workspace, workspace_floats, stream);
 }
 
 static int tau_grad_impl(const cdl_geom *g, float *gup, const float *zout, const float *c, float *dt0, float *dt1,

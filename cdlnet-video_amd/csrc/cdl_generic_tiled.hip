@@ -2,8 +2,8 @@
 // (Pw in {3,5,7,9}, stride in {1,2}; any C for analysis, C in {1,3} for synthesis; 2-D and 3-D).
 // Each thread owns 4 consecutive output columns, so one LDS row window of 3*s + Pw values feeds
 // 4*Pw FMAs per channel and the filter row arrives as one wave-uniform (scalar) vector load.
-// cdl_analysis / cdl_synthesis (cdl_generic.hip) try these first and fall back to the untiled
-// kernels for every other shape.
+// The operators' ladder (cdl_operators.hip) tries these ahead of the untiled kernels of
+// cdl_generic.hip, which serve every other shape.
 #include "cdl_common.h"
 
 namespace {
@@ -870,19 +870,38 @@ int cdl_tiled_synthesis(const cdl_geom *g, const float *z, const float *gate, co
     return CDL_EUNSUPPORTED;
 }
 
+// The two workspace-backed kernels of cdl_tiled_wgrad, planned once for the launcher and for the size function.  The
+// launcher picks its kernel by the floats it is handed, so what `ws` offers decides which kernel a caller gets.
+struct TiledWgradPlan {
+    int tX, tY;
+    long tiles;           // k_wgrad_l: WLX x WLY tiles of code pixels, one partial filter bank each
+    size_t total, chunks; // k_wgrad_p: floats of one bank; the most chunks of code rows (a partial bank each)
+    size_t ws;            // room for k_wgrad_p's chunks and, up to 4096 tiles (a few tens of MB), for k_wgrad_l's tiles
+};
+static TiledWgradPlan tiled_wgrad_plan(const cdl_geom *g)
+{
+    TiledWgradPlan p;
+    p.tX = (g->W / g->sw + WLX - 1) / WLX, p.tY = (g->H / g->sh + WLY - 1) / WLY;
+    p.tiles = (long)g->N * (g->D / g->sd) * p.tX * p.tY;
+    p.total = (size_t)g->M * g->C * g->Pd * g->Ph * g->Pw;
+    p.chunks = max_sz(1, 2048 / ((size_t)g->M * g->C * g->Pd));      // about 2048 workgroups
+    p.ws = max_sz(p.chunks * p.total, p.tiles <= 4096 ? (size_t)p.tiles * p.total : 0);
+    return p;
+}
+size_t cdl_tiled_wgrad_ws_floats(const cdl_geom *g) { return tiled_wgrad_plan(g).ws; }
+
 int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const float *x, float alpha,
                     float *dw, float *workspace, size_t workspace_floats, void *stream)
 {
     if (g->sw != g->sh) return CDL_EUNSUPPORTED;
     if (workspace) {
         // first choice: image tile in LDS, every code channel inside the workgroup (z read C*Pd times in total)
-        const int Dz_ = g->D / g->sd, Hz_ = g->H / g->sh, Wz_ = g->W / g->sw;
-        const int tX = (Wz_ + WLX - 1) / WLX, tY = (Hz_ + WLY - 1) / WLY;
-        const long tiles = (long)g->N * Dz_ * tX * tY;
+        const TiledWgradPlan p = tiled_wgrad_plan(g);
+        const int tX = p.tX, tY = p.tY; const long tiles = p.tiles;
         const int CPd = g->C * g->Pd, tapsl = g->Ph * g->Pw;
         const int XW = (((WLX - 1) * g->sw + g->Pw + 3) + 3) & ~3;     // multiple of 4 words + room for the 16-byte reads
         const size_t ldsl = (size_t)((WLY - 1) * g->sh + g->Ph) * XW * sizeof(float);
-        if (tiles * CPd >= 128 && (size_t)tiles * CPd * g->M * tapsl <= workspace_floats && ldsl <= 64 * 1024 &&
+        if (tiles * CPd >= 128 && (size_t)tiles * p.total <= workspace_floats && ldsl <= 64 * 1024 &&
             tiles < (1L << 31)) {
             dim3 gridl((unsigned)tiles, (unsigned)CPd);
             const int totall = g->M * CPd * tapsl;
@@ -901,11 +920,10 @@ int cdl_tiled_wgrad(const cdl_geom *g, const float *z, const float *gate, const 
 #undef CDL_L
         }
         // second tier: whole filter planes in registers, code rows split into chunks
-        const int total = g->M * g->C * g->Pd * g->Ph * g->Pw;
+        const int total = (int)p.total;
         const int Hz = g->H / g->sh, Wz = g->W / g->sw;
         const int rows = g->N * (g->D / g->sd) * ((Hz + ZR - 1) / ZR);      // row groups of ZR code rows
-        int chunks = 2048 / (g->M * g->C * g->Pd);
-        if (chunks < 1) chunks = 1;
+        int chunks = (int)p.chunks;
         if (chunks > rows) chunks = rows;
         while (chunks > 1 && (size_t)chunks * total > workspace_floats) --chunks;
         const int rpc = (rows + chunks - 1) / chunks;

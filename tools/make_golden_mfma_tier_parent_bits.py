@@ -187,13 +187,13 @@ def part_paths(path):
     return paths
 
 
-def save_parts(path, rec):
-    """Write {name: array} as path, <stem>.1.npz, ...: whole cases in the order of CASES, a new file whenever the next
-    case would take the current one past PART_BYTES.  Returns {file: names}."""
+def save_parts(path, rec, cases=None):
+    """Write {name: array} as path, <stem>.1.npz, ...: whole cases in the order of `cases` (CASES), a new file whenever the
+    next case would take the current one past PART_BYTES.  Returns {file: names}."""
     import numpy as np
     assert path.endswith(".npz")
     parts, size = [[]], 0
-    for case in CASES:
+    for case in (CASES if cases is None else cases):
         names = [k for k in rec if k.startswith(case + "/")]
         nbytes = sum(rec[k].nbytes for k in names)
         if parts[-1] and size + nbytes > PART_BYTES:
