@@ -61,7 +61,7 @@ SIGNATURES = {
     "cdl_ista_backward": [_G, _I] + [_P] * 26 + [ctypes.c_size_t, _P, _P, _P, _P, _P, _P],     # .., dyp, dtau, cmap, tslope, dcmap, stream
     "cdl_tangent_forward": [_G, _I] + [_P] * 10 + [ctypes.c_size_t, _P],
     "cdl_tangent_backward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P],      # .., g_xp, g_zd, dA, ..
-    "cdl_csr_tangent_forward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P],
+    "cdl_csr_tangent_forward": [_G, _I] + [_P] * 16 + [ctypes.c_size_t, _P, _P, _P],
     "cdl_nle_mad": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _P],
     "cdl_nle_mad_cells": [_P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _I, _P],
     "cdl_nle_nlf_bins": [_P, _P, _P, _P, ctypes.c_size_t, _I, _I, _I, _I, _I, _F, _F, _P],
@@ -77,13 +77,13 @@ SIGNATURES = {
     "cdl_residual_backward": [_G] + [_P] * 11 + [ctypes.c_size_t, _P],
     "cdl_prox_csr": [_G, _P, _P, _P, _P, _P, _P, _P, _P],
     "cdl_prox_csr_bwd": [_G] + [_P] * 15 + [ctypes.c_size_t, _P, _P, _P, _P, _P],              # .., cmap, tslope, dcmap, dsum_n, stream
-    "cdl_prox_csr_tangent": [_G] + [_P] * 11,
+    "cdl_prox_csr_tangent": [_G] + [_P] * 13,
     # thresholds of any broadcast shape (each threshold pointer is followed by its strides)
     "cdl_shrink_b": [_P, _P, _B, _P, _I, _I, ctypes.c_size_t, _P],
     "cdl_shrink_b_bwd": [_P, _P, _P, _B, _P, _P, _I, _I, ctypes.c_size_t, _P],
     "cdl_prox_csr_b": [_G, _P, _P, _P, _P, _B, _P, _B, _P, _B, _P, _P],
     "cdl_prox_csr_b_bwd": [_G, _P, _P, _P, _P, _P, _B, _P, _B, _P, _B] + [_P] * 7 + [ctypes.c_size_t, _P],
-    "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P],
+    "cdl_analysis_prox_tangent": [_G, _P, _P, _F] + [_P] * 11 + [ctypes.c_size_t, _P, _P, _P],
     "cdl_project_filter_banks": [_P, _I, _I, _I, _P],
     "cdl_options_reload": [],
     "cdl_set_exact_fp32": [_I],

@@ -131,15 +131,17 @@ int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float a
 int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha, const float *zin,
                               const float *u, const float *z_prev, const float *z_after, const float *lam,
                               const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                              float *out, float *workspace, size_t workspace_floats, void *stream)
+                              float *out, float *workspace, size_t workspace_floats, const float *cmap,
+                              const float *tslope, void *stream)
 {
     if (!u || !z_prev || !lam || !gam1) return CDL_EINVAL;
     if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
     if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
+    if ((cmap == nullptr) != (tslope == nullptr)) return CDL_EINVAL;   // (the map only enters the pointwise pass's gates)
     // Two launches: the analysis writes ud into `out`, the pointwise tangent rewrites it in place.  (The tangent as a branch
     // of the kernels' CSR epilogue cost the PRIMAL epilogue scalar-register spills: DESIGN.md section 22.)
     CDL_TRY(analysis_impl(g, x, w, alpha, zin, nullptr, nullptr, out, cdl_prox_args{}, workspace, workspace_floats, stream));
-    return cdl_prox_csr_tangent(g, out, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, stream);
+    return cdl_prox_csr_tangent(g, out, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, cmap, tslope, stream);
 }
 
 size_t cdl_synthesis_workspace_floats(const cdl_geom *g) { return walk_ws(SYNTHESIS, SYNTHESIS_RUNGS, g); }

@@ -36,17 +36,72 @@ __device__ __forceinline__ size_t at(const cdl_bcast &s, int n, int m, size_t pi
     return (size_t)n * (size_t)s.n + (size_t)m * (size_t)s.m + pix * (size_t)s.p;
 }
 
+// ---- the tangent under a noise-level map: the thresholds of element (n, m, pix) are
+// cdl_map_threshold(lam0[n,m], cmap[n,pix], tsl[0,m]) and the same with tsl[1,m], tsl[2,m] for gam1, gam2 -- the function of
+// the primal's CSR epilogue, so the gates are the primal's bit for bit; no threshold enters a value.  The GRID is that of
+// prox_bwd_map (map_chunks, map_msplits): one workgroup takes MAP_PIX pixels of one sample and a range of channels.  Within
+// it the threads are laid out differently: a thread holds ONE pixel's map value in a register while it walks the channels,
+// whose constant parts and slopes are wave-uniform (scalar loads), then steps 256 pixels on -- MAP_PXT pixels per thread one
+// after the other, not MAP_PXT at once in registers as prox_bwd_map keeps them.  Entered from k_prox_fwd on a launch-uniform
+// branch (TanMap::cmap) with a grid of its own shape.  out may alias in: a thread reads its element before it writes it.
+struct TanMap {
+    const float *cmap, *tsl;   // (N, pixels), (3, M); cmap == nullptr: the row / broadcast forms
+    int chunks, MS;            // pixel chunks, channel ranges: the grid is chunks * MS * N workgroups
+};
+constexpr int MAP_PXT = 4;                 // pixels of a chunk per thread (prox_bwd_map: held in registers together)
+constexpr int MAP_PIX = 256 * MAP_PXT;     // pixels of a chunk, both map kernels
+
+template <bool F2>
+__device__ __forceinline__ void prox_tangent_map(const float *in, const float *__restrict__ up, const float *__restrict__ zp,
+                                                 const float *__restrict__ za, const float *__restrict__ lam,
+                                                 const float *__restrict__ g1, const float *__restrict__ g2,
+                                                 const float *__restrict__ zpd, const float *__restrict__ zad, float *out,
+                                                 size_t per_m, int M, const TanMap &tm)
+{
+    const float *__restrict__ cmap = tm.cmap, *__restrict__ tsl = tm.tsl;
+    const int chunks = tm.chunks, MS = tm.MS;
+    int b = blockIdx.x;
+    const int chunk = b % chunks;
+    b /= chunks;
+    const int ms = b % MS, n = b / MS;
+    const int mper = (M + MS - 1) / MS, m_lo = ms * mper, m_hi = m_lo + mper < M ? m_lo + mper : M;
+    const size_t lo = (size_t)chunk * MAP_PIX, hi = lo + MAP_PIX < per_m ? lo + MAP_PIX : per_m;
+#pragma unroll 1
+    for (size_t j = lo + threadIdx.x; j < hi; j += 256) {
+        const float c = cmap[(size_t)n * per_m + j];
+        for (int m = m_lo; m < m_hi; ++m) {
+            const size_t row = (size_t)n * M + m, i = row * per_m + j;
+            const float l = cdl_map_threshold(lam[row], c, tsl[m]), a1 = cdl_map_threshold(g1[row], c, tsl[M + m]);
+            const float ud = in[i], dp = zpd ? zpd[i] : 0.0f;
+            if (!F2)
+                out[i] = cdl_prox_csr1_tangent(prox1(up[i], zp[i], l, a1), l, ud, dp);
+            else
+                out[i] = cdl_prox_csr2_tangent(prox2(up[i], zp[i], za[i], l, a1, cdl_map_threshold(g2[row], c, tsl[2 * M + m])),
+                                               l, ud, dp, zad ? zad[i] : 0.0f);
+        }
+    }
+}
+
 // The map itself (up == nullptr: in = u, out = prox(u; zp[, za])) or its tangent at the primal (up, zp[, za]) along
 // (in = ud, zpd, zad; a null neighbour tangent is a zero one): one kernel, one launch site (launch_prox).  out may alias in
 // (each thread reads its element before it writes it).  M == 0: every threshold is in the row form (index = row); M > 0:
-// the general broadcast form `bs` of the map itself (up == nullptr), M the channel count.
-__global__ __launch_bounds__(256) void k_prox_fwd(const float *in, const float *__restrict__ up,
+// the general broadcast form `bs` of the map itself (up == nullptr), M the channel count.  tm.cmap: the tangent under a
+// noise-level map (prox_tangent_map above), M the channel count, the grid tm.chunks * tm.MS * N workgroups.
+// (8 waves per SIMD asked for: the map branch's loop invariants otherwise fill the scalar file and cost every form a wave.)
+__global__ __launch_bounds__(256, 8) void k_prox_fwd(const float *in, const float *__restrict__ up,
                                                   const float *__restrict__ zp, const float *__restrict__ za,
                                                   const float *__restrict__ lam, const float *__restrict__ g1,
                                                   const float *__restrict__ g2, const float *__restrict__ zpd,
                                                   const float *__restrict__ zad, float *out, size_t total, size_t per_m,
-                                                  int M, Bcast3 bs)
+                                                  int M, Bcast3 bs, TanMap tm)
 {
+    if (tm.cmap) {                                                   // uniform: the whole launch takes the map form
+        if (za)
+            prox_tangent_map<true>(in, up, zp, za, lam, g1, g2, zpd, zad, out, per_m, M, tm);
+        else
+            prox_tangent_map<false>(in, up, zp, nullptr, lam, g1, nullptr, zpd, nullptr, out, per_m, M, tm);
+        return;
+    }
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / per_m;
@@ -147,8 +202,6 @@ struct ProxMap {
     int N, chunks, MS;         // samples, pixel chunks, channel ranges: k_prox_bwd's grid is their product
     size_t NP;                 // N * pixels: the elements of dcmap
 };
-constexpr int MAP_PXT = 4;
-constexpr int MAP_PIX = 256 * MAP_PXT;
 
 template <bool F2>
 __device__ __forceinline__ void prox_bwd_map(const float *gz, const float *__restrict__ u, const float *__restrict__ zp,
@@ -389,14 +442,17 @@ extern "C" {
 
 static int launch_prox(const cdl_geom *g, const float *in, const float *up, const float *z_prev, const float *z_after,
                        const float *lam, const float *gam1, const float *gam2, const float *zd_prev, const float *zd_after,
-                       float *out, const Bcast3 &bs, void *stream)
+                       float *out, const Bcast3 &bs, void *stream, const TanMap &tm = TanMap{})
 {
     const size_t per_m = code_elems(g), total = (size_t)g->N * g->M * per_m;
     const bool rows = is_row(bs.lam, g->M) && is_row(bs.g1, g->M) && (!z_after || is_row(bs.g2, g->M));
-    const size_t blocks = (total + 255) / 256;
-    if (blocks >= ((size_t)1 << 31) || (up && !rows)) return CDL_EUNSUPPORTED;
+    // the tangent's map form: a grid of its own shape (prox_tangent_map), the constant parts in the row form
+    const size_t blocks = tm.cmap ? (size_t)tm.chunks * tm.MS * g->N : (total + 255) / 256;
+    if (blocks >= ((size_t)1 << 31) || (up && !rows) || (tm.cmap && !up)) return CDL_EUNSUPPORTED;
+    if (tm.cmap) CDL_TRACE_NOTE("map MS=%d chunks=%d", tm.MS, tm.chunks);
     k_prox_fwd<<<(unsigned)blocks, 256, 0, S(stream)>>>(in, up, z_prev, z_after, lam, gam1, gam2, zd_prev,
-                                                                         zd_after, out, total, per_m, rows ? 0 : g->M, bs);
+                                                                         zd_after, out, total, per_m,
+                                                                         (rows && !tm.cmap) ? 0 : g->M, bs, tm);
     CDL_LAUNCH_CHECK();
     return 0;
 }
@@ -424,13 +480,20 @@ int cdl_prox_csr(const cdl_geom *g, const float *u, const float *z_prev, const f
 
 int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, const float *z_prev, const float *z_after,
                          const float *lam, const float *gam1, const float *gam2, const float *zd_prev,
-                         const float *zd_after, float *out, void *stream)
+                         const float *zd_after, float *out, const float *cmap, const float *tslope, void *stream)
 {
     if (!cdl_geom_ok(g) || !ud || !u || !z_prev || !lam || !gam1 || !out) return CDL_EINVAL;
     if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
     if (out == u || out == z_prev || out == z_after || out == zd_prev || out == zd_after) return CDL_EINVAL;
+    if ((cmap == nullptr) != (tslope == nullptr)) return CDL_EINVAL;
+    TanMap tm{};
+    if (cmap) {
+        const size_t chunks = map_chunks(code_elems(g));
+        if (chunks >= ((size_t)1 << 28)) return CDL_EUNSUPPORTED;
+        tm = TanMap{cmap, tslope, (int)chunks, map_msplits(g->N, g->M, chunks)};
+    }
     const Bcast3 bs{ROW(g->M), ROW(g->M), ROW(g->M)};
-    return launch_prox(g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, bs, stream);
+    return launch_prox(g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, bs, stream, tm);
 }
 
 size_t cdl_prox_csr_scratch_floats(const cdl_geom *g)

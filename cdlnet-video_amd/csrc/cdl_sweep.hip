@@ -250,17 +250,18 @@ int cdl_csr_tangent_forward(const cdl_geom *g, int K, const float *vp, const flo
                             const float *z_after, const float *lam, const float *gam1, const float *gam2,
                             const float *zd_prev, const float *zd_after, const float *const *wA, const float *const *wB,
                             const float *const *u, float *const *zd, float *const *rd, float *xdp, float *scratch,
-                            size_t scratch_floats, void *stream)
+                            size_t scratch_floats, const float *cmap, const float *tslope, void *stream)
 {
     if (!cdl_geom_ok(g) || K < 1 || !vp || !z_prev || !lam || !gam1 || !wA || !wB || !u || !zd || !xdp || (K > 1 && !rd))
         return CDL_EINVAL;
     if (z_after ? !gam2 : (zd_after != nullptr)) return CDL_EINVAL;
+    if ((cmap == nullptr) != (tslope == nullptr)) return CDL_EINVAL;   // the (K, 3, M) slopes of lam, gam1, gam2
     const size_t NM = (size_t)g->N * g->M;
     const Scratch sc{scratch, scratch_floats, stream};
     return forward_order_loop(g, K, vp, mask, wB, zd, rd, xdp, sc, [&](int k, const float *x, float alpha, const float *zin) {
         return cdl_analysis_prox_tangent(g, x, wA[k], alpha, zin, u[k], z_prev, z_after, lam + k * NM, gam1 + k * NM,
                                          gam2 ? gam2 + k * NM : nullptr, zd_prev, zd_after, zd[k], scratch, scratch_floats,
-                                         stream);
+                                         cmap, cmap ? tslope + (size_t)k * 3 * g->M : nullptr, stream);
     });
 }
 

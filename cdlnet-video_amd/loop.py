@@ -890,21 +890,24 @@ def _backward_csr_stepwise(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, 
 # what cdl_prox_csr_bwd applies, so its reverse sweep is the primal's (_backward_csr) with yp -> vp, codes -> zd,
 # residuals -> rd and the PRIMAL's u_k, neighbour codes and thresholds: it yields the filter gradients and
 # dL/dzd_prev, dL/dzd_after; its threshold sums are discarded (the gates are piecewise constant).
-def _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep):
+# Under a noise-level map the gates are read at the primal's per-element thresholds: cmap with
+# tslope (K,3,M) as in _forward_csr, lam / gam* the constant parts, handed to the forward and the reverse tangent sweep alike.
+def _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep, cmap=None, tslope=None):
     """Whole CSR tangent sweep from one C call (cdl_csr_tangent_forward): (xdp, zd_K, zd, rd)."""
-    return ops.csr_tangent_forward(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep)
+    return ops.csr_tangent_forward(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep, cmap=cmap, tslope=tslope)
 
 
-def _tangent_csr_stepwise(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep):
+def _tangent_csr_stepwise(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep, cmap=None, tslope=None):
     """Same sweep driven launch by launch from Python (kept for tests and experiments)."""
     K = len(A)
     g2 = (lambda k: gam2[k]) if za is not None else (lambda k: None)
+    mp = (lambda k: dict(cmap=cmap, tslope=tslope[k])) if cmap is not None else (lambda k: {})
     zd, rd = [], []
-    z = ops.analysis_prox_tangent(g, vp, A[0], 1.0, None, us[0], zp, lam[0], gam1[0], za, g2(0), zdp, zda)
+    z = ops.analysis_prox_tangent(g, vp, A[0], 1.0, None, us[0], zp, lam[0], gam1[0], za, g2(0), zdp, zda, **mp(0))
     zd.append(z)
     for k in range(1, K):
         r = ops.synthesis(g, z, B[k], 1.0, None, mask_p, vp)
-        z = ops.analysis_prox_tangent(g, r, A[k], -1.0, z, us[k], zp, lam[k], gam1[k], za, g2(k), zdp, zda)
+        z = ops.analysis_prox_tangent(g, r, A[k], -1.0, z, us[k], zp, lam[k], gam1[k], za, g2(k), zdp, zda, **mp(k))
         zd.append(z)
         rd.append(r)
     xdp = ops.synthesis(g, z, B[0], 1.0)
@@ -912,12 +915,13 @@ def _tangent_csr_stepwise(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B
 
 
 def _tangent_backward_csr(g, K, vp, mask_p, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, gzdp, gzda,
-                          sweep=_backward_csr):
+                          sweep=_backward_csr, cmap=None, tslope=None):
     """Reverse sweep of the CSR tangent sweep: (dA, dB), accumulating dL/dzd_prev, dL/dzd_after into gzdp / gzda (nullable).
-    `sweep`: _backward_csr (one C call) or _backward_csr_stepwise."""
+    `sweep`: _backward_csr (one C call) or _backward_csr_stepwise.  cmap / tslope: the primal's noise-level map (no map
+    gradient leaves the tangent: the gates are piecewise constant in it)."""
     sink = torch.empty((3, K, 2, g.M), device=vp.device, dtype=torch.float32)       # threshold sums nobody reads
     return sweep(g, K, vp, mask_p, None, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, sink[0], sink[1],
-                 sink[2] if za is not None else None, gzdp, gzda)
+                 sink[2] if za is not None else None, gzdp, gzda, cmap=cmap, tslope=tslope)
 
 
 @_arithmetic_aware
@@ -925,7 +929,8 @@ class TangentTemporalISTA(torch.autograd.Function):
     """(y, v, mask, c, z_prev, zd_prev|None, z_after|None, zd_after|None, t, g1, g2|None, A.., B..) -> (xhat, xdot, z_K, zd_K):
     the primal of TemporalISTA and its derivative along (v, zd_prev, zd_after) at the primal's gates.  Gradients for the
     neighbour codes and the three threshold families (from xhat and z_K alone), for the neighbour tangents (from xdot and zd_K
-    alone) and for both filter banks (the sum of the two reverse sweeps)."""
+    alone) and for both filter banks (the sum of the two reverse sweeps).  c: None, one level per sample (N,), or a
+    noise-level map (N,1,*code grid) as TemporalISTA takes it (no gradient for c here)."""
 
     @staticmethod
     def forward(ctx, y, v, mask, c, zp, zdp, za, zda, t, g1, g2, cfg, *weights):
@@ -939,14 +944,17 @@ class TangentTemporalISTA(torch.autograd.Function):
             if x is not None and tuple(x.shape) != g.code_shape():
                 raise ValueError(f"{name}: shape {tuple(x.shape)} does not match this frame's code shape {g.code_shape()}")
         zp, zdp, za, zda = (x.contiguous() if x is not None else None for x in (zp, zdp, za, zda))
-        lam, gam1 = ops.thresholds(t, c, N), ops.thresholds(g1, c, N)
-        gam2 = ops.thresholds(g2, c, N) if za is not None else None
+        ctx.is_map = c is not None and c.dim() > 1
+        cs = None if ctx.is_map else c                 # a map: the thresholds' constant parts, the slopes beside them
+        lam, gam1 = ops.thresholds(t, cs, N), ops.thresholds(g1, cs, N)
+        gam2 = ops.thresholds(g2, cs, N) if za is not None else None
+        mp = dict(cmap=c, tslope=_csr_slopes(t, g1, g2 if za is not None else None)) if ctx.is_map else {}
         ctx.set_materialize_grads(False)
         _no_data_gradients(ctx, ((0, "y"), (1, "v"), (2, "mask"), (3, "sigma")))
         keep = any(ctx.needs_input_grad)
         # the gates are read off the primal's u_k: all K are kept whatever `keep` says
-        xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, True)
-        xdp, zdK, zd, rd = _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep)
+        xp, z, us, codes, resid = _forward_csr(g, yp, mask_p, lam, gam1, gam2, zp, za, A, B, True, **mp)
+        xdp, zdK, zd, rd = _tangent_csr(g, vp, mask_p, lam, gam1, gam2, zp, za, zdp, zda, A, B, us, keep, **mp)
         xhat = ops.postprocess(xp, mean, pads)
         xdot = ops.postprocess(xdp, vmean, pads)
         ctx.geom, ctx.pads, ctx.K = g, pads, K
@@ -973,14 +981,16 @@ class TangentTemporalISTA(torch.autograd.Function):
         g_z = g_z.contiguous() if g_z is not None else None
         g_zd = g_zd.contiguous() if g_zd is not None else None
         dA = dB = None
+        # a map takes c's place in both reverse sweeps (dt[:,1], dg*[:,1] are then the map-weighted sums)
+        mp = dict(cmap=c, tslope=_csr_slopes(t, g1, g2 if za is not None else None)) if ctx.is_map else {}
         if g_xhat is not None or g_z is not None:      # the primal's reverse sweep, as TemporalISTA runs it
             g_xp = ops.postprocess_bwd(g_xhat.contiguous(), ctx.pads) if g_xhat is not None else None
-            dA, dB = _backward_csr(g, K, yp, mask_p, c, A, B, codes, resid, us, zp, za, lam, gam1, gam2, g_xp, g_z, dt, dg1,
-                                   dg2, gzp, gza)
+            dA, dB = _backward_csr(g, K, yp, mask_p, None if ctx.is_map else c, A, B, codes, resid, us, zp, za, lam, gam1,
+                                   gam2, g_xp, g_z, dt, dg1, dg2, gzp, gza, **mp)
         if g_xdot is not None or g_zd is not None:     # the tangent's: same sweep, other operands, the primal's gates
             g_xdp = ops.postprocess_bwd(g_xdot.contiguous(), ctx.pads) if g_xdot is not None else None
             tA, tB = _tangent_backward_csr(g, K, vp, mask_p, A, B, zd, rd, us, zp, za, lam, gam1, gam2, g_xdp, g_zd, gzdp,
-                                           gzda)
+                                           gzda, **mp)
             dA, dB = _add_sweeps((dA, dB), (tA, tB))
         if dA is None:
             dA, dB = _zero_grads(A, B)

@@ -266,30 +266,45 @@ class _CSRBase(_ISTANet):
         return ("the CSR nets take neighbour codes, which jvp(y, v) cannot carry; their tangent sweep is "
                 "jvp_recurrent(y, v, z_prev, zdot_prev, ...)")
 
-    def _prep_tangent(self, y, v, sigma, mask, pairs):
-        """Argument checks of jvp_recurrent: forward's (_prep) and jvp's, and each neighbour tangent with its code."""
-        name = type(self).__name__
+    def _check_tangent(self, y, v, sigma, mask, pairs, who=None):
+        """Argument checks of a tangent call, jvp's and each neighbour tangent with its code: jvp_recurrent's, and those of
+        temporal.csr_jvp_step (which names itself in `who`)."""
+        fn = who or "jvp_recurrent"
+        qual = who or f"{type(self).__name__}.jvp_recurrent"
         if not torch.is_tensor(v):
-            raise TypeError("jvp_recurrent: v must be a tensor shaped like y")
+            raise TypeError(f"{fn}: v must be a tensor shaped like y")
         for label, code, dot in pairs:
             if dot is not None and code is None:
-                raise ValueError(f"jvp_recurrent: zdot_{label} given without z_{label} (a tangent belongs to a code)")
+                raise ValueError(f"{fn}: zdot_{label} given without z_{label} (a tangent belongs to a code)")
         for label, x in (("y", y), ("v", v)):
             if not x.is_cuda:
                 raise RuntimeError(
-                    f"{name}.jvp_recurrent: {label} is on {x.device}. This package has no CPU "
+                    f"{qual}: {label} is on {x.device}. This package has no CPU "
                     "compute path; the iterations run in HIP kernels on a ROCm device.")
         if tuple(v.shape) != tuple(y.shape):
-            raise ValueError(f"jvp_recurrent: v has shape {tuple(v.shape)}, y has {tuple(y.shape)}")
+            raise ValueError(f"{fn}: v has shape {tuple(v.shape)}, y has {tuple(y.shape)}")
         for label, x in (("v", v), ("y", y), ("sigma", sigma), ("mask", mask)):
             if torch.is_tensor(x) and x.requires_grad:
-                raise NotImplementedError(f"cdlnet_video_amd: {name}.jvp_recurrent: `{label}` requires grad; the tangent sweep "
+                raise NotImplementedError(f"cdlnet_video_amd: {qual}: `{label}` requires grad; the tangent sweep "
                                           "returns parameter and neighbour-code gradients only (detach() it)")
         if loop.CODE_LAYOUT == "blocked_bf16":
-            raise NotImplementedError("cdlnet_video_amd: jvp_recurrent with set_code_layout('blocked_bf16') is not "
+            raise NotImplementedError(f"cdlnet_video_amd: {fn} with set_code_layout('blocked_bf16') is not "
                                       "implemented (tangent codes are stored in fp32)")
+
+    def _prep_tangent(self, y, v, sigma, mask, pairs):
+        """Argument checks of jvp_recurrent: the tangent's (_check_tangent) and forward's (_prep)."""
+        self._check_tangent(y, v, sigma, mask, pairs)
         y, mask_t, c = self._prep(y, sigma, mask)
         return y, v.to(torch.float32), mask_t, c
+
+    def _jvp_branch(self, y, v, mask_t, c, z_prev, zdot_prev, z_after=None, zdot_after=None):
+        """The tangent call of the branch forward takes (_tangent_branch of the variant): jvp_recurrent after its checks, and
+        temporal.csr_jvp_step after its own (c may then be a noise-level map)."""
+        t, A, B, nb = self._tangent_branch(z_prev, zdot_prev, z_after, zdot_after)
+        if nb is None:
+            return loop.run_tangent(y, v, mask_t, c, t, A, B, self.s, codes=True)
+        zp, zdp, za, zda, g1, g2 = nb
+        return loop.run_csr_tangent(y, v, mask_t, c, zp, zdp, za, zda, t, g1, g2, A, B, self.s)
 
     def _prep(self, y, sigma, mask):
         if not y.is_cuda:
@@ -346,12 +361,19 @@ class CDLNet_CSR(_CSRBase):
         the parameters and in z_prev / zdot_prev, so the calls of a clip chain; the thresholds get their gradient through
         (xhat, z) alone.  Gradients with respect to y, v, sigma or mask are not produced."""
         y, v, mask_t, c = self._prep_tangent(y, v, sigma, mask, (("prev", z_prev, zdot_prev),))
+        return self._jvp_branch(y, v, mask_t, c, z_prev, zdot_prev)
+
+    def _tangent_branch(self, z_prev, zdot_prev, z_after=None, zdot_after=None):
+        """(t, A, B, neighbours): without a neighbour the plain loop on the second bank (neighbours None; B2[0] is never
+        applied), else (z_prev, zdot_prev, None, None, g, None) on the first."""
+        if z_after is not None or zdot_after is not None:
+            raise ValueError("CDLNet_CSR has no z_after")
         if z_prev is None:
             A = [m.weight for m in self.A2]
             B = [self.B[0].weight] + [m.weight for m in self.B2][1:]
-            return loop.run_tangent(y, v, mask_t, c, self.t2, A, B, self.s, codes=True)
+            return self.t2, A, B, None
         A, B = self._filters()
-        return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, None, None, self.t, self.g, None, A, B, self.s)
+        return self.t, A, B, (z_prev, zdot_prev, None, None, self.g, None)
 
 
 class CDLNet_CSRf2(_CSRBase):
@@ -387,15 +409,19 @@ class CDLNet_CSRf2(_CSRBase):
         (v, zdot_prev, zdot_after) in (y, z_prev, z_after) at the primal's gates; the branch is forward's.  See
         CDLNet_CSR.jvp_recurrent."""
         y, v, mask_t, c = self._prep_tangent(y, v, sigma, mask, (("prev", z_prev, zdot_prev), ("after", z_after, zdot_after)))
+        return self._jvp_branch(y, v, mask_t, c, z_prev, zdot_prev, z_after, zdot_after)
+
+    def _tangent_branch(self, z_prev, zdot_prev, z_after=None, zdot_after=None):
+        """(t, A, B, neighbours): forward's four branches -- no neighbour (None), both (g1, g2), the previous one (g1), or the
+        next one alone, which takes the one-neighbour map around z_after with g2."""
         A, B = self._filters()
         if z_prev is None and z_after is None:
-            return loop.run_tangent(y, v, mask_t, c, self.t, A, B, self.s, codes=True)
+            return self.t, A, B, None
         if z_prev is not None and z_after is not None:
-            return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, z_after, zdot_after, self.t, self.g1, self.g2,
-                                        A, B, self.s)
+            return self.t, A, B, (z_prev, zdot_prev, z_after, zdot_after, self.g1, self.g2)
         if z_prev is not None:
-            return loop.run_csr_tangent(y, v, mask_t, c, z_prev, zdot_prev, None, None, self.t, self.g1, None, A, B, self.s)
-        return loop.run_csr_tangent(y, v, mask_t, c, z_after, zdot_after, None, None, self.t, self.g2, None, A, B, self.s)
+            return self.t, A, B, (z_prev, zdot_prev, None, None, self.g1, None)
+        return self.t, A, B, (z_after, zdot_after, None, None, self.g2, None)
 
 
 # ------------------------------------------------------------------------------------------ 3-D

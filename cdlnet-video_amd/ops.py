@@ -614,24 +614,28 @@ def analysis_prox(g: Geometry, x, w, alpha, zin, z_prev, lam, gam1, z_after=None
 
 
 def prox_csr_tangent(g: Geometry, ud, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None, zd_after=None,
-                     out=None):
+                     out=None, *, cmap=None, tslope=None):
     """Tangent of prox_csr at the primal (u, z_prev[, z_after]) along (ud, zd_prev, zd_after) (cdl_prox_csr_tangent): a nest
-    of gates read off the primal's intermediates; a None neighbour tangent is a zero one.  out may be ud."""
+    of gates read off the primal's intermediates; a None neighbour tangent is a zero one.  out may be ud.
+    cmap / tslope as analysis_prox's (lam, gam* then hold the constant parts): the gates are read at the primal's thresholds."""
+    cmap, tslope = _check_map_pair(g, cmap, tslope, 3)
     ud, u, z_prev, lam, gam1 = _dev(ud, "ud"), _dev(u, "u"), _dev(z_prev, "z_prev"), _dev(lam, "lam"), _dev(gam1, "gam1")
     z_after, gam2 = _opt(z_after, "z_after"), _opt(gam2, "gam2")
     zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
     _check_codes(g, ud=ud, u=u, z_prev=z_prev, z_after=z_after, zd_prev=zd_prev, zd_after=zd_after)
     _check_rows(g, lam=lam, gam1=gam1, gam2=gam2)
     out = torch.empty_like(ud) if out is None else _buf(out, "out", g.code_shape())
-    _call("cdl_prox_csr_tangent", g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out)
+    _call("cdl_prox_csr_tangent", g, ud, u, z_prev, z_after, lam, gam1, gam2, zd_prev, zd_after, out, cmap, tslope)
     return out
 
 
 def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z_after=None, gam2=None, zd_prev=None,
-                          zd_after=None, out=None):
+                          zd_after=None, out=None, *, cmap=None, tslope=None):
     """cdl_analysis followed by the tangent of the CSR map in place (cdl_analysis_prox_tangent): with ud = zin +
-    alpha*corr(x; w), returns Jprox(u; z_prev[, z_after]) (ud, zd_prev, zd_after) -- the bits of analysis, then prox_csr_tangent."""
+    alpha*corr(x; w), returns Jprox(u; z_prev[, z_after]) (ud, zd_prev, zd_after) -- the bits of analysis, then prox_csr_tangent.
+    cmap / tslope: as prox_csr_tangent's."""
     x, w = _dev(x, "x"), _dev(w, "w")
+    cmap, tslope = _check_map_pair(g, cmap, tslope, 3)
     zin, u, z_prev, z_after = _opt(zin, "zin"), _dev(u, "u"), _dev(z_prev, "z_prev"), _opt(z_after, "z_after")
     zd_prev, zd_after = _opt(zd_prev, "zd_prev"), _opt(zd_after, "zd_after")
     assert tuple(x.shape) == g.image_shape(), (x.shape, g.image_shape())
@@ -640,7 +644,7 @@ def analysis_prox_tangent(g: Geometry, x, w, alpha, zin, u, z_prev, lam, gam1, z
     out = _new(g.code_shape(), x.device) if out is None else _buf(out, "out", g.code_shape())
     ws, n = _analysis_workspace(g, x.device)
     _call("cdl_analysis_prox_tangent", g, x, w, alpha, zin, u, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
-          _opt(gam2, "gam2"), zd_prev, zd_after, out, ws, n)
+          _opt(gam2, "gam2"), zd_prev, zd_after, out, ws, n, cmap, tslope)
     return out
 
 
@@ -1510,11 +1514,14 @@ def tangent_backward(g: Geometry, vp, mask_p, A, B, gates, zd, rd, g_xp, g_zd=No
     return dA, dB
 
 
-def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_after, zd_prev, zd_after, A, B, us, keep):
+def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_after, zd_prev, zd_after, A, B, us, keep, *,
+                        cmap=None, tslope=None):
     """Tangent sweep of the CSR loop in one C call (cdl_csr_tangent_forward): us = the primal's u_0..u_{K-1} (its gates, with
     z_prev / z_after and the primal's lam / gam* (K,N,M)); zd_prev / zd_after (nullable) the neighbours' tangents.  Returns
-    (xdp, zd_K, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else []."""
+    (xdp, zd_K, zd, rd): with keep the K tangent codes and K-1 tangent residuals, else [].
+    cmap (N,1,*code_spatial) with tslope (K,3,M): the primal's noise-level map (ista_forward), lam / gam* the constant parts."""
     K = len(A)
+    cmap, tslope = _check_map_pair(g, cmap, tslope, 3 * K)
     vp, mask_p = _dev(vp, "vp"), _opt(mask_p, "mask")
     A = [_dev(w, "A") for w in A]
     B = [_dev(w, "B") for w in B]
@@ -1528,7 +1535,7 @@ def csr_tangent_forward(g: Geometry, vp, mask_p, lam, gam1, gam2, z_prev, z_afte
     xdp = _new(g.image_shape(), dev)
     ws, n = ista_scratch(g, dev)
     _call("cdl_csr_tangent_forward", g, K, vp, mask_p, z_prev, z_after, _dev(lam, "lam"), _dev(gam1, "gam1"),
-          _opt(gam2, "gam2"), zd_prev, zd_after, A, B, us, zd, rd, xdp, ws, n)
+          _opt(gam2, "gam2"), zd_prev, zd_after, A, B, us, zd, rd, xdp, ws, n, cmap, tslope)
     return xdp, zd[K - 1], (zd if keep else []), (rd if keep else [])
 
 

@@ -7,6 +7,7 @@ carry the sparse code of one frame into the call for its neighbour.
 
 `csr_step` is one call of a CSR net on the surface that takes what `net(...)` refuses: a
 noise-level map as sigma, and y / sigma that require grad.  The drivers go through it for the frames whose sigma is a map.
+`csr_jvp_step` is the same surface for `jvp_recurrent`: the call with its tangent, sigma a map or not (section 38).
 """
 import torch
 
@@ -68,6 +69,28 @@ def csr_step(net, y, z_prev=None, z_after=None, sigma=None, mask=1):
     if z_prev is not None:
         return functional.ista_csr(y, z_prev, None, sigma, mask, net.t, net.g1, None, A, B, net.s)
     return functional.ista_csr(y, z_after, None, sigma, mask, net.t, net.g2, None, A, B, net.s)
+
+
+def csr_jvp_step(net, y, v, z_prev=None, zdot_prev=None, z_after=None, zdot_after=None, sigma=None, mask=1):
+    """(xhat, xdot, z, zdot): one call of a CDLNet_CSR / CDLNet_CSRf2 and its derivative along (v, zdot_prev, zdot_after) in
+    (y, z_prev, z_after) at the primal's gates -- net.jvp_recurrent on the surface where sigma may be a noise-level map (any
+    tensor that broadcasts to (N,1,*code grid); t, g1 and g2 all follow it, and the gates are the ones csr_step's primal
+    takes).  Banks and branch are picked as csr_step / jvp_recurrent pick them.  All four outputs are
+    differentiable in the parameters and in the neighbour codes and tangents; gradients with respect to y, v, sigma or mask
+    are not produced.  With a float or per-sample sigma it returns the bits of net.jvp_recurrent(...)."""
+    from . import functional
+    from .net import CDLNet_CSR, CDLNet_CSRf2, _code_grid, _mask_tensor, _noise_scale
+    functional._no_mask_gradient(mask)
+    if not isinstance(net, (CDLNet_CSR, CDLNet_CSRf2)):
+        raise TypeError(f"csr_jvp_step: expected a CDLNet_CSR or CDLNet_CSRf2, got {type(net).__name__}")
+    if isinstance(net, CDLNet_CSR) and (z_after is not None or zdot_after is not None):
+        raise ValueError("csr_jvp_step: CDLNet_CSR has no z_after")
+    # jvp_recurrent's own checks and branch pick (net._check_tangent, net._jvp_branch); only forward's refusal of a map is
+    # not taken over
+    net._check_tangent(y, v, sigma, mask, (("prev", z_prev, zdot_prev), ("after", z_after, zdot_after)), who="csr_jvp_step")
+    y, v = y.to(torch.float32), v.to(torch.float32)
+    c = _noise_scale(sigma, net.adaptive, y.shape[0], y.device, _code_grid(y.shape[2:], net.s))
+    return net._jvp_branch(y, v, _mask_tensor(mask, y), c, z_prev, zdot_prev, z_after, zdot_after)
 
 
 def _call(net, y, codes, sigma, mask):

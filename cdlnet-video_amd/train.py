@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import temporal
 from .net import CDLNet, CDLNet_CSR, CDLNet_CSRf2, CDLNetVideo, GDLNet
 from .parallel import phase_consensus
-from .utils import awgn, gen_bayer_mask
+from .utils import awgn, gen_bayer_mask, sigma_to_code_grid
 
 MODEL_TYPES = {
     "CDLNet": CDLNet,
@@ -78,7 +78,30 @@ def init_model(args, device=torch.device("cpu")):
     return net, opt, sched, epoch0
 
 
-def mcsure_loss(net, obsrv, xhat, sigma, mask=1, h=1e-3, generator=None, b=None):
+# Noise levels with spatial extent.  The nets take sigma on the CODE grid, the divergence weight
+# (level/255)^2 * b * xdot lives on the IMAGE grid: the SURE forms take the image-resolution level as `noise=` beside the
+# net's `sigma`, and the steps derive the one from the other (utils.sigma_to_code_grid).
+def _has_spatial_extent(level):
+    return torch.is_tensor(level) and level.dim() > 2 and any(d > 1 for d in level.shape[2:])
+
+
+def _divergence_weight(sigma, noise, image):
+    """(level/255)^2 of the SURE divergence term, shaped against `image`: from `noise` (the noise standard deviation on the
+    255 scale at image resolution) when given, else from the net's `sigma` -- today's expression."""
+    if noise is not None:
+        return (noise / 255.0) ** 2
+    if _has_spatial_extent(sigma) and any(d not in (1, n) for d, n in zip(sigma.shape[2:], image.shape[2:])):
+        raise ValueError(f"sigma of shape {tuple(sigma.shape)} is a noise-level map on the code grid of a stride > 1 net; the "
+                         f"divergence term needs the level at the image resolution {tuple(image.shape[2:])}: pass it as noise=")
+    return (sigma / 255.0) ** 2
+
+
+def _net_sigma(net, level):
+    """What the net takes as `sigma` for a level awgn drew: a level with spatial extent goes onto the net's code grid."""
+    return sigma_to_code_grid(level, net.s) if _has_spatial_extent(level) else level
+
+
+def mcsure_loss(net, obsrv, xhat, sigma, mask=1, h=1e-3, generator=None, b=None, *, noise=None):
     """Monte-Carlo SURE objective of train.py:87-93: data fidelity to the OBSERVATION plus a divergence
     estimate from one extra forward at obsrv + h*b, b ~ N(0, I):
         mean((obsrv - xhat)^2) + 2 * mean((sigma/255)^2 * b * (net(obsrv + h b) - xhat)) / h
@@ -91,28 +114,30 @@ def mcsure_loss(net, obsrv, xhat, sigma, mask=1, h=1e-3, generator=None, b=None)
     "split4")` adds the lo * lo products on the fused 2-D path; measured, it does not change that (the operand
     truncation, not the dropped product, is the floor), so it is not selected here.  `with loop.precision_scope("fp32")`
     around the training step runs both passes and their backward on the fp32 VALU kernels (6e-6 instead of 7e-5 per step,
-    several times slower); the caller chooses."""
+    several times slower); the caller chooses.
+    noise (keyword-only): the noise standard deviation on the 255 scale at image resolution, used for the divergence weight
+    in place of sigma -- needed when sigma is a code-grid map of a stride > 1 net."""
     if b is None:
         dev = generator.device if generator is not None else obsrv.device
         b = torch.randn(obsrv.shape, device=dev, dtype=obsrv.dtype, generator=generator).to(obsrv.device)
     xhat_b, _ = net(obsrv.clone() + h * b, sigma, mask=mask)
-    s2 = (sigma / 255.0) ** 2
+    s2 = _divergence_weight(sigma, noise, obsrv)
     div = 2.0 * torch.mean(s2 * b * (xhat_b - xhat)) / h
     return torch.mean((obsrv - xhat) ** 2) + div
 
 
-def sure_loss(net, obsrv, sigma, mask=1, generator=None, b=None):
+def sure_loss(net, obsrv, sigma, mask=1, generator=None, b=None, *, noise=None):
     """SURE objective with the divergence term from the exact directional derivative (net.jvp) instead of a finite
     difference: with (xhat, xdot) = net.jvp(obsrv, b, sigma, mask), b ~ N(0, I) drawn as mcsure_loss draws it,
         mean((obsrv - xhat)^2) + 2 * mean((sigma/255)^2 * b * xdot)
     xdot = J(obsrv) b at the supports of the primal codes: what h -> 0 of mcsure_loss converges to, with no step size,
     no 1/h in the gradient, and the same number of sweeps (two forward, two reverse).
-    Returns (loss, xhat)."""
+    noise: as mcsure_loss's.  Returns (loss, xhat)."""
     if b is None:
         dev = generator.device if generator is not None else obsrv.device
         b = torch.randn(obsrv.shape, device=dev, dtype=obsrv.dtype, generator=generator).to(obsrv.device)
     xhat, xdot = net.jvp(obsrv, b, sigma, mask=mask)
-    s2 = (sigma / 255.0) ** 2
+    s2 = _divergence_weight(sigma, noise, obsrv)
     return torch.mean((obsrv - xhat) ** 2) + 2.0 * torch.mean(s2 * b * xdot), xhat
 
 
@@ -124,21 +149,24 @@ def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, proje
     `grad_sync` is a callable run between backward and clipping (parallel.GradientBucket.sync).  `loss_fn(xhat, batch)`
     replaces the MSE (trainmri.py's `combmse`: a loss.CombinedLossWithSSIM); `mcsure` takes precedence over it.
     `mcsure`: False, True (the reference's finite-difference MC-SURE, mcsure_loss) or "exact" (sure_loss: the divergence
-    from net.jvp).
-    Returns (loss tensor, sigma).
+    from net.jvp).  A `noise_std` tensor with spatial extent (an image-resolution level map, which awgn takes) reaches the
+    net on its code grid (utils.sigma_to_code_grid) and the SURE forms as `noise=`.
+    Returns (loss tensor, sigma): sigma as awgn returned it.
     """
     if isinstance(mcsure, str) and mcsure != "exact":          # any other value keeps its truthiness
         raise ValueError(f"mcsure must be False, True or 'exact', got {mcsure!r}")
     mask = gen_bayer_mask(batch) if demosaic else 1
-    noisy, sigma = awgn(batch, noise_std, generator)
+    noisy, level = awgn(batch, noise_std, generator)
+    sigma = _net_sigma(net, level)
+    noise = level if sigma is not level else None
     obsrv = mask * noisy
     opt.zero_grad(set_to_none=True)
     if isinstance(mcsure, str):
-        loss, xhat = sure_loss(net, obsrv, sigma, mask=mask, generator=generator)
+        loss, xhat = sure_loss(net, obsrv, sigma, mask=mask, generator=generator, noise=noise)
     else:
         xhat, _ = net(obsrv, sigma, mask=mask)
         if mcsure:
-            loss = mcsure_loss(net, obsrv, xhat, sigma, mask=mask, generator=generator)
+            loss = mcsure_loss(net, obsrv, xhat, sigma, mask=mask, generator=generator, noise=noise)
         elif loss_fn is not None:
             loss = loss_fn(xhat, batch)
         else:
@@ -151,7 +179,7 @@ def train_step(net, opt, batch, noise_std, clip_grad=None, demosaic=False, proje
     opt.step()
     if project and hasattr(net, "project"):
         net.project()
-    return loss.detach(), sigma
+    return loss.detach(), level
 
 
 # ------------------------------------------------------------------------------------------ CSR clip steps
@@ -212,7 +240,7 @@ def _draw_b(frames, generator):
     return [torch.randn(y.shape, device=dev, dtype=y.dtype, generator=generator).to(y.device) for y in frames]
 
 
-def sure_loss_clip(net, frames, sigmas, b=None, generator=None):
+def sure_loss_clip(net, frames, sigmas, b=None, generator=None, *, noise=None):
     """Exact SURE objective of a clip step: the chain of clip_forward run with `jvp_recurrent`, one direction b_t ~ N(0, I)
     per distinct frame (drawn as sure_loss draws b, in frame order), the same b_t at every call on frame t, and the code
     tangent zdot carried from call to call next to the code:
@@ -220,14 +248,17 @@ def sure_loss_clip(net, frames, sigmas, b=None, generator=None):
     over the calls that enter the supervised loss.  The chain maps ALL frames to all outputs jointly; sum_t b_t . xdot_t with
     xdot the derivative along (b_0, .., b_{D-1}) at once is the trace estimator of that joint map's Jacobian -- which needs
     the dependence of xhat_t on y_s (s != t) through the neighbour codes, hence zdot.
-    Returns (loss, [xhat_t])."""
+    A frame whose sigma is a noise-level map goes through temporal.csr_jvp_step (the rule of _net_call; section 38).
+    noise: a list per frame of mcsure_loss's `noise`.  Returns (loss, [xhat_t])."""
     D = len(frames)
     if b is None:
         b = _draw_b(frames, generator)
-    if D == 2:
-        jvp = lambda t, prev, after: net.jvp_recurrent(frames[t], b[t], prev[0], prev[1], sigmas[t])
-    else:
-        jvp = lambda t, prev, after: net.jvp_recurrent(frames[t], b[t], prev[0], prev[1], after[0], after[1], sigmas[t])
+
+    def jvp(t, prev, after):
+        pairs = prev if D == 2 else prev + after
+        if temporal._is_sigma_map(sigmas[t], frames[t]):
+            return temporal.csr_jvp_step(net, frames[t], b[t], *pairs, sigma=sigmas[t])
+        return net.jvp_recurrent(frames[t], b[t], *pairs, sigmas[t])
     none = (None, None)
 
     def call(t, prev, after):
@@ -238,27 +269,40 @@ def sure_loss_clip(net, frames, sigmas, b=None, generator=None):
     loss = 0.0
     for t in range(D):
         xhat, xdot = outs[t]
-        s2 = (sigmas[t] / 255.0) ** 2
+        s2 = _divergence_weight(sigmas[t], noise[t] if noise is not None else None, frames[t])
         loss = loss + torch.mean((frames[t] - xhat) ** 2) + 2.0 * torch.mean(s2 * b[t] * xdot)
     return loss, [outs[t][0] for t in range(D)]
 
 
-def mcsure_loss_clip(net, frames, sigmas, xhats, h=1e-3, b=None, generator=None):
-    """The finite-difference form of sure_loss_clip (mcsure_loss over the chain): a second chain at y_t + h b_t."""
+def mcsure_loss_clip(net, frames, sigmas, xhats, h=1e-3, b=None, generator=None, *, noise=None):
+    """The finite-difference form of sure_loss_clip (mcsure_loss over the chain): a second chain at y_t + h b_t.
+    noise: as sure_loss_clip's."""
     if b is None:
         b = _draw_b(frames, generator)
     xb = clip_forward(net, [y.clone() + h * bt for y, bt in zip(frames, b)], sigmas)
     loss = 0.0
-    for y, s, bt, xhat, xhat_b in zip(frames, sigmas, b, xhats, xb):
-        loss = loss + torch.mean((y - xhat) ** 2) + 2.0 * torch.mean((s / 255.0) ** 2 * bt * (xhat_b - xhat)) / h
+    for t, (y, s, bt, xhat, xhat_b) in enumerate(zip(frames, sigmas, b, xhats, xb)):
+        s2 = _divergence_weight(s, noise[t] if noise is not None else None, y)
+        loss = loss + torch.mean((y - xhat) ** 2) + 2.0 * torch.mean(s2 * bt * (xhat_b - xhat)) / h
     return loss
 
 
 def _clip_noise(clip, noise_std, generator):
-    """awgn per frame, in frame order (traincsr.py:196-197, 251-253)."""
+    """awgn per frame, in frame order (traincsr.py:196-197, 251-253): (clean, noisy, levels).  A `noise_std` tensor shaped
+    like the clip (B,1,D,H,W) holds one level map per frame; any other applies to every frame as awgn takes it."""
     clean = [clip[:, :, d] for d in range(clip.shape[2])]
-    noisy, sigmas = zip(*(awgn(x, noise_std, generator) for x in clean))
+    per_frame = torch.is_tensor(noise_std) and noise_std.dim() == clip.dim()
+    nstd = [noise_std[:, :, d] if per_frame else noise_std for d in range(len(clean))]
+    noisy, sigmas = zip(*(awgn(x, n, generator) for x, n in zip(clean, nstd)))
     return clean, list(noisy), list(sigmas)
+
+
+def _clip_sigmas(net, levels):
+    """(sigmas the net takes, `noise=` of the SURE forms) for the levels awgn drew: levels with spatial extent go onto the
+    code grid for the net and stay at image resolution for the divergence weight."""
+    if not any(_has_spatial_extent(l) for l in levels):
+        return levels, None
+    return [_net_sigma(net, l) for l in levels], [l if _has_spatial_extent(l) else None for l in levels]
 
 
 def _clip_mse(xhats, clean):
@@ -269,27 +313,31 @@ def _clip_mse(xhats, clean):
 def eval_step_clip(net, clip, noise_std, generator=None):
     """The val / test body of traincsr.py's train_model: (loss, sigmas, mse) of the supervised chain, no step."""
     D = _clip_depth(net, clip)
-    clean, noisy, sigmas = _clip_noise(clip, noise_std, generator)
-    per, mse = _clip_mse(clip_forward(net, noisy, sigmas), clean)
-    return sum(per[1:], per[0]), sigmas, mse
+    clean, noisy, levels = _clip_noise(clip, noise_std, generator)
+    per, mse = _clip_mse(clip_forward(net, noisy, _clip_sigmas(net, levels)[0]), clean)
+    return sum(per[1:], per[0]), levels, mse
 
 
 def train_step_clip(net, opt, clip, noise_std, clip_grad=None, project=True, grad_sync=None, generator=None, mcsure=False):
     """One optimiser step of a CSR net on a clip (B, C, D, H, W) (traincsr.py:192-217 / 247-273): awgn per frame -> the
     reference's chain of calls -> sum of the per-frame MSEs -> backward -> [all-reduce] -> clip -> Adam -> project.
     `mcsure`: False (supervised), True (finite differences over the chain, mcsure_loss_clip) or "exact" (sure_loss_clip).
-    Returns (loss, sigmas, mse): mse the mean of the per-frame MSEs against the clean frames (traincsr.py:217, 273)."""
+    A `noise_std` tensor with spatial extent (image-resolution level maps: _clip_noise) reaches the net on its code grid and
+    the SURE forms as `noise=`.
+    Returns (loss, sigmas, mse): sigmas as awgn returned them, mse the mean of the per-frame MSEs against the clean frames
+    (traincsr.py:217, 273)."""
     if isinstance(mcsure, str) and mcsure != "exact":
         raise ValueError(f"mcsure must be False, True or 'exact', got {mcsure!r}")
     _clip_depth(net, clip)
-    clean, noisy, sigmas = _clip_noise(clip, noise_std, generator)
+    clean, noisy, levels = _clip_noise(clip, noise_std, generator)
+    sigmas, noise = _clip_sigmas(net, levels)
     opt.zero_grad(set_to_none=True)
     if isinstance(mcsure, str):
-        loss, xhats = sure_loss_clip(net, noisy, sigmas, generator=generator)
+        loss, xhats = sure_loss_clip(net, noisy, sigmas, generator=generator, noise=noise)
     else:
         xhats = clip_forward(net, noisy, sigmas)
         if mcsure:
-            loss = mcsure_loss_clip(net, noisy, sigmas, xhats, generator=generator)
+            loss = mcsure_loss_clip(net, noisy, sigmas, xhats, generator=generator, noise=noise)
         else:
             per = [torch.mean((xh - x) ** 2) for xh, x in zip(xhats, clean)]
             loss = sum(per[1:], per[0])
@@ -301,7 +349,7 @@ def train_step_clip(net, opt, clip, noise_std, clip_grad=None, project=True, gra
     opt.step()
     if project and hasattr(net, "project"):
         net.project()
-    return loss.detach(), sigmas, _clip_mse(xhats, clean)[1]
+    return loss.detach(), levels, _clip_mse(xhats, clean)[1]
 
 
 # ------------------------------------------------------------------------------------------ fit loop
@@ -364,6 +412,9 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     Rank 0 alone writes logs and checkpoints into `save_dir` (one node: the directory is shared); a
     barrier orders its writes before the other ranks' reads, and a backtrack reloads the SAME file on
     every rank, so replicas, optimiser states and learning rates stay identical.
+    `noise_std`: a number, a `(lo, hi)` range, or a tensor -- an image-resolution level map that broadcasts against a batch
+    ((B,1,H,W); for clips also (B,1,D,H,W), one map per frame), handed to awgn unwrapped in every phase (no level is drawn);
+    the net then takes it on its code grid and the SURE forms as `noise=` (train_step / train_step_clip).
     `combmse` (trainmri.py / train3d.py): the train phase's loss is `loss_fn`, by default
     loss.CombinedLossWithSSIM(1.0, 0.01, 0.1) (VGG16 weights from the default local file); a `loss_fn` given without
     `combmse` is used the same way.  `mcsure` (True: finite differences; "exact": net.jvp, see train_step) takes
@@ -388,7 +439,8 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
     if save_dir is None:
         raise ValueError("fit needs save_dir (checkpoints drive the backtracking)")
     os.makedirs(save_dir, exist_ok=True)
-    if not isinstance(noise_std, (list, tuple)):
+    level_map = torch.is_tensor(noise_std)               # a level map (awgn's tensor form): every phase takes it as it is
+    if not level_map and not isinstance(noise_std, (list, tuple)):
         noise_std = (noise_std, noise_std)
     if combmse and loss_fn is None and not isinstance(net, (CDLNet_CSR, CDLNet_CSRf2)):
         from .loss import CombinedLossWithSSIM
@@ -415,10 +467,12 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
                 continue
             if phase not in loaders or loaders[phase] is None:
                 continue
-            phase_nstd = noise_std if phase == "train" else (noise_std[0] + noise_std[1]) / 2.0
+            phase_nstd = noise_std if (phase == "train" or level_map) else (noise_std[0] + noise_std[1]) / 2.0
             psnr, nb, bad = 0.0, 0, False
             for batch in loaders[phase]:
                 batch = batch.to(device)
+                if level_map:
+                    phase_nstd = phase_nstd.to(device)
                 mse_t = None
                 if clips and phase == "train":
                     loss_t, _, mse_t = train_step_clip(net, opt, batch, phase_nstd, clip_grad=clip_grad, grad_sync=grad_sync,
@@ -433,7 +487,7 @@ def fit(net, opt, loaders, sched=None, epochs=1, device=torch.device("cpu"), sav
                     with torch.no_grad():
                         mask = gen_bayer_mask(batch) if demosaic else 1
                         noisy, sigma = awgn(batch, phase_nstd, generator)
-                        xhat, _ = net(mask * noisy, sigma, mask=mask)
+                        xhat, _ = net(mask * noisy, _net_sigma(net, sigma), mask=mask)
                         loss_t = torch.mean((batch - xhat) ** 2)
                 loss = float(loss_t)
                 if verbose and phase == "train":

@@ -256,22 +256,27 @@ int cdl_analysis_prox(const cdl_geom *g, const float *x, const float *w, float a
  *   prox_CSR:     Ga = st_dx(a, lam*gam1), Gm = st_dx(m, lam):              out = Gm ? (Ga ? ud : zd_prev) : 0
  *   prox_CSR_f2:  Ga = st_dx(a, t1), Gb = st_dx(b, t2), Gm = st_dx(m, lam): out = Gm ? (Gb ? (Ga ? ud - zd_prev : 0) : zd_after) : 0
  * evaluated as selects (a NaN in a dead branch does not leak); no threshold enters a value.  ud: the tangent of u;
- * zd_prev / zd_after (nullable): the neighbours' tangents, NULL = zero (a constant neighbour).  out may alias ud. */
+ * zd_prev / zd_after (nullable): the neighbours' tangents, NULL = zero (a constant neighbour).  out may alias ud.
+ * Noise-level map (both NULL: none, one without the other: CDL_EINVAL): cmap (N, code pixels) with
+ * tslope (3,M) as in cdl_analysis_prox, lam / gam1 / gam2 the constant parts -- the gates are read at the thresholds the
+ * primal's epilogue formed, lam[n,m] + cmap[n,pix]*tslope[0,m] etc., the product rounded before the sum. */
 int cdl_prox_csr_tangent(const cdl_geom *g, const float *ud, const float *u, const float *z_prev,
                          const float *z_after /*nullable*/, const float *lam, const float *gam1,
                          const float *gam2 /*nullable iff z_after is*/, const float *zd_prev /*nullable*/,
-                         const float *zd_after /*nullable*/, float *out, void *stream);
+                         const float *zd_after /*nullable*/, float *out, const float *cmap /*nullable*/,
+                         const float *tslope /*3*M, nullable*/, void *stream);
 
 /* The tangent step of one iteration: ud = zin + alpha*corr(x ; w) (cdl_analysis into out), then
  * out = Jprox(u; z_prev[, z_after])(ud, zd_prev, zd_after) in place (cdl_prox_csr_tangent): two launches, the bits of the
  * two calls.  (As a branch of the kernels' CSR epilogue it slowed the primal epilogue: DESIGN.md section 22.)
- * workspace: as cdl_analysis's (NULL: VALU). */
+ * workspace: as cdl_analysis's (NULL: VALU).  cmap / tslope: as cdl_prox_csr_tangent's (the analysis takes no map). */
 int cdl_analysis_prox_tangent(const cdl_geom *g, const float *x, const float *w, float alpha,
                               const float *zin /*nullable*/, const float *u, const float *z_prev,
                               const float *z_after /*nullable*/, const float *lam, const float *gam1,
                               const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
                               const float *zd_after /*nullable*/, float *out, float *workspace /*nullable*/,
-                              size_t workspace_floats, void *stream);
+                              size_t workspace_floats, const float *cmap /*nullable*/,
+                              const float *tslope /*3*M, nullable*/, void *stream);
 
 /* Reverse of cdl_prox_csr as autograd differentiates the reference expression (sign() has zero
  * gradient): gu = dL/du (may alias gz); gz_prev / gz_after (nullable) are ACCUMULATED into, because a
@@ -522,13 +527,16 @@ int cdl_tangent_backward(const cdl_geom *g, int K, const float *vp, const float 
  * Per iteration cdl_synthesis + cdl_analysis_prox_tangent.  zd: K code buffers,
  * rd: K-1 thin ones (two each suffice when nothing is kept).  The reverse sweep is cdl_ista_backward's CSR branch with
  * yp -> vp, z -> zd, r -> rd, the primal's u / lam / gam*, c = NULL: gz_prev / gz_after then receive dL/dzd_prev, dL/dzd_after
- * and dt / dg1 / dg2 sums nobody reads (the gates are piecewise constant: no threshold gradient through the tangent). */
+ * and dt / dg1 / dg2 sums nobody reads (the gates are piecewise constant: no threshold gradient through the tangent).
+ * Noise-level map (both NULL: none): cmap (N, code pixels) with tslope (K,3,M) as in cdl_ista_forward's
+ * CSR branch, lam / gam1 / gam2 the constant parts; the reverse sweep takes the same cmap / tslope, dcmap = NULL. */
 int cdl_csr_tangent_forward(const cdl_geom *g, int K, const float *vp, const float *mask /*nullable*/,
                             const float *z_prev, const float *z_after /*nullable*/, const float *lam,
                             const float *gam1, const float *gam2 /*nullable*/, const float *zd_prev /*nullable*/,
                             const float *zd_after /*nullable*/, const float *const *wA, const float *const *wB,
                             const float *const *u, float *const *zd, float *const *rd, float *xdp, float *scratch,
-                            size_t scratch_floats, void *stream);
+                            size_t scratch_floats, const float *cmap /*nullable*/,
+                            const float *tslope /*K*3*M, nullable*/, void *stream);
 
 /* model/solvers.py:24-28 (uball_project) applied by net.py:72-73,189-190: every filter
  * (consecutive `flen` floats) with l2 norm > 1 is scaled onto the unit sphere, in place, for `nbanks` banks of identical
