@@ -1,9 +1,9 @@
 """The generic operators after their tier ladder moved into cdl_operators.hip and the dense tier's host side was folded
 (DESIGN.md section 37), against the record made on the commit before (tools/make_golden_operator_ladder_parent_bits.py): the
 same launch sites and every value byte for byte -- the change moves host text only, so there is no tolerance.  The cases are
-every (tier, key) at which test_gpu_dispatch.py pins a launch site, through the calls it makes there, and the dense tier,
-which has no cell test: cdl_dense_conv in both roles, cdl_dense_wgrad, the ResidualBlock and the perceptual loss (every form
-of cdl_dense_vgg)."""
+every (tier, key) at which test_gpu_dispatch.py pins a launch site, through the calls it makes there, and the dense tier
+(held to its own past output here, to the float64 model cell by cell in test_gpu_dense_cells.py): cdl_dense_conv in both
+roles, cdl_dense_wgrad, the ResidualBlock and the perceptual loss (every form of cdl_dense_vgg)."""
 import functools
 import importlib.util
 import os

@@ -13,6 +13,7 @@ import torch
 
 import perceptual_restate as R
 from gpu_util import check, log
+from vgg_scratch_util import scratch_views as _scratch_views
 
 pytestmark = pytest.mark.gpu
 
@@ -87,44 +88,6 @@ def test_value_and_gradients(shape):
     l_dx, l_dy = _l2(oc.grad, o64.grad), _l2(tc.grad, t64.grad)
     log(f"perceptual dx / dy {shape} vs free restatement: max {e_dx:.3e} / {e_dy:.3e}, l2 {l_dx:.3e} / {l_dy:.3e}")
     assert l_dx < 5e-2 and l_dy < 5e-2
-
-
-def _scratch_views(scr, P, H, W, grads):
-    """The activations cdl_vgg_forward keeps, read from its scratch (the layout of csrc/cdl_vgg.hip, restated)."""
-    up = lambda n: (n + 63) // 64 * 64                                          # noqa: E731
-    H2, W2 = H // 2, W // 2
-    H4, W4 = H2 // 2, W2 // 2
-    px0, px1, px2 = P * H * W, P * H2 * W2, P * H4 * W4
-    frag = 0
-    for i, o in ((64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256)):
-        for a, b in ((i, o), (o, i)):
-            mtt = 2 * math.ceil(math.ceil(b / 32) / 2)
-            frag = max(frag, math.ceil(a / 16) * 9 * mtt * 128 * 4)
-    part = up(frag) + 576
-    nparts = P * math.ceil(W4 / 32) * math.ceil(H4 / 16) * 4
-    fy = part + up(2 * nparts)
-    f3 = up(256 * px2)
-    sx = fy + f3
-    sy = sx + f3
-    base = sy + (f3 if grads & 2 else 0)
-
-    def one(q):
-        views = {}
-        for name, n, shape, byte in (("a1", 64 * px0, (P, 64, H, W), False), ("p1", 64 * px1, (P, 64, H2, W2), False),
-                                     ("am1", 64 * px1, (P, 64, H2, W2), True), ("a3", 128 * px1, (P, 128, H2, W2), False),
-                                     ("p2", 128 * px2, (P, 128, H4, W4), False), ("am2", 128 * px2, (P, 128, H4, W4), True),
-                                     ("a5", 256 * px2, (P, 256, H4, W4), False), ("a6", 256 * px2, (P, 256, H4, W4), False)):
-            if byte:
-                views[name] = scr[q:q + (n + 3) // 4].view(torch.uint8)[:n].reshape(shape)
-                q += up((n + 3) // 4)
-            else:
-                views[name] = scr[q:q + n].reshape(shape)
-                q += up(n)
-        return views, q
-
-    s0, end = one(base)
-    s1 = one(end)[0] if grads & 2 else None
-    return s0, s1, scr[fy:fy + 256 * px2].reshape(P, 256, H4, W4)
 
 
 def _gates_of(v, f):
