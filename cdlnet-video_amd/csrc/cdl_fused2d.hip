@@ -109,7 +109,8 @@ struct FusedParams {
     int do_synth;            // 0: skip the synthesis-like half (last backward stage)
     CDL_DBG_FIELD(int dbg;)  // probe build only (CDL_FUSED_DEBUG): 1 no stores, 2 no synthesis, 32 no LDS adds, 64 no ST,
                              // 4 no analysis MFMAs, 8 no thin loads (both operands), 16 no fat loads, 128 no per-tile phase
-                             // behind the row loop (patch write-out, staging stores); results are wrong
+                             // behind the row loop (patch write-out, staging stores), 256 no threshold partials (neither the
+                             // per-element sums nor their per-tile transposition: dtau comes out 0); results are wrong
     int N, H, W, tilesX, tilesY;
     int rev;                 // walk the tiles from the last to the first (see "snake order" at the sweeps)
     const float *r2;         // reverse stage with DA: (N,H,W) thin operand of dA_k = alpha * du_k (x) im2col(r2) (r_k or yp)
@@ -226,6 +227,18 @@ __global__ void k_prep_batch(PrepBatch b, uint4 *__restrict__ out, int frag_uint
 #endif
 #ifndef CDL_POL_WGRAD_FAT_LD
 #define CDL_POL_WGRAD_FAT_LD 2
+#endif
+// The reverse stage's row loop, each piece with a -D override for A/B builds like the policies above:
+// the threshold partials written into the synthesis k-steps, their per-tile transposition by DPP instead of through LDS, and
+// the next row block's fat inputs issued behind the epilogue of this one.  None of them changes a value.
+#ifndef CDL_STAGE_TSUM_SHADOW
+#define CDL_STAGE_TSUM_SHADOW 1
+#endif
+#ifndef CDL_STAGE_TSUM_DPP
+#define CDL_STAGE_TSUM_DPP 1
+#endif
+#ifndef CDL_STAGE_PREFETCH
+#define CDL_STAGE_PREFETCH 1
 #endif
 struct CachePolicy {
     static constexpr int stage_fat_ld = CDL_POL_STAGE_FAT_LD;   // k_stage: z_k / du_{k+1}, 16 B per lane (LAY_BLK)
@@ -344,11 +357,20 @@ __device__ __forceinline__ void blk_store4(float a0, float a1, float a2, float a
     }
 }
 
-// LaneTransposeSum (cdl_wave_dev.h) with the two halves of each of 16 totals joined
+// a or b by a compile-time flag, where the two have different types
+template <bool FIRST, class A, class B>
+__device__ __forceinline__ decltype(auto) pick_ref(A &a, B &b)
+{
+    if constexpr (FIRST) return (a);
+    else return (b);
+}
+
+// LaneTransposeSum (cdl_wave_dev.h; the DPP form: called once per tile by every lane of every wave) with the two halves of
+// each of 16 totals joined
 template <int N>
 __device__ __forceinline__ float lane_transpose_sum(const float (&v)[N], int c)
 {
-    float r = LaneTransposeSum<N>::run(v, c);
+    float r = LaneTransposeSum<N, CDL_STAGE_TSUM_DPP != 0>::run(v, c);
     if (N == 16) r += __shfl_xor(r, 16, 64);           // lanes c and c^16 hold halves of the same index
     return r;
 }
@@ -783,6 +805,25 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
 #pragma unroll
         for (int i = 0; i < MT * 16; ++i) tsum_w[i] = 0.0f;
     }
+    // Reverse: one element's threshold partial, gt = -sign(z') * du.  Each element has its own accumulator, visited once per row
+    // block in row-block order, so WHERE in the row block the update issues changes no bit.  TS_SHADOW: the updates of the 8
+    // elements a synthesis k-step converts are written inside that k-step.  In the epilogue the compiler carried them round to
+    // the head of the row loop, in front of the fat loads with the matrix pipe idle; from here it sinks them behind the last
+    // synthesis MFMA (it does not interleave them), where the next block's loads are in flight (measured
+    // together with PREFETCH below -- without it this form is the slower one).  A bf16-stored du_k sums the value
+    // BEFORE its rounding, which the synthesis no longer has: those instances keep the update in the epilogue.  So do the map
+    // modes: with a second set of partials live across the dA_k products their dA_k instances no longer fit 512 registers.
+    constexpr bool TS_SHADOW = CDL_STAGE_TSUM_SHADOW && MODE == MODE_BWD && LOUT != LAY_BLK16 && !MAP;
+    auto tsum_add = [&](int R, int v, float zz, unsigned sgb, float cm) __attribute__((always_inline)) {
+        if CDL_DBG(p.dbg, 256) return;
+        // zz where the sign bit of z' is set, -zz where it is clear: the complement of that bit, moved onto zz's sign (a shift, an
+        // and, an xor; as a select it was a compare into a lane mask -- 32 scalar register pairs -- and a conditional move).
+        // An off-support element is +0.0f and comes out -0.0f, as from the negation.
+        const unsigned flip = (~sgb << (31 - (16 * R + v))) & 0x80000000u;
+        const float gt = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, zz) ^ flip);
+        tsum[16 * R + v] += gt;
+        if constexpr (MAP_BWD) tsum_w[16 * R + v] = fmaf(cm, gt, tsum_w[16 * R + v]);
+    };
     // thresholds are >= 0 whenever project() runs (net.py:70); a negative one (3-D trainer, never projected) sends
     // the whole tile through the general shrinkage -- wave-uniform, so the common case pays 3 instructions per
     // element (u - clamp(u, -t, t)) instead of 10
@@ -804,20 +845,9 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
     constexpr int EB_IN = LIN == LAY_BLK16 ? 8 : 16, EB_OUT = LOUT == LAY_BLK16 ? 8 : 16;
     const int lane_blk_in = (h * 32 + c) * EB_IN, lane_blk_out = (h * 32 + c) * EB_OUT;
 
-#pragma unroll 1
-    for (int b = 0; b < RB; ++b) {
-        const int yl = wyi * RB + b;         // tile-local image row of this block
-        const int y = ty0 + yl;
-        const bool valid = xok && (y < p.H);
-        const int voff = valid ? lane_off + y * p.W * 4 : OOB;
-        const int blk = (y * XB + xb) * (M / 4) * 32;            // first [px][4 ch] slot of the block
-        const int voff_in = LIN == LAY_NCHW ? voff : (valid ? blk * EB_IN + lane_blk_in : OOB);
-        const int voff_st = (CDL_DBG(p.dbg, 1) || (MODE == MODE_BWD && p.drop_zout)) ? OOB : (LOUT == LAY_NCHW ? voff : (valid ? blk * EB_OUT + lane_blk_out : OOB));
-
-        // -- fat inputs of this block, issued first: the analysis MFMAs below (and the partner
-        //    wave on this SIMD) run while they are in flight
-        float zc[MT][16];
-        u32x2 zr[MT][4];                     // LAY_BLK16: packed, decoded in the epilogue
+    // -- fat inputs of the row block at image row y (valid: this lane's pixel is inside the image; else nothing is read)
+    auto fat_loads = [&](int y, bool valid, int voff, int voff_in, float (&zc)[MT][16], u32x2 (&zr)[MT][4], unsigned &sup,
+                         unsigned &sgb, float &cm) __attribute__((always_inline)) {
         if (MODE != MODE_FIRST && LIN == LAY_BLK16) {
             blk16_load_raw<MT>(zr, rs_in, voff_in);
         } else if (MODE != MODE_FIRST && CDL_DBG(p.dbg, 16)) {
@@ -836,15 +866,59 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                     zc[R][v] = buf_ld(rs_in, voff, soff);
                 }
         }
-        unsigned sup = 0, sgb = 0;           // backward: support / sign words of this lane's pixel (0 outside)
+        sup = 0; sgb = 0;                    // backward: support / sign words of this lane's pixel (0 outside)
         if (MODE == MODE_BWD && valid) {
             sup = map_n[(size_t)y * p.W + x];
             sgb = map_n[HW + (size_t)y * p.W + x];
         }
-        float cm = 0.0f;                     // MAP: the noise-level map at this lane's pixel (0 outside the image)
+        cm = 0.0f;                           // MAP: the noise-level map at this lane's pixel (0 outside the image)
         if constexpr (MAP) {
             if (valid) cm = p.cmap[(size_t)n * HW + (size_t)y * p.W + x];
         }
+    };
+    // Reverse stage, one wave per SIMD: the fat inputs of row block b + 1 are issued behind the epilogue of block b -- its last
+    // reader of these registers -- and land in the SAME registers while the dA_k products, the synthesis and the col2im of
+    // block b run: no second landing set, no copies.  (Issued at the top of their own block they had the analysis GEMM's 24
+    // MFMAs to arrive in, and with one wave per SIMD nobody else covers the rest of the wait.)  The first block of a tile is
+    // loaded in front of the loop.
+    // (Every other instance keeps its landing registers local to the row block, as they were: *_a are then one element.)
+    constexpr bool PREFETCH = CDL_STAGE_PREFETCH && MODE == MODE_BWD && WY == 2;
+    float zc_a[PREFETCH ? MT : 1][PREFETCH ? 16 : 1];
+    u32x2 zr_a[PREFETCH ? MT : 1][PREFETCH ? 4 : 1];
+    unsigned sup_a = 0, sgb_a = 0;
+    float cm_a = 0.0f;
+    auto fat_loads_ahead = [&](int b_, bool live) __attribute__((always_inline)) {
+        if constexpr (PREFETCH) {
+            const int y = ty0 + wyi * RB + b_;
+            const bool valid = live && xok && (y < p.H);
+            const int voff = valid ? lane_off + y * p.W * 4 : OOB;
+            const int blk = (y * XB + xb) * (M / 4) * 32;
+            fat_loads(y, valid, voff, LIN == LAY_NCHW ? voff : (valid ? blk * EB_IN + lane_blk_in : OOB), zc_a, zr_a, sup_a, sgb_a, cm_a);
+        }
+    };
+    fat_loads_ahead(0, true);
+
+#pragma unroll 1
+    for (int b = 0; b < RB; ++b) {
+        const int yl = wyi * RB + b;         // tile-local image row of this block
+        const int y = ty0 + yl;
+        const bool valid = xok && (y < p.H);
+        const int voff = valid ? lane_off + y * p.W * 4 : OOB;
+        const int blk = (y * XB + xb) * (M / 4) * 32;            // first [px][4 ch] slot of the block
+        const int voff_in = LIN == LAY_NCHW ? voff : (valid ? blk * EB_IN + lane_blk_in : OOB);
+        const int voff_st = (CDL_DBG(p.dbg, 1) || (MODE == MODE_BWD && p.drop_zout)) ? OOB : (LOUT == LAY_NCHW ? voff : (valid ? blk * EB_OUT + lane_blk_out : OOB));
+
+        // -- fat inputs of this block, issued first: the analysis MFMAs below (and the partner
+        //    wave on this SIMD) run while they are in flight
+        float zc_b[PREFETCH ? 1 : MT][PREFETCH ? 1 : 16];
+        u32x2 zr_b[PREFETCH ? 1 : MT][PREFETCH ? 1 : 4];         // LAY_BLK16: packed, decoded in the epilogue
+        unsigned sup_b = 0, sgb_b = 0;
+        float cm_b = 0.0f;
+        float (&zc)[MT][16] = pick_ref<PREFETCH>(zc_a, zc_b);
+        u32x2 (&zr)[MT][4] = pick_ref<PREFETCH>(zr_a, zr_b);
+        unsigned &sup = PREFETCH ? sup_a : sup_b, &sgb = PREFETCH ? sgb_a : sgb_b;
+        float &cm = PREFETCH ? cm_a : cm_b;
+        if constexpr (!PREFETCH) fat_loads(y, valid, voff, voff_in, zc, zr, sup, sgb, cm);
 
         // -- im2col fragments of the thin input: 8 consecutive rows yl..yl+7 of column xl + j
         const int q = b & 3, e = yl - q;     // copy q is shifted up by q rows: 8-byte aligned window
@@ -914,9 +988,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                 if (MODE == MODE_BWD) {
                     const bool on = (sup >> (16 * R + v)) & 1u;         // never for out-of-image lanes
                     zz = on ? zbase + acc[R][v] : 0.0f;
-                    const float gt = ((sgb >> (16 * R + v)) & 1u) ? zz : -zz;        // -sign(z') * du
-                    tsum[16 * R + v] += gt;
-                    if constexpr (MAP_BWD) tsum_w[16 * R + v] = fmaf(cm, gt, tsum_w[16 * R + v]);
+                    if constexpr (!TS_SHADOW) tsum_add(R, v, zz, sgb, cm);
                 } else {
                     const float base = (MODE == MODE_FWD) ? zbase : 0.0f;
                     const float u = fmaf(p.sgn, acc[R][v], base);
@@ -986,6 +1058,12 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                 }
             }
         }
+        const unsigned sgb_t = sgb;          // this block's sign words and map value, for the partials further down
+        const float cm_t = cm;
+        if constexpr (PREFETCH) {
+            fat_loads_ahead(b + 1, b + 1 < RB);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (DA) {
             // dA_k += du_k (x) im2col(r2) for this row block: k_wgrad2d's product with the fat operand taken from the
             // accumulator registers (register v of tile R = channel 32R + 8(v>>2) + 4h + (v&3) of pixel column c: the
@@ -1002,8 +1080,16 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
             __builtin_amdgcn_wave_barrier();
             wgrad_products<MT, PREC, ALO>(dacc, wimg, thin2, yl, wxi, lane);
         }
-        if (MODE == MODE_BWD && !p.do_synth) continue;
-        if CDL_DBG(p.dbg, 2) { ring[0][0] += acc[0][0] + acc[MT - 1][15]; continue; }
+        if ((MODE == MODE_BWD && !p.do_synth) || CDL_DBG(p.dbg, 2)) {           // no synthesis half: the partials here (launch-uniform)
+            if constexpr (TS_SHADOW) {
+#pragma unroll
+                for (int R = 0; R < MT; ++R)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) tsum_add(R, v, acc[R][v], sgb_t, cm_t);
+            }
+            if CDL_DBG(p.dbg, 2) ring[0][0] += acc[0][0] + acc[MT - 1][15];
+            continue;
+        }
 
         __builtin_amdgcn_sched_barrier(0);
         // -- synthesis-like GEMM: the accumulator tiles are the B operand (k = channel) as they stand
@@ -1035,6 +1121,7 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
                     split_bf16(acc[R][8 * s + jj], hh, ll);
                     zh[jj] = hh;
                     if (PREC != 1 && LOUT != LAY_BLK16) zl[jj] = ll;      // a bf16-stored code has no lo part
+                    if constexpr (TS_SHADOW) tsum_add(R, 8 * s + jj, acc[R][8 * s + jj], sgb_t, cm_t);
                 }
                 if (PREC != 1) {
 #pragma unroll
@@ -1086,7 +1173,10 @@ __global__ __launch_bounds__(Shape<WY>::NT) void k_stage(StageParams<MODE_M> p)
             if (lane < 38 && !CDL_DBG(p.dbg, 32)) rsum[(wyi * RB + RB + i) * RTW + 32 * wxi + lane] = cs;
         }
     }
-    if (MODE == MODE_BWD) {
+    if (MODE == MODE_BWD && CDL_DBG(p.dbg, 256)) {           // timing only: the partials come out as zeros
+        tacc_s[wid * 64 + lane] = 0.0f;
+        if constexpr (MAP_BWD) tacc_w_s[wid * 64 + lane] = 0.0f;
+    } else if (MODE == MODE_BWD) {
         tsum_to_lds<MT>(tsum, tacc_s + wid * 64, c, h);
         if constexpr (MAP_BWD) tsum_to_lds<MT>(tsum_w, tacc_w_s + wid * 64, c, h);   // the weighted sums: their own [wave][64]
     }

@@ -87,7 +87,28 @@ __device__ __forceinline__ float upper_half_to_lower(float v)
 // Sum over the 32 pixel lanes of each half-wave of N per-lane values, leaving total #i on lane
 // (c with c mod N == i): a halving butterfly, N-1 exchanges instead of 5N.  Template recursion keeps
 // every register index static.  (N = 16: lanes c and c ^ 16 end up with the two halves of total #(c mod 16).)
-template <int N>
+// DPP = true: the exchanges at distances 8, 4, 2 and 1 stay inside a 16-lane row and are DPP moves (lane_xor_dpp) instead of
+// ds_bpermute round trips through LDS; longer distances keep __shfl_xor.  Same keep / send selection, same keep + received:
+// the same bits.  Needs every lane of the wave active.
+template <int DIST>
+__device__ __forceinline__ float lane_xor_dpp(float v)
+{
+    static_assert(DIST == 8 || DIST == 4 || DIST == 2 || DIST == 1, "distances inside a 16-lane row");
+    const int s = __builtin_bit_cast(int, v);
+    int r;
+    if constexpr (DIST == 8) {
+        r = __builtin_amdgcn_update_dpp(0, s, 0x128, 0xf, 0xf, false);           // row_ror:8
+    } else if constexpr (DIST == 4) {
+        r = __builtin_amdgcn_update_dpp(0, s, 0x104, 0xf, 0x5, false);           // row_shl:4 (lane i <- i + 4) into banks 0, 2
+        r = __builtin_amdgcn_update_dpp(r, s, 0x114, 0xf, 0xa, false);           // row_shr:4 (lane i <- i - 4) into banks 1, 3
+    } else if constexpr (DIST == 2) {
+        r = __builtin_amdgcn_update_dpp(0, s, 0x4e, 0xf, 0xf, false);            // quad_perm:[2,3,0,1]
+    } else {
+        r = __builtin_amdgcn_update_dpp(0, s, 0xb1, 0xf, 0xf, false);            // quad_perm:[1,0,3,2]
+    }
+    return __builtin_bit_cast(float, r);
+}
+template <int N, bool DPP = false>
 struct LaneTransposeSum {
     static __device__ __forceinline__ float run(const float (&v)[N], int c)
     {
@@ -98,12 +119,13 @@ struct LaneTransposeSum {
         for (int k = 0; k < n; ++k) {
             const float keep = up ? v[k + n] : v[k];
             const float send = up ? v[k] : v[k + n];
-            w[k] = keep + __shfl_xor(send, n, 64);
+            if constexpr (DPP && n <= 8) w[k] = keep + lane_xor_dpp<n>(send);
+            else w[k] = keep + __shfl_xor(send, n, 64);
         }
-        return LaneTransposeSum<n>::run(w, c);
+        return LaneTransposeSum<n, DPP>::run(w, c);
     }
 };
-template <>
-struct LaneTransposeSum<1> {
+template <bool DPP>
+struct LaneTransposeSum<1, DPP> {
     static __device__ __forceinline__ float run(const float (&v)[1], int) { return v[0]; }
 };
