@@ -112,6 +112,7 @@ SIGNATURES = {
     "cdl_fusedg_stage_bwd": [_G, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "cdl_fusedg_assemble": [_G, _P, _P, _P, _F, _P, _P, _I, _P],
     "cdl_fusedg_dtau_reduce": [_G, _P, _P, _P, _P, _P, _P],
+    "cdl_fusedg_dtau_reduce_planes": [_G, _P, _P, _P, _P, _P, _P],
     "cdl_fusedg_forward": [_G, _I] + [_P] * 11 + [_I, _P],
     "cdl_fusedg_backward": [_G, _I] + [_P] * 20 + [ctypes.c_size_t, _I, _P, _P, _P],
     # gradients with respect to the data (y, sigma)

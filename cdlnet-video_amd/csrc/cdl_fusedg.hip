@@ -50,13 +50,14 @@ struct GParams {
     const float *zin;        // (N,M,D,H,W) or nullptr
     unsigned *map;           // (N,4,D,H,W) support / sign bit planes (forward: written when given; reverse: read)
     float *zout;             // (N,M,D,H,W)
-    const float *tau;        // forward: (N,M)
+    const float *tau;        // forward: (N,M); (N*D,M), a row per (sample, depth) plane, with tau_planes
     float *dtau;             // reverse: (tiles, M) partial sums of -sign(z') * du
     const uint4 *frags;      // prepared weights (k_prep_g)
     float *patches;          // (tiles, G, PY, PX)
     float sgn;
     int do_synth;
     int N, C, M, D, H, W, Pd, tilesX, tilesY, KS, rev;
+    int tau_planes;          // CDL_TAU_PER_PLANE: the tile's thresholds are row n * D + zd of tau, not row n
     unsigned long long *tl;  // profiling hook (cdl_fusedg_set_timeline): s_memtime stamps of workgroup 0, [wave][256]
     CDL_DBG_FIELD(int dbg;)  // probe build only (CDL_FUSED_DEBUG; results are wrong): 1 no thin staging after the
                              // first tile, 2 no analysis GEMM, 4 no synthesis / col2im, 8 no fat loads, 16 no fat stores,
@@ -306,7 +307,10 @@ __global__ __launch_bounds__(NT) void k_stage_g(GParams p)
         __syncthreads();                                     // previous tile's readers are done (and the tables are in)
         CDL_TL();
         stage_store();                                       // thin planes of this tile (loaded into registers earlier)
-        if (MODE != MODE_BWD && tid < 64) tau_s[tid] = tid < M ? p.tau[(size_t)n * M + tid] : 0.0f;
+        if (MODE != MODE_BWD && tid < 64) {
+            const int trow = p.tau_planes ? n * p.D + zd : n;   // every code element of a tile shares one frame
+            tau_s[tid] = tid < M ? p.tau[(size_t)trow * M + tid] : 0.0f;
+        }
         // (the wave's private patch needs no zeroing: the row loop stores rows 0 .. RB-1, the ring flush rows RB .. WPH-1,
         //  every column)
         CDL_TL();
@@ -922,7 +926,8 @@ int prep(const cdl_geom *g, const Plan &pl, const float *const *w1, const float 
 // One stage launch behind cdl_fusedg_iter_fwd (MODE_FWD, MODE_FIRST: z' = ST(zin + sgn * A r, tau); map nullable) and
 // cdl_fusedg_stage_bwd (MODE_BWD: du = [map](zin + acc), dtau).  precision: the entry points' word -- arithmetic in
 // bits 0-3 (tile kernel: 0 = split-bf16 x3, 2 = x4; strip kernels: 0), CDL_TILES_REVERSED, and for the strip kernels
-// CDL_LAYOUT_IN / CDL_LAYOUT_OUT (CDL_LAY_NCHW or CDL_LAY_RSC) of zin / zout.
+// CDL_LAYOUT_IN / CDL_LAYOUT_OUT (CDL_LAY_NCHW or CDL_LAY_RSC) of zin / zout; CDL_TAU_PER_PLANE: tau is (N*D, M) (tile and
+// stripg kernels; the reverse mode reads no threshold and ignores it).
 int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const float *zin, const float *tau,
           const void *frags, float sgn, float *zout, float *patches, unsigned *map, float *dtau, int do_synth,
           int precision, hipStream_t st)
@@ -932,6 +937,9 @@ int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const flo
     if (!cdl_aligned16(frags, patches)) return CDL_EUNSUPPORTED;     // library-sized buffers: 16-byte accesses (cdlnet_hip.h)
     if (do_synth && !patches) return CDL_EINVAL;
     const int rev = (precision >> 4) & 1;
+    const int planes = (precision & CDL_TAU_PER_PLANE) ? 1 : 0;
+    if (planes && pl.kind == CDL_PLAN_STRIP) return CDL_EINVAL;      // k_strip (2-D, D == 1) has no per-plane form
+    precision &= ~CDL_TAU_PER_PLANE;
     if (pl.kind != CDL_PLAN_TILE) {
         const int li = (precision >> 5) & 3, lo = (precision >> 7) & 3;
         if ((precision >> 9) != 0) return CDL_EINVAL;
@@ -941,7 +949,8 @@ int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const flo
         if ((rsc_in && !cdl_aligned16(zin)) || (rsc_out && !cdl_aligned16(zout))) return CDL_EUNSUPPORTED;   // rsc codes: 16-byte accesses
         if (pl.kind == CDL_PLAN_STRIP)
             return cdl_strip_stage(g, pl, mode, r, zin, tau, frags, sgn, zout, patches, map, dtau, do_synth, rev, rsc_in, rsc_out, st);
-        return cdl_stripg_stage(g, pl, mode, r, zin, tau, frags, sgn, zout, patches, map, dtau, do_synth, rev, rsc_in, rsc_out, st);
+        return cdl_stripg_stage(g, pl, mode, r, zin, tau, frags, sgn, zout, patches, map, dtau, do_synth, rev, rsc_in, rsc_out,
+                                planes, st);
     }
     if ((precision >> 5) != 0) return CDL_EINVAL;
     if ((precision & 15) == 2) mode += 3;                    // split-bf16 x4
@@ -952,6 +961,7 @@ int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const flo
     p.patches = patches; p.sgn = sgn; p.do_synth = do_synth;
     p.tl = g_timeline.load();
     p.rev = rev;
+    p.tau_planes = planes;
     CDL_DBG_FIELD(p.dbg = cdl_opts().fused_debug;)
     p.N = g->N; p.C = g->C; p.M = g->M; p.D = g->D; p.H = g->H; p.W = g->W; p.Pd = g->Pd;
     p.tilesX = pl.tilesX; p.tilesY = pl.tilesY; p.KS = pl.KS;
@@ -964,6 +974,7 @@ int stage(const cdl_geom *g, const Plan &pl, int mode, const float *r, const flo
 // CDL_LAY_RSC for the strip kernels only, and only where the caller's other kernels read it (rsc_ok)
 bool sweep_layout(const Plan &pl, int precision, bool rsc_ok, int *lay)
 {
+    precision &= ~CDL_TAU_PER_PLANE;
     *lay = (precision >> 5) & 3;
     return (precision >> 7) == 0 && (*lay == CDL_LAY_NCHW || (pl.kind != CDL_PLAN_TILE && *lay == CDL_LAY_RSC && rsc_ok));
 }
@@ -976,7 +987,24 @@ int sweep_flags(const Plan &pl, int precision, bool reversed, int lay_in, int la
 {
     const int forced = cdl_opts().fusedg_bwd_prec;
     const int prec = (pl.kind == CDL_PLAN_TILE && (forced == 0 || forced == 2)) ? forced : (precision & 15);
-    return prec | (reversed ? CDL_TILES_REVERSED : 0) | CDL_LAYOUT_IN(lay_in) | CDL_LAYOUT_OUT(lay_out);
+    return prec | (reversed ? CDL_TILES_REVERSED : 0) | CDL_LAYOUT_IN(lay_in) | CDL_LAYOUT_OUT(lay_out) |
+           (precision & CDL_TAU_PER_PLANE);
+}
+
+// The two reductions behind cdl_fusedg_dtau_reduce and its per-plane sibling: `samples` groups of `per` consecutive partial
+// rows -- the N samples of per_img rows each, or (planes) the N * D planes of per_img / D rows each: the rows are in
+// [n][zd][ty][tx] order, so either grouping sums the same rows in the same order, c[group] weighting dt1.
+int dtau_reduce(const cdl_geom *g, const Plan &pl, const float *dtau_partial, const float *c, float *dt0, float *dt1,
+                float *dtau_n, bool planes, void *stream)
+{
+    if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
+    if (planes && pl.kind == CDL_PLAN_STRIP) return CDL_EINVAL;
+    const int samples = planes ? g->N * g->D : g->N, per = planes ? pl.per_img / g->D : pl.per_img;
+    k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, samples, per, g->M);
+    CDL_LAUNCH_CHECK();
+    if (!dtau_n) return 0;
+    // partial rows: [n][tile][m], as k_dtau_reduce_g reads them
+    return cdl_dtau_per_sample(dtau_partial, samples, g->M, per, (size_t)per * g->M, 1, g->M, dtau_n, stream);
 }
 
 }  // namespace
@@ -1100,12 +1128,15 @@ int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const f
 {
     Plan pl;
     if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
-    if (!dtau_partial || !dt0 || !dt1) return CDL_EINVAL;
-    k_dtau_reduce_g<<<(g->M + 3) / 4, 1024, 0, S(stream)>>>(dtau_partial, c, dt0, dt1, g->N, pl.per_img, g->M);
-    CDL_LAUNCH_CHECK();
-    if (!dtau_n) return 0;
-    // partial rows: [n][tile][m], as k_dtau_reduce_g reads them
-    return cdl_dtau_per_sample(dtau_partial, g->N, g->M, pl.per_img, (size_t)pl.per_img * g->M, 1, g->M, dtau_n, stream);
+    return dtau_reduce(g, pl, dtau_partial, c, dt0, dt1, dtau_n, false, stream);
+}
+
+int cdl_fusedg_dtau_reduce_planes(const cdl_geom *g, const float *dtau_partial, const float *c, float *dt0, float *dt1,
+                                  float *dtau_nd, void *stream)
+{
+    Plan pl;
+    if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
+    return dtau_reduce(g, pl, dtau_partial, c, dt0, dt1, dtau_nd, true, stream);
 }
 
 /* ---- whole sweeps (one C call each), the counterparts of cdl_fused2d_forward / _backward ------------------------ */
@@ -1116,7 +1147,8 @@ int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *m
     Plan pl;
     if (!route_for(g, &pl)) return CDL_EUNSUPPORTED;
     if (K < 1 || !yp || !tau || !wA || !wB || !z || !xp || !frags || !patches || (K > 1 && !r)) return CDL_EINVAL;
-    const size_t nm = (size_t)g->N * g->M;
+    if ((precision & CDL_TAU_PER_PLANE) && pl.kind == CDL_PLAN_STRIP) return CDL_EINVAL;
+    const size_t nm = (size_t)g->N * g->M * ((precision & CDL_TAU_PER_PLANE) ? g->D : 1);      // tau rows of one iteration
     int rc = prep(g, pl, wA, wB, K, 1, frags, S(stream));             // (A_k, B_{k+1}) for every k
     if (rc) return rc;
     int lay;                                                 // of z[0..K-2]; z[K-1] is always the reference's (N,M,..) layout
@@ -1176,6 +1208,8 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
     if (K < 1 || !yp || !wA || !wB || !z || !maps || !g_xp || !dA || !dB || !dt || !du0 || !du1 || !q || !frags ||
         !patches || !dtau_partial || (K > 1 && !r))
         return CDL_EINVAL;
+    const bool planes = (precision & CDL_TAU_PER_PLANE) != 0;      // c (N*D), dtau (K, N*D, M)
+    if (planes && pl.kind == CDL_PLAN_STRIP) return CDL_EINVAL;
     const int M = g->M;
     float *du[2] = {du0, du1};
     // the layout of z[0..K-2] and of the du buffers: CDL_LAY_RSC when the matrix-core filter-gradient kernel takes the
@@ -1198,8 +1232,8 @@ int cdl_fusedg_backward(const cdl_geom *g, int K, const float *yp, const float *
         rc = stage(g, pl, MODE_BWD, thin, base, nullptr, fk, 1.0f, duk, patches, const_cast<unsigned *>(maps[k]), dtau_partial,
                    k >= 1 || dyp, sweep_flags(pl, precision, reversed, k == K - 1 ? CDL_LAY_NCHW : lay, lay), S(stream));
         if (rc) return rc;
-        rc = cdl_fusedg_dtau_reduce(g, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
-                                    dtau ? dtau + (size_t)k * g->N * M : nullptr, stream);
+        rc = dtau_reduce(g, pl, dtau_partial, c, dt + (size_t)k * 2 * M, dt + (size_t)k * 2 * M + M,
+                         dtau ? dtau + (size_t)k * g->N * (planes ? g->D : 1) * M : nullptr, planes, stream);
         if (rc) return rc;
         if (k == 0 && dyp) {                                    // u_0 = A_0 yp: dyp += A_0^T du_0 (no q at k = 0)
             rc = cdl_fusedg_assemble(g, patches, nullptr, nullptr, 1.0f, nullptr, dyp, K > 1, stream);

@@ -69,8 +69,9 @@ int cdl_strip_assemble(const cdl_geom *g, const cdl_fusedg_plan &pl, const float
 
 // ---- cdl_stripg.hip (fragments: the tile kernel's prep_pairs in cdl_fusedg.hip)
 bool cdl_stripg_plan_for(const cdl_geom *g, cdl_fusedg_plan *pl);
+// tau_planes (CDL_TAU_PER_PLANE of the entry points): tau is (N*D, M), an item reads row n * D + zd
 int cdl_stripg_stage(const cdl_geom *g, const cdl_fusedg_plan &pl, int mode, const float *r, const float *zin,
                      const float *tau, const void *frags, float sgn, float *zout, float *patches, unsigned *map,
-                     float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, hipStream_t st);
+                     float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, int tau_planes, hipStream_t st);
 int cdl_stripg_assemble(const cdl_geom *g, const cdl_fusedg_plan &pl, const float *patches, const float *mask,
                         const float *sub, float alpha, float *out, float *acc, int acc_add, hipStream_t st);

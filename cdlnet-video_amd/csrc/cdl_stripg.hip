@@ -30,13 +30,16 @@ struct GSParams {
     const float *zin;        // (N,M,D,H,W) / CDL_LAY_RSC, or nullptr
     unsigned *map;           // (N,4,D,H,W) words: plane 2h = support, 2h+1 = sign, bit 16R + v (as k_stage_g)
     float *zout;
-    const float *tau;        // (N,M)
+    const float *tau;        // (N,M); (N*D,M), a row per (sample, depth) plane, with tau_planes
     float *dtau;             // (items, M)
     const uint4 *frags;      // cdl_fusedg.hip's prepared pair: [A hi | A lo | B hi | B lo]
     float *patches;          // (items, G, prows, PXW)
     float sgn;
     int do_synth;
-    int N, C, M, D, H, W, Pd, KQ, nsx, nsy, SEG, prows, rev, items, lay_in, lay_out;
+    int N, C, M, D, H, W, Pd, KQ, nsx, nsy, SEG, prows, order, items, lay_in, lay_out;
+                             // order: bit 0 walk the items from the last to the first; bit 1 (CDL_TAU_PER_PLANE) the item's
+                             // thresholds are row n * D + zd of tau, not row n (one word: every instance is at the scalar
+                             // register limit already)
     CDL_DBG_FIELD(int dbg;)  // probe build only (CDL_FUSED_DEBUG; results are wrong): 1 no fat loads, 2 no fat stores,
                              // 4 no analysis-like MFMAs, 8 no synthesis-like MFMAs, 16 no col2im, 32 no gather
 };
@@ -125,18 +128,20 @@ __global__ __launch_bounds__(NTS) void k_stripg(GSParams p)
 
 #pragma unroll 1
     for (int it = blockIdx.x * NWV + wid; it < p.items; it += nwaves) {
-        int bid = p.rev ? p.items - 1 - it : it;
+        int bid = (p.order & 1) ? p.items - 1 - it : it;
         const int item = bid;
         const int sx = bid % p.nsx; bid /= p.nsx;
         const int sy = bid % p.nsy; bid /= p.nsy;
         const int zd = bid % p.D, n = bid / p.D;
+        const int trow = (p.order & 2) ? bid : n;                        // the item's row of tau; bid = n * D + zd: an item lies in one frame
         const int xz0 = sx * 32, yz0 = sy * p.SEG;
         const int x = xz0 + c;
         const bool xok = x < p.W;
         const int nblk = min(p.SEG, p.H - yz0);
         const bool edge = __ballot(!xok) != 0ull;                        // uniform
 
-        if (MODE != MODE_BWD) tau_s[lane] = lane < M ? p.tau[(size_t)n * M + lane] : 0.0f;
+        // (a 32-bit offset: N * D <= 65535 rows of M <= 64 floats, cdl_grouped_plan_base)
+        if (MODE != MODE_BWD) tau_s[lane] = lane < M ? p.tau[trow * M + lane] : 0.0f;
 
         // thin row group bb: image row yz0 + bb + HALO of the G planes (plane g = (c, kd): depth zd - Pd/2 + kd of channel c).
         // Per item and lane: the byte offset of its element's (plane, column) in r (out of range where the plane or the
@@ -573,7 +578,7 @@ bool cdl_stripg_plan_for(const cdl_geom *g, cdl_fusedg_plan *pl)
 
 int cdl_stripg_stage(const cdl_geom *g, const cdl_fusedg_plan &pl, int mode, const float *r, const float *zin,
                      const float *tau, const void *frags, float sgn, float *zout, float *patches, unsigned *map,
-                     float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, hipStream_t st)
+                     float *dtau_partial, int do_synth, int rev, int lay_in, int lay_out, int tau_planes, hipStream_t st)
 {
     if (sgn != 1.0f && sgn != -1.0f) return CDL_EINVAL;
     GSParams p = {};
@@ -581,7 +586,7 @@ int cdl_stripg_stage(const cdl_geom *g, const cdl_fusedg_plan &pl, int mode, con
     p.frags = reinterpret_cast<const uint4 *>(frags);
     p.patches = patches; p.sgn = sgn; p.do_synth = do_synth;
     p.N = g->N; p.C = g->C; p.M = g->M; p.D = g->D; p.H = g->H; p.W = g->W; p.Pd = g->Pd; p.KQ = pl.KQ;
-    p.nsx = pl.nsx; p.nsy = pl.nsy; p.SEG = pl.SEG; p.prows = pl.prows; p.rev = rev; p.items = (int)pl.items;
+    p.nsx = pl.nsx; p.nsy = pl.nsy; p.SEG = pl.SEG; p.prows = pl.prows; p.order = (rev ? 1 : 0) | (tau_planes ? 2 : 0); p.items = (int)pl.items;
     p.lay_in = lay_in; p.lay_out = lay_out;
     CDL_DBG_FIELD(p.dbg = cdl_opts().fused_debug;)
     if (pl.P == 3) return launch_p<3>(p, pl, mode, st);

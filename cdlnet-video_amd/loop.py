@@ -76,6 +76,40 @@ class map_tier_scope:
         return False
 
 
+# Where a CDLNetVideo sweep with one noise level per FRAME -- c of shape (N,1,D,1,1) -- runs: "generic" (the level is
+# expanded to a dense map and takes the map's route: the default) or "fused" -- the tile / grouped strip kernels with one
+# threshold row per (sample, frame) wherever _route allows it, the dense map everywhere else.  A knob
+# of its own: neither value of MAP_TIER changes what it does.
+FRAME_TIER = "generic"
+
+
+def set_frame_tier(name):
+    global FRAME_TIER
+    if name not in _MAP_TIERS:
+        raise ValueError(name)
+    FRAME_TIER = name
+
+
+class frame_tier_scope:
+    """`with frame_tier_scope("fused"): ...` -- network calls with per-frame noise levels started inside take that tier
+    (their reverse sweeps follow their forward whenever backward() is called); restored on exit, also when the block raises."""
+
+    def __init__(self, name):
+        if name not in _MAP_TIERS:
+            raise ValueError(name)
+        self.name = name
+
+    def __enter__(self):
+        global FRAME_TIER
+        self.saved, FRAME_TIER = FRAME_TIER, self.name
+        return self
+
+    def __exit__(self, *exc):
+        global FRAME_TIER
+        FRAME_TIER = self.saved
+        return False
+
+
 def set_backend(name):
     global BACKEND
     if name not in ("auto", "generic"):
@@ -257,23 +291,27 @@ def _forward_fused_stepwise(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, la
     return xp, z, codes, resid, maps
 
 
-def _forward_fusedg(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw", *, keep_maps=False):
+def _forward_fusedg(g, yp, mask_p, tau, A, B, keep_codes, keep_resid, layout="nchw", *, keep_maps=False, planes=False):
     """cdl_fusedg_forward: the fused iteration for C > 1 / 3-D / P in {3,5,7} / M <= 64, and (the strip kernel) for one
     image channel, stride 1 / 2, M <= 192: one fused launch + a thin assemble per iteration.  codes[:-1] come back in
     `layout` ("nchw", or "rsc" where ops.fusedg_code_layout(g) says so), codes[-1] = z_K as (N,M,..).  keep_maps: as
-    _forward_fused's."""
+    _forward_fused's.  planes: tau is (K, N*D, M), one threshold row per (sample, frame)."""
     keep = keep_codes or keep_resid
-    xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, layout, keep_maps=keep_maps)
+    xp, z, codes, resid, maps = ops.fusedg_forward(g, yp, mask_p, tau, A, B, keep, layout, keep_maps=keep_maps,
+                                                   **(dict(planes=True) if planes else {}))
     return xp, z, codes, (resid if keep_resid else []), (maps if keep_resid or keep_maps else [])
 
 
-def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw", dyp=None, dtau=None):
+def _backward_fusedg(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw", dyp=None, dtau=None,
+                     planes=False):
     """cdl_fusedg_backward: per iteration one fused reverse stage (du_k, threshold partials, patches of q_k), a thin
-    assemble and the two filter gradients.  `layout`: that of codes[:-1]."""
+    assemble and the two filter gradients.  `layout`: that of codes[:-1].  planes: c is (N*D), one level per (sample, frame),
+    and dtau (K, N*D, M)."""
     if g_xp is None and g_z is None:
         return _zero_grads(A, B)
     return ops.fusedg_backward(g, yp, mask_p, c, list(A), list(B), list(codes), list(resid), g_xp, g_z, dt,
-                               maps=list(maps) if maps else None, layout=layout, dyp=dyp, dtau=dtau)
+                               maps=list(maps) if maps else None, layout=layout, dyp=dyp, dtau=dtau,
+                               **(dict(planes=True) if planes else {}))
 
 
 def _backward_generic(g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, dyp=None, dtau=None,
@@ -424,13 +462,17 @@ def _no_data_gradients(ctx, names=((0, "y"), (1, "mask"), (2, "sigma"))):
                                       f"(the HIP reverse sweep returns parameter gradients only); detach() it")
 
 
-def _route(g, exact, is_map):
+def _route(g, exact, is_map, frames=False):
     """The tier of a sweep: "fused" (the 2-D MFMA kernels), "fusedg" (the tile / strip kernels) or "generic".  The fused
     tiers are matrix-core kernels that read tau[n,m]: the "fp32" arithmetic (`exact`) and a noise-level map run the generic --
     unless MAP_TIER is "fused" and the sweep is one the 2-D kernels' map forms exist for: split3 arithmetic, fp32 code storage,
-    a geometry of the 2-D tier (the tile / strip kernels take no map)."""
+    a geometry of the 2-D tier (the tile / strip kernels take no map).  frames: the map is one level per (sample, frame),
+    (N,1,D,1,1) -- with FRAME_TIER "fused" the tile / grouped strip kernels take it as a threshold row per plane, where there
+    is more than one frame and one of the two takes the geometry (with D > 1 the strip kernel proper, which is 2-D, never does)."""
     if BACKEND != "auto" or exact:
         return "generic"
+    if is_map and frames and FRAME_TIER == "fused" and g.dims[0] > 1 and ops.fusedg_supported(g):
+        return "fusedg"
     if is_map:
         fused_map = MAP_TIER == "fused" and PRECISION == "split3" and CODE_LAYOUT in ("nchw", "blocked")
         return "fused" if fused_map and ops.fused_supported(g) else "generic"
@@ -459,6 +501,24 @@ def _tangent_reverse_fused(name):
         st, g, K, vp, mask_p, None, A, B, zd, rd, g_xdp, g_zd, vp.new_empty((K, 2, g.M)), maps)
 
 
+def _planes(st):
+    """The keyword that switches a sweep of the fused generic tier to one threshold row per (sample, frame): set where
+    _forward_sweep routed per-frame levels there (st.frames), absent otherwise -- the sweeps then get today's arguments."""
+    return dict(planes=True) if getattr(st, "frames", False) else {}
+
+
+def _frame_levels(g, c):
+    """Whether c holds one noise level per (sample, frame) of a clip: (N,1,D,1,1) against an in-plane code grid larger than
+    one pixel (net._noise_scale hands it over in this form under FRAME_TIER "fused")."""
+    return (c is not None and c.dim() == 5 and g.ndim == 3 and tuple(c.shape[3:]) == (1, 1)
+            and tuple(g.code_spatial[1:]) != (1, 1))
+
+
+def _dense_levels(g, c):
+    """Per-frame levels as the dense map the generic tier reads: what net._noise_scale expands them to without the knob."""
+    return c.expand((g.N, 1) + tuple(g.code_spatial)).contiguous()
+
+
 _TIERS = {
     "fused": _Tier(
         layout=lambda g, keep, handed_out, tangent: "nchw" if handed_out else CODE_LAYOUT,
@@ -473,9 +533,10 @@ _TIERS = {
     "fusedg": _Tier(                               # handed-out codes are (N,M,..), and cdl_fusedg_tangent takes nothing else
         layout=lambda g, keep, handed_out, tangent: "nchw" if handed_out or tangent else ops.fusedg_code_layout(g, training=keep),
         forward=lambda st, g, yp, mask_p, tau, A, B, keep_codes, keep_resid, keep_gates=False: _forward_fusedg(
-            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates),
+            g, yp, mask_p, tau, A, B, keep_codes, keep_resid, st.layout, keep_maps=keep_gates, **_planes(st)),
         reverse=lambda st, g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps, dyp=None, dtau=None: _backward_fusedg(
-            g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=st.layout, dyp=dyp, dtau=dtau),
+            g, K, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=maps, layout=st.layout, dyp=dyp, dtau=dtau,
+            **(_planes(st) if c is not None else {})),          # (a tangent's reverse sweep reads no level: the plain form)
         tangent=lambda st, g, vp, mask_p, A, B, codes, maps, keep, last: _tangent_fusedg(
             g, vp, mask_p, A, B, maps, keep, last=last),
         tangent_reverse=_tangent_reverse_fused("fusedg"), negated_dA=True),
@@ -499,10 +560,17 @@ def _forward_sweep(ctx, g, yp, mask_p, c, t, A, B, keep, want_codes, keep_maps=F
     is_map, layout, precision.  UnrolledISTA.forward, TangentISTA.forward and run_windows all go through here, so a window
     and a tangent's primal take exactly the tier a sample of their geometry takes.  want_codes: the codes are handed to the
     caller (forward_generator), as (N,M,..); tangent: a tangent sweep follows, in a layout it reads; keep_maps: _Tier's keep_gates."""
-    cmap, tslope = _map_args(c, t)                 # with a map tau holds t[k,0,m] for every sample
+    frames = _frame_levels(g, c)
+    ctx.tier = _route(g, ctx.exact, c is not None and c.dim() > 1, **(dict(frames=True) if frames else {}))
+    ctx.frames = frames and ctx.tier == "fusedg"   # per-frame levels stay on the fused generic tier: a threshold row per plane
+    if frames and not ctx.frames:
+        c = _dense_levels(g, c)                    # any other route: the dense map, as without FRAME_TIER
+    cmap, tslope = (None, None) if ctx.frames else _map_args(c, t)      # with a map tau holds t[k,0,m] for every sample
     ctx.is_map = cmap is not None
-    tau = ops.thresholds(t, None if ctx.is_map else c, g.N)
-    ctx.tier = _route(g, ctx.exact, ctx.is_map)
+    if ctx.frames:                                 # t[k,0] + c[n,d] * t[k,1]: cdl_thresholds with N * D levels
+        tau = ops.thresholds(t, c.reshape(-1), g.N * g.dims[0])
+    else:
+        tau = ops.thresholds(t, None if ctx.is_map else c, g.N)
     ctx.fused, ctx.fusedg = ctx.tier == "fused", ctx.tier == "fusedg"
     tier = _TIERS[ctx.tier]
     ctx.layout = tier.layout(g, keep, want_codes, tangent)
@@ -518,12 +586,19 @@ def _reverse_sweep(ctx, sv, g_xp, g_z, dt, want_y=False, want_c=False):
     K, g, dev = ctx.K, ctx.geom, sv.yp.device
     live = g_xp is not None or g_z is not None
     dyp = torch.empty(g.image_shape(), device=dev, dtype=torch.float32) if want_y and live else None
-    dtau = torch.empty((K, g.N, g.M), device=dev, dtype=torch.float32) if want_c and live and not ctx.is_map else None
-    cmap, tslope = _map_args(sv.c, sv.t)
+    frames = getattr(ctx, "frames", False)         # per-frame levels on the fused generic tier: N * D "samples"
+    c = sv.c.reshape(-1) if frames else sv.c
+    if not frames and _frame_levels(g, c):         # per-frame levels that took another route: the dense map of the forward
+        c = _dense_levels(g, c)
+    rows = g.N * g.dims[0] if frames else g.N
+    dtau = torch.empty((K, rows, g.M), device=dev, dtype=torch.float32) if want_c and live and not ctx.is_map else None
+    cmap, tslope = (None, None) if frames else _map_args(c, sv.t)
     dcmap = torch.empty_like(cmap) if want_c and live and ctx.is_map else None      # dL/dc comes back as a map
     mp = dict(cmap=cmap, tslope=tslope, dcmap=dcmap) if ctx.is_map else {}
-    dA, dB = _TIERS[ctx.tier].reverse(ctx, g, K, sv.yp, sv.mask_p, None if ctx.is_map else sv.c, sv.A, sv.B, sv.codes,
+    dA, dB = _TIERS[ctx.tier].reverse(ctx, g, K, sv.yp, sv.mask_p, None if ctx.is_map else c, sv.A, sv.B, sv.codes,
                                       sv.resid, g_xp, g_z, dt, sv.maps, dyp, dtau, **mp)
+    if dcmap is not None and dcmap.shape != sv.c.shape:       # expanded per-frame levels: the adjoint of the expansion
+        dcmap = dcmap.sum(dim=(3, 4), keepdim=True)
     return dA, dB, dyp, dtau, dcmap
 
 
@@ -570,8 +645,8 @@ class UnrolledISTA(torch.autograd.Function):
         dy = None
         if dyp is not None:                            # a loss on z only: no mean term
             dy = ops.preprocess_bwd(dyp, ctx.pads, g_xhat.contiguous() if g_xhat is not None else None, sv.y_mask)
-        if dtau is not None:                           # tau[k,n,m] = t[k,0,m] + c[n] t[k,1,m]
-            dc = torch.einsum("knm,km->n", dtau, sv.t.detach().reshape(K, 2, g.M)[:, 1])
+        if dtau is not None:                           # tau[k,n,m] = t[k,0,m] + c[n] t[k,1,m] (per-frame levels: n = (sample, frame))
+            dc = torch.einsum("knm,km->n", dtau, sv.t.detach().reshape(K, 2, g.M)[:, 1]).reshape(sv.c.shape)
 
         _queue_backward_end()
         return (dy, None, dc, dt.reshape(sv.t.shape), None, *dA, *dB)
@@ -1096,6 +1171,8 @@ def run_residual(y, mask, c, t, A, B, s, blocks, all_codes=False):
         raise NotImplementedError("cdlnet_video_amd: gradients with respect to y / mask / sigma are not implemented")
     yp, mean, pads, mask_p = ops.preprocess(y, s, mask)
     g = _sweep_geometry(yp, A, s)
+    if _frame_levels(g, c):                        # the chain of per-iteration nodes runs the generic operators: a dense map
+        c = _dense_levels(g, c)
     z, shrunk = None, []
     for k in range(K):
         z = _ISTAIteration.apply(z, t[k], A[k], B[k], g, yp, mask_p, c)

@@ -66,7 +66,11 @@ def _noise_scale(sigma, adaptive, N, device, code_spatial):
     and must broadcast to (N, 1, *code_spatial) as it does against a code tensor in the reference: one level per frame
     (N,1,D,1,1), a full map (N,1,Hc,Wc) / (N,1,Dc,Hc,Wc), or anything between; it is expanded on the host (it is 1/M of
     a code tensor).  The one ambiguity of the first rule: a (1,1,H,W) map with H*W == N is read as N per-sample levels --
-    expand it to (N,1,H,W) to have it read as a map."""
+    expand it to (N,1,H,W) to have it read as a map.
+
+    Under loop.set_frame_tier("fused") a map of a clip with extent 1 on both in-plane axes -- (N,1,D,1,1), (1,1,D,1,1),
+    (D,1,1): one level per frame -- comes back as a contiguous (N,1,D,1,1) tensor: the form the fused generic tier reads as a
+    threshold row per (sample, frame); a sweep that takes another route expands it itself (loop._forward_sweep)."""
     if sigma is None or not adaptive:
         return None
     if torch.is_tensor(sigma):
@@ -87,6 +91,8 @@ def _noise_scale(sigma, adaptive, N, device, code_spatial):
                              "(the stride-padded image extent over the stride; utils.sigma_to_code_grid maps an "
                              "image-resolution map onto it)")
         c = sigma.to(device=device, dtype=torch.float32).reshape(shape) / 255.0
+        if loop.FRAME_TIER == "fused" and len(want) == 5 and shape[3:] == (1, 1) and want[3:] != (1, 1):
+            return c.expand(want[:3] + (1, 1)).contiguous()        # one level per frame: the sweep expands it where it must
         return c.expand(want).contiguous()
     return torch.full((N,), float(sigma) / 255.0, device=device, dtype=torch.float32)
 

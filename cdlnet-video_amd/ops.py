@@ -872,6 +872,7 @@ class trace:
 LAYOUT = {"nchw": 0, "blocked": 1, "blocked_bf16": 2, "rsc": 3}
 _FUSED_LAYOUTS = ("nchw", "blocked", "blocked_bf16")     # of the fused 2-D kernels; "rsc": the strip kernels' (fusedg_*)
 TILES_REVERSED = 16
+TAU_PER_PLANE = 512                # cdl_fusedg_* only: one threshold row per (sample, depth) plane (CDL_TAU_PER_PLANE)
 
 
 def _lay_in(layout):
@@ -1006,11 +1007,12 @@ def fused_wgrad(g: Geometry, workspace, X0=None, T0=None, alpha0=1.0, X1=None, T
     return outs
 
 
-def _check_data_grads(g: Geometry, K, dyp, dtau, families=1):
+def _check_data_grads(g: Geometry, K, dyp, dtau, families=1, rows=None):
     """The optional outputs of the *_backward sweeps: dyp (thin, as yp), dtau (K,N,M) -- (K,3,N,M) for the three threshold
-    families of the CSR sweep; contiguous fp32."""
+    families of the CSR sweep, (K,rows,M) with per-plane thresholds; contiguous fp32."""
     _buf(dyp, "dyp", g.image_shape())
-    _buf(dtau, "dtau", (K, g.N, g.M) if families == 1 else (K, families, g.N, g.M))
+    rows = g.N if rows is None else rows
+    _buf(dtau, "dtau", (K, rows, g.M) if families == 1 else (K, families, rows, g.M))
 
 
 def _dt_sweep(g: Geometry, K, dt, name="dt"):
@@ -1144,8 +1146,25 @@ def fusedg_support_map(g: Geometry, z):
     return out.to(torch.int32).contiguous()
 
 
-def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None):
-    _dtau_reduce("cdl_fusedg_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
+def _plane_rows(g: Geometry, planes):
+    """Threshold rows of one iteration on the fused generic tier: one per sample, or (planes) one per (sample, depth) plane."""
+    return g.N * g.dims[0] if planes else g.N
+
+
+def _plane_levels(g: Geometry, c, planes):
+    """The levels c that weight dt[:,1]: (N), or (N*D) with per-plane thresholds (None stays None)."""
+    if c is not None and c.numel() != _plane_rows(g, planes):
+        raise ValueError(f"c: expected {_plane_rows(g, planes)} noise levels, got {c.numel()}")
+    return c
+
+
+def fusedg_dtau_reduce(g: Geometry, dtau_partial, c, dt_k, dtau_n=None, planes=False):
+    """planes: the (sample, depth) plane is the "sample" -- c (N*D), dtau_n (N*D, M); dt_k[0] does not change."""
+    if not planes:
+        return _dtau_reduce("cdl_fusedg_dtau_reduce", g, dtau_partial, c, dt_k, dtau_n)
+    dt0, dt1 = _dt_halves(g, dt_k)
+    _call("cdl_fusedg_dtau_reduce_planes", g, _buf(dtau_partial, "dtau_partial"), _plane_levels(g, _opt(c, "c"), True), dt0, dt1,
+          _buf(dtau_n, "dtau_n", (_plane_rows(g, True), g.M)))
 
 
 def fusedg_code_layout(g: Geometry, training=True) -> str:
@@ -1209,15 +1228,19 @@ def _code(t, name, layout):
     return t if t is None or layout.startswith("blocked") else _dev(t, name)
 
 
-def _fused_iter(tier, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, cmap=None, tslope=None):
+def _fused_iter(tier, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, cmap=None, tslope=None,
+                planes=False):
     r, zin, tau = _dev(r, "r"), _code(zin, "zin", lay_in), _dev(tau, "tau")
     assert tuple(r.shape) == g.image_shape()
+    if planes and tau.numel() != _plane_rows(g, True) * g.M:
+        raise ValueError(f"tau: expected {_plane_rows(g, True)} x {g.M} per-plane thresholds, got {tau.numel()}")
     frags, patches = _buf(frags, "frags", dtype=torch.uint8), _buf(patches, "patches")
     mp = _tier_map(tier, g, cmap, tslope)
     if out is None:
         out = tier.code_buffers(g, lay_out, r.device, 1)[0]
     _call(tier.prefix + "_iter_fwd", g, r, zin, tau, frags, sgn, _buf(out, "out", dtype=out.dtype), patches,
-          _buf(map_out, "map_out", dtype=torch.int32), PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out), *mp)
+          _buf(map_out, "map_out", dtype=torch.int32),
+          PRECISION[precision] | _lay_in(lay_in) | _lay_out(lay_out) | (TAU_PER_PLANE if planes else 0), *mp)
     return out
 
 
@@ -1252,10 +1275,12 @@ def _fused_stage_bwd(tier, g, thin, base, gate_map, frags, patches, dtau_partial
     return out
 
 
-def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps, cmap=None, tslope=None):
+def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps, cmap=None, tslope=None, planes=False):
     K = len(A)
     mp = _tier_map(tier, g, cmap, tslope, rows=K)
     yp, tau, mask_p = _dev(yp, "yp"), _dev(tau, "tau"), _opt(mask_p, "mask")
+    if planes and tau.numel() != K * _plane_rows(g, True) * g.M:
+        raise ValueError(f"tau: expected {K} x {_plane_rows(g, True)} x {g.M} per-plane thresholds, got {tau.numel()}")
     A, B = [_dev(w, "A") for w in A], [_dev(w, "B") for w in B]
     dev = yp.device
     # one allocation per family (views into it): at cfg1's size the allocator calls cost more than the kernels
@@ -1266,7 +1291,7 @@ def _fused_forward(tier, g, yp, mask_p, tau, A, B, keep, precision, layout, keep
     xp = _new(g.image_shape(), dev)
     frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
     _call(tier.prefix + "_forward", g, K, yp, mask_p, tau, A, B, z, r, maps, xp, frags, _new((tier.patch_floats(g),), dev),
-          PRECISION[precision] | _lay_in(layout), *mp)
+          PRECISION[precision] | _lay_in(layout) | (TAU_PER_PLANE if planes else 0), *mp)
     return xp, z[K - 1], (z if keep else [z[K - 1]]), (r if keep else []), maps
 
 
@@ -1287,7 +1312,7 @@ def _fused_tangent(tier, g, vp, mask_p, A, B, maps, keep, precision, layout, las
 
 
 def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision, maps, layout, dyp, dtau,
-                    cmap=None, tslope=None, dcmap=None):
+                    cmap=None, tslope=None, dcmap=None, planes=False):
     K = len(A)
     dev = yp.device
     _check_map(g, _buf(dcmap, "dcmap"))
@@ -1303,15 +1328,17 @@ def _fused_backward(tier, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, p
     if g_xp is None:
         g_xp = torch.zeros(g.image_shape(), device=dev, dtype=torch.float32)
     g_xp, g_z, c, mask_p = _dev(g_xp, "g_xp"), _opt(g_z, "g_z"), _opt(c, "c"), _opt(mask_p, "mask")
+    if planes:
+        _plane_levels(g, c, True)
     dt = _dt_sweep(g, K, dt)
-    _check_data_grads(g, K, dyp, dtau)
+    _check_data_grads(g, K, dyp, dtau, rows=_plane_rows(g, planes))
     dA, dB = _filter_grads(g, K, dev)
     du = tier.code_buffers(g, layout, dev, 2 if K > 1 else 1)
     frags = torch.empty(K * tier.frag_bytes(g), device=dev, dtype=torch.uint8)
     _call(tier.prefix + "_backward", g, K, yp, mask_p, c, A, B, codes, resid, list(maps), g_xp, g_z, dA, dB, dt, du[0],
           du[1 if K > 1 else 0], _new(g.image_shape(), dev), frags, _new((tier.patch_floats(g),), dev),
           _new((_dtau_partial_floats(tier, g, cmap is not None),), dev), *tier.reverse_ws(g, dev),
-          PRECISION[precision] | _lay_in(layout), dyp, dtau, *mp)
+          PRECISION[precision] | _lay_in(layout) | (TAU_PER_PLANE if planes else 0), dyp, dtau, *mp)
     return dA, dB
 
 
@@ -1324,10 +1351,10 @@ def fused_iter(g: Geometry, r, zin, tau, frags, sgn, patches, precision="split3"
 
 
 def fusedg_iter(g: Geometry, r, zin, tau, frags, sgn, patches, out=None, map_out=None, lay_in="nchw", lay_out="nchw",
-                precision="split3"):
+                precision="split3", planes=False):
     """precision: "split4" asks the tile kernel for its four-product instances; the strip kernels take "split3" only
-    (CDL_EUNSUPPORTED otherwise)."""
-    return _fused_iter(_FUSEDG, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out)
+    (CDL_EUNSUPPORTED otherwise).  planes: tau is (N*D, M), a threshold row per (sample, depth) plane (CDL_TAU_PER_PLANE)."""
+    return _fused_iter(_FUSEDG, g, r, zin, tau, frags, sgn, patches, precision, out, map_out, lay_in, lay_out, planes=planes)
 
 
 def fused_stage_bwd(g: Geometry, thin, base, gate, frags, patches, dtau_partial, do_synth,
@@ -1368,10 +1395,11 @@ def fused_forward(g: Geometry, yp, mask_p, tau, A, B, keep, precision="split3", 
     return _fused_forward(_FUSED2D, g, yp, mask_p, tau, A, B, keep, precision, layout, keep_maps, cmap, tslope)
 
 
-def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep_maps=False):
+def fusedg_forward(g: Geometry, yp, mask_p, tau, A, B, keep, layout="nchw", keep_maps=False, planes=False):
     """Whole forward sweep in one C call (cdl_fusedg_forward); same contract as fused_forward: codes[:-1] come back
-    in `layout` ("nchw", or "rsc" where fusedg_code_layout allows it), codes[-1] = z_K as (N,M,..)."""
-    return _fused_forward(_FUSEDG, g, yp, mask_p, tau, A, B, keep, "split3", layout, keep_maps)
+    in `layout` ("nchw", or "rsc" where fusedg_code_layout allows it), codes[-1] = z_K as (N,M,..).  planes: tau is
+    (K, N*D, M), a threshold row per (sample, depth) plane (CDL_TAU_PER_PLANE: one noise level per frame)."""
+    return _fused_forward(_FUSEDG, g, yp, mask_p, tau, A, B, keep, "split3", layout, keep_maps, planes=planes)
 
 
 def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, precision="split3", maps=None,
@@ -1388,10 +1416,12 @@ def fused_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt
 
 
 def fusedg_backward(g: Geometry, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, maps=None, layout="nchw",
-                    dyp=None, dtau=None):
+                    dyp=None, dtau=None, planes=False):
     """Whole reverse sweep in one C call (cdl_fusedg_backward); returns (dA list, dB list), fills dt (K,2,M) [and
-    dyp, dtau: see fused_backward].  `layout`: that of codes[:-1] (and of the du buffers allocated here)."""
-    return _fused_backward(_FUSEDG, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, "split3", maps, layout, dyp, dtau)
+    dyp, dtau: see fused_backward].  `layout`: that of codes[:-1] (and of the du buffers allocated here).  planes: the
+    forward ran with per-plane thresholds -- c is (N*D) and dtau (K, N*D, M)."""
+    return _fused_backward(_FUSEDG, g, yp, mask_p, c, A, B, codes, resid, g_xp, g_z, dt, "split3", maps, layout, dyp, dtau,
+                           planes=planes)
 
 
 def fused_tangent(g: Geometry, vp, mask_p, A, B, maps, keep, precision="split3", layout="blocked", last=False):

@@ -23,12 +23,14 @@ def gen_bayer_mask3d(x):
     return torch.ones_like(x)
 
 
-def _awgn(x, noise_std, generator=None):
+def _awgn(x, noise_std, generator=None, per_frame=False):
     # The draws happen on the generator's device and in the reference's order (rand for sigma, then randn): with a
     # CPU generator (e.g. torch.default_generator) a GPU run sees the very noise the reference's CPU path draws.
     dev = generator.device if generator is not None else x.device
     if isinstance(noise_std, (list, tuple)):
         shape = (len(x),) + (1,) * (x.dim() - 1)
+        if per_frame:
+            shape = (len(x), 1, x.shape[2], 1, 1)
         sigma = noise_std[0] + (noise_std[1] - noise_std[0]) * torch.rand(
             shape, device=dev, generator=generator).to(x.device)
     else:
@@ -42,9 +44,13 @@ def awgn(input, noise_std, generator=None):
     return _awgn(input, noise_std, generator)
 
 
-def awgn3d(input, noise_std, generator=None):
-    """Same for (N,C,D,H,W) clips, sigma shaped (N,1,1,1,1) (utils.py:43-55)."""
-    return _awgn(input, noise_std, generator)
+def awgn3d(input, noise_std, generator=None, per_frame=False):
+    """Same for (N,C,D,H,W) clips, sigma shaped (N,1,1,1,1) (utils.py:43-55).  per_frame (not in the reference): a
+    (lo, hi) range draws one level per (sample, frame), sigma shaped (N,1,D,1,1) -- the form the nets take as one noise
+    level per frame; a fixed noise_std is used as it is."""
+    if per_frame and input.dim() != 5:
+        raise ValueError(f"per_frame needs an (N,C,D,H,W) clip, got {tuple(input.shape)}")
+    return _awgn(input, noise_std, generator, per_frame)
 
 
 def sigma_to_code_grid(sigma_img, s):

@@ -161,9 +161,13 @@ class Plan:
         return tuple(slice(a[i].w0 // scale, a[i].w1 // scale) for a, i in zip(self.axes, idx))
 
     def gather(self, x, pairs, scale=1):
-        """The (window, sample) `pairs` of x (N, C, *dims / scale) stacked along the batch axis."""
+        """The (window, sample) `pairs` of x (N, C, *dims / scale) stacked along the batch axis.  An axis on which x has
+        extent 1 is kept whole: per-frame noise levels (N,1,D,1,1) are cropped along depth only."""
         wins = self.windows
-        return torch.cat([x[(slice(n, n + 1), slice(None)) + self.slices(wins[w], scale)] for w, n in pairs], 0).contiguous()
+
+        def cut(w):
+            return tuple(slice(None) if e == 1 else sl for e, sl in zip(x.shape[2:], self.slices(wins[w], scale)))
+        return torch.cat([x[(slice(n, n + 1), slice(None)) + cut(w)] for w, n in pairs], 0).contiguous()
 
     def assemble(self, outs, blend="crop"):
         """outs[w] (N, C, *window shape), in the order of `windows`, put together as (N, C, *dims): one axis after the

@@ -583,6 +583,18 @@ int cdl_gabor_filter_banks_bwd(int nbanks, const float *const *alpha, const floa
 #define CDL_LAY_RSC   3
 #define CDL_LAYOUT_IN(l)  ((l) << 5)
 #define CDL_LAYOUT_OUT(l) ((l) << 7)
+/* cdl_fusedg_* only, OR-ed into `precision` beside the bits above: one threshold row per (sample, depth) PLANE instead of
+ * one per sample -- one noise level per frame of a clip.  Every work item of the tile kernel and of
+ * the grouped strip kernel lies in one plane (n, zd) and loads its thresholds once, so the bit only changes which row that
+ * load reads: n * D + zd instead of n.  With the bit set
+ *   cdl_fusedg_iter_fwd            tau is (N*D, M)
+ *   cdl_fusedg_forward             tau is (K, N*D, M)
+ *   cdl_fusedg_backward            c is (N*D): dt[k,1,m] = sum_{n,d} c[n,d] * (sum over the tiles of plane (n,d));
+ *                                  dtau (nullable) is (K, N*D, M).  Same partial rows in the same order as without the bit.
+ *   cdl_fusedg_stage_bwd           unchanged (the reverse stage reads no threshold); cdl_fusedg_tangent does not take it
+ * and the strip kernel proper (2-D, D == 1: CDL_PLAN_STRIP geometries) returns CDL_EINVAL.  With the bit clear every call
+ * enqueues exactly the launches it enqueued before the bit existed. */
+#define CDL_TAU_PER_PLANE 512
 
 /* ==== fused MFMA path (cdl_fused2d.hip): 2-D, C = 1, stride 1, odd P <= 7, M in {32, 64} =========
  * One launch per unrolled iteration replaces the whole body of net.py:87
@@ -754,6 +766,11 @@ int cdl_fusedg_assemble(const cdl_geom *g, const float *patches, const float *ma
                         float *acc /*nullable*/, int acc_add, void *stream);
 int cdl_fusedg_dtau_reduce(const cdl_geom *g, const float *dtau_partial, const float *c /*N, nullable*/, float *dt0,
                            float *dt1, float *dtau_n /*N,M, nullable*/, void *stream);
+/* The same reduction with the (sample, depth) plane as the "sample" (CDL_TAU_PER_PLANE): c is (N*D), dt1[m] =
+ * sum_{n,d} c[n,d] * (sum over the tiles of plane (n,d)), dtau_nd (nullable) the per-plane sums (N*D, M).  dt0 is
+ * cdl_fusedg_dtau_reduce's bit for bit; CDL_EINVAL where the strip kernel proper takes the geometry. */
+int cdl_fusedg_dtau_reduce_planes(const cdl_geom *g, const float *dtau_partial, const float *c /*N*D, nullable*/,
+                                  float *dt0, float *dt1, float *dtau_nd /*N*D,M, nullable*/, void *stream);
 /* Whole sweeps (arguments as cdl_fused2d_forward / _backward, the data gradients dyp / dtau included).  The reverse sweep takes the filter gradients
  * dA_k = -du_k (x) r_k, dB_k = z_k (x) q_k from cdl_wgrad: wgrad_ws = cdl_wgrad_workspace_floats(g) floats. */
 int cdl_fusedg_forward(const cdl_geom *g, int K, const float *yp, const float *mask /*nullable*/, const float *tau,
