@@ -234,3 +234,185 @@ def crafted_split4_inputs(N, M, P, H, W, seed):
     tap = torch.randint(0, P * P, (M,), generator=gen)
     w.view(M, P * P)[torch.arange(M), tap] = 0.25 * operand(M)
     return r, w
+
+
+# ------------------------------------------------------------------------------------------------ exactly-summable stages
+# DESIGN.md section 41.  The bound above grows with the number of terms and rounding errors with its square root, so in the
+# long sums (synthesis, threshold sums, filter gradients) a wrong kernel passes it.  The second instrument is
+# generic_arith_restate's: operands whose kept products are multiples of one quantum and few enough that every partial sum in
+# every order is an fp32 number (S_e / quantum < CAP_QUANTA), so a correct kernel EQUALS the model.  A stage is two chained
+# halves and the second half's operand is the first half's output, so three recipes are needed:
+#   "int"    every operand an integer in {0, +-1, +-2}, tau integer per (n, m), c powers of two: every intermediate is an
+#            integer below 2^8 with no lo part and the whole launch, its assemble and its reductions are exact (quantum 1);
+#   "hilo-a" r / thin, wA, base hi + lo operands (hi in {0, +-1}, lo in {0, +-2^-9}), tau multiples of 2^-9: the ANALYSIS half
+#            is exact (quantum 2^-9); z' then carries up to 15 bits and the synthesis half is held to b;
+#   "hilo-p" the analysis half passes a hi + lo operand through the registers (an all-zero wA bank with tau in {0, 2}, or
+#            single-tap +-1 filters with tau = 0 in a first stage), so the SYNTHESIS half, the threshold sums and the dA_k
+#            ride get hi + lo operands and are exact.
+# The quantum follows from the arithmetic: bf16 keeps hi.hi (integers here); split3 adds hi.lo + lo.hi (2^-9); split4 adds lo.lo
+# (2^-18), under which the cap would ask for S_e < 8 -- so under split4 the filter banks (and the thin operand of a filter
+# gradient) carry no lo part, and lo.lo stays with the crafted-input tests.  The generic module is imported where it is used:
+# it imports this one.
+RECIPES = ("int", "hilo-a", "hilo-p")
+EXACT_HELD = {"int": ("code", "thin", "dt", "dA"), "hilo-a": ("code",), "hilo-p": ("code", "thin", "dt", "dA")}
+
+
+def _G():
+    import generic_arith_restate as G
+    return G
+
+
+def hi_only(x):
+    """The operand with its lo part removed (a bf16 value as fp32)."""
+    return bf16_rne(x).float()
+
+
+def product_quantum(precision, a32, b32):
+    """The quantum of the kept products of two exact operands, derived from their parts: 1 where only hi.hi is kept or neither
+    has a lo part, 2^-9 where one side's lo meets the other's hi, 2^-18 where lo.lo is kept and both sides have a lo part."""
+    la, lb = bool(parts(a32)[1].any()), bool(parts(b32)[1].any())
+    kept = _KEPT[precision]
+    q = 1.0
+    if ((1, 0) in kept and la) or ((0, 1) in kept and lb):
+        q = 2.0 ** -9
+    if (1, 1) in kept and la and lb:
+        q = 2.0 ** -18
+    return q
+
+
+def operand_quantum(x32):
+    """The quantum of an fp32 term added as it is (a base, a threshold, a subtrahend): 2^-9 if it has a lo part, else 1."""
+    return 2.0 ** -9 if bool(parts(x32)[1].any()) else 1.0
+
+
+def exact_stage_operands(recipe, precision, ish, csh, fsh, seed, first=False, density=(0.5, 0.25, 0.5)):
+    """The operands of one stage under a recipe, for any geometry of the fused tiers: images of shape ish (r, thin, r2, sub,
+    mask), codes of shape csh (zin, base, gate), banks of shape fsh (wA, wB), tau (N, M), c (N).  density: images, banks,
+    gate.  first: the pass-through bank of a FIRST stage (single taps) instead of the all-zero one.  Every tensor has a
+    generator of its own."""
+    G = _G()
+    N, M = csh[:2]
+    integer = recipe == "int"
+    gens = iter(torch.Generator().manual_seed(1000 * seed + i) for i in range(32))
+    op = lambda shape, dens, integ=integer: G._exact_operand(tuple(shape), dens, integ, next(gens))
+    e = dict(recipe=recipe, r=op(ish, density[0]), thin=op(ish, density[0]), r2=op(ish, density[0]), sub=op(ish, density[0]),
+             wA=op(fsh, density[1]), wB=op(fsh, density[1]), zin=op(csh, 0.4), base=op(csh, 1.0), gate=op(csh, density[2], True))
+    e["mask"] = (torch.rand(ish, generator=next(gens)) < 0.5).float()
+    e["c"] = torch.exp2(torch.arange(N) % 3 - 1.0)                           # 1/2, 1, 2, ...
+    g = next(gens)
+    if integer:
+        e["tau"] = torch.randint(0, 4, (N, M), generator=g).float()
+        e["tau"][:, M // 3] = 1024.0                                         # silences a whole channel
+    elif recipe == "hilo-a":
+        e["tau"] = torch.randint(0, 600, (N, M), generator=g).float() * 2.0 ** -9 * (torch.rand(N, M, generator=g) < 0.8)
+    else:
+        e["tau"] = 2.0 * (torch.rand(N, M, generator=g) < 0.3).float()
+        e["tau"][:, M // 3] = 2.0
+        e["tau"][:, 0] = 0.0
+        # the reverse forms: ONE non-zero channel per code pixel (generic_arith_restate.exact_inputs' F), so that the threshold
+        # sums and the filter gradients stay under the cap
+        ch = torch.randint(0, M, (N, 1) + tuple(csh[2:]), generator=g)
+        e["base"] = torch.zeros(csh).scatter_(1, ch, op((N, 1) + tuple(csh[2:]), 1.0))
+        e["wA"] = torch.zeros(fsh)
+        if first:
+            taps = e["wA"][0].numel()
+            e["wA"].view(M, taps)[torch.arange(M), torch.randint(0, taps, (M,), generator=g)] = \
+                torch.randint(0, 2, (M,), generator=g).float() * 2 - 1
+            e["tau"] = torch.zeros(N, M)
+    if precision == "split4" and not integer:
+        e["wA"], e["wB"], e["r2"] = hi_only(e["wA"]), hi_only(e["wB"]), hi_only(e["r2"])
+    return e
+
+
+def exact_stage_inputs(recipe, precision, N, M, P, H, W, seed, first=False):
+    """exact_stage_operands at the 2-D tier's geometry (one image channel, P x P filters)."""
+    return exact_stage_operands(recipe, precision, (N, 1, H, W), (N, M, H, W), (M, 1, P, P), seed, first)
+
+
+def _value_and_abs(op, a, b, precision):
+    """(value, S_e) of the kept products: `_product` without the term count."""
+    val = S = None
+    for (i, j) in _KEPT[precision]:
+        v, s = op(a[i], b[j]), op(a[i].abs(), b[j].abs())
+        val, S = (v, s) if val is None else (val + v, S + s)
+    return val, S
+
+
+def _rows(x):
+    """A code tensor with its depth (if any) folded into its rows, (N,M,D*H,W): what the elementwise helpers above take."""
+    return x.reshape(x.shape[0], x.shape[1], -1, x.shape[-1])
+
+
+def exact_stage_model(mode, e, precision, blk16_in=False, blk16_out=False, masked=True, ride=False, ops=None, wgrad_P=None):
+    """{output: (value, S_e, quantum)} of one stage on exact operands, each half fed the MODEL's own output of the half before
+    it: "code" (z' / du as stored: bf16_rne of it for a bf16-stored output), "thin" (the assembled r_next = mask B z' - sub of
+    a forward stage, q = -mask B du of a reverse one), "dt" and "dA" (reverse stages).  The synthesis half and the dA_k ride
+    take the code as stored; the threshold sums take du_k BEFORE its rounding for a bf16-stored buffer (k_stage adds the
+    register value in its epilogue, in front of bf16_round: the sums are the more accurate for it, and an fp32 input layout
+    shows the difference).  mode: first | fwd | bwd | bwd0 (a reverse stage without base).  ops: (analysis, synthesis) of the
+    geometry, this module's by default.  Which outputs a recipe holds to equality is EXACT_HELD; the cap is asserted on
+    S_e / quantum by the CPU tests."""
+    ana, syn = (analysis, synthesis) if ops is None else ops
+    stored = lambda x: bf16_rne(x).float() if blk16_in else x
+    if mode in ("first", "fwd"):
+        val, S = _value_and_abs(ana, parts(e["r"]), parts(e["wA"]), precision)
+        q = product_quantum(precision, e["r"], e["wA"])
+        if mode == "fwd":
+            val, S = stored(e["zin"]).double() - val, S + stored(e["zin"]).double().abs()
+            q = min(q, operand_quantum(stored(e["zin"])))
+        code, S = shrink(_rows(val), e["tau"]).reshape(val.shape), S + e["tau"].double().reshape(e["tau"].shape + (1,) * (val.dim() - 2))
+        q = min(q, operand_quantum(e["tau"]))
+    else:
+        val, S = _value_and_abs(ana, parts(e["thin"]), parts(e["wA"]), precision)
+        q = product_quantum(precision, e["thin"], e["wA"])
+        if mode == "bwd":
+            val, S = val + stored(e["base"]).double(), S + stored(e["base"]).double().abs()
+            q = min(q, operand_quantum(stored(e["base"])))
+        on = e["gate"] != 0
+        code, S = val * on, S * on
+    full = code                                              # a bf16-stored du_k enters the threshold sums BEFORE its rounding
+    if blk16_out:
+        code = bf16_rne(code)
+    out = {"code": (code, S, q)}
+    z = code.float()
+    assert torch.equal(z.double(), code), "the code of an exact recipe is an fp32 number"
+    val, S = _value_and_abs(syn, parts(z, blk16_out), parts(e["wB"]), precision)
+    q = product_quantum(precision, z, e["wB"])
+    m = e["mask"].double() if masked else 1.0
+    if mode in ("first", "fwd"):
+        out["thin"] = (m * val - e["sub"].double(), m * S + e["sub"].double().abs(), min(q, operand_quantum(e["sub"])))
+    else:
+        out["thin"] = (-(m * val), m * S, q)
+        assert torch.equal(full.float().double(), full)
+        zf, onf, negf = _rows(full.float()), _rows(on), _rows(e["gate"] < 0)
+        dt, _ = dtau_sums(zf, onf, negf, e["c"])
+        pa = zf.double().abs().mul(onf).sum(dim=(2, 3))
+        out["dt"] = (dt, torch.stack([pa.sum(0), (e["c"].double().abs()[:, None] * pa).sum(0)]),
+                     operand_quantum(full.float()) * min(1.0, float(e["c"].min())))
+        if ride:
+            val, S = _value_and_abs(lambda a, b: filter_grad(a, b, wgrad_P), parts(z, blk16_out), parts(e["r2"]), precision)
+            out["dA"] = (-val, S, product_quantum(precision, z, e["r2"]))
+    return out
+
+
+def exact_wgrad_model(X, T, alpha, P, precision, blk16=False):
+    """(value, S_e, quantum) of k_wgrad2d's alpha * X (x) im2col(T) on exact operands; alpha = +-1."""
+    Xs = hi_only(X) if blk16 else X
+    val, S = _value_and_abs(lambda a, b: filter_grad(a, b, P), parts(Xs, blk16), parts(T), precision)
+    return alpha * val, S, product_quantum(precision, Xs, T)
+
+
+def cap_quanta(S, quantum):
+    """The largest S_e of an output in quanta: what the cap (generic_arith_restate.CAP_QUANTA) is asserted on."""
+    return float(S.max()) / quantum if S.numel() else 0.0
+
+
+def violations_exact(got, model, quantum=1.0):
+    """(number of elements that are NOT equal in value to the model, largest |got - model| in quanta): the predicate of the
+    exact inputs.  The count is of the negated predicate, so a NaN is a violation (and makes `worst` infinite); -0 equals +0.
+    A bf16-stored output is compared as the values it decodes to, against a model that is bf16_rne of the exact value."""
+    g, m = got.double(), model.double()
+    bad = int((~(g == m)).sum())
+    err = (g - m).abs() / quantum
+    err = torch.where(err.isnan(), torch.full_like(err, float("inf")), err)
+    return bad, (float(err.max()) if err.numel() else 0.0)

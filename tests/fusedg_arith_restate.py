@@ -142,3 +142,31 @@ def crafted_split4_inputs(N, C, M, P, sp, seed):
     tap = torch.randint(0, taps, (M,), generator=gen)
     w.view(M, taps)[torch.arange(M), tap] = 0.25 * operand(M)
     return r, w
+
+
+# ------------------------------------------------------------------------------------------------ exactly-summable stages
+# the three recipes of fused2d_arith_restate (its comment has them) at this tier's geometries.  The
+# generator, the cap and the quantum rules are generic_arith_restate's and the 2-D module's, imported; what is added is the
+# shapes (C > 1, depth, stride 2), the Bayer mosaic and this module's operators.
+from generic_arith_restate import CAP_QUANTA, _exact_operand, exact_cap_ok, exact_inputs, exact_term_quanta  # noqa: E402,F401
+from fused2d_arith_restate import (EXACT_HELD, RECIPES, cap_quanta, exact_stage_operands, hi_only,  # noqa: E402,F401
+                                   operand_quantum, product_quantum, violations_exact)
+
+
+def exact_stage_inputs(recipe, precision, N, C, M, P, sp, s, seed, first=False, bayer=False):
+    """The exact operands of one stage of a geometry of this tier (stage_inputs' arguments): fused2d_arith_restate's
+    exact_stage_operands, the mask the Bayer mosaic where the cell has it."""
+    ish = (N, C) + tuple(sp)
+    csh = (N, M) + tuple(sp[:-2]) + (sp[-2] // s, sp[-1] // s)
+    e = exact_stage_operands(recipe, precision, ish, csh, (M, C) + tuple(P), seed, first)
+    if bayer:
+        assert C == 3 and len(sp) == 2
+        e["mask"] = bayer_mask(N, *sp)
+    return e
+
+
+def exact_stage_model(mode, e, precision, s=1, masked=True):
+    """{output: (value, S_e, quantum)}: fused2d_arith_restate.exact_stage_model with this module's strided operators; mode
+    first | fwd | bwd | bwd0.  masked False: the assemble runs without a mask."""
+    return R2.exact_stage_model(mode, e, precision, masked=masked,
+                                ops=(lambda a, b: analysis(a, b, s), lambda a, b: synthesis(a, b, s)))

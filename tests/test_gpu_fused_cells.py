@@ -3,7 +3,8 @@ and without the dA_k ride -- against the float64 model of its arithmetic (fused2
 |got - model| <= b at every element, exact zeros off the support, the written map that of the output, every output bit
 for bit the same in a second call.  Geometry of test_gpu_stage_tile_phase.py: N = 2, 40 x 150, masked, 18 tiles, ragged in
 both axes, padding pixels in the blocked layouts; at the default grid (one tile per workgroup) and under CDL_FUSED_GRID=4
-(5, 5, 4, 4 tiles: the next tile's thin inputs are loaded across an image boundary and past the last tile)."""
+(5, 5, 4, 4 tiles: the next tile's thin inputs are loaded across an image boundary and past the last tile).  The same cells on
+exactly-summable inputs, where the outputs must EQUAL the model: the second half of the file."""
 import functools
 
 import pytest
@@ -310,3 +311,173 @@ def test_forward_sweep_launch_by_launch_against_the_float64_model(lay, prec, M, 
     log(f"cell forward-sweep M{M}P{P} {prec} {lay} g4".ljust(64) + f" (WY, MT, PREC, MODE, LIN, LOUT)={want} worst|err|/b "
         + " ".join(f"{k}={v:.2e}" for k, v in ratios.items()))
     assert not any(counts.values()), (counts, ratios)
+
+
+# ------------------------------------------------------------------------------------------------ exactly-summable inputs
+# operands on which every partial sum in every order is an fp32 number (the cap is asserted on the CPU,
+# test_fused2d_arith_cpu.py, for every input enumerated by exact_inputs_of_this_file), so the device must EQUAL the model at
+# every element.  Three recipes per cell (fused2d_arith_restate.RECIPES); EXACT_HELD names the outputs a recipe holds to
+# equality, the others stay with the bound.
+EXACT_G4 = [(64, 7, "split3"), (64, 7, "bf16")]               # CDL_FUSED_GRID=4: the thin prefetch across an image boundary
+EXACT_CASES = [(mode, M, P, prec, recipe, grid)
+               for grid, rows in (("gdef", ROWS), ("g4", EXACT_G4)) for (M, P, prec) in rows
+               for mode in ("first", "fwd", "bwd", "ride") for recipe in R.RECIPES]
+
+
+@functools.lru_cache(maxsize=4)
+def _exact_operands(recipe, M, P, no_bank_lo, first):
+    return R.exact_stage_inputs(recipe, "split4" if no_bank_lo else "split3", N, M, P, H, W, seed=31 + M + P, first=first)
+
+
+_EXACT_SECONDS = [0.0]                                        # the time the exact cases of this file have added, for the parity log
+
+
+def _added(t0):
+    import time
+    _EXACT_SECONDS[0] += time.perf_counter() - t0
+    return f"{time.perf_counter() - t0:.2f} s (exact cases of this file so far: {_EXACT_SECONDS[0]:.1f} s)"
+
+
+def exact_data(mode, M, P, prec, recipe):
+    """The operands of an exact case; they depend on the arithmetic only through split4's rule (no lo part in the banks) and
+    on the mode only through the pass-through bank of a first stage."""
+    return _exact_operands(recipe, M, P, prec == "split4" and recipe != "int", mode == "first" and recipe == "hilo-p")
+
+
+@functools.lru_cache(maxsize=8)
+def exact_model(mode, M, P, prec, recipe, blk16_in, blk16_out):
+    """{output: (value, S_e, quantum)} of an exact case, once per rounding of the fat input and output."""
+    return R.exact_stage_model("bwd" if mode == "ride" else mode, exact_data(mode, M, P, prec, recipe), prec, blk16_in, blk16_out,
+                               ride=mode == "ride", wgrad_P=P)
+
+
+@functools.lru_cache(maxsize=2)
+def exact_wgrad_data(M, P, prec, variant):
+    """k_wgrad2d's operands: F, F2 with one non-zero channel per code pixel (generic_arith_restate.exact_inputs), x, x2 the thin
+    operands -- without lo parts under split4."""
+    import generic_arith_restate as G
+    d = G.exact_inputs(N, 1, M, (P, P), (H, W), 1, seed=57 + M + P, integer=variant == "integer", only=("x", "x2", "F", "F2"))
+    if prec == "split4":
+        d["x"], d["x2"] = R.hi_only(d["x"]), R.hi_only(d["x2"])
+    return d
+
+
+def exact_wgrad_model(M, P, prec, variant, blk16):
+    d = exact_wgrad_data(M, P, prec, variant)
+    return [R.exact_wgrad_model(d["F"], d["x2"], -1.0, P, prec, blk16), R.exact_wgrad_model(d["F2"], d["x"], 1.0, P, prec, blk16)]
+
+
+def exact_inputs_of_this_file():
+    """Every exact input a test below feeds a kernel, with the model that is compared: ("stage", mode, M, P, prec, recipe,
+    blk16_in, blk16_out) and ("wgrad", M, P, prec, variant, blk16).  The grid does not change the operands."""
+    out = set()
+    for (mode, M, P, prec, recipe, _) in EXACT_CASES:
+        for (lin, lout) in PAIRS[mode]:
+            out.add(("stage", mode, M, P, prec, recipe, lin == B16 and mode != "first", lout == B16))
+    for (M, P, prec) in ROWS:
+        for variant in ("hilo", "integer"):
+            for blk16 in (False, True):
+                out.add(("wgrad", M, P, prec, variant, blk16))
+    return sorted(out)
+
+
+def _pin_stage(o, t, mode, M, prec, lin, lout):
+    """The one k_stage launch of the trace, with the template arguments asked for."""
+    sites = launch_sites(t)
+    keys = [k for k in sites if k.startswith(STAGE)]
+    assert len(keys) == 1 and len(sites[keys[0]]) == 1, sites.keys()
+    tpl = sites[keys[0]][0].template()
+    want = dict(WY=2, MT=M // 32, PREC=o.PRECISION[prec], MODE=MODE_ID[mode], LIN=LAY_ID[lout if mode == "first" else lin],
+                LOUT=LAY_ID[lout])
+    assert {k: tpl[k] for k in want} == want and keys[0].split(",")[-2] == ("true" if mode == "ride" else "false"), (tpl, keys)
+    return tpl
+
+
+@pytest.mark.parametrize("mode,M,P,prec,recipe,grid", EXACT_CASES)
+def test_exact_inputs_hold_the_stage_to_equality(mode, M, P, prec, recipe, grid, hip_env):
+    """Every (mode, layout pair) of PAIRS on exactly-summable operands: the outputs the recipe holds (EXACT_HELD) equal the
+    model in value at every element, a bf16-stored code equals bf16_rne(model), the written map is that of the code; the outputs
+    it does not hold stay inside the bound of the model fed the device's own z' / du."""
+    import time
+    import generic_arith_restate as G
+    import cdlnet_video_amd as cva
+    o = cva.ops
+    t0 = time.perf_counter()
+    if grid == "g4":
+        hip_env("CDL_FUSED_GRID", "4")
+    g = _geom(o, M, P)
+    e = exact_data(mode, M, P, prec, recipe)
+    ev = {k: v.cuda() for k, v in e.items() if torch.is_tensor(v)}
+    ev["bits"] = o.fused_support_map(g, ev["gate"])
+    frags = o.fused_prep(ev["wA"], ev["wB"])
+    on, neg = e["gate"] != 0, e["gate"] < 0
+    held = R.EXACT_HELD[recipe]
+    failures = []
+    for (lin, lout) in PAIRS[mode]:
+        tag = f"cell exact {recipe} {mode} M{M}P{P} {prec} {lin}->{lout} {grid}"
+        res, t = _run_cell(o, g, mode, lin, lout, prec, ev, frags)
+        tpl = _pin_stage(o, t, mode, M, prec, lin, lout)
+        assert _pad_untouched(g, res["code"], lout), tag
+        model = exact_model(mode, M, P, prec, recipe, lin == B16 and mode != "first", lout == B16)
+        code = o.fused_to_nchw(g, res["code"], lout).cpu()
+        counts, quanta = {}, {}
+        for name in ("code", "thin", "dt", "dA"):
+            if name in model and name in held:
+                val, S, q = model[name]
+                counts[name], _ = R.violations_exact(code if name == "code" else res[name].cpu(), val, q)
+                quanta[name] = R.cap_quanta(S, q)
+                assert quanta[name] < G.CAP_QUANTA, (tag, name)
+        fwd = mode in ("first", "fwd")
+        if fwd:
+            # the written map is that of the output, which equals the model (the sign bit of a zero is not the model's to say)
+            counts["map"] = int((res["map"] != o.fused_support_map(g, code.cuda())).sum())
+        else:
+            counts["off-support"] = R.zeros_off_support(code, on)
+        if "thin" not in held:                                # the synthesis half of the analysis recipe: the bound, as today
+            counts["thin<=b"], _ = R.violations_fp32(res["thin"].cpu(), *R.synth_assemble(
+                code, e["wB"], prec, lout == B16, e["mask"], e["sub"] if fwd else None, 1.0 if fwd else -1.0))
+            if not fwd:
+                counts["dt<=b"], _ = R.violations_fp32(res["dt"].cpu(), *R.dtau_sums(code, on, neg, e["c"]))
+            if mode == "ride":
+                counts["dA<=b"], _ = R.violations_fp32(res["dA"].cpu(), *R.wgrad(code, e["r2"], -1.0, P, prec, lout == B16))
+        log(f"{tag:72s} {tpl} violations={counts} largest S_e in quanta "
+            + " ".join(f"{k}={v:.0f}" for k, v in quanta.items()) + f" cap={G.CAP_QUANTA:.0f}")
+        if any(counts.values()):
+            failures.append((tag, counts))
+    log(f"cell exact {recipe} {mode} M{M}P{P} {prec} {grid}: {len(PAIRS[mode])} pairs in {_added(t0)}")
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("lay", LAYS)
+@pytest.mark.parametrize("M,P,prec", ROWS)
+def test_exact_inputs_hold_the_filter_gradient_to_equality(M, P, prec, lay):
+    """k_wgrad2d, pair and single, on the one-channel-per-pixel code operands: equality at every filter tap."""
+    import time
+    import generic_arith_restate as G
+    import cdlnet_video_amd as cva
+    o = cva.ops
+    t0 = time.perf_counter()
+    g = _geom(o, M, P)
+    ws = o.fused_wgrad_workspace(g, "cuda")
+    for variant in ("hilo", "integer"):
+        d = exact_wgrad_data(M, P, prec, variant)
+        dv = {k: v.cuda() for k, v in d.items() if torch.is_tensor(v)}
+        X0, X1 = o.fused_from_nchw(g, dv["F"], lay), o.fused_from_nchw(g, dv["F2"], lay)
+        with o.trace() as t:
+            pair = o.fused_wgrad(g, ws, X0, dv["x2"], -1.0, X1, dv["x"], 1.0, precision=prec, layout=lay)
+            single = o.fused_wgrad(g, ws, X1, dv["x"], 1.0, precision=prec, layout=lay, tiles_reversed=True)
+            torch.cuda.synchronize()
+        recs = [r for k, v in launch_sites(t).items() if k.startswith("cdl_fused2d.hip:k_wgrad2d<") for r in v]
+        assert len(recs) == 2
+        for r in recs:
+            tpl = r.template()
+            assert (tpl["MT"], tpl["PREC"], tpl["LAY"]) == (M // 32, o.PRECISION[prec], LAY_ID[lay]), tpl
+        m0, m1 = exact_wgrad_model(M, P, prec, variant, lay == B16)
+        counts = {name: R.violations_exact(got.cpu(), m[0], m[2])[0]
+                  for name, got, m in (("pair0", pair[0], m0), ("pair1", pair[1], m1), ("single", single[0], m1))}
+        quanta = max(R.cap_quanta(m[1], m[2]) for m in (m0, m1))
+        assert quanta < G.CAP_QUANTA
+        log(f"cell exact wgrad {variant} M{M}P{P} {prec} {lay}".ljust(72) + f" {tpl} violations={counts} largest S_e in quanta "
+            f"{quanta:.0f} cap={G.CAP_QUANTA:.0f}")
+        assert not any(counts.values()), (variant, counts)
+    log(f"cell exact wgrad M{M}P{P} {prec} {lay}: {_added(t0)}")

@@ -4,7 +4,8 @@ k_strip<P,S,MTP,MODE,MAPPED> (cdl_strip.hip) -- against the float64 model of its
 DESIGN.md section 33): |got - model| <= b at every element of z' / du, exact zeros off the map, the written map that of the
 output, the assembled r_next / q (NaN-filled patches) and the threshold sums inside the bound of the model fed the device's
 own z' / du, every output bit for bit the same in a second call, with and without map_out, with do_synth on and off, and
-(strip kernels) in the row-strip layout.  Each cell pins its template arguments from the launch trace.
+(strip kernels) in the row-strip layout.  Each cell pins its template arguments from the launch trace.  The same cells on
+exactly-summable inputs, where the outputs must EQUAL the model: the last part of the file.
 
 Shapes: the smallest with every kind of boundary.  Tile kernels (64 x 16 tiles): N = 2, plane 20 x 70 = 2 x 2 ragged tiles,
 D = 3 for Pd = 3 and D = 4 for Pd = 5, 7 (fewer frames than depth taps: absent planes); M = 24 (MT = 1) and 56 (MT = 2),
@@ -372,3 +373,120 @@ def test_forward_sweep_launch_by_launch_against_the_float64_model(kind, cid):
     assert torch.equal(zK, codes[-1])
     log(f"gcell forward-sweep {kind} {cid} {prec}".ljust(56) + f" {want[0]} worst|err|/b " + " ".join(f"{k}={v:.2e}" for k, v in ratios.items()))
     assert not any(counts.values()), (counts, ratios)
+
+
+# ------------------------------------------------------------------------------------------------ exactly-summable inputs
+# operands on which every partial sum in every order is an fp32 number (the cap is asserted on the CPU,
+# test_fusedg_arith_cpu.py, for every input enumerated by exact_inputs_of_this_file), so the device must EQUAL the model at
+# every element.  The integer chain runs every cell of every kernel; the two hi + lo recipes once per (P, G) and per (P, S),
+# MT alternating, on every kernel; the strip kernels with the row-strip layout on one side in one case per P.
+def _alternating(cells, key):
+    """One cell per value of `key`, MT = 1, 2, 1, ... (strip cells: MT = 1 .. 6 in turn) where the table has it."""
+    out, groups = [], {}
+    for c in cells:
+        groups.setdefault(key(c), []).append(c)
+    for i, (_, cs) in enumerate(sorted(groups.items())):
+        if "MT" in cs[0].want:                                # tile cells: MT = 1, 2 in turn; G = 3: the c3 and the d form in turn
+            cs = [c for c in cs if c.want["MT"] == 1 + i % 2] or cs
+            out.append(cs[(i // 4) % len(cs)])
+        else:
+            out.append(cs[i % len(cs)])
+    return out
+
+
+HILO_TILE = _alternating(TILE_CELLS, lambda c: (c.want["P"], c.want["G"]))
+HILO_STRIP = _alternating(STRIP_CELLS, lambda c: (c.want["P"], c.s))
+RSC_CASES = {("stripg", c.id) for c in HILO_TILE if c.want["G"] == 3} | {("strip", c.id) for c in HILO_STRIP if c.s == 2}
+EXACT_CASES = ([(kind, c.id, prec, "int") for c in TILE_CELLS for kind, prec in (("tile", "split3"), ("tile", "split4"), ("stripg", "split3"))]
+               + [("strip", c.id, "split3", "int") for c in STRIP_CELLS]
+               + [(kind, c.id, prec, recipe) for c in HILO_TILE for recipe in ("hilo-a", "hilo-p")
+                  for kind, prec in (("tile", "split3"), ("tile", "split4"), ("stripg", "split3"))]
+               + [("strip", c.id, "split3", recipe) for c in HILO_STRIP for recipe in ("hilo-a", "hilo-p")])
+EXACT_MODES = ("first", "fwd", "bwd", "bwd0")
+
+
+_EXACT_SECONDS = [0.0]                                        # the time the exact cases of this file have added, for the parity log
+
+
+def _seed(c):
+    return 23 + sum(c.P) + c.M + len(c.sp) + c.s
+
+
+@functools.lru_cache(maxsize=4)
+def _exact_operands(cid, recipe, no_bank_lo, first):
+    c = BY_ID[cid]
+    return R.exact_stage_inputs(recipe, "split4" if no_bank_lo else "split3", N, c.C, c.M, c.P, c.sp, c.s, _seed(c), first, c.bayer)
+
+
+def exact_data(cid, prec, recipe, mode):
+    """The operands of an exact case; they depend on the arithmetic only through split4's rule (no lo part in the banks) and
+    on the mode only through the pass-through bank of a first stage."""
+    return _exact_operands(cid, recipe, prec == "split4" and recipe != "int", mode == "first" and recipe == "hilo-p")
+
+
+@functools.lru_cache(maxsize=8)
+def exact_model(cid, prec, recipe, mode):
+    """{output: (value, S_e, quantum)}: once per (cell, arithmetic, recipe, mode), shared by the tile and the grouped strip
+    kernel when they follow each other."""
+    c = BY_ID[cid]
+    return R.exact_stage_model(mode, exact_data(cid, prec, recipe, mode), prec, c.s, c.masked)
+
+
+def exact_inputs_of_this_file():
+    """(cell id, arithmetic, recipe, mode) of every exact input a test below feeds a kernel."""
+    return sorted({(cid, prec, recipe, mode) for (_, cid, prec, recipe) in EXACT_CASES for mode in EXACT_MODES})
+
+
+@pytest.mark.parametrize("kind,cid,prec,recipe", EXACT_CASES)
+def test_exact_inputs_hold_the_stage_to_equality(kind, cid, prec, recipe, hip_env):
+    """FIRST, FWD, BWD with and without base on exactly-summable operands: z' / du, the written map (that of the output), the
+    assembled r_next / q with mask, sub or the Bayer mosaic, and fusedg_dtau_reduce equal the model in value at every element
+    where the recipe holds them (EXACT_HELD); what it does not hold stays inside the bound of the model fed the device's own
+    z' / du."""
+    import time
+    import cdlnet_video_amd as cva
+    o = cva.ops
+    t0 = time.perf_counter()
+    if kind == "stripg":
+        hip_env("CDL_FUSEDG_STRIP", "1")
+    cell = BY_ID[cid]
+    g = _geom(o, cell)
+    assert o.fusedg_supported(g)
+    held = R.EXACT_HELD[recipe]
+    rsc = (kind, cid) in RSC_CASES
+    counts, quanta, tpls = {}, {}, []
+    for mode in EXACT_MODES:
+        e = exact_data(cid, prec, recipe, mode)
+        dv = {k: v.cuda() for k, v in e.items() if torch.is_tensor(v)}
+        dv["bits"] = o.fusedg_support_map(g, dv["gate"])
+        frags = o.fusedg_prep(g, dv["wA"], dv["wB"])
+        mask = e["mask"] if cell.masked else None
+        on, neg = e["gate"] != 0, e["gate"] < 0
+        model = exact_model(cid, prec, recipe, mode)
+        fwd = mode in ("first", "fwd")
+        if fwd:
+            res, bits, tpl = _forward(o, g, kind, cell, dv, frags, mode, prec, True, ("rsc", "nchw") if rsc and mode == "fwd" else ("nchw", "nchw"))
+            # the written map is that of the output, which equals the model (the sign bit of a zero is not the model's to say)
+            counts[f"{mode}.map"] = int((bits != o.fusedg_support_map(g, res["code"])).sum())
+        else:
+            res, tpl = _reverse(o, g, kind, cell, dv, frags, mode == "bwd", True, prec, ("nchw", "rsc") if rsc and mode == "bwd" else ("nchw", "nchw"))
+            counts[f"{mode}.off"] = R.zeros_off_support(res["code"].cpu(), on)
+        tpls.append(tpl)
+        code = res["code"].cpu()
+        for name in ("code", "thin", "dt"):
+            if name in model and name in held:
+                val, S, q = model[name]
+                counts[f"{mode}.{name}"], _ = R.violations_exact(res[name].cpu(), val, q)
+                quanta[f"{mode}.{name}"] = R.cap_quanta(S, q)
+                assert quanta[f"{mode}.{name}"] < R.CAP_QUANTA, (cid, mode, name)
+        if "thin" not in held:                                # the synthesis half of the analysis recipe: the bound, as today
+            counts[f"{mode}.thin<=b"], _ = R.violations_fp32(res["thin"].cpu(), *R.synth_assemble(
+                code, e["wB"], prec, False, mask, e["sub"] if fwd else None, 1.0 if fwd else -1.0, s=cell.s))
+            if not fwd:
+                counts[f"{mode}.dt<=b"], _ = R.violations_fp32(res["dt"].cpu(), *R.dtau_sums(code, on, neg, e["c"]))
+    log(f"gcell exact {recipe} {kind} {cid} {prec}{' rsc' if rsc else ''}".ljust(56) + f" {tpls[0]} modes {[t['MODE'] for t in tpls]} "
+        f"violations={sum(counts.values())} { {k: v for k, v in counts.items() if v} } largest S_e in quanta "
+        f"{max(quanta.values()):.0f} cap={R.CAP_QUANTA:.0f} {time.perf_counter() - t0:.2f} s")
+    _EXACT_SECONDS[0] += time.perf_counter() - t0
+    log(f"gcell exact: the exact cases of this file so far {_EXACT_SECONDS[0]:.1f} s")
+    assert not any(counts.values()), counts
